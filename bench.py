@@ -19,6 +19,13 @@ Table and output buffer (gather; source buffer for scatter / SGD gradient apply)
 timed region as in the reference bench. (`--table-candidates T --out-candidates O` is round 2's side experiment: T x O candidate
 pairs probed, the fastest kept, every probe in the line as `placement.probe_ms`. Round 3 launches the row kernels in order —
 DESIGN.md section 3.1 — which removed the dependence on the buffers' physical placement, and the default is 1 x 1.)
+A plain run (no --full) does only what the headline figure needs: set up, warm up, time --steps steps, write the outputs
+(--dump-outputs) and print the line. Everything else it can measure or check — the closed-form check of the output, the
+table placement probe, the `stability` leg, the sequential-copy ceiling, the N > 1 Zipf and local-kernel legs, the CPU
+baseline and the HOST-table (C1) legs, C5's check and its re-timing on the other graph — runs with --full only.
+--dump-outputs DIR: after the timed steps, what the last step computed is written as DIR/<name>.npy (float32 / float64, at
+most 48 MB in all): the gathered rows (gather, sample_gather), or the table rows the step wrote (scatter, grad_apply), as a
+fixed, seeded sample of rows when the whole array is larger; ranks > 0 add `_rank<r>` to the names.
 """
 import os as _os
 _os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")   # dmabuf IPC (RCCL, hipIpc across ranks): must be set before the HIP runtime loads
@@ -26,6 +33,7 @@ import argparse
 import gc
 import json
 import os
+import random
 import socket
 import subprocess
 import sys
@@ -48,8 +56,13 @@ def parse():
     p.add_argument("--gpus", type=int, default=1)
     p.add_argument("--steps", type=int, default=200)
     p.add_argument("--warmup", type=int, default=5)
+    p.add_argument("--full", action="store_true",
+                   help="also run the checks and side measurements (stability, copy ceiling, CPU baseline, C1, Zipf, probes); "
+                        "a plain run only times the steps")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="write what the last timed step computed to DIR/<name>.npy (a fixed, seeded sample of large outputs)")
     p.add_argument("--stability-steps", type=int, default=200,
-                   help="per-step HIP-event timing leg after the timed region (0 = skip)")
+                   help="--full: per-step HIP-event timing leg after the timed region (0 = skip)")
     p.add_argument("--rows", type=int, default=0, help="table rows per GPU (default: 100M at N=1, 125M at N>1)")
     p.add_argument("--dim", type=int, default=128)
     p.add_argument("--indices", type=int, default=10_000_000)
@@ -123,6 +136,22 @@ def fill_table(local, row_start):
         r = torch.arange(row_start + s, row_start + e, device="cuda", dtype=torch.int64) & 0xFFFFFF
         local[s:e] = r.to(torch.float32).unsqueeze(1).to(local.dtype).to(local.device)
     torch.cuda.synchronize()
+
+
+DUMP_BYTES = 48 << 20     # all files of all ranks together
+
+
+def dump_rows(a, world, rank, n, arrays):
+    """--dump-outputs: arrays = {name: (width, take)}, n rows each, take(positions) returning the rows at a device tensor of
+    row positions; written as DIR/<name>[_rank<r>].npy in float32 (float64 for integer arrays). More rows than fit this rank's
+    share of DUMP_BYTES: the same fixed, seeded sample of rows from every array, in order of position."""
+    cap = max(1, DUMP_BYTES // world // (8 * sum(w for w, _ in arrays.values())))   # (8 bytes per value at most)
+    pos = np.arange(n) if n <= cap else np.sort(np.random.default_rng(2024 + rank).choice(n, cap, replace=False))
+    os.makedirs(a.dump_outputs, exist_ok=True)
+    for name, (_, take) in arrays.items():
+        got = take(torch.from_numpy(pos).cuda()).cpu()
+        got = got.to(torch.float32 if got.is_floating_point() else torch.float64).numpy()
+        np.save(os.path.join(a.dump_outputs, name + ("_rank%d" % rank if rank else "") + ".npy"), got)
 
 
 def usable_cores():
@@ -291,6 +320,7 @@ def run_sample_gather(a, wgth, comm, world, rank, launched, barrier):
     mt = a.memory_type or ("chunked" if world == 1 else "distributed")
     nodes, avg = a.nodes, a.avg_degree
     fanouts = [int(x) for x in a.fanouts.split(",")]
+    random.seed(7 + rank)    # the sampler's per-hop seeds come from Python's RNG: the same ones from run to run
     gen = torch.Generator(device="cuda").manual_seed(1)             # the same degrees on every rank
     row = torch.zeros(nodes + 1, dtype=torch.int64, device="cuda")
     torch.cumsum(torch.randint(0, 2 * avg + 1, (nodes,), device="cuda", generator=gen), 0, out=row[1:])
@@ -345,7 +375,7 @@ def run_sample_gather(a, wgth, comm, world, rank, launched, barrier):
     for _ in range(max(a.warmup, 2)):
         x, ids = step()
     barrier()
-    if not a.no_check:
+    if a.full and not a.no_check:
         assert torch.equal(x[:, 0], (ids.long() & 0xFFFFFF).to(torch.float32)), "gathered features differ from the closed form"
     # nothing of the warm-up stays referenced: a live output (15 GB at 65536 seeds) in the middle of the caching allocator's
     # blocks makes the next steps' buffers miss their cached blocks, and fresh hipMallocs land inside the timed region
@@ -366,19 +396,28 @@ def run_sample_gather(a, wgth, comm, world, rank, launched, barrier):
     gc.collect()
     gc.freeze()
     allocs0 = torch.cuda.memory_stats().get("num_device_alloc", 0)
+    last = None
     t0 = time.perf_counter()
-    for _ in range(a.steps):
-        step()
+    for i in range(a.steps):
+        last = step()
+        if i + 1 < a.steps:
+            last = None   # only the last step's outputs outlive it (see above: no live output while a step allocates)
     barrier()
     wall = time.perf_counter() - t0
     gc.unfreeze()
+    if a.dump_outputs:
+        x, ids = last
+        dump_rows(a, world, rank, x.shape[0], {"sample_gather_features": (x.shape[1], lambda p: x[p]),
+                                               "sample_gather_node_ids": (1, lambda p: ids[p])})
+        del x, ids
+    del last
     stat["device_allocs_in_timed_region"] = torch.cuda.memory_stats().get("num_device_alloc", 0) - allocs0
     dt = torch.tensor([wall], device="cuda" if a.backend == "nccl" else "cpu", dtype=torch.float64)
     if launched:
         torch.distributed.all_reduce(dt, op=torch.distributed.ReduceOp.MAX)
     wall = float(dt.item())
     per = []
-    for _ in range(a.stability_steps):
+    for _ in range(a.stability_steps if a.full else 0):
         torch.cuda.synchronize()
         t1 = time.perf_counter()
         step()
@@ -420,7 +459,7 @@ def run_sample_gather(a, wgth, comm, world, rank, launched, barrier):
         res["stability"] = {"steps": len(per), "min_ms": round(float(per.min()), 4), "median_ms": round(float(np.median(per)), 4),
                             "p95_ms": round(float(np.percentile(per, 95)), 4), "max_ms": round(float(per.max()), 4),
                             "note": "per-step host times (synchronised), separate from the timed region"}
-    if not a.one_graph:
+    if a.full and not a.one_graph:
         # the OTHER synthetic graph in the same process (round-5 review: C5 is papers100M, a graph with hubs — the default — and
         # every line before round 6 was measured on the hub-free one): neighbour ids redrawn in place, same degrees and seeds
         other = "uniform" if a.col_dist == "powerlaw" else "powerlaw"
@@ -610,7 +649,7 @@ def main():
     # where the table landed in HBM: the fixed placement probe on this rank's shard, outside the timed
     # region and non-destructive (kind 1 = random 512-byte rows read, kind 2 = read and written back), ms per GiB of rows
     table_probe = None
-    if a.location == "cuda" and policy is None:
+    if a.full and a.location == "cuda" and policy is None:
         try:
             import ctypes
             shard, _ = emb.get_embedding_tensor().get_local_tensor()
@@ -634,6 +673,10 @@ def main():
         if not (sgd_apply and placement is not None):   # (the placement probes gave every candidate its optimizer)
             opt = wgth.create_wholememory_optimizer(emb, a.optimizer, {})
         out.normal_()
+    if a.op == "scatter":
+        # the rows scattered are a function of their target id (not whatever the fresh buffer held): the same table from run to
+        # run, whichever of a duplicate id's rows lands
+        out.copy_(((idx * 7 + 3) % 256).to(torch.float32).unsqueeze(1).expand(-1, a.dim))   # (0 ... 255: exact in fp32, fp16 and bf16)
 
     def step():
         if a.op == "gather":
@@ -658,7 +701,7 @@ def main():
         ok = bool(torch.equal(out[:, 0], exp) and torch.equal(out[:, a.dim - 1], exp) and
                   torch.equal(out[::1009].sum(1), exp[::1009] * a.dim))
         assert ok, "gathered rows differ from the closed-form table"
-    if not a.no_check and out is not None:
+    if a.full and not a.no_check and out is not None:
         check_once()
     for _ in range(max(a.warmup, 1)):
         step()
@@ -688,6 +731,12 @@ def main():
     wall = float(dt.item())
     dev_ms = ev0.elapsed_time(ev1) / a.steps  # HIP events on the stream the kernels were launched on
     rows_kernel = wmb.lib().wholememory_ext_last_rows_kernel().decode()   # what the HIP runtime calls the kernel just run
+    if a.dump_outputs:   # before any side leg writes into `out` or the table again
+        if a.op == "gather":
+            dump_rows(a, world, rank, a.indices, {"gather_out": (a.dim, lambda p: out[p])})
+        else:   # scatter / gradient apply hand nothing back: what they computed is the table rows at the step's ids
+            dump_rows(a, world, rank, a.indices, {a.op + "_table_rows": (a.dim, lambda p: emb.gather(idx[p]))})
+        barrier()
 
     # Side legs, outside the timed region. They must never cost the contract line its measurement: an exception in one of
     # them is recorded in the line (`side_errors`) instead of ending the run — all ranks run the same code on the same shapes,
@@ -784,12 +833,12 @@ def main():
                 "scope": "owner-side row gather on rank 0's local shard, timed outside the step loop; "
                          "the step itself is link-bound (see exchange)"}
 
-    stability = guarded("stability", stability_leg) if a.stability_steps > 0 else None
+    stability = guarded("stability", stability_leg) if a.full and a.stability_steps > 0 else None
     c3_zipf = None
-    if world > 1 and a.op == "gather" and a.dist == "uniform" and mt == "distributed":
+    if a.full and world > 1 and a.op == "gather" and a.dist == "uniform" and mt == "distributed":
         c3_zipf = guarded("c3_zipf", zipf_leg)
     local_kernel_roofline = None
-    if world > 1 and a.op == "gather" and a.dtype == "f32" and rank == 0:
+    if a.full and world > 1 and a.op == "gather" and a.dtype == "f32" and rank == 0:
         local_kernel_roofline = guarded("local_kernel_roofline", local_kernel_leg)
     if launched:
         torch.distributed.barrier()
@@ -866,7 +915,7 @@ def main():
                                                "it); cited as kernel_ms_rocprof only when that run was within 2 % of this one"}
                 except Exception:
                     kernel_ms_rocprof, profile = None, None
-            copy_ms = guarded("copy_leg", copy_leg)
+            copy_ms = guarded("copy_leg", copy_leg) if a.full else None
             res["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s",
                                "frac": round(achieved / 8000.0, 4), "traffic": traffic, "traffic_source": traffic_source,
                                "kernel": rows_kernel, "step_ms_hip_events": round(dev_ms, 4),
@@ -881,7 +930,7 @@ def main():
                 res["roofline"]["vs_copy"] = round(copy_ms / dev_ms, 4)
             if stability is not None:
                 res["roofline"]["frac_at_median_step"] = round(a.indices * algo_bytes / (stability["median_ms"] * 1e-3) / 8e12, 4)
-            if not a.no_cpu_baseline:
+            if a.full and not a.no_cpu_baseline:
                 res["cpu_baseline"] = guarded("cpu_baseline", lambda: cpu_baseline(a.dim, a.cpu_seconds))
                 res["gpu_c1_host"] = guarded("gpu_c1_host", lambda: gpu_c1_host(wgth, comm))
                 res["gpu_c1_host_cached"] = guarded("gpu_c1_host_cached", lambda: gpu_c1_host_cached(wgth, comm))
@@ -890,7 +939,7 @@ def main():
             res["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": 8000.0, "unit": "GB/s",
                                "frac": round(achieved / 8000.0, 4), "traffic": None, "kernel": rows_kernel,
                                "step_ms_hip_events": round(dev_ms, 4), "algorithmic_bytes_per_launch": a.indices * algo_bytes}
-        if world == 1 and a.op == "grad_apply" and a.optimizer == "sgd":
+        if a.full and world == 1 and a.op == "grad_apply" and a.optimizer == "sgd":
             # whole call: ids + gradient rows read once, every DISTINCT table row read and written once (the duplicates' sum and
             # the SGD statement are fused into that one pass); sort and run detection are overhead, not algorithmic bytes
             n_unique = guarded("n_unique", lambda: int(torch.unique(idx).numel()))
@@ -903,7 +952,7 @@ def main():
                                             "fused duplicate-sum / SGD kernel), HIP events around the timed loop",
                                    "call_ms": round(dev_ms, 4), "distinct_rows": n_unique,
                                    "algorithmic_bytes_per_call": call_bytes}
-        if world > 1 and a.op == "gather" and a.dtype == "f32":
+        if a.full and world > 1 and a.op == "gather" and a.dtype == "f32":
             res["roofline"] = local_kernel_roofline
         if world > 1 and a.op == "gather" and mt == "distributed":
             # the step is bound by the point-to-point xGMI links: every rank pulls (W-1)/W of its rows from peers,

@@ -10,11 +10,11 @@ R=$GRAFT_REPO_ROOT
 OUT=$R/gpurun_out/profiles_$TAG
 mkdir -p $OUT
 cd $R
-python bench.py > $OUT/${TAG}_n1_bench.json 2> $OUT/${TAG}_n1_bench.err
+python bench.py --full > $OUT/${TAG}_n1_bench.json 2> $OUT/${TAG}_n1_bench.err
 cut -c1-400 $OUT/${TAG}_n1_bench.json
 stats() {  # stats <name> <bench args...>: bench line + kernel stats of the same command
   local name=$1; shift
-  ( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/prof_$name && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$name -- python $R/bench.py "$@" > $OUT/${TAG}_${name}_under_rocprof.json 2>/dev/null )
+  ( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/prof_$name && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$name -- python $R/bench.py --full "$@" > $OUT/${TAG}_${name}_under_rocprof.json 2>/dev/null )
   cp $(find /tmp/prof_$name -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_${name}_kernel_stats.csv
   head -4 $OUT/${TAG}_${name}_kernel_stats.csv | cut -c1-160
 }
@@ -38,7 +38,7 @@ json.dump({"file": os.environ.get("WM_TAG", "r05") + "_n1_bench_kernel_stats.csv
            "collection_ms_per_step": step_ms,
            "kernel": rows[-1]["Kernel_Name"], "launches": len(tail), "average_ms": round(sum(tail) / len(tail), 4),
            "min_ms": round(min(tail), 4), "max_ms": round(max(tail), 4),
-           "what": "rocprofv3 --kernel-trace of `python bench.py --no-cpu-baseline`: the last launches of the process "
+           "what": "rocprofv3 --kernel-trace of `python bench.py --full --no-cpu-baseline`: the last launches of the process "
                    "(timed region + stability leg)"}, open(os.environ["WM_KERNEL_MS_OUT"], "w"), indent=1)
 print("all %d launches of the process (placement probes included): average %.4f ms" % (len(dur), sum(dur) / len(dur)))
 print("last %d launches (timed region + stability leg, on the picked pair): average %.4f ms, min %.4f, max %.4f" % (
@@ -46,7 +46,7 @@ print("last %d launches (timed region + stability leg, on the picked pair): aver
 PY
 cat $OUT/${TAG}_n1_bench_kernel_trace_tail.txt
 for c in FETCH_SIZE WRITE_SIZE; do
-  ( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/pmc_$c && timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmc_$c -- python $R/bench.py --no-cpu-baseline --steps 10 --warmup 2 --stability-steps 0 > /dev/null 2>&1 )
+  ( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/pmc_$c && timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmc_$c -- python $R/bench.py --full --no-cpu-baseline --steps 10 --warmup 2 --stability-steps 0 > /dev/null 2>&1 )
   cp $(find /tmp/pmc_$c -name "*counter_collection.csv" | head -1) $OUT/${TAG}_bench_${c}_counter_collection.csv
   if [ -x $R/experiments/gather_variants ]; then
     ( cd /tmp && rm -rf /tmp/cal_$c && timeout 300 rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/cal_$c -- $R/experiments/gather_variants 100000000 10000000 3 pmc > /dev/null 2>&1 )
@@ -54,16 +54,16 @@ for c in FETCH_SIZE WRITE_SIZE; do
   fi
 done
 python scripts/collect_traffic.py $OUT $TAG && cat $OUT/pmc_traffic.json | head -30
-python bench.py --op scatter --no-cpu-baseline > $OUT/${TAG}_scatter_bench.json 2>/dev/null
+python bench.py --full --op scatter --no-cpu-baseline > $OUT/${TAG}_scatter_bench.json 2>/dev/null
 stats scatter --op scatter --no-cpu-baseline --steps 50 --stability-steps 0
 for d in uniform zipf; do for o in sgd adam; do
-  python bench.py --op grad_apply --dist $d --optimizer $o --no-cpu-baseline > $OUT/${TAG}_grad_apply_${o}_${d}_bench.json 2>/dev/null
+  python bench.py --full --op grad_apply --dist $d --optimizer $o --no-cpu-baseline > $OUT/${TAG}_grad_apply_${o}_${d}_bench.json 2>/dev/null
   cut -c1-200 $OUT/${TAG}_grad_apply_${o}_${d}_bench.json | head -1
 done; done
 stats grad_apply --op grad_apply --no-cpu-baseline --steps 30 --stability-steps 0
 stats grad_apply_zipf --op grad_apply --dist zipf --no-cpu-baseline --steps 30 --stability-steps 0
 for c in FETCH_SIZE WRITE_SIZE; do
-  ( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/pmcg_$c && timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmcg_$c -- python $R/bench.py --op grad_apply --no-cpu-baseline --steps 5 --warmup 2 --stability-steps 0 > /dev/null 2>&1 )
+  ( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/pmcg_$c && timeout 600 rocprofv3 --pmc $c --kernel-trace --output-format csv -d /tmp/pmcg_$c -- python $R/bench.py --full --op grad_apply --no-cpu-baseline --steps 5 --warmup 2 --stability-steps 0 > /dev/null 2>&1 )
   python - $(find /tmp/pmcg_$c -name "*counter_collection.csv" | head -1) $c >> $OUT/${TAG}_grad_apply_pmc_per_kernel.txt <<'PY'
 import csv, sys, collections
 agg = collections.defaultdict(lambda: [0, 0.0])
@@ -77,7 +77,7 @@ for k, (n, v) in sorted(agg.items(), key=lambda kv: -kv[1][1])[:8]:
 PY
 done
 cat $OUT/${TAG}_grad_apply_pmc_per_kernel.txt | head -24
-python bench.py --op sample_gather --steps 50 --stability-steps 50 > $OUT/${TAG}_sample_gather_bench.json 2>/dev/null
+python bench.py --full --op sample_gather --steps 50 --stability-steps 50 > $OUT/${TAG}_sample_gather_bench.json 2>/dev/null
 stats sample_gather --op sample_gather --steps 50 --stability-steps 0
 if [ -x tools/gather_scatter_bench ]; then
   for f in gather scatter; do

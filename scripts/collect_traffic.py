@@ -41,7 +41,7 @@ def main():
         sha = os.environ.get("WM_COMMIT", "worktree")   # no .git on the GPU box: the caller passes the commit it snapshots
     out = {
         "source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, kernel trace only) around `python bench.py "
-                  "--no-cpu-baseline --steps 10 --warmup 2`, raw CSVs: profiles/%s_pmc/" % tag,
+                  "--full --no-cpu-baseline --steps 10 --warmup 2`, raw CSVs: profiles/%s_pmc/" % tag,
         "collected": "round %s, %s" % (tag, time.strftime("%Y-%m-%d")), "commit": sha,
         "kernel": kname, "launches_averaged": {"FETCH_SIZE": nf, "WRITE_SIZE": nw},
         "units": "counter values are KiB",

@@ -35,8 +35,8 @@ fi
 fail() { echo "first_contact: FAILED at step '$1' (see $OUT/$1.err)"; python3 scripts/first_contact_report.py "$OUT" "$N" "$DRY" "$1"; exit 1; }
 run() {   # run <name> <env assignments or ''> <bench args...>: one bench line -> $OUT/<name>.json
   local name=$1; local envs=$2; shift 2
-  echo "== $name: $envs python bench.py $*"
-  env $envs timeout $TMO python bench.py "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" || fail "$name"
+  echo "== $name: $envs python bench.py --full $*"
+  env $envs timeout $TMO python bench.py --full "$@" > "$OUT/$name.json" 2> "$OUT/$name.err" || fail "$name"
   python3 -c "import json,sys; r=json.loads(open('$OUT/$name.json').read().strip().splitlines()[-1]); print('   ms_per_step', r['ms_per_step'], 'value', r['value'], r['unit'], 'rccl_ranks', r.get('rccl_ranks'))" || fail "$name"
 }
 
@@ -72,7 +72,7 @@ run c5_sample_gather_n$N "" --gpus $N --op sample_gather $C5SIZES
 if [ "$DRY" != "1" ] && command -v rocprofv3 > /dev/null; then
   echo "== rocprofv3 kernel stats, $N ranks, uniform"
   ( cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/fc_prof && timeout $TMO rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/fc_prof -- \
-      python "$ROOT/bench.py" --gpus $N --no-cpu-baseline --steps 10 --stability-steps 0 > "$OUT/c3_uniform_n${N}_under_rocprof.json" 2> /dev/null )
+      python "$ROOT/bench.py" --full --gpus $N --no-cpu-baseline --steps 10 --stability-steps 0 > "$OUT/c3_uniform_n${N}_under_rocprof.json" 2> /dev/null )
   f=$(find /tmp/fc_prof -name "*kernel_stats.csv" 2>/dev/null | head -1)
   [ -n "$f" ] && cp "$f" "$OUT/c3_uniform_n${N}_kernel_stats.csv"
 fi

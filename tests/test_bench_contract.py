@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,7 +24,7 @@ def _one_json_line(stdout):
 
 
 def test_single_gpu_line(wm_lib):
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "4000000", "--indices", "500000",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--rows", "4000000", "--indices", "500000",
                         "--steps", "3", "--warmup", "1", "--cpu-seconds", "0.5"], capture_output=True, timeout=600)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     r = _one_json_line(p.stdout)
@@ -51,11 +52,36 @@ def test_single_gpu_line(wm_lib):
     assert r["transport"] == "none" and r["rccl_ranks"] == 0
 
 
+def test_plain_line_times_only_and_dumps_its_outputs(wm_lib, tmp_path):
+    """Without --full the line carries the headline figures and none of the side legs; --dump-outputs writes a fixed, seeded
+    sample of the last step's gathered rows (float32), the same bytes from one process to the next."""
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "4000000", "--indices", "500000",
+                            "--steps", "4", "--warmup", "1", "--dump-outputs", str(d)], capture_output=True, timeout=600)
+        assert p.returncode == 0, p.stderr.decode()[-3000:]
+        r = _one_json_line(p.stdout)
+        assert all(k in r for k in CONTRACT) and r["steps"] == 4 and r["warmup"] == 1 and r["ms_per_step"] > 0
+        assert r["unit"] == "GB/s" and r["higher_is_better"] is True and r["dtype"] == "f32" and r["value"] > 0
+        for side in ("stability", "cpu_baseline", "gpu_c1_host", "gpu_c1_host_cached", "side_errors"):
+            assert side not in r, side
+        assert r["table_probe"] is None and "copy_ms_sequential_ids" not in r["roofline"]
+        assert sorted(os.listdir(str(d))) == ["gather_out.npy"]
+        dumps.append(np.load(str(d / "gather_out.npy")))
+    got = dumps[0]
+    assert got.dtype == np.float32 and got.ndim == 2 and got.shape[1] == 128 and 1000 < got.shape[0] < 500000
+    assert got.nbytes <= 64 << 20
+    # closed-form table: every gathered row holds one integral row id in all its columns
+    assert np.all(got == got[:, :1]) and np.all(got[:, 0] == np.floor(got[:, 0])) and got.min() >= 0 and got.max() < 4000000
+    assert got.tobytes() == dumps[1].tobytes()
+
+
 def test_self_launch_without_a_launcher(wm_lib):
     """`python bench.py --gpus 2` with no RANK in the environment starts the ranks itself (reference bench:
     gather_scatter_bench.cu:257-284 forks one process per device)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--rows", "1000003",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--backend", "gloo", "--rows", "1000003",
                         "--indices", "300000", "--steps", "3", "--warmup", "1", "--stability-steps", "5"],
                        capture_output=True, timeout=900, env=dict(env, OMP_NUM_THREADS="1"))
     assert p.returncode == 0, p.stderr.decode()[-3000:]
@@ -67,7 +93,7 @@ def test_eight_ranks_exchange_object(wm_lib):
     """The N = 8 plumbing of bench.py before the first SCALE run: 8 ranks (sharing the one GPU, host collectives), toy
     sizes, the line's `exchange` object with the bytes every ordered pair moves per step and the link-bound prediction."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--rows", "250007",
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "8", "--backend", "gloo", "--rows", "250007",
                         "--indices", "80000", "--steps", "2", "--warmup", "1", "--stability-steps", "0"],
                        capture_output=True, timeout=900, env=dict(env, OMP_NUM_THREADS="1"))
     assert p.returncode == 0, p.stderr.decode()[-3000:]
@@ -109,7 +135,7 @@ def test_multi_rank_line_over_host_collectives(wm_lib, world):
     port = s.getsockname()[1]
     s.close()
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr",
-           "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--backend", "gloo",
+           "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", str(world), "--backend", "gloo",
            "--rows", "1000003", "--indices", "300000", "--steps", "3", "--warmup", "1"]
     p = subprocess.run(cmd, capture_output=True, timeout=900, env=dict(os.environ, OMP_NUM_THREADS="1"))
     assert p.returncode == 0, p.stderr.decode()[-3000:]
@@ -125,12 +151,14 @@ def test_multi_rank_line_over_host_collectives(wm_lib, world):
 
 
 @pytest.mark.parametrize("world", [1, 2])
-def test_sample_gather_line(wm_lib, world):
+def test_sample_gather_line(wm_lib, world, tmp_path):
     """BASELINE config 5 as a bench op (small graph): one JSON line with the contract keys and its own roofline object; at
-    world 2 the CSR and the features are DISTRIBUTED over two ranks sharing the GPU (collectives over gloo)."""
+    world 2 the CSR and the features are DISTRIBUTED over two ranks sharing the GPU (collectives over gloo). The last step's
+    features and sub-graph node ids are dumped, every rank its own."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--op", "sample_gather", "--nodes", "2000003", "--avg-degree", "12",
-           "--seeds", "512", "--fanouts", "10,5", "--steps", "3", "--warmup", "2", "--stability-steps", "4"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--op", "sample_gather", "--nodes", "2000003", "--avg-degree", "12",
+           "--seeds", "512", "--fanouts", "10,5", "--steps", "3", "--warmup", "2", "--stability-steps", "4",
+           "--dump-outputs", str(tmp_path)]
     if world > 1:
         cmd += ["--gpus", str(world), "--backend", "gloo"]
     p = subprocess.run(cmd, capture_output=True, timeout=900, env=dict(env, OMP_NUM_THREADS="1"))
@@ -142,6 +170,11 @@ def test_sample_gather_line(wm_lib, world):
     roof = r["roofline"]
     assert roof["bound"] == "hbm" and "latency" in roof["limited_by"] and 0 < roof["frac"] < 1
     assert r["stability"]["steps"] == 4
+    for rank in range(world):
+        sfx = "_rank%d" % rank if rank else ""
+        x, ids = np.load(str(tmp_path / ("sample_gather_features%s.npy" % sfx))), np.load(str(tmp_path / ("sample_gather_node_ids%s.npy" % sfx)))
+        assert x.dtype == np.float32 and ids.dtype == np.float64 and x.shape == (ids.shape[0], 128) and ids.shape[0] > 512
+        assert np.array_equal(x[:, 0], ids) and np.all(x == x[:, :1]) and ids.max() < 2000003     # closed-form features
 
 
 @pytest.mark.parametrize("world", [2, 4])

@@ -3,11 +3,12 @@
 block of it) is cythonized against THIS repo's ``include/`` and linked against ``libwholegraph.so``; the extension then
 imports (so every symbol the binding references resolves) and its host-only entry points behave.
 
-Runs only where the reference tree and Cython exist (the build container). Nothing of the reference is copied into
-the repository: the generated C++ and the extension live under ``build/`` (git-ignored and not shipped to the GPU box).
+The extension is built by ``build()`` (oracle/Makefile, target ``refbind``) where the reference tree and Cython exist, into
+``oracle/_ref/`` like the other reference binaries; the test imports it from there and skips where it was never built.
+Nothing of the reference is copied into the repository: the generated C++ and the extension live under ``oracle/_ref/``
+(git-ignored).
 """
 import os
-import shutil
 import subprocess
 import sys
 import sysconfig
@@ -16,29 +17,21 @@ import textwrap
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PYX = "/root/reference/python/pylibwholegraph/pylibwholegraph/binding/wholememory_binding.pyx"
-OUT = os.path.join(ROOT, "build", "refbind")
-
-pytestmark = pytest.mark.skipif(not os.path.exists(PYX) or shutil.which("cython") is None,
-                                reason="needs the reference tree and cython (build container only)")
+OUT = os.path.join(ROOT, "oracle", "_ref")
+EXT = os.path.join(OUT, "wholememory_binding" + sysconfig.get_config_var("EXT_SUFFIX"))
 
 
 @pytest.fixture(scope="module")
 def reference_binding(wm_lib):
-    os.makedirs(OUT, exist_ok=True)
-    cpp = os.path.join(OUT, "wholememory_binding.cpp")
-    ext = os.path.join(OUT, "wholememory_binding" + sysconfig.get_config_var("EXT_SUFFIX"))
-    subprocess.check_call(["cython", "--cplus", "-3", "-I", os.path.join(ROOT, "include"), PYX, "-o", cpp],
-                          stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    subprocess.check_call(["g++", "-O0", "-std=c++17", "-fPIC", "-shared", "-w", "-I", os.path.join(ROOT, "include"),
-                           "-I", sysconfig.get_paths()["include"], cpp, "-o", ext,
-                           "-L", os.path.join(ROOT, "wholegraph_amd"), "-lwholegraph",
-                           "-Wl,-rpath," + os.path.join(ROOT, "wholegraph_amd")])
-    return ext
+    if not os.path.exists(EXT):
+        pytest.skip("oracle/_ref/wholememory_binding not built (reference tree or cython absent at build time)")
+    return EXT
 
 
 def _run(code, env=None):
-    """in a fresh interpreter: torch first (so the HIP runtime is shared), then the product library, then the binding"""
+    """in a fresh interpreter: torch first (so the HIP runtime is shared), then the product library, then the binding.
+    Host-only checks: the interpreter sees no GPU (HIP_VISIBLE_DEVICES=-1), also where the machine has one."""
+    env = dict({"HIP_VISIBLE_DEVICES": "-1"}, **(env or {}))
     prolog = textwrap.dedent("""
         import sys, ctypes
         sys.path.insert(0, %r); sys.path.insert(0, %r)

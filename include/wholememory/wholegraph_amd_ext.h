@@ -9,6 +9,8 @@
  *  (2) the raw device stages of the distributed path on plain device pointers (id bucketing,
  *      owner-side dedup + optimizer step), so parity tests can check each stage against the oracle
  *      through the C ABI.
+ *      (2b) the neighbour aggregation of a sampled CSC block behind the GraphSAGE layer (forward and a deterministic
+ *      backward).
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -246,6 +248,58 @@ int64_t wholememory_ext_alltoallv_bytes(void);
  * (decided by all ranks from the duplicate estimates in the counts exchange; WM_GRAD_COMBINE=0|1 forces): every rank folds ITS
  * duplicates of an id into one partial sum before the exchange, the owner folds at most world_size partial rows per id. */
 int64_t wholememory_ext_combined_gradient_calls(void);
+
+/* ---- (2b) neighbour aggregation of a sampled CSC block (GraphSAGE `agg_concat`) -------------------------------- */
+/* The block as the sampler and graph_append_unique leave it: row_ptr int32 [n_dst + 1] with row_ptr[n_dst] = n_edges,
+ * col_ind int32 [n_edges] in [0, n_src) (out-of-range ids are the caller's contract), x fp32 [n_src, x_stride] whose first
+ * n_dst rows are the targets themselves. Strides in elements, all arrays DEVICE memory, all work queued on `stream`.
+ *
+ * forward: out [n_dst, out_stride] fp32, out_stride >= 2 * dim.
+ *   out[d, 0:dim]     = A(d). S(d) = fp32 sum of x[col_ind[e]] for e = row_ptr[d] .. row_ptr[d+1] - 1, added left to right
+ *                       from the first term. SUM: A = S. MEAN: A = S * fl(1.0f / deg(d)) (one multiply). No edge: +0.0.
+ *   out[d, dim:2dim]  = x[d].
+ * backward: grad_out [n_dst, grad_out_stride] (2 * dim columns used) -> grad_x [n_src, grad_x_stride], every row written.
+ *   t(e) = grad_out[dst(e), 0:dim] (times fl(1.0f / deg(dst(e))) for MEAN). P(s) sums t(e) over the edges with
+ *   col_ind[e] = s in ascending edge position: left to right from the first term when s has at most C edges; otherwise the
+ *   edges are cut into consecutive chunks of C, each chunk summed left to right and the chunk sums added in chunk order,
+ *   ((p0 + p1) + p2) + ... . grad_x[s] = P(s) + grad_out[s, dim:2dim] (the self term added last, only for s < n_dst); with one
+ *   part missing the other is copied, with neither the row is +0.0. C = wholememory_ext_csc_aggregate_chunk_edges(). The
+ *   order is fixed: results are bitwise reproducible, no atomics. The edge index is built with the library's id sort, scratch
+ *   from p_env_fns.
+ * n_edges = 0 and n_dst = 0 are valid. INVALID_INPUT for null pointers, negative sizes, dim < 1, n_dst > n_src, strides
+ * smaller than the row, an unknown aggr; NOT_SUPPORTED (nothing queued) when the device backend has no such kernels. */
+enum wholememory_ext_aggr_t {
+  WHOLEMEMORY_EXT_AGGR_SUM  = 0,
+  WHOLEMEMORY_EXT_AGGR_MEAN = 1,
+};
+enum wholememory_error_code_t wholememory_ext_csc_aggregate_forward(const int32_t* row_ptr,
+                                                                    const int32_t* col_ind,
+                                                                    int64_t n_edges,
+                                                                    int64_t n_dst,
+                                                                    int64_t n_src,
+                                                                    const float* x,
+                                                                    int64_t x_stride,
+                                                                    int64_t dim,
+                                                                    int aggr,
+                                                                    float* out,
+                                                                    int64_t out_stride,
+                                                                    struct wholememory_env_func_t* p_env_fns,
+                                                                    void* stream);
+enum wholememory_error_code_t wholememory_ext_csc_aggregate_backward(const int32_t* row_ptr,
+                                                                     const int32_t* col_ind,
+                                                                     int64_t n_edges,
+                                                                     int64_t n_dst,
+                                                                     int64_t n_src,
+                                                                     const float* grad_out,
+                                                                     int64_t grad_out_stride,
+                                                                     int64_t dim,
+                                                                     int aggr,
+                                                                     float* grad_x,
+                                                                     int64_t grad_x_stride,
+                                                                     struct wholememory_env_func_t* p_env_fns,
+                                                                     void* stream);
+/* C of the backward's chunked sums (a compile-time constant of the library) */
+int64_t wholememory_ext_csc_aggregate_chunk_edges(void);
 
 /* ---- (3) testing seam ---------------------------------------------------------------------- */
 /* Replaces the device backend. Refuses (WHOLEMEMORY_NOT_SUPPORTED) unless the environment has

@@ -28,6 +28,7 @@ MT_NONE, MT_CONTINUOUS, MT_CHUNKED, MT_DISTRIBUTED, MT_HIERARCHY = range(5)
 ML_NONE, ML_DEVICE, ML_HOST = range(3)
 (DT_UNKNOWN, DT_FLOAT, DT_HALF, DT_DOUBLE, DT_BF16, DT_INT, DT_INT64, DT_INT16, DT_INT8, DT_COUNT) = range(10)
 MA_NONE, MA_DEVICE, MA_HOST, MA_PINNED = range(4)
+AGGR_SUM, AGGR_MEAN = range(2)
 OPT_NONE, OPT_SGD, OPT_LAZY_ADAM, OPT_RMSPROP, OPT_ADAGRAD = range(5)
 AT_NONE, AT_READONLY, AT_READWRITE = range(3)
 LEVEL_FATAL, LEVEL_ERROR, LEVEL_WARN, LEVEL_INFO, LEVEL_DEBUG, LEVEL_TRACE = range(6)
@@ -273,6 +274,11 @@ PROTOTYPES = {
     "wholememory_ext_get_malloc_probe": (_i, [C.c_char_p, C.c_size_t]),
     "wholememory_ext_handle_was_probed": (_i, [_vp]),
     "wholememory_ext_multilayer_sample": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wholememory_ext_csc_aggregate_forward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i, _vp, _i64, _P(EnvFunc),
+                                                  _vp]),
+    "wholememory_ext_csc_aggregate_backward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i, _vp, _i64, _P(EnvFunc),
+                                                   _vp]),
+    "wholememory_ext_csc_aggregate_chunk_edges": (_i64, []),
     "wm_testing_install_backend": (_i, [_vp]),
 }
 

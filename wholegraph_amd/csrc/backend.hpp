@@ -175,6 +175,20 @@ struct wm_cache_args {
   int64_t raw2_row_stride_bytes;
 };
 
+// neighbour aggregation of a sampled CSC block (kernels/agg.hip): rows / strides / dim in ELEMENTS (fp32)
+struct wm_agg_args {
+  const int32_t* row_ptr;   // [n_dst + 1]
+  const int32_t* col_ind;   // [n_edges], ids in [0, n_src)
+  int64_t n_edges, n_dst, n_src, dim;
+  int mean;                 // 1: "mean" (sum times fl(1 / degree)), 0: "sum"
+  const float* in;          // forward: x [n_src, in_stride]
+  int64_t in_stride;
+  const float* grad;        // backward: dL/dout [n_dst, grad_stride], 2 * dim columns used
+  int64_t grad_stride;
+  float* out;               // forward: out [n_dst, out_stride] (2 * dim columns); backward: grad_x [n_src, out_stride]
+  int64_t out_stride;
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -357,11 +371,23 @@ struct wm_device_backend {
   // the float16 range (a single gradient cannot). Leaves the flag alone otherwise. nullptr in a backend without 16-bit tables.
   int (*partials_nonfinite)(const int32_t* run_starts, const int64_t* n_unique_dev, int64_t n_upper, const void* rows,
                             int64_t dim, int64_t stride, int64_t* flag_dev, void* stream);
+  // ---- neighbour aggregation of a sampled CSC block (kernels/agg.hip); nullptr in a backend that does not provide it ----
+  // out[d] = (sum or mean of x[col_ind[e]] over the edges of d, x[d]) — the order of every sum: wholegraph_amd_ext.h
+  int (*agg_forward)(const wm_agg_args* a, void* stream);
+  // grad_x from dL/dout. order / run_starts / unique_ids / n_unique_dev: dedup_ids over col_ind (int32, key_upper_bound =
+  // n_src); workspace of agg_backward_workspace_bytes(n_edges, n_src, dim). Edges whose run is longer than kAggChunkEdges are
+  // summed in chunks of that many edges, the chunk sums added in chunk order.
+  size_t (*agg_backward_workspace_bytes)(int64_t n_edges, int64_t n_src, int64_t dim);
+  int (*agg_backward)(const wm_agg_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                      const int64_t* n_unique_dev, void* workspace, void* stream);
 };
 
 }  // extern "C"
 
 namespace wm {
+// edges per chunk of the aggregation backward's sums (backend.hpp: agg_backward; wholememory_ext_csc_aggregate_chunk_edges)
+constexpr int64_t kAggChunkEdges = 512;
+
 // Host copies of a chunked handle's per-rank tables, keyed by the DEVICE pointer array its gref carries (gref.pointer).
 // memory_handle.cpp registers them when it uploads the device arrays; the row kernels of a table of up to
 // kOwnersByValue ranks then get bases and bounds as kernel arguments instead of loading them per row. A gref somebody

@@ -1,0 +1,383 @@
+// wholegraph_amd — neighbour aggregation of a sampled CSC block (the GraphSAGE `agg_concat` op) on gfx950.
+//
+// Forward (one group of LANES lanes per target row d, LANES = 16 / 32 / 64 from the row width):
+//   out[d, 0:F]  = A(d): the fp32 sum of x[col_ind[e]] over e in [row_ptr[d], row_ptr[d+1]), left to right from the first
+//                  term, times r(d) = fl(1 / deg(d)) for "mean"; +0.0 for a target without neighbours
+//   out[d, F:2F] = x[d]
+// The group loads the column ids of up to LANES edges with one coalesced load and hands them out with shuffles; the
+// neighbour rows of a batch of kAggBatch edges are then loaded back to back (16-byte pieces when the rows allow it).
+//
+// Backward (grad_x[s] for every source row s; no atomics, one fixed order of every sum):
+//   1 the existing id sort (dedup_ids, called by the host) sorts col_ind: runs of equal sources, positions ascending
+//   2 agg_bwd_prep_kernel: sorted_dst[j] = target of edge order[j] (a search in row_ptr), run_of[unique[u]] = u
+//   3 agg_bwd_chunk_kernel: a run of more than kAggChunkEdges edges is cut into chunks of that many edges from its start;
+//     chunk k >= 1 is summed by a group of its own into a partial row. Tile t = [t*C, (t+1)*C) of the sorted positions
+//     holds at most one such chunk start (only the run that covers position t*C can have one there), so the chunk's slot
+//     is its tile.
+//   4 agg_bwd_fold_kernel: one group per source row: chunk 0 of its run, then the partials of chunks 1, 2, ... in chunk
+//     order, then the self term G[s, F:2F] for s < n_dst; rows without edges get the self term or +0.0.
+// run_of[] is not initialised: a value is used only when 0 <= u < n_unique and unique[u] == s (a sparse-set check).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../backend.hpp"
+
+namespace wm {
+namespace {
+
+constexpr int kAggBlock = 256;
+constexpr int kAggBatch = 8;   // neighbour rows in flight per lane
+constexpr int64_t kAggMaxBlocks = 1 << 20;
+
+// backward scratch: the id sort's outputs and this op's workspace (hip_agg_backward carves it)
+struct wm_agg_bwd_state {
+  const int32_t* order;        // [n_edges] edge positions, sorted by source (stable)
+  const int32_t* run_starts;   // [n_unique + 1]
+  const int32_t* unique_ids;   // [n_unique] sources with edges, ascending
+  const int64_t* n_unique;     // device scalar written by the sort
+  int32_t* sorted_dst;         // [n_edges]
+  int32_t* run_of;             // [n_src]
+  float* partial;              // [n_tiles, partial_stride]
+  int64_t n_tiles, partial_stride;
+};
+
+template <int VEC>
+struct fvec {
+  float v[VEC];
+};
+
+template <int VEC>
+__device__ __forceinline__ fvec<VEC> ldv(const float* p)
+{
+  fvec<VEC> r;
+  if constexpr (VEC == 4) {
+    const float4 t = *reinterpret_cast<const float4*>(p);
+    r.v[0] = t.x, r.v[1] = t.y, r.v[2] = t.z, r.v[3] = t.w;
+  } else {
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) r.v[i] = p[i];
+  }
+  return r;
+}
+
+template <int VEC>
+__device__ __forceinline__ void stv(float* p, const fvec<VEC>& a)
+{
+  if constexpr (VEC == 4) {
+    *reinterpret_cast<float4*>(p) = make_float4(a.v[0], a.v[1], a.v[2], a.v[3]);
+  } else {
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) p[i] = a.v[i];
+  }
+}
+
+template <int VEC>
+__device__ __forceinline__ fvec<VEC> splat(float s)
+{
+  fvec<VEC> r;
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) r.v[i] = s;
+  return r;
+}
+
+template <int VEC>
+__device__ __forceinline__ void add_to(fvec<VEC>& acc, const fvec<VEC>& b)
+{
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) acc.v[i] = acc.v[i] + b.v[i];
+}
+
+template <int VEC>
+__device__ __forceinline__ fvec<VEC> scaled(const fvec<VEC>& a, float s)
+{
+  fvec<VEC> r;
+#pragma unroll
+  for (int i = 0; i < VEC; ++i) r.v[i] = a.v[i] * s;
+  return r;
+}
+
+// edges of target d, clamped to [0, n_edges) so that an inconsistent row_ptr cannot send a load out of col_ind
+__device__ __forceinline__ void edge_range(const int32_t* row_ptr, int64_t d, int64_t n_edges, int64_t& e0, int64_t& e1)
+{
+  int64_t a = row_ptr[d], b = row_ptr[d + 1];
+  a  = a < 0 ? 0 : (a > n_edges ? n_edges : a);
+  b  = b < a ? a : (b > n_edges ? n_edges : b);
+  e0 = a, e1 = b;
+}
+
+// -0.0 is the identity of IEEE addition: acc = -0.0 followed by acc + t_0 + t_1 + ... is the left-to-right sum that starts
+// from the first term (also when that term is -0.0)
+
+template <int VEC, int LANES>
+__global__ __launch_bounds__(kAggBlock) void agg_forward_kernel(wm_agg_args p)
+{
+  constexpr int kGroups = kAggBlock / LANES;
+  const int gl          = threadIdx.x % LANES;
+  const int64_t F       = p.dim;
+  for (int64_t d = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; d < p.n_dst;
+       d += static_cast<int64_t>(gridDim.x) * kGroups) {
+    int64_t e0, e1;
+    edge_range(p.row_ptr, d, p.n_edges, e0, e1);
+    const int64_t deg = e1 - e0;
+    const float r     = deg > 0 ? 1.0f / static_cast<float>(deg) : 0.0f;
+    const float* self = p.in + d * p.in_stride;
+    float* orow       = p.out + d * p.out_stride;
+    for (int64_t cb = 0; cb < F; cb += LANES * VEC) {   // (group-uniform trip count: the shuffles below stay in step)
+      const int64_t c  = cb + gl * VEC;
+      const bool act   = c < F;
+      const int64_t cl = act ? c : 0;
+      fvec<VEC> acc    = splat<VEC>(-0.0f);
+      for (int64_t eb = e0; eb < e1; eb += LANES) {
+        const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
+        const int my = gl < nb ? p.col_ind[eb + gl] : 0;
+        for (int j = 0; j < nb; j += kAggBatch) {
+          fvec<VEC> v[kAggBatch];
+#pragma unroll
+          for (int k = 0; k < kAggBatch; ++k) {
+            const int src = __shfl(my, j + k < nb ? j + k : nb - 1, LANES);
+            v[k]          = ldv<VEC>(p.in + static_cast<int64_t>(src) * p.in_stride + cl);
+          }
+#pragma unroll
+          for (int k = 0; k < kAggBatch; ++k)
+            if (j + k < nb) add_to(acc, v[k]);
+        }
+      }
+      if (act) {
+        const fvec<VEC> a = deg == 0 ? splat<VEC>(0.0f) : (p.mean ? scaled(acc, r) : acc);
+        stv(orow + c, a);
+        stv(orow + F + c, ldv<VEC>(self + c));
+      }
+    }
+  }
+}
+
+// acc += t(e) for the edges at sorted positions [eb0, ee), in that order (LANES lanes, this lane's columns at cl)
+template <int VEC, int LANES>
+__device__ __forceinline__ void fold_edges(fvec<VEC>& acc, const wm_agg_args& p, const int32_t* sorted_dst, int64_t eb0,
+                                           int64_t ee, int64_t cl, int gl)
+{
+  for (int64_t eb = eb0; eb < ee; eb += LANES) {
+    const int nb = static_cast<int>(ee - eb < LANES ? ee - eb : LANES);
+    int my_d     = 0;
+    float my_r   = 1.0f;
+    if (gl < nb) {
+      my_d = sorted_dst[eb + gl];
+      if (p.mean) my_r = 1.0f / static_cast<float>(p.row_ptr[my_d + 1] - p.row_ptr[my_d]);
+    }
+    for (int j = 0; j < nb; j += kAggBatch) {
+      fvec<VEC> v[kAggBatch];
+      float rs[kAggBatch];
+#pragma unroll
+      for (int k = 0; k < kAggBatch; ++k) {
+        const int from = j + k < nb ? j + k : nb - 1;
+        const int d    = __shfl(my_d, from, LANES);
+        rs[k]          = __shfl(my_r, from, LANES);
+        v[k]           = ldv<VEC>(p.grad + static_cast<int64_t>(d) * p.grad_stride + cl);
+      }
+#pragma unroll
+      for (int k = 0; k < kAggBatch; ++k)
+        if (j + k < nb) add_to(acc, p.mean ? scaled(v[k], rs[k]) : v[k]);
+    }
+  }
+}
+
+// sorted_dst[j] = the target whose edge range holds position order[j]; run_of[unique[u]] = u
+__global__ __launch_bounds__(kAggBlock) void agg_bwd_prep_kernel(wm_agg_args p, wm_agg_bwd_state b)
+{
+  const int64_t nu = *b.n_unique;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < p.n_edges;
+       i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const int64_t pos = b.order[i];
+    int64_t lo = 0, hi = p.n_dst;   // the last d in [0, n_dst) with row_ptr[d] <= pos
+    while (hi - lo > 1) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (p.row_ptr[mid] <= pos) lo = mid;
+      else hi = mid;
+    }
+    b.sorted_dst[i] = static_cast<int32_t>(lo);
+    if (i < nu) b.run_of[b.unique_ids[i]] = static_cast<int32_t>(i);
+  }
+}
+
+template <int VEC, int LANES>
+__global__ __launch_bounds__(kAggBlock) void agg_bwd_chunk_kernel(wm_agg_args p, wm_agg_bwd_state b)
+{
+  constexpr int kGroups = kAggBlock / LANES;
+  constexpr int64_t C   = kAggChunkEdges;
+  const int gl          = threadIdx.x % LANES;
+  const int64_t F       = p.dim;
+  const int64_t nu      = *b.n_unique;
+  if (nu == 0) return;
+  const int64_t covered = b.run_starts[nu];   // sorted positions that belong to runs (ids out of range sort behind them)
+  for (int64_t t = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; t < b.n_tiles;
+       t += static_cast<int64_t>(gridDim.x) * kGroups) {
+    const int64_t pos0 = t * C;
+    if (pos0 >= covered) continue;
+    int64_t lo = 0, hi = nu;   // the run that covers pos0: last u with run_starts[u] <= pos0
+    while (hi - lo > 1) {
+      const int64_t mid = (lo + hi) >> 1;
+      if (b.run_starts[mid] <= pos0) lo = mid;
+      else hi = mid;
+    }
+    const int64_t s0 = b.run_starts[lo], s1 = b.run_starts[lo + 1];
+    const int64_t k  = (pos0 - s0 + C - 1) / C;
+    const int64_t cs = s0 + k * C;
+    if (k < 1 || cs >= s1 || cs >= pos0 + C) continue;   // no chunk k >= 1 starts in this tile
+    const int64_t ce = cs + C < s1 ? cs + C : s1;
+    for (int64_t cb = 0; cb < F; cb += LANES * VEC) {
+      const int64_t c  = cb + gl * VEC;
+      const bool act   = c < F;
+      const int64_t cl = act ? c : 0;
+      fvec<VEC> acc    = splat<VEC>(-0.0f);
+      fold_edges<VEC, LANES>(acc, p, b.sorted_dst, cs, ce, cl, gl);
+      if (act) stv(b.partial + t * b.partial_stride + c, acc);
+    }
+  }
+}
+
+template <int VEC, int LANES>
+__global__ __launch_bounds__(kAggBlock) void agg_bwd_fold_kernel(wm_agg_args p, wm_agg_bwd_state b)
+{
+  constexpr int kGroups = kAggBlock / LANES;
+  constexpr int64_t C   = kAggChunkEdges;
+  const int gl          = threadIdx.x % LANES;
+  const int64_t F       = p.dim;
+  const int64_t nu      = *b.n_unique;
+  for (int64_t s = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; s < p.n_src;
+       s += static_cast<int64_t>(gridDim.x) * kGroups) {
+    const int64_t u = b.run_of[s];   // (uninitialised unless s has edges: checked against unique_ids)
+    const bool has  = u >= 0 && u < nu && b.unique_ids[u] == s;
+    int64_t s0 = 0, s1 = 0;
+    if (has) s0 = b.run_starts[u], s1 = b.run_starts[u + 1];
+    const int64_t c0e     = s1 - s0 > C ? s0 + C : s1;
+    const int64_t nchunks = (s1 - s0 + C - 1) / C;
+    const bool self       = s < p.n_dst;
+    for (int64_t cb = 0; cb < F; cb += LANES * VEC) {
+      const int64_t c  = cb + gl * VEC;
+      const bool act   = c < F;
+      const int64_t cl = act ? c : 0;
+      fvec<VEC> acc    = splat<VEC>(-0.0f);
+      fold_edges<VEC, LANES>(acc, p, b.sorted_dst, s0, c0e, cl, gl);
+      for (int64_t k0 = 1; k0 < nchunks; k0 += kAggBatch) {   // partials in chunk order, a batch of them in flight
+        fvec<VEC> v[kAggBatch];
+#pragma unroll
+        for (int k = 0; k < kAggBatch; ++k) {
+          const int64_t kk = k0 + k < nchunks ? k0 + k : nchunks - 1;
+          v[k]             = ldv<VEC>(b.partial + ((s0 + kk * C) / C) * b.partial_stride + cl);
+        }
+#pragma unroll
+        for (int k = 0; k < kAggBatch; ++k)
+          if (k0 + k < nchunks) add_to(acc, v[k]);
+      }
+      fvec<VEC> res;
+      if (self) {
+        const fvec<VEC> g = ldv<VEC>(p.grad + s * p.grad_stride + F + cl);
+        res               = g;
+        if (has) {
+          res = acc;
+          add_to(res, g);
+        }
+      } else {
+        res = has ? acc : splat<VEC>(0.0f);
+      }
+      if (act) stv(p.out + s * p.out_stride + c, res);
+    }
+  }
+}
+
+int rc_last() { return hipGetLastError() == hipSuccess ? 0 : -2; }
+
+int blocks_for(int64_t groups, int groups_per_block)
+{
+  int64_t n = (groups + groups_per_block - 1) / groups_per_block;
+  if (n < 1) n = 1;
+  return static_cast<int>(n < kAggMaxBlocks ? n : kAggMaxBlocks);
+}
+
+// 16-byte pieces when every row start is 16-byte aligned; group width from the number of pieces (or floats) of a row
+bool use_vec4(int64_t dim, const void* a, int64_t a_stride, const void* b, int64_t b_stride)
+{
+  return dim % 4 == 0 && a_stride % 4 == 0 && b_stride % 4 == 0 && reinterpret_cast<uintptr_t>(a) % 16 == 0 &&
+         reinterpret_cast<uintptr_t>(b) % 16 == 0;
+}
+int lanes_for(int64_t pieces) { return pieces <= 16 ? 16 : (pieces <= 32 ? 32 : 64); }
+
+#define WM_AGG_DISPATCH(VEC_, PIECES_, LAUNCH_)                          \
+  do {                                                                   \
+    const int lanes__ = lanes_for(PIECES_);                              \
+    if (VEC_) {                                                          \
+      if (lanes__ == 16) LAUNCH_(4, 16);                                 \
+      else if (lanes__ == 32) LAUNCH_(4, 32);                            \
+      else LAUNCH_(4, 64);                                               \
+    } else {                                                             \
+      if (lanes__ == 16) LAUNCH_(1, 16);                                 \
+      else if (lanes__ == 32) LAUNCH_(1, 32);                            \
+      else LAUNCH_(1, 64);                                               \
+    }                                                                    \
+  } while (0)
+
+}  // namespace
+
+int hip_agg_forward(const wm_agg_args* a, void* stream_v)
+{
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  if (a->n_dst == 0 || a->dim == 0) return 0;
+  const bool v4 = use_vec4(a->dim, a->in, a->in_stride, a->out, a->out_stride);
+#define WM_AGG_FWD(V, L)                                                                                                  \
+  hipLaunchKernelGGL((agg_forward_kernel<V, L>), dim3(blocks_for(a->n_dst, kAggBlock / (L))), dim3(kAggBlock), 0, stream, \
+                     *a)
+  WM_AGG_DISPATCH(v4, v4 ? a->dim / 4 : a->dim, WM_AGG_FWD);
+#undef WM_AGG_FWD
+  return rc_last();
+}
+
+size_t hip_agg_backward_workspace_bytes(int64_t n_edges, int64_t n_src, int64_t dim)
+{
+  const int64_t tiles = (n_edges + kAggChunkEdges - 1) / kAggChunkEdges;
+  const int64_t pstr  = (dim + 3) / 4 * 4;
+  return static_cast<size_t>(n_edges + n_src + 64) * 4 + 256 + static_cast<size_t>(tiles * pstr) * 4;
+}
+
+int hip_agg_backward(const wm_agg_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                     const int64_t* n_unique_dev, void* workspace, void* stream_v)
+{
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  if (a->n_src == 0 || a->dim == 0) return 0;
+  wm_agg_bwd_state b;
+  b.order          = order;
+  b.run_starts     = run_starts;
+  b.unique_ids     = unique_ids;
+  b.n_unique       = n_unique_dev;
+  b.n_tiles        = (a->n_edges + kAggChunkEdges - 1) / kAggChunkEdges;
+  b.partial_stride = (a->dim + 3) / 4 * 4;
+  auto up16        = [](uintptr_t v) { return (v + 255) & ~static_cast<uintptr_t>(255); };
+  uintptr_t w      = up16(reinterpret_cast<uintptr_t>(workspace));
+  b.sorted_dst     = reinterpret_cast<int32_t*>(w);
+  w                = up16(w + static_cast<uintptr_t>(a->n_edges) * 4);
+  b.run_of         = reinterpret_cast<int32_t*>(w);
+  w                = up16(w + static_cast<uintptr_t>(a->n_src) * 4);
+  b.partial        = reinterpret_cast<float*>(w);
+
+  if (a->n_edges > 0) {
+    const int blocks = blocks_for(a->n_edges, kAggBlock);
+    hipLaunchKernelGGL(agg_bwd_prep_kernel, dim3(blocks < 8192 ? blocks : 8192), dim3(kAggBlock), 0, stream, *a, b);
+    if (rc_last() != 0) return -2;
+  }
+  const bool v4 = use_vec4(a->dim, a->grad, a->grad_stride, a->out, a->out_stride);
+  if (b.n_tiles > 1) {   // (one tile holds no chunk k >= 1)
+#define WM_AGG_CHUNK(V, L)                                                                                                   \
+  hipLaunchKernelGGL((agg_bwd_chunk_kernel<V, L>), dim3(blocks_for(b.n_tiles, kAggBlock / (L))), dim3(kAggBlock), 0, stream, \
+                     *a, b)
+    WM_AGG_DISPATCH(v4, v4 ? a->dim / 4 : a->dim, WM_AGG_CHUNK);
+#undef WM_AGG_CHUNK
+    if (rc_last() != 0) return -2;
+  }
+#define WM_AGG_FOLD(V, L)                                                                                                   \
+  hipLaunchKernelGGL((agg_bwd_fold_kernel<V, L>), dim3(blocks_for(a->n_src, kAggBlock / (L))), dim3(kAggBlock), 0, stream, \
+                     *a, b)
+  WM_AGG_DISPATCH(v4, v4 ? a->dim / 4 : a->dim, WM_AGG_FOLD);
+#undef WM_AGG_FOLD
+  return rc_last();
+}
+
+}  // namespace wm

@@ -70,6 +70,10 @@ int hip_probe_memory(void* ptr, size_t bytes, int kind, int reps, float* ms_per_
 size_t hip_sort_ids_workspace_bytes(int64_t n);
 int hip_sort_ids(const void* ids, wholememory_dtype_t index_dtype, int64_t n, int64_t key_upper_bound, int low_bit,
                  void* sorted_ids, int64_t* raw, void* workspace, void* stream);
+int hip_agg_forward(const wm_agg_args* a, void* stream);
+size_t hip_agg_backward_workspace_bytes(int64_t n_edges, int64_t n_src, int64_t dim);
+int hip_agg_backward(const wm_agg_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                     const int64_t* n_unique_dev, void* workspace, void* stream);
 
 namespace {
 
@@ -237,6 +241,9 @@ const wm_device_backend kHipBackend = {
   hip_device_error,
   hip_fill_iota,
   hip_partials_nonfinite,
+  hip_agg_forward,
+  hip_agg_backward_workspace_bytes,
+  hip_agg_backward,
 };
 
 }  // namespace

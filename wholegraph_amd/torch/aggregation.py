@@ -1,0 +1,106 @@
+"""Neighbour aggregation of a sampled CSC block — the ``agg_concat`` op behind the GraphSAGE layer
+(``wholememory_ext_csc_aggregate_forward`` / ``_backward``, kernels in ``csrc/kernels/agg.hip``).
+
+``agg_concat(x, row_ptr, col_ind, aggr)`` returns ``[n_dst, 2F]``: the sum (or mean) of each target's neighbour rows of
+``x``, then the target's own row (the targets are the first ``n_dst`` rows of ``x``, as ``append_unique`` leaves them).
+Every fp32 sum, forward and backward, is taken in one fixed order (stated in ``include/wholememory/wholegraph_amd_ext.h``),
+so results are bitwise reproducible."""
+import ctypes as C
+
+import torch
+
+from .. import binding as wmb
+from .wholegraph_env import get_stream, get_wholegraph_env_fns
+
+_AGGR = {"sum": wmb.AGGR_SUM, "mean": wmb.AGGR_MEAN}
+
+
+def aggr_code(aggr: str) -> int:
+    if aggr in ("max", "min"):
+        raise NotImplementedError("aggr=%r: only 'mean' and 'sum' are implemented" % aggr)
+    if aggr not in _AGGR:
+        raise ValueError("aggr must be 'mean' or 'sum' (got %r)" % (aggr,))
+    return _AGGR[aggr]
+
+
+def chunk_edges() -> int:
+    """C: a source's edges are summed in chunks of this many by the backward (the chunk sums added in chunk order)"""
+    return int(wmb.lib().wholememory_ext_csc_aggregate_chunk_edges())
+
+
+def _rows(t: torch.Tensor, what: str) -> torch.Tensor:
+    """a 2-D fp32 tensor whose rows are unit-stride (a row stride of its own is fine)"""
+    if t.dtype != torch.float32:
+        raise TypeError("%s must be float32 (got %s)" % (what, t.dtype))
+    if t.dim() != 2:
+        raise ValueError("%s must be 2-D (got shape %s)" % (what, tuple(t.shape)))
+    if (t.shape[1] > 1 and t.stride(1) != 1) or t.stride(0) < t.shape[1]:
+        t = t.contiguous()
+    return t
+
+
+def _index(t: torch.Tensor, what: str, device) -> torch.Tensor:
+    if t.dim() != 1:
+        raise ValueError("%s must be 1-D" % what)
+    if t.dtype not in (torch.int32, torch.int64):
+        raise TypeError("%s must be int32 or int64 (got %s)" % (what, t.dtype))
+    if t.device != device:
+        raise ValueError("%s is on %s, x on %s" % (what, t.device, device))
+    return t.to(torch.int32).contiguous()
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr())
+
+
+class CscAggregateConcat(torch.autograd.Function):
+    """autograd over the two entry points; the edge index of the backward is built only when x needs a gradient (the
+    backward runs only then)"""
+
+    @staticmethod
+    def forward(ctx, x, row_ptr, col_ind, aggr_code_):
+        n_src, dim = x.shape
+        n_dst = row_ptr.shape[0] - 1
+        out = torch.empty((n_dst, 2 * dim), dtype=torch.float32, device=x.device)
+        wmb.check(wmb.lib().wholememory_ext_csc_aggregate_forward(
+            _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, _ptr(x), x.stride(0) if n_src else dim, dim,
+            aggr_code_, _ptr(out), out.stride(0) if n_dst else 2 * dim, get_wholegraph_env_fns(), C.c_void_p(get_stream())),
+            "csc_aggregate_forward")
+        ctx.save_for_backward(row_ptr, col_ind)
+        ctx.shape = (n_src, dim)
+        ctx.aggr = aggr_code_
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        row_ptr, col_ind = ctx.saved_tensors
+        n_src, dim = ctx.shape
+        n_dst = row_ptr.shape[0] - 1
+        grad_out = _rows(grad_out, "grad_out")
+        grad_x = torch.empty((n_src, dim), dtype=torch.float32, device=grad_out.device)
+        wmb.check(wmb.lib().wholememory_ext_csc_aggregate_backward(
+            _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, _ptr(grad_out),
+            grad_out.stride(0) if n_dst else 2 * dim, dim, ctx.aggr, _ptr(grad_x), dim, get_wholegraph_env_fns(),
+            C.c_void_p(get_stream())), "csc_aggregate_backward")
+        return grad_x, None, None, None
+
+
+def agg_concat(x: torch.Tensor, csr_row_ptr: torch.Tensor, csr_col_ind: torch.Tensor, aggr: str = "mean") -> torch.Tensor:
+    """[n_dst, 2F] = (aggr over each target's neighbour rows of x, the target's own row). csr_row_ptr [n_dst + 1] and
+    csr_col_ind [E] (int32 or int64, converted to int32) describe the block in CSC form: the edges of target d are
+    csr_col_ind[csr_row_ptr[d] : csr_row_ptr[d + 1]], row positions in x. x: fp32 [n_src, F], n_src >= n_dst."""
+    code = aggr_code(aggr)
+    x = _rows(x, "x")
+    if not x.is_cuda:
+        raise ValueError("x must be a GPU tensor")
+    row_ptr = _index(csr_row_ptr, "csr_row_ptr", x.device)
+    col_ind = _index(csr_col_ind, "csr_col_ind", x.device)
+    if row_ptr.shape[0] < 1:
+        raise ValueError("csr_row_ptr needs n_dst + 1 >= 1 entries")
+    if row_ptr.shape[0] - 1 > x.shape[0]:
+        raise ValueError("more targets (%d) than rows of x (%d)" % (row_ptr.shape[0] - 1, x.shape[0]))
+    if x.shape[1] < 1:
+        raise ValueError("x needs at least one column")
+    return CscAggregateConcat.apply(x, row_ptr, col_ind, code)

@@ -1,0 +1,57 @@
+"""GraphSAGE layer of the ``cugraph`` route: ``pylibwholegraph.torch.cugraphops.sage_conv.CuGraphSAGEConv`` (same
+constructor, parameters and ``forward`` signature) over this library's HIP ``agg_concat`` op."""
+import torch
+import torch.nn.functional as F
+from torch import Tensor
+from torch.nn import Linear
+
+from ..aggregation import aggr_code, agg_concat
+
+
+class CuGraphSAGEConv(torch.nn.Module):
+    r"""GraphSAGE ("Inductive Representation Learning on Large Graphs", Hamilton et al. 2017) on a sampled block.
+
+    ``out = lin(cat(aggr_{j in N(i)} x_j, x_i))`` with ``root_weight`` (else ``lin(aggr x_j)``); ``project`` first maps
+    ``x`` through ``relu(pre_lin(x))``; ``normalize`` L2-normalises the output rows. The block is given in CSC form:
+    the neighbours of target ``i`` are ``x[csr_col_ind[csr_row_ptr[i]:csr_row_ptr[i + 1]]]`` and the targets are the
+    first ``len(csr_row_ptr) - 1`` rows of ``x``."""
+
+    def __init__(self, in_channels: int, out_channels: int, aggr: str = "mean", normalize: bool = False,
+                 root_weight: bool = True, project: bool = False, bias: bool = True):
+        super().__init__()
+        if aggr not in ("mean", "sum", "min", "max"):
+            raise ValueError("Aggregation function must be either 'mean', 'sum', 'min' or 'max' (got %r)" % (aggr,))
+        aggr_code(aggr)   # max / min: NotImplementedError here rather than at the first forward
+        self.in_channels = in_channels
+        self.out_channels = out_channels
+        self.aggr = aggr
+        self.normalize = normalize
+        self.root_weight = root_weight
+        self.project = project
+        if self.project:
+            self.pre_lin = Linear(in_channels, in_channels, bias=True)
+        self.lin = Linear((2 if root_weight else 1) * in_channels, out_channels, bias=bias)
+        self.reset_parameters()
+
+    def reset_parameters(self):
+        gain = torch.nn.init.calculate_gain("relu")
+        torch.nn.init.xavier_uniform_(self.lin.weight, gain=gain)
+        if self.project:
+            torch.nn.init.xavier_uniform_(self.pre_lin.weight, gain=gain)
+
+    def forward(self, x: Tensor, csr_row_ptr: Tensor, csr_col_ind: Tensor, max_num_neighbors: int) -> Tensor:
+        # max_num_neighbors: a hint of the reference's fused kernel; the HIP op reads every target's degree from csr_row_ptr
+        del max_num_neighbors
+        if self.project:
+            x = self.pre_lin(x).relu()
+        out = agg_concat(x, csr_row_ptr, csr_col_ind, self.aggr)
+        if self.root_weight:
+            out = self.lin(out)
+        else:
+            out = self.lin(out[:, :self.in_channels])
+        if self.normalize:
+            out = F.normalize(out, p=2.0, dim=-1)
+        return out
+
+    def __repr__(self) -> str:
+        return "%s(%d, %d, aggr=%s)" % (self.__class__.__name__, self.in_channels, self.out_channels, self.aggr)

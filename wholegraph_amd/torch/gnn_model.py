@@ -1,0 +1,111 @@
+"""The GNN model surface of ``pylibwholegraph.torch.gnn_model`` (``set_framework``, ``create_gnn_layers``,
+``create_sub_graph``, ``layer_forward``, ``HomoGNNModel``) for the ``cugraph`` framework route with GraphSAGE layers, on the
+HIP aggregation op (``aggregation.py``). The dgl / pyg / wg routes and GAT are not part of this build.
+
+Flow of ``HomoGNNModel.forward`` (the reference's): sample ``layernum`` hops from the seed ids, gather the float32
+features of the outermost frontier through ``WholeMemoryEmbeddingModule`` (so the embedding receives gradients), then one
+layer per hop from the outermost block inwards, with relu and dropout between layers."""
+import torch
+import torch.nn.functional as F
+
+from .embedding import WholeMemoryEmbedding, WholeMemoryEmbeddingModule
+from .graph_ops import add_csr_self_loop
+from .graph_structure import GraphStructure
+
+FRAMEWORKS = ("cugraph",)
+framework_name = None
+SAGEConv = None
+
+
+def set_framework(framework: str):
+    """Select the layer implementation: "cugraph" (CuGraphSAGEConv on the HIP aggregation op) is the one available."""
+    global framework_name, SAGEConv
+    if framework not in FRAMEWORKS:
+        raise ValueError("framework %r is not available; available: %s" % (framework, ", ".join(FRAMEWORKS)))
+    from .cugraphops.sage_conv import CuGraphSAGEConv
+    framework_name = framework
+    SAGEConv = CuGraphSAGEConv
+
+
+def _require_framework():
+    if framework_name is None:
+        raise RuntimeError("call set_framework(...) first (available: %s)" % ", ".join(FRAMEWORKS))
+
+
+def parse_max_neighbors(num_layer, neighbor_str):
+    """"30,20" -> [30, 20]; a single number is used for every layer"""
+    max_neighbors = [int(ns) for ns in str(neighbor_str).split(",")]
+    if len(max_neighbors) not in (1, num_layer):
+        raise ValueError("%d fan-outs given for %d layers" % (len(max_neighbors), num_layer))
+    if len(max_neighbors) != num_layer:
+        max_neighbors = max_neighbors * num_layer
+    return max_neighbors
+
+
+def create_gnn_layers(in_feat_dim, hidden_feat_dim, class_count, num_layer, num_head, model_type):
+    _require_framework()
+    if model_type == "gat":
+        raise NotImplementedError("model 'gat' is not implemented on the cugraph route yet (only 'sage')")
+    if model_type != "sage":
+        raise ValueError("model %r is not available on the cugraph route (only 'sage')" % (model_type,))
+    gnn_layers = torch.nn.ModuleList()
+    for i in range(num_layer):
+        layer_output_dim = hidden_feat_dim // num_head if i != num_layer - 1 else class_count
+        layer_input_dim = in_feat_dim if i == 0 else hidden_feat_dim
+        gnn_layers.append(SAGEConv(layer_input_dim, layer_output_dim))
+    return gnn_layers
+
+
+def create_sub_graph(target_gid, target_gid_1, edge_data, csr_row_ptr, csr_col_ind, max_num_neighbors: int,
+                     add_self_loop: bool):
+    """[csr_row_ptr, csr_col_ind, max_num_neighbors] of one sampled block (the cugraph route's sub-graph)"""
+    _require_framework()
+    if add_self_loop:
+        csr_row_ptr, csr_col_ind = add_csr_self_loop(csr_row_ptr, csr_col_ind)
+        max_num_neighbors = max_num_neighbors + 1
+    return [csr_row_ptr, csr_col_ind, max_num_neighbors]
+
+
+def layer_forward(layer, x_feat, x_target_feat, sub_graph):
+    _require_framework()
+    return layer(x_feat, sub_graph[0], sub_graph[1], sub_graph[2])
+
+
+class HomoGNNModel(torch.nn.Module):
+    """Node classification model over a homogeneous graph: settings from an ``args`` namespace as the reference reads them
+    (hiddensize, layernum, model, classnum, dropout, neighbors, inferencesample; heads for gat)."""
+
+    def __init__(self, graph_structure: GraphStructure, node_embedding: WholeMemoryEmbedding, args):
+        super().__init__()
+        hidden_feat_dim = args.hiddensize
+        self.graph_structure = graph_structure
+        self.node_embedding = node_embedding
+        self.num_layer = args.layernum
+        self.hidden_feat_dim = args.hiddensize
+        num_head = args.heads if args.model == "gat" else 1
+        assert hidden_feat_dim % num_head == 0
+        in_feat_dim = self.node_embedding.shape[1]
+        self.gnn_layers = create_gnn_layers(in_feat_dim, hidden_feat_dim, args.classnum, args.layernum, num_head,
+                                            args.model)
+        self.mean_output = args.model == "gat"
+        self.add_self_loop = args.model == "gat"
+        self.gather_fn = WholeMemoryEmbeddingModule(self.node_embedding)
+        self.dropout = args.dropout
+        self.max_neighbors = parse_max_neighbors(args.layernum, args.neighbors)
+        self.max_inference_neighbors = parse_max_neighbors(args.layernum, getattr(args, "inferencesample", args.neighbors))
+
+    def forward(self, ids):
+        max_neighbors = self.max_neighbors if self.training else self.max_inference_neighbors
+        ids = ids.to(self.graph_structure.csr_col_ind.dtype).cuda()
+        target_gids, edge_indice, csr_row_ptrs, csr_col_inds = self.graph_structure.multilayer_sample_without_replacement(
+            ids, max_neighbors)
+        x_feat = self.gather_fn(target_gids[0], force_dtype=torch.float32)
+        for i in range(self.num_layer):
+            x_target_feat = x_feat[:target_gids[i + 1].numel()]
+            sub_graph = create_sub_graph(target_gids[i], target_gids[i + 1], edge_indice[i], csr_row_ptrs[i],
+                                         csr_col_inds[i], max_neighbors[self.num_layer - 1 - i], self.add_self_loop)
+            x_feat = layer_forward(self.gnn_layers[i], x_feat, x_target_feat, sub_graph)
+            if i != self.num_layer - 1:
+                x_feat = F.relu(x_feat)
+                x_feat = F.dropout(x_feat, self.dropout, training=self.training)
+        return x_feat

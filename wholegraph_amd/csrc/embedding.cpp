@@ -177,12 +177,8 @@ wholememory_error_code_t create_states(wholememory_embedding_* e)
     }
     // zero the local shard of the packed states (reference zero_local_state_tensor)
     auto* ld = wholememory_tensor_get_tensor_description(e->state_local);
-    if (WM_AB_KNOB("WM_STATE_ZERO_MEMSET") != nullptr)
-      WM_BK(bk->memset_async(wholememory_tensor_get_data_pointer(e->state_local), 0,
-                             static_cast<size_t>(ld->sizes[0]) * ld->strides[0] * sizeof(float), nullptr));
-    else
-      WM_BK(bk->fill_float(static_cast<float*>(wholememory_tensor_get_data_pointer(e->state_local)), 0.0f,
-                           ld->sizes[0] * ld->strides[0], nullptr));
+    WM_BK(bk->fill_float(static_cast<float*>(wholememory_tensor_get_data_pointer(e->state_local)), 0.0f,
+                         ld->sizes[0] * ld->strides[0], nullptr));
     WM_BK(bk->stream_sync(nullptr));
     // a read-write device cache also holds the states of its resident rows (reference: cachable optimizer states)
     if (e->cache != nullptr && e->cache->writable) WHOLEMEMORY_RETURN_ON_FAIL(wm::row_cache_attach_states(e->cache, e->state_local));
@@ -561,11 +557,9 @@ wholememory_error_code_t gather_gradient_apply(wholememory_embedding_* e, wholem
   const char* idx_ptr = static_cast<const char*>(wholememory_tensor_get_data_pointer(indices));  // data ptr already offset
 
   // this rank's own rows are not copied at all: the step kernels read them where the caller left them (the receive
-  // positions of the self segment are remapped to caller rows after the sort). WM_GRAD_SELF_COPY=1 restores the copy.
-  const char* self_copy_env = WM_AB_KNOB("WM_GRAD_SELF_COPY");
-  const bool self_local     = !e->comm->loopback;  // loopback: the self segment is exchanged like a peer's
-  const bool self_in_place  = self_local && bk->remap_self_order != nullptr &&
-                             !(self_copy_env != nullptr && self_copy_env[0] == '1');
+  // positions of the self segment are remapped to caller rows after the sort).
+  const bool self_local    = !e->comm->loopback;  // loopback: the self segment is exchanged like a peer's
+  const bool self_in_place = self_local && bk->remap_self_order != nullptr;
   // One rank, nothing to exchange: the batch IS the receive buffer, the caller's gradient tensor IS the row buffer. Ids that
   // address no row (negative "skip me" ids, ids past the table) are dropped by the sort itself — they read as one marker key
   // that sorts behind every row and whose run is not counted (backend.hpp: dedup_ids) — so no pass over the ids and no look

@@ -395,12 +395,11 @@ wholememory_error_code_t graph_append_unique(wholememory_tensor_t target_nodes_t
 
 namespace {
 // offsets[0 .. n] of a hop: one launch (counts inside the scan, kernels/graph.hip: chain_scan_kernel) where the backend has
-// it and takes the size, else count kernel + scan. WM_SAMPLE_FUSED_SCAN=0 forces the two steps (A/B).
+// it and takes the size, else count kernel + scan.
 int hop_offsets(const wm_device_backend* bk, const wm_sample_args& a, const int* n_dev, int* counts, int* offsets, void* scan_ws,
                 size_t scan_ws_bytes, void* stream, int ws_is_ones = 0)
 {
-  const char* sw = WM_AB_KNOB("WM_SAMPLE_FUSED_SCAN");
-  if (bk->sample_offsets != nullptr && !(sw != nullptr && sw[0] == '0')) {
+  if (bk->sample_offsets != nullptr) {
     const int rc = bk->sample_offsets(&a.row_gref, a.row_storage_offset, a.centers, a.center_dtype, a.n_center, n_dev,
                                       a.max_sample_count, offsets, scan_ws, scan_ws_bytes, ws_is_ones, stream);
     if (rc != -3) return rc;

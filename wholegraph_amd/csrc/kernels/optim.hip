@@ -400,11 +400,10 @@ struct sort_lane {
   struct adapt_entry {
     int64_t lower = -1, upper = -1;
     unsigned calls = 0;
-    int mode = 0;   // round 6: 0 the plain split sort, 1 the split sort with hot ids peeled (split::launch_hot), 2 rocPRIM's sort
+    bool generic = false;   // the range's batches go to rocPRIM's sort (its last split sort or probe overflowed)
   };
   adapt_entry adapt[kAdapt];
-  // pinned, three words per row range: [i] the overflow word of its last PLAIN split sort, [kAdapt + i] of its last HOT split
-  // sort or probe, [2 kAdapt + i] how many ids that one peeled
+  // pinned, one word per row range: the overflow word of its last split sort or probe
   volatile int32_t* adapt_flags = nullptr;
   unsigned adapt_generation     = ~0u;       // a knob reload forgets what was learnt (tests, A/B runs)
   int adapt_next                = 0;
@@ -413,21 +412,21 @@ struct sort_lane {
   {
     if (adapt_flags == nullptr) {
       void* h = nullptr;
-      if (hipHostMalloc(&h, 3 * kAdapt * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) return -1;
+      if (hipHostMalloc(&h, kAdapt * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) return -1;
       adapt_flags = static_cast<volatile int32_t*>(h);
-      for (int i = 0; i < 3 * kAdapt; i++) adapt_flags[i] = 0;
+      for (int i = 0; i < kAdapt; i++) adapt_flags[i] = 0;
     }
     const unsigned g = g_knob_generation.load(std::memory_order_acquire);
     if (g != adapt_generation) {
-      for (int i = 0; i < kAdapt; i++) adapt[i] = adapt_entry{}, adapt_flags[i] = adapt_flags[kAdapt + i] = adapt_flags[2 * kAdapt + i] = 0;
+      for (int i = 0; i < kAdapt; i++) adapt[i] = adapt_entry{}, adapt_flags[i] = 0;
       adapt_generation = g;
     }
     for (int i = 0; i < kAdapt; i++)
       if (adapt[i].lower == lower && adapt[i].upper == upper) return i;
     const int i = adapt_next;
     adapt_next  = (adapt_next + 1) % kAdapt;
-    adapt[i]    = adapt_entry{lower, upper, 0, 0};
-    adapt_flags[i] = adapt_flags[kAdapt + i] = adapt_flags[2 * kAdapt + i] = 0;
+    adapt[i]    = adapt_entry{lower, upper, 0, false};
+    adapt_flags[i] = 0;
     return i;
   }
   // Device-side waits that gave up (split_sort.cuh: wait_cfg) leave their code in this word of pinned, device-mapped host
@@ -523,7 +522,6 @@ inline split::wait_cfg wait_limits(const split::plan* sp = nullptr)
 }
 inline bool stall_join() { const char* st = WM_KNOB("WM_DEBUG_STALL"); return st != nullptr && st[0] == 'j'; }
 std::atomic<int64_t> g_split_sorts{0};
-std::atomic<int64_t> g_hot_split_sorts{0};   // ... of them with hot ids peeled (split::launch_hot)
 // The optimizer step that follows a split sort on the same thread finds the sort's control words through the run_starts array
 // both were given: its long-run counters live there (zeroed by the sort's first kernel: no fill in front of the step), and
 // the listing kernels return at once when the sort saw neither an overflow nor a bucket with a run of more than kMaxDup ids —
@@ -645,21 +643,9 @@ int run_dedup(const void* ids, int64_t n, int64_t key_upper_bound, int64_t key_l
   // batch goes straight to rocPRIM (below), and every kProbeEvery-th such call runs the split sort's first two kernels as a
   // probe in front (30 us / 4); the first batch that would not overflow switches back. A wrong guess costs time, once.
   // WM_DEDUP_ADAPT=0: always the split sort. Not while a stream is captured (a graph replays ONE route).
-  // Round 6: three routes per row range. 0 = the plain split sort; when it overflowed, 1 = the split sort with the batch's hot ids
-  // peeled into buckets of their own (split::launch_hot: a Zipf batch then fits; taken only with WM_DEDUP_HOT=1, see below); when THAT
-  // overflowed too (ids clustered in a few thousand rows), 2 = rocPRIM's sort, probed every kProbeEvery-th call with the first
-  // kernels of the hot-mode sort. Back: a hot-mode sort that peeled nothing returns the range to route 0.
   bool expect_overflow = false;
-  bool hot_route       = false;
   int adapt_slot       = -1;
-  // (OPT-IN, WM_DEDUP_HOT=1: correct on every case of the harness and the parity tests, but on the Zipf(1.05) batch of 10 M ids the
-  // hot-mode sort takes 0.54-0.70 ms where rocPRIM's takes 0.36 — putting the ~90 k listed segments into receive order costs more
-  // than the radix passes it avoids: profiles/r06_split_sort_hot_harness.txt. Route 2 follows a plain overflow by default.)
-  const bool hot_allowed = WM_KNOB("WM_DEDUP_HOT") != nullptr && (WM_KNOB("WM_DEDUP_HOT")[0] == '1' || WM_KNOB("WM_DEDUP_HOT")[0] == '2');
-  const bool hot_forced  = WM_KNOB("WM_DEDUP_HOT") != nullptr && WM_KNOB("WM_DEDUP_HOT")[0] == '2';   // (tests: every batch takes route 1)
-  if (hot_forced) {
-    hot_route = span > 0 && span < INT64_C(0xFFFFFFFF) && n >= split_min() && split::make_plan(n, span, 0, 0, true).ok;
-  } else if (span > 0 && span < INT64_C(0xFFFFFFFF) && n >= split_min() && WM_KNOB("WM_DEDUP_SERIAL") == nullptr &&
+  if (span > 0 && span < INT64_C(0xFFFFFFFF) && n >= split_min() && WM_KNOB("WM_DEDUP_SERIAL") == nullptr &&
       !(WM_KNOB("WM_DEDUP_ADAPT") != nullptr && WM_KNOB("WM_DEDUP_ADAPT")[0] == '0')) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusNone && sort_lane::get().ok) {
@@ -667,48 +653,32 @@ int run_dedup(const void* ids, int64_t n, int64_t key_upper_bound, int64_t key_l
       std::lock_guard<std::mutex> lk(lane.mu);
       adapt_slot = lane.adapt_slot(key_lower_bound, key_upper_bound);
       if (adapt_slot >= 0) {
-        auto& e = lane.adapt[adapt_slot];
-        volatile int32_t* f_plain = lane.adapt_flags + adapt_slot;
-        volatile int32_t* f_hot   = lane.adapt_flags + sort_lane::kAdapt + adapt_slot;
-        volatile int32_t* f_nhot  = lane.adapt_flags + 2 * sort_lane::kAdapt + adapt_slot;
-        const split::plan hp = hot_allowed ? split::make_plan(n, span, 0, 0, true) : split::plan{};
-        const bool can_hot   = hot_allowed && hp.ok;
-        if (e.mode == 0 && *f_plain != 0) {
-          e.mode = can_hot ? 1 : 2, e.calls = 0;
-          *f_hot = can_hot ? 0 : 1, *f_nhot = 1;
-        } else if (e.mode == 1 && (!can_hot || *f_hot != 0)) {
-          e.mode = 2, e.calls = 0;
-        } else if (e.mode == 1 && *f_nhot == 0) {
-          e.mode = 0, *f_plain = 0;   // (nothing was peeled: the batches are no longer skewed)
-        }
-        if (e.mode == 2) {
-          const split::plan sp = can_hot ? hp : split::make_plan(n, span);
+        auto& e                   = lane.adapt[adapt_slot];
+        volatile int32_t* verdict = lane.adapt_flags + adapt_slot;
+        if (!e.generic && *verdict != 0) e.generic = true, e.calls = 0;
+        if (e.generic) {
+          const split::plan sp = split::make_plan(n, span);
           if (!sp.ok) {
-            e.mode = 0, *f_plain = 0;   // (a batch the split sort would not take anyway)
-          } else {
-            volatile int32_t* verdict = can_hot ? f_hot : f_plain;
-            if (*verdict == 0) {
-              e.mode = can_hot ? 1 : 0;   // the last probe found room: back to the split sort
-              if (e.mode == 1) *f_nhot = 1;
-            } else if (++e.calls % sort_lane::kProbeEvery == 0) {
-              if (lane.probe_ws == nullptr && hipMalloc(&lane.probe_ws, split::probe_workspace_bytes()) != hipSuccess) lane.probe_ws = nullptr;
-              if (lane.probe_ws != nullptr) {
-                if (split::launch_probe<UKey>(sp, static_cast<const UKey*>(ids), n, static_cast<UKey>(key_lower_bound),
-                                              static_cast<uint32_t>(span), lane.probe_ws, stream) != 0)
-                  return -2;
-                (void)hipMemcpyAsync(const_cast<int32_t*>(verdict), split::probe_overflow_word(sp, lane.probe_ws), sizeof(int32_t),
-                                     hipMemcpyDeviceToHost, stream);
-              }
+            e.generic = false, *verdict = 0;   // (a batch the split sort would not take anyway)
+          } else if (*verdict == 0) {
+            e.generic = false;   // the last probe found room: back to the split sort
+          } else if (++e.calls % sort_lane::kProbeEvery == 0) {
+            if (lane.probe_ws == nullptr && hipMalloc(&lane.probe_ws, split::probe_workspace_bytes()) != hipSuccess) lane.probe_ws = nullptr;
+            if (lane.probe_ws != nullptr) {
+              if (split::launch_probe<UKey>(sp, static_cast<const UKey*>(ids), n, static_cast<UKey>(key_lower_bound),
+                                            static_cast<uint32_t>(span), lane.probe_ws, stream) != 0)
+                return -2;
+              (void)hipMemcpyAsync(const_cast<int32_t*>(verdict), split::probe_overflow_word(sp, lane.probe_ws), sizeof(int32_t),
+                                   hipMemcpyDeviceToHost, stream);
             }
           }
         }
-        expect_overflow = e.mode == 2;
-        hot_route       = e.mode == 1;
+        expect_overflow = e.generic;
       }
     }
   }
   if (!expect_overflow && span > 0 && span < INT64_C(0xFFFFFFFF) && n >= split_min()) {
-    const split::plan sp = split::make_plan(n, span, 0, 0, hot_route);
+    const split::plan sp = split::make_plan(n, span);
     if (sp.ok) {
       const split_layout sl = split_carve(workspace, n);
       const unsigned bits   = significant_bits(span + 1, 32);
@@ -766,34 +736,24 @@ int run_dedup(const void* ids, int64_t n, int64_t key_upper_bound, int64_t key_l
                    hipStreamWaitEvent(lane.side(), lane.forked, 0) == hipSuccess;
         }
         generic(forked ? lane.side() : stream);
-        if (forked && adapt_slot >= 0) {   // (what this batch did decides the route of the next: see "adaptive route")
-          (void)hipMemcpyAsync(const_cast<int32_t*>(lane.adapt_flags) + (hot_route ? sort_lane::kAdapt : 0) + adapt_slot, gate,
-                               sizeof(int32_t), hipMemcpyDeviceToHost, lane.side());
-          if (hot_route)   // ... and how many ids it peeled (none: the range goes back to the plain split sort)
-            (void)hipMemcpyAsync(const_cast<int32_t*>(lane.adapt_flags) + 2 * sort_lane::kAdapt + adapt_slot,
-                                 split::hot_view(sp, sl.split_ws).n_hot, sizeof(int32_t), hipMemcpyDeviceToHost, lane.side());
-        }
+        if (forked && adapt_slot >= 0)   // (what this batch did decides the route of the next: see "adaptive route")
+          (void)hipMemcpyAsync(const_cast<int32_t*>(lane.adapt_flags) + adapt_slot, gate, sizeof(int32_t), hipMemcpyDeviceToHost,
+                               lane.side());
         if (forked) forked = hipEventRecord(lane.joined, lane.side()) == hipSuccess;
       };
       // With the fork by a word nothing ties the side stream's launches to a place in the caller's queue: the caller's kernels
       // — the split sort's four — are enqueued FIRST (a mini-batch is bound by the host's launch rate — the nine side launches in the middle delayed the
       // scatter kernel by as many launch times), then the side stream, then the join kernel.
-      const bool side_last = verdict_word != nullptr && !(WM_AB_KNOB("WM_SIDE_FIRST") != nullptr && WM_AB_KNOB("WM_SIDE_FIRST")[0] == '1');
+      // (forked by an event, the side stream is enqueued between the scan and the scatter kernel: the event has to follow the scan)
+      const bool side_last = verdict_word != nullptr;
       auto nothing         = []() {};
-      const bool after_scatter = WM_AB_KNOB("WM_DEDUP_FORK") != nullptr && WM_AB_KNOB("WM_DEDUP_FORK")[0] == '3';
       const int launched =
-        hot_route ? (side_last ? split::launch_hot<UKey>(sp, static_cast<const UKey*>(ids), n, static_cast<UKey>(key_lower_bound),
-                                                         static_cast<uint32_t>(span), unique_ids, run_starts, order, n_unique_out,
-                                                         sl.split_ws, sl.osw_ctrl, zero_n, stream, nothing, verdict_word, verdict_value, wc)
-                               : split::launch_hot<UKey>(sp, static_cast<const UKey*>(ids), n, static_cast<UKey>(key_lower_bound),
-                                                         static_cast<uint32_t>(span), unique_ids, run_starts, order, n_unique_out,
-                                                         sl.split_ws, sl.osw_ctrl, zero_n, stream, between, verdict_word, verdict_value, wc)) :
         side_last ? split::launch<UKey>(sp, static_cast<const UKey*>(ids), n, static_cast<UKey>(key_lower_bound),
                                         static_cast<uint32_t>(span), unique_ids, run_starts, order, n_unique_out, sl.split_ws,
-                                        sl.osw_ctrl, zero_n, stream, nothing, false, verdict_word, verdict_value, wc)
+                                        sl.osw_ctrl, zero_n, stream, nothing, verdict_word, verdict_value, wc)
                   : split::launch<UKey>(sp, static_cast<const UKey*>(ids), n, static_cast<UKey>(key_lower_bound),
                                         static_cast<uint32_t>(span), unique_ids, run_starts, order, n_unique_out, sl.split_ws,
-                                        sl.osw_ctrl, zero_n, stream, between, after_scatter, verdict_word, verdict_value, wc);
+                                        sl.osw_ctrl, zero_n, stream, between, verdict_word, verdict_value, wc);
       if (launched != 0) return -2;
       // (every wave that waits is enqueued BEHIND the kernel it waits for — the side stream's behind the split sort's kernels,
       // the join kernel behind the side stream's last — so that even one in-order hardware queue makes progress)
@@ -807,7 +767,6 @@ int run_dedup(const void* ids, int64_t n, int64_t key_upper_bound, int64_t key_l
                          sort_lane::get().host_err_dev);
       if (defer) g_join_pending = true;
       g_split_sorts.fetch_add(1, std::memory_order_relaxed);
-      if (hot_route) g_hot_split_sorts.fetch_add(1, std::memory_order_relaxed);
       g_last_split.run_starts = run_starts;
       g_last_split.unique_ids = unique_ids;
       g_last_split.n_unique   = n_unique_out;
@@ -873,13 +832,12 @@ struct opt_params {
   long_run_entry* long_list;
   int32_t* long_count;
   const uint32_t* split_ctl;   // control words of the split sort that produced the runs (or nullptr): see last_split_record
-  // step_tile_kernel: runs per wave tile. 64 with the persistent grid of round 2; one batch (RPS x kU runs) when the tiles
-  // are handed out in order, one per wave (round 3, see launch_step_opt)
+  // step_tile_kernel: runs per wave tile (64: the persistent grid of round 2, tile_launch_shape)
   int tile_runs;
   // runs of more rows than this are not folded by step_tile_kernel / step_short_kernel but listed for the long-run side
-  // (kLongRun with the ordered fold, tree_threshold() with the tree fold)
+  // (kLongRun with the ordered fold, kTreeMin with the tree fold)
   int long_threshold;
-  int detached_side;   // 1 / 2: the long-run side runs on a side stream the caller's stream does NOT wait for (hip_optimizer_step_dev)
+  int detached_side;   // 1: the long-run side runs on a side stream the caller's stream does NOT wait for (hip_optimizer_step_dev)
   int fold_tree;   // 1: the long-run side is the tree fold (tree_fold_kernel), 0: the ordered fold (step_long4_kernel)
   // ordered fold of the very long runs through a dense transposed copy (kernels/long_dense.cuh; round 6): listed runs of at least
   // dense_min rows get a job and room in dense_buf while it lasts (dense_cap floats), the others stay step_long4_kernel's.
@@ -1226,7 +1184,7 @@ __device__ __forceinline__ P* tile_bcast_ptr(P* p, int e0, int sub)
 #ifndef WM_TILE_DUP
 #define WM_TILE_DUP 2
 #endif
-// 16 bytes per lane, KU = steps in flight (0: the default for the optimizer). Swept on the 10 M-row SGD / LazyAdam call
+// 16 bytes per lane, kU = steps in flight. Swept on the 10 M-row SGD / LazyAdam call
 // (profiles/r02_tile_sweep.txt): 16 B x 4 steps (SGD) and 16 B x 2 (stateful) are the defaults; 8 B per lane (a 512-byte row
 // per wave, every per-row quantity wave-uniform) is 5 % slower, 8 steps in flight no faster, grids of 2048 / 4096
 // workgroups 5-8 % slower than 8192.
@@ -1310,9 +1268,8 @@ __device__ __forceinline__ tile_raw4 tile_pack(const tile_vals<16 / sizeof(T)>& 
 // of peak). Here the first dim / 4 pieces of every row go through the same straight-line batches (the packed gradient rows are
 // only 4-byte aligned: tile_raw4_u; table and state rows sit on a 16-byte stride), and the last dim % 4 floats of the tile's
 // 64 rows are a pass of their own, one LANE per run (4-byte accesses, duplicates added in receive order as everywhere).
-template <typename IdxT, int OPT, int RPS, bool CACHED, typename T = float, int KU = 0, int OCC = 0, int PIECE = 16, bool RAGGED = false>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(OCC > 0 ? OCC : 1, OCC > 0 ? OCC : 8)))
-void step_tile_kernel(opt_params p)
+template <typename IdxT, int OPT, int RPS, bool CACHED, typename T = float, int PIECE = 16, bool RAGGED = false>
+__global__ __launch_bounds__(kBlock) void step_tile_kernel(opt_params p)
 {
   static_assert(PIECE == 16 || (PIECE == 8 && sizeof(T) == 4), "pieces of 16 bytes, or of 8 bytes of fp32 rows");
   static_assert(!RAGGED || (PIECE == 16 && sizeof(T) == 4 && !CACHED), "ragged rows: fp32, 16-byte pieces, no row cache");
@@ -1328,7 +1285,7 @@ void step_tile_kernel(opt_params p)
   auto st_state = [](void* q, raw_t v) { st_global_nt<raw_t>(q, v); };
   constexpr int kVE          = PIECE / static_cast<int>(sizeof(T));  // elements per lane
   constexpr bool k16         = sizeof(T) == 2;
-  constexpr int kU           = KU > 0 ? KU : ((OPT == WHOLEMEMORY_OPT_SGD && !k16) ? WM_TILE_KU_SGD : WM_TILE_KU_STATE);
+  constexpr int kU           = (OPT == WHOLEMEMORY_OPT_SGD && !k16) ? WM_TILE_KU_SGD : WM_TILE_KU_STATE;
   constexpr int kLpr         = 64 / RPS;
   constexpr bool kState      = OPT != WHOLEMEMORY_OPT_SGD;
   constexpr bool kAdam       = OPT == WHOLEMEMORY_OPT_LAZY_ADAM;
@@ -1992,7 +1949,7 @@ void launch_mark_long_runs(const opt_params& p, hipStream_t stream, hipStream_t 
 // "listed for the long-run side" drops from 256 rows to kTreeMin.
 constexpr int kTreeSeg     = 512;   // rows per segment, at least
 constexpr int kTreeMaxSegs = 256;   // segments per run, at most (a longer run gets longer segments): bounds the combine chain
-constexpr int kTreeMin     = 128;   // runs of more rows than this are listed (WM_GRAD_FOLD_MIN; swept 16 ... 256 on the Zipf batch:
+constexpr int kTreeMin     = 128;   // runs of more rows than this are listed (swept 16 ... 256 on the Zipf batch:
                                     // 2.58 / 2.34 / 2.23 / 2.19 / 2.25 ms per call at 16 / 32 / 64 / 128 / 256)
 
 struct tree_run {
@@ -2236,12 +2193,6 @@ __global__ __launch_bounds__(kBlock) void tree_combine_kernel(opt_params p, tree
   }
 }
 
-inline int tree_threshold()
-{
-  const char* e = WM_AB_KNOB("WM_GRAD_FOLD_MIN");
-  const int v   = e != nullptr ? atoi(e) : 0;
-  return v >= 4 && v <= kLongRun ? v : kTreeMin;
-}
 // ordered (0) or tree (1): WM_GRAD_FOLD overrides, then the caller's fold_mode, then the default of the value dtype
 inline int resolve_fold_mode(const wm_optimizer_args& a)
 {
@@ -2265,35 +2216,18 @@ void launch_tree(const opt_params& p, hipStream_t stream, hipStream_t lstream)
     (void)hipEventRecord(long_lane::get().marked, lstream);
     (void)hipStreamWaitEvent(stream, long_lane::get().marked, 0);
   }
-  int fgrid = 2048;
-  if (const char* e = WM_AB_KNOB("WM_TREE_GRID")) fgrid = std::max(1, atoi(e));
-  hipLaunchKernelGGL((tree_fold_kernel<IdxT, OPT, T>), dim3(fgrid), dim3(kBlock), 0, lstream, p, w);
+  hipLaunchKernelGGL((tree_fold_kernel<IdxT, OPT, T>), dim3(2048), dim3(kBlock), 0, lstream, p, w);
   hipLaunchKernelGGL((tree_combine_kernel<IdxT, OPT, T>), dim3(256), dim3(kBlock), 0, lstream, p, w);
 }
 
-// Launch shape of step_tile_kernel. Default: round 2's persistent grid of 8192 workgroups over tiles of 64 runs.
-// WM_TILE_INORDER=1: the in-order shape of the row kernels (rows.hip: rows_op) — one tile of ONE batch of runs per wave
-// (RPS x kU runs: 8 for SGD on 512-byte rows), as many workgroups as the upper bound of the run count takes (the true count is
-// on the device: waves past it leave at once). Measured on whole 10 M-row calls, interleaved in one process
-// (experiments/grad_inorder_ab.py, profiles/r03_grad_inorder_ab.txt): SGD uniform 3.281 vs 3.268 ms, Zipf 3.12-3.23 vs 3.09-3.10,
-// LazyAdam 6.295 vs 6.305, fp16 x 256 3.143 vs 3.189, 256-byte rows 1.856 vs 1.877 — a wash: this kernel has no dense streamed
-// side whose DRAM pages an ordered window could keep open (gradient rows arrive through order[], table rows are 1 in 10 of a
-// sorted sweep), so the default stays. WM_TILE_RUNS forces the tile (a multiple of the batch).
-inline void tile_launch_shape(int64_t count_bound, int vecs, int ku, int* tile_runs, int* tblocks)
+// Launch shape of step_tile_kernel: round 2's persistent grid of 8192 workgroups over tiles of 64 runs. (The in-order shape
+// of the row kernels — one batch of runs per wave tile, as many workgroups as the run count's upper bound takes — was a wash
+// on whole 10 M-row calls: profiles/r03_grad_inorder_ab.txt.)
+inline void tile_launch_shape(int64_t count_bound, int* tile_runs, int* tblocks)
 {
-  const int rps      = vecs > 32 ? 1 : vecs > 16 ? 2 : vecs > 8 ? 4 : 8;
-  const int batch    = rps * ku;
-  const char* io_env = WM_AB_KNOB("WM_TILE_INORDER");
-  const bool inorder = io_env != nullptr && io_env[0] == '1';
-  *tile_runs         = inorder ? std::min(64, batch) : 64;
-  if (const char* e = WM_AB_KNOB("WM_TILE_RUNS")) {
-    const int v = atoi(e);
-    if (v >= batch && v <= 64 && v % batch == 0) *tile_runs = v;
-  }
-  const int64_t tiles = (count_bound + *tile_runs - 1) / *tile_runs;
-  int b = static_cast<int>(std::min<int64_t>((tiles + 3) / 4, inorder ? INT64_C(0x7fffffff) : INT64_C(256 * 32)));
-  if (const char* e = WM_AB_KNOB("WM_STEP_BLOCKS")) b = std::min(b, std::max(1, atoi(e)));
-  *tblocks = std::max(b, 1);
+  *tile_runs          = 64;
+  const int64_t tiles = (count_bound + 63) / 64;
+  *tblocks            = std::max(static_cast<int>(std::min<int64_t>((tiles + 3) / 4, INT64_C(256 * 32))), 1);
 }
 
 template <typename IdxT, int OPT>
@@ -2314,8 +2248,7 @@ int launch_step_opt(const opt_params& p, int blocks, hipStream_t stream, hipStre
       const bool long4 = p.a.dim % kSliceCols == 0 && p.a.grad_stride % 4 == 0 && gaddr % 16 == 0 && self_ok4;
       const bool rows4 = p.a.dim % 4 == 0 && p.a.grad_stride % 4 == 0 && gaddr % 16 == 0 && self_ok4 &&
                          p.a.dim <= 65535 * slice4_cols<float>();
-      const bool old_long = WM_AB_KNOB("WM_STEP_LONG_OLD") != nullptr;
-      if (rows4 && !old_long) {
+      if (rows4) {
         static const bool lds_ok =
           hipFuncSetAttribute(reinterpret_cast<const void*>(&step_long4_kernel<IdxT, OPT>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(kLong4LdsBytes)) == hipSuccess;
@@ -2323,8 +2256,7 @@ int launch_step_opt(const opt_params& p, int blocks, hipStream_t stream, hipStre
         // 144 KiB of LDS = one workgroup per CU: launch one resident wave of workgroups (256 CUs) and let each walk the
         // run list — with more workgroups than CUs the hottest run may only START after several rounds of others
         const int slices4 = static_cast<int>((p.a.dim + slice4_cols<float>() - 1) / slice4_cols<float>());
-        int gx            = std::max(1, 256 / slices4);
-        if (const char* e = WM_AB_KNOB("WM_LONG_GRID")) gx = std::max(1, atoi(e));
+        const int gx      = std::max(1, 256 / slices4);
         // (the first workgroups per slice fold the dense copies — 16 x slices4 of them take 4 runs of 128 columns in 8-column
         // slices —, the others walk the list as before; TOGETHER one resident round: with 16 workgroups per slice on top of
         // the 256 / slices4 the last ones only started when the tile kernel had filled the chip, and finished after it —
@@ -2340,25 +2272,24 @@ int launch_step_opt(const opt_params& p, int blocks, hipStream_t stream, hipStre
     }
     return 0;
   };
-  if (p.detached_side != 1 && long_side() != 0) return -2;
+  if (!p.detached_side && long_side() != 0) return -2;
   // (a float4-per-lane variant, two runs per wave instruction, was measured too: no gain for SGD, 10-15 % slower for the
   // stateful optimizers through register pressure — 8 bytes per lane stay)
   const bool cached = p.a.cache_slot_of != nullptr;
-  // rows of whole 16-byte pieces on every side: the tile kernel (WM_STEP_TILE=0 keeps the wave-per-run kernel)
-  const bool tile_off = WM_AB_KNOB("WM_STEP_TILE") != nullptr && WM_AB_KNOB("WM_STEP_TILE")[0] == '0';
+  // rows of whole 16-byte pieces on every side: the tile kernel
   const bool st_ok = p.a.per_element_state == nullptr ||
                      (p.a.per_element_stride % 4 == 0 && reinterpret_cast<uint64_t>(p.a.per_element_state) % 16 == 0 &&
                       (p.a.cache_state_data == nullptr || (p.a.cache_state_row_elems % 4 == 0 &&
                                                            reinterpret_cast<uint64_t>(p.a.cache_state_data) % 16 == 0)));
   const bool tb_ok = p.a.table_stride % 4 == 0 && reinterpret_cast<uint64_t>(p.a.local_table) % 16 == 0 &&
                      (!cached || (p.a.cache_row_elems % 4 == 0 && reinterpret_cast<uint64_t>(p.a.cache_data) % 16 == 0));
-  const bool tile_ok = !tile_off && p.a.dim % 4 == 0 && p.a.dim >= 32 && p.a.grad_stride % 4 == 0 && gaddr % 16 == 0 &&
+  const bool tile_ok = p.a.dim % 4 == 0 && p.a.dim >= 32 && p.a.grad_stride % 4 == 0 && gaddr % 16 == 0 &&
                        self_ok4 && st_ok && tb_ok;
   if (tile_ok) {
     const int vecs = static_cast<int>(p.a.dim / 4);
     opt_params tp = p;
     int tblocks   = 1;
-    tile_launch_shape(p.a.count, vecs, OPT == WHOLEMEMORY_OPT_SGD ? WM_TILE_KU_SGD : WM_TILE_KU_STATE, &tp.tile_runs, &tblocks);
+    tile_launch_shape(p.a.count, &tp.tile_runs, &tblocks);
     // (Round 3 ran SGD on 512-byte rows through a copy of the kernel forced to 7 waves / SIMD, 10 values spilled to scratch:
     // its loads were serialised and occupancy was the only source of loads in flight. With the straight-line batches the
     // natural register budget — 84 VGPRs, 5 waves, no scratch — is the faster one: 2.92 vs 2.98 ms per 10 M rows,
@@ -2375,47 +2306,44 @@ int launch_step_opt(const opt_params& p, int blocks, hipStream_t stream, hipStre
     else if (vecs > 8) WM_TILE(4);
     else WM_TILE(8);
 #undef WM_TILE
-    if (p.detached_side == 1 && long_side() != 0) return -2;
+    if (p.detached_side && long_side() != 0) return -2;
     return hipGetLastError() == hipSuccess ? 0 : -2;
   }
   // rows of whole 8-byte pieces that are not whole 16-byte ones (dim = 2 mod 4: 602 floats, the Reddit feature width): the tile
   // kernel with 8-byte pieces (round 6) — one 512-byte wave step per row instead of the wave-per-run kernel below.
-  // WM_STEP_TILE8=0 keeps the wave-per-run kernel (A/B).
   // rows of dim % 4 != 0 floats: the tile kernel on the first dim / 4 sixteen-byte pieces + a lane-per-run pass over the last
   // dim % 4 floats (RAGGED). Gradient rows may start anywhere (4-byte aligned). Whole calls, 10 M rows, probed placement
   // (profiles/r06_dim_sweep_ragged.txt): 513 floats 47.8 -> 62-64 % of peak, 301 floats 46 -> 55 %; 129 / 127 floats 36-44 % either
   // way (rows of ~512 B that start inside a line on every side); dim = 2 mod 4: 602 floats 60.0 -> 61.7 %, 130 floats 41.8 -> 43.7 %
   // against the 8-byte-piece kernel below, which WM_STEP_RAGGED=0 keeps (with the wave-per-run kernel for odd dims).
   const char* ragged_env = WM_KNOB("WM_STEP_RAGGED");
-  const bool ragged_ok = !tile_off && !cached && p.a.dim >= 36 && p.a.dim % 4 != 0 && st_ok && tb_ok &&
+  const bool ragged_ok = !cached && p.a.dim >= 36 && p.a.dim % 4 != 0 && st_ok && tb_ok &&
                          !(ragged_env != nullptr && ragged_env[0] == '0');
   if (ragged_ok) {
     const int vecs = static_cast<int>(p.a.dim / 4);
     opt_params tp = p;
     int tblocks   = 1;
-    tile_launch_shape(p.a.count, vecs, OPT == WHOLEMEMORY_OPT_SGD ? WM_TILE_KU_SGD : WM_TILE_KU_STATE, &tp.tile_runs, &tblocks);
+    tile_launch_shape(p.a.count, &tp.tile_runs, &tblocks);
 #define WM_TILE_RAGGED(RPS) \
-    hipLaunchKernelGGL((step_tile_kernel<IdxT, OPT, RPS, false, float, 0, 0, 16, true>), dim3(tblocks), dim3(kBlock), 0, stream, tp)
+    hipLaunchKernelGGL((step_tile_kernel<IdxT, OPT, RPS, false, float, 16, true>), dim3(tblocks), dim3(kBlock), 0, stream, tp)
     if (vecs > 32) WM_TILE_RAGGED(1);
     else if (vecs > 16) WM_TILE_RAGGED(2);
     else if (vecs > 8) WM_TILE_RAGGED(4);
     else WM_TILE_RAGGED(8);
 #undef WM_TILE_RAGGED
-    if (p.detached_side == 1 && long_side() != 0) return -2;
+    if (p.detached_side && long_side() != 0) return -2;
     return hipGetLastError() == hipSuccess ? 0 : -2;
   }
-  const bool tile8_off = WM_AB_KNOB("WM_STEP_TILE8") != nullptr && WM_AB_KNOB("WM_STEP_TILE8")[0] == '0';
-  const bool tile8_ok  = !tile_off && !tile8_off && !cached && vec2 && p.a.dim >= 66 && p.a.table_stride % 2 == 0 &&
+  const bool tile8_ok  = !cached && vec2 && p.a.dim >= 66 && p.a.table_stride % 2 == 0 &&
                         reinterpret_cast<uint64_t>(p.a.local_table) % 8 == 0 &&
                         (p.a.per_element_state == nullptr ||
                          (p.a.per_element_stride % 2 == 0 && reinterpret_cast<uint64_t>(p.a.per_element_state) % 8 == 0));
   if (tile8_ok) {
     opt_params tp = p;
     int tblocks   = 1;
-    constexpr int kKu = OPT == WHOLEMEMORY_OPT_SGD ? WM_TILE_KU_SGD : WM_TILE_KU_STATE;
-    tile_launch_shape(p.a.count, static_cast<int>(p.a.dim / 2), kKu, &tp.tile_runs, &tblocks);   // (> 32 pieces: one row per wave step)
-    hipLaunchKernelGGL((step_tile_kernel<IdxT, OPT, 1, false, float, 0, 0, 8>), dim3(tblocks), dim3(kBlock), 0, stream, tp);
-    if (p.detached_side == 1 && long_side() != 0) return -2;
+    tile_launch_shape(p.a.count, &tp.tile_runs, &tblocks);   // (dim >= 66: > 32 pieces, one row per wave step)
+    hipLaunchKernelGGL((step_tile_kernel<IdxT, OPT, 1, false, float, 8>), dim3(tblocks), dim3(kBlock), 0, stream, tp);
+    if (p.detached_side && long_side() != 0) return -2;
     return hipGetLastError() == hipSuccess ? 0 : -2;
   }
   if (vec2 && !cached)
@@ -2426,7 +2354,7 @@ int launch_step_opt(const opt_params& p, int blocks, hipStream_t stream, hipStre
     hipLaunchKernelGGL((step_short_kernel<IdxT, OPT, 1, float, false>), dim3(blocks), dim3(kBlock), 0, stream, p);
   else
     hipLaunchKernelGGL((step_short_kernel<IdxT, OPT, 1, float, true>), dim3(blocks), dim3(kBlock), 0, stream, p);
-  if (p.detached_side == 1 && long_side() != 0) return -2;
+  if (p.detached_side && long_side() != 0) return -2;
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -2458,17 +2386,16 @@ int launch_step_sgd16(opt_params p, int blocks, hipStream_t stream, hipStream_t 
     }
     return 0;
   };
-  if (p.detached_side != 1 && long_side() != 0) return -2;
+  if (!p.detached_side && long_side() != 0) return -2;
   const bool cached = p.a.cache_slot_of != nullptr;
   // rows of whole 16-byte pieces (8 elements) on every side: the tile kernel, as for fp32 tables
-  const bool tile_off = WM_AB_KNOB("WM_STEP_TILE") != nullptr && WM_AB_KNOB("WM_STEP_TILE")[0] == '0';
-  const bool tile_ok = !tile_off && rows16 && p.a.dim >= 64 && p.a.table_stride % 8 == 0 &&
+  const bool tile_ok = rows16 && p.a.dim >= 64 && p.a.table_stride % 8 == 0 &&
                        reinterpret_cast<uint64_t>(p.a.local_table) % 16 == 0 &&
                        (!cached || (p.a.cache_row_elems % 8 == 0 && reinterpret_cast<uint64_t>(p.a.cache_data) % 16 == 0));
   if (tile_ok) {
     const int vecs = static_cast<int>(p.a.dim / 8);
     int tblocks    = 1;
-    tile_launch_shape(p.a.count, vecs, WM_TILE_KU_STATE, &p.tile_runs, &tblocks);
+    tile_launch_shape(p.a.count, &p.tile_runs, &tblocks);
 #define WM_TILE16(RPS)                                                                                                       \
   do {                                                                                                                       \
     if (cached)                                                                                                              \
@@ -2481,7 +2408,7 @@ int launch_step_sgd16(opt_params p, int blocks, hipStream_t stream, hipStream_t 
     else if (vecs > 8) WM_TILE16(4);
     else WM_TILE16(8);
 #undef WM_TILE16
-    if (p.detached_side == 1 && long_side() != 0) return -2;
+    if (p.detached_side && long_side() != 0) return -2;
     return hipGetLastError() == hipSuccess ? 0 : -2;
   }
   if (vec4 && !cached)
@@ -2492,7 +2419,7 @@ int launch_step_sgd16(opt_params p, int blocks, hipStream_t stream, hipStream_t 
     hipLaunchKernelGGL((step_short_kernel<IdxT, kOpt, 1, T, false>), dim3(blocks), dim3(kBlock), 0, stream, p);
   else
     hipLaunchKernelGGL((step_short_kernel<IdxT, kOpt, 1, T, true>), dim3(blocks), dim3(kBlock), 0, stream, p);
-  if (p.detached_side == 1 && long_side() != 0) return -2;
+  if (p.detached_side && long_side() != 0) return -2;
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
@@ -2544,7 +2471,6 @@ __global__ void fill_float_kernel(float* p, float v, int64_t n)
 
 }  // namespace wm
 extern "C" int64_t wholememory_ext_split_sorts(void) { return wm::g_split_sorts.load(std::memory_order_relaxed); }
-extern "C" int64_t wholememory_ext_hot_split_sorts(void) { return wm::g_hot_split_sorts.load(std::memory_order_relaxed); }
 // runs of the last finished ORDERED optimizer step on the current device that were folded through a dense transposed copy
 // (kernels/long_dense.cuh); read after a synchronise. A counter for tests and benchmarks.
 extern "C" int64_t wholememory_ext_dense_fold_last(void)
@@ -2725,7 +2651,7 @@ size_t hip_long_run_ws_bytes(int64_t n_recv, int64_t dim)
     expect = long_lane::get().expect_long();
   }
   const size_t ordered = expect ? dense_layout(ordered_list_bytes(n_recv), n_recv, dim).total : ordered_list_bytes(n_recv);
-  return std::max(ordered, tree_ws_bytes(n_recv, dim, std::min(tree_threshold(), kTreeMin)));
+  return std::max(ordered, tree_ws_bytes(n_recv, dim, kTreeMin));
 }
 
 // a->count is an UPPER BOUND for the launch geometry; the true run count is read on the device from
@@ -2748,9 +2674,9 @@ int hip_optimizer_step_dev(const wm_optimizer_args* a, const int64_t* n_unique_d
                         (a->self_grads == nullptr || a->self_grad_stride % ve == 0);
     if (resolve_fold_mode(*a) == 1 && pieces && a->count < (INT64_C(1) << 31)) {
       p.fold_tree      = 1;
-      p.long_threshold = tree_threshold();
+      p.long_threshold = kTreeMin;
       p.long_list      = reinterpret_cast<long_run_entry*>(static_cast<char*>(a->long_run_ws) + 64);   // (non-null marker; the tree kernels carve the workspace themselves)
-    } else if (f32 && pieces && a->dim <= 256 && WM_AB_KNOB("WM_STEP_LONG_OLD") == nullptr) {
+    } else if (f32 && pieces && a->dim <= 256) {
       // (rows of up to 256 columns: the long-run kernel's one resident round — 256 / (dim / 32) workgroups per 32-column slice —
       // then has 16 per slice to spare for the dense copies, launch_step_opt)
       const dense_carve dc = dense_layout(ordered_list_bytes(a->count), a->count, a->dim);
@@ -2766,8 +2692,7 @@ int hip_optimizer_step_dev(const wm_optimizer_args* a, const int64_t* n_unique_d
   // runs that a split sort of this thread has just written: its control words hold the long-run counters (already zero) and
   // say whether a long run can exist at all (last_split_record)
   if (g_last_split.run_starts == a->run_starts && g_last_split.unique_ids == a->ids && g_last_split.n_unique == n_unique_dev &&
-      n_unique_dev != nullptr && g_last_split.ctl != nullptr && p.long_list != nullptr &&
-      WM_AB_KNOB("WM_STEP_OWN_COUNTERS") == nullptr) {
+      n_unique_dev != nullptr && g_last_split.ctl != nullptr && p.long_list != nullptr) {
     p.split_ctl  = g_last_split.ctl;
     p.long_count = reinterpret_cast<int32_t*>(g_last_split.ctl + split::kCtlLongCounters);
   }
@@ -2790,9 +2715,9 @@ int hip_optimizer_step_dev(const wm_optimizer_args* a, const int64_t* n_unique_d
     sort_lock = std::unique_lock<std::mutex>(sort_lane::get().mu);
     lstream   = sort_lane::get().side();
     detached  = true;
-    // (launch_mark_long_runs / launch_tree queue the waiting wave in front of their first kernel; 1: the side is enqueued
-    // behind the tile kernel, 2 = WM_SIDE_FIRST=1: in front of it, the order of the first version, for A/B runs)
-    p.detached_side = WM_AB_KNOB("WM_SIDE_FIRST") != nullptr && WM_AB_KNOB("WM_SIDE_FIRST")[0] == '1' ? 2 : 1;
+    // (launch_mark_long_runs / launch_tree queue the waiting wave in front of their first kernel; the side is enqueued behind
+    // the tile kernel)
+    p.detached_side = 1;
   }
   if (p.long_list != nullptr && !serial && long_lane::get().fork(stream)) lstream = long_lane::get().stream;
   // (the counters are cleared on the side stream: only the long-run kernels read them)
@@ -2800,9 +2725,7 @@ int hip_optimizer_step_dev(const wm_optimizer_args* a, const int64_t* n_unique_d
       hipMemsetAsync(p.long_count, 0, p.fold_tree ? 64 : 32, lstream) != hipSuccess)
     return -2;
   int64_t waves = a->count;
-  int max_blocks = 256 * 8;
-  if (const char* e = WM_AB_KNOB("WM_STEP_BLOCKS")) max_blocks = std::max(1, atoi(e));
-  int blocks = static_cast<int>(std::min<int64_t>((waves + 3) / 4, max_blocks));
+  int blocks = static_cast<int>(std::min<int64_t>((waves + 3) / 4, 256 * 8));
   if (blocks < 1) blocks = 1;
   int rc = -1;
   if (a->index_dtype == WHOLEMEMORY_DT_INT) rc = launch_step<int32_t>(p, blocks, stream, lstream);

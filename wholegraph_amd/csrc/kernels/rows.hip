@@ -121,7 +121,6 @@ struct rows_params {
   int tile_rows;
   // LDS-staged gather (rows_staged_gather_kernel): rows per chunk (a power of two, chunk bytes a multiple of 16), 0 = not used
   int stage_rows;
-  int stage_align;                 // staged gather: wave stores shifted onto the 128-byte lines of the output (1) or begun with the chunk (0)
   // host side only: threads per workgroup of this launch (a multiple of 64, <= kBlock; the kernels read blockDim)
   int launch_threads;
   // host side only: 32 / 64 / 128 / 256 = this launch takes rows_batch_kernel<..., that many 16-byte pieces per row>
@@ -636,7 +635,7 @@ __global__ __launch_bounds__(kBlock) void rows_staged_gather_kernel(rows_params 
         // ---- LDS -> the contiguous, 16-byte aligned output stream. The lanes are shifted so that every wave store begins on a
         // 128-byte line of the output (the chunk itself begins wherever R rows put it): whole-line writes except at the two
         // ends of the chunk (what writes that begin inside a line cost: profiles/r04_misaligned_rows.txt)
-        const int head = p.stage_align ? __builtin_amdgcn_readfirstlane(static_cast<int>((reinterpret_cast<uint64_t>(out) >> 4) & 7)) : 0;
+        const int head = __builtin_amdgcn_readfirstlane(static_cast<int>((reinterpret_cast<uint64_t>(out) >> 4) & 7));
         for (int v = lane - head; v < chunk_vecs; v += kWave)
           if (v >= 0) st_global_nt<u32x4>(out + v * 16, *reinterpret_cast<const u32x4*>(lds + v * 16));
         __builtin_amdgcn_wave_barrier();                      // the next chunk overwrites the region
@@ -859,10 +858,7 @@ template <typename K>
 inline void launch_rows_kernel(K kernel, int blocks, hipStream_t stream, const rows_params& p)
 {
   t_last_rows_kernel = reinterpret_cast<const void*>(kernel);
-  // WM_ROWS_LDS=bytes (experiments): dynamic LDS nobody uses, to cap the workgroups resident per CU
-  const char* le   = WM_AB_KNOB("WM_ROWS_LDS");
-  const size_t lds = le != nullptr ? static_cast<size_t>(atoi(le)) : 0;
-  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(p.launch_threads), lds, stream, p);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(p.launch_threads), 0, stream, p);
 }
 
 // rank = off / chunk_stride as multiply-high + shift (Granlund / Montgomery, dividends below 2^63): with l = ceil(log2 d)
@@ -934,21 +930,14 @@ int inorder_setting()
   const char* e = WM_KNOB("WM_ROWS_INORDER");
   return (e == nullptr || e[0] == '\0') ? -1 : (e[0] == '0' ? 0 : 1);
 }
-// threads per workgroup of the in-order launches (WM_ROWS_BLOCK=64 / 128 / 256; measured: 64 and 256 within 1 %, 512 and
-// 1024 5-12 % slower — the finer the unit the dispatcher hands out, the tighter the window)
-int inorder_block_threads()
-{
-  const char* e = WM_AB_KNOB("WM_ROWS_BLOCK");
-  const int v   = e != nullptr ? atoi(e) : 0;
-  return (v == 64 || v == 128 || v == 256) ? v : 256;
-}
+// threads per workgroup of the in-order launches (measured: 64 and 256 within 1 %, 512 and 1024 5-12 % slower — the finer the
+// unit the dispatcher hands out, the tighter the window)
+constexpr int kInorderBlock = 256;
 
 // rows per wave tile of rows_copy_kernel / rows_convert_kernel when they are launched in order: about 4 KiB of the (wider) row
-// side, a power of two between one batch of the kernel (rps x 4 rows) and 64. WM_ROWS_SMALL_TILE=0 keeps 64-row tiles (A/B).
+// side, a power of two between one batch of the kernel (rps x 4 rows) and 64
 int small_tile_rows(int lpr_log2, int64_t row_bytes)
 {
-  const char* e = WM_AB_KNOB("WM_ROWS_SMALL_TILE");
-  if (e != nullptr && e[0] == '0') return kWave;
   const int batch = (kWave >> lpr_log2) * 4;
   int t           = kWave;
   while (t > batch && static_cast<int64_t>(t) * row_bytes > 4096) t >>= 1;
@@ -962,29 +951,15 @@ int flat_override()
   return e == nullptr ? -1 : atoi(e);
 }
 
-// WM_ROWS_STAGED_SCATTER=0 switches the LDS-staged scatter off (A/B: the flat-stream kernel then)
-bool staged_scatter_enabled()
-{
-  const char* e = WM_AB_KNOB("WM_ROWS_STAGED_SCATTER");
-  return e == nullptr || e[0] != '0';
-}
-// longest row the staged kernels take (WM_ROWS_STAGED_MAXROW overrides, A/B)
-int64_t staged_max_row(bool gather)
-{
-  const char* e = WM_AB_KNOB("WM_ROWS_STAGED_MAXROW");
-  if (e != nullptr && atoll(e) > 0) return atoll(e);
-  (void)gather;
-  return 5120;
-}
-// shortest row the staged kernels are tried on (WM_ROWS_STAGED_MINROW overrides, A/B). Measured against rows_copy_kernel
+// longest row the staged kernels take
+constexpr int64_t kStagedMaxRow = 5120;
+// shortest row the staged kernels are tried on. Measured against rows_copy_kernel
 // (profiles/r03_dim_sweep_flat_forced.csv): gather of ragged rows 132 B 29.8 -> 49.5 % of peak, 164 B 34.3 -> 56.5, 200 B
 // 46.8 -> 57.0, 260 B 29.5 -> 58.9, and r03_dim_sweep_staged_small_rows.csv: 36 B 23.4 -> 29.5, 52 B 34.0 -> 45.1, 68 B 28.6 ->
 // 40.2, 100 B 33.8 -> 47.6, 120 B 60.9 -> 70.1; scatter 164 B +3.2, 200 B +4.1, 260 B +8.2 points, 132 B and below equal
 // or -1; rows of whole 16-byte pieces, scatter: 144 B +0.8, 176 B +2.2, 208 B +3.4, 240 B +5.2, 80 B equal.
 bool staged_row_wanted(bool gather, int64_t row_bytes)
 {
-  const char* e = WM_AB_KNOB("WM_ROWS_STAGED_MINROW");
-  if (e != nullptr && atoll(e) > 0) return row_bytes >= atoll(e);
   if (gather) return row_bytes >= 16;
   // (scatter of 64 / 128 / 256 B rows: +1 / +1.2 / +6.6 although 96 B and 112 B lose 1-2: r03_dim_sweep_pow2_small.csv)
   if ((row_bytes & (row_bytes - 1)) == 0 && row_bytes >= 64) return true;
@@ -994,18 +969,9 @@ bool staged_row_wanted(bool gather, int64_t row_bytes)
 // (profiles/r03_dim_sweep_staged_aligned.csv): scatter +1.3 ... +4.3 points on every shape from 400 B to 4000 B, gather mixed
 // (+4.7 at 400 B and 1600 B, -0.9 at 544 B and 1200 B, -6.3 at 4000 B; under 512 B always ahead: 48 B +1.8, 112 B +3.5, 176 B
 // +5.7, 240 B +5.5, 304 B +3.1, r03_dim_sweep_staged_aligned_small.csv) -> yes for the scatter, under 512 B for the gather.
-// WM_ROWS_STAGED_ALIGNED=0 / 1 forces.
 bool staged_aligned_rows(bool gather, int64_t row_bytes)
 {
-  const char* e = WM_AB_KNOB("WM_ROWS_STAGED_ALIGNED");
-  if (e != nullptr && (e[0] == '0' || e[0] == '1')) return e[0] == '1';
   return !gather || row_bytes < 512;
-}
-// WM_ROWS_STAGED=0 switches the LDS-staged gather off (A/B)
-bool staged_enabled()
-{
-  const char* e = WM_AB_KNOB("WM_ROWS_STAGED");
-  return e == nullptr || e[0] != '0';
 }
 
 // flat-stream kernel or the pow-of-two lane mappings? (rule from experiments/dim_sweep.py, see rows_flat_kernel)
@@ -1222,7 +1188,7 @@ int rows_op(const wm_rows_args* a, void* stream_v)
   const int inorder_mode = inorder_setting();
   // (a batch of 2^31 entries or more could need more workgroups than a grid has: the persistent launch loops)
   bool inorder           = a->max_blocks <= 0 && inorder_mode != 0 && a->n < (INT64_C(1) << 31);
-  p.launch_threads       = inorder ? inorder_block_threads() : kBlock;
+  p.launch_threads       = inorder ? kInorderBlock : kBlock;
   p.tile_rows            = kWave;
   auto grid_for = [&](int tile_rows) {
     const int64_t tiles = (a->n + tile_rows - 1) / tile_rows;
@@ -1268,28 +1234,24 @@ int rows_op(const wm_rows_args* a, void* stream_v)
     // chunk. Measured against the flat-stream kernel (same file): scatter 516 B 39.4 -> 46.1 % of peak on a slow box and
     // 49.9 -> 61.0 on a fast one, 1000 B 42.9 -> 55.0, 1204 B 51.9 -> 63.2, 2408 B 51.4 -> 60.0, 4120 B 56.5 -> 58.7; gather
     // 1032 B 52.0 -> 64.1, 2408 B 60.4 -> 66.6, 4120 B 61.8 -> 68.6.
-    if ((GATHER ? staged_enabled() : staged_scatter_enabled()) && p.flat_slots > 0 && (p.flat_tail != 16 || staged_aligned_rows(GATHER, row_bytes)) && (flat || stage_try) &&
+    if (p.flat_slots > 0 && (p.flat_tail != 16 || staged_aligned_rows(GATHER, row_bytes)) && (flat || stage_try) &&
         p.row_map == nullptr &&
         p.plain_stride_bytes == row_bytes &&
         (reinterpret_cast<uint64_t>(p.plain) & 15) == 0 && p.table_stride_bytes % 16 == 0 && p.table_offset_bytes % 16 == 0 &&
         (tab_base & 15) == 0 && a->gref.stride % 16 == 0 && p.table_stride_bytes >= static_cast<int64_t>(p.flat_slots) * 16 &&
-        row_bytes <= staged_max_row(GATHER)) {
+        row_bytes <= kStagedMaxRow) {
       const int need    = row_bytes % 16 == 0 ? 1 : row_bytes % 8 == 0 ? 2 : 4;   // rows per 16-byte-aligned piece of the dense stream
       const int64_t cap = static_cast<int64_t>(need) * row_bytes <= 5120 ? 5120 : 10240;   // 5 or 10 x 1 KiB per wave
       int R             = 64;
       while (R > need && static_cast<int64_t>(R) * row_bytes > cap) R >>= 1;
       if (static_cast<int64_t>(R) * row_bytes <= cap) {   // bigger rows stay on the flat kernel
         p.stage_rows = R;
-        {
-          const char* sa = WM_AB_KNOB("WM_ROWS_STAGED_ALIGN_STORES");
-          p.stage_align  = (sa != nullptr && sa[0] == '0') ? 0 : 1;
-        }
         if (inorder_mode == 0 || a->max_blocks > 0 || a->n >= (INT64_C(1) << 31)) {
           inorder          = false;
           p.launch_threads = kBlock;
         } else {          // in order: one chunk per wave (the flat branch above may have switched it off for the scatter)
           inorder          = true;
-          p.launch_threads = inorder_block_threads();
+          p.launch_threads = kInorderBlock;
         }
         p.tile_rows = inorder ? R : kWave;
         blocks      = grid_for(p.tile_rows);
@@ -1304,8 +1266,6 @@ int rows_op(const wm_rows_args* a, void* stream_v)
       }
     }
     if (p.stage_rows == 0 && (p.flat_slots > 0 || (vb == 16 && p.row_vecs >= 32))) {  // the two kernels that take tile_rows
-      const char* te    = WM_AB_KNOB("WM_ROWS_TILE");  // experiment switch
-      const int forced  = te != nullptr ? atoi(te) : 0;
       p.tile_rows = row_bytes <= 768 ? 64 : row_bytes <= 1536 ? 32 : row_bytes <= 3072 ? 16 : 8;
       if (inorder) {
         if (p.flat_slots > 0) {   // flat stream: a batch is 4 x 64 slots of 16 bytes; the rows that fill one batch, or two when
@@ -1317,26 +1277,22 @@ int rows_op(const wm_rows_args* a, void* stream_v)
           // of 128 bytes and every wave store a whole, aligned 1 KiB of it; with tiles that begin on 32-byte multiples each
           // wave writes two partial lines (4000 B rows on a packed output 64 % against 71 % on an output padded to 4 KiB,
           // profiles/r04_misaligned_rows.txt). Measured: 528 B +2.3, 640 B +2.0, 800 B +2.2, 2000 B +3.0, 4000 B +2.0 points,
-          // 960 / 1200 / 1600 B within +-0.7. (WM_ROWS_FLAT_TILE8=0: the batch-filling rule above, A/B)
-          const char* t8 = WM_AB_KNOB("WM_ROWS_FLAT_TILE8");
-          if (GATHER && vb == 16 && p.row_map == nullptr && !(t8 != nullptr && t8[0] == '0')) p.tile_rows = 8;
+          // 960 / 1200 / 1600 B within +-0.7.
+          if (GATHER && vb == 16 && p.row_map == nullptr) p.tile_rows = 8;
         } else {                  // readlane kernel: (tile_rows / RPS) x chunks steps, a multiple of its 4-step batch
           const int chunks = p.row_vecs > 32 ? (p.row_vecs + kWave - 1) / kWave : 1;
           p.tile_rows      = p.row_vecs == 32 ? 8 : chunks == 1 ? 4 : chunks == 2 ? 2 : chunks % 4 == 0 ? 1 : 4;
-          // 512 B / 1 / 2 / 4 KiB rows: exactly one 4 KiB batch per tile -> the specialised kernel (WM_ROWS_BATCH=0: A/B)
-          const char* be = WM_AB_KNOB("WM_ROWS_BATCH");
+          // 512 B / 1 / 2 / 4 KiB rows: exactly one 4 KiB batch per tile -> the specialised kernel
           // (continuous tables and owner tables by value; plain rows less than 2 GiB apart: 32-bit lane offsets)
-          if ((p.row_vecs == 32 || p.row_vecs == 64 || p.row_vecs == 128 || p.row_vecs == 256) && forced == 0 &&
-              (p.chunk_stride == 0 || p.owners_by_value) && p.plain_stride_bytes < (INT64_C(1) << 31) &&
-              !(be != nullptr && be[0] == '0')) {
+          if ((p.row_vecs == 32 || p.row_vecs == 64 || p.row_vecs == 128 || p.row_vecs == 256) &&
+              (p.chunk_stride == 0 || p.owners_by_value) && p.plain_stride_bytes < (INT64_C(1) << 31)) {
             p.batch_vecs = p.row_vecs;
             // one wave per workgroup for this kernel: the finest unit the dispatcher can hand out (measured against 256
             // threads on 512 B - 4 KiB rows: gather +0.2 ... +1.4 %, scatter +0.5 ... +1 %; the flat kernel loses 2-3 % with it)
-            if (WM_AB_KNOB("WM_ROWS_BLOCK") == nullptr) p.launch_threads = kWave;
+            p.launch_threads = kWave;
           }
         }
       }
-      if ((forced == 8 || forced == 16 || forced == 32 || forced == 64) && (p.flat_slots > 0 || forced % 8 == 0)) p.tile_rows = forced;
       blocks = grid_for(p.tile_rows);
     }
     if (inorder && p.stage_rows == 0 && p.flat_slots == 0 && !(vb == 16 && p.row_vecs >= 32)) {   // rows_copy_kernel

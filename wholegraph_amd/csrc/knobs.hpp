@@ -8,6 +8,8 @@
 // its next use. A reload never frees a value: every (re)load parks its string in a list that lives as long as the process, so a
 // pointer returned to an op on another thread stays valid (advisor, round 4) — that thread simply keeps the old answer until
 // its next look. (A few bytes per reload and variable; reloads are a test / experiment device.)
+// Kernel variants are not switched here: they are compiled in or out with -D (scripts/build_variant.sh), and every WM_KNOB
+// site is live in the shipped build.
 #pragma once
 
 #include <atomic>
@@ -62,12 +64,3 @@ inline void reload_knobs() { g_knob_generation.fetch_add(1, std::memory_order_ac
     return k.str();                        \
   }())
 
-// A/B switches of kernel variants (WM_ROWS_*, WM_TILE_*, WM_STEP_TILE*, WM_SAMPLE_*, ... — what rounds 2-5 used to compare code
-// paths inside one process) are NOT part of the product (round-5 review: ~45 variables, two thirds of them branches in hot
-// launchers): in the shipped build such a site is the constant nullptr and its branch folds away. A variant build
-// (scripts/build_variant.sh NAME "..." with AB=1, or make AB=1) compiles them back in for experiments/*.
-#ifdef WM_AB_KNOBS
-#define WM_AB_KNOB(NAME) WM_KNOB(NAME)
-#else
-#define WM_AB_KNOB(NAME) (static_cast<const char*>(nullptr))
-#endif

@@ -1154,7 +1154,7 @@ wholememory_error_code_t wholememory_gather(wholememory_tensor_t wholememory_ten
   // per setting): 1 M ids 4.81 -> 4.71 ms (53.3 -> 54.4 GB/s of 256-byte rows), 4 M ids of 128-byte rows 12.59 -> 11.86 ms;
   // the sort costs ~60 us whatever the batch (histogram + 3 passes + the expansion), so 100 k ids LOSE 0.06 ms (0.518 -> 0.578):
   // the route starts at WM_HOST_SORTED_MIN ids (default 2^19; the reference sorts every batch). WM_HOST_SORTED_GATHER=0
-  // switches it off. Ignoring the low id bits in the sort (WM_HOST_SORTED_LOW_BIT) buys nothing: 4 bits equal, 8 / 12 slower.
+  // switches it off. Ignoring the low id bits in the sort buys nothing: 4 bits equal, 8 / 12 slower.
   std::unique_ptr<wm::temp_mem> sorted_ids_mem, sorted_raw_mem, sorted_ws_mem;   // (alive until the kernels are queued)
   if (has_handle && p_env_fns != nullptr && wm::backend()->sort_ids != nullptr && wm::host_sorted_gather_min() > 0 &&
       d.indices.size >= wm::host_sorted_gather_min() &&
@@ -1169,7 +1169,7 @@ wholememory_error_code_t wholememory_gather(wholememory_tensor_t wholememory_ten
     int64_t* raw      = static_cast<int64_t*>(sorted_raw_mem->device(n, WHOLEMEMORY_DT_INT64));
     void* ws          = sorted_ws_mem->device(static_cast<int64_t>(bk->sort_ids_workspace_bytes(n)), WHOLEMEMORY_DT_INT8);
     // ids address rows of the VIEW that was passed in (gather_scatter_func.cuh:297-298): its row count bounds the keys
-    const int src = bk->sort_ids(d.indices_ptr, d.indices.dtype, n, d.table.sizes[0], wm::host_sorted_gather_low_bit(), sorted, raw,
+    const int src = bk->sort_ids(d.indices_ptr, d.indices.dtype, n, d.table.sizes[0], /*low_bit=*/0, sorted, raw,
                                  ws, stream);
     if (src == 0) {
       a.indices = sorted;

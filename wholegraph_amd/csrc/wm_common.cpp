@@ -105,12 +105,6 @@ int64_t host_sorted_gather_min()
   return e != nullptr && atoll(e) > 0 ? static_cast<int64_t>(atoll(e)) : static_cast<int64_t>(1) << 19;
 }
 
-int host_sorted_gather_low_bit()
-{
-  const char* e = WM_AB_KNOB("WM_HOST_SORTED_LOW_BIT");
-  return e != nullptr && atoi(e) > 0 ? atoi(e) : 0;
-}
-
 }  // namespace wm
 
 extern "C" wholememory_error_code_t wholememory_ext_reload_knobs()

@@ -57,9 +57,8 @@ bool debug_sync_enabled();
 void set_async_completion(bool on);
 bool async_completion_enabled();
 // sorted-ids gather of HOST tables (ops.cpp: wholememory_gather): smallest batch that takes it (0: route off,
-// WM_HOST_SORTED_GATHER=0 / WM_HOST_SORTED_MIN) and the lowest id bit the sort looks at (WM_HOST_SORTED_LOW_BIT)
+// WM_HOST_SORTED_GATHER=0 / WM_HOST_SORTED_MIN)
 int64_t host_sorted_gather_min();
-int host_sorted_gather_low_bit();
 
 }  // namespace wm
 

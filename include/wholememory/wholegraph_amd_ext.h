@@ -11,6 +11,8 @@
  *      through the C ABI.
  *      (2b) the neighbour aggregation of a sampled CSC block behind the GraphSAGE layer (forward and a deterministic
  *      backward).
+ *      (2c) the multi-head graph attention of a sampled CSC block behind the GAT layer (forward and a deterministic
+ *      backward).
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -294,6 +296,83 @@ enum wholememory_error_code_t wholememory_ext_csc_aggregate_backward(const int32
                                                                      void* stream);
 /* C of the backward's chunked sums (a compile-time constant of the library) */
 int64_t wholememory_ext_csc_aggregate_chunk_edges(void);
+
+/* ---- (2c) multi-head graph attention of a sampled CSC block (GAT `mha_gat_n2n`) ------------------------------ */
+/* The block as for (2b): row_ptr int32 [n_dst + 1], col_ind int32 [n_edges] in [0, n_src), h fp32 [n_src, h_stride] with
+ * H * F columns used (H = heads, F = dim; the layer's lin(x)), whose first n_dst rows are the targets. Head k owns the
+ * columns [k*F, (k+1)*F) of a row. att fp32 [2 * H * F], viewed as (2, H, F): half 0 is the source (neighbour) side, half 1
+ * the target side (cugraph-ops' layout). Strides in elements, all arrays DEVICE memory, all work queued on `stream`.
+ * Every `*` and `+` below is one fp32 operation, rounded on its own (no fused multiply-add). A sum "left to right" starts
+ * from its first term; a sum with no term is +0.0.
+ *
+ * forward: writes scores [n_src + n_dst, H] (s_src then s_dst), alpha [n_edges, H] and out, all of which the backward
+ * reads back.
+ *   s_src[j,k] = sum over f of att[0,k,f] * h[j,k,f], left to right (j < n_src); s_dst[d,k] the same with att[1] (d < n_dst).
+ *   For each edge e of target d (e = row_ptr[d] .. row_ptr[d+1] - 1): z = s_src[col_ind[e],k] + s_dst[d,k],
+ *   l = z > 0 ? z : negative_slope * z. m = max of l over the edges of d; w = expf(l - m) (the device's expf);
+ *   den = sum of w over the edges of d, left to right; alpha[e,k] = w / den.
+ *   o[d,k,:] = sum of alpha[e,k] * h[col_ind[e],k,:] over the edges of d, left to right; +0.0 for a target without edges.
+ *   concat != 0: out [n_dst, out_stride >= H*F] = o. concat == 0: out [n_dst, out_stride >= F] =
+ *   ((o[d,0,:] + o[d,1,:]) + ...) * fl(1.0f / H).
+ * backward: grad_out G [n_dst, grad_out_stride] (H*F columns with concat, else F) -> grad_h [n_src, grad_h_stride >= H*F]
+ * (every row written) and grad_att [2*H*F].
+ *   G_k[d,f] = G[d, k*F + f] with concat, else G[d,f] * fl(1.0f / H).
+ *   da[e,k] = sum over f of G_k[d,f] * h[col_ind[e],k,f], left to right. c[d,k] = sum of alpha[e,k] * da[e,k] over the
+ *   edges of d, left to right. dl = alpha * (da - c); dz = z > 0 ? dl : dl * negative_slope (z recomputed from scores).
+ *   ds_dst[d,k] = sum of dz over the edges of d, left to right.
+ *   Per source j, over the edges with col_ind[e] = j in ascending edge position: P(j)[k,:] = sum of alpha[e,k] * G_k[d(e),:]
+ *   and ds_src[j,k] = sum of dz[e,k]; left to right when j has at most C edges, otherwise cut into consecutive chunks of C
+ *   edges, each chunk summed left to right and the chunk sums added in chunk order. C =
+ *   wholememory_ext_csc_aggregate_chunk_edges().
+ *   grad_h[j,k,:] = (P(j)[k,:] + ds_src[j,k] * att[0,k,:]) + ds_dst[j,k] * att[1,k,:], the last term only for j < n_dst.
+ *   grad_att[0,k,f] = sum over j < n_src of ds_src[j,k] * h[j,k,f]; grad_att[1,k,f] the same over j < n_dst with ds_dst.
+ *   Both are cut into node chunks of N = wholememory_ext_csc_gat_node_chunk() rows from row 0: each chunk summed left to
+ *   right, the chunk sums added in chunk order.
+ *   The order is fixed: results are bitwise reproducible, no atomics. The edge index is built with the library's id sort,
+ *   scratch from p_env_fns.
+ * n_edges = 0 and n_dst = 0 are valid. INVALID_INPUT for null pointers, negative sizes, heads < 1, dim < 1, n_dst > n_src,
+ * strides smaller than the row; NOT_SUPPORTED (nothing queued) when the device backend has no such kernels. */
+enum wholememory_error_code_t wholememory_ext_csc_gat_forward(const int32_t* row_ptr,
+                                                              const int32_t* col_ind,
+                                                              int64_t n_edges,
+                                                              int64_t n_dst,
+                                                              int64_t n_src,
+                                                              const float* h,
+                                                              int64_t h_stride,
+                                                              const float* att,
+                                                              int64_t heads,
+                                                              int64_t dim,
+                                                              float negative_slope,
+                                                              int concat,
+                                                              float* out,
+                                                              int64_t out_stride,
+                                                              float* alpha,
+                                                              float* scores,
+                                                              struct wholememory_env_func_t* p_env_fns,
+                                                              void* stream);
+enum wholememory_error_code_t wholememory_ext_csc_gat_backward(const int32_t* row_ptr,
+                                                               const int32_t* col_ind,
+                                                               int64_t n_edges,
+                                                               int64_t n_dst,
+                                                               int64_t n_src,
+                                                               const float* h,
+                                                               int64_t h_stride,
+                                                               const float* att,
+                                                               int64_t heads,
+                                                               int64_t dim,
+                                                               float negative_slope,
+                                                               int concat,
+                                                               const float* alpha,
+                                                               const float* scores,
+                                                               const float* grad_out,
+                                                               int64_t grad_out_stride,
+                                                               float* grad_h,
+                                                               int64_t grad_h_stride,
+                                                               float* grad_att,
+                                                               struct wholememory_env_func_t* p_env_fns,
+                                                               void* stream);
+/* N of the backward's grad_att node chunks (a compile-time constant of the library) */
+int64_t wholememory_ext_csc_gat_node_chunk(void);
 
 /* ---- (3) testing seam ---------------------------------------------------------------------- */
 /* Replaces the device backend. Refuses (WHOLEMEMORY_NOT_SUPPORTED) unless the environment has

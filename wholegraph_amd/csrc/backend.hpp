@@ -189,6 +189,28 @@ struct wm_agg_args {
   int64_t out_stride;
 };
 
+// multi-head graph attention of a sampled CSC block (kernels/gat.hip, the GAT `mha_gat_n2n` op): rows / strides in
+// ELEMENTS (fp32); head k owns columns [k * dim, (k + 1) * dim) of a row of h
+struct wm_gat_args {
+  const int32_t* row_ptr;   // [n_dst + 1]
+  const int32_t* col_ind;   // [n_edges], ids in [0, n_src)
+  int64_t n_edges, n_dst, n_src, heads, dim;
+  float slope;              // LeakyReLU negative slope
+  int concat;               // 1: out [n_dst, heads * dim]; 0: the mean over heads, [n_dst, dim]
+  const float* h;           // [n_src, h_stride], heads * dim columns used
+  int64_t h_stride;
+  const float* att;         // [2, heads, dim]: half 0 the source side, half 1 the target side
+  float* alpha;             // [n_edges, heads]: written by the forward, read by the backward
+  float* scores;            // [n_src + n_dst, heads]: s_src then s_dst; written by the forward, read by the backward
+  float* out;               // forward: [n_dst, out_stride]
+  int64_t out_stride;
+  const float* grad;        // backward: dL/dout [n_dst, grad_stride]
+  int64_t grad_stride;
+  float* grad_h;            // backward: [n_src, grad_h_stride]
+  int64_t grad_h_stride;
+  float* grad_att;          // backward: [2 * heads * dim]
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -380,6 +402,16 @@ struct wm_device_backend {
   size_t (*agg_backward_workspace_bytes)(int64_t n_edges, int64_t n_src, int64_t dim);
   int (*agg_backward)(const wm_agg_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
                       const int64_t* n_unique_dev, void* workspace, void* stream);
+  // ---- multi-head graph attention of a sampled CSC block (kernels/gat.hip); nullptr in a backend without it ----
+  // forward: node scores, alpha and out (the order of every sum: wholegraph_amd_ext.h, section 2c); workspace of
+  // gat_forward_workspace_bytes (the per-head rows before the mean over heads)
+  size_t (*gat_forward_workspace_bytes)(const wm_gat_args* a);
+  int (*gat_forward)(const wm_gat_args* a, void* workspace, void* stream);
+  // backward: grad_h and grad_att from dL/dout, alpha and the scores of the forward. order / run_starts / unique_ids /
+  // n_unique_dev as for agg_backward; workspace of gat_backward_workspace_bytes
+  size_t (*gat_backward_workspace_bytes)(const wm_gat_args* a);
+  int (*gat_backward)(const wm_gat_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                      const int64_t* n_unique_dev, void* workspace, void* stream);
 };
 
 }  // extern "C"
@@ -387,6 +419,8 @@ struct wm_device_backend {
 namespace wm {
 // edges per chunk of the aggregation backward's sums (backend.hpp: agg_backward; wholememory_ext_csc_aggregate_chunk_edges)
 constexpr int64_t kAggChunkEdges = 512;
+// nodes per chunk of the GAT backward's grad_att sums (wholememory_ext_csc_gat_node_chunk)
+constexpr int64_t kGatNodeChunk = 1024;
 
 // Host copies of a chunked handle's per-rank tables, keyed by the DEVICE pointer array its gref carries (gref.pointer).
 // memory_handle.cpp registers them when it uploads the device arrays; the row kernels of a table of up to

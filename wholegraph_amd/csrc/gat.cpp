@@ -1,0 +1,142 @@
+// wholegraph_amd — host side of the multi-head graph attention of a sampled CSC block (wholegraph_amd_ext.h, section 2c):
+// validation, scratch, the edge index of the backward (the library's id sort over col_ind) and the launches of
+// kernels/gat.hip. The semantics, and the one order of every fp32 sum, are stated in the header.
+#include <wholememory/wholegraph_amd_ext.h>
+
+#include "ops_internal.hpp"
+
+namespace {
+
+using namespace wm;
+
+#define WM_BK(call)                                                                      \
+  do {                                                                                   \
+    int rc__ = (call);                                                                   \
+    if (rc__ != 0) throw wm::hip_error(wm::format_string("%s failed: %d", #call, rc__)); \
+  } while (0)
+
+void check_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src,
+                const float* h, int64_t h_stride, const float* att, int64_t heads, int64_t dim, const float* alpha,
+                const float* scores)
+{
+  auto bad = [](const char* what) { throw invalid_input(what); };
+  if (n_edges < 0 || n_dst < 0 || n_src < 0) bad("negative size");
+  if (heads < 1) bad("heads must be >= 1");
+  if (dim < 1) bad("dim must be >= 1");
+  if (n_dst > n_src) bad("n_dst > n_src: the targets are the first rows of h");
+  if (row_ptr == nullptr) bad("row_ptr is null");
+  if (n_edges > 0 && n_dst > 0 && col_ind == nullptr) bad("col_ind is null");
+  if (n_src > 0 && h == nullptr) bad("h is null");
+  if (att == nullptr) bad("att is null");
+  if (n_edges > 0 && n_dst > 0 && alpha == nullptr) bad("alpha is null");
+  if (n_src > 0 && scores == nullptr) bad("scores is null");
+  if (h_stride < heads * dim) bad("h stride smaller than its row");
+  if (n_edges >= (int64_t(1) << 31) || n_src >= (int64_t(1) << 31)) bad("more than 2^31 - 1 edges or rows");
+  if (heads * dim >= (int64_t(1) << 31)) bad("heads * dim too large");
+}
+
+wm_gat_args make_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src,
+                      const float* h, int64_t h_stride, const float* att, int64_t heads, int64_t dim, float slope,
+                      int concat, const float* alpha, const float* scores)
+{
+  wm_gat_args a{};
+  a.row_ptr  = row_ptr;
+  a.col_ind  = col_ind;
+  a.n_edges  = n_dst == 0 ? 0 : n_edges;   // (no target, no edge of any target)
+  a.n_dst    = n_dst;
+  a.n_src    = n_src;
+  a.heads    = heads;
+  a.dim      = dim;
+  a.slope    = slope;
+  a.concat   = concat ? 1 : 0;
+  a.h        = h;
+  a.h_stride = h_stride;
+  a.att      = att;
+  a.alpha    = const_cast<float*>(alpha);    // (written by the forward only)
+  a.scores   = const_cast<float*>(scores);   // (written by the forward only)
+  return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+wholememory_error_code_t wholememory_ext_csc_gat_forward(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges,
+                                                         int64_t n_dst, int64_t n_src, const float* h, int64_t h_stride,
+                                                         const float* att, int64_t heads, int64_t dim, float negative_slope,
+                                                         int concat, float* out, int64_t out_stride, float* alpha,
+                                                         float* scores, wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  const auto* bk = backend();
+  if (bk->gat_forward == nullptr || bk->gat_forward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, h, h_stride, att, heads, dim, alpha, scores);
+  if (n_dst > 0 && out == nullptr) throw invalid_input("out is null");
+  if (out_stride < (concat ? heads * dim : dim)) throw invalid_input("out stride smaller than its row");
+  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
+  wm_gat_args a = make_args(row_ptr, col_ind, n_edges, n_dst, n_src, h, h_stride, att, heads, dim, negative_slope, concat,
+                            alpha, scores);
+  a.out         = out;
+  a.out_stride  = out_stride;
+  temp_mem ws(p_env_fns);
+  const size_t wb = bk->gat_forward_workspace_bytes(&a);
+  void* d_ws      = wb > 0 ? ws.device(static_cast<int64_t>(wb), WHOLEMEMORY_DT_INT8) : nullptr;
+  WM_BK(bk->gat_forward(&a, d_ws, stream));
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+wholememory_error_code_t wholememory_ext_csc_gat_backward(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges,
+                                                          int64_t n_dst, int64_t n_src, const float* h, int64_t h_stride,
+                                                          const float* att, int64_t heads, int64_t dim,
+                                                          float negative_slope, int concat, const float* alpha,
+                                                          const float* scores, const float* grad_out,
+                                                          int64_t grad_out_stride, float* grad_h, int64_t grad_h_stride,
+                                                          float* grad_att, wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  const auto* bk = backend();
+  if (bk->gat_backward == nullptr || bk->gat_backward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, h, h_stride, att, heads, dim, alpha, scores);
+  if (n_dst > 0 && grad_out == nullptr) throw invalid_input("grad_out is null");
+  if (grad_out_stride < (concat ? heads * dim : dim)) throw invalid_input("grad_out stride smaller than its row");
+  if (n_src > 0 && grad_h == nullptr) throw invalid_input("grad_h is null");
+  if (grad_h_stride < heads * dim) throw invalid_input("grad_h stride smaller than its row");
+  if (grad_att == nullptr) throw invalid_input("grad_att is null");
+  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
+  wm_gat_args a   = make_args(row_ptr, col_ind, n_edges, n_dst, n_src, h, h_stride, att, heads, dim, negative_slope, concat,
+                              alpha, scores);
+  a.grad          = grad_out;
+  a.grad_stride   = grad_out_stride;
+  a.grad_h        = grad_h;
+  a.grad_h_stride = grad_h_stride;
+  a.grad_att      = grad_att;
+  const int64_t E = a.n_edges;
+  // the edge index: a stable sort of col_ind (runs of one source, edge positions ascending in each run). dedup_ids joins
+  // any side stream of its own before it returns (no deferred join asked for), so its outputs are ready for the kernels
+  // queued behind it on `stream`
+  temp_mem unique_mem(p_env_fns), starts_mem(p_env_fns), order_mem(p_env_fns), nu_mem(p_env_fns), sort_ws(p_env_fns),
+    gat_ws(p_env_fns);
+  int32_t *d_unique = nullptr, *d_starts = nullptr, *d_order = nullptr;
+  int64_t* d_nu     = nullptr;
+  if (n_src > 0) {
+    d_unique    = static_cast<int32_t*>(unique_mem.device(E, WHOLEMEMORY_DT_INT));
+    d_starts    = static_cast<int32_t*>(starts_mem.device(E + 1, WHOLEMEMORY_DT_INT));
+    d_order     = static_cast<int32_t*>(order_mem.device(E, WHOLEMEMORY_DT_INT));
+    d_nu        = static_cast<int64_t*>(nu_mem.device(1, WHOLEMEMORY_DT_INT64));
+    void* d_sws = sort_ws.device(static_cast<int64_t>(bk->dedup_workspace_bytes(E, WHOLEMEMORY_DT_INT)), WHOLEMEMORY_DT_INT8);
+    if (bk->device_error != nullptr && bk->device_error() != 0)
+      throw hip_error("an earlier id sort reported a device-side timeout (see the ERROR line above)");
+    const int rc = bk->dedup_ids(col_ind, WHOLEMEMORY_DT_INT, E, n_src, 0, d_unique, d_starts, d_order, d_nu, d_sws, stream);
+    if (rc == -1) throw logic_error("dedup_ids: unsupported index dtype or more than 2^31 edges");
+    if (rc != 0) throw hip_error("dedup_ids failed");
+  }
+  void* d_gws = gat_ws.device(static_cast<int64_t>(bk->gat_backward_workspace_bytes(&a)), WHOLEMEMORY_DT_INT8);
+  WM_BK(bk->gat_backward(&a, d_order, d_starts, d_unique, d_nu, d_gws, stream));
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+int64_t wholememory_ext_csc_gat_node_chunk(void) { return wm::kGatNodeChunk; }
+
+}  // extern "C"

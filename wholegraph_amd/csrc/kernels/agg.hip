@@ -21,13 +21,10 @@
 #include <stdint.h>
 
 #include "../backend.hpp"
+#include "agg_common.cuh"
 
 namespace wm {
 namespace {
-
-constexpr int kAggBlock = 256;
-constexpr int kAggBatch = 8;   // neighbour rows in flight per lane
-constexpr int64_t kAggMaxBlocks = 1 << 20;
 
 // backward scratch: the id sort's outputs and this op's workspace (hip_agg_backward carves it)
 struct wm_agg_bwd_state {
@@ -40,70 +37,6 @@ struct wm_agg_bwd_state {
   float* partial;              // [n_tiles, partial_stride]
   int64_t n_tiles, partial_stride;
 };
-
-template <int VEC>
-struct fvec {
-  float v[VEC];
-};
-
-template <int VEC>
-__device__ __forceinline__ fvec<VEC> ldv(const float* p)
-{
-  fvec<VEC> r;
-  if constexpr (VEC == 4) {
-    const float4 t = *reinterpret_cast<const float4*>(p);
-    r.v[0] = t.x, r.v[1] = t.y, r.v[2] = t.z, r.v[3] = t.w;
-  } else {
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) r.v[i] = p[i];
-  }
-  return r;
-}
-
-template <int VEC>
-__device__ __forceinline__ void stv(float* p, const fvec<VEC>& a)
-{
-  if constexpr (VEC == 4) {
-    *reinterpret_cast<float4*>(p) = make_float4(a.v[0], a.v[1], a.v[2], a.v[3]);
-  } else {
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) p[i] = a.v[i];
-  }
-}
-
-template <int VEC>
-__device__ __forceinline__ fvec<VEC> splat(float s)
-{
-  fvec<VEC> r;
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) r.v[i] = s;
-  return r;
-}
-
-template <int VEC>
-__device__ __forceinline__ void add_to(fvec<VEC>& acc, const fvec<VEC>& b)
-{
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) acc.v[i] = acc.v[i] + b.v[i];
-}
-
-template <int VEC>
-__device__ __forceinline__ fvec<VEC> scaled(const fvec<VEC>& a, float s)
-{
-  fvec<VEC> r;
-#pragma unroll
-  for (int i = 0; i < VEC; ++i) r.v[i] = a.v[i] * s;
-  return r;
-}
-
-// edges of target d, clamped to [0, n_edges) so that an inconsistent row_ptr cannot send a load out of col_ind
-__device__ __forceinline__ void edge_range(const int32_t* row_ptr, int64_t d, int64_t n_edges, int64_t& e0, int64_t& e1)
-{
-  int64_t a = row_ptr[d], b = row_ptr[d + 1];
-  a  = a < 0 ? 0 : (a > n_edges ? n_edges : a);
-  b  = b < a ? a : (b > n_edges ? n_edges : b);
-  e0 = a, e1 = b;
-}
 
 // -0.0 is the identity of IEEE addition: acc = -0.0 followed by acc + t_0 + t_1 + ... is the left-to-right sum that starts
 // from the first term (also when that term is -0.0)
@@ -186,44 +119,22 @@ __global__ __launch_bounds__(kAggBlock) void agg_bwd_prep_kernel(wm_agg_args p, 
 {
   const int64_t nu = *b.n_unique;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < p.n_edges;
-       i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-    const int64_t pos = b.order[i];
-    int64_t lo = 0, hi = p.n_dst;   // the last d in [0, n_dst) with row_ptr[d] <= pos
-    while (hi - lo > 1) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (p.row_ptr[mid] <= pos) lo = mid;
-      else hi = mid;
-    }
-    b.sorted_dst[i] = static_cast<int32_t>(lo);
-    if (i < nu) b.run_of[b.unique_ids[i]] = static_cast<int32_t>(i);
-  }
+       i += static_cast<int64_t>(gridDim.x) * blockDim.x)
+    bwd_prep_at(i, p.row_ptr, p.n_dst, b.order, b.unique_ids, nu, b.sorted_dst, b.run_of);
 }
 
 template <int VEC, int LANES>
 __global__ __launch_bounds__(kAggBlock) void agg_bwd_chunk_kernel(wm_agg_args p, wm_agg_bwd_state b)
 {
   constexpr int kGroups = kAggBlock / LANES;
-  constexpr int64_t C   = kAggChunkEdges;
   const int gl          = threadIdx.x % LANES;
   const int64_t F       = p.dim;
   const int64_t nu      = *b.n_unique;
   if (nu == 0) return;
-  const int64_t covered = b.run_starts[nu];   // sorted positions that belong to runs (ids out of range sort behind them)
   for (int64_t t = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; t < b.n_tiles;
        t += static_cast<int64_t>(gridDim.x) * kGroups) {
-    const int64_t pos0 = t * C;
-    if (pos0 >= covered) continue;
-    int64_t lo = 0, hi = nu;   // the run that covers pos0: last u with run_starts[u] <= pos0
-    while (hi - lo > 1) {
-      const int64_t mid = (lo + hi) >> 1;
-      if (b.run_starts[mid] <= pos0) lo = mid;
-      else hi = mid;
-    }
-    const int64_t s0 = b.run_starts[lo], s1 = b.run_starts[lo + 1];
-    const int64_t k  = (pos0 - s0 + C - 1) / C;
-    const int64_t cs = s0 + k * C;
-    if (k < 1 || cs >= s1 || cs >= pos0 + C) continue;   // no chunk k >= 1 starts in this tile
-    const int64_t ce = cs + C < s1 ? cs + C : s1;
+    int64_t cs, ce;
+    if (!chunk_in_tile(t, b.run_starts, nu, cs, ce)) continue;
     for (int64_t cb = 0; cb < F; cb += LANES * VEC) {
       const int64_t c  = cb + gl * VEC;
       const bool act   = c < F;
@@ -284,37 +195,6 @@ __global__ __launch_bounds__(kAggBlock) void agg_bwd_fold_kernel(wm_agg_args p, 
     }
   }
 }
-
-int rc_last() { return hipGetLastError() == hipSuccess ? 0 : -2; }
-
-int blocks_for(int64_t groups, int groups_per_block)
-{
-  int64_t n = (groups + groups_per_block - 1) / groups_per_block;
-  if (n < 1) n = 1;
-  return static_cast<int>(n < kAggMaxBlocks ? n : kAggMaxBlocks);
-}
-
-// 16-byte pieces when every row start is 16-byte aligned; group width from the number of pieces (or floats) of a row
-bool use_vec4(int64_t dim, const void* a, int64_t a_stride, const void* b, int64_t b_stride)
-{
-  return dim % 4 == 0 && a_stride % 4 == 0 && b_stride % 4 == 0 && reinterpret_cast<uintptr_t>(a) % 16 == 0 &&
-         reinterpret_cast<uintptr_t>(b) % 16 == 0;
-}
-int lanes_for(int64_t pieces) { return pieces <= 16 ? 16 : (pieces <= 32 ? 32 : 64); }
-
-#define WM_AGG_DISPATCH(VEC_, PIECES_, LAUNCH_)                          \
-  do {                                                                   \
-    const int lanes__ = lanes_for(PIECES_);                              \
-    if (VEC_) {                                                          \
-      if (lanes__ == 16) LAUNCH_(4, 16);                                 \
-      else if (lanes__ == 32) LAUNCH_(4, 32);                            \
-      else LAUNCH_(4, 64);                                               \
-    } else {                                                             \
-      if (lanes__ == 16) LAUNCH_(1, 16);                                 \
-      else if (lanes__ == 32) LAUNCH_(1, 32);                            \
-      else LAUNCH_(1, 64);                                               \
-    }                                                                    \
-  } while (0)
 
 }  // namespace
 

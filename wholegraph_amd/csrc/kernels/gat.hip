@@ -1,0 +1,483 @@
+// wholegraph_amd — multi-head graph attention over a sampled CSC block (the GAT `mha_gat_n2n` op) on gfx950.
+// The semantics and the one order of every fp32 sum: wholegraph_amd_ext.h, section 2c. H heads of F columns; head k owns
+// columns [k*F, (k+1)*F) of a row of h. s_src / s_dst are the node scores, z = s_src[col[e]] + s_dst[d], l = LeakyReLU(z).
+//
+// Forward:
+//   gat_score_kernel: one thread per (node, head): s_src[j,k] = att[0,k,:] . h[j,k,:] for j < n_src, s_dst[d,k] with att[1]
+//     for d < n_dst, each a left-to-right sum over f.
+//   gat_fwd_kernel: one group of LANES lanes per target d (LANES = 16 / 32 / 64 from the row's pieces, as agg_forward_kernel).
+//     A lane owns VEC columns of one head hk and runs the softmax of that head itself: a pass over s_src for the max, one
+//     for den = sum of expf(l - max) (left to right), then the pass over the neighbour rows, a batch of kAggBatch rows (and
+//     their s_src) loaded back to back, alpha = expf(l - max) / den recomputed per edge with the same operations (so every
+//     lane of head hk, and the alpha written out, hold the same bits). The lane at the head's first column writes alpha.
+//     With concat the group writes out; otherwise it writes the per-head rows to the workspace and gat_head_mean_kernel
+//     forms ((o_0 + o_1) + ...) * fl(1/H).
+//
+// Backward (no atomics; one fixed order of every sum):
+//   1 gat_bwd_edge_kernel, one thread per (target, head): da = G_k . h[col[e], k, :] per edge (kept in dz[]), c = sum of
+//     alpha * da, then dz = LeakyReLU'(z) * alpha * (da - c) per edge and ds_dst = sum of dz.
+//   2 the library's id sort of col_ind (host), gat_bwd_prep_kernel: the target of each sorted position, run_of (as agg).
+//   3 gat_bwd_chunk_kernel / gat_bwd_fold_kernel: per source j, P(j) = sum of alpha * G_k[dst] and ds_src(j) = sum of dz
+//     over its edges in sorted order, cut into chunks of kAggChunkEdges exactly as the agg backward; the fold then writes
+//     grad_h[j] = (P + ds_src * att[0]) + ds_dst * att[1] (the last term for j < n_dst) and ds_src[j].
+//   4 gat_att_chunk_kernel / gat_att_fold_kernel: grad_att[0] = sum over j of ds_src[j] * h[j] and grad_att[1] over
+//     j < n_dst with ds_dst, in node chunks of kGatNodeChunk: each chunk left to right, the chunk sums in chunk order.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "../backend.hpp"
+#include "agg_common.cuh"
+
+namespace wm {
+namespace {
+
+// backward scratch: the id sort's outputs and this op's workspace (hip_gat_backward carves it)
+struct wm_gat_bwd_state {
+  const int32_t* order;        // [n_edges] edge positions, sorted by source (stable)
+  const int32_t* run_starts;   // [n_unique + 1]
+  const int32_t* unique_ids;   // [n_unique] sources with edges, ascending
+  const int64_t* n_unique;     // device scalar written by the sort
+  int32_t* sorted_dst;         // [n_edges]
+  int32_t* run_of;             // [n_src]
+  float* dz;                   // [n_edges, heads]: da, then dz
+  float* ds_dst;               // [n_dst, heads]
+  float* ds_src;               // [n_src, heads]
+  float* partial;              // [n_tiles, partial_stride]: P of a chunk (ds_off columns), then its ds_src (heads)
+  float* att_partial;          // [n_node_chunks, 2 * heads * dim]
+  int64_t n_tiles, partial_stride, ds_off, n_node_chunks;
+};
+
+__device__ __forceinline__ float leaky(float z, float slope) { return z > 0.0f ? z : slope * z; }
+
+// -0.0 is the identity of IEEE addition: acc = -0.0 followed by acc + t_0 + t_1 + ... is the left-to-right sum that starts
+// from the first term (also when that term is -0.0)
+
+template <int VEC>
+__global__ __launch_bounds__(kAggBlock) void gat_score_kernel(wm_gat_args p)
+{
+  const int64_t H = p.heads, F = p.dim, n = (p.n_src + p.n_dst) * H;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n;
+       i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const int64_t j = i / H, k = i - j * H;
+    const bool dst  = j >= p.n_src;
+    const float* x  = p.h + (dst ? j - p.n_src : j) * p.h_stride + k * F;
+    const float* a  = p.att + (dst ? H * F : 0) + k * F;
+    float acc       = -0.0f;
+#pragma unroll 4
+    for (int64_t f = 0; f < F; f += VEC) {
+      const fvec<VEC> xv = ldv<VEC>(x + f), av = ldv<VEC>(a + f);
+#pragma unroll
+      for (int q = 0; q < VEC; ++q) acc = acc + av.v[q] * xv.v[q];
+    }
+    p.scores[i] = acc;
+  }
+}
+
+template <int VEC, int LANES>
+__global__ __launch_bounds__(kAggBlock) void gat_fwd_kernel(wm_gat_args p, float* o, int64_t o_stride)
+{
+  constexpr int kGroups = kAggBlock / LANES;
+  const int gl          = threadIdx.x % LANES;
+  const int64_t H = p.heads, F = p.dim, HF = H * F;
+  const float* s_src = p.scores;
+  for (int64_t d = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; d < p.n_dst;
+       d += static_cast<int64_t>(gridDim.x) * kGroups) {
+    int64_t e0, e1;
+    edge_range(p.row_ptr, d, p.n_edges, e0, e1);
+    for (int64_t cb = 0; cb < HF; cb += LANES * VEC) {   // (group-uniform trip count: the shuffles below stay in step)
+      const int64_t c  = cb + gl * VEC;
+      const bool act   = c < HF;
+      const int64_t cl = act ? c : 0;
+      const int64_t hk = cl / F;   // (a piece never straddles two heads: VEC = 4 only when F % 4 == 0)
+      const bool writer = act && c == hk * F;
+      const float sd    = s_src[(p.n_src + d) * H + hk];
+      float m = -INFINITY, den = -0.0f;
+      for (int pass = 0; pass < 2; ++pass) {   // 0: the max of l, 1: den = sum of expf(l - max), left to right
+        for (int64_t eb = e0; eb < e1; eb += LANES) {
+          const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
+          const int my = gl < nb ? p.col_ind[eb + gl] : 0;
+          for (int j = 0; j < nb; j += kAggBatch) {
+            float s[kAggBatch];
+#pragma unroll
+            for (int k = 0; k < kAggBatch; ++k) {
+              const int src = __shfl(my, j + k < nb ? j + k : nb - 1, LANES);
+              s[k]          = s_src[static_cast<int64_t>(src) * H + hk];
+            }
+#pragma unroll
+            for (int k = 0; k < kAggBatch; ++k) {
+              if (j + k < nb) {
+                const float l = leaky(s[k] + sd, p.slope);
+                if (pass == 0) m = fmaxf(m, l);
+                else den = den + expf(l - m);
+              }
+            }
+          }
+        }
+      }
+      fvec<VEC> acc = splat<VEC>(-0.0f);
+      for (int64_t eb = e0; eb < e1; eb += LANES) {
+        const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
+        const int my = gl < nb ? p.col_ind[eb + gl] : 0;
+        for (int j = 0; j < nb; j += kAggBatch) {
+          fvec<VEC> v[kAggBatch];
+          float s[kAggBatch];
+#pragma unroll
+          for (int k = 0; k < kAggBatch; ++k) {
+            const int src = __shfl(my, j + k < nb ? j + k : nb - 1, LANES);
+            v[k]          = ldv<VEC>(p.h + static_cast<int64_t>(src) * p.h_stride + cl);
+            s[k]          = s_src[static_cast<int64_t>(src) * H + hk];
+          }
+#pragma unroll
+          for (int k = 0; k < kAggBatch; ++k) {
+            if (j + k < nb) {
+              const float a = expf(leaky(s[k] + sd, p.slope) - m) / den;
+              add_to(acc, scaled(v[k], a));
+              if (writer) p.alpha[(eb + j + k) * H + hk] = a;
+            }
+          }
+        }
+      }
+      if (act) stv(o + d * o_stride + c, e1 > e0 ? acc : splat<VEC>(0.0f));
+    }
+  }
+}
+
+// out[d, f] = ((o[d, 0, f] + o[d, 1, f]) + ...) * fl(1 / H)
+__global__ __launch_bounds__(kAggBlock) void gat_head_mean_kernel(wm_gat_args p, const float* o, int64_t o_stride)
+{
+  const int64_t H = p.heads, F = p.dim, n = p.n_dst * F;
+  const float r   = 1.0f / static_cast<float>(H);
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n;
+       i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const int64_t d = i / F, f = i - d * F;
+    const float* row = o + d * o_stride + f;
+    float acc        = row[0];
+    for (int64_t k = 1; k < H; ++k) acc = acc + row[k * F];
+    p.out[d * p.out_stride + f] = acc * r;
+  }
+}
+
+// one thread per (target d, head k): da[e] = G_k[d] . h[col[e], k] (into dz), c = sum of alpha * da, then dz and ds_dst
+template <int VEC>
+__global__ __launch_bounds__(kAggBlock) void gat_bwd_edge_kernel(wm_gat_args p, wm_gat_bwd_state b)
+{
+  const int64_t H = p.heads, F = p.dim, n = p.n_dst * H;
+  const float r   = 1.0f / static_cast<float>(H);
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n;
+       i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const int64_t d = i / H, k = i - d * H;
+    int64_t e0, e1;
+    edge_range(p.row_ptr, d, p.n_edges, e0, e1);
+    const float* g = p.grad + d * p.grad_stride + (p.concat ? k * F : 0);
+    float c        = -0.0f;
+    for (int64_t e = e0; e < e1; ++e) {
+      const float* x = p.h + static_cast<int64_t>(p.col_ind[e]) * p.h_stride + k * F;
+      float da       = -0.0f;
+#pragma unroll 4
+      for (int64_t f = 0; f < F; f += VEC) {
+        const fvec<VEC> gv = ldv<VEC>(g + f), xv = ldv<VEC>(x + f);
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) da = da + (p.concat ? gv.v[q] : gv.v[q] * r) * xv.v[q];
+      }
+      b.dz[e * H + k] = da;
+      c               = c + p.alpha[e * H + k] * da;
+    }
+    const float sd = p.scores[(p.n_src + d) * H + k];
+    float dd       = -0.0f;
+    for (int64_t e = e0; e < e1; ++e) {
+      const float z  = p.scores[static_cast<int64_t>(p.col_ind[e]) * H + k] + sd;
+      const float dl = p.alpha[e * H + k] * (b.dz[e * H + k] - c);
+      const float dz = z > 0.0f ? dl : dl * p.slope;
+      b.dz[e * H + k] = dz;
+      dd              = dd + dz;
+    }
+    b.ds_dst[i] = e1 > e0 ? dd : 0.0f;
+  }
+}
+
+__global__ __launch_bounds__(kAggBlock) void gat_bwd_prep_kernel(wm_gat_args p, wm_gat_bwd_state b)
+{
+  const int64_t nu = *b.n_unique;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < p.n_edges;
+       i += static_cast<int64_t>(gridDim.x) * blockDim.x)
+    bwd_prep_at(i, p.row_ptr, p.n_dst, b.order, b.unique_ids, nu, b.sorted_dst, b.run_of);
+}
+
+// acc += alpha[e, hk] * G_k[dst(e)] and ds += dz[e, hk] for the edges at sorted positions [eb0, ee), in that order
+template <int VEC, int LANES>
+__device__ __forceinline__ void fold_gat_edges(fvec<VEC>& acc, float& ds, const wm_gat_args& p, const wm_gat_bwd_state& b,
+                                               int64_t eb0, int64_t ee, int64_t gcol, int64_t hk, int gl)
+{
+  const int64_t H = p.heads;
+  const float r   = 1.0f / static_cast<float>(H);
+  for (int64_t eb = eb0; eb < ee; eb += LANES) {
+    const int nb = static_cast<int>(ee - eb < LANES ? ee - eb : LANES);
+    int my_e = 0, my_d = 0;
+    if (gl < nb) my_e = b.order[eb + gl], my_d = b.sorted_dst[eb + gl];
+    for (int j = 0; j < nb; j += kAggBatch) {
+      fvec<VEC> v[kAggBatch];
+      float a[kAggBatch], z[kAggBatch];
+#pragma unroll
+      for (int k = 0; k < kAggBatch; ++k) {
+        const int from = j + k < nb ? j + k : nb - 1;
+        const int64_t e = __shfl(my_e, from, LANES);
+        const int dst   = __shfl(my_d, from, LANES);
+        v[k]            = ldv<VEC>(p.grad + static_cast<int64_t>(dst) * p.grad_stride + gcol);
+        a[k]            = p.alpha[e * H + hk];
+        z[k]            = b.dz[e * H + hk];
+      }
+#pragma unroll
+      for (int k = 0; k < kAggBatch; ++k) {
+        if (j + k < nb) {
+          add_to(acc, scaled(p.concat ? v[k] : scaled(v[k], r), a[k]));
+          ds = ds + z[k];
+        }
+      }
+    }
+  }
+}
+
+template <int VEC, int LANES>
+__global__ __launch_bounds__(kAggBlock) void gat_bwd_chunk_kernel(wm_gat_args p, wm_gat_bwd_state b)
+{
+  constexpr int kGroups = kAggBlock / LANES;
+  const int gl          = threadIdx.x % LANES;
+  const int64_t F = p.dim, HF = p.heads * F;
+  const int64_t nu = *b.n_unique;
+  if (nu == 0) return;
+  for (int64_t t = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; t < b.n_tiles;
+       t += static_cast<int64_t>(gridDim.x) * kGroups) {
+    int64_t cs, ce;
+    if (!chunk_in_tile(t, b.run_starts, nu, cs, ce)) continue;
+    for (int64_t cb = 0; cb < HF; cb += LANES * VEC) {
+      const int64_t c  = cb + gl * VEC;
+      const bool act   = c < HF;
+      const int64_t cl = act ? c : 0;
+      const int64_t hk = cl / F;
+      fvec<VEC> acc    = splat<VEC>(-0.0f);
+      float ds         = -0.0f;
+      fold_gat_edges<VEC, LANES>(acc, ds, p, b, cs, ce, p.concat ? cl : cl - hk * F, hk, gl);
+      float* prow = b.partial + t * b.partial_stride;
+      if (act) stv(prow + c, acc);
+      if (act && c == hk * F) prow[b.ds_off + hk] = ds;
+    }
+  }
+}
+
+template <int VEC, int LANES>
+__global__ __launch_bounds__(kAggBlock) void gat_bwd_fold_kernel(wm_gat_args p, wm_gat_bwd_state b)
+{
+  constexpr int kGroups = kAggBlock / LANES;
+  constexpr int64_t C   = kAggChunkEdges;
+  const int gl          = threadIdx.x % LANES;
+  const int64_t H = p.heads, F = p.dim, HF = H * F;
+  const int64_t nu = *b.n_unique;
+  for (int64_t s = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; s < p.n_src;
+       s += static_cast<int64_t>(gridDim.x) * kGroups) {
+    const int64_t u = b.run_of[s];   // (uninitialised unless s has edges: checked against unique_ids)
+    const bool has  = u >= 0 && u < nu && b.unique_ids[u] == s;
+    int64_t s0 = 0, s1 = 0;
+    if (has) s0 = b.run_starts[u], s1 = b.run_starts[u + 1];
+    const int64_t c0e     = s1 - s0 > C ? s0 + C : s1;
+    const int64_t nchunks = (s1 - s0 + C - 1) / C;
+    for (int64_t cb = 0; cb < HF; cb += LANES * VEC) {
+      const int64_t c  = cb + gl * VEC;
+      const bool act   = c < HF;
+      const int64_t cl = act ? c : 0;
+      const int64_t hk = cl / F;
+      fvec<VEC> acc    = splat<VEC>(-0.0f);
+      float ds         = -0.0f;
+      fold_gat_edges<VEC, LANES>(acc, ds, p, b, s0, c0e, p.concat ? cl : cl - hk * F, hk, gl);
+      for (int64_t k0 = 1; k0 < nchunks; k0 += kAggBatch) {   // partials in chunk order, a batch of them in flight
+        fvec<VEC> v[kAggBatch];
+        float pd[kAggBatch];
+#pragma unroll
+        for (int k = 0; k < kAggBatch; ++k) {
+          const int64_t kk   = k0 + k < nchunks ? k0 + k : nchunks - 1;
+          const float* prow  = b.partial + ((s0 + kk * C) / C) * b.partial_stride;
+          v[k]               = ldv<VEC>(prow + cl);
+          pd[k]              = prow[b.ds_off + hk];
+        }
+#pragma unroll
+        for (int k = 0; k < kAggBatch; ++k) {
+          if (k0 + k < nchunks) {
+            add_to(acc, v[k]);
+            ds = ds + pd[k];
+          }
+        }
+      }
+      if (!has) acc = splat<VEC>(0.0f), ds = 0.0f;
+      fvec<VEC> res = acc;
+      add_to(res, scaled(ldv<VEC>(p.att + cl), ds));
+      if (s < p.n_dst) add_to(res, scaled(ldv<VEC>(p.att + HF + cl), b.ds_dst[s * H + hk]));
+      if (act) stv(p.grad_h + s * p.grad_h_stride + c, res);
+      if (act && c == hk * F) b.ds_src[s * H + hk] = ds;
+    }
+  }
+}
+
+// one thread per (node chunk q, column c of [0, 2 * H * F)): the chunk's sum of ds[j, k] * h[j, c'], left to right
+__global__ __launch_bounds__(kAggBlock) void gat_att_chunk_kernel(wm_gat_args p, wm_gat_bwd_state b)
+{
+  const int64_t H = p.heads, F = p.dim, HF = H * F, W = 2 * HF, n = b.n_node_chunks * W;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n;
+       i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const int64_t q = i / W, c = i - q * W;
+    const bool half = c >= HF;
+    const int64_t cc = half ? c - HF : c, k = cc / F;
+    const int64_t rows = half ? p.n_dst : p.n_src;
+    const float* ds    = half ? b.ds_dst : b.ds_src;
+    const int64_t j0 = q * kGatNodeChunk, j1 = j0 + kGatNodeChunk < rows ? j0 + kGatNodeChunk : rows;
+    float acc = -0.0f;
+#pragma unroll 8
+    for (int64_t j = j0; j < j1; ++j) acc = acc + ds[j * H + k] * p.h[j * p.h_stride + cc];
+    b.att_partial[i] = acc;
+  }
+}
+
+// grad_att[c]: the chunk sums in chunk order; +0.0 when the half has no rows
+__global__ __launch_bounds__(kAggBlock) void gat_att_fold_kernel(wm_gat_args p, wm_gat_bwd_state b)
+{
+  const int64_t HF = p.heads * p.dim, W = 2 * HF;
+  const int64_t c = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (c >= W) return;
+  const int64_t rows = c >= HF ? p.n_dst : p.n_src;
+  const int64_t nq   = (rows + kGatNodeChunk - 1) / kGatNodeChunk;
+  float acc          = -0.0f;
+#pragma unroll 8
+  for (int64_t q = 0; q < nq; ++q) acc = acc + b.att_partial[q * W + c];
+  p.grad_att[c] = nq > 0 ? acc : 0.0f;
+}
+
+int64_t up4(int64_t v) { return (v + 3) / 4 * 4; }
+uintptr_t up256(uintptr_t v) { return (v + 255) & ~static_cast<uintptr_t>(255); }
+bool aligned16(const void* ptr) { return reinterpret_cast<uintptr_t>(ptr) % 16 == 0; }
+
+}  // namespace
+
+size_t hip_gat_forward_workspace_bytes(const wm_gat_args* a)
+{
+  return a->concat ? 0 : static_cast<size_t>(a->n_dst * a->heads * a->dim) * 4 + 256;
+}
+
+int hip_gat_forward(const wm_gat_args* a, void* workspace, void* stream_v)
+{
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  const int64_t H = a->heads, F = a->dim, HF = H * F;
+  const bool f4   = F % 4 == 0 && aligned16(a->att);
+  const int64_t ns = (a->n_src + a->n_dst) * H;
+  if (ns > 0) {
+    const bool v4 = f4 && use_vec4(HF, a->h, a->h_stride, a->h, a->h_stride);
+    if (v4) hipLaunchKernelGGL(gat_score_kernel<4>, dim3(blocks_for(ns, kAggBlock)), dim3(kAggBlock), 0, stream, *a);
+    else hipLaunchKernelGGL(gat_score_kernel<1>, dim3(blocks_for(ns, kAggBlock)), dim3(kAggBlock), 0, stream, *a);
+    if (rc_last() != 0) return -2;
+  }
+  if (a->n_dst == 0) return 0;
+  float* o         = a->concat ? a->out : reinterpret_cast<float*>(up256(reinterpret_cast<uintptr_t>(workspace)));
+  const int64_t os = a->concat ? a->out_stride : HF;
+  const bool v4    = f4 && use_vec4(HF, a->h, a->h_stride, o, os);
+#define WM_GAT_FWD(V, L)                                                                                                   \
+  hipLaunchKernelGGL((gat_fwd_kernel<V, L>), dim3(blocks_for(a->n_dst, kAggBlock / (L))), dim3(kAggBlock), 0, stream, *a, \
+                     o, os)
+  WM_AGG_DISPATCH(v4, v4 ? HF / 4 : HF, WM_GAT_FWD);
+#undef WM_GAT_FWD
+  if (rc_last() != 0) return -2;
+  if (!a->concat) {
+    hipLaunchKernelGGL(gat_head_mean_kernel, dim3(blocks_for(a->n_dst * F, kAggBlock)), dim3(kAggBlock), 0, stream, *a,
+                       static_cast<const float*>(o), os);
+    if (rc_last() != 0) return -2;
+  }
+  return 0;
+}
+
+namespace {
+struct gat_bwd_layout {
+  int64_t n_tiles, partial_stride, ds_off, n_node_chunks;
+  size_t off[7], bytes;   // sorted_dst, run_of, dz, ds_dst, ds_src, partial, att_partial
+};
+
+gat_bwd_layout bwd_layout(const wm_gat_args* a)
+{
+  gat_bwd_layout l;
+  const int64_t H = a->heads, HF = H * a->dim, E = a->n_edges;
+  l.n_tiles        = (E + kAggChunkEdges - 1) / kAggChunkEdges;
+  l.ds_off         = up4(HF);
+  l.partial_stride = l.ds_off + up4(H);
+  l.n_node_chunks  = (a->n_src + kGatNodeChunk - 1) / kGatNodeChunk;
+  const int64_t sizes[7] = {E * 4, a->n_src * 4, E * H * 4, a->n_dst * H * 4, a->n_src * H * 4,
+                            l.n_tiles * l.partial_stride * 4, l.n_node_chunks * 2 * HF * 4};
+  size_t w = 0;
+  for (int i = 0; i < 7; ++i) {
+    l.off[i] = w;
+    w        = up256(w + static_cast<size_t>(sizes[i]));
+  }
+  l.bytes = w + 256;   // (+ the alignment of the workspace's start)
+  return l;
+}
+}  // namespace
+
+size_t hip_gat_backward_workspace_bytes(const wm_gat_args* a) { return bwd_layout(a).bytes; }
+
+int hip_gat_backward(const wm_gat_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                     const int64_t* n_unique_dev, void* workspace, void* stream_v)
+{
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  const int64_t H = a->heads, F = a->dim, HF = H * F;
+  const gat_bwd_layout l = bwd_layout(a);
+  const uintptr_t w0     = up256(reinterpret_cast<uintptr_t>(workspace));
+  wm_gat_bwd_state b;
+  b.order          = order;
+  b.run_starts     = run_starts;
+  b.unique_ids     = unique_ids;
+  b.n_unique       = n_unique_dev;
+  b.sorted_dst     = reinterpret_cast<int32_t*>(w0 + l.off[0]);
+  b.run_of         = reinterpret_cast<int32_t*>(w0 + l.off[1]);
+  b.dz             = reinterpret_cast<float*>(w0 + l.off[2]);
+  b.ds_dst         = reinterpret_cast<float*>(w0 + l.off[3]);
+  b.ds_src         = reinterpret_cast<float*>(w0 + l.off[4]);
+  b.partial        = reinterpret_cast<float*>(w0 + l.off[5]);
+  b.att_partial    = reinterpret_cast<float*>(w0 + l.off[6]);
+  b.n_tiles        = l.n_tiles;
+  b.partial_stride = l.partial_stride;
+  b.ds_off         = l.ds_off;
+  b.n_node_chunks  = l.n_node_chunks;
+
+  // 16-byte pieces: whole heads of F % 4 == 0 columns, every row start and att 16-byte aligned
+  const int64_t gcols = a->concat ? HF : F;
+  const bool f4       = F % 4 == 0 && aligned16(a->att) && use_vec4(gcols, a->grad, a->grad_stride, a->h, a->h_stride);
+  if (a->n_dst > 0) {
+    if (f4) hipLaunchKernelGGL(gat_bwd_edge_kernel<4>, dim3(blocks_for(a->n_dst * H, kAggBlock)), dim3(kAggBlock), 0, stream, *a, b);
+    else hipLaunchKernelGGL(gat_bwd_edge_kernel<1>, dim3(blocks_for(a->n_dst * H, kAggBlock)), dim3(kAggBlock), 0, stream, *a, b);
+    if (rc_last() != 0) return -2;
+  }
+  if (a->n_src > 0) {
+    if (a->n_edges > 0) {
+      const int blocks = blocks_for(a->n_edges, kAggBlock);
+      hipLaunchKernelGGL(gat_bwd_prep_kernel, dim3(blocks < 8192 ? blocks : 8192), dim3(kAggBlock), 0, stream, *a, b);
+      if (rc_last() != 0) return -2;
+    }
+    const bool v4 = f4 && use_vec4(HF, a->grad_h, a->grad_h_stride, a->grad_h, a->grad_h_stride);
+    if (b.n_tiles > 1) {   // (one tile holds no chunk k >= 1)
+#define WM_GAT_CHUNK(V, L)                                                                                                   \
+  hipLaunchKernelGGL((gat_bwd_chunk_kernel<V, L>), dim3(blocks_for(b.n_tiles, kAggBlock / (L))), dim3(kAggBlock), 0, stream, \
+                     *a, b)
+      WM_AGG_DISPATCH(v4, v4 ? HF / 4 : HF, WM_GAT_CHUNK);
+#undef WM_GAT_CHUNK
+      if (rc_last() != 0) return -2;
+    }
+#define WM_GAT_FOLD(V, L)                                                                                                   \
+  hipLaunchKernelGGL((gat_bwd_fold_kernel<V, L>), dim3(blocks_for(a->n_src, kAggBlock / (L))), dim3(kAggBlock), 0, stream, \
+                     *a, b)
+    WM_AGG_DISPATCH(v4, v4 ? HF / 4 : HF, WM_GAT_FOLD);
+#undef WM_GAT_FOLD
+    if (rc_last() != 0) return -2;
+    hipLaunchKernelGGL(gat_att_chunk_kernel, dim3(blocks_for(b.n_node_chunks * 2 * HF, kAggBlock)), dim3(kAggBlock), 0,
+                       stream, *a, b);
+    if (rc_last() != 0) return -2;
+  }
+  hipLaunchKernelGGL(gat_att_fold_kernel, dim3(blocks_for(2 * HF, kAggBlock)), dim3(kAggBlock), 0, stream, *a, b);
+  return rc_last();
+}
+
+}  // namespace wm

@@ -3,12 +3,12 @@
 Same names and signatures as reference ``python/pylibwholegraph/pylibwholegraph/torch/__init__.py:14-78`` for
 communicators, initialisation, WholeMemory tensors, embeddings / optimizers / cache policies, the gather / scatter
 functors, neighbour sampling and GraphStructure, and for the GNN model surface of the ``cugraph`` framework route
-(``set_framework``, ``create_gnn_layers``, ``create_sub_graph``, ``HomoGNNModel``; the GraphSAGE layer in ``cugraphops``,
-on the HIP neighbour aggregation op of ``aggregation``). GAT, the dgl / pyg / wg routes, data loaders, launch helpers and
-option parsers of the reference are outside this build's scope.
+(``set_framework``, ``create_gnn_layers``, ``create_sub_graph``, ``HomoGNNModel``; the GraphSAGE and GAT layers in
+``cugraphops``, on the HIP ops of ``aggregation`` and ``gat_aggregation``). GAT in ``HomoGNNModel``, the dgl / pyg / wg
+routes, data loaders, launch helpers and option parsers of the reference are outside this build's scope.
 """
 from . import comm, embedding, graph_ops, graph_structure, initialize, tensor, utils, wholegraph_ops, wholememory_ops
-from . import aggregation, cugraphops, gnn_model
+from . import aggregation, cugraphops, gat_aggregation, gnn_model
 
 _PUBLIC = {
     comm: ("WholeMemoryCommunicator create_group_communicator destroy_communicator get_global_communicator "
@@ -25,7 +25,7 @@ _PUBLIC = {
     graph_structure: "GraphStructure",
     gnn_model: "set_framework create_gnn_layers create_sub_graph HomoGNNModel",
 }
-__all__ = ["graph_ops", "wholegraph_ops", "aggregation", "cugraphops", "gnn_model"]
+__all__ = ["graph_ops", "wholegraph_ops", "aggregation", "cugraphops", "gat_aggregation", "gnn_model"]
 for _module, _names in _PUBLIC.items():
     for _name in _names.split():
         globals()[_name] = getattr(_module, _name)

@@ -1,6 +1,7 @@
 """The GNN model surface of ``pylibwholegraph.torch.gnn_model`` (``set_framework``, ``create_gnn_layers``,
 ``create_sub_graph``, ``layer_forward``, ``HomoGNNModel``) for the ``cugraph`` framework route with GraphSAGE layers, on the
-HIP aggregation op (``aggregation.py``). The dgl / pyg / wg routes and GAT are not part of this build.
+HIP aggregation op (``aggregation.py``). The dgl / pyg / wg routes and GAT models are not part of this build (the GAT
+layer itself is ``cugraphops.CuGraphGATConv``).
 
 Flow of ``HomoGNNModel.forward`` (the reference's): sample ``layernum`` hops from the seed ids, gather the float32
 features of the outermost frontier through ``WholeMemoryEmbeddingModule`` (so the embedding receives gradients), then one

@@ -297,6 +297,52 @@ enum wholememory_error_code_t wholememory_ext_csc_aggregate_backward(const int32
 /* C of the backward's chunked sums (a compile-time constant of the library) */
 int64_t wholememory_ext_csc_aggregate_chunk_edges(void);
 
+/* (2b, rows of 16-bit floats) The same op with x, out, grad_out and grad_x all of type T = `dtype`: WHOLEMEMORY_DT_HALF
+ * (IEEE binary16) or WHOLEMEMORY_DT_BF16; strides in elements of T. Every sum is taken in fp32, in exactly the order
+ * stated above, and each output element is rounded to T once, round to nearest even. Widening T -> fp32 is exact, so:
+ *   forward: S(d) = fp32 sum of fp32(x[col_ind[e]]), left to right from the first term. A = S (SUM) or
+ *     S * fl(1.0f / deg(d)) (MEAN, one fp32 multiply). out[d, 0:dim] = round_T(A); no edge: +0.0. out[d, dim:2dim] = x[d],
+ *     copied bit for bit.
+ *   backward: t(e) = fp32(grad_out[dst(e), 0:dim]), times fl(1.0f / deg(dst(e))) in fp32 for MEAN. P(s) as above, with the
+ *     same chunk size C; the partial rows of chunks stay fp32 in the workspace.
+ *     grad_x[s] = round_T(P(s) + fp32(grad_out[s, dim:2dim])) (the self term last, s < n_dst only); only the self term: its
+ *     bits are copied; only P: round_T(P); neither: +0.0. No atomics; bitwise reproducible.
+ *   fp16 results that leave the fp16 range round to +-inf (IEEE); results in the subnormal range of T are rounded, not
+ *     flushed. A NaN stays a NaN (payload not specified).
+ * The running sum never lives in T. Hence, for any input, op_T(x) == round_T(op_fp32(fp32(x))) bit for bit: the A half of
+ * the forward, and the backward (the copied halves are equal as well, since widening and rounding back is the identity
+ * on every value but a NaN's payload).
+ * WHOLEMEMORY_DT_FLOAT takes the fp32 entry points above (the same bits); any other dtype is INVALID_INPUT. All other
+ * argument checks, and NOT_SUPPORTED, as for the fp32 entry points. */
+enum wholememory_error_code_t wholememory_ext_csc_aggregate_forward_typed(const int32_t* row_ptr,
+                                                                          const int32_t* col_ind,
+                                                                          int64_t n_edges,
+                                                                          int64_t n_dst,
+                                                                          int64_t n_src,
+                                                                          const void* x,
+                                                                          int64_t x_stride,
+                                                                          int64_t dim,
+                                                                          int aggr,
+                                                                          void* out,
+                                                                          int64_t out_stride,
+                                                                          enum wholememory_dtype_t dtype,
+                                                                          struct wholememory_env_func_t* p_env_fns,
+                                                                          void* stream);
+enum wholememory_error_code_t wholememory_ext_csc_aggregate_backward_typed(const int32_t* row_ptr,
+                                                                           const int32_t* col_ind,
+                                                                           int64_t n_edges,
+                                                                           int64_t n_dst,
+                                                                           int64_t n_src,
+                                                                           const void* grad_out,
+                                                                           int64_t grad_out_stride,
+                                                                           int64_t dim,
+                                                                           int aggr,
+                                                                           void* grad_x,
+                                                                           int64_t grad_x_stride,
+                                                                           enum wholememory_dtype_t dtype,
+                                                                           struct wholememory_env_func_t* p_env_fns,
+                                                                           void* stream);
+
 /* ---- (2c) multi-head graph attention of a sampled CSC block (GAT `mha_gat_n2n`) ------------------------------ */
 /* The block as for (2b): row_ptr int32 [n_dst + 1], col_ind int32 [n_edges] in [0, n_src), h fp32 [n_src, h_stride] with
  * H * F columns used (H = heads, F = dim; the layer's lin(x)), whose first n_dst rows are the targets. Head k owns the

@@ -13,7 +13,13 @@ Per shape: the forward, the full backward, and the backward split into the edge 
 target / run lookups of agg_bwd_prep_kernel) and the fold (agg_bwd_chunk_kernel + agg_bwd_fold_kernel) from per-kernel
 device times (torch.profiler). Algorithmic bytes: forward E(4 + 4F) + n_dst(4 + 12F); fold E(8 + 4F) + n_src 4F + n_dst 4F;
 the fraction is of 8 TB/s. The torch composite of the same op in the same process (index_select + index_add_ segment sum
-+ cat for the forward; index_select + index_add_ for the backward) gives the ratios."""
++ cat for the forward; index_select + index_add_ for the backward) gives the ratios.
+
+--dtype float16 | bfloat16 times the op on 16-bit rows (csrc/kernels/agg_half.hip; bytes with 2-byte rows: forward
+E(4 + 2F) + n_dst(4 + 6F); fold E(8 + 2F) + n_src 2F + n_dst 2F) and, on the same block in the same process, the two
+baselines it is judged against: the fp32 op on x.float() (with the min and max of its repetitions, its run-to-run spread)
+and the "cast composite" a user had to write without 16-bit rows, agg_concat(x.float(), ...).to(T), forward and backward
+through autograd. The 16-bit result is also checked bit for bit against the fp32 result rounded once."""
 import argparse
 import json
 import os
@@ -26,7 +32,7 @@ sys.path.insert(0, ROOT)
 PEAK = 8.0e12
 
 
-def timed(fn, warmup, reps):
+def timed_all(fn, warmup, reps):
     import torch
     for _ in range(warmup):
         fn()
@@ -39,7 +45,11 @@ def timed(fn, warmup, reps):
         e1.record()
         e1.synchronize()
         ms.append(e0.elapsed_time(e1))
-    return statistics.median(ms)
+    return ms
+
+
+def timed(fn, warmup, reps):
+    return statistics.median(timed_all(fn, warmup, reps))
 
 
 def kernel_split(fn, reps):
@@ -65,10 +75,10 @@ def kernel_split(fn, reps):
             t = getattr(ev, "cuda_time", 0.0)
         if ev.device_type != torch.autograd.DeviceType.CUDA:
             continue
-        if "agg_bwd_chunk_kernel" in name or "agg_bwd_fold_kernel" in name:
+        if "agg_bwd_chunk_kernel" in name or "agg_bwd_fold_kernel" in name or "agg16_bwd_" in name:
             fold += t
             seen = True
-        elif "agg_forward_kernel" not in name and "elementwise" not in name.lower() and "fill" not in name.lower():
+        elif "agg_forward_kernel" not in name and "agg16_forward_kernel" not in name and "elementwise" not in name.lower() and "fill" not in name.lower():
             index += t   # the id sort's kernels and agg_bwd_prep_kernel
     if not seen:
         return None
@@ -174,6 +184,78 @@ def run_shape(name, row_ptr, col_ind, n_src, dim, warmup, reps, split_kernels=Tr
     return res
 
 
+def run_shape_16(name, row_ptr, col_ind, n_src, dim, warmup, reps, dtype, split_kernels=True):
+    """the op on rows of `dtype` (fp16 / bf16), the fp32 op and the cast composite on the same block"""
+    import torch
+    from wholegraph_amd.torch.aggregation import agg_concat
+    n_dst, E = row_ptr.numel() - 1, col_ind.numel()
+    gen = torch.Generator(device="cuda").manual_seed(3)
+    x16 = torch.randn((n_src, dim), device="cuda", generator=gen).to(dtype).requires_grad_(True)
+    out16 = agg_concat(x16, row_ptr, col_ind, "mean")
+    G16 = torch.randn(tuple(out16.shape), device="cuda", generator=gen).to(dtype)
+    x32 = x16.detach().float().requires_grad_(True)
+    out32 = agg_concat(x32, row_ptr, col_ind, "mean")
+    G32 = G16.float()
+    xc = x16.detach().clone().requires_grad_(True)   # the cast composite's leaf
+    outc = agg_concat(xc.float(), row_ptr, col_ind, "mean").to(dtype)
+
+    def bwd_of(x, out, G):
+        def f():
+            x.grad = None
+            torch.autograd.backward(out, G, retain_graph=True)
+        return f
+    bwd16, bwd32, bwdc = bwd_of(x16, out16, G16), bwd_of(x32, out32, G32), bwd_of(xc, outc, G16)
+    # the same op: the 16-bit result is the fp32 result rounded once, bit for bit (and so is the cast composite's)
+    bwd16(), bwd32(), bwdc()
+    assert torch.equal(out16.view(torch.int16), out32.to(dtype).view(torch.int16))
+    assert torch.equal(x16.grad.view(torch.int16), x32.grad.to(dtype).view(torch.int16))
+    assert torch.equal(xc.grad.view(torch.int16), x16.grad.view(torch.int16))
+
+    def stats(ms):
+        return round(statistics.median(ms), 4), round(min(ms), 4), round(max(ms), 4)
+    fwd = stats(timed_all(lambda: agg_concat(x16, row_ptr, col_ind, "mean"), warmup, reps))
+    bwd = stats(timed_all(bwd16, warmup, reps))
+    split = kernel_split(bwd16, max(3, reps // 2)) if split_kernels else None
+    f32_fwd = stats(timed_all(lambda: agg_concat(x32, row_ptr, col_ind, "mean"), warmup, reps))
+    f32_bwd = stats(timed_all(bwd32, warmup, reps))
+    f32_split = kernel_split(bwd32, max(3, reps // 2)) if split_kernels else None
+    xd = x16.detach()
+    cast_fwd = stats(timed_all(lambda: agg_concat(xd.float(), row_ptr, col_ind, "mean").to(dtype), warmup, reps))
+    cast_bwd = stats(timed_all(bwdc, warmup, reps))
+
+    fwd_bytes = E * (4 + 2 * dim) + n_dst * (4 + 6 * dim)
+    fold_bytes = E * (8 + 2 * dim) + n_src * 2 * dim + n_dst * 2 * dim
+    counts = torch.bincount(col_ind.long(), minlength=n_src)
+    res = {"shape": name, "dtype": str(dtype).replace("torch.", ""), "n_dst": n_dst, "n_src": n_src, "edges": E, "dim": dim,
+           "max_edges_per_source": int(counts.max()), "median_edges_per_used_source": float(counts[counts > 0].median()),
+           "forward_ms": fwd[0], "forward_ms_min_max": fwd[1:], "forward_GBps": round(fwd_bytes / fwd[0] / 1e6, 1),
+           "forward_frac_8TBps": round(fwd_bytes / fwd[0] / 1e-3 / PEAK, 4),
+           "backward_ms": bwd[0], "backward_ms_min_max": bwd[1:],
+           "fp32_forward_ms": f32_fwd[0], "fp32_forward_ms_min_max": f32_fwd[1:],
+           "fp32_backward_ms": f32_bwd[0], "fp32_backward_ms_min_max": f32_bwd[1:],
+           "cast_forward_ms": cast_fwd[0], "cast_forward_ms_min_max": cast_fwd[1:],
+           "cast_backward_ms": cast_bwd[0], "cast_backward_ms_min_max": cast_bwd[1:],
+           "forward_over_fp32": round(fwd[0] / f32_fwd[0], 3), "backward_over_fp32": round(bwd[0] / f32_bwd[0], 3),
+           "forward_over_cast": round(fwd[0] / cast_fwd[0], 3), "backward_over_cast": round(bwd[0] / cast_bwd[0], 3),
+           # the gates: faster than the cast composite; not slower than the fp32 op by more than that op's own spread
+           "faster_than_cast": bool(fwd[0] < cast_fwd[0] and bwd[0] < cast_bwd[0]),
+           "within_fp32_spread": bool(fwd[0] <= f32_fwd[0] + (f32_fwd[2] - f32_fwd[1]) and
+                                      bwd[0] <= f32_bwd[0] + (f32_bwd[2] - f32_bwd[1]))}
+    if split is not None:
+        index_ms, fold_ms = split
+        res.update({"index_ms": round(index_ms, 4), "fold_ms": round(fold_ms, 4),
+                    "fold_GBps": round(fold_bytes / fold_ms / 1e6, 1),
+                    "fold_frac_8TBps": round(fold_bytes / fold_ms / 1e-3 / PEAK, 4)})
+        if f32_split is not None:
+            res.update({"fp32_index_ms": round(f32_split[0], 4), "fp32_fold_ms": round(f32_split[1], 4),
+                        "fold_over_fp32": round(fold_ms / f32_split[1], 3)})
+    else:
+        res.update({"index_ms": None, "fold_ms": None, "fold_GBps": None, "fold_frac_8TBps": None})
+    del x16, out16, G16, x32, out32, G32, xc, outc, xd
+    torch.cuda.empty_cache()
+    return res
+
+
 def main():
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     p.add_argument("--warmup", type=int, default=3)
@@ -184,6 +266,8 @@ def main():
     p.add_argument("--n-src", type=int, default=2_000_000)
     p.add_argument("--nodes", type=int, default=111_059_956, help="shape c: graph nodes (bench.py sample_gather default)")
     p.add_argument("--shapes", default="a,b,c")
+    p.add_argument("--dtype", choices=("float32", "float16", "bfloat16"), default="float32",
+                   help="row type; a 16-bit type also times the fp32 op and the cast composite on the same block")
     p.add_argument("--out", help="also write the JSON line to this file")
     p.add_argument("--no-kernel-split", action="store_true",
                    help="skip the torch.profiler split of the backward (when an outer profiler such as rocprofv3 traces the run)")
@@ -198,6 +282,11 @@ def main():
     comm = wgth.create_group_communicator(1)
     from wholegraph_amd.torch.aggregation import chunk_edges
 
+    if a.dtype == "float32":
+        run = run_shape
+    else:
+        def run(*args):
+            return run_shape_16(*args[:7], getattr(torch, a.dtype), args[7])
     results = []
     gen = torch.Generator(device="cuda").manual_seed(2)
     row_ptr = (torch.arange(a.n_dst + 1, device="cuda", dtype=torch.int32) * a.fanout)
@@ -205,14 +294,16 @@ def main():
     for shape in a.shapes.split(","):
         if shape == "a":
             col = torch.randint(0, a.n_src, (E,), device="cuda", generator=gen, dtype=torch.int32)
-            results.append(run_shape("a_uniform", row_ptr, col, a.n_src, a.dim, a.warmup, a.reps, not a.no_kernel_split))
+            results.append(run("a_uniform", row_ptr, col, a.n_src, a.dim, a.warmup, a.reps, not a.no_kernel_split))
         elif shape == "b":
             col = powerlaw_ids(a.n_src, E, 0.8, gen)
-            results.append(run_shape("b_powerlaw", row_ptr, col, a.n_src, a.dim, a.warmup, a.reps, not a.no_kernel_split))
+            results.append(run("b_powerlaw", row_ptr, col, a.n_src, a.dim, a.warmup, a.reps, not a.no_kernel_split))
         elif shape == "c":
             rp, ci, n_src = c5_layer0(wgth, comm, a.nodes, 29, 1024, [30, 30])
-            results.append(run_shape("c_c5_layer0", rp, ci, n_src, a.dim, a.warmup, a.reps, not a.no_kernel_split))
+            results.append(run("c_c5_layer0", rp, ci, n_src, a.dim, a.warmup, a.reps, not a.no_kernel_split))
     line = {"bench": "sage_agg", "chunk_edges": chunk_edges(), "peak_Bps": PEAK, "results": results}
+    if a.dtype != "float32":
+        line["dtype"] = a.dtype
     by = {r["shape"]: r for r in results}
     if "a_uniform" in by and "b_powerlaw" in by and by["a_uniform"]["fold_ms"] and by["b_powerlaw"]["fold_ms"]:
         # at equal bytes: both shapes move the same algorithmic fold bytes (same E, n_src, n_dst, F)

@@ -278,6 +278,10 @@ PROTOTYPES = {
     "wholememory_ext_csc_aggregate_backward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i, _vp, _i64, _P(EnvFunc),
                                                    _vp]),
     "wholememory_ext_csc_aggregate_chunk_edges": (_i64, []),
+    "wholememory_ext_csc_aggregate_forward_typed": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i, _vp, _i64, _i,
+                                                        _P(EnvFunc), _vp]),
+    "wholememory_ext_csc_aggregate_backward_typed": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i, _vp, _i64, _i,
+                                                         _P(EnvFunc), _vp]),
     "wholememory_ext_csc_gat_forward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _i64, C.c_float, _i, _vp,
                                             _i64, _vp, _vp, _P(EnvFunc), _vp]),
     "wholememory_ext_csc_gat_backward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _i64, C.c_float, _i, _vp,

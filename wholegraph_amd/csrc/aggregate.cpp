@@ -1,6 +1,7 @@
 // wholegraph_amd — host side of the neighbour aggregation of a sampled CSC block (wholegraph_amd_ext.h, section 2b):
-// validation, the edge index of the backward (the library's id sort over col_ind) and the launches of kernels/agg.hip.
-// The semantics, and the one order of every fp32 sum, are stated in the header.
+// validation, the edge index of the backward (the library's id sort over col_ind) and the launches of kernels/agg.hip
+// (fp32 rows) and kernels/agg_half.hip (fp16 / bf16 rows, the _typed entry points). The semantics, and the one order of
+// every fp32 sum, are stated in the header.
 #include <wholememory/wholegraph_amd_ext.h>
 
 #include "ops_internal.hpp"
@@ -16,7 +17,7 @@ using namespace wm;
   } while (0)
 
 void check_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src,
-                const float* in, int64_t in_stride, int64_t in_cols, int64_t dim, int aggr, const float* out,
+                const void* in, int64_t in_stride, int64_t in_cols, int64_t dim, int aggr, const void* out,
                 int64_t out_stride, int64_t out_cols, int64_t in_rows, int64_t out_rows)
 {
   auto bad = [](const char* what) { throw invalid_input(what); };
@@ -46,6 +47,47 @@ wm_agg_args make_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_
   a.mean    = aggr == WHOLEMEMORY_EXT_AGGR_MEAN ? 1 : 0;
   return a;
 }
+
+// the edge index of a backward: a stable sort of col_ind (runs of one source, edge positions ascending in each run), then
+// launch(order, run_starts, unique_ids, n_unique_dev, workspace) with the workspace of agg_backward_workspace_bytes.
+// dedup_ids joins any side stream of its own before it returns (no deferred join asked for), so its outputs are ready for
+// the kernels queued behind it on `stream`
+template <class Launch>
+void backward_over_index(const wm_device_backend* bk, const int32_t* col_ind, int64_t E, int64_t n_src, int64_t dim,
+                         wholememory_env_func_t* p_env_fns, void* stream, Launch launch)
+{
+  temp_mem unique_mem(p_env_fns), starts_mem(p_env_fns), order_mem(p_env_fns), nu_mem(p_env_fns), sort_ws(p_env_fns),
+    agg_ws(p_env_fns);
+  auto* d_unique = static_cast<int32_t*>(unique_mem.device(E, WHOLEMEMORY_DT_INT));
+  auto* d_starts = static_cast<int32_t*>(starts_mem.device(E + 1, WHOLEMEMORY_DT_INT));
+  auto* d_order  = static_cast<int32_t*>(order_mem.device(E, WHOLEMEMORY_DT_INT));
+  auto* d_nu     = static_cast<int64_t*>(nu_mem.device(1, WHOLEMEMORY_DT_INT64));
+  void* d_sws    = sort_ws.device(static_cast<int64_t>(bk->dedup_workspace_bytes(E, WHOLEMEMORY_DT_INT)), WHOLEMEMORY_DT_INT8);
+  if (bk->device_error != nullptr && bk->device_error() != 0)
+    throw hip_error("an earlier id sort reported a device-side timeout (see the ERROR line above)");
+  const int rc = bk->dedup_ids(col_ind, WHOLEMEMORY_DT_INT, E, n_src, 0, d_unique, d_starts, d_order, d_nu, d_sws, stream);
+  if (rc == -1) throw logic_error("dedup_ids: unsupported index dtype or more than 2^31 edges");
+  if (rc != 0) throw hip_error("dedup_ids failed");
+  void* d_aws = agg_ws.device(static_cast<int64_t>(bk->agg_backward_workspace_bytes(E, n_src, dim)), WHOLEMEMORY_DT_INT8);
+  launch(d_order, d_starts, d_unique, d_nu, d_aws);
+}
+
+wm_agg16_args make_args16(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src,
+                          int64_t dim, int aggr, wholememory_dtype_t dtype)
+{
+  wm_agg16_args a{};
+  a.row_ptr = row_ptr;
+  a.col_ind = col_ind;
+  a.n_edges = n_dst == 0 ? 0 : n_edges;
+  a.n_dst   = n_dst;
+  a.n_src   = n_src;
+  a.dim     = dim;
+  a.mean    = aggr == WHOLEMEMORY_EXT_AGGR_MEAN ? 1 : 0;
+  a.dtype   = dtype;
+  return a;
+}
+
+bool rows16(wholememory_dtype_t dtype) { return dtype == WHOLEMEMORY_DT_HALF || dtype == WHOLEMEMORY_DT_BF16; }
 
 }  // namespace
 
@@ -89,24 +131,67 @@ wholememory_error_code_t wholememory_ext_csc_aggregate_backward(const int32_t* r
   a.out         = grad_x;
   a.out_stride  = grad_x_stride;
   if (n_src == 0) return WHOLEMEMORY_SUCCESS;
-  const int64_t E = a.n_edges;
-  // the edge index: a stable sort of col_ind (runs of one source, edge positions ascending in each run). dedup_ids joins
-  // any side stream of its own before it returns (no deferred join asked for), so its outputs are ready for the kernels
-  // queued behind it on `stream`
-  temp_mem unique_mem(p_env_fns), starts_mem(p_env_fns), order_mem(p_env_fns), nu_mem(p_env_fns), sort_ws(p_env_fns),
-    agg_ws(p_env_fns);
-  auto* d_unique = static_cast<int32_t*>(unique_mem.device(E, WHOLEMEMORY_DT_INT));
-  auto* d_starts = static_cast<int32_t*>(starts_mem.device(E + 1, WHOLEMEMORY_DT_INT));
-  auto* d_order  = static_cast<int32_t*>(order_mem.device(E, WHOLEMEMORY_DT_INT));
-  auto* d_nu     = static_cast<int64_t*>(nu_mem.device(1, WHOLEMEMORY_DT_INT64));
-  void* d_sws    = sort_ws.device(static_cast<int64_t>(bk->dedup_workspace_bytes(E, WHOLEMEMORY_DT_INT)), WHOLEMEMORY_DT_INT8);
-  if (bk->device_error != nullptr && bk->device_error() != 0)
-    throw hip_error("an earlier id sort reported a device-side timeout (see the ERROR line above)");
-  const int rc = bk->dedup_ids(col_ind, WHOLEMEMORY_DT_INT, E, n_src, 0, d_unique, d_starts, d_order, d_nu, d_sws, stream);
-  if (rc == -1) throw logic_error("dedup_ids: unsupported index dtype or more than 2^31 edges");
-  if (rc != 0) throw hip_error("dedup_ids failed");
-  void* d_aws = agg_ws.device(static_cast<int64_t>(bk->agg_backward_workspace_bytes(E, n_src, dim)), WHOLEMEMORY_DT_INT8);
-  WM_BK(bk->agg_backward(&a, d_order, d_starts, d_unique, d_nu, d_aws, stream));
+  backward_over_index(bk, col_ind, a.n_edges, n_src, dim, p_env_fns, stream,
+                      [&](const int32_t* order, const int32_t* starts, const int32_t* unique, const int64_t* nu, void* ws) {
+                        WM_BK(bk->agg_backward(&a, order, starts, unique, nu, ws, stream));
+                      });
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+wholememory_error_code_t wholememory_ext_csc_aggregate_forward_typed(const int32_t* row_ptr, const int32_t* col_ind,
+                                                                     int64_t n_edges, int64_t n_dst, int64_t n_src,
+                                                                     const void* x, int64_t x_stride, int64_t dim, int aggr,
+                                                                     void* out, int64_t out_stride, wholememory_dtype_t dtype,
+                                                                     wholememory_env_func_t* p_env_fns, void* stream)
+{
+  if (dtype == WHOLEMEMORY_DT_FLOAT)
+    return wholememory_ext_csc_aggregate_forward(row_ptr, col_ind, n_edges, n_dst, n_src, static_cast<const float*>(x),
+                                                 x_stride, dim, aggr, static_cast<float*>(out), out_stride, p_env_fns, stream);
+  WM_API_BEGIN
+  (void)p_env_fns;
+  if (!rows16(dtype)) throw invalid_input("dtype must be FLOAT, HALF or BF16");
+  const auto* bk = backend();
+  if (bk->agg16_forward == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, x, x_stride, dim, dim, aggr, out, out_stride, 2 * dim, n_src, n_dst);
+  wm_agg16_args a = make_args16(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr, dtype);
+  a.in            = x;
+  a.in_stride     = x_stride;
+  a.out           = out;
+  a.out_stride    = out_stride;
+  WM_BK(bk->agg16_forward(&a, stream));
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+wholememory_error_code_t wholememory_ext_csc_aggregate_backward_typed(const int32_t* row_ptr, const int32_t* col_ind,
+                                                                      int64_t n_edges, int64_t n_dst, int64_t n_src,
+                                                                      const void* grad_out, int64_t grad_out_stride,
+                                                                      int64_t dim, int aggr, void* grad_x,
+                                                                      int64_t grad_x_stride, wholememory_dtype_t dtype,
+                                                                      wholememory_env_func_t* p_env_fns, void* stream)
+{
+  if (dtype == WHOLEMEMORY_DT_FLOAT)
+    return wholememory_ext_csc_aggregate_backward(row_ptr, col_ind, n_edges, n_dst, n_src,
+                                                  static_cast<const float*>(grad_out), grad_out_stride, dim, aggr,
+                                                  static_cast<float*>(grad_x), grad_x_stride, p_env_fns, stream);
+  WM_API_BEGIN
+  if (!rows16(dtype)) throw invalid_input("dtype must be FLOAT, HALF or BF16");
+  const auto* bk = backend();
+  if (bk->agg16_backward == nullptr || bk->agg_backward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, grad_out, grad_out_stride, 2 * dim, dim, aggr, grad_x, grad_x_stride,
+             dim, n_dst, n_src);
+  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
+  wm_agg16_args a = make_args16(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr, dtype);
+  a.grad          = grad_out;
+  a.grad_stride   = grad_out_stride;
+  a.out           = grad_x;
+  a.out_stride    = grad_x_stride;
+  if (n_src == 0) return WHOLEMEMORY_SUCCESS;
+  backward_over_index(bk, col_ind, a.n_edges, n_src, dim, p_env_fns, stream,
+                      [&](const int32_t* order, const int32_t* starts, const int32_t* unique, const int64_t* nu, void* ws) {
+                        WM_BK(bk->agg16_backward(&a, order, starts, unique, nu, ws, stream));
+                      });
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }

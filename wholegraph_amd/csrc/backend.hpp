@@ -189,6 +189,22 @@ struct wm_agg_args {
   int64_t out_stride;
 };
 
+// the same op on rows of 16-bit floats (kernels/agg_half.hip): `dtype` is WHOLEMEMORY_DT_HALF or WHOLEMEMORY_DT_BF16 and is
+// the type of in, grad and out alike; strides / dim in ELEMENTS of it. Sums are fp32, each output element rounded once.
+struct wm_agg16_args {
+  const int32_t* row_ptr;   // [n_dst + 1]
+  const int32_t* col_ind;   // [n_edges], ids in [0, n_src)
+  int64_t n_edges, n_dst, n_src, dim;
+  int mean;
+  wholememory_dtype_t dtype;
+  const void* in;           // forward: x [n_src, in_stride]
+  int64_t in_stride;
+  const void* grad;         // backward: dL/dout [n_dst, grad_stride], 2 * dim columns used
+  int64_t grad_stride;
+  void* out;                // forward: out [n_dst, out_stride] (2 * dim columns); backward: grad_x [n_src, out_stride]
+  int64_t out_stride;
+};
+
 // multi-head graph attention of a sampled CSC block (kernels/gat.hip, the GAT `mha_gat_n2n` op): rows / strides in
 // ELEMENTS (fp32); head k owns columns [k * dim, (k + 1) * dim) of a row of h
 struct wm_gat_args {
@@ -412,6 +428,12 @@ struct wm_device_backend {
   size_t (*gat_backward_workspace_bytes)(const wm_gat_args* a);
   int (*gat_backward)(const wm_gat_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
                       const int64_t* n_unique_dev, void* workspace, void* stream);
+  // ---- agg_forward / agg_backward on fp16 / bf16 rows (kernels/agg_half.hip); nullptr in a backend without them ----
+  // the same sums in fp32 in the same order, one rounding per output element; the backward takes the index and the
+  // workspace of agg_backward (agg_backward_workspace_bytes: the partial rows of chunks stay fp32)
+  int (*agg16_forward)(const wm_agg16_args* a, void* stream);
+  int (*agg16_backward)(const wm_agg16_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                        const int64_t* n_unique_dev, void* workspace, void* stream);
 };
 
 }  // extern "C"

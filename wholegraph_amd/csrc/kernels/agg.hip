@@ -17,6 +17,8 @@
 //   4 agg_bwd_fold_kernel: one group per source row: chunk 0 of its run, then the partials of chunks 1, 2, ... in chunk
 //     order, then the self term G[s, F:2F] for s < n_dst; rows without edges get the self term or +0.0.
 // run_of[] is not initialised: a value is used only when 0 <= u < n_unique and unique[u] == s (a sparse-set check).
+// Steps 1 and 2 do not depend on the type of the rows: agg_bwd_prepare (below) is shared with kernels/agg_half.hip, the
+// same op on fp16 / bf16 rows.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -25,18 +27,6 @@
 
 namespace wm {
 namespace {
-
-// backward scratch: the id sort's outputs and this op's workspace (hip_agg_backward carves it)
-struct wm_agg_bwd_state {
-  const int32_t* order;        // [n_edges] edge positions, sorted by source (stable)
-  const int32_t* run_starts;   // [n_unique + 1]
-  const int32_t* unique_ids;   // [n_unique] sources with edges, ascending
-  const int64_t* n_unique;     // device scalar written by the sort
-  int32_t* sorted_dst;         // [n_edges]
-  int32_t* run_of;             // [n_src]
-  float* partial;              // [n_tiles, partial_stride]
-  int64_t n_tiles, partial_stride;
-};
 
 // -0.0 is the identity of IEEE addition: acc = -0.0 followed by acc + t_0 + t_1 + ... is the left-to-right sum that starts
 // from the first term (also when that term is -0.0)
@@ -218,31 +208,39 @@ size_t hip_agg_backward_workspace_bytes(int64_t n_edges, int64_t n_src, int64_t 
   return static_cast<size_t>(n_edges + n_src + 64) * 4 + 256 + static_cast<size_t>(tiles * pstr) * 4;
 }
 
+int agg_bwd_prepare(const wm_agg_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                    const int64_t* n_unique_dev, void* workspace, wm_agg_bwd_state* bp, void* stream_v)
+{
+  hipStream_t stream  = static_cast<hipStream_t>(stream_v);
+  wm_agg_bwd_state& b = *bp;
+  b.order             = order;
+  b.run_starts        = run_starts;
+  b.unique_ids        = unique_ids;
+  b.n_unique          = n_unique_dev;
+  b.n_tiles           = (a->n_edges + kAggChunkEdges - 1) / kAggChunkEdges;
+  b.partial_stride    = (a->dim + 3) / 4 * 4;
+  auto up16           = [](uintptr_t v) { return (v + 255) & ~static_cast<uintptr_t>(255); };
+  uintptr_t w         = up16(reinterpret_cast<uintptr_t>(workspace));
+  b.sorted_dst        = reinterpret_cast<int32_t*>(w);
+  w                   = up16(w + static_cast<uintptr_t>(a->n_edges) * 4);
+  b.run_of            = reinterpret_cast<int32_t*>(w);
+  w                   = up16(w + static_cast<uintptr_t>(a->n_src) * 4);
+  b.partial           = reinterpret_cast<float*>(w);
+  if (a->n_edges > 0) {
+    const int blocks = blocks_for(a->n_edges, kAggBlock);
+    hipLaunchKernelGGL(agg_bwd_prep_kernel, dim3(blocks < 8192 ? blocks : 8192), dim3(kAggBlock), 0, stream, *a, b);
+    if (rc_last() != 0) return -2;
+  }
+  return 0;
+}
+
 int hip_agg_backward(const wm_agg_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
                      const int64_t* n_unique_dev, void* workspace, void* stream_v)
 {
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   if (a->n_src == 0 || a->dim == 0) return 0;
   wm_agg_bwd_state b;
-  b.order          = order;
-  b.run_starts     = run_starts;
-  b.unique_ids     = unique_ids;
-  b.n_unique       = n_unique_dev;
-  b.n_tiles        = (a->n_edges + kAggChunkEdges - 1) / kAggChunkEdges;
-  b.partial_stride = (a->dim + 3) / 4 * 4;
-  auto up16        = [](uintptr_t v) { return (v + 255) & ~static_cast<uintptr_t>(255); };
-  uintptr_t w      = up16(reinterpret_cast<uintptr_t>(workspace));
-  b.sorted_dst     = reinterpret_cast<int32_t*>(w);
-  w                = up16(w + static_cast<uintptr_t>(a->n_edges) * 4);
-  b.run_of         = reinterpret_cast<int32_t*>(w);
-  w                = up16(w + static_cast<uintptr_t>(a->n_src) * 4);
-  b.partial        = reinterpret_cast<float*>(w);
-
-  if (a->n_edges > 0) {
-    const int blocks = blocks_for(a->n_edges, kAggBlock);
-    hipLaunchKernelGGL(agg_bwd_prep_kernel, dim3(blocks < 8192 ? blocks : 8192), dim3(kAggBlock), 0, stream, *a, b);
-    if (rc_last() != 0) return -2;
-  }
+  if (agg_bwd_prepare(a, order, run_starts, unique_ids, n_unique_dev, workspace, &b, stream_v) != 0) return -2;
   const bool v4 = use_vec4(a->dim, a->grad, a->grad_stride, a->out, a->out_stride);
   if (b.n_tiles > 1) {   // (one tile holds no chunk k >= 1)
 #define WM_AGG_CHUNK(V, L)                                                                                                   \

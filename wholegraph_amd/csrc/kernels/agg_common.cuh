@@ -1,5 +1,6 @@
 // wholegraph_amd — device and launch helpers shared by the aggregation ops of a sampled CSC block (kernels/agg.hip, the
-// GraphSAGE `agg_concat` op; kernels/gat.hip, the GAT `mha_gat_n2n` op): fp32 pieces of a row, the clamped edge range of a
+// GraphSAGE `agg_concat` op, and kernels/agg_half.hip, the same op on fp16 / bf16 rows; kernels/gat.hip, the GAT
+// `mha_gat_n2n` op): fp32 pieces of a row, the clamped edge range of a
 // target, the lookups of the deterministic per-source backward over the id sort, and the launch shape.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -8,6 +9,24 @@
 #include "../backend.hpp"
 
 namespace wm {
+
+// scratch of the agg_concat backward: the id sort's outputs and the op's workspace (agg_bwd_prepare carves it)
+struct wm_agg_bwd_state {
+  const int32_t* order;        // [n_edges] edge positions, sorted by source (stable)
+  const int32_t* run_starts;   // [n_unique + 1]
+  const int32_t* unique_ids;   // [n_unique] sources with edges, ascending
+  const int64_t* n_unique;     // device scalar written by the sort
+  int32_t* sorted_dst;         // [n_edges]
+  int32_t* run_of;             // [n_src]
+  float* partial;              // [n_tiles, partial_stride] fp32, whatever the type of the rows
+  int64_t n_tiles, partial_stride;
+};
+
+// fills `b` from the id sort's outputs and `workspace` (hip_agg_backward_workspace_bytes) and queues agg_bwd_prep_kernel
+// (kernels/agg.hip), which reads only the index part of `a`: row_ptr, n_dst, n_edges, n_src, dim. 0 or -2.
+int agg_bwd_prepare(const wm_agg_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                    const int64_t* n_unique_dev, void* workspace, wm_agg_bwd_state* b, void* stream);
+
 namespace {
 
 constexpr int kAggBlock = 256;

@@ -1,0 +1,377 @@
+// wholegraph_amd — the GraphSAGE `agg_concat` op (kernels/agg.hip) on rows of 16-bit floats, fp16 or bf16, on gfx950.
+//
+// x, out, grad_out and grad_x all hold T. Every sum is the fp32 sum of kernels/agg.hip, term by term in the same order
+// (widening T -> fp32 is exact), and each output element is rounded to T once, to nearest even, at the store: the running
+// sum never lives in T. So op_T(x) == round_T(op_fp32(fp32(x))) bit for bit, forward and backward. Rows that are only
+// copied (the target's own row of the forward, a self term without edges in the backward) keep their bits.
+//
+// Same structure as the fp32 kernels: one group of 16 / 32 / 64 lanes per row, sized from the row's 16-byte pieces (a
+// piece is 8 elements here: F = 128 is 16 pieces) or, on the element-wise path, from its elements; column ids loaded
+// coalesced and handed out with shuffles; the rows of a batch of kAggBatch edges issued back to back as raw pieces and
+// widened when they are added. The edge index, agg_bwd_prep_kernel and the fp32 partial rows of chunks are those of
+// kernels/agg.hip (agg_bwd_prepare).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../backend.hpp"
+#include "agg_common.cuh"
+
+namespace wm {
+// the two row types (tags: a row is handled as raw 16-bit words)
+struct f16_rows {};
+struct bf16_rows {};
+
+namespace {
+
+// ---- conversions: T -> fp32 exact; fp32 -> T round to nearest even, once
+template <class T>
+__device__ __forceinline__ float widen(uint32_t h);   // h: the 16 bits of one element, in the low half
+template <>
+__device__ __forceinline__ float widen<bf16_rows>(uint32_t h)
+{
+  return __uint_as_float(h << 16);
+}
+template <>
+__device__ __forceinline__ float widen<f16_rows>(uint32_t h)
+{
+  const uint16_t s = static_cast<uint16_t>(h);
+  _Float16 v;
+  __builtin_memcpy(&v, &s, 2);
+  return static_cast<float>(v);   // (subnormals included: fp16 denormals are not flushed in this mode)
+}
+
+template <class T>
+__device__ __forceinline__ uint32_t narrow(float f);   // the 16 bits of round_T(f), in the low half
+template <>
+__device__ __forceinline__ uint32_t narrow<bf16_rows>(float f)
+{
+  const uint32_t u = __float_as_uint(f);
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (u >> 16) | 0x0040u;   // NaN stays NaN (made quiet)
+  return (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;                     // ties to even; past the largest finite: inf
+}
+template <>
+__device__ __forceinline__ uint32_t narrow<f16_rows>(float f)
+{
+  const _Float16 v = static_cast<_Float16>(f);   // IEEE: ties to even, overflow to inf, subnormal results kept
+  uint16_t s;
+  __builtin_memcpy(&s, &v, 2);
+  return s;
+}
+
+// ---- a lane's raw piece of a row: VEC == 8: 16 bytes (element 2i in the low half of word i); VEC == 1: one element
+template <int VEC>
+struct hraw {
+  uint32_t w[VEC == 8 ? 4 : 1];
+};
+
+template <int VEC>
+__device__ __forceinline__ hraw<VEC> ldh(const uint16_t* p)
+{
+  hraw<VEC> r;
+  if constexpr (VEC == 8) {
+    const uint4 t = *reinterpret_cast<const uint4*>(p);
+    r.w[0] = t.x, r.w[1] = t.y, r.w[2] = t.z, r.w[3] = t.w;
+  } else {
+    r.w[0] = *p;
+  }
+  return r;
+}
+
+template <int VEC>
+__device__ __forceinline__ void sth(uint16_t* p, const hraw<VEC>& a)
+{
+  if constexpr (VEC == 8) *reinterpret_cast<uint4*>(p) = make_uint4(a.w[0], a.w[1], a.w[2], a.w[3]);
+  else *p = static_cast<uint16_t>(a.w[0]);
+}
+
+template <class T, int VEC>
+__device__ __forceinline__ fvec<VEC> widened(const hraw<VEC>& a)
+{
+  fvec<VEC> r;
+  if constexpr (VEC == 8) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r.v[2 * i] = widen<T>(a.w[i] & 0xffffu), r.v[2 * i + 1] = widen<T>(a.w[i] >> 16);
+  } else {
+    r.v[0] = widen<T>(a.w[0]);
+  }
+  return r;
+}
+
+template <class T, int VEC>
+__device__ __forceinline__ hraw<VEC> narrowed(const fvec<VEC>& a)
+{
+  hraw<VEC> r;
+  if constexpr (VEC == 8) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r.w[i] = narrow<T>(a.v[2 * i]) | (narrow<T>(a.v[2 * i + 1]) << 16);
+  } else {
+    r.w[0] = narrow<T>(a.v[0]);
+  }
+  return r;
+}
+
+template <int VEC>
+__device__ __forceinline__ hraw<VEC> zero_raw()
+{
+  hraw<VEC> r;
+#pragma unroll
+  for (int i = 0; i < (VEC == 8 ? 4 : 1); ++i) r.w[i] = 0u;
+  return r;
+}
+
+// fp32 pieces of a partial row (the workspace): VEC floats, as 16-byte accesses when VEC == 8
+template <int VEC>
+__device__ __forceinline__ fvec<VEC> ldp(const float* p)
+{
+  if constexpr (VEC == 8) {
+    const fvec<4> lo = ldv<4>(p), hi = ldv<4>(p + 4);
+    fvec<8> r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r.v[i] = lo.v[i], r.v[4 + i] = hi.v[i];
+    return r;
+  } else {
+    return ldv<VEC>(p);
+  }
+}
+
+template <int VEC>
+__device__ __forceinline__ void stp(float* p, const fvec<VEC>& a)
+{
+  if constexpr (VEC == 8) {
+    fvec<4> lo, hi;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) lo.v[i] = a.v[i], hi.v[i] = a.v[4 + i];
+    stv(p, lo);
+    stv(p + 4, hi);
+  } else {
+    stv(p, a);
+  }
+}
+
+template <class T, int VEC, int LANES>
+__global__ __launch_bounds__(kAggBlock) void agg16_forward_kernel(wm_agg16_args p)
+{
+  constexpr int kGroups = kAggBlock / LANES;
+  const int gl          = threadIdx.x % LANES;
+  const int64_t F       = p.dim;
+  const uint16_t* in    = static_cast<const uint16_t*>(p.in);
+  uint16_t* out         = static_cast<uint16_t*>(p.out);
+  for (int64_t d = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; d < p.n_dst;
+       d += static_cast<int64_t>(gridDim.x) * kGroups) {
+    int64_t e0, e1;
+    edge_range(p.row_ptr, d, p.n_edges, e0, e1);
+    const int64_t deg    = e1 - e0;
+    const float r        = deg > 0 ? 1.0f / static_cast<float>(deg) : 0.0f;
+    const uint16_t* self = in + d * p.in_stride;
+    uint16_t* orow       = out + d * p.out_stride;
+    for (int64_t cb = 0; cb < F; cb += LANES * VEC) {   // (group-uniform trip count: the shuffles below stay in step)
+      const int64_t c  = cb + gl * VEC;
+      const bool act   = c < F;
+      const int64_t cl = act ? c : 0;
+      fvec<VEC> acc    = splat<VEC>(-0.0f);
+      for (int64_t eb = e0; eb < e1; eb += LANES) {
+        const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
+        const int my = gl < nb ? p.col_ind[eb + gl] : 0;
+        for (int j = 0; j < nb; j += kAggBatch) {
+          hraw<VEC> v[kAggBatch];
+#pragma unroll
+          for (int k = 0; k < kAggBatch; ++k) {
+            const int src = __shfl(my, j + k < nb ? j + k : nb - 1, LANES);
+            v[k]          = ldh<VEC>(in + static_cast<int64_t>(src) * p.in_stride + cl);
+          }
+#pragma unroll
+          for (int k = 0; k < kAggBatch; ++k)
+            if (j + k < nb) add_to(acc, widened<T, VEC>(v[k]));
+        }
+      }
+      if (act) {
+        sth(orow + c, deg == 0 ? zero_raw<VEC>() : narrowed<T, VEC>(p.mean ? scaled(acc, r) : acc));
+        sth(orow + F + c, ldh<VEC>(self + c));
+      }
+    }
+  }
+}
+
+// acc += t(e) for the edges at sorted positions [eb0, ee), in that order (LANES lanes, this lane's columns at cl)
+template <class T, int VEC, int LANES>
+__device__ __forceinline__ void fold_edges16(fvec<VEC>& acc, const wm_agg16_args& p, const int32_t* sorted_dst, int64_t eb0,
+                                             int64_t ee, int64_t cl, int gl)
+{
+  const uint16_t* grad = static_cast<const uint16_t*>(p.grad);
+  for (int64_t eb = eb0; eb < ee; eb += LANES) {
+    const int nb = static_cast<int>(ee - eb < LANES ? ee - eb : LANES);
+    int my_d     = 0;
+    float my_r   = 1.0f;
+    if (gl < nb) {
+      my_d = sorted_dst[eb + gl];
+      if (p.mean) my_r = 1.0f / static_cast<float>(p.row_ptr[my_d + 1] - p.row_ptr[my_d]);
+    }
+    for (int j = 0; j < nb; j += kAggBatch) {
+      hraw<VEC> v[kAggBatch];
+      float rs[kAggBatch];
+#pragma unroll
+      for (int k = 0; k < kAggBatch; ++k) {
+        const int from = j + k < nb ? j + k : nb - 1;
+        const int d    = __shfl(my_d, from, LANES);
+        rs[k]          = __shfl(my_r, from, LANES);
+        v[k]           = ldh<VEC>(grad + static_cast<int64_t>(d) * p.grad_stride + cl);
+      }
+#pragma unroll
+      for (int k = 0; k < kAggBatch; ++k)
+        if (j + k < nb) add_to(acc, p.mean ? scaled(widened<T, VEC>(v[k]), rs[k]) : widened<T, VEC>(v[k]));
+    }
+  }
+}
+
+template <class T, int VEC, int LANES>
+__global__ __launch_bounds__(kAggBlock) void agg16_bwd_chunk_kernel(wm_agg16_args p, wm_agg_bwd_state b)
+{
+  constexpr int kGroups = kAggBlock / LANES;
+  const int gl          = threadIdx.x % LANES;
+  const int64_t F       = p.dim;
+  const int64_t nu      = *b.n_unique;
+  if (nu == 0) return;
+  for (int64_t t = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; t < b.n_tiles;
+       t += static_cast<int64_t>(gridDim.x) * kGroups) {
+    int64_t cs, ce;
+    if (!chunk_in_tile(t, b.run_starts, nu, cs, ce)) continue;
+    for (int64_t cb = 0; cb < F; cb += LANES * VEC) {
+      const int64_t c  = cb + gl * VEC;
+      const bool act   = c < F;
+      const int64_t cl = act ? c : 0;
+      fvec<VEC> acc    = splat<VEC>(-0.0f);
+      fold_edges16<T, VEC, LANES>(acc, p, b.sorted_dst, cs, ce, cl, gl);
+      if (act) stp(b.partial + t * b.partial_stride + c, acc);   // (the partial row stays fp32)
+    }
+  }
+}
+
+template <class T, int VEC, int LANES>
+__global__ __launch_bounds__(kAggBlock) void agg16_bwd_fold_kernel(wm_agg16_args p, wm_agg_bwd_state b)
+{
+  constexpr int kGroups = kAggBlock / LANES;
+  constexpr int64_t C   = kAggChunkEdges;
+  const int gl          = threadIdx.x % LANES;
+  const int64_t F       = p.dim;
+  const int64_t nu      = *b.n_unique;
+  const uint16_t* grad  = static_cast<const uint16_t*>(p.grad);
+  uint16_t* out         = static_cast<uint16_t*>(p.out);
+  for (int64_t s = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; s < p.n_src;
+       s += static_cast<int64_t>(gridDim.x) * kGroups) {
+    const int64_t u = b.run_of[s];   // (uninitialised unless s has edges: checked against unique_ids)
+    const bool has  = u >= 0 && u < nu && b.unique_ids[u] == s;
+    int64_t s0 = 0, s1 = 0;
+    if (has) s0 = b.run_starts[u], s1 = b.run_starts[u + 1];
+    const int64_t c0e     = s1 - s0 > C ? s0 + C : s1;
+    const int64_t nchunks = (s1 - s0 + C - 1) / C;
+    const bool self       = s < p.n_dst;
+    for (int64_t cb = 0; cb < F; cb += LANES * VEC) {
+      const int64_t c  = cb + gl * VEC;
+      const bool act   = c < F;
+      const int64_t cl = act ? c : 0;
+      fvec<VEC> acc    = splat<VEC>(-0.0f);
+      fold_edges16<T, VEC, LANES>(acc, p, b.sorted_dst, s0, c0e, cl, gl);
+      for (int64_t k0 = 1; k0 < nchunks; k0 += kAggBatch) {   // partials in chunk order, a batch of them in flight
+        fvec<VEC> v[kAggBatch];
+#pragma unroll
+        for (int k = 0; k < kAggBatch; ++k) {
+          const int64_t kk = k0 + k < nchunks ? k0 + k : nchunks - 1;
+          v[k]             = ldp<VEC>(b.partial + ((s0 + kk * C) / C) * b.partial_stride + cl);
+        }
+#pragma unroll
+        for (int k = 0; k < kAggBatch; ++k)
+          if (k0 + k < nchunks) add_to(acc, v[k]);
+      }
+      hraw<VEC> res = zero_raw<VEC>();
+      if (self) {
+        res = ldh<VEC>(grad + s * p.grad_stride + F + cl);   // only the self term: its bits
+        if (has) {
+          add_to(acc, widened<T, VEC>(res));
+          res = narrowed<T, VEC>(acc);
+        }
+      } else if (has) {
+        res = narrowed<T, VEC>(acc);
+      }
+      if (act) sth(out + s * p.out_stride + c, res);
+    }
+  }
+}
+
+// 16-byte pieces when every row start is 16-byte aligned (8 elements a piece)
+bool use_vec8(int64_t dim, const void* a, int64_t a_stride, const void* b, int64_t b_stride)
+{
+  return dim % 8 == 0 && a_stride % 8 == 0 && b_stride % 8 == 0 && reinterpret_cast<uintptr_t>(a) % 16 == 0 &&
+         reinterpret_cast<uintptr_t>(b) % 16 == 0;
+}
+
+#define WM_AGG16_LANES(T_, V_, PIECES_, LAUNCH_)  \
+  do {                                            \
+    const int lanes__ = lanes_for(PIECES_);       \
+    if (lanes__ == 16) LAUNCH_(T_, V_, 16);       \
+    else if (lanes__ == 32) LAUNCH_(T_, V_, 32);  \
+    else LAUNCH_(T_, V_, 64);                     \
+  } while (0)
+
+#define WM_AGG16_DISPATCH(BF16_, VEC_, DIM_, LAUNCH_)                  \
+  do {                                                                 \
+    if (BF16_) {                                                       \
+      if (VEC_) WM_AGG16_LANES(bf16_rows, 8, (DIM_) / 8, LAUNCH_);     \
+      else WM_AGG16_LANES(bf16_rows, 1, DIM_, LAUNCH_);                \
+    } else {                                                           \
+      if (VEC_) WM_AGG16_LANES(f16_rows, 8, (DIM_) / 8, LAUNCH_);      \
+      else WM_AGG16_LANES(f16_rows, 1, DIM_, LAUNCH_);                 \
+    }                                                                  \
+  } while (0)
+
+}  // namespace
+
+int hip_agg16_forward(const wm_agg16_args* a, void* stream_v)
+{
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  if (a->dtype != WHOLEMEMORY_DT_HALF && a->dtype != WHOLEMEMORY_DT_BF16) return -1;
+  if (a->n_dst == 0 || a->dim == 0) return 0;
+  const bool bf = a->dtype == WHOLEMEMORY_DT_BF16;
+  const bool v8 = use_vec8(a->dim, a->in, a->in_stride, a->out, a->out_stride);
+#define WM_AGG16_FWD(T, V, L)                                                                                         \
+  hipLaunchKernelGGL((agg16_forward_kernel<T, V, L>), dim3(blocks_for(a->n_dst, kAggBlock / (L))), dim3(kAggBlock), 0, \
+                     stream, *a)
+  WM_AGG16_DISPATCH(bf, v8, a->dim, WM_AGG16_FWD);
+#undef WM_AGG16_FWD
+  return rc_last();
+}
+
+int hip_agg16_backward(const wm_agg16_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                       const int64_t* n_unique_dev, void* workspace, void* stream_v)
+{
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  if (a->dtype != WHOLEMEMORY_DT_HALF && a->dtype != WHOLEMEMORY_DT_BF16) return -1;
+  if (a->n_src == 0 || a->dim == 0) return 0;
+  wm_agg_args ix{};   // the index part, all that the shared prepare step reads
+  ix.row_ptr = a->row_ptr;
+  ix.col_ind = a->col_ind;
+  ix.n_edges = a->n_edges;
+  ix.n_dst   = a->n_dst;
+  ix.n_src   = a->n_src;
+  ix.dim     = a->dim;
+  ix.mean    = a->mean;
+  wm_agg_bwd_state b;
+  if (agg_bwd_prepare(&ix, order, run_starts, unique_ids, n_unique_dev, workspace, &b, stream_v) != 0) return -2;
+  const bool bf = a->dtype == WHOLEMEMORY_DT_BF16;
+  const bool v8 = use_vec8(a->dim, a->grad, a->grad_stride, a->out, a->out_stride);
+  if (b.n_tiles > 1) {   // (one tile holds no chunk k >= 1)
+#define WM_AGG16_CHUNK(T, V, L)                                                                                          \
+  hipLaunchKernelGGL((agg16_bwd_chunk_kernel<T, V, L>), dim3(blocks_for(b.n_tiles, kAggBlock / (L))), dim3(kAggBlock), 0, \
+                     stream, *a, b)
+    WM_AGG16_DISPATCH(bf, v8, a->dim, WM_AGG16_CHUNK);
+#undef WM_AGG16_CHUNK
+    if (rc_last() != 0) return -2;
+  }
+#define WM_AGG16_FOLD(T, V, L)                                                                                         \
+  hipLaunchKernelGGL((agg16_bwd_fold_kernel<T, V, L>), dim3(blocks_for(a->n_src, kAggBlock / (L))), dim3(kAggBlock), 0, \
+                     stream, *a, b)
+  WM_AGG16_DISPATCH(bf, v8, a->dim, WM_AGG16_FOLD);
+#undef WM_AGG16_FOLD
+  return rc_last();
+}
+
+}  // namespace wm

@@ -1,10 +1,17 @@
 """Neighbour aggregation of a sampled CSC block — the ``agg_concat`` op behind the GraphSAGE layer
-(``wholememory_ext_csc_aggregate_forward`` / ``_backward``, kernels in ``csrc/kernels/agg.hip``).
+(``wholememory_ext_csc_aggregate_forward_typed`` / ``_backward_typed``, kernels in ``csrc/kernels/agg.hip`` for fp32 rows
+and ``csrc/kernels/agg_half.hip`` for fp16 / bf16 rows).
 
 ``agg_concat(x, row_ptr, col_ind, aggr)`` returns ``[n_dst, 2F]``: the sum (or mean) of each target's neighbour rows of
 ``x``, then the target's own row (the targets are the first ``n_dst`` rows of ``x``, as ``append_unique`` leaves them).
 Every fp32 sum, forward and backward, is taken in one fixed order (stated in ``include/wholememory/wholegraph_amd_ext.h``),
-so results are bitwise reproducible."""
+so results are bitwise reproducible.
+
+``x`` may be float32, float16 or bfloat16; ``out`` and the gradient of ``x`` have its dtype. With 16-bit rows the sums are
+still taken in fp32, in the same order, and each output element is rounded once (to nearest even): the result equals the
+fp32 op on ``x.float()`` rounded to ``x.dtype``, bit for bit. The op has no autocast rule of its own: inside
+``torch.autocast`` it runs in the dtype its input arrives in, so a layer fed by an autocast ``Linear`` aggregates 16-bit
+rows and one fed by fp32 features aggregates fp32 rows."""
 import ctypes as C
 
 import torch
@@ -13,6 +20,7 @@ from .. import binding as wmb
 from .wholegraph_env import get_stream, get_wholegraph_env_fns
 
 _AGGR = {"sum": wmb.AGGR_SUM, "mean": wmb.AGGR_MEAN}
+_ROW_DTYPES = {torch.float32: wmb.DT_FLOAT, torch.float16: wmb.DT_HALF, torch.bfloat16: wmb.DT_BF16}
 
 
 def aggr_code(aggr: str) -> int:
@@ -28,10 +36,10 @@ def chunk_edges() -> int:
     return int(wmb.lib().wholememory_ext_csc_aggregate_chunk_edges())
 
 
-def _rows(t: torch.Tensor, what: str) -> torch.Tensor:
-    """a 2-D fp32 tensor whose rows are unit-stride (a row stride of its own is fine)"""
-    if t.dtype != torch.float32:
-        raise TypeError("%s must be float32 (got %s)" % (what, t.dtype))
+def _rows(t: torch.Tensor, what: str, dtypes=(torch.float32,)) -> torch.Tensor:
+    """a 2-D tensor of one of `dtypes` whose rows are unit-stride (a row stride of its own is fine)"""
+    if t.dtype not in dtypes:
+        raise TypeError("%s must be %s (got %s)" % (what, " or ".join(str(d).replace("torch.", "") for d in dtypes), t.dtype))
     if t.dim() != 2:
         raise ValueError("%s must be 2-D (got shape %s)" % (what, tuple(t.shape)))
     if (t.shape[1] > 1 and t.stride(1) != 1) or t.stride(0) < t.shape[1]:
@@ -61,13 +69,14 @@ class CscAggregateConcat(torch.autograd.Function):
     def forward(ctx, x, row_ptr, col_ind, aggr_code_):
         n_src, dim = x.shape
         n_dst = row_ptr.shape[0] - 1
-        out = torch.empty((n_dst, 2 * dim), dtype=torch.float32, device=x.device)
-        wmb.check(wmb.lib().wholememory_ext_csc_aggregate_forward(
+        out = torch.empty((n_dst, 2 * dim), dtype=x.dtype, device=x.device)
+        wmb.check(wmb.lib().wholememory_ext_csc_aggregate_forward_typed(
             _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, _ptr(x), x.stride(0) if n_src else dim, dim,
-            aggr_code_, _ptr(out), out.stride(0) if n_dst else 2 * dim, get_wholegraph_env_fns(), C.c_void_p(get_stream())),
-            "csc_aggregate_forward")
+            aggr_code_, _ptr(out), out.stride(0) if n_dst else 2 * dim, _ROW_DTYPES[x.dtype], get_wholegraph_env_fns(),
+            C.c_void_p(get_stream())), "csc_aggregate_forward")
         ctx.save_for_backward(row_ptr, col_ind)
         ctx.shape = (n_src, dim)
+        ctx.dtype = x.dtype
         ctx.aggr = aggr_code_
         return out
 
@@ -78,21 +87,22 @@ class CscAggregateConcat(torch.autograd.Function):
         row_ptr, col_ind = ctx.saved_tensors
         n_src, dim = ctx.shape
         n_dst = row_ptr.shape[0] - 1
-        grad_out = _rows(grad_out, "grad_out")
-        grad_x = torch.empty((n_src, dim), dtype=torch.float32, device=grad_out.device)
-        wmb.check(wmb.lib().wholememory_ext_csc_aggregate_backward(
+        grad_out = _rows(grad_out, "grad_out", (ctx.dtype,))   # (autograd hands over the dtype of out)
+        grad_x = torch.empty((n_src, dim), dtype=ctx.dtype, device=grad_out.device)
+        wmb.check(wmb.lib().wholememory_ext_csc_aggregate_backward_typed(
             _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, _ptr(grad_out),
-            grad_out.stride(0) if n_dst else 2 * dim, dim, ctx.aggr, _ptr(grad_x), dim, get_wholegraph_env_fns(),
-            C.c_void_p(get_stream())), "csc_aggregate_backward")
+            grad_out.stride(0) if n_dst else 2 * dim, dim, ctx.aggr, _ptr(grad_x), dim, _ROW_DTYPES[ctx.dtype],
+            get_wholegraph_env_fns(), C.c_void_p(get_stream())), "csc_aggregate_backward")
         return grad_x, None, None, None
 
 
 def agg_concat(x: torch.Tensor, csr_row_ptr: torch.Tensor, csr_col_ind: torch.Tensor, aggr: str = "mean") -> torch.Tensor:
     """[n_dst, 2F] = (aggr over each target's neighbour rows of x, the target's own row). csr_row_ptr [n_dst + 1] and
     csr_col_ind [E] (int32 or int64, converted to int32) describe the block in CSC form: the edges of target d are
-    csr_col_ind[csr_row_ptr[d] : csr_row_ptr[d + 1]], row positions in x. x: fp32 [n_src, F], n_src >= n_dst."""
+    csr_col_ind[csr_row_ptr[d] : csr_row_ptr[d + 1]], row positions in x. x: float32, float16 or bfloat16 [n_src, F],
+    n_src >= n_dst; the result has x's dtype (16-bit rows: fp32 sums, one rounding per element)."""
     code = aggr_code(aggr)
-    x = _rows(x, "x")
+    x = _rows(x, "x", tuple(_ROW_DTYPES))
     if not x.is_cuda:
         raise ValueError("x must be a GPU tensor")
     row_ptr = _index(csr_row_ptr, "csr_row_ptr", x.device)

@@ -14,7 +14,12 @@ class CuGraphSAGEConv(torch.nn.Module):
     ``out = lin(cat(aggr_{j in N(i)} x_j, x_i))`` with ``root_weight`` (else ``lin(aggr x_j)``); ``project`` first maps
     ``x`` through ``relu(pre_lin(x))``; ``normalize`` L2-normalises the output rows. The block is given in CSC form:
     the neighbours of target ``i`` are ``x[csr_col_ind[csr_row_ptr[i]:csr_row_ptr[i + 1]]]`` and the targets are the
-    first ``len(csr_row_ptr) - 1`` rows of ``x``."""
+    first ``len(csr_row_ptr) - 1`` rows of ``x``.
+
+    Mixed precision needs no argument: the aggregation runs in the dtype of its input (float32, float16 or bfloat16; with
+    16-bit rows the sums are still taken in fp32 and rounded once). So the layer works after ``.half()`` / ``.bfloat16()``
+    on input of that dtype, and under ``torch.autocast``, where a layer fed by another layer's ``Linear`` output
+    aggregates 16-bit rows."""
 
     def __init__(self, in_channels: int, out_channels: int, aggr: str = "mean", normalize: bool = False,
                  root_weight: bool = True, project: bool = False, bias: bool = True):

@@ -6,7 +6,10 @@
 the source (neighbour) side, half 1 the target side. Per target and head, an edge softmax of
 ``LeakyReLU(att[0] . h[src] + att[1] . h[dst])`` weights the neighbour rows. Every fp32 sum, forward and backward, is
 taken in one fixed order (stated in ``include/wholememory/wholegraph_amd_ext.h``, section 2c), so results are bitwise
-reproducible."""
+reproducible.
+
+The op is fp32 only. Inside a ``torch.autocast("cuda")`` region a 16-bit ``h`` (what an autocast ``Linear`` returns) is
+cast to fp32 on the way in and the op runs in fp32 with autocast off; outside autocast a 16-bit ``h`` is a ``TypeError``."""
 import ctypes as C
 
 import torch
@@ -25,6 +28,7 @@ class CscGatConv(torch.autograd.Function):
     """autograd over the two entry points: out (and alpha, which carries no gradient) from h and att"""
 
     @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
     def forward(ctx, h, att, row_ptr, col_ind, heads, negative_slope, concat):
         n_src, hf = h.shape
         dim = hf // heads
@@ -42,6 +46,7 @@ class CscGatConv(torch.autograd.Function):
         return out, alpha
 
     @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
     def backward(ctx, grad_out, grad_alpha):
         if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
             return None, None, None, None, None, None, None
@@ -71,6 +76,8 @@ def mha_gat_n2n(h: torch.Tensor, att: torch.Tensor, csr_row_ptr: torch.Tensor, c
     heads = int(heads)
     if heads < 1:
         raise ValueError("heads must be >= 1 (got %d)" % heads)
+    if h.is_cuda and h.dtype in (torch.float16, torch.bfloat16) and torch.is_autocast_enabled("cuda"):
+        h = h.float()   # (what custom_fwd's cast_inputs does, ahead of the checks below; the op is fp32)
     h = _rows(h, "h")
     if not h.is_cuda:
         raise ValueError("h must be a GPU tensor")

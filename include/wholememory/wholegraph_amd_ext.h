@@ -147,6 +147,18 @@ wholememory_error_code_t wholememory_ext_sample_append_unique(
   void* output_neighbor_pos_memory_context, void* output_center_localid_memory_context, wholememory_env_func_t* p_env_fns,
   void* stream);
 
+/* wholememory_ext_sample_append_unique with the WEIGHTED sampler (wholegraph_csr_weighted_sample_without_replacement on
+ * wm_csr_weight_ptr_tensor: one float or double per edge): same outputs, bit-identical to that sampler followed by
+ * graph_append_unique, ONE host round trip. WHOLEMEMORY_NOT_SUPPORTED (nothing queued, nothing allocated) in every case the
+ * unweighted call answers it, and when the weight tensor is not mapped into this rank (DISTRIBUTED / HIERARCHY), is not float
+ * or double, does not hold one entry per edge, or max_sample_count > 8192: the two-op route then reports what is wrong. */
+wholememory_error_code_t wholememory_ext_weighted_sample_append_unique(
+  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor,
+  wholememory_tensor_t wm_csr_weight_ptr_tensor, wholememory_tensor_t center_nodes_tensor, int max_sample_count,
+  unsigned long long random_seed, wholememory_tensor_t output_sample_offset_tensor, void* output_unique_memory_context,
+  void* output_neighbor_pos_memory_context, void* output_center_localid_memory_context, wholememory_env_func_t* p_env_fns,
+  void* stream);
+
 /* Every hop of a multi-layer unweighted sample (hop = neighbour sample + graph_append_unique, as in
  * wholememory_ext_sample_append_unique) in ONE call with NO host round trip inside. The caller sizes every array for its upper
  * bound: hop h (h = 0 next to the seeds) has at most cap_c[h] centres and cap_s[h] = cap_c[h] * max_sample_counts[h] samples,
@@ -168,6 +180,16 @@ enum wholememory_error_code_t wholememory_ext_multilayer_sample(
   int hops, const int* max_sample_counts, const unsigned long long* random_seeds, void* const* sample_offsets,
   void* const* unique, int* const* neighbor_pos, int* const* center_lid, int* counts_host,
   struct wholememory_env_func_t* p_env_fns, void* stream);
+
+/* wholememory_ext_multilayer_sample with the WEIGHTED sampler on every hop (one weight tensor: a float or double per edge):
+ * same arrays, same counts, same QUERY mode (sample_offsets == NULL), bit-identical to `hops` calls of
+ * wholememory_ext_weighted_sample_append_unique with the same seeds. WHOLEMEMORY_NOT_SUPPORTED (nothing queued) in every case
+ * the unweighted chain answers it, for a weight tensor that call declines, and for a fan-out above 8192. */
+enum wholememory_error_code_t wholememory_ext_multilayer_sample_weighted(
+  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor,
+  wholememory_tensor_t wm_csr_weight_ptr_tensor, wholememory_tensor_t seed_nodes_tensor, int hops, const int* max_sample_counts,
+  const unsigned long long* random_seeds, void* const* sample_offsets, void* const* unique, int* const* neighbor_pos,
+  int* const* center_lid, int* counts_host, struct wholememory_env_func_t* p_env_fns, void* stream);
 
 /* Completion semantics of the ops whose reference versions drain the stream before returning (neighbour sampling,
  * graph_append_unique and the fused hop above). Default 0 = the reference's: outputs complete and scratch idle at return,

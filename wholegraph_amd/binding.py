@@ -258,6 +258,7 @@ PROTOTYPES = {
     "wholememory_ext_last_rows_kernel": (C.c_char_p, []),
     "wholememory_ext_sample_append_unique": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_ulonglong, C.c_void_p,
                                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "wholememory_ext_weighted_sample_append_unique": (_i, [_vp, _vp, _vp, _vp, _i, C.c_ulonglong, _vp, _vp, _vp, _vp, _vp, _vp]),
     "wholememory_ext_set_async_completion": (_i, [_i]),
     "wholememory_ext_reload_knobs": (_i, []),
     "wholememory_ext_probe_memory": (_i, [_vp, C.c_size_t, _i, _i, _P(_f)]),
@@ -273,6 +274,7 @@ PROTOTYPES = {
     "wholememory_ext_get_malloc_probe": (_i, [C.c_char_p, C.c_size_t]),
     "wholememory_ext_handle_was_probed": (_i, [_vp]),
     "wholememory_ext_multilayer_sample": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "wholememory_ext_multilayer_sample_weighted": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "wholememory_ext_csc_aggregate_forward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i, _vp, _i64, _P(EnvFunc),
                                                   _vp]),
     "wholememory_ext_csc_aggregate_backward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i, _vp, _i64, _P(EnvFunc),

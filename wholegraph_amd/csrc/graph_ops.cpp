@@ -409,6 +409,27 @@ int hop_offsets(const wm_device_backend* bk, const wm_sample_args& a, const int*
   if (rc != 0) return rc;
   return bk->exclusive_scan_i32(counts, offsets, static_cast<int64_t>(a.n_center) + 1, scan_ws, scan_ws_bytes, stream);
 }
+
+// the weight tensor of a weighted fused hop / chain: one float or double per edge, mapped into this rank. SUCCESS fills the
+// weight fields of `a`; NOT_SUPPORTED = the caller takes the two-op route, which reports what is wrong with the tensor
+wholememory_error_code_t ext_weights(wholememory_tensor_t weight_tensor, const wholememory_array_description_t& col_desc,
+                                     wm_sample_args* a)
+{
+  wholememory_error_code_t err = WHOLEMEMORY_SUCCESS;
+  wholememory_array_description_t weight_desc;
+  if (!array_of(weight_tensor, "wm_csr_weight_ptr_tensor", &weight_desc, &err)) return err;
+  const auto wmt = memory_type_of(weight_tensor);
+  if (wmt == WHOLEMEMORY_MT_HIERARCHY || wmt == WHOLEMEMORY_MT_DISTRIBUTED ||
+      (weight_desc.dtype != WHOLEMEMORY_DT_FLOAT && weight_desc.dtype != WHOLEMEMORY_DT_DOUBLE) || weight_desc.size != col_desc.size)
+    return WHOLEMEMORY_NOT_SUPPORTED;
+  if (a != nullptr) {
+    WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(weight_tensor, &a->weight_gref));
+    a->weight_storage_offset = weight_desc.storage_offset;
+    a->weight_dtype          = weight_desc.dtype;
+  }
+  return WHOLEMEMORY_SUCCESS;
+}
+constexpr int kMaxWeightedFanout = 8192;   // what the weighted sampler takes (sample_without_replacement above)
 }  // namespace
 
 // One hop of multi-layer sampling as ONE call (extension; the reference runs the sampler and append_unique as two ops with a
@@ -422,14 +443,15 @@ int hop_offsets(const wm_device_backend* bk, const wm_sample_args& a, const int*
 //   center_lid                   int32 [n_samples]: position of its centre in the frontier
 // Mapped CSR (CONTINUOUS / CHUNKED / plain) with column ids of the frontier's dtype only; anything else answers
 // WHOLEMEMORY_NOT_SUPPORTED before touching the stream and the caller takes the two-op route.
-wholememory_error_code_t wholememory_ext_sample_append_unique(
+// (weighted: the same hop with the weighted sampler, wholememory_ext_weighted_sample_append_unique; it also declines a weight
+// tensor that is not mapped, not float / double or not one entry per edge, and a fan-out above 8192)
+static wholememory_error_code_t sample_append_unique_body(
   wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor,
-  wholememory_tensor_t center_nodes_tensor, int max_sample_count, unsigned long long random_seed,
-  wholememory_tensor_t output_sample_offset_tensor, void* output_unique_memory_context,
+  wholememory_tensor_t wm_csr_weight_ptr_tensor, bool weighted, wholememory_tensor_t center_nodes_tensor, int max_sample_count,
+  unsigned long long random_seed, wholememory_tensor_t output_sample_offset_tensor, void* output_unique_memory_context,
   void* output_neighbor_pos_memory_context, void* output_center_localid_memory_context, wholememory_env_func_t* p_env_fns,
   void* stream)
 {
-  WM_API_BEGIN
   const auto* bk = graph_backend();
   if (bk == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
   if (p_env_fns == nullptr || output_unique_memory_context == nullptr || output_neighbor_pos_memory_context == nullptr ||
@@ -441,6 +463,7 @@ wholememory_error_code_t wholememory_ext_sample_append_unique(
   if (!array_of(wm_csr_col_ptr_tensor, "wm_csr_col_ptr_tensor", &col_desc, &err)) return err;
   if (!array_of(center_nodes_tensor, "center_nodes_tensor", &center_desc, &err)) return err;
   if (!array_of(output_sample_offset_tensor, "output_sample_offset_tensor", &offset_desc, &err)) return err;
+  if (weighted && wm_csr_weight_ptr_tensor == nullptr) return WHOLEMEMORY_INVALID_INPUT;
   const auto row_mt = memory_type_of(wm_csr_row_ptr_tensor), col_mt = memory_type_of(wm_csr_col_ptr_tensor);
   const bool mapped = row_mt != WHOLEMEMORY_MT_HIERARCHY && col_mt != WHOLEMEMORY_MT_HIERARCHY &&
                       row_mt != WHOLEMEMORY_MT_DISTRIBUTED && col_mt != WHOLEMEMORY_MT_DISTRIBUTED;
@@ -451,6 +474,10 @@ wholememory_error_code_t wholememory_ext_sample_append_unique(
       n + room >= (INT64_C(1) << 31) - 1)
     return WHOLEMEMORY_NOT_SUPPORTED;
   wm_sample_args a{};
+  if (weighted) {
+    WHOLEMEMORY_RETURN_ON_FAIL(ext_weights(wm_csr_weight_ptr_tensor, col_desc, &a));
+    if (max_sample_count > kMaxWeightedFanout) return WHOLEMEMORY_NOT_SUPPORTED;
+  }
   WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_row_ptr_tensor, &a.row_gref));
   WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_col_ptr_tensor, &a.col_gref));
   a.row_storage_offset = row_desc.storage_offset;
@@ -479,7 +506,7 @@ wholememory_error_code_t wholememory_ext_sample_append_unique(
   WM_BK(hop_offsets(bk, a, nullptr, counts, offsets, scan_ws_ptr, scan_ws, stream));
   a.out_ids        = ids;
   a.out_center_lid = lid;
-  WM_BK(bk->sample_unweighted(&a, stream));   // writes exactly offsets[n] entries of the scratch arrays
+  WM_BK(weighted ? bk->sample_weighted(&a, stream) : bk->sample_unweighted(&a, stream));   // writes exactly offsets[n] entries of the scratch arrays
   int rc = bk->append_unique_phase1(a.centers, nt, ids, nn_room, offsets + n, center_desc.dtype, ws, nullptr, host, nullptr, stream);
   int total = 0, n_new = 0;
   if (rc == -3) {
@@ -510,6 +537,34 @@ wholememory_error_code_t wholememory_ext_sample_append_unique(
   WM_BK(bk->append_unique_phase2(a.centers, nt, nn_room, total, center_desc.dtype, ws, uniq, pos, lid, olid, nullptr, stream));
   if (!async_completion_enabled() || debug_sync_enabled()) WM_BK(bk->stream_sync(stream));   // else: outputs and scratch are ordered on `stream`
   return WHOLEMEMORY_SUCCESS;
+}
+
+wholememory_error_code_t wholememory_ext_sample_append_unique(
+  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor,
+  wholememory_tensor_t center_nodes_tensor, int max_sample_count, unsigned long long random_seed,
+  wholememory_tensor_t output_sample_offset_tensor, void* output_unique_memory_context,
+  void* output_neighbor_pos_memory_context, void* output_center_localid_memory_context, wholememory_env_func_t* p_env_fns,
+  void* stream)
+{
+  WM_API_BEGIN
+  return sample_append_unique_body(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, nullptr, false, center_nodes_tensor,
+                                   max_sample_count, random_seed, output_sample_offset_tensor, output_unique_memory_context,
+                                   output_neighbor_pos_memory_context, output_center_localid_memory_context, p_env_fns, stream);
+  WM_API_END
+}
+
+wholememory_error_code_t wholememory_ext_weighted_sample_append_unique(
+  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor,
+  wholememory_tensor_t wm_csr_weight_ptr_tensor, wholememory_tensor_t center_nodes_tensor, int max_sample_count,
+  unsigned long long random_seed, wholememory_tensor_t output_sample_offset_tensor, void* output_unique_memory_context,
+  void* output_neighbor_pos_memory_context, void* output_center_localid_memory_context, wholememory_env_func_t* p_env_fns,
+  void* stream)
+{
+  WM_API_BEGIN
+  return sample_append_unique_body(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_weight_ptr_tensor, true,
+                                   center_nodes_tensor, max_sample_count, random_seed, output_sample_offset_tensor,
+                                   output_unique_memory_context, output_neighbor_pos_memory_context,
+                                   output_center_localid_memory_context, p_env_fns, stream);
   WM_API_END
 }
 
@@ -528,12 +583,14 @@ wholememory_error_code_t wholememory_ext_sample_append_unique(
 // with n_c[0] = seeds, n_c[h + 1] = n_c[h] + new[h]. Outputs equal those of `hops` fused-hop calls bit for bit (same kernels,
 // same per-hop seeds). WHOLEMEMORY_NOT_SUPPORTED (nothing queued): CSR not mapped into this rank, dtypes differ, an empty seed
 // array, a fan-out <= 0, or a hop whose upper bounds are too big for the hash-table route of append_unique.
-wholememory_error_code_t wholememory_ext_multilayer_sample(
-  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor, wholememory_tensor_t seed_nodes_tensor,
-  int hops, const int* max_sample_counts, const unsigned long long* random_seeds, void* const* sample_offsets, void* const* unique,
+// (weighted: every hop samples with the weighted sampler on the same weight tensor, wholememory_ext_multilayer_sample_weighted;
+// declined as well for a weight tensor the fused hop declines and for a fan-out above 8192)
+static wholememory_error_code_t multilayer_sample_body(
+  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor,
+  wholememory_tensor_t wm_csr_weight_ptr_tensor, bool weighted, wholememory_tensor_t seed_nodes_tensor, int hops,
+  const int* max_sample_counts, const unsigned long long* random_seeds, void* const* sample_offsets, void* const* unique,
   int* const* neighbor_pos, int* const* center_lid, int* counts_host, wholememory_env_func_t* p_env_fns, void* stream)
 {
-  WM_API_BEGIN
   const auto* bk = graph_backend();
   if (bk == nullptr || bk->append_unique_takes_bounds == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
   // sample_offsets == nullptr: a QUERY — would this chain be taken? (SUCCESS / NOT_SUPPORTED, nothing queued, no buffer needed:
@@ -548,16 +605,19 @@ wholememory_error_code_t wholememory_ext_multilayer_sample(
   if (!array_of(wm_csr_row_ptr_tensor, "wm_csr_row_ptr_tensor", &row_desc, &err)) return err;
   if (!array_of(wm_csr_col_ptr_tensor, "wm_csr_col_ptr_tensor", &col_desc, &err)) return err;
   if (!array_of(seed_nodes_tensor, "seed_nodes_tensor", &seed_desc, &err)) return err;
+  if (weighted && wm_csr_weight_ptr_tensor == nullptr) return WHOLEMEMORY_INVALID_INPUT;
   const auto row_mt = memory_type_of(wm_csr_row_ptr_tensor), col_mt = memory_type_of(wm_csr_col_ptr_tensor);
   const bool mapped = row_mt != WHOLEMEMORY_MT_HIERARCHY && col_mt != WHOLEMEMORY_MT_HIERARCHY &&
                       row_mt != WHOLEMEMORY_MT_DISTRIBUTED && col_mt != WHOLEMEMORY_MT_DISTRIBUTED;
   if (!mapped || row_desc.dtype != WHOLEMEMORY_DT_INT64 || !is_index_dtype(seed_desc.dtype) || col_desc.dtype != seed_desc.dtype ||
       seed_desc.size == 0)
     return WHOLEMEMORY_NOT_SUPPORTED;
+  wm_sample_args a{};
+  if (weighted) WHOLEMEMORY_RETURN_ON_FAIL(ext_weights(wm_csr_weight_ptr_tensor, col_desc, query ? nullptr : &a));
   std::vector<int64_t> cap_c(hops + 1), cap_s(hops);
   cap_c[0] = seed_desc.size;
   for (int h = 0; h < hops; h++) {
-    if (max_sample_counts[h] <= 0) return WHOLEMEMORY_NOT_SUPPORTED;
+    if (max_sample_counts[h] <= 0 || (weighted && max_sample_counts[h] > kMaxWeightedFanout)) return WHOLEMEMORY_NOT_SUPPORTED;
     cap_s[h]     = cap_c[h] * max_sample_counts[h];
     cap_c[h + 1] = cap_c[h] + cap_s[h];
     if (cap_c[h + 1] >= (INT64_C(1) << 31) - 1 ||
@@ -565,7 +625,6 @@ wholememory_error_code_t wholememory_ext_multilayer_sample(
       return WHOLEMEMORY_NOT_SUPPORTED;
   }
   if (query) return WHOLEMEMORY_SUCCESS;
-  wm_sample_args a{};
   WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_row_ptr_tensor, &a.row_gref));
   WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_col_ptr_tensor, &a.col_gref));
   a.row_storage_offset = row_desc.storage_offset;
@@ -617,7 +676,7 @@ wholememory_error_code_t wholememory_ext_multilayer_sample(
     const bool side_fill = bk->append_unique_table_region != nullptr &&
                            bk->append_unique_table_region(nc, ns, seed_desc.dtype, ws, &a.fill_ff_ptr, &a.fill_ff_bytes) == 0;
     if (!side_fill) a.fill_ff_ptr = nullptr, a.fill_ff_bytes = 0;
-    WM_BK(bk->sample_unweighted(&a, stream));
+    WM_BK(weighted ? bk->sample_weighted(&a, stream) : bk->sample_unweighted(&a, stream));
     // (the hop's counts are published by phase 2's emitting kernel: one tiny launch fewer per hop)
     // (the outermost frontier is padded with -1 up to its room: a gather can be queued on the whole array before the host
     // has read the counts — negative ids are skipped, gather_scatter_func.cuh:296)
@@ -631,6 +690,30 @@ wholememory_error_code_t wholememory_ext_multilayer_sample(
   // counts_host
   if (!async_completion_enabled() || debug_sync_enabled()) WM_BK(bk->stream_sync(stream));
   return WHOLEMEMORY_SUCCESS;
+}
+
+wholememory_error_code_t wholememory_ext_multilayer_sample(
+  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor, wholememory_tensor_t seed_nodes_tensor,
+  int hops, const int* max_sample_counts, const unsigned long long* random_seeds, void* const* sample_offsets, void* const* unique,
+  int* const* neighbor_pos, int* const* center_lid, int* counts_host, wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  return multilayer_sample_body(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, nullptr, false, seed_nodes_tensor, hops,
+                                max_sample_counts, random_seeds, sample_offsets, unique, neighbor_pos, center_lid, counts_host,
+                                p_env_fns, stream);
+  WM_API_END
+}
+
+wholememory_error_code_t wholememory_ext_multilayer_sample_weighted(
+  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor,
+  wholememory_tensor_t wm_csr_weight_ptr_tensor, wholememory_tensor_t seed_nodes_tensor, int hops, const int* max_sample_counts,
+  const unsigned long long* random_seeds, void* const* sample_offsets, void* const* unique, int* const* neighbor_pos,
+  int* const* center_lid, int* counts_host, wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  return multilayer_sample_body(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_weight_ptr_tensor, true, seed_nodes_tensor,
+                                hops, max_sample_counts, random_seeds, sample_offsets, unique, neighbor_pos, center_lid,
+                                counts_host, p_env_fns, stream);
   WM_API_END
 }
 

@@ -634,6 +634,7 @@ __global__ __launch_bounds__(64) void sample_weighted_kernel(weighted_params w)
   extern __shared__ uint64_t cand[];
   const sample_params& p = w.sp;
   const int center       = blockIdx.x;
+  if (center >= centers_in_use(p)) return;   // (block-uniform)
   const int lane         = threadIdx.x;
   const int M            = p.max_sample;
   ColT* out              = static_cast<ColT*>(p.out_ids);
@@ -692,10 +693,125 @@ __global__ __launch_bounds__(64) void sample_weighted_kernel(weighted_params w)
   }
 }
 
-template <typename IdT, typename ColT, typename WT>
-int launch_weighted(const weighted_params& w, hipStream_t stream)
+// The same selection for max_sample <= 64 (the fan-outs GNN samplers use) with nothing in LDS and no barrier, in the shape of
+// sample_small_kernel: G = 64 or 32 lanes per centre (two centres per wave for max_sample <= 32). The kernel above spends a
+// workgroup, a 128-key LDS list and a barriered bitonic sort on every centre; a mini-batch hop has tens of thousands of
+// centres with a few dozen neighbours each. Here lane i of a group holds the i-th largest composite key seen so far (0 = none
+// yet: composite keys are > 0). The neighbours come in batches of G, one per lane; a batch with a key above the running M-th
+// largest is sorted across the lanes (bitonic network of shuffles) and merged: top[i] = max(top[i], batch[G - 1 - i]) holds
+// the G largest of both as a bitonic sequence, which log2 G compare-exchanges put back in descending order. The M largest
+// composite keys in descending order are a function of the key SET alone, so the output equals sample_weighted_kernel's
+// position for position. Stream / draw of a neighbour as there: lane gl plays the virtual threads gl, gl + G, ... < 128, each
+// a PCG stream of its own that serves neighbours vt, vt + 128, ...
+template <int G>
+__device__ __forceinline__ uint64_t top_merge(uint64_t top, uint64_t b, int gl)
 {
-  if (w.sp.n_center == 0) return 0;
+  using u64 = unsigned long long;
+#pragma unroll
+  for (int k = 2; k <= G; k <<= 1) {
+#pragma unroll
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      const uint64_t o    = __shfl_xor(static_cast<u64>(b), j, 64);
+      const bool keep_max = ((gl & k) == 0) == ((gl & j) == 0);   // descending where (gl & k) == 0; k == G: everywhere
+      b                   = keep_max ? max(b, o) : min(b, o);
+    }
+  }
+  const uint64_t r = __shfl_xor(static_cast<u64>(b), G - 1, 64);   // the batch in ascending order
+  top              = max(top, r);
+#pragma unroll
+  for (int j = G >> 1; j > 0; j >>= 1) {
+    const uint64_t o = __shfl_xor(static_cast<u64>(top), j, 64);
+    top              = (gl & j) == 0 ? max(top, o) : min(top, o);
+  }
+  return top;
+}
+
+template <typename IdT, typename ColT, typename WT, int G>
+__global__ __launch_bounds__(kBlock) void sample_weighted_small_kernel(weighted_params w)
+{
+  constexpr int kVThreads = 128;             // the reference geometry for max_sample <= 256 (launch_weighted checks)
+  constexpr int kStreams  = kVThreads / G;   // virtual threads a lane plays
+  constexpr int kPerWave  = 64 / G;
+  const sample_params& p  = w.sp;
+  side_fill(p);
+  const int M      = p.max_sample;   // 1 ... G
+  const int lane   = threadIdx.x & 63;
+  const int gl     = lane & (G - 1);
+  const int gbase  = lane & ~(G - 1);
+  const int wave   = blockIdx.x * kWavesPerBlk + (threadIdx.x >> 6);
+  const int center = wave * kPerWave + lane / G;
+  // as in sample_small_kernel: no early return for a single group, the groups of a wave share the shuffles below
+  const bool live = center < centers_in_use(p);
+  int64_t s = 0, e = 0;
+  if (live) row_bounds<IdT>(p, center, &s, &e);
+  const int N = static_cast<int>(e - s);
+  if (!__any(live && N > 0)) return;
+  const int off   = live && N > 0 ? p.offsets[center] : 0;
+  ColT* out       = static_cast<ColT*>(p.out_ids);
+  const bool all  = live && N > 0 && N <= M;
+  const bool draw = live && N > M;
+  // neighbours to visit, per group and for the wave (scalar: the loops below are wave-uniform)
+  const int n_draw = draw ? N : 0;
+  const int n_wave = G == 64 ? __builtin_amdgcn_readlane(n_draw, 0)
+                             : max(__builtin_amdgcn_readlane(n_draw, 0), __builtin_amdgcn_readlane(n_draw, 32));
+  uint64_t top = 0;
+  // the weights of a lane's first kStreams neighbours (all of them for a degree <= 128) are fetched together, up front: ONE
+  // guard, index clamped (see chain_scan_kernel)
+  float wt0[kStreams];
+#pragma unroll
+  for (int k = 0; k < kStreams; k++) wt0[k] = 0.f;
+  if (draw) {
+#pragma unroll
+    for (int k = 0; k < kStreams; k++)
+      wt0[k] = static_cast<float>(gref_load<WT>(w.weight_ptr, w.weight_off + s + min(k * G + gl, N - 1)));
+  }
+#pragma unroll
+  for (int k = 0; k < kStreams; k++) {
+    const int vbase = k * G;
+    if (vbase >= n_wave) break;
+    const int vt = vbase + gl;
+    pcg32 rng(p.seed, 0, static_cast<uint64_t>(center) * kVThreads + vt);
+    for (int id0 = vbase; id0 < n_wave; id0 += kVThreads) {
+      const int id  = id0 + gl;
+      uint64_t comp = 0;
+      if (id < n_draw) {
+        const float wt  = id0 == vbase ? wt0[k] : static_cast<float>(gref_load<WT>(w.weight_ptr, w.weight_off + s + id));
+        const float key = weighted_sample_key(rng, wt);
+        comp            = (static_cast<uint64_t>(orderable_float(key)) << 32) | (0xffffffffu - static_cast<uint32_t>(id));
+      }
+      const uint64_t thr = __shfl(static_cast<unsigned long long>(top), gbase + M - 1, 64);   // the running M-th largest
+      if (__any(comp > thr)) top = top_merge<G>(top, comp, gl);
+    }
+  }
+  const int pos = all ? gl : static_cast<int>(0xffffffffu - static_cast<uint32_t>(top));
+  if ((all && gl < N) || (draw && gl < M)) {
+    if (out) out[off + gl] = gref_load<ColT>(p.col_ptr, p.col_off + s + pos);
+    if (p.out_lid) p.out_lid[off + gl] = center;
+    if (p.out_egid) p.out_egid[off + gl] = s + pos;
+  }
+}
+
+template <typename IdT, typename ColT, typename WT>
+int launch_weighted(weighted_params w, hipStream_t stream)
+{
+  sample_params& p = w.sp;
+  const bool small = p.max_sample >= 1 && p.max_sample <= 64 && w.vthreads == 128;
+  if (p.fill_ptr != nullptr && (p.n_center == 0 || !small)) {   // only the small-sample kernel carries the side job
+    if (fill_ff(p.fill_ptr, p.fill_vecs * 16, stream) != 0) return -2;
+    p.fill_ptr = nullptr;
+  }
+  if (p.n_center == 0) return 0;
+  if (small && p.max_sample <= 32) {
+    const int per_block = 2 * kWavesPerBlk;   // two centres per wave
+    hipLaunchKernelGGL((sample_weighted_small_kernel<IdT, ColT, WT, 32>), dim3((p.n_center + per_block - 1) / per_block),
+                       dim3(kBlock), 0, stream, w);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+  }
+  if (small) {
+    hipLaunchKernelGGL((sample_weighted_small_kernel<IdT, ColT, WT, 64>), dim3((p.n_center + kWavesPerBlk - 1) / kWavesPerBlk),
+                       dim3(kBlock), 0, stream, w);
+    return hipGetLastError() == hipSuccess ? 0 : -2;
+  }
   const size_t lds = static_cast<size_t>(w.capacity) * sizeof(uint64_t);
   if (lds > 64 * 1024) {  // above the default dynamic-LDS limit: raise it once per instantiation
     static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_weighted_kernel<IdT, ColT, WT>),
@@ -1454,6 +1570,11 @@ int hip_sample_weighted(const wm_sample_args* a, void* stream_v)
   p.centers = a->centers, p.n_center = a->n_center, p.max_sample = a->max_sample_count;
   p.seed = a->random_seed, p.offsets = a->sample_offsets;
   p.out_ids = a->out_ids, p.out_lid = a->out_center_lid, p.out_egid = a->out_edge_gid;
+  p.n_center_dev = a->n_center_dev;
+  if (a->fill_ff_ptr != nullptr && a->fill_ff_bytes > 0) {
+    if ((reinterpret_cast<uintptr_t>(a->fill_ff_ptr) | a->fill_ff_bytes) & 15) return -1;
+    p.fill_ptr = a->fill_ff_ptr, p.fill_vecs = a->fill_ff_bytes / 16;
+  }
   w.weight_ptr = make_view(a->weight_gref);
   w.weight_off = a->weight_storage_offset;
   w.vthreads   = a->max_sample_count > 256 ? 256 : 128;  // reference block sizes (func.cuh:540-560, test utils :597-598)

@@ -6,8 +6,8 @@ layouts, so cuGraph-DGL / PyG call sites keep working). The bodies are this pack
 in a helper, attributes live in one registry keyed by kind, and the multi-hop sampler is a loop over a per-hop record
 instead of four parallel lists. Extensions: ``multilayer_sample_without_replacement(..., random_seeds=[...])`` fixes the
 per-hop sampler seeds (the reference draws them from the global RNG), which is what lets tests/test_c5_flow_gpu.py replay
-the whole chain on the CPU oracle; an unweighted multi-hop sample on a CSR mapped into this rank runs as ONE library call
-with ONE host round trip for all hops (``wholegraph_ops.multilayer_sample``: upper-bound-sized buffers, counts kept on the
+the whole chain on the CPU oracle; a multi-hop sample (unweighted, or weighted by an edge attribute) on a CSR mapped into this
+rank runs as ONE library call with ONE host round trip for all hops (``wholegraph_ops.multilayer_sample``: upper-bound-sized buffers, counts kept on the
 device, views trimmed at the end; ``WM_MULTILAYER_CHAIN=0`` switches it off), and where that does not apply a hop still runs as
 one call (``wholegraph_ops.sample_append_unique``: sampler + append_unique with a single host round trip, same outputs).
 """
@@ -39,10 +39,10 @@ def _chain_layers(chain, hops):
 class _DeferredSample(object):
     """handle of GraphStructure.multilayer_sample_begin"""
 
-    def __init__(self, graph, node_ids, max_neighbors, random_seeds, pending):
+    def __init__(self, graph, node_ids, max_neighbors, random_seeds, pending, weight_name=None):
         self._node_ids, self._hops, self._pending, self._lists = node_ids, len(max_neighbors), pending, None
         if pending is None:      # not queued as one chain: sampled now, hop by hop
-            self._lists = graph._sample_hop_by_hop(node_ids, max_neighbors, None, random_seeds)
+            self._lists = graph._sample_hop_by_hop(node_ids, max_neighbors, weight_name, random_seeds)
             self.padded_frontier = self._lists[0][0]
         else:
             self.padded_frontier = pending.padded_frontier
@@ -102,14 +102,20 @@ class GraphStructure(object):
     def set_edge_attribute(self, attr_name: str, attr_tensor: WholeMemoryTensor):
         self._register("edge", attr_name, attr_tensor, self.edge_count)
 
+    def _weights(self, weight_name: Optional[str]):
+        """handle of the edge attribute a weighted sample draws by; None = unweighted"""
+        if weight_name is None:
+            return None
+        assert weight_name in self.edge_attributes, "no edge attribute named %r" % weight_name
+        return self.edge_attributes[weight_name].wmb_tensor
+
     # ------------------------------------------------------------------------------------------- one hop
     def _one_hop(self, centers: torch.Tensor, fanout: int, weight_name: Optional[str], seed, want_lid: bool, want_eid: bool):
         csr = (self.csr_row_ptr.wmb_tensor, self.csr_col_ind.wmb_tensor)
         if weight_name is None:
             return wholegraph_ops.unweighted_sample_without_replacement(*csr, centers, fanout, seed, want_lid, want_eid)
-        assert weight_name in self.edge_attributes, "no edge attribute named %r" % weight_name
-        weights = self.edge_attributes[weight_name].wmb_tensor
-        return wholegraph_ops.weighted_sample_without_replacement(*csr, weights, centers, fanout, seed, want_lid, want_eid)
+        return wholegraph_ops.weighted_sample_without_replacement(*csr, self._weights(weight_name), centers, fanout, seed,
+                                                                  want_lid, want_eid)
 
     def unweighted_sample_without_replacement_one_hop(self, center_nodes_tensor: torch.Tensor, max_sample_count: int, *,
                                                       random_seed: Union[int, None] = None,
@@ -139,19 +145,20 @@ class GraphStructure(object):
         hops = len(max_neighbors)
         if random_seeds is not None:
             assert len(random_seeds) == hops, "one seed per hop"
-        layers = [None] * hops
-        if weight_name is None and hops > 0 and os.environ.get("WM_MULTILAYER_CHAIN", "1") != "0":
+        if hops > 0 and os.environ.get("WM_MULTILAYER_CHAIN", "1") != "0":
             # the whole chain as one library call with a single host round trip (extension); None = not applicable to this
             # graph or these sizes: hop by hop below then
             chain = wholegraph_ops.multilayer_sample(self.csr_row_ptr.wmb_tensor, self.csr_col_ind.wmb_tensor, node_ids,
-                                                     max_neighbors, random_seeds)
+                                                     max_neighbors, random_seeds,
+                                                     wm_csr_weight_ptr_tensor=self._weights(weight_name))
             if chain is not None:
                 return _layer_lists(_chain_layers(chain, hops), node_ids)
         return self._sample_hop_by_hop(node_ids, max_neighbors, weight_name, random_seeds)
 
     def multilayer_sample_begin(self, node_ids: torch.Tensor, max_neighbors: List[int], *,
-                                random_seeds: Optional[Sequence[int]] = None):
-        """Extension: the unweighted multi-layer sample QUEUED, the host not waiting for it. Returns a handle with
+                                random_seeds: Optional[Sequence[int]] = None, weight_name: Optional[str] = None):
+        """Extension: the multi-layer sample (weighted by the edge attribute `weight_name` when given) QUEUED, the host not
+        waiting for it. Returns a handle with
           .padded_frontier   the outermost frontier (what target_gids[0] will be) at its upper-bound size, the entries behind the
                              sampled nodes set to -1 — hand it to WholeMemoryEmbedding.gather right away: negative ids are
                              skipped, so rows [0, n) of that gather's output are the features of target_gids[0];
@@ -165,8 +172,9 @@ class GraphStructure(object):
         pending = None
         if hops > 0 and os.environ.get("WM_MULTILAYER_CHAIN", "1") != "0":
             pending = wholegraph_ops.multilayer_sample_begin(self.csr_row_ptr.wmb_tensor, self.csr_col_ind.wmb_tensor, node_ids,
-                                                             max_neighbors, random_seeds)
-        return _DeferredSample(self, node_ids, max_neighbors, random_seeds, pending)
+                                                             max_neighbors, random_seeds,
+                                                             wm_csr_weight_ptr_tensor=self._weights(weight_name))
+        return _DeferredSample(self, node_ids, max_neighbors, random_seeds, pending, weight_name)
 
     def _sample_hop_by_hop(self, node_ids, max_neighbors, weight_name, random_seeds):
         hops = len(max_neighbors)
@@ -174,12 +182,10 @@ class GraphStructure(object):
         frontier = node_ids
         for depth, fanout in enumerate(max_neighbors):          # depth 0 = next to the seeds = layer hops - 1
             seed = None if random_seeds is None else random_seeds[depth]
-            fused = None
-            if weight_name is None:
-                # sampler + append_unique as one library call with one host round trip (extension); None = not applicable
-                # to this graph (CSR not mapped into this rank, id dtypes differ ...): the two ops below then
-                fused = wholegraph_ops.sample_append_unique(self.csr_row_ptr.wmb_tensor, self.csr_col_ind.wmb_tensor,
-                                                            frontier, fanout, seed)
+            # sampler + append_unique as one library call with one host round trip (extension); None = not applicable
+            # to this graph (CSR not mapped into this rank, id dtypes differ ...): the two ops below then
+            fused = wholegraph_ops.sample_append_unique(self.csr_row_ptr.wmb_tensor, self.csr_col_ind.wmb_tensor, frontier,
+                                                        fanout, seed, wm_csr_weight_ptr_tensor=self._weights(weight_name))
             if fused is not None:
                 offsets, widened, neighbour_pos, centre_lid = fused
             else:

@@ -55,11 +55,13 @@ def unweighted_sample_without_replacement(wm_csr_row_ptr_tensor, wm_csr_col_ptr_
 
 
 def sample_append_unique(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, center_nodes_tensor: torch.Tensor, max_sample_count: int,
-                         random_seed: Union[int, None] = None):
+                         random_seed: Union[int, None] = None, *, wm_csr_weight_ptr_tensor=None):
     """Extension (include/wholememory/wholegraph_amd_ext.h): one hop = unweighted sampling + append_unique(center nodes,
     sampled neighbours) in ONE call with one host round trip. Returns (sample_offset int32 [n + 1], unique nodes, position of
     every sampled neighbour in `unique` int32, center local id int32) — or None when the library declines (CSR not mapped
-    into this rank, dtypes differ, empty frontier, max_sample_count <= 0): run the two ops then."""
+    into this rank, dtypes differ, empty frontier, max_sample_count <= 0): run the two ops then.
+    wm_csr_weight_ptr_tensor (keyword): the hop samples with the weighted sampler on these edge weights; also declined for a
+    weight tensor that is not mapped, not float / double or not one entry per edge, and for max_sample_count > 8192."""
     row, col = _handle(wm_csr_row_ptr_tensor), _handle(wm_csr_col_ptr_tensor)
     assert center_nodes_tensor.dim() == 1
     if random_seed is None:
@@ -67,10 +69,12 @@ def sample_append_unique(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, center_no
     offset = torch.empty(center_nodes_tensor.shape[0] + 1, device=op_device(), dtype=torch.int)
     uniq, pos, lid = TorchMemoryContext(), TorchMemoryContext(), TorchMemoryContext()
     wc, wo = wrap_torch_tensor(center_nodes_tensor), wrap_torch_tensor(offset)
-    rc = wmb.lib().wholememory_ext_sample_append_unique(
-        row, col, wc.handle, int(max_sample_count), C.c_ulonglong(random_seed & 0xFFFFFFFFFFFFFFFF), wo.handle,
-        C.c_void_p(uniq.get_c_context()), C.c_void_p(pos.get_c_context()), C.c_void_p(lid.get_c_context()),
-        get_wholegraph_env_fns(), C.c_void_p(get_stream()))
+    tail = (int(max_sample_count), C.c_ulonglong(random_seed & 0xFFFFFFFFFFFFFFFF), wo.handle, C.c_void_p(uniq.get_c_context()),
+            C.c_void_p(pos.get_c_context()), C.c_void_p(lid.get_c_context()), get_wholegraph_env_fns(), C.c_void_p(get_stream()))
+    if wm_csr_weight_ptr_tensor is None:
+        rc = wmb.lib().wholememory_ext_sample_append_unique(row, col, wc.handle, *tail)
+    else:
+        rc = wmb.lib().wholememory_ext_weighted_sample_append_unique(row, col, _handle(wm_csr_weight_ptr_tensor), wc.handle, *tail)
     if rc == wmb.NOT_SUPPORTED:
         return None
     wmb.check(rc)
@@ -142,12 +146,20 @@ class PendingMultilayerSample:
 
 
 def multilayer_sample_begin(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, seed_nodes_tensor: torch.Tensor, max_sample_counts,
-                            random_seeds=None):
+                            random_seeds=None, *, wm_csr_weight_ptr_tensor=None):
     """Queues every hop of an unweighted multi-layer sample (wholememory_ext_multilayer_sample: one library call, counts kept
     on the device between hops, no host round trip) and returns a PendingMultilayerSample WITHOUT waiting — or None when the
     library declines (CSR not mapped into this rank, dtypes differ, empty seeds, upper bounds beyond append_unique's hash-table
-    route or beyond the memory budget, allocation failure): run hop by hop then."""
+    route or beyond the memory budget, allocation failure): run hop by hop then.
+    wm_csr_weight_ptr_tensor (keyword): every hop samples with the weighted sampler on these edge weights
+    (wholememory_ext_multilayer_sample_weighted); also declined for a weight tensor that is not mapped, not float / double or
+    not one entry per edge, and for a fan-out above 8192."""
     row, col = _handle(wm_csr_row_ptr_tensor), _handle(wm_csr_col_ptr_tensor)
+    if wm_csr_weight_ptr_tensor is None:
+        chain = lambda *rest: wmb.lib().wholememory_ext_multilayer_sample(row, col, *rest)
+    else:
+        wgt = _handle(wm_csr_weight_ptr_tensor)
+        chain = lambda *rest: wmb.lib().wholememory_ext_multilayer_sample_weighted(row, col, wgt, *rest)
     assert seed_nodes_tensor.dim() == 1
     hops = len(max_sample_counts)
     n0 = seed_nodes_tensor.shape[0]
@@ -169,8 +181,7 @@ def multilayer_sample_begin(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, seed_n
     fan = (C.c_int * hops)(*[int(m) for m in max_sample_counts])
     ws = wrap_torch_tensor(seed_nodes_tensor)
     # ask first (no buffers yet); anything but SUCCESS is a decline
-    if wmb.lib().wholememory_ext_multilayer_sample(row, col, ws.handle, hops, fan, None, None, None, None, None, None, None,
-                                                   None) != wmb.WHOLEMEMORY_SUCCESS:
+    if chain(ws.handle, hops, fan, None, None, None, None, None, None, None, None) != wmb.WHOLEMEMORY_SUCCESS:
         return None
     dev = op_device()
     try:
@@ -184,9 +195,8 @@ def multilayer_sample_begin(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, seed_n
     rng = (C.c_ulonglong * hops)(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in random_seeds])
     ptrs = lambda ts: (C.c_void_p * hops)(*[t.data_ptr() for t in ts])
     try:
-        rc = wmb.lib().wholememory_ext_multilayer_sample(
-            row, col, ws.handle, hops, fan, rng, ptrs(offsets), ptrs(uniques), ptrs([e[0] for e in edges]),
-            ptrs([e[1] for e in edges]), C.c_void_p(counts.data_ptr()), get_wholegraph_env_fns(), C.c_void_p(get_stream()))
+        rc = chain(ws.handle, hops, fan, rng, ptrs(offsets), ptrs(uniques), ptrs([e[0] for e in edges]),
+                   ptrs([e[1] for e in edges]), C.c_void_p(counts.data_ptr()), get_wholegraph_env_fns(), C.c_void_p(get_stream()))
     except torch.OutOfMemoryError:      # the library's scratch comes from torch's allocator through the env functions
         rc = wmb.NOT_SUPPORTED
     if rc != wmb.WHOLEMEMORY_SUCCESS:
@@ -198,14 +208,15 @@ def multilayer_sample_begin(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, seed_n
 
 
 def multilayer_sample(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, seed_nodes_tensor: torch.Tensor, max_sample_counts,
-                      random_seeds=None):
+                      random_seeds=None, *, wm_csr_weight_ptr_tensor=None):
     """Extension (wholememory_ext_multilayer_sample): every hop of an unweighted multi-layer sample in ONE library call with no
     host round trip inside — buffers sized for their upper bounds, counts kept on the device between hops, ONE stream
     synchronise here at the end. Returns a list with one (sample_offset, unique, neighbor_pos, center_lid, edge_index) tuple per
     hop, hop 0 next to the seeds, each tensor trimmed to its size and equal to what `sample_append_unique` returns hop by hop
-    with the same seeds — or None when the library declines (see multilayer_sample_begin): run hop by hop then."""
+    with the same seeds — or None when the library declines (see multilayer_sample_begin): run hop by hop then.
+    wm_csr_weight_ptr_tensor (keyword): the weighted sampler on these edge weights, see multilayer_sample_begin."""
     pending = multilayer_sample_begin(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, seed_nodes_tensor, max_sample_counts,
-                                      random_seeds)
+                                      random_seeds, wm_csr_weight_ptr_tensor=wm_csr_weight_ptr_tensor)
     return None if pending is None else pending.finish()
 
 

@@ -13,6 +13,8 @@
  *      backward).
  *      (2c) the multi-head graph attention of a sampled CSC block behind the GAT layer (forward and a deterministic
  *      backward).
+ *      (2d) the neighbour aggregation of (2b) with a weight per edge (forward, and deterministic gradients into the rows
+ *      and into the weights).
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -441,6 +443,62 @@ enum wholememory_error_code_t wholememory_ext_csc_gat_backward(const int32_t* ro
                                                                void* stream);
 /* N of the backward's grad_att node chunks (a compile-time constant of the library) */
 int64_t wholememory_ext_csc_gat_node_chunk(void);
+
+/* ---- (2d) edge-weighted neighbour aggregation of a sampled CSC block (`agg_concat_weighted`) ------------------- */
+/* The block as for (2b): row_ptr int32 [n_dst + 1], col_ind int32 [n_edges] in [0, n_src), x fp32 [n_src, x_stride] whose
+ * first n_dst rows are the targets; and w fp32 [n_edges], one weight per edge POSITION. fp32 rows only. Strides in elements,
+ * all arrays DEVICE memory, all work queued on `stream`. Every `*` and `+` below is one fp32 operation, rounded on its own:
+ * a product and the add that follows it are two roundings, never a fused multiply-add. inv(d) = fl(1.0f / deg(d)).
+ *
+ * forward: out [n_dst, out_stride] fp32, out_stride >= 2 * dim.
+ *   S(d) = sum over e = row_ptr[d] .. row_ptr[d+1] - 1, left to right from the first term, of fl(w[e] * x[col_ind[e], c]).
+ *   SUM: A = S. MEAN: A = fl(S * inv(d)): the mean over the DEGREE, as (2b), not over the sum of the weights. No edge: +0.0.
+ *   out[d, 0:dim] = A(d); out[d, dim:2dim] = x[d], copied bit for bit.
+ * backward into x: grad_out [n_dst, grad_out_stride] (2 * dim columns used) -> grad_x [n_src, grad_x_stride], every row
+ *   written. t(e) = grad_out[dst(e), 0:dim] (MEAN: fl(t * inv(dst(e))) first), u(e) = fl(w[e] * t(e)). P(s) sums u(e) over
+ *   the edges with col_ind[e] = s in ascending edge position, chunked exactly as (2b) with the same
+ *   C = wholememory_ext_csc_aggregate_chunk_edges(). grad_x[s] = P(s) + grad_out[s, dim:2dim], the self term last and only
+ *   for s < n_dst; the copy / +0.0 rules of (2b).
+ * backward into w (only when grad_w is not null): grad_w [n_edges]. For edge e, q[c] = fl(t(e)[c] * x[col_ind[e], c]) for
+ *   c < dim and q[c] = +0.0 for dim <= c < Fp, Fp the smallest power of two >= dim. grad_w[e] = the sum of q as a balanced
+ *   binary tree of adjacent pairs, level by level: q1[i] = q[2i] + q[2i+1], q2[i] = q1[2i] + q1[2i+1], ... until one value
+ *   is left (Fp = 1: q[0] itself). The tree does not depend on how the kernel is launched.
+ * A NaN stays a NaN (payload not specified). No atomics; results are bitwise reproducible. The edge index of grad_x is
+ * built with the library's id sort, scratch from p_env_fns.
+ * grad_x or grad_w may be null (that gradient is then not computed, and nothing is queued for it); both null is
+ * INVALID_INPUT. The backward reads x only for grad_w. n_edges = 0 and n_dst = 0 are valid. INVALID_INPUT for what (2b)
+ * rejects and for a null w with n_edges > 0; NOT_SUPPORTED (nothing queued) when the device backend has no such kernels. */
+enum wholememory_error_code_t wholememory_ext_csc_aggregate_weighted_forward(const int32_t* row_ptr,
+                                                                             const int32_t* col_ind,
+                                                                             const float* w,
+                                                                             int64_t n_edges,
+                                                                             int64_t n_dst,
+                                                                             int64_t n_src,
+                                                                             const float* x,
+                                                                             int64_t x_stride,
+                                                                             int64_t dim,
+                                                                             int aggr,
+                                                                             float* out,
+                                                                             int64_t out_stride,
+                                                                             struct wholememory_env_func_t* p_env_fns,
+                                                                             void* stream);
+enum wholememory_error_code_t wholememory_ext_csc_aggregate_weighted_backward(const int32_t* row_ptr,
+                                                                              const int32_t* col_ind,
+                                                                              int64_t n_edges,
+                                                                              int64_t n_dst,
+                                                                              int64_t n_src,
+                                                                              const float* x,
+                                                                              int64_t x_stride,
+                                                                              const float* w,
+                                                                              const float* grad_out,
+                                                                              int64_t grad_out_stride,
+                                                                              int64_t dim,
+                                                                              int aggr,
+                                                                              float* grad_x,
+                                                                              int64_t grad_x_stride,
+                                                                              float* grad_w,
+                                                                              struct wholememory_env_func_t* p_env_fns,
+                                                                              void* stream);
 
 /* ---- (3) testing seam ---------------------------------------------------------------------- */
 /* Replaces the device backend. Refuses (WHOLEMEMORY_NOT_SUPPORTED) unless the environment has

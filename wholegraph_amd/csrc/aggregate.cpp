@@ -1,7 +1,7 @@
 // wholegraph_amd — host side of the neighbour aggregation of a sampled CSC block (wholegraph_amd_ext.h, section 2b):
 // validation, the edge index of the backward (the library's id sort over col_ind) and the launches of kernels/agg.hip
-// (fp32 rows) and kernels/agg_half.hip (fp16 / bf16 rows, the _typed entry points). The semantics, and the one order of
-// every fp32 sum, are stated in the header.
+// (fp32 rows), kernels/agg_half.hip (fp16 / bf16 rows, the _typed entry points) and kernels/agg_weighted.hip (a weight per
+// edge, section 2d, the _weighted entry points). The semantics, and the one order of every fp32 sum, are stated in the header.
 #include <wholememory/wholegraph_amd_ext.h>
 
 #include "ops_internal.hpp"
@@ -84,6 +84,21 @@ wm_agg16_args make_args16(const int32_t* row_ptr, const int32_t* col_ind, int64_
   a.dim     = dim;
   a.mean    = aggr == WHOLEMEMORY_EXT_AGGR_MEAN ? 1 : 0;
   a.dtype   = dtype;
+  return a;
+}
+
+wm_aggw_args make_args_w(const int32_t* row_ptr, const int32_t* col_ind, const float* w, int64_t n_edges, int64_t n_dst,
+                         int64_t n_src, int64_t dim, int aggr)
+{
+  wm_aggw_args a{};
+  a.row_ptr = row_ptr;
+  a.col_ind = col_ind;
+  a.w       = w;
+  a.n_edges = n_dst == 0 ? 0 : n_edges;
+  a.n_dst   = n_dst;
+  a.n_src   = n_src;
+  a.dim     = dim;
+  a.mean    = aggr == WHOLEMEMORY_EXT_AGGR_MEAN ? 1 : 0;
   return a;
 }
 
@@ -192,6 +207,67 @@ wholememory_error_code_t wholememory_ext_csc_aggregate_backward_typed(const int3
                       [&](const int32_t* order, const int32_t* starts, const int32_t* unique, const int64_t* nu, void* ws) {
                         WM_BK(bk->agg16_backward(&a, order, starts, unique, nu, ws, stream));
                       });
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+wholememory_error_code_t wholememory_ext_csc_aggregate_weighted_forward(const int32_t* row_ptr, const int32_t* col_ind,
+                                                                        const float* w, int64_t n_edges, int64_t n_dst,
+                                                                        int64_t n_src, const float* x, int64_t x_stride,
+                                                                        int64_t dim, int aggr, float* out, int64_t out_stride,
+                                                                        wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  (void)p_env_fns;   // (the forward needs no scratch)
+  const auto* bk = backend();
+  if (bk->aggw_forward == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, x, x_stride, dim, dim, aggr, out, out_stride, 2 * dim, n_src, n_dst);
+  if (n_edges > 0 && w == nullptr) throw invalid_input("w is null");
+  wm_aggw_args a = make_args_w(row_ptr, col_ind, w, n_edges, n_dst, n_src, dim, aggr);
+  a.in           = x;
+  a.in_stride    = x_stride;
+  a.out          = out;
+  a.out_stride   = out_stride;
+  WM_BK(bk->aggw_forward(&a, stream));
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+wholememory_error_code_t wholememory_ext_csc_aggregate_weighted_backward(
+  const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src, const float* x,
+  int64_t x_stride, const float* w, const float* grad_out, int64_t grad_out_stride, int64_t dim, int aggr, float* grad_x,
+  int64_t grad_x_stride, float* grad_w, wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  const auto* bk = backend();
+  if (bk->aggw_backward == nullptr || bk->agg_backward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  // (grad_x may be null: its rows and stride are checked only when it is asked for)
+  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, grad_out, grad_out_stride, 2 * dim, dim, aggr, grad_x,
+             grad_x != nullptr ? grad_x_stride : dim, dim, n_dst, grad_x != nullptr ? n_src : 0);
+  if (grad_x == nullptr && grad_w == nullptr) throw invalid_input("grad_x and grad_w are both null");
+  if (n_edges > 0 && w == nullptr) throw invalid_input("w is null");
+  if (grad_w != nullptr) {   // the gradient of the weights reads the rows of x
+    if (n_src > 0 && x == nullptr) throw invalid_input("x is null");
+    if (x_stride < dim) throw invalid_input("input stride smaller than its row");
+  }
+  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
+  wm_aggw_args a = make_args_w(row_ptr, col_ind, w, n_edges, n_dst, n_src, dim, aggr);
+  a.in           = x;
+  a.in_stride    = x_stride;
+  a.grad         = grad_out;
+  a.grad_stride  = grad_out_stride;
+  a.out          = grad_x;
+  a.out_stride   = grad_x_stride;
+  a.grad_w       = grad_w;
+  if (grad_x != nullptr && n_src > 0) {
+    backward_over_index(bk, col_ind, a.n_edges, n_src, dim, p_env_fns, stream,
+                        [&](const int32_t* order, const int32_t* starts, const int32_t* unique, const int64_t* nu, void* ws) {
+                          WM_BK(bk->aggw_backward(&a, order, starts, unique, nu, ws, stream));
+                        });
+  } else if (grad_w != nullptr) {
+    a.out = nullptr;
+    WM_BK(bk->aggw_backward(&a, nullptr, nullptr, nullptr, nullptr, nullptr, stream));
+  }
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }

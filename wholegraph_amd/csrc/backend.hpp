@@ -227,6 +227,23 @@ struct wm_gat_args {
   float* grad_att;          // backward: [2 * heads * dim]
 };
 
+// edge-weighted neighbour aggregation of a sampled CSC block (kernels/agg_weighted.hip): wm_agg_args plus one fp32 weight
+// per edge position; rows / strides / dim in ELEMENTS (fp32)
+struct wm_aggw_args {
+  const int32_t* row_ptr;   // [n_dst + 1]
+  const int32_t* col_ind;   // [n_edges], ids in [0, n_src)
+  const float* w;           // [n_edges]
+  int64_t n_edges, n_dst, n_src, dim;
+  int mean;                 // 1: "mean" (sum times fl(1 / degree)), 0: "sum"
+  const float* in;          // x [n_src, in_stride] (forward; backward into w)
+  int64_t in_stride;
+  const float* grad;        // backward: dL/dout [n_dst, grad_stride], 2 * dim columns used
+  int64_t grad_stride;
+  float* out;               // forward: out [n_dst, out_stride] (2 * dim columns); backward: grad_x [n_src, out_stride] or nullptr
+  int64_t out_stride;
+  float* grad_w;            // backward: [n_edges] or nullptr
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -434,6 +451,14 @@ struct wm_device_backend {
   int (*agg16_forward)(const wm_agg16_args* a, void* stream);
   int (*agg16_backward)(const wm_agg16_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
                         const int64_t* n_unique_dev, void* workspace, void* stream);
+  // ---- agg_forward / agg_backward with a weight per edge (kernels/agg_weighted.hip, wholegraph_amd_ext.h section 2d);
+  // nullptr in a backend without them ----
+  int (*aggw_forward)(const wm_aggw_args* a, void* stream);
+  // a->out != nullptr: grad_x, with the index and the workspace of agg_backward (agg_backward_workspace_bytes);
+  // a->grad_w != nullptr: the gradient of the weights (needs a->in; no index). With a->out == nullptr the index arguments
+  // and the workspace are not read and may be nullptr.
+  int (*aggw_backward)(const wm_aggw_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                       const int64_t* n_unique_dev, void* workspace, void* stream);
 };
 
 }  // extern "C"

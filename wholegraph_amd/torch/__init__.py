@@ -4,11 +4,12 @@ Same names and signatures as reference ``python/pylibwholegraph/pylibwholegraph/
 communicators, initialisation, WholeMemory tensors, embeddings / optimizers / cache policies, the gather / scatter
 functors, neighbour sampling and GraphStructure, and for the GNN model surface of the ``cugraph`` framework route
 (``set_framework``, ``create_gnn_layers``, ``create_sub_graph``, ``HomoGNNModel``; the GraphSAGE and GAT layers in
-``cugraphops``, on the HIP ops of ``aggregation`` and ``gat_aggregation``). GAT in ``HomoGNNModel``, the dgl / pyg / wg
+``cugraphops``, on the HIP ops of ``aggregation`` and ``gat_aggregation``; and, beyond the reference, the edge-weighted
+GraphSAGE layer ``cugraphops.EdgeWeightedSAGEConv`` on ``weighted_aggregation``). GAT in ``HomoGNNModel``, the dgl / pyg / wg
 routes, data loaders, launch helpers and option parsers of the reference are outside this build's scope.
 """
 from . import comm, embedding, graph_ops, graph_structure, initialize, tensor, utils, wholegraph_ops, wholememory_ops
-from . import aggregation, cugraphops, gat_aggregation, gnn_model
+from . import aggregation, cugraphops, gat_aggregation, gnn_model, weighted_aggregation
 
 _PUBLIC = {
     comm: ("WholeMemoryCommunicator create_group_communicator destroy_communicator get_global_communicator "
@@ -25,7 +26,7 @@ _PUBLIC = {
     graph_structure: "GraphStructure",
     gnn_model: "set_framework create_gnn_layers create_sub_graph HomoGNNModel",
 }
-__all__ = ["graph_ops", "wholegraph_ops", "aggregation", "cugraphops", "gat_aggregation", "gnn_model"]
+__all__ = ["graph_ops", "wholegraph_ops", "aggregation", "cugraphops", "gat_aggregation", "gnn_model", "weighted_aggregation"]
 for _module, _names in _PUBLIC.items():
     for _name in _names.split():
         globals()[_name] = getattr(_module, _name)

@@ -1,5 +1,6 @@
 """Layers of the ``cugraph`` framework route (``gnn_model.set_framework("cugraph")``), on the HIP aggregation ops."""
 from .gat_conv import CuGraphGATConv
 from .sage_conv import CuGraphSAGEConv
+from .weighted_sage_conv import EdgeWeightedSAGEConv
 
-__all__ = ["CuGraphSAGEConv", "CuGraphGATConv"]
+__all__ = ["CuGraphSAGEConv", "CuGraphGATConv", "EdgeWeightedSAGEConv"]

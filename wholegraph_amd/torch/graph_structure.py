@@ -176,6 +176,33 @@ class GraphStructure(object):
                                                              wm_csr_weight_ptr_tensor=self._weights(weight_name))
         return _DeferredSample(self, node_ids, max_neighbors, random_seeds, pending, weight_name)
 
+    def multilayer_sample_with_edge_attributes(self, node_ids: torch.Tensor, max_neighbors: List[int],
+                                               edge_attr_names: Sequence[str], weight_name: Union[str, None] = None, *,
+                                               random_seeds: Optional[Sequence[int]] = None):
+        """Extension: multilayer_sample_without_replacement plus the attributes of the SAMPLED edges. Returns its four lists
+        and a fifth, per layer (outermost first) a dict {name: tensor [n_edges]} aligned with that layer's csr_col_ind:
+        entry e is the named edge attribute at the graph edge that block edge e was drawn from. The name "__edge_id__"
+        delivers those int64 graph edge ids (positions in the graph's csr_col_ind) themselves. The sample is taken hop by
+        hop over the one-hop sampler with edge output; with the same random_seeds the four lists equal
+        multilayer_sample_without_replacement's."""
+        names = list(edge_attr_names)
+        for name in names:
+            assert name == "__edge_id__" or name in self.edge_attributes, "no edge attribute named %r" % name
+        hops = len(max_neighbors)
+        if random_seeds is not None:
+            assert len(random_seeds) == hops, "one seed per hop"
+        layers, attrs = [None] * hops, [None] * hops
+        frontier = node_ids
+        for depth, fanout in enumerate(max_neighbors):          # depth 0 = next to the seeds = layer hops - 1
+            seed = None if random_seeds is None else random_seeds[depth]
+            offsets, neighbours, centre_lid, edge_id = self._one_hop(frontier, fanout, weight_name, seed, True, True)
+            widened, neighbour_pos = graph_ops.append_unique(frontier, neighbours, need_neighbor_raw_to_unique=True)
+            layers[hops - 1 - depth] = _Hop(widened, torch.stack([neighbour_pos, centre_lid]), offsets, neighbour_pos)
+            attrs[hops - 1 - depth] = {name: edge_id if name == "__edge_id__" else self.edge_attributes[name].gather(edge_id)
+                                       for name in names}
+            frontier = widened
+        return _layer_lists(layers, node_ids) + (attrs,)
+
     def _sample_hop_by_hop(self, node_ids, max_neighbors, weight_name, random_seeds):
         hops = len(max_neighbors)
         layers = [None] * hops

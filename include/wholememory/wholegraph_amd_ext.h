@@ -193,6 +193,54 @@ enum wholememory_error_code_t wholememory_ext_multilayer_sample_weighted(
   const unsigned long long* random_seeds, void* const* sample_offsets, void* const* unique, int* const* neighbor_pos,
   int* const* center_lid, int* counts_host, struct wholememory_env_func_t* p_env_fns, void* stream);
 
+/* wholememory_ext_sample_append_unique / wholememory_ext_weighted_sample_append_unique plus the graph EDGE ID of every sample.
+ * wm_csr_weight_ptr_tensor == NULL selects the unweighted sampler, a tensor the weighted one. Outputs: those of the fused hop,
+ * bit for bit, and
+ *   edge_gid      (memory context)  int64 [n_samples]: position in wm_csr_col_ptr_tensor of the edge each sample was drawn
+ *                                   from, aligned with neighbor_pos / center_lid — what the one-hop samplers deliver through
+ *                                   output_edge_gid_memory_context
+ * Still ONE host round trip. WHOLEMEMORY_INVALID_INPUT for a NULL edge id context (as for the other contexts);
+ * WHOLEMEMORY_NOT_SUPPORTED (nothing queued, nothing allocated) in every case wholememory_ext_sample_append_unique answers it
+ * and, with a weight tensor, in every case wholememory_ext_weighted_sample_append_unique does. */
+enum wholememory_error_code_t wholememory_ext_sample_append_unique_edges(
+  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor,
+  wholememory_tensor_t wm_csr_weight_ptr_tensor, wholememory_tensor_t center_nodes_tensor, int max_sample_count,
+  unsigned long long random_seed, wholememory_tensor_t output_sample_offset_tensor, void* output_unique_memory_context,
+  void* output_neighbor_pos_memory_context, void* output_center_localid_memory_context, void* output_edge_gid_memory_context,
+  struct wholememory_env_func_t* p_env_fns, void* stream);
+
+/* wholememory_ext_multilayer_sample / wholememory_ext_multilayer_sample_weighted (wm_csr_weight_ptr_tensor == NULL: unweighted)
+ * plus, per hop, the graph edge ids of the samples and — optionally — attributes of those edges, all still in ONE call with NO
+ * host round trip inside:
+ *   edge_gid[h]                 int64 [cap_s[h]]   first samples[h] entries defined: position in wm_csr_col_ptr_tensor of the
+ *                                                  edge each sample was drawn from, aligned with neighbor_pos[h] / center_lid[h]
+ *   attr_out[h * n_attrs + k]   [cap_s[h]] elements of attr_tensors[k]'s dtype, first samples[h] entries defined:
+ *                                                  attr_tensors[k][edge_gid[h][i]]   (n_attrs > 0 only)
+ * all DEVICE memory sized by the caller like neighbor_pos[h]. The attributes are fetched by one more kernel queued behind hop h
+ * (several when n_attrs > 8) that reads the hop's sample count on the device — sample_offsets[h][cap_c[h]], the last entry of the
+ * offsets array at its upper-bound size. An attribute tensor the kernel takes is 1-D with 4- or 8-byte elements (float, int32,
+ * int64, double; the values are moved as bits), one entry per edge, mapped into this rank (CONTINUOUS / CHUNKED / plain device
+ * memory). Every other array, the counts in counts_host and the QUERY mode (sample_offsets == NULL: edge_gid, attr_out, the
+ * seeds and counts_host are not looked at, attr_tensors is) are those of wholememory_ext_multilayer_sample; the outputs equal
+ * those of `hops` calls of wholememory_ext_sample_append_unique_edges with the same seeds bit for bit.
+ * WHOLEMEMORY_INVALID_INPUT, before anything else is looked at: n_attrs < 0, n_attrs > 0 with attr_tensors == NULL or a NULL
+ * entry in it, and on a call that is not a query edge_gid == NULL or n_attrs > 0 with attr_out == NULL.
+ * WHOLEMEMORY_NOT_SUPPORTED (nothing queued; a query answers the same): every case the chain without edge ids answers it (with a
+ * weight tensor: the weighted chain), an attribute tensor that is DISTRIBUTED / HIERARCHY, not 1-D, of another element size or
+ * not one entry per edge — the caller leaves that attribute out and gathers it by edge id afterwards — and a device backend
+ * without the attribute kernel when n_attrs > 0. */
+enum wholememory_error_code_t wholememory_ext_multilayer_sample_edges(
+  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor,
+  wholememory_tensor_t wm_csr_weight_ptr_tensor, wholememory_tensor_t seed_nodes_tensor, int hops, const int* max_sample_counts,
+  const unsigned long long* random_seeds, void* const* sample_offsets, void* const* unique, int* const* neighbor_pos,
+  int* const* center_lid, int64_t* const* edge_gid, int n_attrs, const wholememory_tensor_t* attr_tensors,
+  void* const* attr_out, int* counts_host, struct wholememory_env_func_t* p_env_fns, void* stream);
+
+/* Number of wholememory_ext_multilayer_sample_edges calls of this process that were not queries and returned
+ * WHOLEMEMORY_SUCCESS: how a caller with several sampling routes (GraphStructure.multilayer_sample_with_edge_attributes) shows
+ * which one ran. A counter for tests and benchmarks. */
+int64_t wholememory_ext_edge_chain_calls(void);
+
 /* Completion semantics of the ops whose reference versions drain the stream before returning (neighbour sampling,
  * graph_append_unique and the fused hop above). Default 0 = the reference's: outputs complete and scratch idle at return,
  * safe with any env functions. 1 = the ops return with their last kernels queued on `stream` (one host round trip fewer

@@ -244,6 +244,22 @@ struct wm_aggw_args {
   float* grad_w;            // backward: [n_edges] or nullptr
 };
 
+// the attributes of a hop's sampled edges (kernels/graph.hip: edge_attr_gather_kernel): out_k[i] = attr_k[edge_gid[i]] for
+// i < *n_dev. Attributes are 1-D tensors of 4- or 8-byte elements mapped into this rank; the values are moved as bits.
+#define WM_MAX_EDGE_ATTRS 8
+struct wm_edge_attr_args {
+  const int64_t* edge_gid;  // [n] device: graph edge id of every block edge
+  const int* n_dev;         // optional (device): entries in use of the n the arrays are sized for; nullptr = n
+  int64_t n;
+  int n_attrs;              // 0 .. WM_MAX_EDGE_ATTRS
+  struct {
+    wholememory_gref_t gref;
+    int64_t storage_offset;  // elements
+    int elt_bytes;           // 4 or 8
+    void* out;               // [n] device, elements of elt_bytes
+  } attr[WM_MAX_EDGE_ATTRS];
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -459,6 +475,8 @@ struct wm_device_backend {
   // and the workspace are not read and may be nullptr.
   int (*aggw_backward)(const wm_aggw_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
                        const int64_t* n_unique_dev, void* workspace, void* stream);
+  // ---- attributes of sampled edges (kernels/graph.hip: edge_attr_gather_kernel); nullptr in a backend without it ----
+  int (*edge_attr_gather)(const wm_edge_attr_args* a, void* stream);
 };
 
 }  // extern "C"

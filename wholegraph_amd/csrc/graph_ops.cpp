@@ -6,9 +6,12 @@
 //   -> ..._impl_mapped.cu -> ..._func.cuh:283-470 (count, scan, D2H of the total, output allocation, sample kernel);
 // graph_append_unique cpp/src/graph_ops/append_unique.cpp:23-83 -> append_unique_func.cuh:300-353;
 // csr_add_self_loop cpp/src/graph_ops/csr_add_self_loop.cpp:22-80.
+#include <atomic>
 #include <cmath>
 #include <cstring>
+#include <memory>
 #include <new>
+#include <vector>
 
 #include <wholememory/graph_op.h>
 #include <wholememory/wholegraph_op.h>
@@ -430,6 +433,32 @@ wholememory_error_code_t ext_weights(wholememory_tensor_t weight_tensor, const w
   return WHOLEMEMORY_SUCCESS;
 }
 constexpr int kMaxWeightedFanout = 8192;   // what the weighted sampler takes (sample_without_replacement above)
+
+// an edge attribute the chain fetches on the device (kernels/graph.hip: edge_attr_gather_kernel): 1-D, 4- or 8-byte elements,
+// one per edge, mapped into this rank. SUCCESS fills *out (when given); NOT_SUPPORTED = the caller gathers it itself
+struct edge_attr {
+  wholememory_gref_t gref;
+  int64_t storage_offset;
+  int elt_bytes;
+};
+wholememory_error_code_t ext_edge_attr(wholememory_tensor_t t, const wholememory_array_description_t& col_desc, edge_attr* out)
+{
+  if (t == nullptr) return WHOLEMEMORY_INVALID_INPUT;
+  auto td = *wholememory_tensor_get_tensor_description(t);
+  wholememory_array_description_t desc;
+  if (td.dim != 1 || !wholememory_convert_tensor_desc_to_array(&desc, &td)) return WHOLEMEMORY_NOT_SUPPORTED;
+  const auto mt       = memory_type_of(t);
+  const size_t elt    = wholememory_dtype_get_element_size(desc.dtype);
+  if (mt == WHOLEMEMORY_MT_HIERARCHY || mt == WHOLEMEMORY_MT_DISTRIBUTED || (elt != 4 && elt != 8) || desc.size != col_desc.size)
+    return WHOLEMEMORY_NOT_SUPPORTED;
+  if (out != nullptr) {
+    WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(t, &out->gref));
+    out->storage_offset = desc.storage_offset;
+    out->elt_bytes      = static_cast<int>(elt);
+  }
+  return WHOLEMEMORY_SUCCESS;
+}
+std::atomic<int64_t> g_edge_chain_calls{0};   // successful non-query wholememory_ext_multilayer_sample_edges calls
 }  // namespace
 
 // One hop of multi-layer sampling as ONE call (extension; the reference runs the sampler and append_unique as two ops with a
@@ -445,12 +474,15 @@ constexpr int kMaxWeightedFanout = 8192;   // what the weighted sampler takes (s
 // WHOLEMEMORY_NOT_SUPPORTED before touching the stream and the caller takes the two-op route.
 // (weighted: the same hop with the weighted sampler, wholememory_ext_weighted_sample_append_unique; it also declines a weight
 // tensor that is not mapped, not float / double or not one entry per edge, and a fan-out above 8192)
+// (edge ids: with output_edge_gid_memory_context the sampler also writes the graph edge id of every sample — position in
+// csr_col_ptr — to scratch of the same upper bound, copied to an exactly sized int64 [n_samples] output once the count is
+// known; wholememory_ext_sample_append_unique_edges. Nothing else about the hop changes.)
 static wholememory_error_code_t sample_append_unique_body(
   wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor,
   wholememory_tensor_t wm_csr_weight_ptr_tensor, bool weighted, wholememory_tensor_t center_nodes_tensor, int max_sample_count,
   unsigned long long random_seed, wholememory_tensor_t output_sample_offset_tensor, void* output_unique_memory_context,
   void* output_neighbor_pos_memory_context, void* output_center_localid_memory_context, wholememory_env_func_t* p_env_fns,
-  void* stream)
+  void* stream, void* output_edge_gid_memory_context = nullptr)
 {
   const auto* bk = graph_backend();
   if (bk == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
@@ -493,12 +525,22 @@ static wholememory_error_code_t sample_append_unique_body(
 
   const int nt = static_cast<int>(n), nn_room = static_cast<int>(room);
   temp_mem counts_mem(p_env_fns), scan_mem(p_env_fns), ids_mem(p_env_fns), lid_mem(p_env_fns), ws_mem(p_env_fns),
-    host_mem(p_env_fns);
+    host_mem(p_env_fns), egid_mem(p_env_fns);
   int* counts          = static_cast<int*>(counts_mem.device(n + 1, WHOLEMEMORY_DT_INT));
   const size_t scan_ws = bk->scan_i32_workspace_bytes(n + 1);
   void* scan_ws_ptr    = scan_mem.device(static_cast<int64_t>(scan_ws), WHOLEMEMORY_DT_INT8);
   void* ids            = ids_mem.device(room, col_desc.dtype);
   int* lid             = static_cast<int*>(lid_mem.device(room, WHOLEMEMORY_DT_INT));
+  int64_t* egid        = nullptr;
+  if (output_edge_gid_memory_context != nullptr) egid = static_cast<int64_t*>(egid_mem.device(room, WHOLEMEMORY_DT_INT64));
+  // the edge ids of the hop at their exact size, once the host knows it
+  auto emit_edge_ids = [&](int total) -> wholememory_error_code_t {
+    if (egid == nullptr) return WHOLEMEMORY_SUCCESS;
+    void* out = output_alloc(p_env_fns, output_edge_gid_memory_context, total, WHOLEMEMORY_DT_INT64);
+    if (total > 0 && out == nullptr) return WHOLEMEMORY_OUT_OF_MEMORY;
+    if (total > 0) WM_BK(bk->memcpy_async(out, egid, static_cast<size_t>(total) * sizeof(int64_t), stream));
+    return WHOLEMEMORY_SUCCESS;
+  };
   void* ws = ws_mem.device(static_cast<int64_t>(bk->append_unique_workspace_bytes(nt, nn_room, center_desc.dtype)), WHOLEMEMORY_DT_INT8);
   // {samples, new unique ids}: left in pinned memory by the last kernel before the host looks (no copy commands)
   int* host = static_cast<int*>(host_mem.pinned(2, WHOLEMEMORY_DT_INT));
@@ -506,6 +548,7 @@ static wholememory_error_code_t sample_append_unique_body(
   WM_BK(hop_offsets(bk, a, nullptr, counts, offsets, scan_ws_ptr, scan_ws, stream));
   a.out_ids        = ids;
   a.out_center_lid = lid;
+  a.out_edge_gid   = egid;
   WM_BK(weighted ? bk->sample_weighted(&a, stream) : bk->sample_unweighted(&a, stream));   // writes exactly offsets[n] entries of the scratch arrays
   int rc = bk->append_unique_phase1(a.centers, nt, ids, nn_room, offsets + n, center_desc.dtype, ws, nullptr, host, nullptr, stream);
   int total = 0, n_new = 0;
@@ -524,6 +567,7 @@ static wholememory_error_code_t sample_append_unique_body(
     int* olid  = static_cast<int*>(output_alloc(p_env_fns, output_center_localid_memory_context, total, WHOLEMEMORY_DT_INT));
     if (uniq == nullptr || (total > 0 && (pos == nullptr || olid == nullptr))) return WHOLEMEMORY_OUT_OF_MEMORY;
     WM_BK(bk->append_unique_phase2(a.centers, nt, total, total, center_desc.dtype, ws2, uniq, pos, lid, olid, nullptr, stream));
+    WHOLEMEMORY_RETURN_ON_FAIL(emit_edge_ids(total));
     WM_BK(bk->stream_sync(stream));   // ws2 goes out of scope here
     return WHOLEMEMORY_SUCCESS;
   }
@@ -535,6 +579,7 @@ static wholememory_error_code_t sample_append_unique_body(
   int* olid  = static_cast<int*>(output_alloc(p_env_fns, output_center_localid_memory_context, total, WHOLEMEMORY_DT_INT));
   if (uniq == nullptr || (total > 0 && (pos == nullptr || olid == nullptr))) return WHOLEMEMORY_OUT_OF_MEMORY;
   WM_BK(bk->append_unique_phase2(a.centers, nt, nn_room, total, center_desc.dtype, ws, uniq, pos, lid, olid, nullptr, stream));
+  WHOLEMEMORY_RETURN_ON_FAIL(emit_edge_ids(total));
   if (!async_completion_enabled() || debug_sync_enabled()) WM_BK(bk->stream_sync(stream));   // else: outputs and scratch are ordered on `stream`
   return WHOLEMEMORY_SUCCESS;
 }
@@ -568,6 +613,22 @@ wholememory_error_code_t wholememory_ext_weighted_sample_append_unique(
   WM_API_END
 }
 
+wholememory_error_code_t wholememory_ext_sample_append_unique_edges(
+  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor,
+  wholememory_tensor_t wm_csr_weight_ptr_tensor, wholememory_tensor_t center_nodes_tensor, int max_sample_count,
+  unsigned long long random_seed, wholememory_tensor_t output_sample_offset_tensor, void* output_unique_memory_context,
+  void* output_neighbor_pos_memory_context, void* output_center_localid_memory_context, void* output_edge_gid_memory_context,
+  wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  if (output_edge_gid_memory_context == nullptr) return WHOLEMEMORY_INVALID_INPUT;
+  return sample_append_unique_body(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_weight_ptr_tensor,
+                                   wm_csr_weight_ptr_tensor != nullptr, center_nodes_tensor, max_sample_count, random_seed,
+                                   output_sample_offset_tensor, output_unique_memory_context, output_neighbor_pos_memory_context,
+                                   output_center_localid_memory_context, p_env_fns, stream, output_edge_gid_memory_context);
+  WM_API_END
+}
+
 // The whole chain of hops of GraphStructure.multilayer_sample_without_replacement as ONE call with NO host round trip inside
 // (extension; the reference pays two per hop, the fused hop above one): every array is sized by the CALLER for its upper
 // bound — hop h has at most cap_c[h] centres (cap_c[0] = seeds, cap_c[h + 1] = cap_c[h] + cap_s[h]) and cap_s[h] = cap_c[h] x
@@ -585,14 +646,22 @@ wholememory_error_code_t wholememory_ext_weighted_sample_append_unique(
 // array, a fan-out <= 0, or a hop whose upper bounds are too big for the hash-table route of append_unique.
 // (weighted: every hop samples with the weighted sampler on the same weight tensor, wholememory_ext_multilayer_sample_weighted;
 // declined as well for a weight tensor the fused hop declines and for a fan-out above 8192)
+// (edge ids, wholememory_ext_multilayer_sample_edges: with `edges` the sampler of hop h also writes the graph edge id of every
+// sample to edge_gid[h], int64 [cap_s[h]], first samples[h] entries defined; with n_attrs > 0 one more kernel behind hop h
+// (edge_attr_gather_kernel) fills attr_out[h * n_attrs + k] = attr_tensors[k][edge_gid[h]] for those entries. It reads the
+// hop's sample count on the device from sample_offsets[h][cap_c[h]], the word append_unique takes its neighbour count from.
+// Kernels, their order, the counts and every other output are those of the chain without edge ids.)
 static wholememory_error_code_t multilayer_sample_body(
   wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor,
   wholememory_tensor_t wm_csr_weight_ptr_tensor, bool weighted, wholememory_tensor_t seed_nodes_tensor, int hops,
   const int* max_sample_counts, const unsigned long long* random_seeds, void* const* sample_offsets, void* const* unique,
-  int* const* neighbor_pos, int* const* center_lid, int* counts_host, wholememory_env_func_t* p_env_fns, void* stream)
+  int* const* neighbor_pos, int* const* center_lid, int* counts_host, wholememory_env_func_t* p_env_fns, void* stream,
+  bool edges = false, int64_t* const* edge_gid = nullptr, int n_attrs = 0, const wholememory_tensor_t* attr_tensors = nullptr,
+  void* const* attr_out = nullptr)
 {
   const auto* bk = graph_backend();
   if (bk == nullptr || bk->append_unique_takes_bounds == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  if (n_attrs > 0 && bk->edge_attr_gather == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
   // sample_offsets == nullptr: a QUERY — would this chain be taken? (SUCCESS / NOT_SUPPORTED, nothing queued, no buffer needed:
   // the caller asks before it allocates the upper-bound buffers)
   const bool query = sample_offsets == nullptr;
@@ -600,6 +669,7 @@ static wholememory_error_code_t multilayer_sample_body(
   if (!query && (p_env_fns == nullptr || random_seeds == nullptr || unique == nullptr || neighbor_pos == nullptr ||
                  center_lid == nullptr || counts_host == nullptr))
     return WHOLEMEMORY_INVALID_INPUT;
+  if (!query && edges && (edge_gid == nullptr || (n_attrs > 0 && attr_out == nullptr))) return WHOLEMEMORY_INVALID_INPUT;
   wholememory_error_code_t err = WHOLEMEMORY_SUCCESS;
   wholememory_array_description_t row_desc, col_desc, seed_desc;
   if (!array_of(wm_csr_row_ptr_tensor, "wm_csr_row_ptr_tensor", &row_desc, &err)) return err;
@@ -614,6 +684,9 @@ static wholememory_error_code_t multilayer_sample_body(
     return WHOLEMEMORY_NOT_SUPPORTED;
   wm_sample_args a{};
   if (weighted) WHOLEMEMORY_RETURN_ON_FAIL(ext_weights(wm_csr_weight_ptr_tensor, col_desc, query ? nullptr : &a));
+  std::vector<edge_attr> attrs(n_attrs);
+  for (int k = 0; k < n_attrs; k++)
+    WHOLEMEMORY_RETURN_ON_FAIL(ext_edge_attr(attr_tensors[k], col_desc, query ? nullptr : &attrs[k]));
   std::vector<int64_t> cap_c(hops + 1), cap_s(hops);
   cap_c[0] = seed_desc.size;
   for (int h = 0; h < hops; h++) {
@@ -671,6 +744,7 @@ static wholememory_error_code_t multilayer_sample_body(
     WM_BK(hop_offsets(bk, a, centres_in_use, counts, offsets, scan_ws_ptr, scan_ws, stream, 1));   // offsets[nc] = samples of the hop
     a.out_ids        = ids;
     a.out_center_lid = center_lid[h];
+    a.out_edge_gid   = edges ? edge_gid[h] : nullptr;
     // the sampling kernel empties the hop's hash table on the side (one fill command fewer per hop)
     a.fill_ff_ptr = nullptr, a.fill_ff_bytes = 0;
     const bool side_fill = bk->append_unique_table_region != nullptr &&
@@ -684,11 +758,24 @@ static wholememory_error_code_t multilayer_sample_body(
     int rc = bk->append_unique_phase1(a.centers, nc, ids, ns, offsets + nc, seed_desc.dtype, ws, nullptr, nullptr, &b, stream);
     if (rc != 0) return rc == -1 ? WHOLEMEMORY_LOGIC_ERROR : WHOLEMEMORY_CUDA_ERROR;
     WM_BK(bk->append_unique_phase2(a.centers, nc, ns, ns, seed_desc.dtype, ws, unique[h], neighbor_pos[h], nullptr, nullptr, &b, stream));
+    // the attributes of the hop's sampled edges, WM_MAX_EDGE_ATTRS per launch, sized on the device by offsets[nc]
+    for (int k0 = 0; k0 < n_attrs; k0 += WM_MAX_EDGE_ATTRS) {
+      wm_edge_attr_args g{};
+      g.edge_gid = edge_gid[h], g.n_dev = offsets + nc, g.n = ns;
+      g.n_attrs  = std::min(n_attrs - k0, WM_MAX_EDGE_ATTRS);
+      for (int k = 0; k < g.n_attrs; k++) {
+        g.attr[k].gref = attrs[k0 + k].gref, g.attr[k].storage_offset = attrs[k0 + k].storage_offset;
+        g.attr[k].elt_bytes = attrs[k0 + k].elt_bytes, g.attr[k].out = attr_out[static_cast<size_t>(h) * n_attrs + k0 + k];
+      }
+      rc = bk->edge_attr_gather(&g, stream);
+      if (rc != 0) return rc == -1 ? WHOLEMEMORY_INVALID_INPUT : WHOLEMEMORY_CUDA_ERROR;
+    }
   }
   // by default the call returns complete, like every op of the reference; a host framework that declared stream-ordered
   // allocators (wholememory_ext_set_async_completion) gets it back with everything queued and synchronises when it reads
   // counts_host
   if (!async_completion_enabled() || debug_sync_enabled()) WM_BK(bk->stream_sync(stream));
+  if (edges) g_edge_chain_calls.fetch_add(1, std::memory_order_relaxed);
   return WHOLEMEMORY_SUCCESS;
 }
 
@@ -716,6 +803,28 @@ wholememory_error_code_t wholememory_ext_multilayer_sample_weighted(
                                 counts_host, p_env_fns, stream);
   WM_API_END
 }
+
+wholememory_error_code_t wholememory_ext_multilayer_sample_edges(
+  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor,
+  wholememory_tensor_t wm_csr_weight_ptr_tensor, wholememory_tensor_t seed_nodes_tensor, int hops, const int* max_sample_counts,
+  const unsigned long long* random_seeds, void* const* sample_offsets, void* const* unique, int* const* neighbor_pos,
+  int* const* center_lid, int64_t* const* edge_gid, int n_attrs, const wholememory_tensor_t* attr_tensors, void* const* attr_out,
+  int* counts_host, wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  // (before anything looks at the device or the backend)
+  if (n_attrs < 0 || (n_attrs > 0 && attr_tensors == nullptr)) return WHOLEMEMORY_INVALID_INPUT;
+  if (sample_offsets != nullptr && (edge_gid == nullptr || (n_attrs > 0 && attr_out == nullptr))) return WHOLEMEMORY_INVALID_INPUT;
+  for (int k = 0; k < n_attrs; k++)
+    if (attr_tensors[k] == nullptr) return WHOLEMEMORY_INVALID_INPUT;
+  return multilayer_sample_body(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_weight_ptr_tensor,
+                                wm_csr_weight_ptr_tensor != nullptr, seed_nodes_tensor, hops, max_sample_counts, random_seeds,
+                                sample_offsets, unique, neighbor_pos, center_lid, counts_host, p_env_fns, stream, true, edge_gid,
+                                n_attrs, attr_tensors, attr_out);
+  WM_API_END
+}
+
+int64_t wholememory_ext_edge_chain_calls(void) { return g_edge_chain_calls.load(std::memory_order_relaxed); }
 
 wholememory_error_code_t csr_add_self_loop(wholememory_tensor_t csr_row_ptr_tensor, wholememory_tensor_t csr_col_ptr_tensor,
                                            wholememory_tensor_t output_csr_row_ptr_tensor,

@@ -1416,6 +1416,66 @@ __global__ void env_test_kernel(const T* in, T* out, int64_t dim, int64_t stride
   for (int c = threadIdx.x; c < dim; c += blockDim.x) out[stride * id + c] = static_cast<T>(static_cast<T>(f_id) + in[c]);
 }
 
+// ------------------------------------------------------------------------------------------------ edge attributes
+// out_k[i] = attr_k[edge_gid[i]] for i < *n_dev, for up to kMaxEdgeAttrs edge attributes per launch: the attributes of the
+// sampled edges of one hop, fetched on the device behind the hop's kernels with no host round trip in between.
+// n_dev: the hop's sample count where the chain keeps it on the device — the LAST entry of the hop's sample_offsets array at
+// its upper-bound size, sample_offsets[h][cap_c[h]] (the offsets scan runs over all cap_c[h] + 1 entries, the ones past the
+// centres in use repeat the total): the same word append_unique reads as its neighbour count (wm_au_bounds::n_neighbor_dev),
+// written before the sampler starts. One lane per block edge: the 8-byte edge ids are read coalesced, every output is written
+// coalesced, the attribute reads are random 4- or 8-byte reads through the tensor's gref (flat or chunked, as the sampler
+// reads csr_col_ptr). The descriptors travel by value in the kernel arguments. A lane's reads of all attributes are issued
+// before its first store. Plain loads and stores only.
+struct edge_attr_desc {
+  gref_view src;
+  int64_t src_off;   // storage offset, elements
+  void* out;
+  int elt_bytes;     // 4 or 8
+};
+template <int kAttrs>
+struct edge_attr_params {
+  const int64_t* edge_gid;
+  const int* n_dev;
+  int n;             // room of edge_gid and of every output
+  edge_attr_desc attr[kAttrs];
+};
+
+template <int kAttrs>
+__global__ __launch_bounds__(kBlock) void edge_attr_gather_kernel(edge_attr_params<kAttrs> p)
+{
+  const int64_t i = static_cast<int64_t>(blockIdx.x) * kBlock + threadIdx.x;
+  const int used  = p.n_dev != nullptr ? min(p.n, *p.n_dev) : p.n;
+  if (i >= used) return;
+  const int64_t e = p.edge_gid[i];
+  uint64_t v[kAttrs];
+#pragma unroll
+  for (int k = 0; k < kAttrs; k++) {
+    const edge_attr_desc& d = p.attr[k];
+    v[k] = d.elt_bytes == 8 ? gref_load<uint64_t>(d.src, d.src_off + e) : static_cast<uint64_t>(gref_load<uint32_t>(d.src, d.src_off + e));
+  }
+#pragma unroll
+  for (int k = 0; k < kAttrs; k++) {
+    const edge_attr_desc& d = p.attr[k];
+    if (d.elt_bytes == 8)
+      static_cast<uint64_t*>(d.out)[i] = v[k];
+    else
+      static_cast<uint32_t*>(d.out)[i] = static_cast<uint32_t>(v[k]);
+  }
+}
+
+template <int kAttrs>
+int launch_edge_attr(const wm_edge_attr_args* a, int first, hipStream_t stream)
+{
+  edge_attr_params<kAttrs> p{};
+  p.edge_gid = a->edge_gid, p.n_dev = a->n_dev, p.n = static_cast<int>(a->n);
+  for (int k = 0; k < kAttrs; k++) {
+    const auto& s = a->attr[first + k];
+    p.attr[k]     = edge_attr_desc{make_view(s.gref), s.storage_offset, s.out, s.elt_bytes};
+  }
+  hipLaunchKernelGGL((edge_attr_gather_kernel<kAttrs>), dim3((p.n + kBlock - 1) / kBlock), dim3(kBlock), 0, stream, p);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
 }  // namespace
 
 int hip_env_test_fill(const void* in, void* out, wholememory_dtype_t dt, int64_t dim, int64_t entries, int64_t stride, void* stream_v)
@@ -1647,6 +1707,29 @@ int hip_csr_add_self_loop(const int* row_ptr, const int* col, int* out_row, int*
   hipLaunchKernelGGL(add_self_loop_kernel, dim3(n_rows), dim3(64), 0, static_cast<hipStream_t>(stream), row_ptr, col, out_row,
                      out_col, n_rows);
   return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+// the attributes of a hop's sampled edges (edge_attr_gather_kernel): groups of 8, 4, 2 and 1 attributes per launch
+int hip_edge_attr_gather(const wm_edge_attr_args* a, void* stream_v)
+{
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  if (a->n_attrs < 0 || a->n_attrs > WM_MAX_EDGE_ATTRS || a->n < 0 || a->n >= (INT64_C(1) << 31) - 1) return -1;
+  if (a->n_attrs > 0 && a->edge_gid == nullptr) return -1;
+  for (int k = 0; k < a->n_attrs; k++)
+    if ((a->attr[k].elt_bytes != 4 && a->attr[k].elt_bytes != 8) || a->attr[k].out == nullptr) return -1;
+  if (a->n == 0) return 0;
+  int first = 0;
+  while (first < a->n_attrs) {
+    const int left = a->n_attrs - first;
+    const int take = left >= 8 ? 8 : left >= 4 ? 4 : left >= 2 ? 2 : 1;
+    const int rc   = take == 8   ? launch_edge_attr<8>(a, first, stream)
+                     : take == 4 ? launch_edge_attr<4>(a, first, stream)
+                     : take == 2 ? launch_edge_attr<2>(a, first, stream)
+                                 : launch_edge_attr<1>(a, first, stream);
+    if (rc != 0) return rc;
+    first += take;
+  }
+  return 0;
 }
 
 }  // namespace wm

@@ -10,13 +10,17 @@ the whole chain on the CPU oracle; a multi-hop sample (unweighted, or weighted b
 rank runs as ONE library call with ONE host round trip for all hops (``wholegraph_ops.multilayer_sample``: upper-bound-sized buffers, counts kept on the
 device, views trimmed at the end; ``WM_MULTILAYER_CHAIN=0`` switches it off), and where that does not apply a hop still runs as
 one call (``wholegraph_ops.sample_append_unique``: sampler + append_unique with a single host round trip, same outputs).
+``multilayer_sample_with_edge_attributes`` and ``multilayer_sample_begin(..., edge_attr_names=[...])`` take the same two routes
+with the graph edge id of every sample carried along, the attributes fetched on the device behind each hop.
 """
 import os
+import random
 from collections import namedtuple
 from typing import List, Optional, Sequence, Union
 
 import torch
 
+from .. import binding as wmb
 from . import graph_ops, wholegraph_ops
 from .tensor import WholeMemoryTensor
 
@@ -37,19 +41,27 @@ def _chain_layers(chain, hops):
 
 
 class _DeferredSample(object):
-    """handle of GraphStructure.multilayer_sample_begin"""
+    """handle of GraphStructure.multilayer_sample_begin; `edge_attrs` = (names, names fetched by the chain) when the sample
+    carries edge attributes"""
 
-    def __init__(self, graph, node_ids, max_neighbors, random_seeds, pending, weight_name=None):
+    def __init__(self, graph, node_ids, max_neighbors, random_seeds, pending, weight_name=None, edge_attrs=None):
         self._node_ids, self._hops, self._pending, self._lists = node_ids, len(max_neighbors), pending, None
+        self._graph, self._edge_attrs = graph, edge_attrs
         if pending is None:      # not queued as one chain: sampled now, hop by hop
-            self._lists = graph._sample_hop_by_hop(node_ids, max_neighbors, weight_name, random_seeds)
+            if edge_attrs is None:
+                self._lists = graph._sample_hop_by_hop(node_ids, max_neighbors, weight_name, random_seeds)
+            else:
+                self._lists = graph._sample_hop_by_hop_with_edges(node_ids, max_neighbors, edge_attrs[0], weight_name, random_seeds)
             self.padded_frontier = self._lists[0][0]
         else:
             self.padded_frontier = pending.padded_frontier
 
     def result(self):
         if self._lists is None:
-            self._lists = _layer_lists(_chain_layers(self._pending.finish(), self._hops), self._node_ids)
+            chain = self._pending.finish()
+            self._lists = _layer_lists(_chain_layers([hop[:5] for hop in chain], self._hops), self._node_ids)
+            if self._edge_attrs is not None:
+                self._lists += (self._graph._chain_edge_attrs(chain, *self._edge_attrs),)
         return self._lists
 
 
@@ -156,7 +168,8 @@ class GraphStructure(object):
         return self._sample_hop_by_hop(node_ids, max_neighbors, weight_name, random_seeds)
 
     def multilayer_sample_begin(self, node_ids: torch.Tensor, max_neighbors: List[int], *,
-                                random_seeds: Optional[Sequence[int]] = None, weight_name: Optional[str] = None):
+                                random_seeds: Optional[Sequence[int]] = None, weight_name: Optional[str] = None,
+                                edge_attr_names: Optional[Sequence[str]] = None):
         """Extension: the multi-layer sample (weighted by the edge attribute `weight_name` when given) QUEUED, the host not
         waiting for it. Returns a handle with
           .padded_frontier   the outermost frontier (what target_gids[0] will be) at its upper-bound size, the entries behind the
@@ -165,10 +178,18 @@ class GraphStructure(object):
           .result()          one stream synchronise, then exactly what multilayer_sample_without_replacement returns.
         The feature gather of a mini-batch then runs back to back with the sampling kernels instead of behind a host round
         trip. When the one-call chain does not apply (see wholegraph_ops.multilayer_sample_begin) the sample is taken here and
-        now, hop by hop, and padded_frontier is target_gids[0] itself."""
+        now, hop by hop, and padded_frontier is target_gids[0] itself.
+        edge_attr_names (keyword): .result() returns the five lists of multilayer_sample_with_edge_attributes for these
+        names; the attributes are fetched on the device behind each hop, still without the host waiting."""
         hops = len(max_neighbors)
         if random_seeds is not None:
             assert len(random_seeds) == hops, "one seed per hop"
+        if edge_attr_names is not None:
+            names = self._checked_edge_attr_names(edge_attr_names)
+            if random_seeds is None:
+                random_seeds = [random.getrandbits(64) for _ in range(hops)]
+            pending, fetched = self._edge_chain_begin(node_ids, max_neighbors, names, weight_name, random_seeds)
+            return _DeferredSample(self, node_ids, max_neighbors, random_seeds, pending, weight_name, (names, fetched))
         pending = None
         if hops > 0 and os.environ.get("WM_MULTILAYER_CHAIN", "1") != "0":
             pending = wholegraph_ops.multilayer_sample_begin(self.csr_row_ptr.wmb_tensor, self.csr_col_ind.wmb_tensor, node_ids,
@@ -176,32 +197,93 @@ class GraphStructure(object):
                                                              wm_csr_weight_ptr_tensor=self._weights(weight_name))
         return _DeferredSample(self, node_ids, max_neighbors, random_seeds, pending, weight_name)
 
+    # ------------------------------------------------------------------------------- several hops, with edge attributes
+    def _checked_edge_attr_names(self, edge_attr_names):
+        names = list(edge_attr_names)
+        for name in names:
+            assert name == "__edge_id__" or name in self.edge_attributes, "no edge attribute named %r" % name
+        return names
+
+    def _chain_takes_edge_attribute(self, tensor: WholeMemoryTensor):
+        """what the chain's attribute kernel fetches (wholememory_ext_multilayer_sample_edges): 1-D, 4- or 8-byte elements,
+        mapped into this rank; anything else is gathered by edge id afterwards"""
+        if tensor.dim() != 1 or torch.tensor([], dtype=tensor.dtype).element_size() not in (4, 8):
+            return False
+        return wmb.lib().wholememory_get_memory_type(tensor._handle()) in (wmb.MT_CONTINUOUS, wmb.MT_CHUNKED)
+
+    def _edge_chain_begin(self, node_ids, max_neighbors, names, weight_name, random_seeds):
+        """(the chain with edge ids queued or None, names of the attributes it fetches)"""
+        if len(max_neighbors) == 0 or os.environ.get("WM_MULTILAYER_CHAIN", "1") == "0":
+            return None, []
+        fetched = []
+        for name in names:
+            if name != "__edge_id__" and name not in fetched and self._chain_takes_edge_attribute(self.edge_attributes[name]):
+                fetched.append(name)
+        pending = wholegraph_ops.multilayer_sample_begin(
+            self.csr_row_ptr.wmb_tensor, self.csr_col_ind.wmb_tensor, node_ids, max_neighbors, random_seeds,
+            wm_csr_weight_ptr_tensor=self._weights(weight_name), need_edge_ids=True,
+            wm_edge_attr_tensors=[self.edge_attributes[name] for name in fetched] if fetched else None)
+        return pending, fetched
+
+    def _edge_attr_dict(self, names, edge_id, fetched=None):
+        fetched = fetched or {}
+        return {name: edge_id if name == "__edge_id__" else fetched[name] if name in fetched
+                else self.edge_attributes[name].gather(edge_id) for name in names}
+
+    def _chain_edge_attrs(self, chain, names, fetched_names):
+        """the fifth list (outermost layer first) from the per-hop tuples of the chain with edge ids"""
+        hops = len(chain)
+        attrs = [None] * hops
+        for depth, hop in enumerate(chain):
+            fetched = dict(zip(fetched_names, hop[6])) if fetched_names else None
+            attrs[hops - 1 - depth] = self._edge_attr_dict(names, hop[5], fetched)
+        return attrs
+
+    def _sample_hop_by_hop_with_edges(self, node_ids, max_neighbors, names, weight_name, random_seeds):
+        hops = len(max_neighbors)
+        layers, attrs = [None] * hops, [None] * hops
+        frontier = node_ids
+        for depth, fanout in enumerate(max_neighbors):          # depth 0 = next to the seeds = layer hops - 1
+            seed = None if random_seeds is None else random_seeds[depth]
+            # the fused hop with edge ids (one host round trip); None = not applicable to this graph: the two ops then
+            fused = wholegraph_ops.sample_append_unique(self.csr_row_ptr.wmb_tensor, self.csr_col_ind.wmb_tensor, frontier,
+                                                        fanout, seed, wm_csr_weight_ptr_tensor=self._weights(weight_name),
+                                                        need_edge_output=True)
+            if fused is not None:
+                offsets, widened, neighbour_pos, centre_lid, edge_id = fused
+            else:
+                offsets, neighbours, centre_lid, edge_id = self._one_hop(frontier, fanout, weight_name, seed, True, True)
+                widened, neighbour_pos = graph_ops.append_unique(frontier, neighbours, need_neighbor_raw_to_unique=True)
+            layers[hops - 1 - depth] = _Hop(widened, torch.stack([neighbour_pos, centre_lid]), offsets, neighbour_pos)
+            attrs[hops - 1 - depth] = self._edge_attr_dict(names, edge_id)
+            frontier = widened
+        return _layer_lists(layers, node_ids) + (attrs,)
+
     def multilayer_sample_with_edge_attributes(self, node_ids: torch.Tensor, max_neighbors: List[int],
                                                edge_attr_names: Sequence[str], weight_name: Union[str, None] = None, *,
                                                random_seeds: Optional[Sequence[int]] = None):
         """Extension: multilayer_sample_without_replacement plus the attributes of the SAMPLED edges. Returns its four lists
         and a fifth, per layer (outermost first) a dict {name: tensor [n_edges]} aligned with that layer's csr_col_ind:
         entry e is the named edge attribute at the graph edge that block edge e was drawn from. The name "__edge_id__"
-        delivers those int64 graph edge ids (positions in the graph's csr_col_ind) themselves. The sample is taken hop by
-        hop over the one-hop sampler with edge output; with the same random_seeds the four lists equal
-        multilayer_sample_without_replacement's."""
-        names = list(edge_attr_names)
-        for name in names:
-            assert name == "__edge_id__" or name in self.edge_attributes, "no edge attribute named %r" % name
+        delivers those int64 graph edge ids (positions in the graph's csr_col_ind) themselves. Routes, first that applies:
+        the one-call chain with edge ids (``wholegraph_ops.multilayer_sample(..., need_edge_ids=True)``: one host round trip
+        for all hops, 1-D attributes of 4- or 8-byte elements mapped into this rank fetched on the device behind each hop;
+        ``WM_MULTILAYER_CHAIN=0`` switches it off), the fused hop with edge ids hop by hop, the one-hop sampler with edge
+        output + append_unique. Attributes the chain does not fetch are gathered by edge id afterwards. Every route returns
+        the same values; with the same random_seeds the four lists equal multilayer_sample_without_replacement's. Without
+        random_seeds one 64-bit seed per hop is drawn from `random`, in hop order."""
+        names = self._checked_edge_attr_names(edge_attr_names)
         hops = len(max_neighbors)
         if random_seeds is not None:
             assert len(random_seeds) == hops, "one seed per hop"
-        layers, attrs = [None] * hops, [None] * hops
-        frontier = node_ids
-        for depth, fanout in enumerate(max_neighbors):          # depth 0 = next to the seeds = layer hops - 1
-            seed = None if random_seeds is None else random_seeds[depth]
-            offsets, neighbours, centre_lid, edge_id = self._one_hop(frontier, fanout, weight_name, seed, True, True)
-            widened, neighbour_pos = graph_ops.append_unique(frontier, neighbours, need_neighbor_raw_to_unique=True)
-            layers[hops - 1 - depth] = _Hop(widened, torch.stack([neighbour_pos, centre_lid]), offsets, neighbour_pos)
-            attrs[hops - 1 - depth] = {name: edge_id if name == "__edge_id__" else self.edge_attributes[name].gather(edge_id)
-                                       for name in names}
-            frontier = widened
-        return _layer_lists(layers, node_ids) + (attrs,)
+        else:
+            random_seeds = [random.getrandbits(64) for _ in range(hops)]
+        pending, fetched = self._edge_chain_begin(node_ids, max_neighbors, names, weight_name, random_seeds)
+        if pending is not None:
+            chain = pending.finish()
+            return _layer_lists(_chain_layers([hop[:5] for hop in chain], hops), node_ids) + (
+                self._chain_edge_attrs(chain, names, fetched),)
+        return self._sample_hop_by_hop_with_edges(node_ids, max_neighbors, names, weight_name, random_seeds)
 
     def _sample_hop_by_hop(self, node_ids, max_neighbors, weight_name, random_seeds):
         hops = len(max_neighbors)

@@ -10,6 +10,7 @@ from typing import Union
 import torch
 
 from .. import binding as wmb
+from .utils import wholememory_dtype_to_torch_dtype
 from .wholegraph_env import TorchMemoryContext, get_stream, get_wholegraph_env_fns, op_device, wrap_torch_tensor
 
 
@@ -55,13 +56,15 @@ def unweighted_sample_without_replacement(wm_csr_row_ptr_tensor, wm_csr_col_ptr_
 
 
 def sample_append_unique(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, center_nodes_tensor: torch.Tensor, max_sample_count: int,
-                         random_seed: Union[int, None] = None, *, wm_csr_weight_ptr_tensor=None):
+                         random_seed: Union[int, None] = None, *, wm_csr_weight_ptr_tensor=None, need_edge_output: bool = False):
     """Extension (include/wholememory/wholegraph_amd_ext.h): one hop = unweighted sampling + append_unique(center nodes,
     sampled neighbours) in ONE call with one host round trip. Returns (sample_offset int32 [n + 1], unique nodes, position of
     every sampled neighbour in `unique` int32, center local id int32) — or None when the library declines (CSR not mapped
     into this rank, dtypes differ, empty frontier, max_sample_count <= 0): run the two ops then.
     wm_csr_weight_ptr_tensor (keyword): the hop samples with the weighted sampler on these edge weights; also declined for a
-    weight tensor that is not mapped, not float / double or not one entry per edge, and for max_sample_count > 8192."""
+    weight tensor that is not mapped, not float / double or not one entry per edge, and for max_sample_count > 8192.
+    need_edge_output (keyword): a fifth tensor, the int64 graph edge id (position in csr_col_ptr) of every sampled neighbour
+    (wholememory_ext_sample_append_unique_edges); declined in the same cases."""
     row, col = _handle(wm_csr_row_ptr_tensor), _handle(wm_csr_col_ptr_tensor)
     assert center_nodes_tensor.dim() == 1
     if random_seed is None:
@@ -71,13 +74,20 @@ def sample_append_unique(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, center_no
     wc, wo = wrap_torch_tensor(center_nodes_tensor), wrap_torch_tensor(offset)
     tail = (int(max_sample_count), C.c_ulonglong(random_seed & 0xFFFFFFFFFFFFFFFF), wo.handle, C.c_void_p(uniq.get_c_context()),
             C.c_void_p(pos.get_c_context()), C.c_void_p(lid.get_c_context()), get_wholegraph_env_fns(), C.c_void_p(get_stream()))
-    if wm_csr_weight_ptr_tensor is None:
+    egid = TorchMemoryContext() if need_edge_output else None
+    if need_edge_output:
+        wgt = None if wm_csr_weight_ptr_tensor is None else _handle(wm_csr_weight_ptr_tensor)
+        rc = wmb.lib().wholememory_ext_sample_append_unique_edges(row, col, wgt, wc.handle, *tail[:6],
+                                                                  C.c_void_p(egid.get_c_context()), *tail[6:])
+    elif wm_csr_weight_ptr_tensor is None:
         rc = wmb.lib().wholememory_ext_sample_append_unique(row, col, wc.handle, *tail)
     else:
         rc = wmb.lib().wholememory_ext_weighted_sample_append_unique(row, col, _handle(wm_csr_weight_ptr_tensor), wc.handle, *tail)
     if rc == wmb.NOT_SUPPORTED:
         return None
     wmb.check(rc)
+    if need_edge_output:
+        return offset, uniq.get_tensor(), pos.get_tensor(), lid.get_tensor(), egid.get_tensor()
     return offset, uniq.get_tensor(), pos.get_tensor(), lid.get_tensor()
 
 
@@ -105,10 +115,12 @@ class PendingMultilayerSample:
     """A multi-hop sample whose kernels are queued and whose counts the host has not read yet (multilayer_sample_begin).
     `padded_frontier` is the outermost frontier at its full upper-bound size, the entries behind the sampled nodes set to -1:
     it can be handed to a gather right away (negative ids are skipped). `finish()` synchronises the stream once, trims every
-    output and returns what multilayer_sample returns."""
+    output and returns what multilayer_sample returns. `edge_ids` / `edge_attrs` (per hop: the int64 edge ids and a list of
+    attribute tensors, at their upper-bound sizes) add a sixth / seventh entry to every hop's tuple."""
 
-    def __init__(self, hops, n0, offsets, uniques, edges, counts, stream):
+    def __init__(self, hops, n0, offsets, uniques, edges, counts, stream, edge_ids=None, edge_attrs=None):
         self._hops, self._n0, self._offsets, self._uniques, self._edges = hops, n0, offsets, uniques, edges
+        self._edge_ids, self._edge_attrs = edge_ids, edge_attrs
         self._counts, self._result = counts, None
         self.padded_frontier = uniques[-1]
         # finish() waits for THIS chain, not for whatever the caller queues behind it (the feature gather on padded_frontier
@@ -138,7 +150,12 @@ class PendingMultilayerSample:
             edge = _compact(self._edges[h][:, :n_samples])
             # (the outermost frontier stays a view of the padded array a gather may still be reading)
             uniq = self._uniques[h][:n_c + n_new] if h == self._hops - 1 else _compact(self._uniques[h][:n_c + n_new])
-            out.append((_compact(self._offsets[h][:n_c + 1]), uniq, edge[0], edge[1], edge))
+            hop = (_compact(self._offsets[h][:n_c + 1]), uniq, edge[0], edge[1], edge)
+            if self._edge_ids is not None:
+                hop += (_compact(self._edge_ids[h][:n_samples]),)
+            if self._edge_attrs is not None:
+                hop += ([_compact(t[:n_samples]) for t in self._edge_attrs[h]],)
+            out.append(hop)
             n_c += n_new
         self.n_frontier = n_c
         self._result = out
@@ -146,20 +163,35 @@ class PendingMultilayerSample:
 
 
 def multilayer_sample_begin(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, seed_nodes_tensor: torch.Tensor, max_sample_counts,
-                            random_seeds=None, *, wm_csr_weight_ptr_tensor=None):
+                            random_seeds=None, *, wm_csr_weight_ptr_tensor=None, need_edge_ids: bool = False,
+                            wm_edge_attr_tensors=None):
     """Queues every hop of an unweighted multi-layer sample (wholememory_ext_multilayer_sample: one library call, counts kept
     on the device between hops, no host round trip) and returns a PendingMultilayerSample WITHOUT waiting — or None when the
     library declines (CSR not mapped into this rank, dtypes differ, empty seeds, upper bounds beyond append_unique's hash-table
     route or beyond the memory budget, allocation failure): run hop by hop then.
     wm_csr_weight_ptr_tensor (keyword): every hop samples with the weighted sampler on these edge weights
     (wholememory_ext_multilayer_sample_weighted); also declined for a weight tensor that is not mapped, not float / double or
-    not one entry per edge, and for a fan-out above 8192."""
+    not one entry per edge, and for a fan-out above 8192.
+    need_edge_ids (keyword): every hop also delivers the int64 graph edge id of each sample
+    (wholememory_ext_multilayer_sample_edges). wm_edge_attr_tensors (keyword, implies need_edge_ids): a sequence of edge
+    attribute tensors whose values at the sampled edges are fetched on the device behind each hop, in the given order; the
+    chain is also declined when one of them is not 1-D, not of 4- or 8-byte elements, not one entry per edge or not mapped
+    into this rank."""
     row, col = _handle(wm_csr_row_ptr_tensor), _handle(wm_csr_col_ptr_tensor)
-    if wm_csr_weight_ptr_tensor is None:
-        chain = lambda *rest: wmb.lib().wholememory_ext_multilayer_sample(row, col, *rest)
+    attr_handles = None if wm_edge_attr_tensors is None else [_handle(t) for t in wm_edge_attr_tensors]
+    with_edges = bool(need_edge_ids) or attr_handles is not None
+    n_attrs = 0 if attr_handles is None else len(attr_handles)
+    if with_edges:
+        wgt = None if wm_csr_weight_ptr_tensor is None else _handle(wm_csr_weight_ptr_tensor)
+        attr_arr = (C.c_void_p * n_attrs)(*[getattr(h, "value", h) for h in attr_handles]) if n_attrs else None
+        # (the edge id / attribute pointer arrays sit between center_lid and counts_host)
+        chain = lambda *rest: wmb.lib().wholememory_ext_multilayer_sample_edges(
+            row, col, wgt, *rest[:8], rest[11], n_attrs, attr_arr, rest[12], *rest[8:11])
+    elif wm_csr_weight_ptr_tensor is None:
+        chain = lambda *rest: wmb.lib().wholememory_ext_multilayer_sample(row, col, *rest[:11])
     else:
         wgt = _handle(wm_csr_weight_ptr_tensor)
-        chain = lambda *rest: wmb.lib().wholememory_ext_multilayer_sample_weighted(row, col, wgt, *rest)
+        chain = lambda *rest: wmb.lib().wholememory_ext_multilayer_sample_weighted(row, col, wgt, *rest[:11])
     assert seed_nodes_tensor.dim() == 1
     hops = len(max_sample_counts)
     n0 = seed_nodes_tensor.shape[0]
@@ -176,27 +208,39 @@ def multilayer_sample_begin(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, seed_n
     idt = seed_nodes_tensor.dtype
     # outputs + the library's scratch (ids, hash table of 2 slots per key, positions ...): ~ 10 words per sampled neighbour
     need = sum(4 * (cap_c[h] + 1) + idt.itemsize * cap_c[h + 1] + 8 * cap_s[h] + 40 * (cap_c[h] + cap_s[h]) for h in range(hops))
+    attr_dtypes = []
+    if with_edges:
+        for h in attr_handles or ():
+            attr_dtypes.append(wholememory_dtype_to_torch_dtype(
+                wmb.lib().wholememory_tensor_get_tensor_description(h).contents.dtype))
+        need += sum((8 + sum(dt.itemsize for dt in attr_dtypes)) * cap_s[h] for h in range(hops))
     if need > _multilayer_budget_bytes():
         return None
     fan = (C.c_int * hops)(*[int(m) for m in max_sample_counts])
     ws = wrap_torch_tensor(seed_nodes_tensor)
     # ask first (no buffers yet); anything but SUCCESS is a decline
-    if chain(ws.handle, hops, fan, None, None, None, None, None, None, None, None) != wmb.WHOLEMEMORY_SUCCESS:
+    if chain(ws.handle, hops, fan, None, None, None, None, None, None, None, None, None, None) != wmb.WHOLEMEMORY_SUCCESS:
         return None
     dev = op_device()
     try:
         offsets = [torch.empty(cap_c[h] + 1, device=dev, dtype=torch.int) for h in range(hops)]
         uniques = [torch.empty(cap_c[h + 1], device=dev, dtype=idt) for h in range(hops)]
         edges = [torch.empty((2, max(cap_s[h], 1)), device=dev, dtype=torch.int) for h in range(hops)]   # row 0 positions, row 1 centre ids
+        edge_ids = [torch.empty(max(cap_s[h], 1), device=dev, dtype=torch.int64) for h in range(hops)] if with_edges else None
+        edge_attrs = None if attr_handles is None else [
+            [torch.empty(max(cap_s[h], 1), device=dev, dtype=dt) for dt in attr_dtypes] for h in range(hops)]
     except torch.OutOfMemoryError:
         return None
     pool = _pinned_pool.setdefault(hops, [])
     counts = pool.pop() if pool else torch.zeros(2 * hops, dtype=torch.int32).pin_memory()
     rng = (C.c_ulonglong * hops)(*[int(s) & 0xFFFFFFFFFFFFFFFF for s in random_seeds])
-    ptrs = lambda ts: (C.c_void_p * hops)(*[t.data_ptr() for t in ts])
+    ptrs = lambda ts: (C.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+    egid_ptrs = ptrs(edge_ids) if with_edges else None
+    attr_ptrs = ptrs([t for per_hop in edge_attrs for t in per_hop]) if n_attrs else None    # [h * n_attrs + k]
     try:
         rc = chain(ws.handle, hops, fan, rng, ptrs(offsets), ptrs(uniques), ptrs([e[0] for e in edges]),
-                   ptrs([e[1] for e in edges]), C.c_void_p(counts.data_ptr()), get_wholegraph_env_fns(), C.c_void_p(get_stream()))
+                   ptrs([e[1] for e in edges]), C.c_void_p(counts.data_ptr()), get_wholegraph_env_fns(), C.c_void_p(get_stream()),
+                   egid_ptrs, attr_ptrs)
     except torch.OutOfMemoryError:      # the library's scratch comes from torch's allocator through the env functions
         rc = wmb.NOT_SUPPORTED
     if rc != wmb.WHOLEMEMORY_SUCCESS:
@@ -204,19 +248,23 @@ def multilayer_sample_begin(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, seed_n
         if rc in (wmb.NOT_SUPPORTED, wmb.OUT_OF_MEMORY):
             return None
         wmb.check(rc)
-    return PendingMultilayerSample(hops, n0, offsets, uniques, edges, counts, torch.cuda.current_stream())
+    return PendingMultilayerSample(hops, n0, offsets, uniques, edges, counts, torch.cuda.current_stream(), edge_ids, edge_attrs)
 
 
 def multilayer_sample(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, seed_nodes_tensor: torch.Tensor, max_sample_counts,
-                      random_seeds=None, *, wm_csr_weight_ptr_tensor=None):
+                      random_seeds=None, *, wm_csr_weight_ptr_tensor=None, need_edge_ids: bool = False,
+                      wm_edge_attr_tensors=None):
     """Extension (wholememory_ext_multilayer_sample): every hop of an unweighted multi-layer sample in ONE library call with no
     host round trip inside — buffers sized for their upper bounds, counts kept on the device between hops, ONE stream
     synchronise here at the end. Returns a list with one (sample_offset, unique, neighbor_pos, center_lid, edge_index) tuple per
     hop, hop 0 next to the seeds, each tensor trimmed to its size and equal to what `sample_append_unique` returns hop by hop
     with the same seeds — or None when the library declines (see multilayer_sample_begin): run hop by hop then.
-    wm_csr_weight_ptr_tensor (keyword): the weighted sampler on these edge weights, see multilayer_sample_begin."""
+    wm_csr_weight_ptr_tensor (keyword): the weighted sampler on these edge weights, see multilayer_sample_begin.
+    need_edge_ids / wm_edge_attr_tensors (keyword): a sixth entry per hop, the int64 graph edge ids of the samples, and a
+    seventh, the list of the given edge attributes at those edges; see multilayer_sample_begin."""
     pending = multilayer_sample_begin(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, seed_nodes_tensor, max_sample_counts,
-                                      random_seeds, wm_csr_weight_ptr_tensor=wm_csr_weight_ptr_tensor)
+                                      random_seeds, wm_csr_weight_ptr_tensor=wm_csr_weight_ptr_tensor,
+                                      need_edge_ids=need_edge_ids, wm_edge_attr_tensors=wm_edge_attr_tensors)
     return None if pending is None else pending.finish()
 
 

@@ -548,6 +548,43 @@ enum wholememory_error_code_t wholememory_ext_csc_aggregate_weighted_backward(co
                                                                               struct wholememory_env_func_t* p_env_fns,
                                                                               void* stream);
 
+/* ---- (2e) agg_concat straight from a WholeMemory table (`gather_agg_concat`) ---------------------------------------- */
+/* (2b) whose rows are read from a table by global id instead of from a dense x: layer 0 of a GNN without the gathered
+ * [n_src, dim] intermediate. `table` is a 2-D WholeMemory tensor [N, dim] of FLOAT, HALF or BF16 with contiguous rows;
+ * node_ids [n_src] (WHOLEMEMORY_DT_INT or WHOLEMEMORY_DT_INT64, device memory) holds the global row of every node of the
+ * block, the targets first. Define x[i] = fp32(table[node_ids[i]]) for i < n_src; widening is exact. Then, with row_ptr
+ * int32 [n_dst + 1] and col_ind int32 [n_edges] in [0, n_src) as for (2b):
+ *   out[d, 0:dim]    = A(d) of (2b) over x: S(d) = fp32 sum of x[col_ind[e]] for e = row_ptr[d] .. row_ptr[d+1] - 1, added
+ *                      left to right from the first term; SUM: A = S; MEAN: A = S * fl(1.0f / deg(d)); no edge: +0.0.
+ *   out[d, dim:2dim] = x[d].
+ * out [n_dst, out_stride] is fp32, out_stride >= 2 * dim. Hence the result equals wholememory_ext_csc_aggregate_forward over
+ * the rows wholememory_gather would write for node_ids as fp32, bit for bit.
+ * Every id must lie in [0, N) (graph_append_unique's output does): the op does not check, and as in wholememory_gather an id
+ * out of range is undefined (there is no "skip me" id here). A subtensor view is honoured: storage offset and row stride come
+ * from the tensor description, in elements.
+ * CONTINUOUS and CHUNKED tables (device- or host-located) and pointer-backed tensors are read through their global
+ * reference, by the calling rank alone; DISTRIBUTED and HIERARCHY tables are NOT_SUPPORTED (nothing queued): gather, then
+ * (2b). There is no backward entry point: the gradient with respect to x is wholememory_ext_csc_aggregate_backward.
+ * INVALID_INPUT, before any device work, for what (2b) rejects and for a null table, a table that is not 2-D or whose dtype
+ * is not FLOAT / HALF / BF16, a node_id_dtype other than INT / INT64, null node_ids with n_src > 0, out_stride < 2 * dim.
+ * NOT_SUPPORTED (nothing queued) when the device backend has no such kernel. */
+enum wholememory_error_code_t wholememory_ext_csc_gather_aggregate_forward(wholememory_tensor_t table,
+                                                                           const void* node_ids,
+                                                                           int node_id_dtype,
+                                                                           const int32_t* row_ptr,
+                                                                           const int32_t* col_ind,
+                                                                           int64_t n_edges,
+                                                                           int64_t n_dst,
+                                                                           int64_t n_src,
+                                                                           int aggr,
+                                                                           float* out,
+                                                                           int64_t out_stride,
+                                                                           struct wholememory_env_func_t* p_env_fns,
+                                                                           void* stream);
+/* wholememory_ext_csc_gather_aggregate_forward calls that reached the device backend (this process). A counter for tests:
+ * it tells the fused route from the gather + (2b) composition. */
+int64_t wholememory_ext_gather_aggregate_calls(void);
+
 /* ---- (3) testing seam ---------------------------------------------------------------------- */
 /* Replaces the device backend. Refuses (WHOLEMEMORY_NOT_SUPPORTED) unless the environment has
  * WHOLEGRAPH_AMD_TESTING=1. `backend` is a const wm_device_backend* (wholegraph_amd/csrc/backend.hpp);

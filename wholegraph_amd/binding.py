@@ -290,6 +290,9 @@ PROTOTYPES = {
                                                          _P(EnvFunc), _vp]),
     "wholememory_ext_csc_aggregate_weighted_forward": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i, _vp, _i64,
                                                            _P(EnvFunc), _vp]),
+    "wholememory_ext_csc_gather_aggregate_forward": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _i64, _i64, _i, _vp, _i64, _P(EnvFunc),
+                                                         _vp]),
+    "wholememory_ext_gather_aggregate_calls": (_i64, []),
     "wholememory_ext_csc_aggregate_weighted_backward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i,
                                                             _vp, _i64, _vp, _P(EnvFunc), _vp]),
     "wholememory_ext_csc_gat_forward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _i64, C.c_float, _i, _vp,

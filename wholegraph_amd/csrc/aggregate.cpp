@@ -1,8 +1,12 @@
 // wholegraph_amd — host side of the neighbour aggregation of a sampled CSC block (wholegraph_amd_ext.h, section 2b):
 // validation, the edge index of the backward (the library's id sort over col_ind) and the launches of kernels/agg.hip
 // (fp32 rows), kernels/agg_half.hip (fp16 / bf16 rows, the _typed entry points) and kernels/agg_weighted.hip (a weight per
-// edge, section 2d, the _weighted entry points). The semantics, and the one order of every fp32 sum, are stated in the header.
+// edge, section 2d, the _weighted entry points) and kernels/agg_gather.hip (rows read from a WholeMemory table by global id,
+// section 2e). The semantics, and the one order of every fp32 sum, are stated in the header.
+#include <atomic>
+
 #include <wholememory/wholegraph_amd_ext.h>
+#include <wholememory/wholememory_tensor.h>
 
 #include "ops_internal.hpp"
 
@@ -103,6 +107,8 @@ wm_aggw_args make_args_w(const int32_t* row_ptr, const int32_t* col_ind, const f
 }
 
 bool rows16(wholememory_dtype_t dtype) { return dtype == WHOLEMEMORY_DT_HALF || dtype == WHOLEMEMORY_DT_BF16; }
+
+std::atomic<int64_t> g_gather_agg_calls{0};   // fused forwards that reached the backend
 
 }  // namespace
 
@@ -273,5 +279,56 @@ wholememory_error_code_t wholememory_ext_csc_aggregate_weighted_backward(
 }
 
 int64_t wholememory_ext_csc_aggregate_chunk_edges(void) { return wm::kAggChunkEdges; }
+
+wholememory_error_code_t wholememory_ext_csc_gather_aggregate_forward(wholememory_tensor_t table, const void* node_ids,
+                                                                      int node_id_dtype, const int32_t* row_ptr,
+                                                                      const int32_t* col_ind, int64_t n_edges, int64_t n_dst,
+                                                                      int64_t n_src, int aggr, float* out, int64_t out_stride,
+                                                                      wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  (void)p_env_fns;   // (the forward needs no scratch)
+  const auto* bk = backend();
+  if (bk->gather_agg_forward == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  if (table == nullptr) throw invalid_input("table is null");
+  const wholememory_tensor_description_t td = *wholememory_tensor_get_tensor_description(table);
+  if (td.dim != 2) throw invalid_input("the table must be a 2-D tensor");
+  if (td.dtype != WHOLEMEMORY_DT_FLOAT && !rows16(td.dtype)) throw invalid_input("table dtype must be FLOAT, HALF or BF16");
+  if (td.strides[1] != 1) throw invalid_input("the table's rows must be contiguous");
+  if (node_id_dtype != WHOLEMEMORY_DT_INT && node_id_dtype != WHOLEMEMORY_DT_INT64)
+    throw invalid_input("node_id_dtype must be INT or INT64");
+  const int64_t dim = td.sizes[1];
+  // (the virtual x: n_src rows of `dim` elements behind node_ids)
+  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, node_ids, dim, dim, dim, aggr, out, out_stride, 2 * dim, n_src, n_dst);
+  if (n_src > 0 && td.sizes[0] < 1) throw invalid_input("node ids into a table without rows");
+  if (wholememory_tensor_has_handle(table)) {
+    const auto mt = wholememory_get_memory_type(wholememory_tensor_get_memory_handle(table));
+    if (mt != WHOLEMEMORY_MT_CONTINUOUS && mt != WHOLEMEMORY_MT_CHUNKED) return WHOLEMEMORY_NOT_SUPPORTED;
+    if (mapped_via_exchange(table, mt)) return WHOLEMEMORY_NOT_SUPPORTED;   // (served by a collective, not by loads)
+  }
+  wm_gather_agg_args a{};
+  WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(table, &a.gref));
+  a.table_dtype          = td.dtype;
+  a.table_rows           = td.sizes[0];
+  a.table_stride         = td.strides[0];
+  a.table_storage_offset = td.storage_offset;
+  a.node_ids             = node_ids;
+  a.node_id_dtype        = static_cast<wholememory_dtype_t>(node_id_dtype);
+  a.row_ptr              = row_ptr;
+  a.col_ind              = col_ind;
+  a.n_edges              = n_dst == 0 ? 0 : n_edges;   // (no target, no edge of any target)
+  a.n_dst                = n_dst;
+  a.n_src                = n_src;
+  a.dim                  = dim;
+  a.mean                 = aggr == WHOLEMEMORY_EXT_AGGR_MEAN ? 1 : 0;
+  a.out                  = out;
+  a.out_stride           = out_stride;
+  WM_BK(bk->gather_agg_forward(&a, stream));
+  g_gather_agg_calls.fetch_add(1, std::memory_order_relaxed);
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+int64_t wholememory_ext_gather_aggregate_calls(void) { return g_gather_agg_calls.load(std::memory_order_relaxed); }
 
 }  // extern "C"

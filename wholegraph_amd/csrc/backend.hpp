@@ -260,6 +260,25 @@ struct wm_edge_attr_args {
   } attr[WM_MAX_EDGE_ATTRS];
 };
 
+// agg_concat over rows that come from a WholeMemory table by global id (kernels/agg_gather.hip, wholegraph_amd_ext.h section
+// 2e): x[i] = fp32(table[node_ids[i]]) for i < n_src is never materialised. `gref` addresses the table (continuous or
+// chunked); stride / offset / dim in ELEMENTS of table_dtype (FLOAT, HALF or BF16); out is fp32
+struct wm_gather_agg_args {
+  wholememory_gref_t gref;
+  wholememory_dtype_t table_dtype;
+  int64_t table_rows;               // rows of the (sub)tensor: ids are in [0, table_rows)
+  int64_t table_stride;             // elements
+  int64_t table_storage_offset;     // elements
+  const void* node_ids;             // [n_src] int32 / int64, device
+  wholememory_dtype_t node_id_dtype;
+  const int32_t* row_ptr;           // [n_dst + 1]
+  const int32_t* col_ind;           // [n_edges], ids in [0, n_src)
+  int64_t n_edges, n_dst, n_src, dim;
+  int mean;                         // 1: "mean" (sum times fl(1 / degree)), 0: "sum"
+  float* out;                       // [n_dst, out_stride] (2 * dim columns)
+  int64_t out_stride;
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -477,6 +496,9 @@ struct wm_device_backend {
                        const int64_t* n_unique_dev, void* workspace, void* stream);
   // ---- attributes of sampled edges (kernels/graph.hip: edge_attr_gather_kernel); nullptr in a backend without it ----
   int (*edge_attr_gather)(const wm_edge_attr_args* a, void* stream);
+  // ---- agg_forward over rows read from a WholeMemory table by global id (kernels/agg_gather.hip); nullptr in a backend
+  // without it ----
+  int (*gather_agg_forward)(const wm_gather_agg_args* a, void* stream);
 };
 
 }  // extern "C"

@@ -81,6 +81,7 @@ int hip_aggw_forward(const wm_aggw_args* a, void* stream);
 int hip_aggw_backward(const wm_aggw_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
                       const int64_t* n_unique_dev, void* workspace, void* stream);
 int hip_edge_attr_gather(const wm_edge_attr_args* a, void* stream);
+int hip_gather_agg_forward(const wm_gather_agg_args* a, void* stream);
 size_t hip_gat_forward_workspace_bytes(const wm_gat_args* a);
 int hip_gat_forward(const wm_gat_args* a, void* workspace, void* stream);
 size_t hip_gat_backward_workspace_bytes(const wm_gat_args* a);
@@ -265,6 +266,7 @@ const wm_device_backend kHipBackend = {
   hip_aggw_forward,
   hip_aggw_backward,
   hip_edge_attr_gather,
+  hip_gather_agg_forward,
 };
 
 }  // namespace

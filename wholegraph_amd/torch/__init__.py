@@ -5,11 +5,12 @@ communicators, initialisation, WholeMemory tensors, embeddings / optimizers / ca
 functors, neighbour sampling and GraphStructure, and for the GNN model surface of the ``cugraph`` framework route
 (``set_framework``, ``create_gnn_layers``, ``create_sub_graph``, ``HomoGNNModel``; the GraphSAGE and GAT layers in
 ``cugraphops``, on the HIP ops of ``aggregation`` and ``gat_aggregation``; and, beyond the reference, the edge-weighted
-GraphSAGE layer ``cugraphops.EdgeWeightedSAGEConv`` on ``weighted_aggregation``). GAT in ``HomoGNNModel``, the dgl / pyg / wg
+GraphSAGE layer ``cugraphops.EdgeWeightedSAGEConv`` on ``weighted_aggregation`` and ``gather_aggregation``, layer 0's
+aggregation straight from a WholeMemory table). GAT in ``HomoGNNModel``, the dgl / pyg / wg
 routes, data loaders, launch helpers and option parsers of the reference are outside this build's scope.
 """
 from . import comm, embedding, graph_ops, graph_structure, initialize, tensor, utils, wholegraph_ops, wholememory_ops
-from . import aggregation, cugraphops, gat_aggregation, gnn_model, weighted_aggregation
+from . import aggregation, cugraphops, gat_aggregation, gather_aggregation, gnn_model, weighted_aggregation
 
 _PUBLIC = {
     comm: ("WholeMemoryCommunicator create_group_communicator destroy_communicator get_global_communicator "
@@ -25,8 +26,10 @@ _PUBLIC = {
     wholememory_ops: "wholememory_gather_forward_functor wholememory_scatter_functor",
     graph_structure: "GraphStructure",
     gnn_model: "set_framework create_gnn_layers create_sub_graph HomoGNNModel",
+    gather_aggregation: "gather_agg_concat",
 }
-__all__ = ["graph_ops", "wholegraph_ops", "aggregation", "cugraphops", "gat_aggregation", "gnn_model", "weighted_aggregation"]
+__all__ = ["graph_ops", "wholegraph_ops", "aggregation", "cugraphops", "gat_aggregation", "gnn_model", "weighted_aggregation",
+           "gather_aggregation"]
 for _module, _names in _PUBLIC.items():
     for _name in _names.split():
         globals()[_name] = getattr(_module, _name)

@@ -6,6 +6,7 @@ from torch import Tensor
 from torch.nn import Linear
 
 from ..aggregation import aggr_code, agg_concat
+from ..gather_aggregation import gather_agg_concat
 
 
 class CuGraphSAGEConv(torch.nn.Module):
@@ -49,7 +50,21 @@ class CuGraphSAGEConv(torch.nn.Module):
         del max_num_neighbors
         if self.project:
             x = self.pre_lin(x).relu()
-        out = agg_concat(x, csr_row_ptr, csr_col_ind, self.aggr)
+        return self._after_aggregation(agg_concat(x, csr_row_ptr, csr_col_ind, self.aggr))
+
+    def forward_from_table(self, source, node_ids: Tensor, csr_row_ptr: Tensor, csr_col_ind: Tensor, max_num_neighbors: int,
+                           is_training: bool = False) -> Tensor:
+        """``forward`` whose ``x`` is ``source[node_ids]`` (a ``WholeMemoryEmbedding`` or ``WholeMemoryTensor``, rows widened
+        to float32), read by the aggregation itself (``gather_agg_concat``): the first layer of a model without the gathered
+        feature matrix. Same result as ``forward(source.gather(node_ids, force_dtype=torch.float32), ...)``, bit for bit.
+        ``is_training``: hand the row gradients to the embedding's optimizer, as ``WholeMemoryEmbeddingModule`` does."""
+        del max_num_neighbors
+        if self.project:
+            raise ValueError("forward_from_table needs project=False: pre_lin must see the rows before they are aggregated")
+        return self._after_aggregation(gather_agg_concat(source, node_ids, csr_row_ptr, csr_col_ind, self.aggr,
+                                                         is_training=is_training))
+
+    def _after_aggregation(self, out: Tensor) -> Tensor:
         if self.root_weight:
             out = self.lin(out)
         else:

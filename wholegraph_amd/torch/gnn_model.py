@@ -5,7 +5,9 @@ layer itself is ``cugraphops.CuGraphGATConv``).
 
 Flow of ``HomoGNNModel.forward`` (the reference's): sample ``layernum`` hops from the seed ids, gather the float32
 features of the outermost frontier through ``WholeMemoryEmbeddingModule`` (so the embedding receives gradients), then one
-layer per hop from the outermost block inwards, with relu and dropout between layers."""
+layer per hop from the outermost block inwards, with relu and dropout between layers. With ``args.fuse_gather`` (an
+extension, off by default) the outermost layer reads its rows from the embedding itself (``forward_from_table``) and the
+feature gather is skipped: same logits and same embedding gradients, bit for bit."""
 import torch
 import torch.nn.functional as F
 
@@ -94,18 +96,23 @@ class HomoGNNModel(torch.nn.Module):
         self.dropout = args.dropout
         self.max_neighbors = parse_max_neighbors(args.layernum, args.neighbors)
         self.max_inference_neighbors = parse_max_neighbors(args.layernum, getattr(args, "inferencesample", args.neighbors))
+        self.fuse_gather = bool(getattr(args, "fuse_gather", False))
 
     def forward(self, ids):
         max_neighbors = self.max_neighbors if self.training else self.max_inference_neighbors
         ids = ids.to(self.graph_structure.csr_col_ind.dtype).cuda()
         target_gids, edge_indice, csr_row_ptrs, csr_col_inds = self.graph_structure.multilayer_sample_without_replacement(
             ids, max_neighbors)
-        x_feat = self.gather_fn(target_gids[0], force_dtype=torch.float32)
+        x_feat = None if self.fuse_gather else self.gather_fn(target_gids[0], force_dtype=torch.float32)
         for i in range(self.num_layer):
-            x_target_feat = x_feat[:target_gids[i + 1].numel()]
             sub_graph = create_sub_graph(target_gids[i], target_gids[i + 1], edge_indice[i], csr_row_ptrs[i],
                                          csr_col_inds[i], max_neighbors[self.num_layer - 1 - i], self.add_self_loop)
-            x_feat = layer_forward(self.gnn_layers[i], x_feat, x_target_feat, sub_graph)
+            if x_feat is None:   # (layer 0 of the fused route: the rows come from the table, by id)
+                x_feat = self.gnn_layers[0].forward_from_table(self.node_embedding, target_gids[0], sub_graph[0], sub_graph[1],
+                                                               sub_graph[2], is_training=self.training)
+            else:
+                x_target_feat = x_feat[:target_gids[i + 1].numel()]
+                x_feat = layer_forward(self.gnn_layers[i], x_feat, x_target_feat, sub_graph)
             if i != self.num_layer - 1:
                 x_feat = F.relu(x_feat)
                 x_feat = F.dropout(x_feat, self.dropout, training=self.training)

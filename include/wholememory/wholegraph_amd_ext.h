@@ -585,6 +585,82 @@ enum wholememory_error_code_t wholememory_ext_csc_gather_aggregate_forward(whole
  * it tells the fused route from the gather + (2b) composition. */
 int64_t wholememory_ext_gather_aggregate_calls(void);
 
+/* ---- (2f) (2c) with edge features in the attention logit (GAT `mha_gat_n2n(..., edge_feat=...)`) ------------------- */
+/* The block, h, H, F and every rule of (2c): row_ptr int32 [n_dst + 1], col_ind int32 [n_edges] in [0, n_src), h fp32
+ * [n_src, h_stride] with H * F columns used, head k owning the columns [k*F, (k+1)*F). Every `*` and `+` below is one fp32
+ * operation, rounded on its own (no fused multiply-add). A sum "left to right" starts from its first term; a sum with no
+ * term is +0.0. New inputs:
+ *   att fp32 [3 * H * F], viewed as (3, H, F): half 0 is the source side, half 1 the target side, half 2 the edge side.
+ *   edge_feat fp32 [n_edges, ef_stride] with H * F columns used, ef_stride >= H*F (the layer's lin_edge(edge_attr)); row e
+ *   belongs to edge POSITION e of col_ind.
+ *
+ * forward: writes scores, alpha and out as (2c), and edge_scores [n_edges, H], which the backward reads back too.
+ *   s_src and s_dst as (2c). s_edge[e,k] = sum over f of att[2,k,f] * edge_feat[e,k,f], left to right; edge_scores = s_edge.
+ *   z = (s_src[col_ind[e],k] + s_dst[d,k]) + s_edge[e,k], in that association.
+ *   l, m, w, den, alpha, o and out (concat or the mean over heads) are exactly as (2c) from this z. The edge features enter
+ *   the logit only: o sums alpha[e,k] * h[col_ind[e],k,:], as cugraph-ops does.
+ * backward: grad_out as (2c) -> grad_h [n_src, grad_h_stride >= H*F], grad_att [3*H*F] and grad_edge_feat
+ * [n_edges, grad_ef_stride >= H*F] (every used column written).
+ *   da, c, dl, dz (z recomputed from scores and edge_scores, associated as above) and ds_dst as (2c); P(j) and ds_src[j]
+ *   with the same chunking and the same C; grad_h as (2c); grad_att[0] and grad_att[1] as (2c), in node chunks of N.
+ *   grad_edge_feat[e,k,f] = dz[e,k] * att[2,k,f].
+ *   grad_att[2,k,f] = sum over e of dz[e,k] * edge_feat[e,k,f] in ascending edge position, cut into chunks of
+ *   N = wholememory_ext_csc_gat_node_chunk() edges from edge 0: each chunk summed left to right, the chunk sums added in
+ *   chunk order.
+ *   No atomics; results are bitwise reproducible.
+ * With edge_feat all +0.0 (and no z of (2c) equal to +-0.0), scores, alpha, out, grad_h, grad_att[0] and grad_att[1] are
+ * those of (2c) over att[0:2], bit for bit.
+ * n_edges = 0 and n_dst = 0 are valid. INVALID_INPUT, before any device work, for everything (2c) rejects, for a null
+ * edge_feat, edge_scores or grad_edge_feat with n_edges > 0 and n_dst > 0, and for an ef_stride or grad_ef_stride smaller
+ * than H*F. NOT_SUPPORTED (nothing queued) when the device backend has no such kernels. */
+enum wholememory_error_code_t wholememory_ext_csc_gat_edge_forward(const int32_t* row_ptr,
+                                                                   const int32_t* col_ind,
+                                                                   int64_t n_edges,
+                                                                   int64_t n_dst,
+                                                                   int64_t n_src,
+                                                                   const float* h,
+                                                                   int64_t h_stride,
+                                                                   const float* att,
+                                                                   const float* edge_feat,
+                                                                   int64_t ef_stride,
+                                                                   int64_t heads,
+                                                                   int64_t dim,
+                                                                   float negative_slope,
+                                                                   int concat,
+                                                                   float* out,
+                                                                   int64_t out_stride,
+                                                                   float* alpha,
+                                                                   float* scores,
+                                                                   float* edge_scores,
+                                                                   struct wholememory_env_func_t* p_env_fns,
+                                                                   void* stream);
+enum wholememory_error_code_t wholememory_ext_csc_gat_edge_backward(const int32_t* row_ptr,
+                                                                    const int32_t* col_ind,
+                                                                    int64_t n_edges,
+                                                                    int64_t n_dst,
+                                                                    int64_t n_src,
+                                                                    const float* h,
+                                                                    int64_t h_stride,
+                                                                    const float* att,
+                                                                    const float* edge_feat,
+                                                                    int64_t ef_stride,
+                                                                    int64_t heads,
+                                                                    int64_t dim,
+                                                                    float negative_slope,
+                                                                    int concat,
+                                                                    const float* alpha,
+                                                                    const float* scores,
+                                                                    const float* edge_scores,
+                                                                    const float* grad_out,
+                                                                    int64_t grad_out_stride,
+                                                                    float* grad_h,
+                                                                    int64_t grad_h_stride,
+                                                                    float* grad_att,
+                                                                    float* grad_edge_feat,
+                                                                    int64_t grad_ef_stride,
+                                                                    struct wholememory_env_func_t* p_env_fns,
+                                                                    void* stream);
+
 /* ---- (3) testing seam ---------------------------------------------------------------------- */
 /* Replaces the device backend. Refuses (WHOLEMEMORY_NOT_SUPPORTED) unless the environment has
  * WHOLEGRAPH_AMD_TESTING=1. `backend` is a const wm_device_backend* (wholegraph_amd/csrc/backend.hpp);

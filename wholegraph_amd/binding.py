@@ -300,6 +300,11 @@ PROTOTYPES = {
     "wholememory_ext_csc_gat_backward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _i64, C.c_float, _i, _vp,
                                              _vp, _vp, _i64, _vp, _i64, _vp, _P(EnvFunc), _vp]),
     "wholememory_ext_csc_gat_node_chunk": (_i64, []),
+    "wholememory_ext_csc_gat_edge_forward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64,
+                                                 C.c_float, _i, _vp, _i64, _vp, _vp, _vp, _P(EnvFunc), _vp]),
+    "wholememory_ext_csc_gat_edge_backward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i64,
+                                                  C.c_float, _i, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64,
+                                                  _P(EnvFunc), _vp]),
     "wm_testing_install_backend": (_i, [_vp]),
 }
 

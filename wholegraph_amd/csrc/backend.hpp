@@ -279,6 +279,17 @@ struct wm_gather_agg_args {
   int64_t out_stride;
 };
 
+// wm_gat_args with an edge term in the logit (kernels/gat_edge.hip, wholegraph_amd_ext.h section 2f): g.att is
+// [3, heads, dim] (half 2 the edge side) and g.grad_att [3 * heads * dim]
+struct wm_gat_edge_args {
+  wm_gat_args g;
+  const float* edge_feat;   // [n_edges, ef_stride], heads * dim columns used; row e belongs to edge position e
+  int64_t ef_stride;
+  float* edge_scores;       // [n_edges, heads]: written by the forward, read by the backward
+  float* grad_edge_feat;    // backward: [n_edges, grad_ef_stride]
+  int64_t grad_ef_stride;
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -499,6 +510,15 @@ struct wm_device_backend {
   // ---- agg_forward over rows read from a WholeMemory table by global id (kernels/agg_gather.hip); nullptr in a backend
   // without it ----
   int (*gather_agg_forward)(const wm_gather_agg_args* a, void* stream);
+  // ---- gat_forward / gat_backward with an edge term in the logit (kernels/gat_edge.hip, wholegraph_amd_ext.h section 2f);
+  // nullptr in a backend without them ----
+  // forward: also a->edge_scores; the workspace of gat_forward_workspace_bytes(&a->g)
+  int (*gat_edge_forward)(const wm_gat_edge_args* a, void* workspace, void* stream);
+  // backward: also grad_edge_feat and half 2 of grad_att; the index of gat_backward, workspace of
+  // gat_edge_backward_workspace_bytes
+  size_t (*gat_edge_backward_workspace_bytes)(const wm_gat_edge_args* a);
+  int (*gat_edge_backward)(const wm_gat_edge_args* a, const int32_t* order, const int32_t* run_starts,
+                           const int32_t* unique_ids, const int64_t* n_unique_dev, void* workspace, void* stream);
 };
 
 }  // extern "C"

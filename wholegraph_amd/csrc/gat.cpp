@@ -1,6 +1,7 @@
-// wholegraph_amd — host side of the multi-head graph attention of a sampled CSC block (wholegraph_amd_ext.h, section 2c):
-// validation, scratch, the edge index of the backward (the library's id sort over col_ind) and the launches of
-// kernels/gat.hip. The semantics, and the one order of every fp32 sum, are stated in the header.
+// wholegraph_amd — host side of the multi-head graph attention of a sampled CSC block (wholegraph_amd_ext.h, section 2c,
+// and section 2f: the same op with an edge term in the logit): validation, scratch, the edge index of the backward (the
+// library's id sort over col_ind) and the launches of kernels/gat.hip / kernels/gat_edge.hip. The semantics, and the one
+// order of every fp32 sum, are stated in the header.
 #include <wholememory/wholegraph_amd_ext.h>
 
 #include "ops_internal.hpp"
@@ -57,6 +58,33 @@ wm_gat_args make_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_
   return a;
 }
 
+// the edge index of a backward: a stable sort of col_ind (runs of one source, edge positions ascending in each run).
+// dedup_ids joins any side stream of its own before it returns (no deferred join asked for), so its outputs are ready for
+// the kernels queued behind it on `stream`
+struct edge_index {
+  temp_mem unique_mem, starts_mem, order_mem, nu_mem, sort_ws;
+  int32_t *unique = nullptr, *starts = nullptr, *order = nullptr;
+  int64_t* nu     = nullptr;
+  explicit edge_index(wholememory_env_func_t* fns)
+    : unique_mem(fns), starts_mem(fns), order_mem(fns), nu_mem(fns), sort_ws(fns)
+  {
+  }
+  void build(const wm_device_backend* bk, const int32_t* col_ind, int64_t E, int64_t n_src, void* stream)
+  {
+    if (n_src <= 0) return;
+    unique      = static_cast<int32_t*>(unique_mem.device(E, WHOLEMEMORY_DT_INT));
+    starts      = static_cast<int32_t*>(starts_mem.device(E + 1, WHOLEMEMORY_DT_INT));
+    order       = static_cast<int32_t*>(order_mem.device(E, WHOLEMEMORY_DT_INT));
+    nu          = static_cast<int64_t*>(nu_mem.device(1, WHOLEMEMORY_DT_INT64));
+    void* d_sws = sort_ws.device(static_cast<int64_t>(bk->dedup_workspace_bytes(E, WHOLEMEMORY_DT_INT)), WHOLEMEMORY_DT_INT8);
+    if (bk->device_error != nullptr && bk->device_error() != 0)
+      throw hip_error("an earlier id sort reported a device-side timeout (see the ERROR line above)");
+    const int rc = bk->dedup_ids(col_ind, WHOLEMEMORY_DT_INT, E, n_src, 0, unique, starts, order, nu, d_sws, stream);
+    if (rc == -1) throw logic_error("dedup_ids: unsupported index dtype or more than 2^31 edges");
+    if (rc != 0) throw hip_error("dedup_ids failed");
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -111,28 +139,88 @@ wholememory_error_code_t wholememory_ext_csc_gat_backward(const int32_t* row_ptr
   a.grad_h        = grad_h;
   a.grad_h_stride = grad_h_stride;
   a.grad_att      = grad_att;
-  const int64_t E = a.n_edges;
-  // the edge index: a stable sort of col_ind (runs of one source, edge positions ascending in each run). dedup_ids joins
-  // any side stream of its own before it returns (no deferred join asked for), so its outputs are ready for the kernels
-  // queued behind it on `stream`
-  temp_mem unique_mem(p_env_fns), starts_mem(p_env_fns), order_mem(p_env_fns), nu_mem(p_env_fns), sort_ws(p_env_fns),
-    gat_ws(p_env_fns);
-  int32_t *d_unique = nullptr, *d_starts = nullptr, *d_order = nullptr;
-  int64_t* d_nu     = nullptr;
-  if (n_src > 0) {
-    d_unique    = static_cast<int32_t*>(unique_mem.device(E, WHOLEMEMORY_DT_INT));
-    d_starts    = static_cast<int32_t*>(starts_mem.device(E + 1, WHOLEMEMORY_DT_INT));
-    d_order     = static_cast<int32_t*>(order_mem.device(E, WHOLEMEMORY_DT_INT));
-    d_nu        = static_cast<int64_t*>(nu_mem.device(1, WHOLEMEMORY_DT_INT64));
-    void* d_sws = sort_ws.device(static_cast<int64_t>(bk->dedup_workspace_bytes(E, WHOLEMEMORY_DT_INT)), WHOLEMEMORY_DT_INT8);
-    if (bk->device_error != nullptr && bk->device_error() != 0)
-      throw hip_error("an earlier id sort reported a device-side timeout (see the ERROR line above)");
-    const int rc = bk->dedup_ids(col_ind, WHOLEMEMORY_DT_INT, E, n_src, 0, d_unique, d_starts, d_order, d_nu, d_sws, stream);
-    if (rc == -1) throw logic_error("dedup_ids: unsupported index dtype or more than 2^31 edges");
-    if (rc != 0) throw hip_error("dedup_ids failed");
-  }
+  edge_index ix(p_env_fns);
+  temp_mem gat_ws(p_env_fns);
+  ix.build(bk, col_ind, a.n_edges, n_src, stream);
   void* d_gws = gat_ws.device(static_cast<int64_t>(bk->gat_backward_workspace_bytes(&a)), WHOLEMEMORY_DT_INT8);
-  WM_BK(bk->gat_backward(&a, d_order, d_starts, d_unique, d_nu, d_gws, stream));
+  WM_BK(bk->gat_backward(&a, ix.order, ix.starts, ix.unique, ix.nu, d_gws, stream));
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+wholememory_error_code_t wholememory_ext_csc_gat_edge_forward(
+  const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src, const float* h,
+  int64_t h_stride, const float* att, const float* edge_feat, int64_t ef_stride, int64_t heads, int64_t dim,
+  float negative_slope, int concat, float* out, int64_t out_stride, float* alpha, float* scores, float* edge_scores,
+  wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  const auto* bk = backend();
+  if (bk->gat_edge_forward == nullptr || bk->gat_forward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, h, h_stride, att, heads, dim, alpha, scores);
+  if (n_edges > 0 && n_dst > 0 && edge_feat == nullptr) throw invalid_input("edge_feat is null");
+  if (n_edges > 0 && n_dst > 0 && edge_scores == nullptr) throw invalid_input("edge_scores is null");
+  if (ef_stride < heads * dim) throw invalid_input("edge_feat stride smaller than its row");
+  if (n_dst > 0 && out == nullptr) throw invalid_input("out is null");
+  if (out_stride < (concat ? heads * dim : dim)) throw invalid_input("out stride smaller than its row");
+  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
+  wm_gat_edge_args a{};
+  a.g = make_args(row_ptr, col_ind, n_edges, n_dst, n_src, h, h_stride, att, heads, dim, negative_slope, concat, alpha,
+                  scores);
+  a.g.out        = out;
+  a.g.out_stride = out_stride;
+  a.edge_feat    = edge_feat;
+  a.ef_stride    = ef_stride;
+  a.edge_scores  = edge_scores;
+  temp_mem ws(p_env_fns);
+  const size_t wb = bk->gat_forward_workspace_bytes(&a.g);
+  void* d_ws      = wb > 0 ? ws.device(static_cast<int64_t>(wb), WHOLEMEMORY_DT_INT8) : nullptr;
+  WM_BK(bk->gat_edge_forward(&a, d_ws, stream));
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+wholememory_error_code_t wholememory_ext_csc_gat_edge_backward(
+  const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src, const float* h,
+  int64_t h_stride, const float* att, const float* edge_feat, int64_t ef_stride, int64_t heads, int64_t dim,
+  float negative_slope, int concat, const float* alpha, const float* scores, const float* edge_scores,
+  const float* grad_out, int64_t grad_out_stride, float* grad_h, int64_t grad_h_stride, float* grad_att,
+  float* grad_edge_feat, int64_t grad_ef_stride, wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  const auto* bk = backend();
+  if (bk->gat_edge_backward == nullptr || bk->gat_edge_backward_workspace_bytes == nullptr)
+    return WHOLEMEMORY_NOT_SUPPORTED;
+  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, h, h_stride, att, heads, dim, alpha, scores);
+  if (n_edges > 0 && n_dst > 0 && edge_feat == nullptr) throw invalid_input("edge_feat is null");
+  if (n_edges > 0 && n_dst > 0 && edge_scores == nullptr) throw invalid_input("edge_scores is null");
+  if (n_edges > 0 && n_dst > 0 && grad_edge_feat == nullptr) throw invalid_input("grad_edge_feat is null");
+  if (ef_stride < heads * dim) throw invalid_input("edge_feat stride smaller than its row");
+  if (grad_ef_stride < heads * dim) throw invalid_input("grad_edge_feat stride smaller than its row");
+  if (n_dst > 0 && grad_out == nullptr) throw invalid_input("grad_out is null");
+  if (grad_out_stride < (concat ? heads * dim : dim)) throw invalid_input("grad_out stride smaller than its row");
+  if (n_src > 0 && grad_h == nullptr) throw invalid_input("grad_h is null");
+  if (grad_h_stride < heads * dim) throw invalid_input("grad_h stride smaller than its row");
+  if (grad_att == nullptr) throw invalid_input("grad_att is null");
+  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
+  wm_gat_edge_args a{};
+  a.g = make_args(row_ptr, col_ind, n_edges, n_dst, n_src, h, h_stride, att, heads, dim, negative_slope, concat, alpha,
+                  scores);
+  a.g.grad          = grad_out;
+  a.g.grad_stride   = grad_out_stride;
+  a.g.grad_h        = grad_h;
+  a.g.grad_h_stride = grad_h_stride;
+  a.g.grad_att      = grad_att;
+  a.edge_feat       = edge_feat;
+  a.ef_stride       = ef_stride;
+  a.edge_scores     = const_cast<float*>(edge_scores);   // (written by the forward only)
+  a.grad_edge_feat  = grad_edge_feat;
+  a.grad_ef_stride  = grad_ef_stride;
+  edge_index ix(p_env_fns);
+  temp_mem gat_ws(p_env_fns);
+  ix.build(bk, col_ind, a.g.n_edges, n_src, stream);
+  void* d_gws = gat_ws.device(static_cast<int64_t>(bk->gat_edge_backward_workspace_bytes(&a)), WHOLEMEMORY_DT_INT8);
+  WM_BK(bk->gat_edge_backward(&a, ix.order, ix.starts, ix.unique, ix.nu, d_gws, stream));
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }

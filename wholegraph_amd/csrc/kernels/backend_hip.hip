@@ -87,6 +87,10 @@ int hip_gat_forward(const wm_gat_args* a, void* workspace, void* stream);
 size_t hip_gat_backward_workspace_bytes(const wm_gat_args* a);
 int hip_gat_backward(const wm_gat_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
                      const int64_t* n_unique_dev, void* workspace, void* stream);
+int hip_gat_edge_forward(const wm_gat_edge_args* a, void* workspace, void* stream);
+size_t hip_gat_edge_backward_workspace_bytes(const wm_gat_edge_args* a);
+int hip_gat_edge_backward(const wm_gat_edge_args* a, const int32_t* order, const int32_t* run_starts,
+                          const int32_t* unique_ids, const int64_t* n_unique_dev, void* workspace, void* stream);
 
 namespace {
 
@@ -267,6 +271,9 @@ const wm_device_backend kHipBackend = {
   hip_aggw_backward,
   hip_edge_attr_gather,
   hip_gather_agg_forward,
+  hip_gat_edge_forward,
+  hip_gat_edge_backward_workspace_bytes,
+  hip_gat_edge_backward,
 };
 
 }  // namespace

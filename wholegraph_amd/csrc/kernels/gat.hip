@@ -27,28 +27,10 @@
 #include <stdint.h>
 
 #include "../backend.hpp"
-#include "agg_common.cuh"
+#include "gat_common.cuh"
 
 namespace wm {
 namespace {
-
-// backward scratch: the id sort's outputs and this op's workspace (hip_gat_backward carves it)
-struct wm_gat_bwd_state {
-  const int32_t* order;        // [n_edges] edge positions, sorted by source (stable)
-  const int32_t* run_starts;   // [n_unique + 1]
-  const int32_t* unique_ids;   // [n_unique] sources with edges, ascending
-  const int64_t* n_unique;     // device scalar written by the sort
-  int32_t* sorted_dst;         // [n_edges]
-  int32_t* run_of;             // [n_src]
-  float* dz;                   // [n_edges, heads]: da, then dz
-  float* ds_dst;               // [n_dst, heads]
-  float* ds_src;               // [n_src, heads]
-  float* partial;              // [n_tiles, partial_stride]: P of a chunk (ds_off columns), then its ds_src (heads)
-  float* att_partial;          // [n_node_chunks, 2 * heads * dim]
-  int64_t n_tiles, partial_stride, ds_off, n_node_chunks;
-};
-
-__device__ __forceinline__ float leaky(float z, float slope) { return z > 0.0f ? z : slope * z; }
 
 // -0.0 is the identity of IEEE addition: acc = -0.0 followed by acc + t_0 + t_1 + ... is the left-to-right sum that starts
 // from the first term (also when that term is -0.0)
@@ -351,8 +333,6 @@ __global__ __launch_bounds__(kAggBlock) void gat_att_fold_kernel(wm_gat_args p, 
 }
 
 int64_t up4(int64_t v) { return (v + 3) / 4 * 4; }
-uintptr_t up256(uintptr_t v) { return (v + 255) & ~static_cast<uintptr_t>(255); }
-bool aligned16(const void* ptr) { return reinterpret_cast<uintptr_t>(ptr) % 16 == 0; }
 
 }  // namespace
 
@@ -361,18 +341,31 @@ size_t hip_gat_forward_workspace_bytes(const wm_gat_args* a)
   return a->concat ? 0 : static_cast<size_t>(a->n_dst * a->heads * a->dim) * 4 + 256;
 }
 
+int gat_scores(const wm_gat_args* a, void* stream_v)
+{
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  const int64_t H = a->heads, F = a->dim, HF = H * F;
+  const int64_t ns = (a->n_src + a->n_dst) * H;
+  if (ns == 0) return 0;
+  const bool v4 = F % 4 == 0 && aligned16(a->att) && use_vec4(HF, a->h, a->h_stride, a->h, a->h_stride);
+  if (v4) hipLaunchKernelGGL(gat_score_kernel<4>, dim3(blocks_for(ns, kAggBlock)), dim3(kAggBlock), 0, stream, *a);
+  else hipLaunchKernelGGL(gat_score_kernel<1>, dim3(blocks_for(ns, kAggBlock)), dim3(kAggBlock), 0, stream, *a);
+  return rc_last();
+}
+
+int gat_head_mean(const wm_gat_args* a, const float* o, int64_t o_stride, void* stream_v)
+{
+  hipLaunchKernelGGL(gat_head_mean_kernel, dim3(blocks_for(a->n_dst * a->dim, kAggBlock)), dim3(kAggBlock), 0,
+                     static_cast<hipStream_t>(stream_v), *a, o, o_stride);
+  return rc_last();
+}
+
 int hip_gat_forward(const wm_gat_args* a, void* workspace, void* stream_v)
 {
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   const int64_t H = a->heads, F = a->dim, HF = H * F;
   const bool f4   = F % 4 == 0 && aligned16(a->att);
-  const int64_t ns = (a->n_src + a->n_dst) * H;
-  if (ns > 0) {
-    const bool v4 = f4 && use_vec4(HF, a->h, a->h_stride, a->h, a->h_stride);
-    if (v4) hipLaunchKernelGGL(gat_score_kernel<4>, dim3(blocks_for(ns, kAggBlock)), dim3(kAggBlock), 0, stream, *a);
-    else hipLaunchKernelGGL(gat_score_kernel<1>, dim3(blocks_for(ns, kAggBlock)), dim3(kAggBlock), 0, stream, *a);
-    if (rc_last() != 0) return -2;
-  }
+  if (gat_scores(a, stream_v) != 0) return -2;
   if (a->n_dst == 0) return 0;
   float* o         = a->concat ? a->out : reinterpret_cast<float*>(up256(reinterpret_cast<uintptr_t>(workspace)));
   const int64_t os = a->concat ? a->out_stride : HF;
@@ -383,11 +376,7 @@ int hip_gat_forward(const wm_gat_args* a, void* workspace, void* stream_v)
   WM_AGG_DISPATCH(v4, v4 ? HF / 4 : HF, WM_GAT_FWD);
 #undef WM_GAT_FWD
   if (rc_last() != 0) return -2;
-  if (!a->concat) {
-    hipLaunchKernelGGL(gat_head_mean_kernel, dim3(blocks_for(a->n_dst * F, kAggBlock)), dim3(kAggBlock), 0, stream, *a,
-                       static_cast<const float*>(o), os);
-    if (rc_last() != 0) return -2;
-  }
+  if (!a->concat && gat_head_mean(a, o, os, stream_v) != 0) return -2;
   return 0;
 }
 
@@ -419,45 +408,41 @@ gat_bwd_layout bwd_layout(const wm_gat_args* a)
 
 size_t hip_gat_backward_workspace_bytes(const wm_gat_args* a) { return bwd_layout(a).bytes; }
 
-int hip_gat_backward(const wm_gat_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                     const int64_t* n_unique_dev, void* workspace, void* stream_v)
+size_t gat_bwd_carve(const wm_gat_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                     const int64_t* n_unique_dev, void* workspace, wm_gat_bwd_state* b)
 {
-  hipStream_t stream = static_cast<hipStream_t>(stream_v);
-  const int64_t H = a->heads, F = a->dim, HF = H * F;
   const gat_bwd_layout l = bwd_layout(a);
   const uintptr_t w0     = up256(reinterpret_cast<uintptr_t>(workspace));
-  wm_gat_bwd_state b;
-  b.order          = order;
-  b.run_starts     = run_starts;
-  b.unique_ids     = unique_ids;
-  b.n_unique       = n_unique_dev;
-  b.sorted_dst     = reinterpret_cast<int32_t*>(w0 + l.off[0]);
-  b.run_of         = reinterpret_cast<int32_t*>(w0 + l.off[1]);
-  b.dz             = reinterpret_cast<float*>(w0 + l.off[2]);
-  b.ds_dst         = reinterpret_cast<float*>(w0 + l.off[3]);
-  b.ds_src         = reinterpret_cast<float*>(w0 + l.off[4]);
-  b.partial        = reinterpret_cast<float*>(w0 + l.off[5]);
-  b.att_partial    = reinterpret_cast<float*>(w0 + l.off[6]);
-  b.n_tiles        = l.n_tiles;
-  b.partial_stride = l.partial_stride;
-  b.ds_off         = l.ds_off;
-  b.n_node_chunks  = l.n_node_chunks;
+  b->order          = order;
+  b->run_starts     = run_starts;
+  b->unique_ids     = unique_ids;
+  b->n_unique       = n_unique_dev;
+  b->sorted_dst     = reinterpret_cast<int32_t*>(w0 + l.off[0]);
+  b->run_of         = reinterpret_cast<int32_t*>(w0 + l.off[1]);
+  b->dz             = reinterpret_cast<float*>(w0 + l.off[2]);
+  b->ds_dst         = reinterpret_cast<float*>(w0 + l.off[3]);
+  b->ds_src         = reinterpret_cast<float*>(w0 + l.off[4]);
+  b->partial        = reinterpret_cast<float*>(w0 + l.off[5]);
+  b->att_partial    = reinterpret_cast<float*>(w0 + l.off[6]);
+  b->n_tiles        = l.n_tiles;
+  b->partial_stride = l.partial_stride;
+  b->ds_off         = l.ds_off;
+  b->n_node_chunks  = l.n_node_chunks;
+  return l.bytes - 256;
+}
 
-  // 16-byte pieces: whole heads of F % 4 == 0 columns, every row start and att 16-byte aligned
-  const int64_t gcols = a->concat ? HF : F;
-  const bool f4       = F % 4 == 0 && aligned16(a->att) && use_vec4(gcols, a->grad, a->grad_stride, a->h, a->h_stride);
-  if (a->n_dst > 0) {
-    if (f4) hipLaunchKernelGGL(gat_bwd_edge_kernel<4>, dim3(blocks_for(a->n_dst * H, kAggBlock)), dim3(kAggBlock), 0, stream, *a, b);
-    else hipLaunchKernelGGL(gat_bwd_edge_kernel<1>, dim3(blocks_for(a->n_dst * H, kAggBlock)), dim3(kAggBlock), 0, stream, *a, b);
-    if (rc_last() != 0) return -2;
-  }
+int gat_bwd_after_dz(const wm_gat_args* a, const wm_gat_bwd_state* bp, void* stream_v)
+{
+  hipStream_t stream        = static_cast<hipStream_t>(stream_v);
+  const wm_gat_bwd_state& b = *bp;
+  const int64_t HF          = a->heads * a->dim;
   if (a->n_src > 0) {
     if (a->n_edges > 0) {
       const int blocks = blocks_for(a->n_edges, kAggBlock);
       hipLaunchKernelGGL(gat_bwd_prep_kernel, dim3(blocks < 8192 ? blocks : 8192), dim3(kAggBlock), 0, stream, *a, b);
       if (rc_last() != 0) return -2;
     }
-    const bool v4 = f4 && use_vec4(HF, a->grad_h, a->grad_h_stride, a->grad_h, a->grad_h_stride);
+    const bool v4 = gat_bwd_vec4(a) && use_vec4(HF, a->grad_h, a->grad_h_stride, a->grad_h, a->grad_h_stride);
     if (b.n_tiles > 1) {   // (one tile holds no chunk k >= 1)
 #define WM_GAT_CHUNK(V, L)                                                                                                   \
   hipLaunchKernelGGL((gat_bwd_chunk_kernel<V, L>), dim3(blocks_for(b.n_tiles, kAggBlock / (L))), dim3(kAggBlock), 0, stream, \
@@ -478,6 +463,21 @@ int hip_gat_backward(const wm_gat_args* a, const int32_t* order, const int32_t* 
   }
   hipLaunchKernelGGL(gat_att_fold_kernel, dim3(blocks_for(2 * HF, kAggBlock)), dim3(kAggBlock), 0, stream, *a, b);
   return rc_last();
+}
+
+int hip_gat_backward(const wm_gat_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                     const int64_t* n_unique_dev, void* workspace, void* stream_v)
+{
+  hipStream_t stream = static_cast<hipStream_t>(stream_v);
+  wm_gat_bwd_state b;
+  gat_bwd_carve(a, order, run_starts, unique_ids, n_unique_dev, workspace, &b);
+  if (a->n_dst > 0) {
+    const int blocks = blocks_for(a->n_dst * a->heads, kAggBlock);
+    if (gat_bwd_vec4(a)) hipLaunchKernelGGL(gat_bwd_edge_kernel<4>, dim3(blocks), dim3(kAggBlock), 0, stream, *a, b);
+    else hipLaunchKernelGGL(gat_bwd_edge_kernel<1>, dim3(blocks), dim3(kAggBlock), 0, stream, *a, b);
+    if (rc_last() != 0) return -2;
+  }
+  return gat_bwd_after_dz(a, &b, stream_v);
 }
 
 }  // namespace wm

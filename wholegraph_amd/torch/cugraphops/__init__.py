@@ -1,6 +1,7 @@
 """Layers of the ``cugraph`` framework route (``gnn_model.set_framework("cugraph")``), on the HIP aggregation ops."""
+from .edge_gat_conv import EdgeGATConv
 from .gat_conv import CuGraphGATConv
 from .sage_conv import CuGraphSAGEConv
 from .weighted_sage_conv import EdgeWeightedSAGEConv
 
-__all__ = ["CuGraphSAGEConv", "CuGraphGATConv", "EdgeWeightedSAGEConv"]
+__all__ = ["CuGraphSAGEConv", "CuGraphGATConv", "EdgeGATConv", "EdgeWeightedSAGEConv"]

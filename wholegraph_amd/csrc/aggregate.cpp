@@ -8,102 +8,37 @@
 #include <wholememory/wholegraph_amd_ext.h>
 #include <wholememory/wholememory_tensor.h>
 
-#include "ops_internal.hpp"
+#include "csc_block.hpp"
 
 namespace {
 
 using namespace wm;
-
-#define WM_BK(call)                                                                      \
-  do {                                                                                   \
-    int rc__ = (call);                                                                   \
-    if (rc__ != 0) throw wm::hip_error(wm::format_string("%s failed: %d", #call, rc__)); \
-  } while (0)
 
 void check_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src,
                 const void* in, int64_t in_stride, int64_t in_cols, int64_t dim, int aggr, const void* out,
                 int64_t out_stride, int64_t out_cols, int64_t in_rows, int64_t out_rows)
 {
   auto bad = [](const char* what) { throw invalid_input(what); };
-  if (n_edges < 0 || n_dst < 0 || n_src < 0) bad("negative size");
+  check_block(row_ptr, col_ind, n_edges, n_dst, n_src, n_edges > 0, "x");
   if (dim < 1) bad("dim must be >= 1");
-  if (n_dst > n_src) bad("n_dst > n_src: the targets are the first rows of x");
   if (aggr != WHOLEMEMORY_EXT_AGGR_SUM && aggr != WHOLEMEMORY_EXT_AGGR_MEAN) bad("aggr must be SUM or MEAN");
-  if (row_ptr == nullptr) bad("row_ptr is null");
-  if (n_edges > 0 && col_ind == nullptr) bad("col_ind is null");
   if (in_rows > 0 && in == nullptr) bad("input rows are null");
   if (out_rows > 0 && out == nullptr) bad("output rows are null");
   if (in_stride < in_cols) bad("input stride smaller than its row");
   if (out_stride < out_cols) bad("output stride smaller than its row");
-  if (n_edges >= (int64_t(1) << 31) || n_src >= (int64_t(1) << 31)) bad("more than 2^31 - 1 edges or rows");
 }
 
-wm_agg_args make_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src,
-                      int64_t dim, int aggr)
-{
-  wm_agg_args a{};
-  a.row_ptr = row_ptr;
-  a.col_ind = col_ind;
-  a.n_edges = n_dst == 0 ? 0 : n_edges;   // (no target, no edge of any target)
-  a.n_dst   = n_dst;
-  a.n_src   = n_src;
-  a.dim     = dim;
-  a.mean    = aggr == WHOLEMEMORY_EXT_AGGR_MEAN ? 1 : 0;
-  return a;
-}
-
-// the edge index of a backward: a stable sort of col_ind (runs of one source, edge positions ascending in each run), then
-// launch(order, run_starts, unique_ids, n_unique_dev, workspace) with the workspace of agg_backward_workspace_bytes.
-// dedup_ids joins any side stream of its own before it returns (no deferred join asked for), so its outputs are ready for
-// the kernels queued behind it on `stream`
+// the edge index of a backward (sort_col_ind), then launch(order, run_starts, unique_ids, n_unique_dev, workspace) with the
+// workspace of agg_backward_workspace_bytes
 template <class Launch>
 void backward_over_index(const wm_device_backend* bk, const int32_t* col_ind, int64_t E, int64_t n_src, int64_t dim,
                          wholememory_env_func_t* p_env_fns, void* stream, Launch launch)
 {
-  temp_mem unique_mem(p_env_fns), starts_mem(p_env_fns), order_mem(p_env_fns), nu_mem(p_env_fns), sort_ws(p_env_fns),
-    agg_ws(p_env_fns);
-  auto* d_unique = static_cast<int32_t*>(unique_mem.device(E, WHOLEMEMORY_DT_INT));
-  auto* d_starts = static_cast<int32_t*>(starts_mem.device(E + 1, WHOLEMEMORY_DT_INT));
-  auto* d_order  = static_cast<int32_t*>(order_mem.device(E, WHOLEMEMORY_DT_INT));
-  auto* d_nu     = static_cast<int64_t*>(nu_mem.device(1, WHOLEMEMORY_DT_INT64));
-  void* d_sws    = sort_ws.device(static_cast<int64_t>(bk->dedup_workspace_bytes(E, WHOLEMEMORY_DT_INT)), WHOLEMEMORY_DT_INT8);
-  if (bk->device_error != nullptr && bk->device_error() != 0)
-    throw hip_error("an earlier id sort reported a device-side timeout (see the ERROR line above)");
-  const int rc = bk->dedup_ids(col_ind, WHOLEMEMORY_DT_INT, E, n_src, 0, d_unique, d_starts, d_order, d_nu, d_sws, stream);
-  if (rc == -1) throw logic_error("dedup_ids: unsupported index dtype or more than 2^31 edges");
-  if (rc != 0) throw hip_error("dedup_ids failed");
+  sorted_ids ix(p_env_fns);
+  temp_mem agg_ws(p_env_fns);
+  sort_col_ind(&ix, col_ind, E, n_src, stream);
   void* d_aws = agg_ws.device(static_cast<int64_t>(bk->agg_backward_workspace_bytes(E, n_src, dim)), WHOLEMEMORY_DT_INT8);
-  launch(d_order, d_starts, d_unique, d_nu, d_aws);
-}
-
-wm_agg16_args make_args16(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src,
-                          int64_t dim, int aggr, wholememory_dtype_t dtype)
-{
-  wm_agg16_args a{};
-  a.row_ptr = row_ptr;
-  a.col_ind = col_ind;
-  a.n_edges = n_dst == 0 ? 0 : n_edges;
-  a.n_dst   = n_dst;
-  a.n_src   = n_src;
-  a.dim     = dim;
-  a.mean    = aggr == WHOLEMEMORY_EXT_AGGR_MEAN ? 1 : 0;
-  a.dtype   = dtype;
-  return a;
-}
-
-wm_aggw_args make_args_w(const int32_t* row_ptr, const int32_t* col_ind, const float* w, int64_t n_edges, int64_t n_dst,
-                         int64_t n_src, int64_t dim, int aggr)
-{
-  wm_aggw_args a{};
-  a.row_ptr = row_ptr;
-  a.col_ind = col_ind;
-  a.w       = w;
-  a.n_edges = n_dst == 0 ? 0 : n_edges;
-  a.n_dst   = n_dst;
-  a.n_src   = n_src;
-  a.dim     = dim;
-  a.mean    = aggr == WHOLEMEMORY_EXT_AGGR_MEAN ? 1 : 0;
-  return a;
+  launch(ix.order, ix.starts, static_cast<const int32_t*>(ix.unique), ix.n_unique_dev, d_aws);
 }
 
 bool rows16(wholememory_dtype_t dtype) { return dtype == WHOLEMEMORY_DT_HALF || dtype == WHOLEMEMORY_DT_BF16; }
@@ -124,7 +59,7 @@ wholememory_error_code_t wholememory_ext_csc_aggregate_forward(const int32_t* ro
   const auto* bk = backend();
   if (bk->agg_forward == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
   check_args(row_ptr, col_ind, n_edges, n_dst, n_src, x, x_stride, dim, dim, aggr, out, out_stride, 2 * dim, n_src, n_dst);
-  wm_agg_args a   = make_args(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
+  auto a = block_args<wm_agg_args>(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
   a.in            = x;
   a.in_stride     = x_stride;
   a.out           = out;
@@ -146,7 +81,7 @@ wholememory_error_code_t wholememory_ext_csc_aggregate_backward(const int32_t* r
   check_args(row_ptr, col_ind, n_edges, n_dst, n_src, grad_out, grad_out_stride, 2 * dim, dim, aggr, grad_x, grad_x_stride,
              dim, n_dst, n_src);
   if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
-  wm_agg_args a = make_args(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
+  auto a = block_args<wm_agg_args>(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
   a.grad        = grad_out;
   a.grad_stride = grad_out_stride;
   a.out         = grad_x;
@@ -175,7 +110,8 @@ wholememory_error_code_t wholememory_ext_csc_aggregate_forward_typed(const int32
   const auto* bk = backend();
   if (bk->agg16_forward == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
   check_args(row_ptr, col_ind, n_edges, n_dst, n_src, x, x_stride, dim, dim, aggr, out, out_stride, 2 * dim, n_src, n_dst);
-  wm_agg16_args a = make_args16(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr, dtype);
+  auto a = block_args<wm_agg16_args>(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
+  a.dtype         = dtype;
   a.in            = x;
   a.in_stride     = x_stride;
   a.out           = out;
@@ -203,7 +139,8 @@ wholememory_error_code_t wholememory_ext_csc_aggregate_backward_typed(const int3
   check_args(row_ptr, col_ind, n_edges, n_dst, n_src, grad_out, grad_out_stride, 2 * dim, dim, aggr, grad_x, grad_x_stride,
              dim, n_dst, n_src);
   if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
-  wm_agg16_args a = make_args16(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr, dtype);
+  auto a = block_args<wm_agg16_args>(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
+  a.dtype         = dtype;
   a.grad          = grad_out;
   a.grad_stride   = grad_out_stride;
   a.out           = grad_x;
@@ -229,7 +166,8 @@ wholememory_error_code_t wholememory_ext_csc_aggregate_weighted_forward(const in
   if (bk->aggw_forward == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
   check_args(row_ptr, col_ind, n_edges, n_dst, n_src, x, x_stride, dim, dim, aggr, out, out_stride, 2 * dim, n_src, n_dst);
   if (n_edges > 0 && w == nullptr) throw invalid_input("w is null");
-  wm_aggw_args a = make_args_w(row_ptr, col_ind, w, n_edges, n_dst, n_src, dim, aggr);
+  auto a = block_args<wm_aggw_args>(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
+  a.w            = w;
   a.in           = x;
   a.in_stride    = x_stride;
   a.out          = out;
@@ -257,7 +195,8 @@ wholememory_error_code_t wholememory_ext_csc_aggregate_weighted_backward(
     if (x_stride < dim) throw invalid_input("input stride smaller than its row");
   }
   if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
-  wm_aggw_args a = make_args_w(row_ptr, col_ind, w, n_edges, n_dst, n_src, dim, aggr);
+  auto a = block_args<wm_aggw_args>(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
+  a.w            = w;
   a.in           = x;
   a.in_stride    = x_stride;
   a.grad         = grad_out;
@@ -306,7 +245,7 @@ wholememory_error_code_t wholememory_ext_csc_gather_aggregate_forward(wholememor
     if (mt != WHOLEMEMORY_MT_CONTINUOUS && mt != WHOLEMEMORY_MT_CHUNKED) return WHOLEMEMORY_NOT_SUPPORTED;
     if (mapped_via_exchange(table, mt)) return WHOLEMEMORY_NOT_SUPPORTED;   // (served by a collective, not by loads)
   }
-  wm_gather_agg_args a{};
+  auto a = block_args<wm_gather_agg_args>(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
   WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(table, &a.gref));
   a.table_dtype          = td.dtype;
   a.table_rows           = td.sizes[0];
@@ -314,13 +253,6 @@ wholememory_error_code_t wholememory_ext_csc_gather_aggregate_forward(wholememor
   a.table_storage_offset = td.storage_offset;
   a.node_ids             = node_ids;
   a.node_id_dtype        = static_cast<wholememory_dtype_t>(node_id_dtype);
-  a.row_ptr              = row_ptr;
-  a.col_ind              = col_ind;
-  a.n_edges              = n_dst == 0 ? 0 : n_edges;   // (no target, no edge of any target)
-  a.n_dst                = n_dst;
-  a.n_src                = n_src;
-  a.dim                  = dim;
-  a.mean                 = aggr == WHOLEMEMORY_EXT_AGGR_MEAN ? 1 : 0;
   a.out                  = out;
   a.out_stride           = out_stride;
   WM_BK(bk->gather_agg_forward(&a, stream));

@@ -65,12 +65,6 @@ namespace wm {
 extern std::atomic<int64_t> g_grad_exchange_launches;   // row kernels queued in front of the gradient exchange (ops.cpp)
 namespace {
 
-#define WM_BK(call)                                                                                  \
-  do {                                                                                               \
-    int rc__ = (call);                                                                               \
-    if (rc__ != 0) throw ::wm::hip_error(::wm::format_string("%s failed with code %d", #call, rc__)); \
-  } while (0)
-
 int64_t align_embedding_dim(int64_t dim, size_t element_size)
 {  // rows padded to 16 bytes: reference embedding.cpp:43-50 — and, round 5, to whole 128-byte lines when that is cheap.
   // A row that does not start on a line boundary is WRITTEN with a partial line at either end; scatter and gradient apply of
@@ -230,9 +224,10 @@ struct self_rows_ref {
   int64_t stride      = 0;
 };
 
-// sorted view of a batch of received ids (unique ids, run starts, sorted order): the scratch lives as long as the object
-struct dedup_result {
-  explicit dedup_result(wholememory_env_func_t* env) : unique_ids(env), run_starts(env), order(env), n_unique(env), ws(env) {}
+// sorted view of a batch of received ids (sorted_ids: the scratch lives as long as the object) plus the join of the sort's
+// side stream, when that was put off
+struct dedup_result : sorted_ids {
+  using sorted_ids::sorted_ids;
   // join_later: the caller queues the optimizer step behind the sort and calls join() after it (the sort's side stream is
   // then joined behind the step instead of in front of it: backend.hpp, dedup_defer_join); the destructor joins in any case
   ~dedup_result() { (void)join(); }
@@ -265,22 +260,10 @@ struct dedup_result {
       }
     } scope(bk, join_later);
     if (scope.on) deferred_on = stream, join_owed = true;
-    d_unique  = unique_ids.device(n, index_dtype);
-    d_starts  = static_cast<int32_t*>(run_starts.device(n + 1, WHOLEMEMORY_DT_INT));
-    d_order   = static_cast<int32_t*>(order.device(n, WHOLEMEMORY_DT_INT));
-    d_nunique = static_cast<int64_t*>(n_unique.device(1, WHOLEMEMORY_DT_INT64));
-    void* d_ws = ws.device(static_cast<int64_t>(bk->dedup_workspace_bytes(n, index_dtype)), WHOLEMEMORY_DT_INT8);
-    int rc = bk->dedup_ids(ids, index_dtype, n, key_upper_bound, key_lower_bound, d_unique, d_starts, d_order, d_nunique, d_ws, stream);
-    if (rc == -1) throw logic_error("dedup_ids: unsupported index dtype or more than 2^31 received ids");
-    if (rc != 0) throw hip_error("dedup_ids failed");
+    run_or_throw(ids, index_dtype, n, key_upper_bound, key_lower_bound, stream);
   }
-  temp_mem unique_ids, run_starts, order, n_unique, ws;
-  void* deferred_on  = nullptr;   // stream a deferred join is owed on (the null stream is a stream like any other)
-  bool join_owed     = false;
-  void* d_unique     = nullptr;
-  int32_t* d_starts  = nullptr;
-  int32_t* d_order   = nullptr;
-  int64_t* d_nunique = nullptr;
+  void* deferred_on = nullptr;   // stream a deferred join is owed on (the null stream is a stream like any other)
+  bool join_owed    = false;
 };
 
 // the fused duplicate-sum + optimizer kernel over an already sorted batch
@@ -290,28 +273,28 @@ void step_sorted(dedup_result& r, wholememory_dtype_t index_dtype, int64_t n_rec
 {
   const auto* bk = backend();
   temp_mem host_n(env), long_ws(env);
-  oa->ids         = r.d_unique;
+  oa->ids         = r.unique;
   oa->index_dtype = index_dtype;
-  oa->run_starts  = r.d_starts;
-  oa->order       = r.d_order;
+  oa->run_starts  = r.starts;
+  oa->order       = r.order;
   oa->grads       = recv_grads;
   oa->grad_stride = grad_stride;
   if (self != nullptr && self->count > 0) {
-    WM_BK(bk->remap_self_order(r.d_order, n_recv, self->begin, self->count, self->rows, stream));
+    WM_BK(bk->remap_self_order(r.order, n_recv, self->begin, self->count, self->rows, stream));
     oa->self_grads       = self->grads;
     oa->self_grad_stride = self->stride;
   }
-  oa->count       = n_recv;  // upper bound; the kernel reads the true count from d_nunique
+  oa->count       = n_recv;  // upper bound; the kernel reads the true count from n_unique_dev
   oa->long_run_ws_bytes = bk->long_run_workspace_bytes(n_recv, oa->dim);
   oa->long_run_ws       = long_ws.device(static_cast<int64_t>(oa->long_run_ws_bytes), WHOLEMEMORY_DT_INT8);
   if (rows_ready != nullptr) WM_BK(bk->stream_wait_event(stream, rows_ready));
-  int rc = bk->optimizer_step(oa, r.d_nunique, stream);
+  int rc = bk->optimizer_step(oa, r.n_unique_dev, stream);
   const int join_rc = r.join();   // the sort's side stream, if it left one running: joined behind the step
   if (rc != 0) throw hip_error("optimizer_step failed");
   if (join_rc != 0) throw hip_error("the id sort of an earlier gradient step reported a device-side timeout (see the ERROR line above)");
   if (n_unique_host != nullptr) {
     auto* h = static_cast<int64_t*>(host_n.pinned(1, WHOLEMEMORY_DT_INT64));
-    WM_BK(bk->memcpy_async(h, r.d_nunique, sizeof(int64_t), stream));
+    WM_BK(bk->memcpy_async(h, r.n_unique_dev, sizeof(int64_t), stream));
     WM_BK(bk->stream_sync(stream));
     *n_unique_host = *h;
     if (bk->device_error != nullptr && bk->device_error() != 0)   // (synchronised: this call's own sort has reported by now)
@@ -465,7 +448,7 @@ int combined_gradient_apply(wholememory_embedding_* e, const char* idx_ptr, cons
   r.run(idx_ptr, iarr.dtype, n, all_rows < INT64_C(0xFFFFFFFF) ? all_rows : 0, stream, 0, /*join_later=*/false);
   temp_mem host_n(env), flag_mem(env);
   auto* h_nu = static_cast<int64_t*>(host_n.pinned(1, WHOLEMEMORY_DT_INT64));
-  WM_BK(bk->memcpy_async(h_nu, r.d_nunique, sizeof(int64_t), stream));
+  WM_BK(bk->memcpy_async(h_nu, r.n_unique_dev, sizeof(int64_t), stream));
   WM_BK(bk->stream_sync(stream));   // (the dense buffer of partial sums is sized and zeroed for exactly the distinct ids)
   const int64_t nu = *h_nu;
   // (2) partial sums: row u of `partial` = fp32 sum of the gradient rows of run u, rounded once
@@ -479,20 +462,20 @@ int combined_gradient_apply(wholememory_embedding_* e, const char* idx_ptr, cons
     WM_BK(bk->fill_iota(iota, iarr.dtype, nu, 0, stream));
     wm_optimizer_args fa{};
     fa.type = WHOLEMEMORY_OPT_SGD, fa.lr = -1.0f, fa.weight_decay = 0.0f;
-    fa.ids = iota, fa.index_dtype = iarr.dtype, fa.run_starts = r.d_starts, fa.order = r.d_order;
+    fa.ids = iota, fa.index_dtype = iarr.dtype, fa.run_starts = r.starts, fa.order = r.order;
     fa.value_dtype = vdt, fa.grads = grads_ptr, fa.grad_stride = gmat.stride;
     fa.count = nu, fa.local_table = partial, fa.table_stride = dim, fa.local_entry_offset = 0, fa.dim = dim;
     fa.fold_mode   = 1;
     fa.long_run_ws_bytes = bk->long_run_workspace_bytes(n, dim);
     fa.long_run_ws       = long_ws.device(static_cast<int64_t>(fa.long_run_ws_bytes), WHOLEMEMORY_DT_INT8);
-    if (bk->optimizer_step(&fa, r.d_nunique, stream) != 0) throw hip_error("folding the duplicate gradient rows failed");
+    if (bk->optimizer_step(&fa, r.n_unique_dev, stream) != 0) throw hip_error("folding the duplicate gradient rows failed");
     if (vdt == WHOLEMEMORY_DT_HALF && bk->partials_nonfinite != nullptr)
-      WM_BK(bk->partials_nonfinite(r.d_starts, r.d_nunique, nu, partial, dim, dim, d_flag, stream));
+      WM_BK(bk->partials_nonfinite(r.starts, r.n_unique_dev, nu, partial, dim, dim, d_flag, stream));
   }
   // (3) owner segments of the sorted distinct ids + their exchange; the verdict on the partial rows travels with the counts
-  sorted_unique su{r.d_nunique, d_flag};
+  sorted_unique su{r.n_unique_dev, d_flag};
   id_exchange x(env);
-  bucket_and_exchange_ids(e->comm, r.d_unique, iarr.dtype, nu, entry_offsets, env, stream, &x, self_local, false, &su);
+  bucket_and_exchange_ids(e->comm, r.unique, iarr.dtype, nu, entry_offsets, env, stream, &x, self_local, false, &su);
   if (x.dup_permille < 0) return 0;   // some rank's float16 partial sums left the range: everybody takes the plain route
   std::vector<int64_t> full_recv_counts = x.recv_counts, full_recv_offsets(W + 1, 0);
   full_recv_counts[rank]                = x.self_count;

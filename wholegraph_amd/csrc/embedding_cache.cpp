@@ -7,12 +7,6 @@
 
 namespace wm {
 
-#define WM_BK(call)                                                                                  \
-  do {                                                                                               \
-    int rc__ = (call);                                                                               \
-    if (rc__ != 0) throw ::wm::hip_error(::wm::format_string("%s failed with code %d", #call, rc__)); \
-  } while (0)
-
 row_cache::~row_cache()
 {
   const auto* bk = backend();
@@ -91,15 +85,10 @@ wholememory_error_code_t row_cache_update(row_cache* c, const void* ids, wholeme
   const auto* bk = backend();
   if (n == 0 || c->args.n_sets == 0) return WHOLEMEMORY_SUCCESS;
   if (n >= (INT64_C(1) << 31)) return WHOLEMEMORY_INVALID_INPUT;
-  temp_mem unique_ids(env), run_starts(env), order(env), n_unique(env), ws(env);
-  void* d_unique  = unique_ids.device(n, index_dtype);
-  auto* d_starts  = static_cast<int32_t*>(run_starts.device(n + 1, WHOLEMEMORY_DT_INT));
-  auto* d_order   = static_cast<int32_t*>(order.device(n, WHOLEMEMORY_DT_INT));
-  auto* d_nunique = static_cast<int64_t*>(n_unique.device(1, WHOLEMEMORY_DT_INT64));
-  void* d_ws      = ws.device(static_cast<int64_t>(bk->dedup_workspace_bytes(n, index_dtype)), WHOLEMEMORY_DT_INT8);
-  int rc = bk->dedup_ids(ids, index_dtype, n, key_upper_bound, 0, d_unique, d_starts, d_order, d_nunique, d_ws, stream);
+  sorted_ids s(env);
+  int rc = s.run(ids, index_dtype, n, key_upper_bound, 0, stream);
   if (rc != 0) return rc == -1 ? WHOLEMEMORY_INVALID_INPUT : WHOLEMEMORY_CUDA_ERROR;
-  rc = bk->cache_update(&c->args, d_unique, index_dtype, d_starts, d_nunique, n, nullptr, nullptr, nullptr, stream);
+  rc = bk->cache_update(&c->args, s.unique, index_dtype, s.starts, s.n_unique_dev, n, nullptr, nullptr, nullptr, stream);
   if (rc != 0) return rc == -1 ? WHOLEMEMORY_INVALID_INPUT : WHOLEMEMORY_CUDA_ERROR;
   WM_BK(bk->stream_sync(stream));  // scratch buffers return to the caller's allocator
   return WHOLEMEMORY_SUCCESS;
@@ -115,17 +104,13 @@ wholememory_error_code_t row_cache_plan(row_cache* c, const void* ids, wholememo
   auto* fill_slots = static_cast<int64_t*>(slots_mem->device(n, WHOLEMEMORY_DT_INT64));
   if (n == 0 || c->args.n_sets == 0) return WHOLEMEMORY_SUCCESS;
   if (n >= (INT64_C(1) << 31) || c->writable) return WHOLEMEMORY_INVALID_INPUT;
-  temp_mem unique_ids(env), run_starts(env), order(env), n_unique(env), ws(env), count(env), host_n(env);
-  void* d_unique  = unique_ids.device(n, index_dtype);
-  auto* d_starts  = static_cast<int32_t*>(run_starts.device(n + 1, WHOLEMEMORY_DT_INT));
-  auto* d_order   = static_cast<int32_t*>(order.device(n, WHOLEMEMORY_DT_INT));
-  auto* d_nunique = static_cast<int64_t*>(n_unique.device(1, WHOLEMEMORY_DT_INT64));
-  void* d_ws      = ws.device(static_cast<int64_t>(bk->dedup_workspace_bytes(n, index_dtype)), WHOLEMEMORY_DT_INT8);
-  auto* d_count   = static_cast<int*>(count.device(1, WHOLEMEMORY_DT_INT));
+  sorted_ids s(env);
+  temp_mem count(env), host_n(env);
+  auto* d_count = static_cast<int*>(count.device(1, WHOLEMEMORY_DT_INT));
   WM_BK(bk->memset_async(d_count, 0, sizeof(int), stream));
-  int rc = bk->dedup_ids(ids, index_dtype, n, key_upper_bound, 0, d_unique, d_starts, d_order, d_nunique, d_ws, stream);
+  int rc = s.run(ids, index_dtype, n, key_upper_bound, 0, stream);
   if (rc != 0) return rc == -1 ? WHOLEMEMORY_INVALID_INPUT : WHOLEMEMORY_CUDA_ERROR;
-  rc = bk->cache_update(&c->args, d_unique, index_dtype, d_starts, d_nunique, n, fill_rows, fill_slots, d_count, stream);
+  rc = bk->cache_update(&c->args, s.unique, index_dtype, s.starts, s.n_unique_dev, n, fill_rows, fill_slots, d_count, stream);
   if (rc != 0) return rc == -1 ? WHOLEMEMORY_INVALID_INPUT : WHOLEMEMORY_CUDA_ERROR;
   auto* h = static_cast<int*>(host_n.pinned(1, WHOLEMEMORY_DT_INT));
   WM_BK(bk->memcpy_async(h, d_count, sizeof(int), stream));

@@ -4,35 +4,25 @@
 // order of every fp32 sum, are stated in the header.
 #include <wholememory/wholegraph_amd_ext.h>
 
-#include "ops_internal.hpp"
+#include "csc_block.hpp"
 
 namespace {
 
 using namespace wm;
-
-#define WM_BK(call)                                                                      \
-  do {                                                                                   \
-    int rc__ = (call);                                                                   \
-    if (rc__ != 0) throw wm::hip_error(wm::format_string("%s failed: %d", #call, rc__)); \
-  } while (0)
 
 void check_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src,
                 const float* h, int64_t h_stride, const float* att, int64_t heads, int64_t dim, const float* alpha,
                 const float* scores)
 {
   auto bad = [](const char* what) { throw invalid_input(what); };
-  if (n_edges < 0 || n_dst < 0 || n_src < 0) bad("negative size");
+  check_block(row_ptr, col_ind, n_edges, n_dst, n_src, n_edges > 0 && n_dst > 0, "h");
   if (heads < 1) bad("heads must be >= 1");
   if (dim < 1) bad("dim must be >= 1");
-  if (n_dst > n_src) bad("n_dst > n_src: the targets are the first rows of h");
-  if (row_ptr == nullptr) bad("row_ptr is null");
-  if (n_edges > 0 && n_dst > 0 && col_ind == nullptr) bad("col_ind is null");
   if (n_src > 0 && h == nullptr) bad("h is null");
   if (att == nullptr) bad("att is null");
   if (n_edges > 0 && n_dst > 0 && alpha == nullptr) bad("alpha is null");
   if (n_src > 0 && scores == nullptr) bad("scores is null");
   if (h_stride < heads * dim) bad("h stride smaller than its row");
-  if (n_edges >= (int64_t(1) << 31) || n_src >= (int64_t(1) << 31)) bad("more than 2^31 - 1 edges or rows");
   if (heads * dim >= (int64_t(1) << 31)) bad("heads * dim too large");
 }
 
@@ -57,33 +47,6 @@ wm_gat_args make_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_
   a.scores   = const_cast<float*>(scores);   // (written by the forward only)
   return a;
 }
-
-// the edge index of a backward: a stable sort of col_ind (runs of one source, edge positions ascending in each run).
-// dedup_ids joins any side stream of its own before it returns (no deferred join asked for), so its outputs are ready for
-// the kernels queued behind it on `stream`
-struct edge_index {
-  temp_mem unique_mem, starts_mem, order_mem, nu_mem, sort_ws;
-  int32_t *unique = nullptr, *starts = nullptr, *order = nullptr;
-  int64_t* nu     = nullptr;
-  explicit edge_index(wholememory_env_func_t* fns)
-    : unique_mem(fns), starts_mem(fns), order_mem(fns), nu_mem(fns), sort_ws(fns)
-  {
-  }
-  void build(const wm_device_backend* bk, const int32_t* col_ind, int64_t E, int64_t n_src, void* stream)
-  {
-    if (n_src <= 0) return;
-    unique      = static_cast<int32_t*>(unique_mem.device(E, WHOLEMEMORY_DT_INT));
-    starts      = static_cast<int32_t*>(starts_mem.device(E + 1, WHOLEMEMORY_DT_INT));
-    order       = static_cast<int32_t*>(order_mem.device(E, WHOLEMEMORY_DT_INT));
-    nu          = static_cast<int64_t*>(nu_mem.device(1, WHOLEMEMORY_DT_INT64));
-    void* d_sws = sort_ws.device(static_cast<int64_t>(bk->dedup_workspace_bytes(E, WHOLEMEMORY_DT_INT)), WHOLEMEMORY_DT_INT8);
-    if (bk->device_error != nullptr && bk->device_error() != 0)
-      throw hip_error("an earlier id sort reported a device-side timeout (see the ERROR line above)");
-    const int rc = bk->dedup_ids(col_ind, WHOLEMEMORY_DT_INT, E, n_src, 0, unique, starts, order, nu, d_sws, stream);
-    if (rc == -1) throw logic_error("dedup_ids: unsupported index dtype or more than 2^31 edges");
-    if (rc != 0) throw hip_error("dedup_ids failed");
-  }
-};
 
 }  // namespace
 
@@ -139,11 +102,11 @@ wholememory_error_code_t wholememory_ext_csc_gat_backward(const int32_t* row_ptr
   a.grad_h        = grad_h;
   a.grad_h_stride = grad_h_stride;
   a.grad_att      = grad_att;
-  edge_index ix(p_env_fns);
+  sorted_ids ix(p_env_fns);   // the edge index; a block without source rows has none: null pointers
   temp_mem gat_ws(p_env_fns);
-  ix.build(bk, col_ind, a.n_edges, n_src, stream);
+  if (n_src > 0) sort_col_ind(&ix, col_ind, a.n_edges, n_src, stream);
   void* d_gws = gat_ws.device(static_cast<int64_t>(bk->gat_backward_workspace_bytes(&a)), WHOLEMEMORY_DT_INT8);
-  WM_BK(bk->gat_backward(&a, ix.order, ix.starts, ix.unique, ix.nu, d_gws, stream));
+  WM_BK(bk->gat_backward(&a, ix.order, ix.starts, static_cast<const int32_t*>(ix.unique), ix.n_unique_dev, d_gws, stream));
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }
@@ -216,11 +179,11 @@ wholememory_error_code_t wholememory_ext_csc_gat_edge_backward(
   a.edge_scores     = const_cast<float*>(edge_scores);   // (written by the forward only)
   a.grad_edge_feat  = grad_edge_feat;
   a.grad_ef_stride  = grad_ef_stride;
-  edge_index ix(p_env_fns);
+  sorted_ids ix(p_env_fns);   // the edge index; a block without source rows has none: null pointers
   temp_mem gat_ws(p_env_fns);
-  ix.build(bk, col_ind, a.g.n_edges, n_src, stream);
+  if (n_src > 0) sort_col_ind(&ix, col_ind, a.g.n_edges, n_src, stream);
   void* d_gws = gat_ws.device(static_cast<int64_t>(bk->gat_edge_backward_workspace_bytes(&a)), WHOLEMEMORY_DT_INT8);
-  WM_BK(bk->gat_edge_backward(&a, ix.order, ix.starts, ix.unique, ix.nu, d_gws, stream));
+  WM_BK(bk->gat_edge_backward(&a, ix.order, ix.starts, static_cast<const int32_t*>(ix.unique), ix.n_unique_dev, d_gws, stream));
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }

@@ -25,12 +25,6 @@ namespace {
 
 using namespace wm;
 
-#define WM_BK(call)                                                                   \
-  do {                                                                                \
-    int rc__ = (call);                                                                \
-    if (rc__ != 0) throw wm::hip_error(wm::format_string("%s failed: %d", #call, rc__)); \
-  } while (0)
-
 // one variable-size result handed to the caller's allocator (reference output_memory_handle.hpp:23-93)
 void* output_alloc(wholememory_env_func_t* env, void* memory_context, int64_t count, wholememory_dtype_t dtype)
 {

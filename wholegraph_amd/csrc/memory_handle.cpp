@@ -72,12 +72,6 @@ struct wholememory_handle_ {
 namespace wm {
 namespace {
 
-#define WM_BK(call)                                                                                \
-  do {                                                                                             \
-    int rc__ = (call);                                                                             \
-    if (rc__ != 0) throw ::wm::hip_error(::wm::format_string("%s failed with code %d", #call, rc__)); \
-  } while (0)
-
 void plan_partition(wholememory_handle_* h, const size_t* rank_entry_partition)
 {
   const int W = h->comm->world_size;

@@ -26,12 +26,6 @@
 
 namespace wm {
 
-#define WM_BK(call)                                                                                  \
-  do {                                                                                               \
-    int rc__ = (call);                                                                               \
-    if (rc__ != 0) throw ::wm::hip_error(::wm::format_string("%s failed with code %d", #call, rc__)); \
-  } while (0)
-
 // ------------------------------------------------------------------------------------------------
 temp_mem::temp_mem(wholememory_env_func_t* env) : env_(env)
 {
@@ -54,6 +48,29 @@ void* temp_mem::alloc(int64_t elt_count, wholememory_dtype_t dtype, wholememory_
   ptr_       = env_->temporary_fns.malloc_fn(&d, type, ctx_, env_->temporary_fns.global_context);
   if (ptr_ == nullptr) throw std::bad_alloc();
   return ptr_;
+}
+
+sorted_ids::sorted_ids(wholememory_env_func_t* env)
+  : unique_mem_(env), starts_mem_(env), order_mem_(env), n_unique_mem_(env), ws_mem_(env)
+{
+}
+int sorted_ids::run(const void* ids, wholememory_dtype_t index_dtype, int64_t n, int64_t key_upper_bound,
+                    int64_t key_lower_bound, void* stream)
+{
+  const auto* bk = backend();
+  unique         = unique_mem_.device(n, index_dtype);
+  starts         = static_cast<int32_t*>(starts_mem_.device(n + 1, WHOLEMEMORY_DT_INT));
+  order          = static_cast<int32_t*>(order_mem_.device(n, WHOLEMEMORY_DT_INT));
+  n_unique_dev   = static_cast<int64_t*>(n_unique_mem_.device(1, WHOLEMEMORY_DT_INT64));
+  void* ws = ws_mem_.device(static_cast<int64_t>(bk->dedup_workspace_bytes(n, index_dtype)), WHOLEMEMORY_DT_INT8);
+  return bk->dedup_ids(ids, index_dtype, n, key_upper_bound, key_lower_bound, unique, starts, order, n_unique_dev, ws, stream);
+}
+void sorted_ids::run_or_throw(const void* ids, wholememory_dtype_t index_dtype, int64_t n, int64_t key_upper_bound,
+                              int64_t key_lower_bound, void* stream)
+{
+  const int rc = run(ids, index_dtype, n, key_upper_bound, key_lower_bound, stream);
+  if (rc == -1) throw logic_error("dedup_ids: unsupported index dtype or more than 2^31 ids");
+  if (rc != 0) throw hip_error("dedup_ids failed");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -471,25 +488,21 @@ wholememory_error_code_t gather_distributed_dedup(wholememory_handle_t handle, c
   const auto* bk    = backend();
   const int64_t n   = d.indices.size;
   const int64_t dim = d.table.sizes[1];
-  temp_mem unique_ids(env), run_starts(env), order(env), n_unique(env), ws(env), rows(env), inverse(env);
-  void* d_unique  = unique_ids.device(n, d.indices.dtype);
-  auto* d_starts  = static_cast<int32_t*>(run_starts.device(n + 1, WHOLEMEMORY_DT_INT));
-  auto* d_order   = static_cast<int32_t*>(order.device(n, WHOLEMEMORY_DT_INT));
-  auto* d_nunique = static_cast<int64_t*>(n_unique.device(1, WHOLEMEMORY_DT_INT64));
-  void* d_ws = ws.device(static_cast<int64_t>(bk->dedup_workspace_bytes(n, d.indices.dtype)), WHOLEMEMORY_DT_INT8);
+  sorted_ids s(env);
+  temp_mem rows(env), inverse(env);
   // full-width keys: negative ("skip me") ids must stay distinct from every valid id; as unsigned keys they sort last
-  int rc = bk->dedup_ids(d.indices_ptr, d.indices.dtype, n, 0, 0, d_unique, d_starts, d_order, d_nunique, d_ws, stream);
-  if (rc != 0) throw hip_error("dedup of the requested ids failed");  // not a return: the peers are committed to the exchange
+  if (s.run(d.indices_ptr, d.indices.dtype, n, 0, 0, stream) != 0)
+    throw hip_error("dedup of the requested ids failed");  // not a return: the peers are committed to the exchange
 
   // (1) owner segments of the distinct ids + the ids exchange; the host learns the counts in the exchange's one sync
-  sorted_unique su{d_nunique};
+  sorted_unique su{s.n_unique_dev};
   id_exchange x(env);
-  bucket_and_exchange_ids(comm, d_unique, d.indices.dtype, n, entry_offsets, env, stream, &x, !comm->loopback, false, &su);
+  bucket_and_exchange_ids(comm, s.unique, d.indices.dtype, n, entry_offsets, env, stream, &x, !comm->loopback, false, &su);
   const int64_t nu = x.total_valid;  // distinct NON-NEGATIVE ids
   // (2) each of them once, through the exchange, straight into its row of a dense [nu, dim] buffer of the output dtype
   char* uniq_rows = static_cast<char*>(rows.device(dim * nu, d.plain.dtype));
   op_descs du     = d;
-  du.indices_ptr  = d_unique;
+  du.indices_ptr  = s.unique;
   du.indices      = wholememory_create_array_desc(nu, 0, d.indices.dtype);
   du.plain_ptr    = uniq_rows;
   int64_t usz[2]  = {nu, dim};
@@ -499,8 +512,8 @@ wholememory_error_code_t gather_distributed_dedup(wholememory_handle_t handle, c
   auto* inv = static_cast<int64_t*>(inverse.device(n, WHOLEMEMORY_DT_INT64));
   // (an id past the last row belongs to no owner segment and was not fetched: its output row stays untouched, like a
   // negative id's — the plain route reads past the last owner's shard for such ids, undefined in the reference too)
-  WM_BK(bk->run_inverse(d_starts, d_order, d_unique, d.indices.dtype, d_nunique, n, static_cast<int64_t>(entry_offsets.back()),
-                        inv, stream));
+  WM_BK(bk->run_inverse(s.starts, s.order, s.unique, d.indices.dtype, s.n_unique_dev, n,
+                        static_cast<int64_t>(entry_offsets.back()), inv, stream));
   wm_rows_args ea{};
   fill_rows_args(&ea, wholememory_create_continuous_global_reference(uniq_rows), du.plain, inv, WHOLEMEMORY_DT_INT64, n,
                  d.plain_ptr, d.plain, gather_sms);
@@ -824,25 +837,21 @@ wholememory_error_code_t gather_hierarchy(wholememory_handle_t handle, const op_
   const int64_t n_relay = xa.total_recv;
 
   // ---- relay: distinct ids only (reference sort_unique_ids_for_hierarchy_func) ----
-  temp_mem unique_ids(env), run_starts(env), order(env), n_unique(env), ws(env), host_n(env), inverse(env);
+  sorted_ids s(env);
+  temp_mem host_n(env), inverse(env);
   const bool dedup = n_relay > 0 && n_relay < (INT64_C(1) << 31) && bk->run_inverse != nullptr;
   void* fetch_ids  = xa.recv_ids;
   int64_t n_fetch  = n_relay;
   int64_t* inv     = nullptr;
   if (dedup) {
-    void* d_unique  = unique_ids.device(n_relay, d.indices.dtype);
-    auto* d_starts  = static_cast<int32_t*>(run_starts.device(n_relay + 1, WHOLEMEMORY_DT_INT));
-    auto* d_order   = static_cast<int32_t*>(order.device(n_relay, WHOLEMEMORY_DT_INT));
-    auto* d_nunique = static_cast<int64_t*>(n_unique.device(1, WHOLEMEMORY_DT_INT64));
-    void* d_ws = ws.device(static_cast<int64_t>(bk->dedup_workspace_bytes(n_relay, d.indices.dtype)), WHOLEMEMORY_DT_INT8);
-    int rc = bk->dedup_ids(xa.recv_ids, d.indices.dtype, n_relay, 0, 0, d_unique, d_starts, d_order, d_nunique, d_ws, stream);
-    if (rc != 0) throw hip_error("dedup of relayed ids failed");  // not a return: the peers are already committed to hop B
+    if (s.run(xa.recv_ids, d.indices.dtype, n_relay, 0, 0, stream) != 0)
+      throw hip_error("dedup of relayed ids failed");  // not a return: the peers are already committed to hop B
     inv = static_cast<int64_t*>(inverse.device(n_relay, WHOLEMEMORY_DT_INT64));
-    WM_BK(bk->run_inverse(d_starts, d_order, d_unique, d.indices.dtype, d_nunique, n_relay, 0, inv, stream));
+    WM_BK(bk->run_inverse(s.starts, s.order, s.unique, d.indices.dtype, s.n_unique_dev, n_relay, 0, inv, stream));
     auto* h_n = static_cast<int64_t*>(host_n.pinned(1, WHOLEMEMORY_DT_INT64));
-    WM_BK(bk->memcpy_async(h_n, d_nunique, sizeof(int64_t), stream));
+    WM_BK(bk->memcpy_async(h_n, s.n_unique_dev, sizeof(int64_t), stream));
     WM_BK(bk->stream_sync(stream));
-    fetch_ids = d_unique;
+    fetch_ids = s.unique;
     n_fetch   = *h_n;
   }
 

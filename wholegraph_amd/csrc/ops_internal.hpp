@@ -1,4 +1,5 @@
-// wholegraph_amd — internals shared by ops.cpp and embedding.cpp (host orchestration helpers).
+// wholegraph_amd — host orchestration helpers shared by the op files (ops.cpp, embedding.cpp, embedding_cache.cpp,
+// aggregate.cpp, gat.cpp): scratch from the caller's env functions, the id sort, the id / row exchanges.
 #pragma once
 
 #include <vector>
@@ -30,6 +31,28 @@ class temp_mem {
   wholememory_env_func_t* env_;
   void* ctx_ = nullptr;
   void* ptr_ = nullptr;
+};
+
+// The id sort every op shares (backend.hpp: dedup_ids) with its scratch, which lives as long as the object: the distinct ids
+// in ascending order of their (unsigned) keys, where the run of each one starts in the sorted batch, the stable order that
+// sorts the batch, and the number of distinct ids, still on the device.
+struct sorted_ids {
+  explicit sorted_ids(wholememory_env_func_t* env);
+  // allocates unique [n], starts [n + 1], order [n], n_unique_dev [1] and the sort's workspace, in that order, and queues
+  // the sort on `stream`. Returns the backend's code as it is (0; -1: an index dtype or an n the sort does not take): what a
+  // failure means is the caller's business. Does not ask device_error(), which clears the code it reads.
+  int run(const void* ids, wholememory_dtype_t index_dtype, int64_t n, int64_t key_upper_bound, int64_t key_lower_bound,
+          void* stream);
+  // run(), with -1 thrown as logic_error and any other failure as hip_error
+  void run_or_throw(const void* ids, wholememory_dtype_t index_dtype, int64_t n, int64_t key_upper_bound,
+                    int64_t key_lower_bound, void* stream);
+  void* unique          = nullptr;  // [n] of the index dtype
+  int32_t* starts       = nullptr;
+  int32_t* order        = nullptr;
+  int64_t* n_unique_dev = nullptr;
+
+ private:
+  temp_mem unique_mem_, starts_mem_, order_mem_, n_unique_mem_, ws_mem_;
 };
 
 // Result of bucket + exchange of lookup ids (reference bucket_and_exchange_ids_func,

@@ -80,6 +80,13 @@ int64_t host_sorted_gather_min();
     }                                                                                           \
   } while (0)
 
+// throw wm::hip_error when a call into the device backend (backend.hpp: 0 = success) returns anything else
+#define WM_BK(call)                                                                                   \
+  do {                                                                                                \
+    int rc__ = (call);                                                                                \
+    if (rc__ != 0) throw ::wm::hip_error(::wm::format_string("%s failed with code %d", #call, rc__)); \
+  } while (0)
+
 // reference *_NOTHROW checks abort the process (error.hpp:86-95)
 #define WM_CHECK_ABORT(cond, ...)                                                     \
   do {                                                                                \

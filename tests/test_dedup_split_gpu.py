@@ -152,7 +152,7 @@ def test_long_run_side_follows_the_batches(gpu_env, knobs):
 @pytest.mark.parametrize("kind", ["uniform", "hot_id"])
 def test_gradient_apply_replays_from_a_hipgraph(gpu_env, knobs, kind):
     """One rank's gradient apply has no host synchronisation, so it can be captured. While a stream is being captured the
-    split sort forks and joins its side stream with EVENTS only (optim.hip: a wave that waits for a word needs the other branch
+    split sort forks and joins its side stream with EVENTS only (dedup.hip: a wave that waits for a word needs the other branch
     to be running, and the branches of a graph may be replayed one after the other): the replay must give the eager call's
     bits on the map path and on the generic path (a hot id that overflows its bucket)."""
     import torch
@@ -202,7 +202,7 @@ def test_gradient_apply_replays_from_a_hipgraph(gpu_env, knobs, kind):
 
 
 MODES = {
-    # how the sort's side stream is forked / joined and where the step's long-run side runs (optim.hip); the default is
+    # how the sort's side stream is forked / joined and where the step's long-run side runs (dedup.hip, optim.hip); the default is
     # "word fork + deferred join + detached long-run side", every other combination stays selectable for A/B runs
     "event_fork": {"WM_DEDUP_FORK_EVENT": 1},
     "join_in_front": {"WM_DEDUP_DEFER_JOIN": 0},
@@ -234,7 +234,7 @@ def test_every_fork_and_join_arrangement_gives_the_same_bits(gpu_env, knobs, nam
 
 
 def test_route_follows_the_batches(gpu_env, knobs):
-    """Adaptive route (optim.hip: run_dedup): once a split sort overflowed a bucket, the next batches of the same row range go
+    """Adaptive route (dedup.hip: run_dedup): once a split sort overflowed a bucket, the next batches of the same row range go
     straight to rocPRIM's sort (a series of skewed batches is the usual case, and the gated generic path is the slower of the two);
     every fourth such call probes with the split sort's first two kernels, and the first batch that would not overflow switches
     back. Whatever the route, every call's result is the oracle's, bit for bit; the route shows in the split sort counter."""

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <mutex>
 #include <type_traits>
 
 namespace wm {
@@ -106,6 +107,20 @@ template <typename V>
 __device__ __forceinline__ void st_global_nt(void* p, V v)
 {
   __builtin_nontemporal_store(v, (WM_GLOBAL_AS V*)p);
+}
+
+// one Lane (a side stream and its events: dedup.hip's sort_lane, optim.hip's long_lane) per device, made at first use, kept for the life of the process
+constexpr int kMaxDevices = 64;
+template <typename Lane>
+Lane& per_device()
+{
+  static std::mutex mu;
+  static Lane* lanes[kMaxDevices] = {};
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) dev = 0;
+  std::lock_guard<std::mutex> lk(mu);
+  if (lanes[dev] == nullptr) lanes[dev] = new Lane();
+  return *lanes[dev];
 }
 
 }  // namespace wm

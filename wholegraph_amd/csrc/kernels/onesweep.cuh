@@ -298,7 +298,7 @@ inline size_t ctrl_words_bound(int64_t n)
 // operator[] returning a 32-bit key). tk / tv: a second (keys, payloads) pair of n words each; ctrl: ctrl_words() words that
 // READ ZERO (the caller's business: one fill, or a kernel that runs before anyway). Enqueues 1 + passes kernels on `stream`,
 // every one gated on `gate` (see the file comment); returns 0 or a negative error.
-// the word (of ctrl) a pass sets when its look-back gave up: whoever consumes the sorted pairs must look at it (optim.hip
+// the word (of ctrl) a pass sets when its look-back gave up: whoever consumes the sorted pairs must look at it (dedup.hip
 // folds it into the split sort's error word in the generic path's closing kernel)
 template <int BLOCK, int IPT>
 inline uint32_t* error_word(uint32_t* ctrl, int64_t n, unsigned bits)

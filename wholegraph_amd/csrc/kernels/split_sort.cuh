@@ -41,10 +41,12 @@
 // When a bucket does not fit (more than 4096 / 8192 ids, by the size of stage 2: a hot id of a Zipf batch, ids clustered in a few
 // thousand rows), the scan
 // kernel raises the overflow word, stages 1c / 2 return at once, and the caller's generic path — gated on the same word, see
-// optim.hip: run_dedup — sorts the batch instead. The decision is taken on the device: no host synchronisation, capturable.
+// dedup.hip: run_dedup — sorts the batch instead. The decision is taken on the device: no host synchronisation, capturable.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "sort_handoff.cuh"   // the control words (kCtl*) and kMaxDup: what the optimizer step reads of a sort
 
 namespace wm {
 namespace split {
@@ -68,26 +70,16 @@ constexpr int kMaxPitch   = kMaxBuckets + 32;
 constexpr int kCapBitsSmall = 12, kCapBitsBig = 13;
 constexpr int kMaxLowBits = 32 - kCapBitsBig;     // low key bits that fit the sort word beside the index
 constexpr int kMapBits    = 16;                   // low key bits the row map of stage 2 covers (2^16 bits = 8 KB)
-constexpr int kMaxDup     = 8;                    // runs of more ids than this send their bucket to the radix passes
 constexpr int kMaxIpt     = 24;                   // ids per thread of a stage-1 tile, at most
 constexpr int kMaxTiles   = 1024;
 constexpr int kSortIpt    = 8;                    // ids per thread of a stage-2 workgroup
 constexpr size_t kLdsBytes = 160 * 1024;
 constexpr uint32_t kFlagAggregate = 1u << 30, kFlagPrefix = 2u << 30, kValueMask = (1u << 30) - 1;
 
-// control words (u32), zeroed by split_hist_kernel's first workgroup
-// [kCtlLongCounters, +16): the counters of the optimizer step's long-run side (optim.hip), zeroed here with the rest so that
-// the step needs no fill of its own when it follows a split sort
-// kCtlGenericDone: set by the generic path's closing kernel (optim.hip: detect_runs)
-// kCtlScanCount: workgroups of split_scan_kernel that have finished (the last one publishes the caller's verdict word)
-// kCtlSortDone: set by split_join_kernel — the runs are final (whichever path wrote them); side-stream work that needs them
-// waits for this word instead of an event on the caller's stream (optim.hip: the detached long-run side)
-enum { kCtlOverflow = 0, kCtlTicket = 1, kCtlError = 2, kCtlRadixBuckets = 3, kCtlGenericDone = 4, kCtlSortDone = 5, kCtlScanCount = 6, kCtlLongCounters = 16, kCtlWords = 32 };
-
 // How long the waiting waves of this file poll before they give up and REPORT instead of hanging the device, in polls. A
 // timeout sets ctl[kCtlError]; split_join_kernel (always the last kernel of a sort on the caller's stream) turns that into
 // "no runs" (*n_unique = 0: the optimizer step that follows leaves the table alone) and a word in pinned host memory that the
-// host looks at when it next synchronises or enters the library (optim.hip: sort_lane::take_error): a stall is an ERROR CODE,
+// host looks at when it next synchronises or enters the library (dedup.hip: sort_lane::take_error): a stall is an ERROR CODE,
 // never a silently wrong step. stall_bucket (tests only, WM_DEBUG_STALL=lookback): the bucket of stage 2 that never publishes.
 struct wait_cfg {
   uint32_t look_back_polls = 1u << 24;   // x ~0.3 us: a bucket takes 20 us, its predecessors a few rounds of that
@@ -889,11 +881,11 @@ int launch(const plan& p, const UKey* ids, int64_t n, UKey key_lower_bound, uint
 }
 
 // The LAST kernel of a sort on the caller's stream: one wave that returns at once in the usual case. When the generic path
-// runs on a side stream and is not joined by an event before the step (optim.hip: deferred join) and the batch overflowed, it
+// runs on a side stream and is not joined by an event before the step (dedup.hip: deferred join) and the batch overflowed, it
 // waits until the generic path's closing kernel has counted itself in. Then it publishes "the runs are final" — or, when any
 // wait of this sort timed out (ctl[kCtlError], which the generic path's closing kernel also folds the onesweep passes' word
 // into), "the sort FAILED": kCtlSortDone = 2, *n_unique = 0 (every consumer reads its run count there: the step that follows
-// does nothing) and the code in *host_err (pinned host memory; optim.hip reports it at the next synchronise / entry).
+// does nothing) and the code in *host_err (pinned host memory; dedup.hip reports it at the next synchronise / entry).
 __global__ void split_join_kernel(uint32_t* ctl, uint32_t expected_blocks, uint32_t join_polls, int64_t* n_unique, uint32_t* host_err)
 {
   if (ctl[kCtlOverflow] != 0) {
@@ -923,7 +915,7 @@ __global__ void split_join_kernel(uint32_t* ctl, uint32_t expected_blocks, uint3
 // A side stream's way to wait for a word another stream's kernel sets (no event on that stream: an event record between two
 // kernels of the caller's stream costs ~7 us of its critical path). One wave, polling far apart. A timeout (about a minute: the
 // kernel waited for was SUBMITTED before this one, so only a tool that runs one kernel at a time, out of submission order, can
-// get here — optim.hip: device_waits_allowed) goes to error_word and to *host_err.
+// get here — dedup.hip: device_waits_allowed) goes to error_word and to *host_err.
 __global__ void split_wait_kernel(const uint32_t* word, uint32_t value, uint32_t* error_word, uint32_t wait_polls, uint32_t* host_err)
 {
   unsigned spins = 0;
@@ -942,7 +934,7 @@ __global__ void split_wait_kernel(const uint32_t* word, uint32_t value, uint32_t
 }
 
 // The first two kernels alone, as a PROBE: "would a split sort of this batch overflow a bucket?" — for a caller that has routed
-// a run of skewed batches to another sort and wants to know when the batches stop being skewed (optim.hip: run_dedup).
+// a run of skewed batches to another sort and wants to know when the batches stop being skewed (dedup.hip: run_dedup).
 // probe_ws: probe_workspace_bytes() bytes of the caller's; the answer is the word probe_overflow_word() points at.
 inline size_t probe_workspace_bytes()
 {

@@ -15,6 +15,8 @@
  *      backward).
  *      (2d) the neighbour aggregation of (2b) with a weight per edge (forward, and deterministic gradients into the rows
  *      and into the weights).
+ *      (2g) the GATv2 ("dynamic") multi-head graph attention of a sampled CSC block behind the GATv2 layer (forward and a
+ *      deterministic backward).
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -660,6 +662,89 @@ enum wholememory_error_code_t wholememory_ext_csc_gat_edge_backward(const int32_
                                                                     int64_t grad_ef_stride,
                                                                     struct wholememory_env_func_t* p_env_fns,
                                                                     void* stream);
+
+/* ---- (2g) GATv2 multi-head graph attention of a sampled CSC block (`mha_gat_v2_n2n`) ---------------------------------- */
+/* The block as for (2b): row_ptr int32 [n_dst + 1], col_ind int32 [n_edges] in [0, n_src). h_src fp32 [n_src, h_src_stride]
+ * with H * F columns used (H = heads, F = dim; the layer's lin_src(x)); h_dst fp32 [n_dst, h_dst_stride] with H * F columns
+ * used: row d belongs to target d (the layer's lin_dst(x[:n_dst])). Head k owns the columns [k*F, (k+1)*F) of a row. att
+ * fp32 [H * F], viewed as (H, F). Strides in elements, all arrays DEVICE memory, all work queued on `stream`.
+ * The contract of (2c): every `*` and `+` below is one fp32 operation, rounded on its own (no fused multiply-add), no
+ * atomics, one fixed order for every sum, results bitwise reproducible. A sum "left to right" starts from its first term; a
+ * sum with no term is +0.0. "Tree sum over f" of terms q[f] is the balanced binary tree of adjacent pairs of (2d): with Fp
+ * the smallest power of two >= F and q[f] = +0.0 for F <= f < Fp, q1[i] = q[2i] + q[2i+1], q2[i] = q1[2i] + q1[2i+1], ...
+ * until one value is left (Fp = 1: q[0] itself). The tree does not depend on how the kernel is launched.
+ *
+ * forward: writes alpha [n_edges, H] and out. For edge e of target d (e = row_ptr[d] .. row_ptr[d+1] - 1), head k,
+ * j = col_ind[e]:
+ *   u[f] = h_src[j,k,f] + h_dst[d,k,f]; v[f] = u[f] > 0 ? u[f] : negative_slope * u[f].
+ *   l[e,k] = tree sum over f of att[k,f] * v[f].
+ *   m = max of l over the edges of d; w = expf(l - m) (the device's expf); den = sum of w over the edges of d, left to
+ *   right; alpha[e,k] = w / den: exactly as (2c).
+ *   o[d,k,:] = sum of alpha[e,k] * h_src[j,k,:] over the edges of d, left to right; +0.0 for a target without edges.
+ *   concat != 0: out [n_dst, out_stride >= H*F] = o. concat == 0: out [n_dst, out_stride >= F] =
+ *   ((o[d,0,:] + o[d,1,:]) + ...) * fl(1.0f / H).
+ * backward: grad_out G [n_dst, grad_out_stride] (H*F columns with concat, else F) -> grad_h_src [n_src, grad_h_src_stride
+ * >= H*F] (every row written), grad_h_dst [n_dst, grad_h_dst_stride >= H*F] (every row written) and grad_att [H*F]. Each of
+ * the three may be null and is then not computed (nothing is queued for it); all three null is INVALID_INPUT.
+ *   G_k[d,f] = G[d, k*F + f] with concat, else G[d,f] * fl(1.0f / H).
+ *   da[e,k] = tree sum over f of G_k[d,f] * h_src[j,k,f]. c[d,k] = sum of alpha[e,k] * da[e,k] over the edges of d, left to
+ *   right. dl[e,k] = alpha[e,k] * (da[e,k] - c[d,k]).
+ *   g[f] = u[f] > 0 ? att[k,f] : att[k,f] * negative_slope (u recomputed); du[e,k,f] = dl[e,k] * g[f].
+ *   grad_h_dst[d,k,f] = sum of du[e,k,f] over the edges of d, left to right; +0.0 without edges.
+ *   grad_h_src[j,k,:] = sum over the edges with col_ind[e] = j, in ascending edge position, of
+ *   (alpha[e,k] * G_k[d(e),:]) + du[e,k,:]: left to right when j has at most C edges, otherwise cut into consecutive chunks
+ *   of C edges, each chunk summed left to right and the chunk sums added in chunk order, exactly as (2b), with
+ *   C = wholememory_ext_csc_aggregate_chunk_edges(). A source without edges gets +0.0.
+ *   grad_att[k,f]: first, per target, A(d)[k,f] = sum over its edges, left to right, of dl[e,k] * v[f] (v of that edge;
+ *   +0.0 without edges). Then the A(d) are summed over d in node chunks of N = wholememory_ext_csc_gat_node_chunk() rows
+ *   from row 0: each chunk left to right, the chunk sums added in chunk order.
+ *   The edge index of grad_h_src is built with the library's id sort, scratch from p_env_fns.
+ * n_edges = 0 and n_dst = 0 are valid. INVALID_INPUT, before any device work, for whatever (2c) rejects (null pointers,
+ * negative sizes, heads < 1, dim < 1, n_dst > n_src, strides smaller than the row) and for a null h_dst with n_dst > 0;
+ * NOT_SUPPORTED (nothing queued) when the device backend has no such kernels. */
+enum wholememory_error_code_t wholememory_ext_csc_gatv2_forward(const int32_t* row_ptr,
+                                                                const int32_t* col_ind,
+                                                                int64_t n_edges,
+                                                                int64_t n_dst,
+                                                                int64_t n_src,
+                                                                const float* h_src,
+                                                                int64_t h_src_stride,
+                                                                const float* h_dst,
+                                                                int64_t h_dst_stride,
+                                                                const float* att,
+                                                                int64_t heads,
+                                                                int64_t dim,
+                                                                float negative_slope,
+                                                                int concat,
+                                                                float* out,
+                                                                int64_t out_stride,
+                                                                float* alpha,
+                                                                struct wholememory_env_func_t* p_env_fns,
+                                                                void* stream);
+enum wholememory_error_code_t wholememory_ext_csc_gatv2_backward(const int32_t* row_ptr,
+                                                                 const int32_t* col_ind,
+                                                                 int64_t n_edges,
+                                                                 int64_t n_dst,
+                                                                 int64_t n_src,
+                                                                 const float* h_src,
+                                                                 int64_t h_src_stride,
+                                                                 const float* h_dst,
+                                                                 int64_t h_dst_stride,
+                                                                 const float* att,
+                                                                 int64_t heads,
+                                                                 int64_t dim,
+                                                                 float negative_slope,
+                                                                 int concat,
+                                                                 const float* alpha,
+                                                                 const float* grad_out,
+                                                                 int64_t grad_out_stride,
+                                                                 float* grad_h_src,
+                                                                 int64_t grad_h_src_stride,
+                                                                 float* grad_h_dst,
+                                                                 int64_t grad_h_dst_stride,
+                                                                 float* grad_att,
+                                                                 struct wholememory_env_func_t* p_env_fns,
+                                                                 void* stream);
 
 /* ---- (3) testing seam ---------------------------------------------------------------------- */
 /* Replaces the device backend. Refuses (WHOLEMEMORY_NOT_SUPPORTED) unless the environment has

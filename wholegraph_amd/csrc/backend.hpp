@@ -290,6 +290,31 @@ struct wm_gat_edge_args {
   int64_t grad_ef_stride;
 };
 
+// GATv2 multi-head graph attention of a sampled CSC block (kernels/gatv2.hip, wholegraph_amd_ext.h section 2g): rows /
+// strides in ELEMENTS (fp32); head k owns columns [k * dim, (k + 1) * dim) of a row
+struct wm_gatv2_args {
+  const int32_t* row_ptr;   // [n_dst + 1]
+  const int32_t* col_ind;   // [n_edges], ids in [0, n_src)
+  int64_t n_edges, n_dst, n_src, heads, dim;
+  float slope;              // LeakyReLU negative slope
+  int concat;               // 1: out [n_dst, heads * dim]; 0: the mean over heads, [n_dst, dim]
+  const float* h_src;       // [n_src, h_src_stride], heads * dim columns used
+  int64_t h_src_stride;
+  const float* h_dst;       // [n_dst, h_dst_stride]: row d belongs to target d
+  int64_t h_dst_stride;
+  const float* att;         // [heads, dim]
+  float* alpha;             // [n_edges, heads]: written by the forward, read by the backward
+  float* out;               // forward: [n_dst, out_stride]
+  int64_t out_stride;
+  const float* grad;        // backward: dL/dout [n_dst, grad_stride]
+  int64_t grad_stride;
+  float* grad_h_src;        // backward: [n_src, grad_h_src_stride] or nullptr
+  int64_t grad_h_src_stride;
+  float* grad_h_dst;        // backward: [n_dst, grad_h_dst_stride] or nullptr
+  int64_t grad_h_dst_stride;
+  float* grad_att;          // backward: [heads * dim] or nullptr
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -519,6 +544,16 @@ struct wm_device_backend {
   size_t (*gat_edge_backward_workspace_bytes)(const wm_gat_edge_args* a);
   int (*gat_edge_backward)(const wm_gat_edge_args* a, const int32_t* order, const int32_t* run_starts,
                            const int32_t* unique_ids, const int64_t* n_unique_dev, void* workspace, void* stream);
+  // ---- GATv2 attention of a sampled CSC block (kernels/gatv2.hip, wholegraph_amd_ext.h section 2g); nullptr in a backend
+  // without it ----
+  // forward: alpha and out; workspace of gatv2_forward_workspace_bytes
+  size_t (*gatv2_forward_workspace_bytes)(const wm_gatv2_args* a);
+  int (*gatv2_forward)(const wm_gatv2_args* a, void* workspace, void* stream);
+  // backward: whichever of grad_h_src, grad_h_dst and grad_att is not null. The index of gat_backward (read for grad_h_src
+  // only: nullptr otherwise); workspace of gatv2_backward_workspace_bytes
+  size_t (*gatv2_backward_workspace_bytes)(const wm_gatv2_args* a);
+  int (*gatv2_backward)(const wm_gatv2_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                        const int64_t* n_unique_dev, void* workspace, void* stream);
 };
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // wholegraph_amd — host side of the multi-head graph attention of a sampled CSC block (wholegraph_amd_ext.h, section 2c,
-// and section 2f: the same op with an edge term in the logit): validation, scratch, the edge index of the backward (the
-// library's id sort over col_ind) and the launches of kernels/gat.hip / kernels/gat_edge.hip. The semantics, and the one
-// order of every fp32 sum, are stated in the header.
+// section 2f: the same op with an edge term in the logit, and section 2g: GATv2): validation, scratch, the edge index of the
+// backward (the library's id sort over col_ind) and the launches of kernels/gat.hip / kernels/gat_edge.hip /
+// kernels/gatv2.hip. The semantics, and the one order of every fp32 sum, are stated in the header.
 #include <wholememory/wholegraph_amd_ext.h>
 
 #include "csc_block.hpp"
@@ -45,6 +45,41 @@ wm_gat_args make_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_
   a.att      = att;
   a.alpha    = const_cast<float*>(alpha);    // (written by the forward only)
   a.scores   = const_cast<float*>(scores);   // (written by the forward only)
+  return a;
+}
+
+// what (2g) shares between its forward and backward: the checks of (2c), minus the scores, plus h_dst
+wm_gatv2_args make_v2_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src,
+                           const float* h_src, int64_t h_src_stride, const float* h_dst, int64_t h_dst_stride,
+                           const float* att, int64_t heads, int64_t dim, float slope, int concat, const float* alpha)
+{
+  auto bad = [](const char* what) { throw invalid_input(what); };
+  check_block(row_ptr, col_ind, n_edges, n_dst, n_src, n_edges > 0 && n_dst > 0, "h_src");
+  if (heads < 1) bad("heads must be >= 1");
+  if (dim < 1) bad("dim must be >= 1");
+  if (n_src > 0 && h_src == nullptr) bad("h_src is null");
+  if (n_dst > 0 && h_dst == nullptr) bad("h_dst is null");
+  if (att == nullptr) bad("att is null");
+  if (n_edges > 0 && n_dst > 0 && alpha == nullptr) bad("alpha is null");
+  if (h_src_stride < heads * dim) bad("h_src stride smaller than its row");
+  if (h_dst_stride < heads * dim) bad("h_dst stride smaller than its row");
+  if (heads * dim >= (int64_t(1) << 31)) bad("heads * dim too large");
+  wm_gatv2_args a{};
+  a.row_ptr      = row_ptr;
+  a.col_ind      = col_ind;
+  a.n_edges      = n_dst == 0 ? 0 : n_edges;   // (no target, no edge of any target)
+  a.n_dst        = n_dst;
+  a.n_src        = n_src;
+  a.heads        = heads;
+  a.dim          = dim;
+  a.slope        = slope;
+  a.concat       = concat ? 1 : 0;
+  a.h_src        = h_src;
+  a.h_src_stride = h_src_stride;
+  a.h_dst        = h_dst;
+  a.h_dst_stride = h_dst_stride;
+  a.att          = att;
+  a.alpha        = const_cast<float*>(alpha);   // (written by the forward only)
   return a;
 }
 
@@ -184,6 +219,66 @@ wholememory_error_code_t wholememory_ext_csc_gat_edge_backward(
   if (n_src > 0) sort_col_ind(&ix, col_ind, a.g.n_edges, n_src, stream);
   void* d_gws = gat_ws.device(static_cast<int64_t>(bk->gat_edge_backward_workspace_bytes(&a)), WHOLEMEMORY_DT_INT8);
   WM_BK(bk->gat_edge_backward(&a, ix.order, ix.starts, static_cast<const int32_t*>(ix.unique), ix.n_unique_dev, d_gws, stream));
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+wholememory_error_code_t wholememory_ext_csc_gatv2_forward(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges,
+                                                           int64_t n_dst, int64_t n_src, const float* h_src,
+                                                           int64_t h_src_stride, const float* h_dst, int64_t h_dst_stride,
+                                                           const float* att, int64_t heads, int64_t dim,
+                                                           float negative_slope, int concat, float* out, int64_t out_stride,
+                                                           float* alpha, wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  const auto* bk = backend();
+  wm_gatv2_args a = make_v2_args(row_ptr, col_ind, n_edges, n_dst, n_src, h_src, h_src_stride, h_dst, h_dst_stride, att,
+                                 heads, dim, negative_slope, concat, alpha);
+  if (n_dst > 0 && out == nullptr) throw invalid_input("out is null");
+  if (out_stride < (concat ? heads * dim : dim)) throw invalid_input("out stride smaller than its row");
+  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
+  // (after the checks: a malformed call is INVALID_INPUT under every backend)
+  if (bk->gatv2_forward == nullptr || bk->gatv2_forward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  a.out        = out;
+  a.out_stride = out_stride;
+  temp_mem ws(p_env_fns);
+  const size_t wb = bk->gatv2_forward_workspace_bytes(&a);
+  void* d_ws      = wb > 0 ? ws.device(static_cast<int64_t>(wb), WHOLEMEMORY_DT_INT8) : nullptr;
+  WM_BK(bk->gatv2_forward(&a, d_ws, stream));
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+wholememory_error_code_t wholememory_ext_csc_gatv2_backward(
+  const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src, const float* h_src,
+  int64_t h_src_stride, const float* h_dst, int64_t h_dst_stride, const float* att, int64_t heads, int64_t dim,
+  float negative_slope, int concat, const float* alpha, const float* grad_out, int64_t grad_out_stride, float* grad_h_src,
+  int64_t grad_h_src_stride, float* grad_h_dst, int64_t grad_h_dst_stride, float* grad_att,
+  wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  const auto* bk = backend();
+  wm_gatv2_args a = make_v2_args(row_ptr, col_ind, n_edges, n_dst, n_src, h_src, h_src_stride, h_dst, h_dst_stride, att,
+                                 heads, dim, negative_slope, concat, alpha);
+  if (n_dst > 0 && grad_out == nullptr) throw invalid_input("grad_out is null");
+  if (grad_out_stride < (concat ? heads * dim : dim)) throw invalid_input("grad_out stride smaller than its row");
+  if (grad_h_src == nullptr && grad_h_dst == nullptr && grad_att == nullptr) throw invalid_input("no gradient asked for");
+  if (grad_h_src != nullptr && grad_h_src_stride < heads * dim) throw invalid_input("grad_h_src stride smaller than its row");
+  if (grad_h_dst != nullptr && grad_h_dst_stride < heads * dim) throw invalid_input("grad_h_dst stride smaller than its row");
+  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
+  if (bk->gatv2_backward == nullptr || bk->gatv2_backward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  a.grad              = grad_out;
+  a.grad_stride       = grad_out_stride;
+  a.grad_h_src        = grad_h_src;
+  a.grad_h_src_stride = grad_h_src_stride;
+  a.grad_h_dst        = grad_h_dst;
+  a.grad_h_dst_stride = grad_h_dst_stride;
+  a.grad_att          = grad_att;
+  sorted_ids ix(p_env_fns);   // the edge index of grad_h_src; without that gradient, or without source rows: null pointers
+  temp_mem gat_ws(p_env_fns);
+  if (grad_h_src != nullptr && n_src > 0) sort_col_ind(&ix, col_ind, a.n_edges, n_src, stream);
+  void* d_gws = gat_ws.device(static_cast<int64_t>(bk->gatv2_backward_workspace_bytes(&a)), WHOLEMEMORY_DT_INT8);
+  WM_BK(bk->gatv2_backward(&a, ix.order, ix.starts, static_cast<const int32_t*>(ix.unique), ix.n_unique_dev, d_gws, stream));
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }

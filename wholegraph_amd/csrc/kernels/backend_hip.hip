@@ -91,6 +91,11 @@ int hip_gat_edge_forward(const wm_gat_edge_args* a, void* workspace, void* strea
 size_t hip_gat_edge_backward_workspace_bytes(const wm_gat_edge_args* a);
 int hip_gat_edge_backward(const wm_gat_edge_args* a, const int32_t* order, const int32_t* run_starts,
                           const int32_t* unique_ids, const int64_t* n_unique_dev, void* workspace, void* stream);
+size_t hip_gatv2_forward_workspace_bytes(const wm_gatv2_args* a);
+int hip_gatv2_forward(const wm_gatv2_args* a, void* workspace, void* stream);
+size_t hip_gatv2_backward_workspace_bytes(const wm_gatv2_args* a);
+int hip_gatv2_backward(const wm_gatv2_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                       const int64_t* n_unique_dev, void* workspace, void* stream);
 
 namespace {
 
@@ -274,6 +279,10 @@ const wm_device_backend kHipBackend = {
   hip_gat_edge_forward,
   hip_gat_edge_backward_workspace_bytes,
   hip_gat_edge_backward,
+  hip_gatv2_forward_workspace_bytes,
+  hip_gatv2_forward,
+  hip_gatv2_backward_workspace_bytes,
+  hip_gatv2_backward,
 };
 
 }  // namespace

@@ -1,7 +1,8 @@
 """Layers of the ``cugraph`` framework route (``gnn_model.set_framework("cugraph")``), on the HIP aggregation ops."""
 from .edge_gat_conv import EdgeGATConv
 from .gat_conv import CuGraphGATConv
+from .gatv2_conv import GATv2Conv
 from .sage_conv import CuGraphSAGEConv
 from .weighted_sage_conv import EdgeWeightedSAGEConv
 
-__all__ = ["CuGraphSAGEConv", "CuGraphGATConv", "EdgeGATConv", "EdgeWeightedSAGEConv"]
+__all__ = ["CuGraphSAGEConv", "CuGraphGATConv", "EdgeGATConv", "GATv2Conv", "EdgeWeightedSAGEConv"]

@@ -1,7 +1,8 @@
 """The GNN model surface of ``pylibwholegraph.torch.gnn_model`` (``set_framework``, ``create_gnn_layers``,
 ``create_sub_graph``, ``layer_forward``, ``HomoGNNModel``) for the ``cugraph`` framework route with GraphSAGE layers, on the
-HIP aggregation op (``aggregation.py``). The dgl / pyg / wg routes and GAT models are not part of this build (the GAT
-layer itself is ``cugraphops.CuGraphGATConv``).
+HIP aggregation op (``aggregation.py``), and with GATv2 layers (model "gatv2": ``cugraphops.GATv2Conv`` on
+``gatv2_aggregation.py``). The dgl / pyg / wg routes and the model "gat" are not part of this build (the GAT layer itself is
+``cugraphops.CuGraphGATConv``).
 
 Flow of ``HomoGNNModel.forward`` (the reference's): sample ``layernum`` hops from the seed ids, gather the float32
 features of the outermost frontier through ``WholeMemoryEmbeddingModule`` (so the embedding receives gradients), then one
@@ -49,13 +50,17 @@ def create_gnn_layers(in_feat_dim, hidden_feat_dim, class_count, num_layer, num_
     _require_framework()
     if model_type == "gat":
         raise NotImplementedError("model 'gat' is not implemented on the cugraph route yet (only 'sage')")
-    if model_type != "sage":
-        raise ValueError("model %r is not available on the cugraph route (only 'sage')" % (model_type,))
+    if model_type not in ("sage", "gatv2"):
+        raise ValueError("model %r is not available on the cugraph route (only 'sage' and 'gatv2')" % (model_type,))
     gnn_layers = torch.nn.ModuleList()
     for i in range(num_layer):
         layer_output_dim = hidden_feat_dim // num_head if i != num_layer - 1 else class_count
         layer_input_dim = in_feat_dim if i == 0 else hidden_feat_dim
-        gnn_layers.append(SAGEConv(layer_input_dim, layer_output_dim))
+        if model_type == "gatv2":   # (the reference's flow for "gat": heads concatenated, averaged in the last layer)
+            from .cugraphops.gatv2_conv import GATv2Conv
+            gnn_layers.append(GATv2Conv(layer_input_dim, layer_output_dim, heads=num_head, concat=i != num_layer - 1))
+        else:
+            gnn_layers.append(SAGEConv(layer_input_dim, layer_output_dim))
     return gnn_layers
 
 
@@ -85,13 +90,16 @@ class HomoGNNModel(torch.nn.Module):
         self.node_embedding = node_embedding
         self.num_layer = args.layernum
         self.hidden_feat_dim = args.hiddensize
-        num_head = args.heads if args.model == "gat" else 1
+        attention = args.model in ("gat", "gatv2")
+        if args.model == "gatv2" and getattr(args, "fuse_gather", False):
+            raise ValueError("fuse_gather reads layer 0's rows from the table: GraphSAGE only, not model 'gatv2'")
+        num_head = args.heads if attention else 1
         assert hidden_feat_dim % num_head == 0
         in_feat_dim = self.node_embedding.shape[1]
         self.gnn_layers = create_gnn_layers(in_feat_dim, hidden_feat_dim, args.classnum, args.layernum, num_head,
                                             args.model)
-        self.mean_output = args.model == "gat"
-        self.add_self_loop = args.model == "gat"
+        self.mean_output = attention
+        self.add_self_loop = attention
         self.gather_fn = WholeMemoryEmbeddingModule(self.node_embedding)
         self.dropout = args.dropout
         self.max_neighbors = parse_max_neighbors(args.layernum, args.neighbors)

@@ -421,12 +421,16 @@ def scenario_tree_fold(comm, rank, world, mt, kind, params):
             rank_grads.append(g.integers(-2, 3, (len(ix), dim)).astype(np.float32))
         emb.add_gradients(dev(torch.from_numpy(rank_idx[rank])), dev(torch.from_numpy(rank_grads[rank])))
         emb.need_apply = True
-        g0 = wmb.lib().wholememory_ext_gradient_exchange_launches()
+        g0, c0 = wmb.lib().wholememory_ext_gradient_exchange_launches(), wmb.lib().wholememory_ext_combined_gradient_calls()
         if step == 2 and world > 2:
             os.environ["WM_EXCHANGE_PER_PEER"] = "1"   # the last step with the per-peer line-ups of rounds 1-5: the same bits
             _reload_knobs()
         opt.step(0.05)
         queued = wmb.lib().wholememory_ext_gradient_exchange_launches() - g0
+        # WM_GRAD_COMBINE is unset: batches of ~5000 ids are under WM_GATHER_DEDUP_MIN_IDS, publish a duplicate estimate of 0 and
+        # never combine by themselves — this scenario is the owner-side tree fold of every copy
+        took = wmb.lib().wholememory_ext_combined_gradient_calls() - c0
+        assert took == 0, "tree fold scenario took the combined route %d times on step %d" % (took, step)
         chunks = int(os.environ.get("WM_EXCHANGE_CHUNKS", "1"))
         if step == 2 and world > 2:
             del os.environ["WM_EXCHANGE_PER_PEER"]
@@ -537,6 +541,207 @@ def scenario_combined_gradients(comm, rank, world, mt, kind, params, tdt=torch.f
     _reload_knobs()
     wgth.destroy_wholememory_optimizer(opt)
     wgth.destroy_embedding(emb)
+
+
+_DENSE_LENGTHS = (129, 130, 200, 300, 511, 512, 513, 600, 1024, 1025, 1100)   # both sides of kTreeMin = 128 and kTreeSeg = 512
+
+
+def _dense_batch(which, r, seed, n_rows, idt):
+    """Batches in which most ids are LONG runs (more than kTreeMin = 128 copies on every sender), so that the sender-side fold
+    lists about as many runs as the batch has distinct ids. The hot ids are the same on every rank and spread over the whole
+    table — every owner receives a partial row from every sender —; lengths, order and seeds differ per rank.
+    all_long: 64 ids, run lengths cycling through _DENSE_LENGTHS, a few -1 ids (~35 k rows).
+    mixed: 600 ids of 129 ... 260 copies plus 3000 single ids (~120 k rows)."""
+    g = np.random.default_rng(seed)
+    perm = np.random.default_rng(77).permutation(n_rows)             # (the same on every rank)
+    if which == "all_long":
+        hot = (np.arange(64) * (n_rows // 64) + 3).astype(np.int64)
+        lens = np.array([_DENSE_LENGTHS[(k + r) % len(_DENSE_LENGTHS)] for k in range(64)])
+        ix = np.concatenate([np.repeat(hot, lens), np.full(37 + r, -1, np.int64)])
+    else:
+        hot = perm[:600].astype(np.int64)
+        lens = 129 + (np.arange(600) * 7 + r) % 132
+        ix = np.concatenate([np.repeat(hot, lens), perm[600 + 300 * r:3600 + 300 * r].astype(np.int64)])
+    g.shuffle(ix)
+    return ix.astype(idt)
+
+
+def _sparse_int_grads(g, n, dim):
+    return g.choice(np.array([-1.0, 0.0, 1.0], np.float32), size=(n, dim), p=[0.02, 0.96, 0.02]).astype(np.float32)
+
+
+def _assert_exact_premise(rank_idx, rank_grads, n_rows, dim):
+    """what makes ANY association order give the same bits, in float32 and in the 16-bit exchange dtypes alike: every sender's
+    partial sum of an id is an integer of at most 128 (exact in bfloat16's 8 bits), the owner's total one of at most 256"""
+    total = np.zeros((n_rows, dim), np.float64)
+    for ix, gr in zip(rank_idx, rank_grads):
+        part = np.zeros((n_rows, dim), np.float64)
+        v = ix >= 0
+        np.add.at(part, ix[v].astype(np.int64), gr[v].astype(np.float64))
+        assert np.abs(part).max() <= 128, "partial sums too large for an exact 16-bit test: %g" % np.abs(part).max()
+        total += part
+    assert np.abs(total).max() <= 256, "totals too large for an exact 16-bit test: %g" % np.abs(total).max()
+
+
+class _ExactTable:
+    """an embedding of integers in [-8, 8] with its optimizer, and the ordered multi-rank oracle beside it (plus the table's
+    one rounding for 16-bit tables): the skeleton of scenario_combined_gradients"""
+
+    def __init__(self, comm, rank, world, mt, kind, params, tdt, n_rows, dim, seed):
+        self.rank, self.world, self.tdt, self.dim, self.n_rows, self.kind = rank, world, tdt, dim, n_rows, kind
+        self.f32 = tdt == torch.float32
+        self.lr = 0.5 if self.f32 else 2.0 ** -6
+        self.emb = wgth.create_embedding(comm, mt, "cuda", tdt, [n_rows, dim])
+        stride = self.emb.get_embedding_tensor().stride()[0]
+        init_t = torch.from_numpy(np.random.default_rng(seed).integers(-8, 9, (n_rows, dim)).astype(np.float32)).to(tdt)
+        padded = np.zeros((n_rows, stride), dtype=np.float32)
+        padded[:, :dim] = init_t.float().numpy()
+        self.tab = oracle.ShardedTable.from_full(padded, world, None)
+        self.tab.dim = dim
+        self.local, start = self.emb.get_embedding_tensor().get_local_tensor()
+        self.cnt = int(self.tab.entry_offsets[rank + 1] - self.tab.entry_offsets[rank])
+        self.local.copy_(dev(init_t[start:start + self.cnt]))
+        if HIP_MODE:
+            torch.cuda.synchronize()
+        comm.barrier()
+        self.opt = wgth.create_wholememory_optimizer(self.emb, kind, params)
+        self.ref_opts = [oracle.Optimizer(kind, int(self.tab.entry_offsets[r + 1] - self.tab.entry_offsets[r]), stride, **params)
+                         for r in range(world)]
+
+    def step(self, rank_idx, rank_grads, what):
+        """one optimizer step of every rank's batch; returns (bytes handed to the all-to-all-v, combined-route calls)"""
+        tdt, dim, rank = self.tdt, self.dim, self.rank
+        _assert_exact_premise(rank_idx, rank_grads, self.n_rows, dim)
+        b0, c0 = wmb.lib().wholememory_ext_alltoallv_bytes(), wmb.lib().wholememory_ext_combined_gradient_calls()
+        self.emb.add_gradients(dev(torch.from_numpy(rank_idx[rank])), dev(torch.from_numpy(rank_grads[rank]).to(tdt)))
+        self.emb.need_apply = True
+        self.opt.step(self.lr)
+        if HIP_MODE:
+            torch.cuda.synchronize()
+        sent = wmb.lib().wholememory_ext_alltoallv_bytes() - b0
+        took = wmb.lib().wholememory_ext_combined_gradient_calls() - c0
+        oracle.gradient_apply(self.tab, self.ref_opts, rank_idx, rank_grads, self.lr)
+        if not self.f32:
+            for r in range(self.world):
+                sh = self.tab.shards[r]
+                sh[:, :dim] = torch.from_numpy(sh[:, :dim].copy()).to(tdt).float().numpy()   # the table's one rounding
+        want = torch.from_numpy(self.tab.shards[rank][:self.cnt, :dim].copy()).to(tdt)
+        got = host(self.local)
+        same = got.numpy().tobytes() == want.numpy().tobytes() if self.f32 else torch.equal(got.view(torch.int16), want.view(torch.int16))
+        if not same:
+            bad = np.nonzero((got.float().numpy() != want.float().numpy()).any(axis=1))[0]
+            raise AssertionError("%s: table differs from the ordered oracle on rank %d in %d of %d rows (first local rows %s)"
+                                 % (what, rank, len(bad), self.cnt, bad[:8]))
+        return sent, took
+
+    def close(self, comm):
+        if self.kind == "adam":
+            m, _ = self.emb.get_optimizer_state("m").get_local_tensor()
+            assert host(m).numpy().tobytes() == self.ref_opts[self.rank].per_element[:self.cnt, :self.dim].tobytes(), "Adam's m differs"
+        comm.barrier()
+        wgth.destroy_wholememory_optimizer(self.opt)
+        wgth.destroy_embedding(self.emb)
+
+
+def scenario_combined_dense(comm, rank, world, mt, kind, params, tdt=torch.float32, idt=np.int64):
+    """The sender-side fold (embedding.cpp: combined_gradient_apply) on batches whose distinct ids are nearly all LONG runs:
+    the tree fold then lists about nu runs among n >> nu rows — 64 of 64 ids in `all_long`, 600 of 3600 in `mixed` — and its
+    workspace has to be carved by the ROWS of the batch (carved by nu it has room for 2 and 29 listed runs). Integer-valued
+    gradients with small partial sums (_assert_exact_premise): table and Adam's m equal the ORDERED multi-rank oracle bit for
+    bit, so a dropped, doubled or misplaced row shows. Per batch three steps: combined, uncombined (WM_GRAD_COMBINE=0: the same
+    bits, every copy travels), combined again; the combined steps hand fewer bytes to the all-to-all-v."""
+    n_rows, dim = 5003, 32
+    os.environ["WM_GRAD_FOLD"] = "tree"
+    _reload_knobs()
+    t = _ExactTable(comm, rank, world, mt, kind, params, tdt, n_rows, dim, seed=62)
+    exchanging = world > 1 or os.environ.get("WM_EXCHANGE_SELF") == "1"
+    for b, which in enumerate(("all_long", "mixed")):
+        sent = {}
+        for step in range(3):
+            combine = step != 1
+            os.environ["WM_GRAD_COMBINE"] = "1" if combine else "0"
+            _reload_knobs()
+            rank_idx, rank_grads = [], []
+            for r in range(world):
+                seed = 7000 + 100 * b + 10 * (step % 2) + r          # (steps 0 and 2 repeat one batch, step 1 is another of the same shape)
+                ix = _dense_batch(which, r, seed, n_rows, idt)
+                gr = _sparse_int_grads(np.random.default_rng(seed + 5000), len(ix), dim)
+                gr[ix < 0] = 3.0                                      # rows of "skip me" ids must not reach any sum
+                rank_idx.append(ix)
+                rank_grads.append(gr)
+            what = "combined dense (%s, %s, %s, %s) %s step %d" % (kind, mt, tdt, np.dtype(idt).name, which, step)
+            sent[step], took = t.step(rank_idx, rank_grads, what)
+            assert took == (1 if combine and exchanging else 0), "%s: combined route taken %d times" % (what, took)
+            comm.barrier()
+        if exchanging:   # every id is sent once instead of 129 ... 1100 times (mixed: 3600 rows instead of ~120 k)
+            assert sent[0] == sent[2] and sent[0] * 10 < sent[1], (which, sent)
+    del os.environ["WM_GRAD_FOLD"]
+    del os.environ["WM_GRAD_COMBINE"]
+    _reload_knobs()
+    t.close(comm)
+
+
+def scenario_combine_auto(comm, rank, world, tdt=torch.float32, fold_knob=True):
+    """The automatic decision for the sender-side combination (embedding.cpp: gather_gradient_apply — WM_GRAD_COMBINE unset):
+    every rank's duplicate estimate rides in the counts exchange and the mean is compared with WM_GRAD_COMBINE_PERMILLE
+    (default 100). Batches under WM_GATHER_DEDUP_MIN_IDS ids publish 0, so the limit is lowered to 0 here. The estimate is a
+    sampled one: only batches far from the threshold, the route asserted through the call counter, and the table bit-exact
+    against the ordered oracle either way — the declined legs go through the deferred ids exchange (finish_id_exchange).
+    fold_knob=False: no fold knob either — the default fold of the table's dtype (tree for 16-bit tables)."""
+    n_rows, dim = 5003, 32
+    if fold_knob:
+        os.environ["WM_GRAD_FOLD"] = "tree"
+    os.environ.pop("WM_GRAD_COMBINE", None)
+    os.environ["WM_GATHER_DEDUP_MIN_IDS"] = "0"
+    _reload_knobs()
+    t = _ExactTable(comm, rank, world, "distributed", "sgd", {"weight_decay": 0.0}, tdt, n_rows, dim, seed=63)
+    exchanging = world > 1 or os.environ.get("WM_EXCHANGE_SELF") == "1"
+
+    def batch(which, r):
+        g = np.random.default_rng(8000 + r)
+        if which == "distinct":
+            return g.permutation(n_rows)[:4000 + 9 * r].astype(np.int64)
+        if which == "all_long":
+            return _dense_batch("all_long", r, 8100 + r, n_rows, np.int64)
+        ix = g.integers(0, n_rows, 4000 + 9 * r).astype(np.int64)     # the half-hot batch of scenario_combined_gradients
+        ix[::2] = 17
+        ix[1::8] = n_rows - 2 - (r % 2)
+        ix[5::97] = -1
+        return ix
+
+    legs = [("distinct", None, 0), ("all_long", None, 1), ("half_hot", None, 1), ("half_hot", "900", 0)]
+    if not fold_knob:
+        legs = legs[1:]
+    for which, permille, want_taken in legs:
+        if permille is not None:
+            os.environ["WM_GRAD_COMBINE_PERMILLE"] = permille
+            _reload_knobs()
+        rank_idx = [batch(which, r) for r in range(world)]
+        rank_grads = [_sparse_int_grads(np.random.default_rng(8200 + r), len(rank_idx[r]), dim) for r in range(world)]
+        what = "automatic combination (%s, %s, threshold %s)" % (tdt, which, permille or "default")
+        _, took = t.step(rank_idx, rank_grads, what)
+        assert took == (want_taken if exchanging else 0), "%s: combined route taken %d times, expected %d" % (what, took, want_taken)
+        if permille is not None:
+            del os.environ["WM_GRAD_COMBINE_PERMILLE"]
+            _reload_knobs()
+        comm.barrier()
+    if fold_knob:
+        del os.environ["WM_GRAD_FOLD"]
+    del os.environ["WM_GATHER_DEDUP_MIN_IDS"]
+    _reload_knobs()
+    t.close(comm)
+
+
+def combined_dense_scenarios(comm, rank, world):
+    """WM_TEST_ONLY=combined_dense (tests/test_combined_fold_gpu.py): fp32 legs on either backend, the rest on the HIP one"""
+    scenario_combined_dense(comm, rank, world, "distributed", "sgd", {"weight_decay": 0.0})
+    scenario_combined_dense(comm, rank, world, "distributed", "adam", {"weight_decay": 0.01}, idt=np.int32)
+    scenario_combine_auto(comm, rank, world)
+    if HIP_MODE:
+        scenario_combined_dense(comm, rank, world, "distributed", "sgd", {"weight_decay": 0.0}, tdt=torch.float16)
+        scenario_combined_dense(comm, rank, world, "chunked", "sgd", {"weight_decay": 0.0}, tdt=torch.bfloat16, idt=np.int32)
+        scenario_combined_dense(comm, rank, world, "continuous", "rmsprop", {"alpha": 0.95})
+        scenario_combine_auto(comm, rank, world, tdt=torch.float16, fold_knob=False)
 
 
 def scenario_cached_embedding(comm, rank, world, mt):
@@ -849,6 +1054,15 @@ def main():
     wgth.init(rank, world, rank, world, os.environ.get("WM_TEST_LOG", "warn"))
     comm = wgth.get_global_communicator()
     assert comm.get_rank() == rank and comm.get_size() == world
+    if os.environ.get("WM_TEST_ONLY") == "combined_dense":   # only the sender-side fold's scenarios, on any backend / transport
+        if RCCL_MODE:
+            assert comm.transport() == ("rccl", world), comm.transport()
+        combined_dense_scenarios(comm, rank, world)
+        comm.barrier()
+        dist.barrier()
+        print("RANK %d OK" % rank)
+        wgth.finalize()
+        return
     if RCCL_MODE:
         rccl_scenarios(comm, rank, world)
         comm.barrier()

@@ -604,6 +604,132 @@ def test_tree_fold_stateful_optimizers_exact_on_integer_gradients(gpu_env, knobs
         assert d_pr.cpu().numpy().tobytes() == ref_opt.per_row.tobytes()
 
 
+# ---- the tree fold's workspace at its bounds (optim.hip: tree_bounds) --------------------------------------------------------
+# kTreeMin = 128: runs of more rows are listed; kTreeSeg = 512 rows per segment; kTreeMaxSegs = 256 segments per run. For n rows
+# the workspace has room for n / 129 + 2 listed runs and 2 (n / 512) + 2 partial rows (only runs of two or more segments park any).
+def _tree_exact_both_folds(wmb, torch, ids, grads, rows, dim, rng):
+    """one scatter-add (SGD, lr -1, wd 0) of integer-valued gradients through the tree fold and through the ordered one: both
+    equal the ordered oracle's bits; the tree step reports no run folded through a dense copy"""
+    stride = int(oracle.align_embedding_dim(dim, 4))
+    table = np.zeros((rows, stride), np.float32)
+    table[:, :dim] = rng.integers(-8, 9, (rows, dim)).astype(np.float32)
+    got, nu = _dedup_apply_sgd(wmb, torch, ids, grads, table, stride, dim, -1.0, "tree")
+    dense_after_tree = wmb.lib().wholememory_ext_dense_fold_last()
+    uniq, dg = oracle.dedup_grads(ids, grads)
+    ref = table.copy()
+    oracle.Optimizer("sgd", rows, stride).step(uniq, dg, ref, stride, 0, dim, -1.0)
+    assert nu == len(uniq)
+    assert got.tobytes() == ref.tobytes(), "tree fold differs from the exact integer sums"
+    assert dense_after_tree == 0, "a tree step reported %d runs folded through a dense copy" % dense_after_tree
+    ordered, _ = _dedup_apply_sgd(wmb, torch, ids, grads, table, stride, dim, -1.0, "ordered")
+    assert ordered.tobytes() == ref.tobytes()
+
+
+def _equal_runs(rng, rows, k, length):
+    ids = np.repeat(rng.choice(rows, k, replace=False).astype(np.int64), length)
+    rng.shuffle(ids)
+    return ids
+
+
+@pytest.mark.parametrize("length", [129, 130])
+def test_tree_fold_every_id_a_listed_run(gpu_env, length):
+    """400 ids of exactly 129 rows: n / (kTreeMin + 1) listed runs, the tight case of the list's bound (and of 130 rows)"""
+    import torch
+    from wholegraph_amd import binding as wmb
+    rng = np.random.default_rng(length)
+    rows, dim, k = 5003, 32, 400
+    ids = _equal_runs(rng, rows, k, length)
+    grads = rng.integers(-3, 4, (len(ids), dim)).astype(np.float32)
+    _tree_exact_both_folds(wmb, torch, ids, grads, rows, dim, rng)
+
+
+@pytest.mark.parametrize("dim", [32, 100])
+def test_tree_fold_every_run_of_two_segments(gpu_env, dim):
+    """100 ids of 513 rows: every run parks two partial rows — 200 of the 2 (n / 512) + 2 = 202 there is room for; 100 columns:
+    partial rows padded to whole 16-byte pieces (tree_dim_pad)"""
+    import torch
+    from wholegraph_amd import binding as wmb
+    rng = np.random.default_rng(513 + dim)
+    rows, k = 5003, 100
+    ids = _equal_runs(rng, rows, k, 513)
+    grads = rng.integers(-3, 4, (len(ids), dim)).astype(np.float32)
+    _tree_exact_both_folds(wmb, torch, ids, grads, rows, dim, rng)
+
+
+@pytest.mark.parametrize("hot,others", [(131_073, 2000), (300_000, 0)])
+def test_tree_fold_run_past_the_segment_cap(gpu_env, hot, others):
+    """one run of more than kTreeMaxSegs x kTreeSeg = 131072 rows: 256 segments of 513 rows (1172 rows for 300 000) instead of
+    more segments of 512. |sums| <= 3 x 300 000 < 2^24: exact."""
+    import torch
+    from wholegraph_amd import binding as wmb
+    rng = np.random.default_rng(hot)
+    rows, dim = 5003, 4
+    ids = np.concatenate([np.full(hot, 1234, np.int64), rng.integers(0, rows, others).astype(np.int64)])
+    rng.shuffle(ids)
+    grads = rng.integers(-3, 4, (len(ids), dim)).astype(np.float32)
+    _tree_exact_both_folds(wmb, torch, ids, grads, rows, dim, rng)
+
+
+def test_tree_fold_lazy_adam_every_id_a_listed_run(gpu_env, knobs):
+    """one LazyAdam step on the 400 x 130 batch: table, states and the per-row beta powers — advanced once per listed run by the
+    listing kernel — equal the ordered oracle bit for bit"""
+    import torch
+    from wholegraph_amd import binding as wmb
+    knobs.set("WM_GRAD_FOLD", "tree")
+    rng = np.random.default_rng(130)
+    local_rows, local_off, dim = 3001, 777, 32
+    ids = local_off + _equal_runs(rng, local_rows, 400, 130)
+    n_recv = len(ids)
+    grads = rng.integers(-2, 3, (n_recv, dim)).astype(np.float32)
+    table = rng.standard_normal((local_rows, dim)).astype(np.float32)
+    params = {"weight_decay": 0.01}
+    ref_opt = oracle.Optimizer("adam", local_rows, dim, **params)
+    d_table = torch.from_numpy(table.copy()).cuda()
+    d_pr = torch.ones((local_rows, 2), device="cuda")
+    d_pe = torch.zeros((local_rows, 2 * dim), device="cuda")
+    arr = (C.c_float * 6)(0.01, 1e-8, 0.9, 0.999, 0.99, 0.0)
+    env, stream = _env()
+    d_ids, d_grads = torch.from_numpy(ids).cuda(), torch.from_numpy(grads).cuda()
+    nu = C.c_int64(-1)
+    wmb.check(wmb.lib().wholememory_ext_dedup_apply(
+        d_ids.data_ptr(), wmb.DT_INT64, n_recv, d_grads.data_ptr(), dim, dim, d_table.data_ptr(), dim, local_off, local_rows, 2,
+        arr, 0.03, d_pe.data_ptr(), d_pr.data_ptr(), C.byref(nu), env, stream))
+    torch.cuda.synchronize()
+    assert wmb.lib().wholememory_ext_dense_fold_last() == 0
+    uniq, dg = oracle.dedup_grads(ids, grads)
+    assert nu.value == len(uniq) == 400
+    ref_table = table.copy()
+    ref_opt.step(uniq, dg, ref_table, dim, local_off, dim, 0.03)
+    assert d_table.cpu().numpy().tobytes() == ref_table.tobytes()
+    assert d_pe.cpu().numpy().tobytes() == ref_opt.per_element.tobytes()
+    assert d_pr.cpu().numpy().tobytes() == ref_opt.per_row.tobytes()
+
+
+def test_dense_fold_counter_follows_the_fold(gpu_env, knobs):
+    """wholememory_ext_dense_fold_last(): at least 1 after an ordered fp32 step whose hot runs go through a dense copy (the
+    batch of test_dense_fold_gpu.py), 0 after a tree step behind it — the tree fold's segment count must not show there"""
+    import torch
+    from wholegraph_amd import binding as wmb
+    rng = np.random.default_rng(5)
+    rows, n, dim = 20011, 60007, 128
+    ids = rng.integers(0, rows, n).astype(np.int64)
+    u = rng.random(n)
+    ids[u < 0.20] = 4242                          # ~12 k rows of one id
+    ids[(u >= 0.20) & (u < 0.21)] = 77            # ~600 rows: two segments for the tree fold
+    grads = rng.integers(-3, 4, (n, dim)).astype(np.float32)
+    table = np.zeros((rows, dim), np.float32)
+    knobs.unset("WM_DENSE_FOLD")
+    knobs.set("WM_DENSE_FOLD_MIN", 300)
+    # (the room for the copies is part of a step's scratch only while the device's recent steps listed long runs: the first call
+    # tells the second)
+    _dedup_apply_sgd(wmb, torch, ids, grads, table, dim, dim, -1.0, "ordered")
+    ordered, _ = _dedup_apply_sgd(wmb, torch, ids, grads, table, dim, dim, -1.0, "ordered")
+    assert wmb.lib().wholememory_ext_dense_fold_last() >= 1
+    tree, _ = _dedup_apply_sgd(wmb, torch, ids, grads, table, dim, dim, -1.0, "tree")
+    assert wmb.lib().wholememory_ext_dense_fold_last() == 0
+    assert tree.tobytes() == ordered.tobytes()
+
+
 @pytest.mark.parametrize("mt", ["chunked", "distributed"])
 @pytest.mark.parametrize("kind,params", [("sgd", {}), ("adam", {"weight_decay": 0.01})])
 def test_embedding_row_align_knob(gpu_env, knobs, tmp_path, mt, kind, params):

@@ -74,7 +74,8 @@ struct wm_optimizer_args {
   // of ids this rank owns itself, read where the caller left them instead of being copied into the receive buffer
   const void* self_grads;
   int64_t self_grad_stride;
-  int64_t count;               // number of unique ids (= grid size)
+  int64_t count;               // number of unique ids (= grid size); with n_unique_dev an UPPER BOUND of it — then the number of
+                               // gradient rows of the batch: the tree fold carves long_run_ws by it (optim.hip: tree_bounds)
   // optional device row cache of the local shard (kernels/cache.hip): row `local` lives in cache line cache_slot_of[local]
   // when that is >= 0 (the update then goes there and the line is marked modified), else in local_table
   const int32_t* cache_slot_of;
@@ -103,6 +104,11 @@ struct wm_optimizer_args {
   // sums are exactly representable). -1 = the backend's default for the value dtype (ordered for fp32, tree for the 16-bit
   // extension, WM_GRAD_FOLD=ordered|tree overrides).
   int fold_mode;
+  // 1: `order` and / or the gradient rows are complete only at this point of the caller's stream, LATER than the id sort that
+  // wrote the runs (positions of the caller's own rows remapped behind the sort — self_grads —, rows that arrive behind an
+  // event): work that the step puts on a stream of its own must then be ordered behind the caller's stream, not only behind
+  // the sort. 0: the sort's end is the last thing the step's inputs waited for.
+  int inputs_behind_sort;
 };
 
 // neighbour sampling on a CSR graph whose arrays are mapped (flat or chunked) in this process

@@ -288,6 +288,9 @@ void step_sorted(dedup_result& r, wholememory_dtype_t index_dtype, int64_t n_rec
   oa->long_run_ws_bytes = bk->long_run_workspace_bytes(n_recv, oa->dim);
   oa->long_run_ws       = long_ws.device(static_cast<int64_t>(oa->long_run_ws_bytes), WHOLEMEMORY_DT_INT8);
   if (rows_ready != nullptr) WM_BK(bk->stream_wait_event(stream, rows_ready));
+  // (both happen on the caller's stream BEHIND the sort: a long-run side that the backend orders behind the sort alone would
+  // read positions that are not remapped yet, or rows that have not arrived)
+  oa->inputs_behind_sort = (oa->self_grads != nullptr || rows_ready != nullptr) ? 1 : 0;
   int rc = bk->optimizer_step(oa, r.n_unique_dev, stream);
   const int join_rc = r.join();   // the sort's side stream, if it left one running: joined behind the step
   if (rc != 0) throw hip_error("optimizer_step failed");
@@ -464,7 +467,12 @@ int combined_gradient_apply(wholememory_embedding_* e, const char* idx_ptr, cons
     fa.type = WHOLEMEMORY_OPT_SGD, fa.lr = -1.0f, fa.weight_decay = 0.0f;
     fa.ids = iota, fa.index_dtype = iarr.dtype, fa.run_starts = r.starts, fa.order = r.order;
     fa.value_dtype = vdt, fa.grads = grads_ptr, fa.grad_stride = gmat.stride;
-    fa.count = nu, fa.local_table = partial, fa.table_stride = dim, fa.local_entry_offset = 0, fa.dim = dim;
+    // count = the batch's ROWS, as on the owner side (step_sorted): the backend takes it as an upper bound for its launch
+    // geometry AND carves the tree fold's workspace by it — a run is listed by its rows, so 64 ids of 300 copies are 64 listed
+    // runs, which a workspace carved for nu = 64 "rows" has no room for. The true number of runs is read on the device from
+    // n_unique_dev by every kernel of the step, so no run past nu is touched: `partial` (nu rows) and `iota` (nu ids) are
+    // addressed by run numbers below nu only.
+    fa.count = n, fa.local_table = partial, fa.table_stride = dim, fa.local_entry_offset = 0, fa.dim = dim;
     fa.fold_mode   = 1;
     fa.long_run_ws_bytes = bk->long_run_workspace_bytes(n, dim);
     fa.long_run_ws       = long_ws.device(static_cast<int64_t>(fa.long_run_ws_bytes), WHOLEMEMORY_DT_INT8);

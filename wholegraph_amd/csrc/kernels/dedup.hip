@@ -782,6 +782,11 @@ int hip_device_error()
 {
   const uint32_t e = sort_lane::get().take_error();
   if (e == 0) return 0;
+  if (e & split::kErrTreeBounds)
+    WM_ERROR("the tree fold of duplicate gradient rows listed more long runs or segments than its workspace was carved for (code "
+             "0x%x): the long runs of that optimizer step were NOT applied. The step's count must be the batch's number of "
+             "gradient rows.", e);
+  if ((e & ~split::kErrTreeBounds) == 0) return static_cast<int>(e);
   WM_ERROR("a device-side wait of the gradient path's id sort timed out (code 0x%x:%s%s%s%s): the optimizer step of that call was "
            "NOT applied (its run count was zeroed on the device). A tool that runs one kernel at a time (counter collection, some "
            "debuggers) stalls these waits: set WM_DEVICE_WAITS=0 for event-only synchronisation.",
@@ -909,6 +914,7 @@ std::unique_lock<std::mutex> lock_pending_join_side(hipStream_t* side)
   return lk;
 }
 hipError_t record_sort_joined(hipStream_t stream) { return hipEventRecord(sort_lane::get().joined, stream); }
+uint32_t* device_error_word() { return sort_lane::get().host_err_dev; }
 void enqueue_final_runs_wait(const uint32_t* ctl, hipStream_t stream)
 {
   hipLaunchKernelGGL(split::split_wait_kernel, dim3(1), dim3(64), 0, stream, ctl + split::kCtlSortDone, 1u,

@@ -1136,11 +1136,13 @@ struct long_lane {
       void* h = nullptr;
       if (hipHostMalloc(&h, 64, hipHostMallocDefault) != hipSuccess) return true;
       listed  = static_cast<volatile int32_t*>(h);
+      for (int i = 0; i < 16; i++) listed[i] = 0;   // (word 1 is read by wholememory_ext_dense_fold_last before any step has reported)
       *listed = 1;
     }
     return *listed != 0;
   }
-  // (two words: [0] the listed runs, [1] — ordered fold — how many of them went through a dense copy: wholememory_ext_dense_fold_last)
+  // (two words: [0] the listed runs, [1] how many of them went through a dense copy: wholememory_ext_dense_fold_last. The tree
+  // fold keeps its word 1 free — kTreeDenseWord — so a tree step reports 0 there)
   void report(const int32_t* long_count_dev, hipStream_t s)
   {
     if (listed != nullptr)
@@ -1202,8 +1204,12 @@ struct tree_seg {
   int32_t run_slot;  // index into the listed runs
   int32_t seg;       // segment number inside the run
 };
+// the tree fold's counters. Word 1 stays zero: long_lane::report copies words 0 and 1 to the host, and word 1 there is "runs
+// folded through a dense copy" (wholememory_ext_dense_fold_last) — none on a tree step
+enum { kTreeRuns = 0, kTreeDenseWord = 1, kTreeSegs = 2, kTreePartials = 3, kTreeMulti = 4 };
 struct tree_ws_view {
-  int32_t* counters;       // [0] listed runs, [1] segments, [2] partial rows, [3] runs of several segments
+  int32_t* counters;       // [kTreeRuns] listed runs, [kTreeSegs] segments, [kTreePartials] partial rows, [kTreeMulti] runs of several segments
+  uint32_t* error_word;    // pinned host word of the device-side errors (sort_handoff.cuh: device_error_word), or nullptr
   tree_run* runs;
   int32_t* multi;          // slots of the runs of several segments (what tree_combine_kernel walks)
   tree_seg* segs;
@@ -1211,6 +1217,9 @@ struct tree_ws_view {
   int64_t max_runs, max_segs, max_partials;
 };
 __host__ __device__ inline int64_t tree_dim_pad(int64_t dim) { return (dim + 3) / 4 * 4; }
+// n_recv is the number of GRADIENT ROWS of the batch (not of its distinct ids): a run is listed when it has more than `threshold`
+// rows, so at most n_recv / (threshold + 1) runs are; a run of len rows has at most len / kTreeSeg + 1 segments, and two or
+// more only from kTreeSeg + 1 rows on, then at most 2 len / kTreeSeg
 inline void tree_bounds(int64_t n_recv, int threshold, int64_t* max_runs, int64_t* max_segs, int64_t* max_partials)
 {
   *max_runs     = n_recv / (threshold + 1) + 2;
@@ -1227,6 +1236,7 @@ inline size_t tree_ws_bytes(int64_t n_recv, int64_t dim, int threshold)
 inline tree_ws_view tree_ws_carve(void* ws, int64_t n_recv, int threshold)
 {
   tree_ws_view v;
+  v.error_word = nullptr;
   tree_bounds(n_recv, threshold, &v.max_runs, &v.max_segs, &v.max_partials);
   char* p    = static_cast<char*>(ws);
   v.counters = reinterpret_cast<int32_t*>(p);
@@ -1240,6 +1250,13 @@ inline tree_ws_view tree_ws_carve(void* ws, int64_t n_recv, int threshold)
   p = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(p) + 63) & ~uintptr_t(63));
   v.partials = reinterpret_cast<float*>(p);
   return v;
+}
+
+// did every entry that tree_mark_kernel counted fit its array? (false: some were not written — the list counts as empty)
+__device__ inline bool tree_list_fits(const tree_ws_view& w)
+{
+  return w.counters[kTreeRuns] <= w.max_runs && w.counters[kTreeSegs] <= w.max_segs && w.counters[kTreePartials] <= w.max_partials &&
+         w.counters[kTreeMulti] <= w.max_runs;
 }
 
 // lists the runs of more than `threshold` rows with their segments. One lane per run finds and registers it (the beta powers of
@@ -1296,11 +1313,11 @@ __global__ __launch_bounds__(256) void tree_mark_kernel(opt_params p, tree_ws_vi
     const int tot_all = __shfl(incl_all, 63, 64), tot_multi = __shfl(incl_multi, 63, 64);
     int b0 = 0, b1 = 0, b2 = 0, b3 = 0;
     if (lane == 0) {
-      b0 = atomicAdd(&w.counters[0], __popcll(lmask));
-      b1 = atomicAdd(&w.counters[1], tot_all);
+      b0 = atomicAdd(&w.counters[kTreeRuns], __popcll(lmask));
+      b1 = atomicAdd(&w.counters[kTreeSegs], tot_all);
       if (mmask != 0) {
-        b2 = atomicAdd(&w.counters[2], tot_multi);
-        b3 = atomicAdd(&w.counters[3], __popcll(mmask));
+        b2 = atomicAdd(&w.counters[kTreePartials], tot_multi);
+        b3 = atomicAdd(&w.counters[kTreeMulti], __popcll(mmask));
       }
     }
     b0 = __shfl(b0, 0, 64), b1 = __shfl(b1, 0, 64), b2 = __shfl(b2, 0, 64), b3 = __shfl(b3, 0, 64);
@@ -1308,8 +1325,22 @@ __global__ __launch_bounds__(256) void tree_mark_kernel(opt_params p, tree_ws_vi
       slot            = b0 + __popcll(lmask & below);
       sbase           = b1 + incl_all - nseg;
       const int pbase = is_multi ? b2 + incl_multi - nseg : -1;
-      w.runs[slot]    = tree_run{static_cast<int32_t>(u), beta1t, beta2t, pbase, seg_rows, nseg, {0, 0}};
-      if (is_multi) w.multi[b3 + __popcll(mmask & below)] = slot;
+      const int mslot = is_multi ? b3 + __popcll(mmask & below) : 0;
+      // The workspace was carved for a number of gradient rows (tree_bounds); a caller that hands over a smaller number than the
+      // batch has makes the arrays too short, and they lie one behind the other. An entry that does not fit is NOT written and
+      // the error word is set (the call ends in WHOLEMEMORY_CUDA_ERROR: backend device_error). The counters only ever grow, so
+      // their final values are past the bounds as well and the kernels behind this one take the list for empty
+      // (tree_list_fits) — a wave that zeroed them here would race with the waves that still add to them.
+      const bool fits = slot < w.max_runs && static_cast<int64_t>(sbase) + nseg <= w.max_segs &&
+                        (!is_multi || (static_cast<int64_t>(pbase) + nseg <= w.max_partials && mslot < w.max_runs));
+      if (fits) {
+        w.runs[slot] = tree_run{static_cast<int32_t>(u), beta1t, beta2t, pbase, seg_rows, nseg, {0, 0}};
+        if (is_multi) w.multi[mslot] = slot;
+      } else {
+        slot = -1;   // (no segment entries either)
+        if (w.error_word != nullptr)
+          __hip_atomic_fetch_or(w.error_word, static_cast<uint32_t>(split::kErrTreeBounds), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      }
     }
   }
   uint64_t pending = __ballot(slot >= 0);
@@ -1336,7 +1367,7 @@ __global__ __launch_bounds__(kBlock) void tree_fold_kernel(opt_params p, tree_ws
   __shared__ float red[kBlock * kVE];
   const wm_optimizer_args& a = p.a;
   const IdxT* ids            = static_cast<const IdxT*>(a.ids);
-  const int n_seg            = w.counters[1];
+  const int n_seg            = tree_list_fits(w) ? w.counters[kTreeSegs] : 0;
   const int pieces           = static_cast<int>(a.dim / kVE);          // 16-byte pieces per row (the launcher checks dim % kVE == 0)
   int lpr                    = 1;
   while (lpr < pieces && lpr < kBlock) lpr <<= 1;                       // pieces handled per pass, a power of two <= 256
@@ -1410,7 +1441,7 @@ __global__ __launch_bounds__(kBlock) void tree_combine_kernel(opt_params p, tree
 {
   const wm_optimizer_args& a = p.a;
   const IdxT* ids            = static_cast<const IdxT*>(a.ids);
-  const int n_multi          = w.counters[3];
+  const int n_multi          = tree_list_fits(w) ? w.counters[kTreeMulti] : 0;
   const int64_t dpad         = tree_dim_pad(a.dim);
   for (int mi = blockIdx.x; mi < n_multi; mi += gridDim.x) {
     const tree_run ent = w.runs[w.multi[mi]];
@@ -1441,11 +1472,14 @@ inline int resolve_fold_mode(const wm_optimizer_args& a)
   return (a.value_dtype == WHOLEMEMORY_DT_HALF || a.value_dtype == WHOLEMEMORY_DT_BF16) ? 1 : 0;
 }
 
+// p.a.count must be (an upper bound of) the batch's GRADIENT ROWS here: the workspace is carved by it
 template <typename IdxT, int OPT, typename T>
-void launch_tree(const opt_params& p, hipStream_t stream, hipStream_t lstream)
+int launch_tree(const opt_params& p, hipStream_t stream, hipStream_t lstream)
 {
+  if (p.a.long_run_ws_bytes < tree_ws_bytes(p.a.count, p.a.dim, p.long_threshold)) return -2;   // (a workspace sized for another count)
   wait_for_final_runs(p, lstream);
   tree_ws_view w = tree_ws_carve(p.a.long_run_ws, p.a.count, p.long_threshold);
+  w.error_word   = device_error_word();
   if (p.split_ctl != nullptr) w.counters = p.long_count;   // (the split sort's control words: already zero)
   // one run per thread, no grid-stride loop: the grid must cover every run (callers keep count below 2^31 -> at most 2^23 blocks)
   const int mblocks    = static_cast<int>(std::min<int64_t>((p.a.count + 255) / 256, INT64_C(1) << 23));
@@ -1456,6 +1490,7 @@ void launch_tree(const opt_params& p, hipStream_t stream, hipStream_t lstream)
   }
   hipLaunchKernelGGL((tree_fold_kernel<IdxT, OPT, T>), dim3(2048), dim3(kBlock), 0, lstream, p, w);
   hipLaunchKernelGGL((tree_combine_kernel<IdxT, OPT, T>), dim3(256), dim3(kBlock), 0, lstream, p, w);
+  return 0;
 }
 
 // Launch shape of step_tile_kernel: round 2's persistent grid of 8192 workgroups over tiles of 64 runs. (The in-order shape
@@ -1479,7 +1514,7 @@ int launch_step_opt(const opt_params& p, int blocks, hipStream_t stream, hipStre
   // side is detached (nothing expected there, the caller's stream does not wait for it): then the tile kernel is enqueued first
   auto long_side = [&]() -> int {
     if (p.long_list != nullptr && p.fold_tree) {
-      launch_tree<IdxT, OPT, float>(p, stream, lstream);
+      if (launch_tree<IdxT, OPT, float>(p, stream, lstream) != 0) return -2;
     } else if (p.long_list != nullptr) {
       launch_mark_long_runs<IdxT>(p, stream, lstream);
       const int slices = static_cast<int>((p.a.dim + kSliceCols - 1) / kSliceCols);
@@ -1611,7 +1646,7 @@ int launch_step_sgd16(opt_params p, int blocks, hipStream_t stream, hipStream_t 
   if (!rows16) p.long_list = nullptr;  // no LDS-DMA path for this shape: the wave-per-run kernel folds every run itself
   auto long_side = [&]() -> int {   // (first, or behind the tile kernel when detached: launch_step_opt)
     if (p.long_list != nullptr && p.fold_tree) {
-      launch_tree<IdxT, kOpt, T>(p, stream, lstream);
+      if (launch_tree<IdxT, kOpt, T>(p, stream, lstream) != 0) return -2;
     } else if (p.long_list != nullptr) {
       static const bool lds_ok =
         hipFuncSetAttribute(reinterpret_cast<const void*>(&step_long4_kernel<IdxT, kOpt, T>),
@@ -1828,6 +1863,15 @@ int hip_optimizer_step_dev(const wm_optimizer_args* a, const int64_t* n_unique_d
   // the tile kernel)
   const bool detached = sort_lock.owns_lock();
   p.detached_side     = detached ? 1 : 0;
+  // The detached side is ordered behind the sort ("runs are final"). Where the caller completed the step's inputs behind the
+  // sort (wm_optimizer_args::inputs_behind_sort: own rows' positions remapped in order[], rows arriving behind an event), the
+  // side also waits for this point of the caller's stream — a wrong guess then still costs time only: without this its fold read
+  // order[] while the remap kernel was still to run (multi-rank tree fold of a batch of 65536 ids or more, right after a step
+  // that listed nothing: sums over receive-buffer rows that are never filled). The caller's stream itself waits for nothing.
+  if (detached && a->inputs_behind_sort != 0 &&
+      (hipEventRecord(long_lane::get().forked, stream) != hipSuccess ||
+       hipStreamWaitEvent(lstream, long_lane::get().forked, 0) != hipSuccess))
+    return -2;
   if (p.long_list != nullptr && !serial && long_lane::get().fork(stream)) lstream = long_lane::get().stream;
   // (the counters are cleared on the side stream: only the long-run kernels read them)
   if (p.long_list != nullptr && p.split_ctl == nullptr &&

@@ -17,6 +17,9 @@ constexpr int kMaxDup = 8;   // runs of more ids than this send their bucket to 
 // kCtlSortDone: set by split_join_kernel — the runs are final (whichever path wrote them); side-stream work that needs them
 // waits for this word instead of an event on the caller's stream (optim.hip: the detached long-run side)
 enum { kCtlOverflow = 0, kCtlTicket = 1, kCtlError = 2, kCtlRadixBuckets = 3, kCtlGenericDone = 4, kCtlSortDone = 5, kCtlScanCount = 6, kCtlLongCounters = 16, kCtlWords = 32 };
+// a bit of the device error word beside the sort's own (split_sort.cuh: kErrLookBack ... kErrOnesweep = 1 ... 8): the tree fold's
+// listing kernel met a run that did not fit the workspace it was handed (optim.hip: tree_mark_kernel)
+constexpr unsigned kErrTreeBounds = 16u;
 }  // namespace split
 
 // The control words of this thread's last id sort if that was a split sort which wrote exactly these three arrays, else nullptr.
@@ -29,4 +32,6 @@ std::unique_lock<std::mutex> lock_pending_join_side(hipStream_t* side);
 hipError_t record_sort_joined(hipStream_t stream);
 // one wave on `stream` that waits for ctl[kCtlSortDone] == 1, "the runs are final" (split_sort.cuh: split_wait_kernel)
 void enqueue_final_runs_wait(const uint32_t* ctl, hipStream_t stream);
+// the device's error word as kernels address it (pinned host memory; hip_device_error reports and clears it), or nullptr
+uint32_t* device_error_word();
 }  // namespace wm

@@ -17,6 +17,8 @@
  *      and into the weights).
  *      (2g) the GATv2 ("dynamic") multi-head graph attention of a sampled CSC block behind the GATv2 layer (forward and a
  *      deterministic backward).
+ *      (2h) the relation-typed neighbour aggregation of a sampled CSC block behind the RGCN layer: (2b) with a type per edge
+ *      and one output slot per relation (forward and a deterministic backward).
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -745,6 +747,69 @@ enum wholememory_error_code_t wholememory_ext_csc_gatv2_backward(const int32_t* 
                                                                  float* grad_att,
                                                                  struct wholememory_env_func_t* p_env_fns,
                                                                  void* stream);
+
+/* ---- (2h) relation-typed neighbour aggregation of a sampled CSC block (`agg_concat_rel`, RGCN) ----------------------- */
+/* The block as for (2b): row_ptr int32 [n_dst + 1], col_ind int32 [n_edges] in [0, n_src), x fp32 [n_src, x_stride] whose
+ * first n_dst rows are the targets; and edge_type int32 [n_edges], one relation per edge POSITION, R = num_relations >= 1.
+ * fp32 rows only. Strides in elements, all arrays DEVICE memory, all work queued on `stream`. Every `*` and `+` below is one
+ * fp32 operation, rounded on its own: a product and the add that follows it are two roundings, never a fused multiply-add.
+ * E_r(d) = the edges e in [row_ptr[d], row_ptr[d+1]) with edge_type[e] = r, in ascending e; n_r(d) their number.
+ *
+ * forward: out [n_dst, out_stride] fp32, out_stride >= (R + 1) * dim: slot r = columns [r * dim, (r + 1) * dim).
+ *   S_r(d) = sum of x[col_ind[e]] over E_r(d), left to right from the first term.
+ *   SUM: out[d, slot r] = S_r(d). MEAN: out[d, slot r] = fl(S_r(d) * fl(1.0f / n_r(d))), the mean over the edges of THAT
+ *   relation (one multiply). E_r(d) empty: the slot is +0.0. out[d, slot R] = x[d], copied bit for bit.
+ *   MEAN also writes edge_scale [n_edges]: edge_scale[e] = fl(1.0f / n_r(d)) for d = dst(e), r = edge_type[e]. SUM neither
+ *   writes nor reads edge_scale (it may be null).
+ * backward: grad_out [n_dst, grad_out_stride] ((R + 1) * dim columns used) and, for MEAN, the edge_scale the forward wrote
+ *   -> grad_x [n_src, grad_x_stride], every row written. u(e) = grad_out[dst(e), slot edge_type[e]] for SUM,
+ *   fl(edge_scale[e] * grad_out[dst(e), slot edge_type[e]]) for MEAN. P(s) sums u(e) over the edges with col_ind[e] = s in
+ *   ascending edge position, chunked exactly as (2b) with the same C = wholememory_ext_csc_aggregate_chunk_edges(): chunks
+ *   of C consecutive positions of the source's run, each chunk summed left to right from its first term, the chunk sums added
+ *   in chunk order. grad_x[s] = P(s) + grad_out[s, slot R], the self term last and only for s < n_dst; with one part missing
+ *   the other is copied, with neither the row is +0.0.
+ * An edge_type[e] outside [0, R) contributes no term anywhere: it is counted in no n_r, its edge_scale is +0.0, and in the
+ *   backward it still occupies its position when the chunks are cut but adds nothing (a chunk, or a whole P(s), all of whose
+ *   edges are such counts as missing). The value is compared, never used to form an address; nothing validates the types on
+ *   the host.
+ * With R = 1 and every type 0, out, and grad_x from the same grad_out, are those of (2b), bit for bit.
+ * No atomics; results are bitwise reproducible. The edge index of the backward is built with the library's id sort, scratch
+ * from p_env_fns (the forward needs none). n_edges = 0 and n_dst = 0 are valid. INVALID_INPUT, before any device work and
+ * under every backend, for what (2b) rejects (with rows of (R + 1) * dim columns), for num_relations < 1 or >= 2^31 - 1, a
+ * null edge_type with n_edges > 0 and, for MEAN, a null edge_scale with n_edges > 0; then NOT_SUPPORTED (nothing queued) when
+ * the device backend has no such kernels. */
+enum wholememory_error_code_t wholememory_ext_csc_rel_aggregate_forward(const int32_t* row_ptr,
+                                                                        const int32_t* col_ind,
+                                                                        const int32_t* edge_type,
+                                                                        int64_t n_edges,
+                                                                        int64_t n_dst,
+                                                                        int64_t n_src,
+                                                                        int64_t num_relations,
+                                                                        const float* x,
+                                                                        int64_t x_stride,
+                                                                        int64_t dim,
+                                                                        int aggr,
+                                                                        float* out,
+                                                                        int64_t out_stride,
+                                                                        float* edge_scale,
+                                                                        struct wholememory_env_func_t* p_env_fns,
+                                                                        void* stream);
+enum wholememory_error_code_t wholememory_ext_csc_rel_aggregate_backward(const int32_t* row_ptr,
+                                                                         const int32_t* col_ind,
+                                                                         const int32_t* edge_type,
+                                                                         int64_t n_edges,
+                                                                         int64_t n_dst,
+                                                                         int64_t n_src,
+                                                                         int64_t num_relations,
+                                                                         const float* edge_scale,
+                                                                         const float* grad_out,
+                                                                         int64_t grad_out_stride,
+                                                                         int64_t dim,
+                                                                         int aggr,
+                                                                         float* grad_x,
+                                                                         int64_t grad_x_stride,
+                                                                         struct wholememory_env_func_t* p_env_fns,
+                                                                         void* stream);
 
 /* ---- (3) testing seam ---------------------------------------------------------------------- */
 /* Replaces the device backend. Refuses (WHOLEMEMORY_NOT_SUPPORTED) unless the environment has

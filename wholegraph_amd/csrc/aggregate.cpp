@@ -2,7 +2,8 @@
 // validation, the edge index of the backward (the library's id sort over col_ind) and the launches of kernels/agg.hip
 // (fp32 rows), kernels/agg_half.hip (fp16 / bf16 rows, the _typed entry points) and kernels/agg_weighted.hip (a weight per
 // edge, section 2d, the _weighted entry points) and kernels/agg_gather.hip (rows read from a WholeMemory table by global id,
-// section 2e). The semantics, and the one order of every fp32 sum, are stated in the header.
+// section 2e) and kernels/agg_rel.hip (a type per edge and a slot per relation, section 2h, the _rel_ entry points). The
+// semantics, and the one order of every fp32 sum, are stated in the header.
 #include <atomic>
 
 #include <wholememory/wholegraph_amd_ext.h>
@@ -44,6 +45,17 @@ void backward_over_index(const wm_device_backend* bk, const int32_t* col_ind, in
 bool rows16(wholememory_dtype_t dtype) { return dtype == WHOLEMEMORY_DT_HALF || dtype == WHOLEMEMORY_DT_BF16; }
 
 std::atomic<int64_t> g_gather_agg_calls{0};   // fused forwards that reached the backend
+
+// what the two _rel_ entry points check alike, ahead of check_args
+void check_rel(const int32_t* edge_type, int64_t n_edges, int64_t num_relations, int aggr, const float* edge_scale)
+{
+  if (num_relations < 1) throw invalid_input("num_relations must be >= 1");
+  if (num_relations >= (int64_t(1) << 31) - 1) throw invalid_input("num_relations must be below 2^31 - 1");
+  if (n_edges < 0) throw invalid_input("negative size");
+  if (n_edges > 0 && edge_type == nullptr) throw invalid_input("edge_type is null");
+  if (aggr == WHOLEMEMORY_EXT_AGGR_MEAN && n_edges > 0 && edge_scale == nullptr)
+    throw invalid_input("edge_scale is null (MEAN writes it in the forward and reads it in the backward)");
+}
 
 }  // namespace
 
@@ -262,5 +274,65 @@ wholememory_error_code_t wholememory_ext_csc_gather_aggregate_forward(wholememor
 }
 
 int64_t wholememory_ext_gather_aggregate_calls(void) { return g_gather_agg_calls.load(std::memory_order_relaxed); }
+
+wholememory_error_code_t wholememory_ext_csc_rel_aggregate_forward(const int32_t* row_ptr, const int32_t* col_ind,
+                                                                   const int32_t* edge_type, int64_t n_edges, int64_t n_dst,
+                                                                   int64_t n_src, int64_t num_relations, const float* x,
+                                                                   int64_t x_stride, int64_t dim, int aggr, float* out,
+                                                                   int64_t out_stride, float* edge_scale,
+                                                                   wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  // (the arguments are judged first: a malformed call is INVALID_INPUT under every backend)
+  check_rel(edge_type, n_edges, num_relations, aggr, edge_scale);
+  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, x, x_stride, dim, dim, aggr, out, out_stride,
+             (num_relations + 1) * dim, n_src, n_dst);
+  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");   // (as the backward; the forward needs no scratch)
+  const auto* bk = backend();
+  if (bk->relagg_forward == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  auto a = block_args<wm_relagg_args>(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
+  a.edge_type     = edge_type;
+  a.num_relations = num_relations;
+  a.edge_scale    = a.mean ? edge_scale : nullptr;
+  a.in            = x;
+  a.in_stride     = x_stride;
+  a.out           = out;
+  a.out_stride    = out_stride;
+  WM_BK(bk->relagg_forward(&a, stream));
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+wholememory_error_code_t wholememory_ext_csc_rel_aggregate_backward(const int32_t* row_ptr, const int32_t* col_ind,
+                                                                    const int32_t* edge_type, int64_t n_edges, int64_t n_dst,
+                                                                    int64_t n_src, int64_t num_relations,
+                                                                    const float* edge_scale, const float* grad_out,
+                                                                    int64_t grad_out_stride, int64_t dim, int aggr,
+                                                                    float* grad_x, int64_t grad_x_stride,
+                                                                    wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  check_rel(edge_type, n_edges, num_relations, aggr, edge_scale);
+  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, grad_out, grad_out_stride, (num_relations + 1) * dim, dim, aggr, grad_x,
+             grad_x_stride, dim, n_dst, n_src);
+  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
+  const auto* bk = backend();
+  if (bk->relagg_backward == nullptr || bk->agg_backward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  auto a = block_args<wm_relagg_args>(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
+  a.edge_type     = edge_type;
+  a.num_relations = num_relations;
+  a.edge_scale    = a.mean ? const_cast<float*>(edge_scale) : nullptr;   // (read only by the backward)
+  a.grad          = grad_out;
+  a.grad_stride   = grad_out_stride;
+  a.out           = grad_x;
+  a.out_stride    = grad_x_stride;
+  if (n_src == 0) return WHOLEMEMORY_SUCCESS;
+  backward_over_index(bk, col_ind, a.n_edges, n_src, dim, p_env_fns, stream,
+                      [&](const int32_t* order, const int32_t* starts, const int32_t* unique, const int64_t* nu, void* ws) {
+                        WM_BK(bk->relagg_backward(&a, order, starts, unique, nu, ws, stream));
+                      });
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
 
 }  // extern "C"

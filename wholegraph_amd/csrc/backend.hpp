@@ -321,6 +321,24 @@ struct wm_gatv2_args {
   float* grad_att;          // backward: [heads * dim] or nullptr
 };
 
+// relation-typed neighbour aggregation of a sampled CSC block (kernels/agg_rel.hip, wholegraph_amd_ext.h section 2h):
+// wm_agg_args plus one int32 type per edge position; slot r of an out / grad row is columns [r * dim, (r + 1) * dim), the
+// self slot is slot num_relations. rows / strides / dim in ELEMENTS (fp32)
+struct wm_relagg_args {
+  const int32_t* row_ptr;     // [n_dst + 1]
+  const int32_t* col_ind;     // [n_edges], ids in [0, n_src)
+  const int32_t* edge_type;   // [n_edges]; a type outside [0, num_relations) contributes nothing and forms no address
+  int64_t n_edges, n_dst, n_src, dim, num_relations;
+  int mean;                   // 1: "mean" (a slot's sum times fl(1 / edges of that relation)), 0: "sum"
+  float* edge_scale;          // [n_edges]: mean only (else nullptr); written by the forward, read by the backward
+  const float* in;            // forward: x [n_src, in_stride]
+  int64_t in_stride;
+  const float* grad;          // backward: dL/dout [n_dst, grad_stride], (num_relations + 1) * dim columns used
+  int64_t grad_stride;
+  float* out;                 // forward: out [n_dst, out_stride] ((num_relations + 1) * dim columns); backward: grad_x
+  int64_t out_stride;         //   [n_src, out_stride]
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -560,6 +578,13 @@ struct wm_device_backend {
   size_t (*gatv2_backward_workspace_bytes)(const wm_gatv2_args* a);
   int (*gatv2_backward)(const wm_gatv2_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
                         const int64_t* n_unique_dev, void* workspace, void* stream);
+  // ---- relation-typed aggregation of a sampled CSC block (kernels/agg_rel.hip, wholegraph_amd_ext.h section 2h); nullptr
+  // in a backend without it ----
+  // forward: out and, for mean, edge_scale. backward: grad_x, with the index and the workspace of agg_backward
+  // (agg_backward_workspace_bytes)
+  int (*relagg_forward)(const wm_relagg_args* a, void* stream);
+  int (*relagg_backward)(const wm_relagg_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                         const int64_t* n_unique_dev, void* workspace, void* stream);
 };
 
 }  // extern "C"

@@ -96,6 +96,9 @@ int hip_gatv2_forward(const wm_gatv2_args* a, void* workspace, void* stream);
 size_t hip_gatv2_backward_workspace_bytes(const wm_gatv2_args* a);
 int hip_gatv2_backward(const wm_gatv2_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
                        const int64_t* n_unique_dev, void* workspace, void* stream);
+int hip_relagg_forward(const wm_relagg_args* a, void* stream);
+int hip_relagg_backward(const wm_relagg_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                        const int64_t* n_unique_dev, void* workspace, void* stream);
 
 namespace {
 
@@ -283,6 +286,8 @@ const wm_device_backend kHipBackend = {
   hip_gatv2_forward,
   hip_gatv2_backward_workspace_bytes,
   hip_gatv2_backward,
+  hip_relagg_forward,
+  hip_relagg_backward,
 };
 
 }  // namespace

@@ -2,7 +2,8 @@
 from .edge_gat_conv import EdgeGATConv
 from .gat_conv import CuGraphGATConv
 from .gatv2_conv import GATv2Conv
+from .rgcn_conv import RGCNConv
 from .sage_conv import CuGraphSAGEConv
 from .weighted_sage_conv import EdgeWeightedSAGEConv
 
-__all__ = ["CuGraphSAGEConv", "CuGraphGATConv", "EdgeGATConv", "GATv2Conv", "EdgeWeightedSAGEConv"]
+__all__ = ["CuGraphSAGEConv", "CuGraphGATConv", "EdgeGATConv", "GATv2Conv", "RGCNConv", "EdgeWeightedSAGEConv"]

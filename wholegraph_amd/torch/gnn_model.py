@@ -1,8 +1,9 @@
 """The GNN model surface of ``pylibwholegraph.torch.gnn_model`` (``set_framework``, ``create_gnn_layers``,
 ``create_sub_graph``, ``layer_forward``, ``HomoGNNModel``) for the ``cugraph`` framework route with GraphSAGE layers, on the
-HIP aggregation op (``aggregation.py``), and with GATv2 layers (model "gatv2": ``cugraphops.GATv2Conv`` on
-``gatv2_aggregation.py``). The dgl / pyg / wg routes and the model "gat" are not part of this build (the GAT layer itself is
-``cugraphops.CuGraphGATConv``).
+HIP aggregation op (``aggregation.py``), with GATv2 layers (model "gatv2": ``cugraphops.GATv2Conv`` on
+``gatv2_aggregation.py``) and, for graphs with typed edges, with RGCN layers (model "rgcn": ``cugraphops.RGCNConv`` on
+``rel_aggregation.py``, built by ``create_rgcn_layers``; the sampler delivers each block's edge types). The dgl / pyg / wg
+routes and the model "gat" are not part of this build (the GAT layer itself is ``cugraphops.CuGraphGATConv``).
 
 Flow of ``HomoGNNModel.forward`` (the reference's): sample ``layernum`` hops from the seed ids, gather the float32
 features of the outermost frontier through ``WholeMemoryEmbeddingModule`` (so the embedding receives gradients), then one
@@ -50,6 +51,9 @@ def create_gnn_layers(in_feat_dim, hidden_feat_dim, class_count, num_layer, num_
     _require_framework()
     if model_type == "gat":
         raise NotImplementedError("model 'gat' is not implemented on the cugraph route yet (only 'sage')")
+    if model_type == "rgcn":
+        raise ValueError("model 'rgcn' needs the number of relations: build its layers with create_rgcn_layers(in_feat_dim, "
+                         "hidden_feat_dim, class_count, num_layer, num_relations, num_bases=None)")
     if model_type not in ("sage", "gatv2"):
         raise ValueError("model %r is not available on the cugraph route (only 'sage' and 'gatv2')" % (model_type,))
     gnn_layers = torch.nn.ModuleList()
@@ -61,6 +65,19 @@ def create_gnn_layers(in_feat_dim, hidden_feat_dim, class_count, num_layer, num_
             gnn_layers.append(GATv2Conv(layer_input_dim, layer_output_dim, heads=num_head, concat=i != num_layer - 1))
         else:
             gnn_layers.append(SAGEConv(layer_input_dim, layer_output_dim))
+    return gnn_layers
+
+
+def create_rgcn_layers(in_feat_dim, hidden_feat_dim, class_count, num_layer, num_relations, num_bases=None):
+    """the layers of model "rgcn": RGCNConv(in -> hidden) ... RGCNConv(hidden -> class_count), each over `num_relations`
+    relations (with `num_bases` basis matrices when given)"""
+    _require_framework()
+    from .cugraphops.rgcn_conv import RGCNConv
+    gnn_layers = torch.nn.ModuleList()
+    for i in range(num_layer):
+        layer_output_dim = hidden_feat_dim if i != num_layer - 1 else class_count
+        layer_input_dim = in_feat_dim if i == 0 else hidden_feat_dim
+        gnn_layers.append(RGCNConv(layer_input_dim, layer_output_dim, num_relations, num_bases=num_bases))
     return gnn_layers
 
 
@@ -81,7 +98,9 @@ def layer_forward(layer, x_feat, x_target_feat, sub_graph):
 
 class HomoGNNModel(torch.nn.Module):
     """Node classification model over a homogeneous graph: settings from an ``args`` namespace as the reference reads them
-    (hiddensize, layernum, model, classnum, dropout, neighbors, inferencesample; heads for gat)."""
+    (hiddensize, layernum, model, classnum, dropout, neighbors, inferencesample; heads for gat). Model "rgcn" (an
+    extension) also reads num_relations, edge_type_name (an integer edge attribute registered with
+    ``graph_structure.set_edge_attribute``: the relation of every graph edge) and, optionally, num_bases."""
 
     def __init__(self, graph_structure: GraphStructure, node_embedding: WholeMemoryEmbedding, args):
         super().__init__()
@@ -96,8 +115,20 @@ class HomoGNNModel(torch.nn.Module):
         num_head = args.heads if attention else 1
         assert hidden_feat_dim % num_head == 0
         in_feat_dim = self.node_embedding.shape[1]
-        self.gnn_layers = create_gnn_layers(in_feat_dim, hidden_feat_dim, args.classnum, args.layernum, num_head,
-                                            args.model)
+        self.edge_type_name = None
+        if args.model == "rgcn":
+            if getattr(args, "fuse_gather", False):
+                raise ValueError("fuse_gather reads layer 0's rows from the table: GraphSAGE only, not model 'rgcn'")
+            if getattr(args, "num_relations", None) is None:
+                raise ValueError("model 'rgcn' needs args.num_relations")
+            if getattr(args, "edge_type_name", None) is None:
+                raise ValueError("model 'rgcn' needs args.edge_type_name (an edge attribute of the graph structure)")
+            self.edge_type_name = args.edge_type_name
+            self.gnn_layers = create_rgcn_layers(in_feat_dim, hidden_feat_dim, args.classnum, args.layernum,
+                                                 args.num_relations, getattr(args, "num_bases", None))
+        else:
+            self.gnn_layers = create_gnn_layers(in_feat_dim, hidden_feat_dim, args.classnum, args.layernum, num_head,
+                                                args.model)
         self.mean_output = attention
         self.add_self_loop = attention
         self.gather_fn = WholeMemoryEmbeddingModule(self.node_embedding)
@@ -109,13 +140,21 @@ class HomoGNNModel(torch.nn.Module):
     def forward(self, ids):
         max_neighbors = self.max_neighbors if self.training else self.max_inference_neighbors
         ids = ids.to(self.graph_structure.csr_col_ind.dtype).cuda()
-        target_gids, edge_indice, csr_row_ptrs, csr_col_inds = self.graph_structure.multilayer_sample_without_replacement(
-            ids, max_neighbors)
+        edge_attrs = None
+        if self.edge_type_name is not None:   # (model "rgcn": the relation of every sampled edge comes with its block)
+            target_gids, edge_indice, csr_row_ptrs, csr_col_inds, edge_attrs = \
+                self.graph_structure.multilayer_sample_with_edge_attributes(ids, max_neighbors, [self.edge_type_name])
+        else:
+            target_gids, edge_indice, csr_row_ptrs, csr_col_inds = \
+                self.graph_structure.multilayer_sample_without_replacement(ids, max_neighbors)
         x_feat = None if self.fuse_gather else self.gather_fn(target_gids[0], force_dtype=torch.float32)
         for i in range(self.num_layer):
             sub_graph = create_sub_graph(target_gids[i], target_gids[i + 1], edge_indice[i], csr_row_ptrs[i],
                                          csr_col_inds[i], max_neighbors[self.num_layer - 1 - i], self.add_self_loop)
-            if x_feat is None:   # (layer 0 of the fused route: the rows come from the table, by id)
+            if edge_attrs is not None:
+                x_feat = self.gnn_layers[i](x_feat, sub_graph[0], sub_graph[1], sub_graph[2],
+                                            edge_attrs[i][self.edge_type_name])
+            elif x_feat is None:   # (layer 0 of the fused route: the rows come from the table, by id)
                 x_feat = self.gnn_layers[0].forward_from_table(self.node_embedding, target_gids[0], sub_graph[0], sub_graph[1],
                                                                sub_graph[2], is_training=self.training)
             else:

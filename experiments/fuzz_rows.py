@@ -25,8 +25,6 @@ bad = 0
 for case in range(cases):
     fam = FLOATS if rng.random() < 0.6 else INTS
     tdt, odt = fam[rng.integers(len(fam))], fam[rng.integers(len(fam))]
-    if torch.bfloat16 in (tdt, odt) and tdt != odt:
-        tdt = odt = torch.bfloat16 if rng.random() < 0.5 else torch.float32   # bf16 is not registered for casts (as in the reference)
     dim = int(rng.choice([1, 2, 3, 4, 7, 8, 16, 31, 32, 33, 64, 100, 127, 128, 129, 200, 256, 300, 513, 602, 700]))
     if WIDE and rng.random() < 0.7:   # any width up to rows of 5.6 KiB (both chunk sizes of the LDS-staged kernels and past them)
         dim = int(rng.integers(1, 1400)) if rng.random() < 0.8 else int(rng.choice([1024, 1030, 1280, 1281, 1279, 2048, 2560, 2561]))

@@ -744,6 +744,98 @@ def combined_dense_scenarios(comm, rank, world):
         scenario_combine_auto(comm, rank, world, tdt=torch.float16, fold_knob=False)
 
 
+def scenario_capped_rows(comm, rank, world, dim, kernels, entries):
+    """WM_TEST_ONLY=capped_rows (tests/test_capped_grid_gpu.py): gather and scatter on a device CHUNKED table of several
+    ranks — a real chunked reference (chunk_stride != 0), which a one-rank table never gets — under a workgroup cap
+    (gather_sms / scatter_sms 1 and 3) and with WM_ROWS_INORDER=0, so that waves loop over tiles while they resolve each
+    row's owner: from the owner tables passed by value, and with WM_ROWS_OWNERS_BY_VALUE=0 from the reference's device
+    arrays (multiply-high for equal chunks, the search over rank offsets for a custom partition). n = 5 / 64 / 2597, int32 and
+    int64 ids, negative ids in the second half only, sentinel-filled outputs, bit for bit against the oracle; the kernel
+    family is asserted through its name. Ranks scatter disjoint ids at the same time."""
+    from wholegraph_amd.torch.wholegraph_env import wrap_torch_tensor, get_wholegraph_env_fns, get_stream
+    import re
+    n_rows = 9001
+    wm = wgth.create_wholememory_tensor(comm, "chunked", "cuda", [n_rows, dim], torch.float32, [dim, 1], entries)
+    full = (np.random.default_rng(3).integers(-240, 240, (n_rows, dim)) / 2).astype(np.float32)
+    tab = oracle.ShardedTable.from_full(full, world, entries)
+    local, start = wm.get_local_tensor(host_view=False)
+    cnt = int(tab.entry_offsets[rank + 1] - tab.entry_offsets[rank])
+    assert start == int(tab.entry_offsets[rank]) and local.shape[0] == cnt and cnt > 0
+
+    def served_by(family, what):
+        name = wmb.lib().wholememory_ext_last_rows_kernel().decode()
+        m = re.search(r"(rows_\w+)<", name)
+        assert m and m.group(1) == family, "%s: served by %r, not by %s" % (what, name, family)
+
+    def skip_some(idx, n):
+        idx[n // 2 + 1::29] = -1
+        return idx
+
+    env_fns, stream = get_wholegraph_env_fns(), C.c_void_p(get_stream())
+    for by_value in (None, "0"):
+        for cap, inorder in ((1, None), (3, None), (-1, "0")):
+            for name, value in (("WM_ROWS_OWNERS_BY_VALUE", by_value), ("WM_ROWS_INORDER", inorder)):
+                if value is not None:
+                    os.environ[name] = value
+            _reload_knobs()
+            for n in (5, 64, 2597):
+                for idt in (np.int32, np.int64):
+                    what = "dim %d, %s partition, owners %s, cap %d, n %d, %s ids, rank %d" % (
+                        dim, "custom" if entries else "equal", "by value" if by_value is None else "from device arrays", cap, n,
+                        np.dtype(idt).name, rank)
+                    # ---- gather (duplicates, every rank asks for rows of every owner)
+                    local.copy_(dev(torch.from_numpy(full[start:start + cnt])))
+                    torch.cuda.synchronize()
+                    comm.barrier()
+                    rng = np.random.default_rng(1000 * rank + 10 * n + cap + 1)
+                    idx = rng.integers(0, n_rows, n).astype(idt)
+                    idx[:min(n, 7)] = idx[0]
+                    idx = skip_some(idx, n)
+                    want = np.full((n, dim), -7, dtype=np.float32)
+                    out = dev(torch.from_numpy(want.copy()))
+                    wi, wo = wrap_torch_tensor(dev(torch.from_numpy(idx))), wrap_torch_tensor(out)
+                    wmb.check(wmb.lib().wholememory_gather(wm.wmb_tensor, wi.handle, wo.handle, env_fns, stream, cap))
+                    torch.cuda.synchronize()
+                    served_by(kernels[0], "gather " + what)
+                    oracle.gather(tab, idx, want)
+                    assert host(out).numpy().tobytes() == want.tobytes(), "gather differs from the oracle: " + what
+                    comm.barrier()
+                    # ---- scatter (rank r takes every world-th id of one permutation: unique, and disjoint between ranks)
+                    local.fill_(-7)
+                    torch.cuda.synchronize()
+                    comm.barrier()
+                    perm = np.random.default_rng(10 * n + cap + 2).permutation(n_rows)
+                    ref = oracle.ShardedTable.from_full(np.full((n_rows, dim), -7, dtype=np.float32), world, entries)
+                    for r in range(world):
+                        ids_r = skip_some(perm[r::world][:n].astype(idt), n)
+                        rows_r = (np.random.default_rng(50 + r).integers(-240, 240, (n, dim)) / 2).astype(np.float32)
+                        oracle.scatter(rows_r, ids_r, ref)
+                        if r == rank:
+                            wr, wx = wrap_torch_tensor(dev(torch.from_numpy(rows_r))), wrap_torch_tensor(dev(torch.from_numpy(ids_r)))
+                            wmb.check(wmb.lib().wholememory_scatter(wr.handle, wx.handle, wm.wmb_tensor, env_fns, stream, cap))
+                            torch.cuda.synchronize()
+                            served_by(kernels[1], "scatter " + what)
+                    comm.barrier()
+                    assert host(local).numpy().tobytes() == ref.shards[rank][:cnt].tobytes(), \
+                        "table after scatter differs from the oracle: " + what
+                    comm.barrier()
+            for name in ("WM_ROWS_OWNERS_BY_VALUE", "WM_ROWS_INORDER"):
+                os.environ.pop(name, None)
+            _reload_knobs()
+    wgth.destroy_wholememory_tensor(wm)
+
+
+def capped_rows_scenarios(comm, rank, world):
+    w = np.sort(np.random.default_rng(7).uniform(60, 100, world))   # ascending: the first ranks hold less than the last one,
+    ent = [int(x) for x in (w / w.sum() * 9001).astype(int)]        # so the chunks are not equal and the owner is searched for
+    ent[-1] += 9001 - sum(ent)
+    assert ent[0] < ent[-1]
+    for entries in (None, ent):
+        # 512 B rows (the C2 shape) and 400 B rows (LDS-staged, eight chunks per 64-row tile)
+        scenario_capped_rows(comm, rank, world, 128, ("rows_copy16_fast_kernel", "rows_copy16_fast_kernel"), entries)
+        scenario_capped_rows(comm, rank, world, 100, ("rows_staged_gather_kernel", "rows_staged_scatter_kernel"), entries)
+
+
 def scenario_cached_embedding(comm, rank, world, mt):
     """HOST embedding with a read-write device cache on every rank (HIP mode): owners serve lookups cache-first through
     the exchange, train through the cache, write back. Bit-exact vs the uncached multi-rank oracle."""
@@ -1058,6 +1150,14 @@ def main():
         if RCCL_MODE:
             assert comm.transport() == ("rccl", world), comm.transport()
         combined_dense_scenarios(comm, rank, world)
+        comm.barrier()
+        dist.barrier()
+        print("RANK %d OK" % rank)
+        wgth.finalize()
+        return
+    if os.environ.get("WM_TEST_ONLY") == "capped_rows":   # only the capped row launches on chunked tables of several ranks
+        assert HIP_MODE
+        capped_rows_scenarios(comm, rank, world)
         comm.barrier()
         dist.barrier()
         print("RANK %d OK" % rank)

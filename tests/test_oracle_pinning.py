@@ -7,6 +7,8 @@ rules, written here in numpy / pure Python (NOT through the oracle):
    (python/.../tests/wholegraph_torch/ops/test_wholegraph_gather_scatter.py:26-37);
  * the reference tests' host CPUOptimizer + first-seen-order dedup, tolerance 1e-5
    (cpp/tests/wholememory_ops/wholememory_embedding_gradient_apply_tests.cu:169-371,437-466,481-501);
+ * torch's CPU casts, through float32 wherever a 16-bit type is involved (the chain of gather_scatter_func.cuh:161-208), on
+   the boundary values of tests/_cast_values.py: ties, subnormals, overflow, values that round twice;
  * partition plans (memory_handle.cpp:1618-1635; host_random_partition embedding_test_utils.cu:531-546;
    python random_partition test_comm.py:188-195) via the committed golden fixtures.
 """
@@ -16,6 +18,7 @@ import os
 import numpy as np
 import pytest
 
+import _cast_values as cv
 import oracle
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -240,3 +243,48 @@ def test_align_embedding_dim():
     assert [oracle.align_embedding_dim(d, 4) for d in (1, 4, 11, 127, 128, 129)] == [4, 4, 12, 128, 128, 132]
     assert [oracle.align_embedding_dim(d, 2) for d in (1, 8, 9, 256)] == [8, 8, 16, 256]
     assert oracle.align_embedding_dim(5, 8) == 6
+
+
+@pytest.mark.parametrize("src,dst", cv.FLOAT_PAIRS, ids=lambda v: v)
+def test_float_casts_on_boundary_values_match_torch_cpu(src, dst):
+    """The oracle's conversion chain (wm_oracle.c: load_fp / store_fp) against torch's CPU casts on the value sets of
+    tests/_cast_values.py — every 16-bit pattern, every float32 tie of both 16-bit formats with its neighbours, overflow and
+    subnormal boundaries, and float64 values whose two roundings differ from one. torch goes through float32 whenever
+    either side is 16-bit, which is the reference's chain (gather_scatter_func.cuh:161-208). A NaN input must give a NaN;
+    everything else is compared bit for bit."""
+    import torch
+    dim = 64
+    table = cv.as_table(cv.float_source(src), dim, src)
+    n_rows = table.shape[0]
+    tab = oracle.ShardedTable([table], np.array([0, n_rows], dtype=np.uint64), dim, dim, 0, cv.ORACLE_DT[src])
+    idx = np.random.default_rng(4).permutation(n_rows).astype(np.int64)
+    out = np.full((n_rows, dim), cv.sentinel(dst), dtype=cv.CARRIER[dst])
+    oracle.gather(tab, idx, out, out_dt=cv.ORACLE_DT[dst])
+    t = cv.to_torch(table[idx], src)
+    if src in ("f16", "bf16") or dst in ("f16", "bf16"):
+        t = t.to(torch.float32)
+    want = cv.from_torch(t.to(cv.torch_dtype(dst)), dst)
+    nan_in = cv.isnan(table[idx], src)
+    assert int(nan_in.sum()) == cv.NAN_COUNT[src]
+    assert cv.isnan(out, dst)[nan_in].all(), "a NaN input did not give a NaN"
+    differ = (cv.bits_of(out) != cv.bits_of(want)) & ~nan_in
+    assert not differ.any(), "%d of %d values differ, first: source bits %#x -> oracle %#x, torch %#x" % (
+        differ.sum(), differ.size, cv.bits_of(table[idx])[differ][0], cv.bits_of(out)[differ][0], cv.bits_of(want)[differ][0])
+
+
+def test_boundary_value_sets_hold_what_they_claim():
+    """tests/_cast_values.py would be vacuous if its ties were not ties: on the float32 set, truncation and round-half-away
+    must each differ from round-to-nearest-even on tens of thousands of values per 16-bit target, and on the float64 set
+    one rounding must differ from the chain's two."""
+    f = cv.f32_values()
+    u = f.view(np.uint32).astype(np.uint64)
+    rne = (u + 0x7fff + ((u >> 16) & 1)) >> 16          # bf16, finite values
+    fin = np.isfinite(f)
+    assert ((rne != (u >> 16)) & fin).sum() > 60000 and ((rne != ((u + 0x8000) >> 16)) & fin).sum() > 30000
+    with np.errstate(over="ignore"):
+        h = f.astype(np.float16)
+        d = cv.f64_values()
+        once, twice = d.astype(np.float16), d.astype(np.float32).astype(np.float16)
+    assert (np.isinf(h) & fin).any() and ((h == 0) & (f != 0)).any()
+    assert ((np.abs(h) < 2.0 ** -14) & (h != 0)).sum() > 1000                     # f16 subnormal results
+    assert (once.view(np.uint16) != twice.view(np.uint16)).sum() > 60000

@@ -1341,6 +1341,14 @@ extern "C" const char* wholememory_ext_last_rows_kernel()
   if (mangled == nullptr) return name.c_str();
   int status       = 0;
   char* demangled  = abi::__cxa_demangle(mangled, nullptr, nullptr, &status);
+  if (status != 0 || demangled == nullptr) {
+    // _Float16 is mangled DF16_, which older C++ runtimes cannot read: every kernel over half_t came back mangled. Dh is
+    // the earlier spelling of the same IEEE half type (also a builtin, so substitutions keep their numbers): "half"
+    if (demangled != nullptr) free(demangled);
+    std::string older = mangled;
+    for (size_t at; (at = older.find("DF16_")) != std::string::npos;) older.replace(at, 5, "Dh");
+    demangled = abi::__cxa_demangle(older.c_str(), nullptr, nullptr, &status);
+  }
   name             = status == 0 && demangled != nullptr ? demangled : mangled;
   if (demangled != nullptr) free(demangled);
   return name.c_str();

@@ -818,7 +818,10 @@ enum wholememory_error_code_t wholememory_ext_csc_rel_aggregate_backward(const i
 enum wholememory_error_code_t wm_testing_install_backend(const void* backend);
 
 /* Occupancy / effectiveness of an embedding's device row cache: slots, occupied slots, modified slots, lookups served
- * from the cache and lookups seen so far (this rank). INVALID_INPUT for an embedding without cache. */
+ * from the cache and lookups seen so far (this rank). A lookup is an id the cache was asked for: the cache of a rank's own
+ * shard (cache communicator = the embedding's) is asked for the ids that reach this owner — an id that addresses no row, the
+ * negative "skip" ids among them, reaches none and is not counted —, a local cache of the whole table for every id of the
+ * caller's batch. INVALID_INPUT for an embedding without cache. */
 enum wholememory_error_code_t wholememory_ext_embedding_cache_info(wholememory_embedding_t embedding, int64_t* slots,
                                                                    int64_t* occupied, int64_t* dirty, int64_t* hits,
                                                                    int64_t* lookups);

@@ -485,29 +485,19 @@ int combined_gradient_apply(wholememory_embedding_* e, const char* idx_ptr, cons
   id_exchange x(env);
   bucket_and_exchange_ids(e->comm, r.unique, iarr.dtype, nu, entry_offsets, env, stream, &x, self_local, false, &su);
   if (x.dup_permille < 0) return 0;   // some rank's float16 partial sums left the range: everybody takes the plain route
-  std::vector<int64_t> full_recv_counts = x.recv_counts, full_recv_offsets(W + 1, 0);
-  full_recv_counts[rank]                = x.self_count;
-  for (int i = 0; i < W; i++) full_recv_offsets[i + 1] = full_recv_offsets[i] + full_recv_counts[i];
-  const int64_t n_recv = full_recv_offsets[W];
+  const rank_major_recv full(x, e->comm);
   temp_mem recv_rows(env), recv_ids_mem(env);
-  char* recv_buf = static_cast<char*>(recv_rows.device(dim * n_recv, vdt));
-  char* recv_ids = static_cast<char*>(recv_ids_mem.device(n_recv, iarr.dtype));
-  for (int q = 0; q < W; q++) {   // ids: the peers' segments were received compactly (self cut out) — around the self slot
-    const char* src = (q == rank && self_local) ? static_cast<const char*>(x.bucketed_ids) + ies * x.self_offset
-                                                : static_cast<const char*>(x.recv_ids) + ies * x.recv_offsets[q];
-    if (full_recv_counts[q] > 0) WM_BK(bk->memcpy_async(recv_ids + ies * full_recv_offsets[q], src, ies * full_recv_counts[q], stream));
-  }
+  char* recv_buf = static_cast<char*>(recv_rows.device(dim * full.n_recv, vdt));
+  char* recv_ids = static_cast<char*>(recv_ids_mem.device(full.n_recv, iarr.dtype));
+  full.place_ids(x, ies, self_local, recv_ids, stream);
   if (self_local && x.self_count > 0)   // this rank's own partial rows: one copy into their rank-major slot
-    WM_BK(bk->memcpy_async(recv_buf + row_bytes * full_recv_offsets[rank], partial + row_bytes * x.self_offset,
+    WM_BK(bk->memcpy_async(recv_buf + row_bytes * full.offsets[rank], partial + row_bytes * x.self_offset,
                            row_bytes * static_cast<size_t>(x.self_count), stream));
-  {
-    std::vector<int64_t> ro(full_recv_offsets.begin(), full_recv_offsets.end() - 1);
-    exchange_segments(e->comm, partial, x.send_counts, x.bucket_offsets, recv_buf, x.recv_counts, ro, row_bytes, stream);
-  }
+  exchange_segments(e->comm, partial, x.send_counts, x.bucket_offsets, recv_buf, x.recv_counts, full.offsets, row_bytes, stream);
   g_grad_combined_calls.fetch_add(1, std::memory_order_relaxed);
   // (4) the owner's step over at most W partial rows per id
   owner_input in;
-  in.recv_ids = recv_ids, in.index_dtype = iarr.dtype, in.n_recv = n_recv, in.rows = recv_buf, in.row_stride = dim;
+  in.recv_ids = recv_ids, in.index_dtype = iarr.dtype, in.n_recv = full.n_recv, in.rows = recv_buf, in.row_stride = dim;
   *rc = owner_apply(e, in, entry_offsets, lr, env, stream, adjust_cache);
   return 1;
 }
@@ -611,10 +601,8 @@ wholememory_error_code_t gather_gradient_apply(wholememory_embedding_* e, wholem
   // The owner needs ids and gradient rows of ALL requesters in rank-major receive order (that order defines
   // the fp32 summation order of duplicates). Peers' rows arrive by all-to-all-v; this rank's own rows are
   // written straight into their slot of the receive buffers (no send staging, no self copy).
-  std::vector<int64_t> full_recv_counts = x.recv_counts, full_recv_offsets(e->comm->world_size + 1, 0);
-  full_recv_counts[rank]                = x.self_count;
-  for (int i = 0; i < e->comm->world_size; i++) full_recv_offsets[i + 1] = full_recv_offsets[i] + full_recv_counts[i];
-  const int64_t n_recv = full_recv_offsets[e->comm->world_size];
+  const rank_major_recv full(x, e->comm);
+  const int64_t n_recv = full.n_recv;
 
   temp_mem send_rows(env), recv_rows(env), recv_ids_mem(env);
   // (x.identity: one rank, nothing dropped — the caller's ids and gradient rows are used where they are: no staging
@@ -623,13 +611,7 @@ wholememory_error_code_t gather_gradient_apply(wholememory_embedding_* e, wholem
   auto* recv_buf = static_cast<char*>(recv_rows.device(x.identity ? 0 : dim * n_recv, vdt));
   const size_t row_bytes = static_cast<size_t>(dim) * ves;
   char* recv_ids = x.identity ? const_cast<char*>(idx_ptr) : static_cast<char*>(recv_ids_mem.device(n_recv, iarr.dtype));
-  // ids: peers' segments were received compactly (self cut out) — place them around the self slot
-  for (int r = 0; r < e->comm->world_size && !x.identity; r++) {
-    const char* src = r == rank ? static_cast<const char*>(x.bucketed_ids) + ies * x.self_offset
-                                : static_cast<const char*>(x.recv_ids) + ies * x.recv_offsets[r];
-    if (full_recv_counts[r] > 0)
-      WM_BK(bk->memcpy_async(recv_ids + ies * full_recv_offsets[r], src, ies * full_recv_counts[r], stream));
-  }
+  if (!x.identity) full.place_ids(x, ies, true, recv_ids, stream);
   // gradient rows in bucketed order: remote segments into the send buffer, the self segment into recv_buf
   const auto grads_gref = wholememory_create_continuous_global_reference(wholememory_tensor_get_data_pointer(grads));
   auto launch_rows = [&](const int64_t* raw, int64_t s0, int64_t s1, char* dst) {   // grads[raw[s0 .. s1)] -> dst rows 0 ..
@@ -652,60 +634,32 @@ wholememory_error_code_t gather_gradient_apply(wholememory_embedding_* e, wholem
   const bool self_direct = x.self_count > 0 && self_in_place;
   self_rows_ref self_ref;
   if (self_direct) {
-    self_ref.begin  = full_recv_offsets[rank];
+    self_ref.begin  = full.offsets[rank];
     self_ref.count  = x.self_count;
     self_ref.rows   = x.raw_indices + x.self_offset;
     self_ref.grads  = wholememory_tensor_get_data_pointer(grads);
     self_ref.stride = gmat.stride;
   } else if (self_local) {
-    launch_rows(x.raw_indices, x.self_offset, x.self_offset + x.self_count, recv_buf + full_recv_offsets[rank] * row_bytes);
+    launch_rows(x.raw_indices, x.self_offset, x.self_offset + x.self_count, recv_buf + full.offsets[rank] * row_bytes);
   }
-  // peers' rows: line-up (HBM) and all-to-all-v (xGMI, side stream) pipelined in C row-chunks; the id sort that
-  // follows on the caller's stream overlaps with the tail of the exchange.
-  // ONE line-up kernel per chunk whatever the number of ranks (round 6; the distributed gather since round 5): the positions
-  // of the rows to send are brought into chunk-major order once (ops_internal.hpp: chunk_layout, backend: permute_chunks)
-  // and the send buffer is laid out chunk-major — C + 1 kernels in front of the exchange instead of (W - 1) C (28 -> 5 at
-  // W = 8, C = 4). The RECEIVE side keeps the rank-major order: it defines the order of the fp32 sum of duplicates.
-  const int W = e->comm->world_size;
-  const int C = exchange_chunks(W, x.global_moved);
-  const bool per_peer = bk->permute_chunks == nullptr || W > 16 || W <= 2 /* one peer: a chunk is one range already */ ||
-                        (WM_KNOB("WM_EXCHANGE_PER_PEER") != nullptr && WM_KNOB("WM_EXCHANGE_PER_PEER")[0] == '1');
-  const bool folded = !per_peer && C > 1 && !x.identity;
-  const chunk_layout want(x.send_counts, C), serve(x.recv_counts, C);
+  // peers' rows: line-up and all-to-all-v in C row-chunks over two streams (ops_internal.hpp: pipeline_chunks), with no third
+  // stage: the id sort that follows on the caller's stream overlaps with the tail of the exchange.
+  // ONE line-up kernel per chunk whatever the number of ranks (round 6; exchange_plan.hpp): the send side is chunk-major —
+  // C + 1 kernels in front of the exchange instead of (W - 1) C (28 -> 5 at W = 8, C = 4). The RECEIVE side keeps the
+  // rank-major order: it defines the order of the fp32 sum of duplicates.
+  const int C         = exchange_chunks(e->comm->world_size, x.global_moved);
+  const bool per_peer = exchange_per_peer(e->comm->world_size);   // (x.identity: one rank, so per peer — and that peer is skipped)
+  const exchange_plan plan(x, rank, C, self_local, per_peer, per_peer);
   temp_mem raw_cm_mem(env);
-  const int64_t* send_raw = x.raw_indices;
-  if (folded && x.total_send > 0) {
-    auto* cm = static_cast<int64_t*>(raw_cm_mem.device(x.total_send, WHOLEMEMORY_DT_INT64));
-    WM_BK(bk->permute_chunks(x.raw_indices, cm, 8, x.bucket_offsets.data(), x.send_counts.data(), W, C, stream));
-    g_grad_exchange_launches.fetch_add(1, std::memory_order_relaxed);
-    send_raw = cm;
-  }
-  void* side = C > 1 ? e->comm->get_side_stream() : stream;
-  event_set lined_up(C > 1 ? C : 0), arrived(C > 1 ? 1 : 0);
-  for (int c = 0; c < C; c++) {
-    std::vector<int64_t> sc(W), so(W), rc(W), ro(W);
-    for (int p = 0; p < W; p++) {
-      sc[p] = want.count(c, p), so[p] = folded ? want.pos(c, p) : x.bucket_offsets[p] + want.first(c, p);
-      rc[p] = serve.count(c, p), ro[p] = full_recv_offsets[p] + serve.first(c, p);
-    }
-    if (folded) {
-      launch_rows(send_raw, want.start(c), want.start(c + 1), send_buf + want.start(c) * row_bytes);
-    } else if (!per_peer && !x.identity) {
-      // one chunk: the rows to send are the bucketed order minus this rank's own segment — the range before it and the one after
-      const int64_t self_b = self_local ? x.self_offset : x.total_valid, self_e = self_local ? x.self_offset + x.self_count : x.total_valid;
-      launch_rows(x.raw_indices, 0, self_b, send_buf);
-      launch_rows(x.raw_indices, self_e, x.total_valid, send_buf + self_e * row_bytes);
-    } else {
-      for (int p = 0; p < W; p++)
-        if (p != rank || !self_local) launch_rows(x.raw_indices, so[p], so[p] + sc[p], send_buf + so[p] * row_bytes);
-    }
-    if (C > 1) {
-      WM_BK(bk->event_record(lined_up[c], stream));
-      WM_BK(bk->stream_wait_event(side, lined_up[c]));
-    }
-    exchange_segments(e->comm, send_buf, sc, so, recv_buf, rc, ro, row_bytes, side);
-  }
-  if (C > 1) WM_BK(bk->event_record(arrived[0], side));
+  auto* send_raw = static_cast<const int64_t*>(chunk_major_copy(x.raw_indices, WHOLEMEMORY_DT_INT64, plan.want, &raw_cm_mem, &g_grad_exchange_launches, stream));
+  const event_set arrived = pipeline_chunks(   // (outlives owner_apply, which waits for it where it first reads the rows)
+    e->comm, C, stream,
+    [&](int c) { for (const auto& r : plan.want.ranges(c)) launch_rows(send_raw, r.first, r.first + r.second, send_buf + r.first * row_bytes); },
+    [&](int c, void* on_stream) {
+      const auto s = segments_of(plan.want, plan.serve, c, &full.offsets);
+      exchange_segments(e->comm, send_buf, s.sc, s.so, recv_buf, s.rc, s.ro, row_bytes, on_stream);
+    },
+    nullptr);
   void* rows_arrived = C > 1 ? arrived[0] : nullptr;
 
   // Everything this rank was given is its own (one rank; ids that address no row are dropped inside the sort, see above):

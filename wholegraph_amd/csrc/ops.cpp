@@ -352,6 +352,72 @@ event_set::~event_set()
     if (e != nullptr) backend()->event_destroy(e);
 }
 
+bool exchange_per_peer(int world_size)
+{
+  const char* e = WM_KNOB("WM_EXCHANGE_PER_PEER");
+  return backend()->permute_chunks == nullptr || world_size > 16 || world_size <= 2 || (e != nullptr && e[0] == '1');
+}
+
+const void* chunk_major_copy(const void* src, wholememory_dtype_t dtype, const exchange_side& side, temp_mem* mem,
+                             std::atomic<int64_t>* launches, void* stream)
+{
+  if (!side.chunk_major() || side.rows() <= 0) return src;
+  void* cm = mem->device(side.rows(), dtype);
+  WM_BK(backend()->permute_chunks(src, cm, static_cast<int>(wholememory_dtype_get_element_size(dtype)), side.seg_offsets(),
+                                  side.seg_counts(), side.peers(), side.chunks(), stream));
+  launches->fetch_add(1, std::memory_order_relaxed);
+  return cm;
+}
+
+event_set pipeline_chunks(wholememory_comm_t comm, int C, void* stream, const chunk_stage& produce,
+                          const std::function<void(int, void*)>& exchange, const chunk_stage& consume)
+{
+  const auto* bk = backend();
+  if (C == 1) {
+    produce(0);
+    exchange(0, stream);
+    if (consume) consume(0);
+    return event_set(0);
+  }
+  void* side = comm->get_side_stream();
+  event_set produced(C), arrived(consume ? C : 1);
+  for (int c = 0; c < C; c++) {
+    produce(c);
+    WM_BK(bk->event_record(produced[c], stream));
+    WM_BK(bk->stream_wait_event(side, produced[c]));
+    exchange(c, side);
+    if (!consume) continue;
+    WM_BK(bk->event_record(arrived[c], side));
+    if (c >= 1) {
+      WM_BK(bk->stream_wait_event(stream, arrived[c - 1]));
+      consume(c - 1);
+    }
+  }
+  if (!consume) {
+    WM_BK(bk->event_record(arrived[0], side));
+    return arrived;
+  }
+  WM_BK(bk->stream_wait_event(stream, arrived[C - 1]));
+  consume(C - 1);
+  return event_set(0);
+}
+
+rank_major_recv::rank_major_recv(const id_exchange& x, wholememory_comm_t comm)
+  : counts(x.recv_counts), offsets(comm->world_size + 1, 0), rank(comm->world_rank)
+{
+  counts[rank] = x.self_count;
+  for (size_t i = 0; i < counts.size(); i++) offsets[i + 1] = offsets[i] + counts[i];
+  n_recv = offsets.back();
+}
+void rank_major_recv::place_ids(const id_exchange& x, size_t id_bytes, bool self_from_bucketed, char* dst, void* stream) const
+{
+  for (int q = 0; q < static_cast<int>(counts.size()); q++) {
+    const char* src = (q == rank && self_from_bucketed) ? static_cast<const char*>(x.bucketed_ids) + id_bytes * x.self_offset
+                                                        : static_cast<const char*>(x.recv_ids) + id_bytes * x.recv_offsets[q];
+    if (counts[q] > 0) WM_BK(backend()->memcpy_async(dst + id_bytes * offsets[q], src, id_bytes * counts[q], stream));
+  }
+}
+
 namespace {
 
 struct op_descs {
@@ -637,79 +703,28 @@ wholememory_error_code_t gather_distributed_rows(wholememory_handle_t handle, co
     g_dist_gather_launches.fetch_add(1, std::memory_order_relaxed);
   }
 
-  // (b)-(d) the peers' rows, pipelined in C row-chunks so the three legs overlap:
+  // (b)-(d) the peers' rows, in C row-chunks whose three legs overlap (ops_internal.hpp: pipeline_chunks):
   //   G_c  owner side: gather chunk c of every peer's requested rows into the send buffer, already cast to the
-  //        output dtype (gather_op_impl_nccl.cu:115-140)                                — HBM, caller's stream
-  //   A_c  rows all-to-all-v of chunk c (gather_op_impl_nccl.cu:141-150)                 — xGMI, side stream
-  //   R_c  reorder on receive: out[raw_indices[j]] = recv[j] (gather_op_impl_nccl.cu:151-168) — HBM, caller's stream
-  // issue order on the caller's stream: G_0 G_1 R_0 G_2 R_1 ... so that G_{c+1} and R_{c-1} run while A_c is on the
-  // links. Chunk c of a segment of n rows is [n*c/C, n*(c+1)/C) on both ends of a pair, so sizes always match.
+  //        output dtype (gather_op_impl_nccl.cu:115-140)
+  //   A_c  rows all-to-all-v of chunk c (gather_op_impl_nccl.cu:141-150)
+  //   R_c  reorder on receive: out[raw_indices[j]] = recv[j] (gather_op_impl_nccl.cu:151-168)
   temp_mem local_rows(env), recv_rows(env), ids_cm_mem(env), raw_cm_mem(env);
   char* local_buf = static_cast<char*>(local_rows.device(dim * x.total_recv, d.plain.dtype));
   char* recv_buf  = in_place ? static_cast<char*>(d.plain_ptr)   // bucketed layout = the output itself
                              : static_cast<char*>(recv_rows.device(dim * x.total_valid, d.plain.dtype));
   const size_t row_bytes = static_cast<size_t>(dim) * oes;
   const int W            = comm->world_size;
-  const int rank         = comm->world_rank;
   const int C            = exchange_chunks(W, x.global_moved);
   const auto out_gref    = wholememory_create_continuous_global_reference(d.plain_ptr);
-  auto chunk_of = [C](int64_t n, int c, int64_t* a, int64_t* b) {
-    *a = n * c / C;
-    *b = n * (c + 1) / C;
-  };
   // ONE launch per chunk and side (round 5; rounds 2-4 launched per peer: 2 (W - 1) C + 1 row kernels per call — 57 at
-  // W = 8, C = 4 — a measurable tax on mini-batch-sized gathers). The received ids (serving side) and the original positions
-  // of the requested rows (requesting side) are brought into CHUNK-MAJOR order once, by one small kernel each (backend:
-  // permute_chunks): chunk c of every peer's segment then lies in one contiguous range of the ids, of the send buffer, of the
-  // receive buffer and of the positions, and the chunk's owner gather / reorder is one row kernel over that range. With one
-  // chunk the peer-major order already is contiguous (and the rows before / after this rank's own segment are two ranges).
-  // Backends without permute_chunks, more than 16 ranks, or WM_EXCHANGE_PER_PEER=1: the per-peer launches as before.
-  const bool per_peer = bk->permute_chunks == nullptr || W > 16 || W <= 2 /* one peer: a chunk is one range already */ ||
-                        (WM_KNOB("WM_EXCHANGE_PER_PEER") != nullptr && WM_KNOB("WM_EXCHANGE_PER_PEER")[0] == '1');
-  const bool fold_serve = !per_peer;                          // serving side: ids -> send buffer
-  const bool fold_recv  = !per_peer && !in_place;            // requesting side: receive buffer -> output rows
-  // chunk-major starts: serve_start[c] over recv_counts, want_start[c] over send_counts (self travels as 0 when kept local)
-  std::vector<int64_t> serve_start(C + 1, 0), want_start(C + 1, 0);
-  for (int c = 0; c < C; c++) {
-    int64_t s1 = 0, s2 = 0;
-    for (int p = 0; p < W; p++) {
-      int64_t a, b;
-      chunk_of(x.recv_counts[p], c, &a, &b), s1 += b - a;
-      chunk_of(x.send_counts[p], c, &a, &b), s2 += b - a;
-    }
-    serve_start[c + 1] = serve_start[c] + s1;
-    want_start[c + 1]  = want_start[c] + s2;
-  }
-  auto serve_pos = [&](int c, int p) {   // where chunk c of peer p's requests starts in the chunk-major order
-    int64_t pos = serve_start[c];
-    for (int q = 0; q < p; q++) {
-      int64_t a, b;
-      chunk_of(x.recv_counts[q], c, &a, &b), pos += b - a;
-    }
-    return pos;
-  };
-  auto want_pos = [&](int c, int p) {
-    int64_t pos = want_start[c];
-    for (int q = 0; q < p; q++) {
-      int64_t a, b;
-      chunk_of(x.send_counts[q], c, &a, &b), pos += b - a;
-    }
-    return pos;
-  };
-  const char* serve_ids  = static_cast<const char*>(x.recv_ids);
-  const int64_t* want_raw = x.raw_indices;
-  if (C > 1 && fold_serve && x.total_recv > 0) {
-    void* cm = ids_cm_mem.device(x.total_recv, d.indices.dtype);
-    WM_BK(bk->permute_chunks(x.recv_ids, cm, static_cast<int>(ies), x.recv_offsets.data(), x.recv_counts.data(), W, C, stream));
-    g_dist_gather_launches.fetch_add(1, std::memory_order_relaxed);
-    serve_ids = static_cast<const char*>(cm);
-  }
-  if (C > 1 && fold_recv && x.total_send > 0) {
-    auto* cm = static_cast<int64_t*>(raw_cm_mem.device(x.total_send, WHOLEMEMORY_DT_INT64));
-    WM_BK(bk->permute_chunks(x.raw_indices, cm, 8, x.bucket_offsets.data(), x.send_counts.data(), W, C, stream));
-    g_dist_gather_launches.fetch_add(1, std::memory_order_relaxed);
-    want_raw = cm;
-  }
+  // W = 8, C = 4 — a measurable tax on mini-batch-sized gathers): the received ids (serving side) and the original positions
+  // of the requested rows (requesting side) are brought into chunk-major order once (exchange_plan.hpp), and the chunk's
+  // owner gather / reorder is one row kernel over one range of ids, positions, send buffer and receive buffer.
+  // (in_place: the rows are received where they belong — the requesting side stays peer-major and launches nothing)
+  const bool per_peer = exchange_per_peer(W);
+  const exchange_plan plan(x, comm->world_rank, C, self_local, per_peer || in_place, per_peer);
+  auto* serve_ids = static_cast<const char*>(chunk_major_copy(x.recv_ids, d.indices.dtype, plan.serve, &ids_cm_mem, &g_dist_gather_launches, stream));
+  auto* want_raw  = static_cast<const int64_t*>(chunk_major_copy(x.raw_indices, WHOLEMEMORY_DT_INT64, plan.want, &raw_cm_mem, &g_dist_gather_launches, stream));
   auto gather_range = [&](const char* ids, int64_t first, int64_t count) {   // ids[first ...] -> send buffer rows first ...
     if (count <= 0) return;
     int64_t lsz[2]  = {count, dim};
@@ -729,72 +744,20 @@ wholememory_error_code_t gather_distributed_rows(wholememory_handle_t handle, co
     WM_BK(bk->scatter_rows(&ra, stream));
     g_dist_gather_launches.fetch_add(1, std::memory_order_relaxed);
   };
-  auto gather_chunk = [&](int c) {
-    if (fold_serve) {
-      // (C == 1: the peer-major arrays are contiguous over the peers as they are)
-      gather_range(serve_ids, serve_start[c], serve_start[c + 1] - serve_start[c]);
-      return;
-    }
-    for (int p = 0; p < W; p++) {
-      int64_t a, b;
-      chunk_of(x.recv_counts[p], c, &a, &b);
-      gather_range(serve_ids, x.recv_offsets[p] + a, b - a);
-    }
-  };
-  auto exchange_chunk = [&](int c, void* on_stream) {
-    std::vector<int64_t> sc(W), so(W), rc(W), ro(W);
-    for (int p = 0; p < W; p++) {
-      int64_t a, b;
-      chunk_of(x.recv_counts[p], c, &a, &b);  // what this rank serves to p
-      sc[p] = b - a, so[p] = (fold_serve && C > 1) ? serve_pos(c, p) : x.recv_offsets[p] + a;
-      chunk_of(x.send_counts[p], c, &a, &b);  // what p serves to this rank
-      rc[p] = b - a, ro[p] = (fold_recv && C > 1) ? want_pos(c, p) : x.bucket_offsets[p] + a;
-    }
-    exchange_segments(comm, local_buf, sc, so, recv_buf, rc, ro, row_bytes, on_stream);
-  };
-  auto reorder_chunk = [&](int c) {
-    if (in_place) return;  // received where they belong
-    if (fold_recv && C > 1) {
-      reorder_range(want_raw, want_start[c], want_start[c + 1] - want_start[c]);
-      return;
-    }
-    if (fold_recv) {
-      // one chunk: the peers' rows are the bucketed order minus this rank's own segment — the range before it and the one after
-      const int64_t self_b = self_local ? x.self_offset : x.total_valid, self_e = self_local ? x.self_offset + x.self_count : x.total_valid;
-      reorder_range(x.raw_indices, 0, self_b);
-      reorder_range(x.raw_indices, self_e, x.total_valid - self_e);
-      return;
-    }
-    for (int p = 0; p < W; p++) {
-      if (p == rank && self_local) continue;
-      int64_t a, b;
-      chunk_of(x.send_counts[p], c, &a, &b);
-      reorder_range(x.raw_indices, x.bucket_offsets[p] + a, b - a);
-    }
-  };
-
-  if (C == 1) {
-    gather_chunk(0);
-    if (debug_sync_enabled()) WM_BK(bk->stream_sync(stream));
-    exchange_chunk(0, stream);
-    reorder_chunk(0);
-  } else {
-    void* side = comm->get_side_stream();
-    event_set gathered(C), arrived(C);
-    for (int c = 0; c < C; c++) {
-      gather_chunk(c);
-      WM_BK(bk->event_record(gathered[c], stream));
-      WM_BK(bk->stream_wait_event(side, gathered[c]));
-      exchange_chunk(c, side);
-      WM_BK(bk->event_record(arrived[c], side));
-      if (c >= 1) {
-        WM_BK(bk->stream_wait_event(stream, arrived[c - 1]));
-        reorder_chunk(c - 1);
-      }
-    }
-    WM_BK(bk->stream_wait_event(stream, arrived[C - 1]));  // also orders every side-stream access to the
-    reorder_chunk(C - 1);                                   // scratch buffers before anything later on `stream`
-  }
+  pipeline_chunks(
+    comm, C, stream,
+    [&](int c) {
+      for (const auto& r : plan.serve.ranges(c)) gather_range(serve_ids, r.first, r.second);
+      if (C == 1 && debug_sync_enabled()) WM_BK(bk->stream_sync(stream));
+    },
+    [&](int c, void* on_stream) {
+      const auto s = segments_of(plan.serve, plan.want, c);   // this rank serves what the peers want, and the other way round
+      exchange_segments(comm, local_buf, s.sc, s.so, recv_buf, s.rc, s.ro, row_bytes, on_stream);
+    },
+    [&](int c) {
+      if (in_place) return;
+      for (const auto& r : plan.want.ranges(c)) reorder_range(want_raw, r.first, r.second);
+    });
   if (debug_sync_enabled()) WM_BK(bk->stream_sync(stream));
   return WHOLEMEMORY_SUCCESS;
 }
@@ -1003,42 +966,25 @@ wholememory_error_code_t scatter_distributed(wholememory_handle_t handle, const 
     g_dist_scatter_launches.fetch_add(1, std::memory_order_relaxed);
   }
 
-  // (b)-(d) rows for the peers, pipelined in C row-chunks over two streams (same scheme as the gather):
-  //   L_c  line up chunk c of every peer's input rows in bucketed order (scatter_op_impl_nccl.cu:118-133) — HBM
-  //   A_c  rows all-to-all-v of chunk c                                                              — xGMI, side stream
-  //   S_c  owner writes (and casts) chunk c into its shard (scatter_op_impl_nccl.cu:145-166)          — HBM
-  // ONE launch per chunk and side (round 6, as the gather since round 5): the positions of the rows to send and the received
-  // ids are brought into chunk-major order once (ops_internal.hpp: chunk_layout), the send and receive buffers are laid out
-  // chunk-major, so L_c and S_c are one row kernel each over a contiguous range: 2 C + 3 kernels per call instead of
-  // 2 (W - 1) C + 1 (57 -> 11 at W = 8, C = 4). A scatter overwrites, duplicates are unordered in the reference
+  // (b)-(d) rows for the peers, in C row-chunks over two streams (ops_internal.hpp: pipeline_chunks):
+  //   L_c  line up chunk c of every peer's input rows in bucketed order (scatter_op_impl_nccl.cu:118-133)
+  //   A_c  rows all-to-all-v of chunk c
+  //   S_c  owner writes (and casts) chunk c into its shard (scatter_op_impl_nccl.cu:145-166)
+  // ONE launch per chunk and side (round 6, as the gather since round 5; exchange_plan.hpp): 2 C + 3 kernels per call instead
+  // of 2 (W - 1) C + 1 (57 -> 11 at W = 8, C = 4). A scatter overwrites, duplicates are unordered in the reference
   // (gather_scatter_func.cuh:519-598), so the order in which the owner writes received rows is free.
   const size_t row_bytes = static_cast<size_t>(dim) * pes;
   const int W            = comm->world_size;
-  const int rank         = comm->world_rank;
   const int C            = exchange_chunks(W, x.global_moved);
   const auto in_gref     = wholememory_create_continuous_global_reference(d.plain_ptr);
-  const bool per_peer    = bk->permute_chunks == nullptr || W > 16 || W <= 2 /* one peer: a chunk is one range already */ ||
-                        (WM_KNOB("WM_EXCHANGE_PER_PEER") != nullptr && WM_KNOB("WM_EXCHANGE_PER_PEER")[0] == '1');
-  const bool folded = !per_peer && C > 1;   // chunk-major buffers
-  const chunk_layout want(x.send_counts, C), serve(x.recv_counts, C);
+  const bool per_peer    = exchange_per_peer(W);
+  const exchange_plan plan(x, comm->world_rank, C, self_local, per_peer, per_peer);
   temp_mem send_rows(env), recv_rows(env), raw_cm_mem(env), ids_cm_mem(env);
   // (peer-major: the send buffer keeps the bucketed layout, this rank's own segment stays unused)
-  char* send_buf = static_cast<char*>(send_rows.device(dim * (folded ? x.total_send : x.total_valid), d.plain.dtype));
+  char* send_buf = static_cast<char*>(send_rows.device(dim * (plan.want.chunk_major() ? x.total_send : x.total_valid), d.plain.dtype));
   char* recv_buf = static_cast<char*>(recv_rows.device(dim * x.total_recv, d.plain.dtype));
-  const int64_t* send_raw = x.raw_indices;
-  const char* write_ids   = static_cast<const char*>(x.recv_ids);
-  if (folded && x.total_send > 0) {
-    auto* cm = static_cast<int64_t*>(raw_cm_mem.device(x.total_send, WHOLEMEMORY_DT_INT64));
-    WM_BK(bk->permute_chunks(x.raw_indices, cm, 8, x.bucket_offsets.data(), x.send_counts.data(), W, C, stream));
-    g_dist_scatter_launches.fetch_add(1, std::memory_order_relaxed);
-    send_raw = cm;
-  }
-  if (folded && x.total_recv > 0) {
-    void* cm = ids_cm_mem.device(x.total_recv, d.indices.dtype);
-    WM_BK(bk->permute_chunks(x.recv_ids, cm, static_cast<int>(ies), x.recv_offsets.data(), x.recv_counts.data(), W, C, stream));
-    g_dist_scatter_launches.fetch_add(1, std::memory_order_relaxed);
-    write_ids = static_cast<const char*>(cm);
-  }
+  auto* send_raw  = static_cast<const int64_t*>(chunk_major_copy(x.raw_indices, WHOLEMEMORY_DT_INT64, plan.want, &raw_cm_mem, &g_dist_scatter_launches, stream));
+  auto* write_ids = static_cast<const char*>(chunk_major_copy(x.recv_ids, d.indices.dtype, plan.serve, &ids_cm_mem, &g_dist_scatter_launches, stream));
   auto lineup_range = [&](const int64_t* raw, int64_t first, int64_t count) {   // in[raw[first ...]] -> send buffer rows first ...
     if (count <= 0) return;
     int64_t ssz[2] = {count, dim};
@@ -1058,59 +1004,13 @@ wholememory_error_code_t scatter_distributed(wholememory_handle_t handle, const 
     WM_BK(bk->scatter_rows(&wa, stream));
     g_dist_scatter_launches.fetch_add(1, std::memory_order_relaxed);
   };
-  auto lineup_chunk = [&](int c) {
-    if (folded) {
-      lineup_range(send_raw, want.start(c), want.size(c));
-    } else if (!per_peer) {
-      // one chunk: the rows to send are the bucketed order minus this rank's own segment — the range before it and the one after
-      const int64_t self_b = self_local ? x.self_offset : x.total_valid, self_e = self_local ? x.self_offset + x.self_count : x.total_valid;
-      lineup_range(x.raw_indices, 0, self_b);
-      lineup_range(x.raw_indices, self_e, x.total_valid - self_e);
-    } else {
-      for (int p = 0; p < W; p++) {
-        if (p == rank && self_local) continue;
-        lineup_range(x.raw_indices, x.bucket_offsets[p] + want.first(c, p), want.count(c, p));
-      }
-    }
-  };
-  auto exchange_chunk = [&](int c, void* on_stream) {
-    std::vector<int64_t> sc(W), so(W), rc(W), ro(W);
-    for (int p = 0; p < W; p++) {
-      sc[p] = want.count(c, p), so[p] = folded ? want.pos(c, p) : x.bucket_offsets[p] + want.first(c, p);
-      rc[p] = serve.count(c, p), ro[p] = folded ? serve.pos(c, p) : x.recv_offsets[p] + serve.first(c, p);
-    }
-    exchange_segments(comm, send_buf, sc, so, recv_buf, rc, ro, row_bytes, on_stream);
-  };
-  auto write_chunk = [&](int c) {
-    if (folded) {
-      write_range(write_ids, serve.start(c), serve.size(c));
-    } else if (!per_peer) {
-      write_range(write_ids, 0, x.total_recv);   // one chunk: everything received is one contiguous range
-    } else {
-      for (int p = 0; p < W; p++) write_range(write_ids, x.recv_offsets[p] + serve.first(c, p), serve.count(c, p));
-    }
-  };
-  if (C == 1) {
-    lineup_chunk(0);
-    exchange_chunk(0, stream);
-    write_chunk(0);
-  } else {
-    void* side = comm->get_side_stream();
-    event_set lined_up(C), arrived(C);
-    for (int c = 0; c < C; c++) {
-      lineup_chunk(c);
-      WM_BK(bk->event_record(lined_up[c], stream));
-      WM_BK(bk->stream_wait_event(side, lined_up[c]));
-      exchange_chunk(c, side);
-      WM_BK(bk->event_record(arrived[c], side));
-      if (c >= 1) {
-        WM_BK(bk->stream_wait_event(stream, arrived[c - 1]));
-        write_chunk(c - 1);
-      }
-    }
-    WM_BK(bk->stream_wait_event(stream, arrived[C - 1]));
-    write_chunk(C - 1);
-  }
+  pipeline_chunks(
+    comm, C, stream, [&](int c) { for (const auto& r : plan.want.ranges(c)) lineup_range(send_raw, r.first, r.second); },
+    [&](int c, void* on_stream) {
+      const auto s = segments_of(plan.want, plan.serve, c);
+      exchange_segments(comm, send_buf, s.sc, s.so, recv_buf, s.rc, s.ro, row_bytes, on_stream);
+    },
+    [&](int c) { for (const auto& r : plan.serve.ranges(c)) write_range(write_ids, r.first, r.second); });
   WM_BK(bk->stream_sync(stream));  // scatter_op_impl_nccl.cu:168
   return WHOLEMEMORY_SUCCESS;
 }

@@ -2,6 +2,8 @@
 // aggregate.cpp, gat.cpp): scratch from the caller's env functions, the id sort, the id / row exchanges.
 #pragma once
 
+#include <atomic>
+#include <functional>
 #include <vector>
 
 #include <wholememory/wholegraph_amd_ext.h>
@@ -9,6 +11,7 @@
 
 #include "backend.hpp"
 #include "communicator.hpp"
+#include "exchange_plan.hpp"
 #include "wm_common.hpp"
 
 namespace wm {
@@ -119,47 +122,51 @@ void exchange_rows(wholememory_comm_t comm, const void* send, const std::vector<
 // global_moved = id_exchange::global_moved, so that every rank decides alike
 int exchange_chunks(int world_size, int64_t global_moved);
 
-// Chunk-major order of per-peer segments (backend.hpp: permute_chunks): chunk c of a segment of n rows is rows
-// [n*c/C, n*(c+1)/C) of it — the same cut on both ends of a pair, so the sizes of an exchanged chunk always match — and the
-// chunk-major order lists chunk 0 of every segment (in peer order), then chunk 1 of every segment, ... A chunk of the
-// pipelined exchange is then ONE contiguous range of ids, positions and row buffer: one row kernel per chunk and side
-// whatever the number of ranks (distributed gather since round 5; distributed scatter and gradient apply since round 6).
-struct chunk_layout {
-  chunk_layout(const std::vector<int64_t>& counts, int n_chunks) : counts_(counts), C_(n_chunks), start_(n_chunks + 1, 0)
-  {
-    for (int c = 0; c < C_; c++) {
-      int64_t s = 0;
-      for (size_t p = 0; p < counts_.size(); p++) s += count(c, static_cast<int>(p));
-      start_[c + 1] = start_[c] + s;
-    }
-  }
-  int64_t first(int c, int p) const { return counts_[p] * c / C_; }                 // first row of chunk c inside segment p
-  int64_t count(int c, int p) const { return counts_[p] * (c + 1) / C_ - counts_[p] * c / C_; }
-  int64_t start(int c) const { return start_[c]; }                                   // where chunk c begins, chunk-major
-  int64_t size(int c) const { return start_[c + 1] - start_[c]; }
-  int64_t pos(int c, int p) const                                                    // where chunk c of segment p begins
-  {
-    int64_t at = start_[c];
-    for (int q = 0; q < p; q++) at += count(c, q);
-    return at;
-  }
-  int64_t total() const { return start_[C_]; }
-
- private:
-  std::vector<int64_t> counts_;
-  int C_;
-  std::vector<int64_t> start_;
-};
-
 // RAII bundle of backend events
 class event_set {
  public:
   explicit event_set(int n);
   ~event_set();
+  event_set(event_set&& o) noexcept : events_(std::move(o.events_)) {}
   void* operator[](int i) const { return events_[i]; }
 
  private:
   std::vector<void*> events_;
+};
+
+// ---- the chunked row exchange of the distributed gather, the distributed scatter and the sparse gradient apply ----------
+// (exchange_plan.hpp has its index arithmetic; loopback — WM_EXCHANGE_SELF=1 — makes the self segment travel like a peer's)
+
+// One row kernel per PEER, chunk and side (2 (W - 1) C + 1 per call; rounds 2-4) instead of one per chunk and side: backends
+// without permute_chunks, more than 16 ranks, one peer (a chunk is one range already), or the knob that asks for it
+bool exchange_per_peer(int world_size);
+
+// `src` (raw_indices or recv_ids: the peer-major array of `side`) as the side's row ranges index it: `src` itself unless the
+// side is chunk-major and has rows — then a chunk-major copy in `mem`, made by one small kernel that `launches` counts
+const void* chunk_major_copy(const void* src, wholememory_dtype_t dtype, const exchange_side& side, temp_mem* mem,
+                             std::atomic<int64_t>* launches, void* stream);
+
+// The two-stream pipeline over C chunks. produce(c) fills chunk c of the send buffer on `stream` (HBM), exchange(c, s) is
+// its all-to-all-v on stream s (xGMI), consume(c) uses what arrived, on `stream` again (HBM). With one chunk all three run
+// on `stream`, without events. Otherwise the exchanges run on the communicator's side stream and the issue order on `stream`
+// is P_0 P_1 C_0 P_2 C_1 ... (for the gather G_0 G_1 R_0 G_2 R_1 ...), so that P_{c+1} and C_{c-1} run while chunk c is on the
+// links; the wait for the last chunk also orders every side-stream access to the buffers before anything later on `stream`.
+// consume may be empty: nothing on `stream` then waits for the rows, and the ONE event recorded behind the last exchange is
+// returned for whoever reads them — it must live until that wait is queued. (Empty set: one chunk, or a consume stage.)
+using chunk_stage = std::function<void(int)>;
+event_set pipeline_chunks(wholememory_comm_t comm, int C, void* stream, const chunk_stage& produce,
+                          const std::function<void(int, void*)>& exchange, const chunk_stage& consume);
+
+// Receive layout of the gradient routes: ids and rows of ALL requesters in rank-major order (that order defines the fp32
+// summation order of duplicates), this rank's own segment in its slot among the peers'
+struct rank_major_recv {
+  rank_major_recv(const id_exchange& x, wholememory_comm_t comm);
+  // the ids: the peers' segments were received compactly (self cut out) — into `dst` around the self slot, which is filled
+  // from the bucketed ids (self_from_bucketed) or from what the loopback exchange delivered
+  void place_ids(const id_exchange& x, size_t id_bytes, bool self_from_bucketed, char* dst, void* stream) const;
+  std::vector<int64_t> counts, offsets;  // [W], [W+1]
+  int64_t n_recv;
+  int rank;
 };
 
 // row offsets [W+1] of a handle whose rows are entry_bytes wide

@@ -19,6 +19,8 @@
  *      deterministic backward).
  *      (2h) the relation-typed neighbour aggregation of a sampled CSC block behind the RGCN layer: (2b) with a type per edge
  *      and one output slot per relation (forward and a deterministic backward).
+ *      (2i) 8-bit row-quantized tables: a gather that dequantizes the rows it reads and a scatter that quantizes the rows
+ *      it writes.
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -810,6 +812,73 @@ enum wholememory_error_code_t wholememory_ext_csc_rel_aggregate_backward(const i
                                                                          int64_t grad_x_stride,
                                                                          struct wholememory_env_func_t* p_env_fns,
                                                                          void* stream);
+
+/* ---- (2i) 8-bit row-quantized tables: fused gather + dequantize, quantize + scatter ---------------------------------- */
+/* A quantized table of logical shape [N, dim] is an ordinary 2-D INT8 WholeMemory tensor [N, >= row_bytes] whose bytes are
+ * read as unsigned. With Q = round_up(dim, 4) and row_bytes = Q + 8, a row is
+ *   bytes [0, dim)      the codes c[j] (uint8)
+ *   bytes [dim, Q)      zero
+ *   bytes [Q, Q + 4)    scale, fp32, little endian
+ *   bytes [Q + 4, Q+8)  bias, fp32, little endian
+ * The row stride in bytes is >= row_bytes and a multiple of 4, and the view's storage offset is a multiple of 4 bytes:
+ * row-range sub-tensors are fine, a column-offset view that breaks the rule is INVALID_INPUT. Being a plain INT8 tensor,
+ * the storage works with file I/O, every memory type and every location unchanged.
+ *
+ * quantize(x[0..dim)), x fp32; every operation below is one fp32 operation rounded on its own (no fused multiply-add):
+ *   lo = min(x), hi = max(x), r = hi - lo
+ *   r == 0: scale = 1.0f, inv = 1.0f (every code 0); else scale = r / 255.0f, inv = 255.0f / r
+ *   c[j] = (uint8) clamp(rintf((x[j] - lo) * inv), 0, 255)          rint: round half to even
+ *   bias = lo; a zero minimum is stored as +0.0 whatever the signs of the row's zeros (bias = lo + 0.0f)
+ * dequantize: y[j] = (float)c[j] * scale + bias, a multiply then an add (two roundings), then rounded once more, to nearest
+ * even, when the output is HALF or BF16. min and max do not depend on the order they are taken in: results are bitwise
+ * reproducible. The inputs must be finite with hi - lo finite; anything else is outside the contract (the bytes written are
+ * unspecified, no address depends on them).
+ *
+ * wholememory_ext_gather_dequantize: for indices[i] >= 0, output[i, 0:dim) = dequantize(row indices[i] of q_table); a
+ * negative id leaves the output row untouched, as wholememory_gather does. indices NULL: rows 0 .. n-1 with n = the rows of
+ * output. output is FLOAT, HALF or BF16, 2-D with dim columns and its own row stride and storage offset.
+ * wholememory_ext_quantize_scatter: for indices[i] >= 0, row indices[i] of q_table = quantize(input[i, :]) — codes, the
+ * zero bytes and the trailer; bytes of the row past row_bytes are left alone. input is FLOAT, 2-D with dim columns.
+ * Duplicate ids have no defined winner, as in wholememory_scatter. indices NULL: rows 0 .. n-1 with n = the rows of input.
+ * Ids at or past the rows of q_table are the caller's contract, as for gather and scatter.
+ *
+ * Routes. CONTINUOUS and CHUNKED tables (device or host located) and a handle-less tensor
+ * (wholememory_make_tensor_from_pointer: a local buffer) are read / written by one kernel that addresses the rows through
+ * the table's global reference. DISTRIBUTED and HIERARCHY tables, and mapped tables served through the exchange
+ * (WM_MAPPED_VIA_EXCHANGE=1), take two steps — collective like wholememory_gather / wholememory_scatter on such tables, and
+ * needing indices: the raw rows move with wholememory_gather into a [n, row_bytes] temporary that is then dequantized in
+ * place order (the ids only marking the rows to skip), or are quantized into such a temporary that wholememory_scatter then
+ * moves; the links carry quantized bytes. A gather of a batch large enough for the sorted-ids gather of HOST-located tables
+ * (WM_HOST_SORTED_MIN ids, rows of at most 512 bytes) from such a table takes the same two steps, for the sake of that
+ * gather's row order. Scratch comes from p_env_fns only. gather_sms / scatter_sms cap the grid as for
+ * gather and scatter (-1: default).
+ *
+ * Before any device work, and under every backend: INVALID_INPUT for a null q_table / output / input, dim < 1, a q_table
+ * that is not 2-D INT8 with unit inner stride, sizes[1] < row_bytes, a row stride below row_bytes or no multiple of 4, a
+ * storage offset that is no multiple of 4, an output / input that is not 2-D with dim columns and unit inner stride or whose
+ * dtype is a floating type other than the ones named above, indices that are not 1-D INT / INT64 or outnumber the rows of
+ * output / input, null indices with more rows than q_table has (or on an exchange-served table), and a null data pointer
+ * where rows are to be moved; LOGIC_ERROR for an output / input of an integer dtype (the float <-> integer mix
+ * wholememory_gather refuses the same way). Then NOT_SUPPORTED (nothing queued) when the device backend has no such
+ * kernels, then success without a launch for n = 0 on a mapped table. */
+int64_t wholememory_ext_quantized_row_bytes(int64_t dim); /* Q + 8; -1 for dim < 1 */
+enum wholememory_error_code_t wholememory_ext_gather_dequantize(wholememory_tensor_t q_table,
+                                                                int64_t dim,
+                                                                wholememory_tensor_t indices /* may be NULL */,
+                                                                wholememory_tensor_t output,
+                                                                struct wholememory_env_func_t* p_env_fns,
+                                                                void* stream,
+                                                                int gather_sms);
+enum wholememory_error_code_t wholememory_ext_quantize_scatter(wholememory_tensor_t input,
+                                                               wholememory_tensor_t indices /* may be NULL */,
+                                                               wholememory_tensor_t q_table,
+                                                               int64_t dim,
+                                                               struct wholememory_env_func_t* p_env_fns,
+                                                               void* stream,
+                                                               int scatter_sms);
+/* wholememory_ext_gather_dequantize calls served by the fused kernel that reads the table itself (this process): a counter
+ * for tests, it tells that route from the two steps. */
+int64_t wholememory_ext_gather_dequantize_calls(void);
 
 /* ---- (3) testing seam ---------------------------------------------------------------------- */
 /* Replaces the device backend. Refuses (WHOLEMEMORY_NOT_SUPPORTED) unless the environment has

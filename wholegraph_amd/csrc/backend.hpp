@@ -339,6 +339,25 @@ struct wm_relagg_args {
   int64_t out_stride;         //   [n_src, out_stride]
 };
 
+// 8-bit row-quantized tables (kernels/qrows.hip, wholegraph_amd_ext.h section 2i): a row is round_up(dim, 4) code bytes, then
+// fp32 scale and fp32 bias. gather: plain[i, 0:dim) = dequantize(row of entry i); scatter: row of entry i = quantize(plain[i]).
+// The row of entry i is table row indices[i] — or, with `positions`, row i itself (`indices`, when not null, then only marks
+// the entries to skip). An entry with a negative id is skipped either way.
+struct wm_qrows_args {
+  wholememory_gref_t gref;            // the table's bytes (continuous or chunked; a local buffer is a continuous gref)
+  int64_t table_stride;               // BYTES between rows: >= round_up(dim, 4) + 8, a multiple of 4
+  int64_t table_storage_offset;       // BYTES, a multiple of 4
+  int64_t dim;                        // values per row
+  int positions;
+  const void* indices;                // [n] int32 / int64, device; nullptr only with `positions`
+  wholememory_dtype_t index_dtype;
+  int64_t n;
+  void* plain;                        // gather: output (FLOAT, HALF or BF16); scatter: input (FLOAT); already offset
+  wholememory_dtype_t plain_dtype;
+  int64_t plain_stride;               // elements
+  int max_blocks;                     // "gather_sms" / "scatter_sms": <= 0 = default
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -584,7 +603,10 @@ struct wm_device_backend {
   // (agg_backward_workspace_bytes)
   int (*relagg_forward)(const wm_relagg_args* a, void* stream);
   int (*relagg_backward)(const wm_relagg_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                         const int64_t* n_unique_dev, void* workspace, void* stream);
+                         const int64_t* n_unique_dev, void* workspace, void* stream);  // ---- 8-bit row-quantized tables (kernels/qrows.hip, wholegraph_amd_ext.h section 2i); nullptr in a backend without
+  // them ----
+  int (*qrows_gather_dequant)(const wm_qrows_args* a, void* stream);
+  int (*qrows_quantize_scatter)(const wm_qrows_args* a, void* stream);
 };
 
 }  // extern "C"

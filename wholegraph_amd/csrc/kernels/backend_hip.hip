@@ -99,6 +99,8 @@ int hip_gatv2_backward(const wm_gatv2_args* a, const int32_t* order, const int32
 int hip_relagg_forward(const wm_relagg_args* a, void* stream);
 int hip_relagg_backward(const wm_relagg_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
                         const int64_t* n_unique_dev, void* workspace, void* stream);
+int hip_qrows_gather_dequant(const wm_qrows_args* a, void* stream);
+int hip_qrows_quantize_scatter(const wm_qrows_args* a, void* stream);
 
 namespace {
 
@@ -288,6 +290,8 @@ const wm_device_backend kHipBackend = {
   hip_gatv2_backward,
   hip_relagg_forward,
   hip_relagg_backward,
+  hip_qrows_gather_dequant,
+  hip_qrows_quantize_scatter,
 };
 
 }  // namespace

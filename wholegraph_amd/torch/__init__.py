@@ -9,12 +9,12 @@ GraphSAGE layer ``cugraphops.EdgeWeightedSAGEConv`` on ``weighted_aggregation``,
 ``cugraphops.EdgeGATConv`` on ``edge_gat_aggregation``, the GATv2 layer ``cugraphops.GATv2Conv`` on ``gatv2_aggregation``
 (model name "gatv2"), the RGCN layer ``cugraphops.RGCNConv`` on ``rel_aggregation`` (model name "rgcn"), and
 ``gather_aggregation``, layer 0's aggregation straight from a
-WholeMemory table). GAT in ``HomoGNNModel``, the dgl / pyg / wg
-routes, data loaders, launch helpers and option parsers of the reference are outside this build's scope.
+WholeMemory table, and ``quantized``, 8-bit row-quantized tables whose gather dequantizes the rows it reads). GAT in
+``HomoGNNModel``, the dgl / pyg / wg routes, data loaders, launch helpers and option parsers of the reference are outside this build's scope.
 """
 from . import comm, embedding, graph_ops, graph_structure, initialize, tensor, utils, wholegraph_ops, wholememory_ops
 from . import aggregation, cugraphops, edge_gat_aggregation, gat_aggregation, gather_aggregation, gnn_model
-from . import gatv2_aggregation, rel_aggregation, weighted_aggregation
+from . import gatv2_aggregation, quantized, rel_aggregation, weighted_aggregation
 
 _PUBLIC = {
     comm: ("WholeMemoryCommunicator create_group_communicator destroy_communicator get_global_communicator "
@@ -31,9 +31,11 @@ _PUBLIC = {
     graph_structure: "GraphStructure",
     gnn_model: "set_framework create_gnn_layers create_rgcn_layers create_sub_graph HomoGNNModel",
     gather_aggregation: "gather_agg_concat",
+    quantized: ("WholeMemoryQuantizedTensor create_quantized_tensor quantized_row_bytes quantize_rows "
+                "dequantize_rows"),
 }
 __all__ = ["graph_ops", "wholegraph_ops", "aggregation", "cugraphops", "gat_aggregation", "gnn_model", "weighted_aggregation",
-           "gather_aggregation", "edge_gat_aggregation", "gatv2_aggregation", "rel_aggregation"]
+           "gather_aggregation", "edge_gat_aggregation", "gatv2_aggregation", "rel_aggregation", "quantized"]
 for _module, _names in _PUBLIC.items():
     for _name in _names.split():
         globals()[_name] = getattr(_module, _name)

@@ -221,6 +221,64 @@ def test_oracle_weighted_sampler_matches_reference_host_statement(m, wdtype):
     assert np.array_equal(ids, col[egid]) and np.array_equal(lid, np.repeat(np.arange(len(centers)), np.diff(off)))
 
 
+@pytest.mark.parametrize("m", [1, 33, 65, 257, 1024])
+@pytest.mark.parametrize("cls", ["half_zero", "extremes32", "extremes64"])
+def test_oracle_weighted_sampler_matches_reference_host_statement_on_the_ladder(cls, m):
+    """The same restatement on the inputs of tests/test_sampler_edges_gpu.py, so that the reference the GPU is held to there is
+    itself pinned without a GPU: the degree ladder (degrees <= 4098 here, to keep the Python restatement at a few seconds) with
+    zero weights, weights whose float32 reciprocal overflows or is subnormal, +inf, and float64 weights outside float32's
+    range. No key may be NaN (the comparator would not be a total order), equal keys go by neighbour index."""
+    import test_sampler_edges_gpu as edges
+    row_ptr, col, centers = edges.ladder_graph(max_degree=4098)
+    weights = edges.ladder_weights(cls, col.shape[0])
+    deg = edges.assert_ladder_classes(row_ptr, centers, m, max_degree=4098)
+    seed = edges.weighted_seed(m)
+    off, ids, lid, egid = oracle.sample_weighted(row_ptr, col, weights, centers, m, seed)
+    w32 = edges.as_float32(weights)
+    want = []
+    for c, nid in enumerate(centers):
+        s, n = int(row_ptr[nid]), int(deg[c])
+        if n <= m:
+            want.append(np.arange(s, s + n))
+            continue
+        keys = edges.host_statement_keys(w32, s, n, c, m, seed)
+        assert not np.isnan(keys).any()
+        want.append(s + np.lexsort((np.arange(n), -keys.astype(np.float64)))[:m])
+    assert np.array_equal(egid, np.concatenate(want))
+    assert np.array_equal(ids, col[egid]) and np.array_equal(lid, np.repeat(np.arange(len(centers)), np.diff(off)))
+    edges.assert_sample_structure(row_ptr, centers, m, off, egid)
+    if cls == "half_zero":
+        edges.assert_zero_weight_order(row_ptr, centers, weights, m, off, egid)
+
+
+def test_oracle_weighted_sampler_all_zero_weights_take_the_first_neighbours():
+    import test_sampler_edges_gpu as edges
+    row_ptr, col, centers = edges.ladder_graph(max_degree=4098)
+    weights = edges.ladder_weights("zeros", col.shape[0])
+    for m in (1, 33, 65, 257, 1024):
+        off, ids, lid, egid = oracle.sample_weighted(row_ptr, col, weights, centers, m, edges.weighted_seed(m))
+        deg = edges.center_degrees(row_ptr, centers)
+        want = [np.arange(row_ptr[nid], row_ptr[nid] + min(int(d), m)) for nid, d in zip(centers, deg)]
+        assert np.array_equal(egid, np.concatenate(want))
+        edges.assert_zero_weight_order(row_ptr, centers, weights, m, off, egid)
+
+
+@pytest.mark.parametrize("m", [20, 40, 100, 300])
+def test_oracle_first_pick_follows_the_weights(m):
+    """The first (largest-key) pick of a weighted sample is neighbour i with probability w_i / sum(w) whatever the fan-out:
+    chi-square over 8000 nodes with 320 neighbours of weights [1, 2, 3, 4, 5, 6, 7, 12] tiled, 7 degrees of freedom, bound 40
+    (p ~ 1e-6) as in the GPU test of the same name. Fan-outs up to 256 share streams and keys: 7.2 (seed 424242) and 9.1 (seed
+    7); fan-out 300 uses 256 virtual threads: 2.5 and 8.6."""
+    import test_sampler_edges_gpu as edges
+    row_ptr, col, weights = edges.first_pick_graph()
+    centers = np.arange(edges.FIRST_PICK_NODES, dtype=np.int32)
+    for seed in edges.FIRST_PICK_SEEDS:
+        off, ids, _, _ = oracle.sample_weighted(row_ptr, col, weights, centers, m, seed, need_lid=False, need_egid=False)
+        chi2 = edges.first_pick_chi_square(ids, m)
+        print("oracle first pick, max_sample_count %d, seed %d: chi-square %.2f over 7 dof" % (m, seed, chi2))
+        assert chi2 < 40.0, "chi-square %.1f over 7 dof at max_sample_count=%d, seed %d" % (chi2, m, seed)
+
+
 def test_sampling_recurrence_closed_form():
     """The closed form sample_small_kernel evaluates (csrc/kernels/graph.hip) against the sequential recurrence of the reference
     (unweighted_sample_without_replacement_func.cuh: a[i] = Q[r_i]; Q[r_i] = Q[N-1-i] over a sparse image of Q): lane i looks for

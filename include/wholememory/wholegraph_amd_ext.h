@@ -21,6 +21,8 @@
  *      and one output slot per relation (forward and a deterministic backward).
  *      (2i) 8-bit row-quantized tables: a gather that dequantizes the rows it reads and a scatter that quantizes the rows
  *      it writes.
+ *      (2j) the neighbour aggregation of (2b) whose rows are read, and dequantized, from a quantized table of (2i) by
+ *      global id (forward).
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -879,6 +881,51 @@ enum wholememory_error_code_t wholememory_ext_quantize_scatter(wholememory_tenso
 /* wholememory_ext_gather_dequantize calls served by the fused kernel that reads the table itself (this process): a counter
  * for tests, it tells that route from the two steps. */
 int64_t wholememory_ext_gather_dequantize_calls(void);
+
+/* ---- (2j) agg_concat straight from a quantized table (`gather_agg_concat` over a quantized source) ------------------- */
+/* (2e) over a table of (2i): layer 0 of a GNN over 8-bit row-quantized features without the dequantized [n_src, dim]
+ * intermediate. `table` is the 2-D INT8 tensor [N, >= row_bytes] of (2i) — Q = round_up(dim, 4) code bytes, fp32 scale, fp32
+ * bias per row; row stride >= row_bytes = Q + 8 and a multiple of 4 bytes, storage offset a multiple of 4 bytes — and `dim`
+ * its logical width. node_ids [n_src] (WHOLEMEMORY_DT_INT or WHOLEMEMORY_DT_INT64, device memory) holds the global row of
+ * every node of the block, the targets first. Define, for i < n_src and j < dim,
+ *   x[i][j] = (float)c[j] * scale + bias    of table row node_ids[i]: the dequantize of (2i), a multiply then an add, each
+ *                                           one fp32 operation rounded on its own (no fused multiply-add).
+ * Then, with row_ptr int32 [n_dst + 1] and col_ind int32 [n_edges] in [0, n_src) as for (2b):
+ *   out[d, 0:dim]    = A(d) of (2b) over x: S(d) = fp32 sum of x[col_ind[e]] for e = row_ptr[d] .. row_ptr[d+1] - 1, started
+ *                      at -0.0f and added in ascending edge position; SUM: A = S; MEAN: A = S * fl(1.0f / (float)deg(d)); a
+ *                      target without edges: +0.0.
+ *   out[d, dim:2dim] = x[d].
+ * out [n_dst, out_stride] is fp32, out_stride >= 2 * dim; columns at and past 2 * dim are left alone, and neither the zero
+ * bytes behind column dim of a row nor its trailer reach out. Hence the result equals
+ * wholememory_ext_csc_aggregate_forward over the FLOAT rows wholememory_ext_gather_dequantize writes for node_ids, bit for
+ * bit. Every id must lie in [0, N): the op does not check, an id out of range is undefined (there is no "skip me" id here).
+ * A row-range sub-tensor is honoured. There is no backward entry point: a quantized table holds frozen features.
+ *
+ * In this order: INVALID_INPUT, before any device work and under every backend, for a null table, a table that is not 2-D,
+ * not INT8 or whose inner stride is not 1, dim < 1, rows of fewer than row_bytes bytes, a row stride below row_bytes or no
+ * multiple of 4, a storage offset that is no multiple of 4, a node_id_dtype other than INT / INT64, what (2b) rejects (null
+ * pointers, negative counts, n_dst > n_src, out_stride < 2 * dim, an unknown aggr) and node ids into a table without rows.
+ * Then NOT_SUPPORTED when the device backend has no such kernel. Then NOT_SUPPORTED for a table whose handle is neither
+ * CONTINUOUS nor CHUNKED (DISTRIBUTED, HIERARCHY) or that is served through the exchange (WM_MAPPED_VIA_EXCHANGE=1): gather
+ * with (2i), then (2b). Nothing is queued in any refused case. CONTINUOUS and CHUNKED tables (device- or host-located) and
+ * handle-less tensors are read through their global reference, by the calling rank alone. */
+enum wholememory_error_code_t wholememory_ext_csc_gather_dequantize_aggregate_forward(wholememory_tensor_t table,
+                                                                                      int64_t dim,
+                                                                                      const void* node_ids,
+                                                                                      int node_id_dtype,
+                                                                                      const int32_t* row_ptr,
+                                                                                      const int32_t* col_ind,
+                                                                                      int64_t n_edges,
+                                                                                      int64_t n_dst,
+                                                                                      int64_t n_src,
+                                                                                      int aggr,
+                                                                                      float* out,
+                                                                                      int64_t out_stride,
+                                                                                      struct wholememory_env_func_t* p_env_fns,
+                                                                                      void* stream);
+/* wholememory_ext_csc_gather_dequantize_aggregate_forward calls that launched on the device backend (this process). A
+ * counter for tests: it tells the fused route from the (2i) gather + (2b) composition. */
+int64_t wholememory_ext_gather_dequantize_aggregate_calls(void);
 
 /* ---- (3) testing seam ---------------------------------------------------------------------- */
 /* Replaces the device backend. Refuses (WHOLEMEMORY_NOT_SUPPORTED) unless the environment has

@@ -318,6 +318,9 @@ PROTOTYPES = {
     "wholememory_ext_gather_dequantize": (_i, [_vp, _i64, _vp, _vp, _P(EnvFunc), _vp, _i]),
     "wholememory_ext_quantize_scatter": (_i, [_vp, _vp, _vp, _i64, _P(EnvFunc), _vp, _i]),
     "wholememory_ext_gather_dequantize_calls": (_i64, []),
+    "wholememory_ext_csc_gather_dequantize_aggregate_forward": (_i, [_vp, _i64, _vp, _i, _vp, _vp, _i64, _i64, _i64, _i, _vp,
+                                                                    _i64, _P(EnvFunc), _vp]),
+    "wholememory_ext_gather_dequantize_aggregate_calls": (_i64, []),
     "wm_testing_install_backend": (_i, [_vp]),
 }
 

@@ -2,8 +2,8 @@
 // validation, the edge index of the backward (the library's id sort over col_ind) and the launches of kernels/agg.hip
 // (fp32 rows), kernels/agg_half.hip (fp16 / bf16 rows, the _typed entry points) and kernels/agg_weighted.hip (a weight per
 // edge, section 2d, the _weighted entry points) and kernels/agg_gather.hip (rows read from a WholeMemory table by global id,
-// section 2e) and kernels/agg_rel.hip (a type per edge and a slot per relation, section 2h, the _rel_ entry points). The
-// semantics, and the one order of every fp32 sum, are stated in the header.
+// section 2e) and kernels/agg_quant.hip (the same from an 8-bit row-quantized table, section 2j) and kernels/agg_rel.hip (a
+// type per edge and a slot per relation, section 2h, the _rel_ entry points). The semantics, and the one order of every fp32 sum, are stated in the header.
 #include <atomic>
 
 #include <wholememory/wholegraph_amd_ext.h>
@@ -45,6 +45,7 @@ void backward_over_index(const wm_device_backend* bk, const int32_t* col_ind, in
 bool rows16(wholememory_dtype_t dtype) { return dtype == WHOLEMEMORY_DT_HALF || dtype == WHOLEMEMORY_DT_BF16; }
 
 std::atomic<int64_t> g_gather_agg_calls{0};   // fused forwards that reached the backend
+std::atomic<int64_t> g_qagg_calls{0};         // the same over a quantized table (section 2j)
 
 // what the two _rel_ entry points check alike, ahead of check_args
 void check_rel(const int32_t* edge_type, int64_t n_edges, int64_t num_relations, int aggr, const float* edge_scale)
@@ -274,6 +275,56 @@ wholememory_error_code_t wholememory_ext_csc_gather_aggregate_forward(wholememor
 }
 
 int64_t wholememory_ext_gather_aggregate_calls(void) { return g_gather_agg_calls.load(std::memory_order_relaxed); }
+
+wholememory_error_code_t wholememory_ext_csc_gather_dequantize_aggregate_forward(
+  wholememory_tensor_t table, int64_t dim, const void* node_ids, int node_id_dtype, const int32_t* row_ptr,
+  const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src, int aggr, float* out, int64_t out_stride,
+  wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  (void)p_env_fns;   // (the forward needs no scratch)
+  // (the arguments are judged first: a malformed call is INVALID_INPUT under every backend)
+  if (table == nullptr) throw invalid_input("table is null");
+  const wholememory_tensor_description_t td = *wholememory_tensor_get_tensor_description(table);
+  if (td.dim != 2) throw invalid_input("the table must be a 2-D tensor");
+  if (td.dtype != WHOLEMEMORY_DT_INT8) throw invalid_input("a quantized table must be INT8");
+  if (td.strides[1] != 1) throw invalid_input("the table's rows must be contiguous");
+  if (dim < 1) throw invalid_input("dim must be >= 1");
+  const int64_t row_bytes = (dim + 3) / 4 * 4 + 8;
+  if (td.sizes[1] < row_bytes)
+    throw invalid_input(format_string("the table's rows hold %ld bytes, dim %ld needs %ld", static_cast<long>(td.sizes[1]),
+                                      static_cast<long>(dim), static_cast<long>(row_bytes)));
+  if (td.strides[0] < row_bytes || td.strides[0] % 4 != 0)
+    throw invalid_input("the table's row stride must be >= the row's bytes and a multiple of 4");
+  if (td.storage_offset % 4 != 0) throw invalid_input("the table's storage offset must be a multiple of 4 bytes");
+  if (node_id_dtype != WHOLEMEMORY_DT_INT && node_id_dtype != WHOLEMEMORY_DT_INT64)
+    throw invalid_input("node_id_dtype must be INT or INT64");
+  // (the virtual x: n_src rows of `dim` values behind node_ids)
+  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, node_ids, dim, dim, dim, aggr, out, out_stride, 2 * dim, n_src, n_dst);
+  if (n_src > 0 && td.sizes[0] < 1) throw invalid_input("node ids into a table without rows");
+  const auto* bk = backend();
+  if (bk->qagg_forward == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  if (wholememory_tensor_has_handle(table)) {
+    const auto mt = wholememory_get_memory_type(wholememory_tensor_get_memory_handle(table));
+    if (mt != WHOLEMEMORY_MT_CONTINUOUS && mt != WHOLEMEMORY_MT_CHUNKED) return WHOLEMEMORY_NOT_SUPPORTED;
+    if (mapped_via_exchange(table, mt)) return WHOLEMEMORY_NOT_SUPPORTED;   // (served by a collective, not by loads)
+  }
+  auto a = block_args<wm_qagg_args>(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
+  WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(table, &a.gref));
+  a.table_rows           = td.sizes[0];
+  a.table_stride         = td.strides[0];
+  a.table_storage_offset = td.storage_offset;
+  a.node_ids             = node_ids;
+  a.node_id_dtype        = static_cast<wholememory_dtype_t>(node_id_dtype);
+  a.out                  = out;
+  a.out_stride           = out_stride;
+  WM_BK(bk->qagg_forward(&a, stream));
+  g_qagg_calls.fetch_add(1, std::memory_order_relaxed);
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+int64_t wholememory_ext_gather_dequantize_aggregate_calls(void) { return g_qagg_calls.load(std::memory_order_relaxed); }
 
 wholememory_error_code_t wholememory_ext_csc_rel_aggregate_forward(const int32_t* row_ptr, const int32_t* col_ind,
                                                                    const int32_t* edge_type, int64_t n_edges, int64_t n_dst,

@@ -358,6 +358,24 @@ struct wm_qrows_args {
   int max_blocks;                     // "gather_sms" / "scatter_sms": <= 0 = default
 };
 
+// agg_concat over rows that come from an 8-bit row-quantized table by global id (kernels/agg_quant.hip, wholegraph_amd_ext.h
+// section 2j): x[i] = dequantize(table row node_ids[i]) for i < n_src is never materialised. The table as in wm_qrows_args
+// (stride / offset in BYTES), the block and out as in wm_gather_agg_args
+struct wm_qagg_args {
+  wholememory_gref_t gref;            // the table's bytes (continuous or chunked)
+  int64_t table_stride;               // BYTES between rows: >= round_up(dim, 4) + 8, a multiple of 4
+  int64_t table_storage_offset;       // BYTES, a multiple of 4
+  int64_t table_rows;                 // rows of the (sub)tensor: ids are in [0, table_rows)
+  const void* node_ids;               // [n_src] int32 / int64, device
+  wholememory_dtype_t node_id_dtype;
+  const int32_t* row_ptr;             // [n_dst + 1]
+  const int32_t* col_ind;             // [n_edges], ids in [0, n_src)
+  int64_t n_edges, n_dst, n_src, dim; // dim: values per row
+  int mean;                           // 1: "mean" (sum times fl(1 / degree)), 0: "sum"
+  float* out;                         // [n_dst, out_stride] (2 * dim columns), fp32
+  int64_t out_stride;
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -607,6 +625,9 @@ struct wm_device_backend {
   // them ----
   int (*qrows_gather_dequant)(const wm_qrows_args* a, void* stream);
   int (*qrows_quantize_scatter)(const wm_qrows_args* a, void* stream);
+  // ---- agg_forward over rows read from an 8-bit row-quantized table by global id (kernels/agg_quant.hip, wholegraph_amd_ext.h
+  // section 2j); nullptr in a backend without it ----
+  int (*qagg_forward)(const wm_qagg_args* a, void* stream);
 };
 
 }  // extern "C"

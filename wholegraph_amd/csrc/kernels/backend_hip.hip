@@ -101,6 +101,7 @@ int hip_relagg_backward(const wm_relagg_args* a, const int32_t* order, const int
                         const int64_t* n_unique_dev, void* workspace, void* stream);
 int hip_qrows_gather_dequant(const wm_qrows_args* a, void* stream);
 int hip_qrows_quantize_scatter(const wm_qrows_args* a, void* stream);
+int hip_qagg_forward(const wm_qagg_args* a, void* stream);
 
 namespace {
 
@@ -292,6 +293,7 @@ const wm_device_backend kHipBackend = {
   hip_relagg_backward,
   hip_qrows_gather_dequant,
   hip_qrows_quantize_scatter,
+  hip_qagg_forward,
 };
 
 }  // namespace

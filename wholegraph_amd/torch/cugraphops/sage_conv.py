@@ -55,9 +55,10 @@ class CuGraphSAGEConv(torch.nn.Module):
     def forward_from_table(self, source, node_ids: Tensor, csr_row_ptr: Tensor, csr_col_ind: Tensor, max_num_neighbors: int,
                            is_training: bool = False) -> Tensor:
         """``forward`` whose ``x`` is ``source[node_ids]`` (a ``WholeMemoryEmbedding`` or ``WholeMemoryTensor``, rows widened
-        to float32), read by the aggregation itself (``gather_agg_concat``): the first layer of a model without the gathered
-        feature matrix. Same result as ``forward(source.gather(node_ids, force_dtype=torch.float32), ...)``, bit for bit.
-        ``is_training``: hand the row gradients to the embedding's optimizer, as ``WholeMemoryEmbeddingModule`` does."""
+        to float32, or a ``WholeMemoryQuantizedTensor``, rows dequantized), read by the aggregation itself
+        (``gather_agg_concat``): the first layer of a model without the gathered feature matrix. Same result as
+        ``forward(source.gather(node_ids, force_dtype=torch.float32), ...)``, bit for bit. ``is_training``: hand the row
+        gradients to the embedding's optimizer, as ``WholeMemoryEmbeddingModule`` does (a quantized table is frozen)."""
         del max_num_neighbors
         if self.project:
             raise ValueError("forward_from_table needs project=False: pre_lin must see the rows before they are aggregated")

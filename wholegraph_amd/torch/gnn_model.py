@@ -16,6 +16,7 @@ import torch.nn.functional as F
 from .embedding import WholeMemoryEmbedding, WholeMemoryEmbeddingModule
 from .graph_ops import add_csr_self_loop
 from .graph_structure import GraphStructure
+from .quantized import WholeMemoryQuantizedTensor
 
 FRAMEWORKS = ("cugraph",)
 framework_name = None
@@ -100,9 +101,11 @@ class HomoGNNModel(torch.nn.Module):
     """Node classification model over a homogeneous graph: settings from an ``args`` namespace as the reference reads them
     (hiddensize, layernum, model, classnum, dropout, neighbors, inferencesample; heads for gat). Model "rgcn" (an
     extension) also reads num_relations, edge_type_name (an integer edge attribute registered with
-    ``graph_structure.set_edge_attribute``: the relation of every graph edge) and, optionally, num_bases."""
+    ``graph_structure.set_edge_attribute``: the relation of every graph edge) and, optionally, num_bases.
+    ``node_embedding`` may also be a ``WholeMemoryQuantizedTensor`` (an extension: 8-bit row-quantized, frozen features):
+    the features then come from its ``gather``, or with ``args.fuse_gather`` from layer 0's aggregation itself."""
 
-    def __init__(self, graph_structure: GraphStructure, node_embedding: WholeMemoryEmbedding, args):
+    def __init__(self, graph_structure: GraphStructure, node_embedding, args):
         super().__init__()
         hidden_feat_dim = args.hiddensize
         self.graph_structure = graph_structure
@@ -131,7 +134,10 @@ class HomoGNNModel(torch.nn.Module):
                                                 args.model)
         self.mean_output = attention
         self.add_self_loop = attention
-        self.gather_fn = WholeMemoryEmbeddingModule(self.node_embedding)
+        if isinstance(self.node_embedding, WholeMemoryQuantizedTensor):   # (nothing to train: no embedding module)
+            self.gather_fn = self.node_embedding.gather
+        else:
+            self.gather_fn = WholeMemoryEmbeddingModule(self.node_embedding)
         self.dropout = args.dropout
         self.max_neighbors = parse_max_neighbors(args.layernum, args.neighbors)
         self.max_inference_neighbors = parse_max_neighbors(args.layernum, getattr(args, "inferencesample", args.neighbors))

@@ -8,6 +8,7 @@ two-layer EdgeGATConv model trained on sampled edge attributes end to end."""
 import numpy as np
 import pytest
 
+import _long_runs as LR
 from test_gat_gpu import F32, U, assert_close_scaled, edge_dst, inputs, ref_alpha64, ref_out, ref_scores, seg_sum
 from test_sage_agg_gpu import _planted_partition, _wm_array, bits, block, dev
 
@@ -226,6 +227,21 @@ def test_bits_ragged_last_edge_chunk(gpu_env):
     assert len(col) == E
     h, att, ef = edge_inputs(rng, E, 4, 8)
     check_bits(h, att, ef, dev(ef), row_ptr, col, 4, True, rng)
+
+
+@pytest.mark.parametrize("F", [5, 8])
+def test_bits_with_runs_of_more_than_one_batch_of_partials(gpu_env, F):
+    """runs of 8, 9 and 17 partial rows (tests/_long_runs.py): a full batch, a second pass of the batch loop, a ragged third"""
+    from wholegraph_amd.torch.aggregation import chunk_edges
+    C, H = chunk_edges(), 2
+    rng = np.random.default_rng(900 + F)
+    row_ptr, col = LR.long_run_block(rng, C)
+    LR.assert_long_runs(row_ptr, col, C)
+    h, att = inputs(rng, LR.N_SRC, H, F)
+    att = np.concatenate([att, (0.5 * rng.standard_normal(H * F) / np.sqrt(F)).astype(F32)])
+    ef = rng.standard_normal((len(col), H * F)).astype(F32)
+    for concat in (True, False):
+        check_bits(h, att, ef, dev(ef), row_ptr, col, H, concat, rng)
 
 
 def test_bits_strided_unaligned_edge_feat(gpu_env):

@@ -7,6 +7,7 @@ and a two-layer GAT trained end to end on a planted-partition graph held in Whol
 import numpy as np
 import pytest
 
+import _long_runs as LR
 from test_sage_agg_gpu import _planted_partition, _wm_array, bits, block, dev
 
 pytestmark = pytest.mark.gpu
@@ -245,6 +246,28 @@ def test_backward_bitwise_with_chunked_hub(gpu_env, H, F, concat):
     want.backward(dev(G_np))
     assert_close_scaled(h.grad, h2.grad)
     assert_close_scaled(att.grad, att2.grad)
+
+
+@pytest.mark.parametrize("F", [5, 8])
+def test_backward_bitwise_with_runs_of_more_than_one_batch_of_partials(gpu_env, F):
+    """runs of 8, 9 and 17 partial rows (tests/_long_runs.py): a full batch, a second pass of the batch loop, a ragged third,
+    each with the chunk's ds_src loaded next to the row"""
+    from wholegraph_amd.torch.aggregation import chunk_edges
+    from wholegraph_amd.torch.gat_aggregation import mha_gat_n2n, node_chunk
+    C, N, H = chunk_edges(), node_chunk(), 2
+    rng = np.random.default_rng(900 + F)
+    row_ptr, col = LR.long_run_block(rng, C)
+    LR.assert_long_runs(row_ptr, col, C)
+    h_np, att_np = inputs(rng, LR.N_SRC, H, F)
+    for concat in (True, False):
+        G_np = rng.standard_normal((LR.N_DST, H * F if concat else F)).astype(F32)
+        h = dev(h_np).requires_grad_(True)
+        att = dev(att_np).requires_grad_(True)
+        out, alpha = mha_gat_n2n(h, att, dev(row_ptr), dev(col), H, 0.2, concat, return_alpha=True)
+        out.backward(dev(G_np))
+        gh, ga = ref_backward(row_ptr, col, h_np, att_np, alpha.cpu().numpy(), G_np, H, 0.2, concat, C, N)
+        assert np.array_equal(bits(h.grad), gh.view(np.uint32))
+        assert np.array_equal(bits(att.grad), ga.view(np.uint32))
 
 
 def test_backward_empty_blocks(gpu_env):

@@ -11,6 +11,7 @@ import types
 import numpy as np
 import pytest
 
+import _long_runs as LR
 from test_gat_gpu import U, assert_close_scaled, edge_dst, ref_out, seg_sum
 from test_sage_agg_gpu import _planted_partition, _wm_array, bits, block, dev
 
@@ -215,6 +216,19 @@ def test_bitwise_on_hub_block(gpu_env, H, F, concat):
     rng = np.random.default_rng(1000 + 10 * H + F + concat)
     hs, hd, att = inputs(rng, n_src, n_dst, H, F)
     check_all(hs, hd, att, row_ptr, col, H, 0.2 if concat else 0.0, concat, rng)
+
+
+@pytest.mark.parametrize("F", [5, 8])
+def test_bitwise_with_runs_of_more_than_one_batch_of_partials(gpu_env, F):
+    """runs of 8, 9 and 17 partial rows (tests/_long_runs.py): a full batch, a second pass of the batch loop, a ragged third"""
+    from wholegraph_amd.torch.aggregation import chunk_edges
+    C, H = chunk_edges(), 2
+    rng = np.random.default_rng(900 + F)
+    row_ptr, col = LR.long_run_block(rng, C)
+    LR.assert_long_runs(row_ptr, col, C)
+    hs, hd, att = inputs(rng, LR.N_SRC, LR.N_DST, H, F)
+    for concat in (True, False):
+        check_all(hs, hd, att, row_ptr, col, H, 0.2, concat, rng, loose=False)
 
 
 @pytest.mark.parametrize("concat,slope", [(True, 0.0), (False, 0.2)])

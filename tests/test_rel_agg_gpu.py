@@ -10,6 +10,8 @@ import types
 import numpy as np
 import pytest
 
+import _long_runs as LR
+
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
@@ -170,6 +172,23 @@ def test_bitwise_power_law_block_with_chunked_hub(gpu_env, dim, R, aggr):
     g = rng.standard_normal((n_dst, (R + 1) * dim)).astype(F32)
     g[5, R * dim:] = -0.0
     check_bitwise(x, row_ptr, col, et, R, g, aggr)
+
+
+@pytest.mark.parametrize("dim", [5, 8])
+def test_bitwise_with_runs_of_more_than_one_batch_of_partials(gpu_env, dim):
+    """runs of 8, 9 and 17 partial rows (tests/_long_runs.py): a full batch, a second pass of the batch loop, a ragged third;
+    three relations, one edge in 50 with a type out of range"""
+    from wholegraph_amd.torch.aggregation import chunk_edges
+    C, R = chunk_edges(), 3
+    rng = np.random.default_rng(900 + dim)
+    row_ptr, col = LR.long_run_block(rng, C)
+    LR.assert_long_runs(row_ptr, col, C)
+    et = rng.integers(0, R, len(col)).astype(np.int32)
+    et[rng.random(len(col)) < 0.02] = R
+    x = rng.standard_normal((LR.N_SRC, dim)).astype(F32)
+    g = rng.standard_normal((LR.N_DST, (R + 1) * dim)).astype(F32)
+    for aggr in ("mean", "sum"):
+        check_bitwise(x, row_ptr, col, et, R, g, aggr)
 
 
 @pytest.mark.parametrize("dim", [3, 128])

@@ -9,6 +9,8 @@ import types
 import numpy as np
 import pytest
 
+import _long_runs as LR
+
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
@@ -194,6 +196,23 @@ def test_backward_bitwise_with_chunked_hub(gpu_env, dim, aggr):
     agg_concat(x3, dev(np.zeros(n_dst + 1, np.int32)), dev(np.zeros(0, np.int32)), aggr).backward(dev(g_np))
     assert np.array_equal(bits(x3.grad[:n_dst]), g_np[:, dim:].view(np.uint32))
     assert not x3.grad[n_dst:].any()
+
+
+@pytest.mark.parametrize("dim", [5, 8])
+def test_backward_bitwise_with_runs_of_more_than_one_batch_of_partials(gpu_env, dim):
+    """runs of 8, 9 and 17 partial rows (tests/_long_runs.py): a full batch, a second pass of the batch loop, a ragged third"""
+    from wholegraph_amd.torch.aggregation import agg_concat, chunk_edges
+    C = chunk_edges()
+    rng = np.random.default_rng(900 + dim)
+    row_ptr, col = LR.long_run_block(rng, C)
+    LR.assert_long_runs(row_ptr, col, C)
+    x_np = rng.standard_normal((LR.N_SRC, dim)).astype(F32)
+    g_np = rng.standard_normal((LR.N_DST, 2 * dim)).astype(F32)
+    for aggr in ("mean", "sum"):
+        x = dev(x_np).requires_grad_(True)
+        agg_concat(x, dev(row_ptr), dev(col), aggr).backward(dev(g_np))
+        want = ref_backward(row_ptr, col, g_np, LR.N_SRC, aggr, C)
+        assert np.array_equal(bits(x.grad), want.view(np.uint32))
 
 
 # ---------------------------------------------------------------- 3 determinism

@@ -12,6 +12,8 @@ import types
 import numpy as np
 import pytest
 
+import _long_runs as LR
+
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
@@ -219,6 +221,24 @@ def test_backward_bitwise_with_chunked_hub(gpu_env, name, aggr, dim):
     agg_concat(x3, dev(np.zeros(n_dst + 1, np.int32)), dev(np.zeros(0, np.int32)), aggr).backward(dev16(gb, name))
     same_bits(bits(x3.grad[:n_dst]), gb[:, dim:], "E = 0: the self terms")
     same_bits(bits(x3.grad[n_dst:]), np.zeros((n_src - n_dst, dim), np.uint16), "E = 0: rows past the targets")
+
+
+@pytest.mark.parametrize("dim", [5, 8])
+@pytest.mark.parametrize("name", DTYPES)
+def test_backward_bitwise_with_runs_of_more_than_one_batch_of_partials(gpu_env, name, dim):
+    """runs of 8, 9 and 17 partial rows (tests/_long_runs.py): a full batch, a second pass of the batch loop, a ragged third"""
+    from wholegraph_amd.torch.aggregation import agg_concat, chunk_edges
+    C = chunk_edges()
+    rng = np.random.default_rng(900 + dim)
+    row_ptr, col = LR.long_run_block(rng, C)
+    LR.assert_long_runs(row_ptr, col, C)
+    xb, _ = random_rows(rng, (LR.N_SRC, dim), name)
+    gb, g32 = random_rows(rng, (LR.N_DST, 2 * dim), name)
+    for aggr in ("mean", "sum"):
+        want = round_bits(ref_backward(row_ptr, col, g32, LR.N_SRC, aggr, C), name)
+        x = dev16(xb, name).requires_grad_(True)
+        agg_concat(x, dev(row_ptr), dev(col), aggr).backward(dev16(gb, name))
+        same_bits(bits(x.grad), want, "grad_x, " + aggr)
 
 
 # ---------------------------------------------------------------- 3 op_T(x) == round_T(op_fp32(fp32(x)))

@@ -9,6 +9,8 @@ order is stated, so the expected bits are derivable."""
 import numpy as np
 import pytest
 
+import _long_runs as LR
+
 pytestmark = pytest.mark.gpu
 
 F32 = np.float32
@@ -343,6 +345,22 @@ def test_two_calls_give_identical_bits_and_unneeded_gradients_are_not_computed(g
     assert call(gxd, None) == 0
     torch.cuda.synchronize()
     assert bool((gwd == 7.0).all()) and torch.equal(gxd.view(torch.int32), gx.view(torch.int32))
+
+
+@pytest.mark.parametrize("dim", [5, 8])
+def test_bitwise_with_runs_of_more_than_one_batch_of_partials(gpu_env, dim):
+    """runs of 8, 9 and 17 partial rows (tests/_long_runs.py): a full batch, a second pass of the batch loop, a ragged third.
+    (It stands behind the test above, which counts the entries of the op's capped log of backward calls.)"""
+    from wholegraph_amd.torch.aggregation import chunk_edges
+    C = chunk_edges()
+    rng = np.random.default_rng(900 + dim)
+    row_ptr, col = LR.long_run_block(rng, C)
+    LR.assert_long_runs(row_ptr, col, C)
+    x = rng.standard_normal((LR.N_SRC, dim)).astype(F32)
+    w = rng.standard_normal(len(col)).astype(F32)
+    g = rng.standard_normal((LR.N_DST, 2 * dim)).astype(F32)
+    for aggr in ("mean", "sum"):
+        check_bitwise(x, row_ptr, col, w, g, aggr)
 
 
 # ---------------------------------------------------------------- 5 the layer

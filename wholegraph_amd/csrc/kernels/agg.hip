@@ -17,8 +17,9 @@
 //   4 agg_bwd_fold_kernel: one group per source row: chunk 0 of its run, then the partials of chunks 1, 2, ... in chunk
 //     order, then the self term G[s, F:2F] for s < n_dst; rows without edges get the self term or +0.0.
 // run_of[] is not initialised: a value is used only when 0 <= u < n_unique and unique[u] == s (a sparse-set check).
-// Steps 1 and 2 do not depend on the type of the rows: agg_bwd_prepare (below) is shared with kernels/agg_half.hip, the
-// same op on fp16 / bf16 rows.
+// Steps 1 and 2 do not depend on the op: agg_bwd_prepare (below) is shared with kernels/agg_half.hip, agg_weighted.hip and
+// agg_rel.hip. The walk of steps 3 and 4 (tiles, the run of a source, the partials in chunk order, the self term) is
+// agg_common.cuh's, shared with those files and with the attention ops; fold_edges, the per-edge term, is this op's own.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -105,82 +106,45 @@ __device__ __forceinline__ void fold_edges(fvec<VEC>& acc, const wm_agg_args& p,
 }
 
 // sorted_dst[j] = the target whose edge range holds position order[j]; run_of[unique[u]] = u
-__global__ __launch_bounds__(kAggBlock) void agg_bwd_prep_kernel(wm_agg_args p, wm_agg_bwd_state b)
+__global__ __launch_bounds__(kAggBlock) void agg_bwd_prep_kernel(const int32_t* row_ptr, int64_t n_dst, int64_t n_edges,
+                                                                 csc_bwd_index b)
 {
   const int64_t nu = *b.n_unique;
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < p.n_edges;
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n_edges;
        i += static_cast<int64_t>(gridDim.x) * blockDim.x)
-    bwd_prep_at(i, p.row_ptr, p.n_dst, b.order, b.unique_ids, nu, b.sorted_dst, b.run_of);
+    bwd_prep_at(i, row_ptr, n_dst, b.order, b.unique_ids, nu, b.sorted_dst, b.run_of);
 }
 
 template <int VEC, int LANES>
 __global__ __launch_bounds__(kAggBlock) void agg_bwd_chunk_kernel(wm_agg_args p, wm_agg_bwd_state b)
 {
-  constexpr int kGroups = kAggBlock / LANES;
-  const int gl          = threadIdx.x % LANES;
-  const int64_t F       = p.dim;
-  const int64_t nu      = *b.n_unique;
-  if (nu == 0) return;
-  for (int64_t t = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; t < b.n_tiles;
-       t += static_cast<int64_t>(gridDim.x) * kGroups) {
-    int64_t cs, ce;
-    if (!chunk_in_tile(t, b.run_starts, nu, cs, ce)) continue;
-    for (int64_t cb = 0; cb < F; cb += LANES * VEC) {
-      const int64_t c  = cb + gl * VEC;
-      const bool act   = c < F;
-      const int64_t cl = act ? c : 0;
-      fvec<VEC> acc    = splat<VEC>(-0.0f);
-      fold_edges<VEC, LANES>(acc, p, b.sorted_dst, cs, ce, cl, gl);
-      if (act) stv(b.partial + t * b.partial_stride + c, acc);
-    }
-  }
+  const int gl = threadIdx.x % LANES;
+  for_chunk_pieces<VEC, LANES>(b, p.dim, [&](int64_t t, int64_t cs, int64_t ce, int64_t c, int64_t cl, bool act) {
+    fvec<VEC> acc = splat<VEC>(-0.0f);
+    fold_edges<VEC, LANES>(acc, p, b.sorted_dst, cs, ce, cl, gl);
+    if (act) stv(b.partial + t * b.partial_stride + c, acc);
+  });
 }
 
 template <int VEC, int LANES>
 __global__ __launch_bounds__(kAggBlock) void agg_bwd_fold_kernel(wm_agg_args p, wm_agg_bwd_state b)
 {
   constexpr int kGroups = kAggBlock / LANES;
-  constexpr int64_t C   = kAggChunkEdges;
   const int gl          = threadIdx.x % LANES;
   const int64_t F       = p.dim;
   const int64_t nu      = *b.n_unique;
   for (int64_t s = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; s < p.n_src;
        s += static_cast<int64_t>(gridDim.x) * kGroups) {
-    const int64_t u = b.run_of[s];   // (uninitialised unless s has edges: checked against unique_ids)
-    const bool has  = u >= 0 && u < nu && b.unique_ids[u] == s;
-    int64_t s0 = 0, s1 = 0;
-    if (has) s0 = b.run_starts[u], s1 = b.run_starts[u + 1];
-    const int64_t c0e     = s1 - s0 > C ? s0 + C : s1;
-    const int64_t nchunks = (s1 - s0 + C - 1) / C;
-    const bool self       = s < p.n_dst;
+    const src_run r = run_of_source(b, nu, s);
+    const bool self = s < p.n_dst;
     for (int64_t cb = 0; cb < F; cb += LANES * VEC) {
       const int64_t c  = cb + gl * VEC;
       const bool act   = c < F;
       const int64_t cl = act ? c : 0;
       fvec<VEC> acc    = splat<VEC>(-0.0f);
-      fold_edges<VEC, LANES>(acc, p, b.sorted_dst, s0, c0e, cl, gl);
-      for (int64_t k0 = 1; k0 < nchunks; k0 += kAggBatch) {   // partials in chunk order, a batch of them in flight
-        fvec<VEC> v[kAggBatch];
-#pragma unroll
-        for (int k = 0; k < kAggBatch; ++k) {
-          const int64_t kk = k0 + k < nchunks ? k0 + k : nchunks - 1;
-          v[k]             = ldv<VEC>(b.partial + ((s0 + kk * C) / C) * b.partial_stride + cl);
-        }
-#pragma unroll
-        for (int k = 0; k < kAggBatch; ++k)
-          if (k0 + k < nchunks) add_to(acc, v[k]);
-      }
-      fvec<VEC> res;
-      if (self) {
-        const fvec<VEC> g = ldv<VEC>(p.grad + s * p.grad_stride + F + cl);
-        res               = g;
-        if (has) {
-          res = acc;
-          add_to(res, g);
-        }
-      } else {
-        res = has ? acc : splat<VEC>(0.0f);
-      }
+      fold_edges<VEC, LANES>(acc, p, b.sorted_dst, r.s0, r.c0e, cl, gl);
+      add_partials(acc, b, r, cl);
+      const fvec<VEC> res = with_self_term(acc, r.has, self, p.grad, s * p.grad_stride + F + cl);
       if (act) stv(p.out + s * p.out_stride + c, res);
     }
   }
@@ -203,32 +167,29 @@ int hip_agg_forward(const wm_agg_args* a, void* stream_v)
 
 size_t hip_agg_backward_workspace_bytes(int64_t n_edges, int64_t n_src, int64_t dim)
 {
-  const int64_t tiles = (n_edges + kAggChunkEdges - 1) / kAggChunkEdges;
-  const int64_t pstr  = (dim + 3) / 4 * 4;
-  return static_cast<size_t>(n_edges + n_src + 64) * 4 + 256 + static_cast<size_t>(tiles * pstr) * 4;
+  return agg_bwd_plan(n_edges, n_src, dim, kAggChunkEdges).ws.bytes;
 }
 
-int agg_bwd_prepare(const wm_agg_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                    const int64_t* n_unique_dev, void* workspace, wm_agg_bwd_state* bp, void* stream_v)
+int agg_bwd_prepare(const int32_t* row_ptr, int64_t n_dst, int64_t n_edges, int64_t n_src, int64_t dim, const int32_t* order,
+                    const int32_t* run_starts, const int32_t* unique_ids, const int64_t* n_unique_dev, void* workspace,
+                    csc_bwd_index* bp, void* stream_v)
 {
-  hipStream_t stream  = static_cast<hipStream_t>(stream_v);
-  wm_agg_bwd_state& b = *bp;
-  b.order             = order;
-  b.run_starts        = run_starts;
-  b.unique_ids        = unique_ids;
-  b.n_unique          = n_unique_dev;
-  b.n_tiles           = (a->n_edges + kAggChunkEdges - 1) / kAggChunkEdges;
-  b.partial_stride    = (a->dim + 3) / 4 * 4;
-  auto up16           = [](uintptr_t v) { return (v + 255) & ~static_cast<uintptr_t>(255); };
-  uintptr_t w         = up16(reinterpret_cast<uintptr_t>(workspace));
-  b.sorted_dst        = reinterpret_cast<int32_t*>(w);
-  w                   = up16(w + static_cast<uintptr_t>(a->n_edges) * 4);
-  b.run_of            = reinterpret_cast<int32_t*>(w);
-  w                   = up16(w + static_cast<uintptr_t>(a->n_src) * 4);
-  b.partial           = reinterpret_cast<float*>(w);
-  if (a->n_edges > 0) {
-    const int blocks = blocks_for(a->n_edges, kAggBlock);
-    hipLaunchKernelGGL(agg_bwd_prep_kernel, dim3(blocks < 8192 ? blocks : 8192), dim3(kAggBlock), 0, stream, *a, b);
+  hipStream_t stream     = static_cast<hipStream_t>(stream_v);
+  const agg_bwd_layout l = agg_bwd_plan(n_edges, n_src, dim, kAggChunkEdges);
+  csc_bwd_index& b       = *bp;
+  b.order                = order;
+  b.run_starts           = run_starts;
+  b.unique_ids           = unique_ids;
+  b.n_unique             = n_unique_dev;
+  b.sorted_dst           = ws_at<int32_t>(workspace, l.ws.off[0]);
+  b.run_of               = ws_at<int32_t>(workspace, l.ws.off[1]);
+  b.partial              = ws_at<float>(workspace, l.ws.off[2]);
+  b.n_tiles              = l.n_tiles;
+  b.partial_stride       = l.partial_stride;
+  if (n_edges > 0) {
+    const int blocks = blocks_for(n_edges, kAggBlock);
+    hipLaunchKernelGGL(agg_bwd_prep_kernel, dim3(blocks < 8192 ? blocks : 8192), dim3(kAggBlock), 0, stream, row_ptr, n_dst,
+                       n_edges, b);
     if (rc_last() != 0) return -2;
   }
   return 0;
@@ -240,7 +201,9 @@ int hip_agg_backward(const wm_agg_args* a, const int32_t* order, const int32_t* 
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   if (a->n_src == 0 || a->dim == 0) return 0;
   wm_agg_bwd_state b;
-  if (agg_bwd_prepare(a, order, run_starts, unique_ids, n_unique_dev, workspace, &b, stream_v) != 0) return -2;
+  if (agg_bwd_prepare(a->row_ptr, a->n_dst, a->n_edges, a->n_src, a->dim, order, run_starts, unique_ids, n_unique_dev,
+                      workspace, &b, stream_v) != 0)
+    return -2;
   const bool v4 = use_vec4(a->dim, a->grad, a->grad_stride, a->out, a->out_stride);
   if (b.n_tiles > 1) {   // (one tile holds no chunk k >= 1)
 #define WM_AGG_CHUNK(V, L)                                                                                                   \

@@ -1,17 +1,20 @@
-// wholegraph_amd — device and launch helpers shared by the aggregation ops of a sampled CSC block (kernels/agg.hip, the
-// GraphSAGE `agg_concat` op, and kernels/agg_half.hip, the same op on fp16 / bf16 rows; kernels/gat.hip, the GAT
-// `mha_gat_n2n` op): fp32 pieces of a row, the clamped edge range of a
-// target, the lookups of the deterministic per-source backward over the id sort, and the launch shape.
+// wholegraph_amd — device and launch helpers shared by the ops of a sampled CSC block (kernels/agg.hip, agg_half.hip,
+// agg_weighted.hip and agg_rel.hip, the `agg_concat` family; kernels/gat.hip, gat_edge.hip and gatv2.hip, the attention
+// ops): fp32 pieces of a row, the clamped edge range of a target, the launch shape, and the walk of the deterministic
+// per-source backward over the id sort: its index (csc_bwd_index), the run of a source (run_of_source), the partial rows
+// of a run's later chunks (add_partials), the tile loop of a chunk kernel (for_chunk_pieces) and the self term of the
+// agg_concat ops (with_self_term). What an op adds per edge, its fold_edges*, stays in the op's own file.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../backend.hpp"
+#include "../csc_workspace.hpp"
 
 namespace wm {
 
-// scratch of the agg_concat backward: the id sort's outputs and the op's workspace (agg_bwd_prepare carves it)
-struct wm_agg_bwd_state {
+// index of the per-source backward: the id sort's outputs and what the prep kernel derives from them (in the op's workspace)
+struct csc_bwd_index {
   const int32_t* order;        // [n_edges] edge positions, sorted by source (stable)
   const int32_t* run_starts;   // [n_unique + 1]
   const int32_t* unique_ids;   // [n_unique] sources with edges, ascending
@@ -21,11 +24,13 @@ struct wm_agg_bwd_state {
   float* partial;              // [n_tiles, partial_stride] fp32, whatever the type of the rows
   int64_t n_tiles, partial_stride;
 };
+using wm_agg_bwd_state = csc_bwd_index;   // the agg_concat ops need nothing more
 
-// fills `b` from the id sort's outputs and `workspace` (hip_agg_backward_workspace_bytes) and queues agg_bwd_prep_kernel
-// (kernels/agg.hip), which reads only the index part of `a`: row_ptr, n_dst, n_edges, n_src, dim. 0 or -2.
-int agg_bwd_prepare(const wm_agg_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                    const int64_t* n_unique_dev, void* workspace, wm_agg_bwd_state* b, void* stream);
+// fills `b` from the id sort's outputs and `workspace` (hip_agg_backward_workspace_bytes: agg_bwd_plan lays out both) for
+// partial rows of `dim` columns and queues agg_bwd_prep_kernel (kernels/agg.hip). 0 or -2.
+int agg_bwd_prepare(const int32_t* row_ptr, int64_t n_dst, int64_t n_edges, int64_t n_src, int64_t dim, const int32_t* order,
+                    const int32_t* run_starts, const int32_t* unique_ids, const int64_t* n_unique_dev, void* workspace,
+                    csc_bwd_index* b, void* stream);
 
 namespace {
 
@@ -132,6 +137,117 @@ __device__ __forceinline__ bool chunk_in_tile(int64_t t, const int32_t* run_star
   if (k < 1 || cs >= s1 || cs >= pos0 + C) return false;   // no chunk k >= 1 starts in this tile
   ce = cs + C < s1 ? cs + C : s1;
   return true;
+}
+
+// fp32 pieces of a partial row: VEC floats, as 16-byte accesses when VEC is 4 or 8 (8: a piece of 16-bit rows)
+template <int VEC>
+__device__ __forceinline__ fvec<VEC> ldp(const float* p)
+{
+  if constexpr (VEC == 8) {
+    const fvec<4> lo = ldv<4>(p), hi = ldv<4>(p + 4);
+    fvec<8> r;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) r.v[i] = lo.v[i], r.v[4 + i] = hi.v[i];
+    return r;
+  } else {
+    return ldv<VEC>(p);
+  }
+}
+
+// the run of source s in the sorted positions: [s0, s1), chunk 0 = [s0, c0e), nchunks chunks in all; all 0 without edges
+struct src_run {
+  bool has;
+  int64_t s0, s1, c0e, nchunks;
+};
+
+__device__ __forceinline__ src_run run_of_source(const csc_bwd_index& b, int64_t nu, int64_t s)
+{
+  constexpr int64_t C = kAggChunkEdges;
+  src_run r;
+  const int64_t u = b.run_of[s];   // (uninitialised unless s has edges: checked against unique_ids)
+  r.has           = u >= 0 && u < nu && b.unique_ids[u] == s;
+  r.s0 = 0, r.s1 = 0;
+  if (r.has) r.s0 = b.run_starts[u], r.s1 = b.run_starts[u + 1];
+  r.c0e     = r.s1 - r.s0 > C ? r.s0 + C : r.s1;
+  r.nchunks = (r.s1 - r.s0 + C - 1) / C;
+  return r;
+}
+
+// what an op keeps next to the columns of a partial row: load(prow, k) runs with the load of batch slot k, add(k) with its
+// add. The attention op of kernels/gat.hip carries a scalar per head there; the others nothing.
+struct no_partial_extra {
+  __device__ __forceinline__ void load(const float*, int) {}
+  __device__ __forceinline__ void add(int) {}
+};
+
+// acc += the partial rows of chunks 1 .. nchunks-1 of run r, in chunk order, a batch of them in flight (this lane's columns
+// at cl)
+template <int VEC, class Extra = no_partial_extra>
+__device__ __forceinline__ void add_partials(fvec<VEC>& acc, const csc_bwd_index& b, const src_run& r, int64_t cl,
+                                             Extra extra = Extra())
+{
+  constexpr int64_t C   = kAggChunkEdges;
+  const int64_t nchunks = r.nchunks;
+  for (int64_t k0 = 1; k0 < nchunks; k0 += kAggBatch) {
+    fvec<VEC> v[kAggBatch];
+#pragma unroll
+    for (int k = 0; k < kAggBatch; ++k) {
+      const int64_t kk = k0 + k < nchunks ? k0 + k : nchunks - 1;   // (a ragged last batch loads its last row again)
+      const float* prow = b.partial + ((r.s0 + kk * C) / C) * b.partial_stride;
+      v[k]              = ldp<VEC>(prow + cl);
+      extra.load(prow, k);
+    }
+#pragma unroll
+    for (int k = 0; k < kAggBatch; ++k) {
+      if (k0 + k < nchunks) {
+        add_to(acc, v[k]);
+        extra.add(k);
+      }
+    }
+  }
+}
+
+// the walk of a chunk kernel: a group of LANES lanes per tile t of the sorted positions; for the chunk [cs, ce) that starts
+// in it, if any, body(t, cs, ce, c, cl, act) once per piece of `width` columns of this lane (c: its first column, act: c is
+// inside the row, cl: c, or 0 for a lane outside it)
+template <int VEC, int LANES, class Body>
+__device__ __forceinline__ void for_chunk_pieces(const csc_bwd_index& b, int64_t width, Body body)
+{
+  constexpr int kGroups = kAggBlock / LANES;
+  const int gl          = threadIdx.x % LANES;
+  const int64_t nu      = *b.n_unique;
+  if (nu == 0) return;
+  for (int64_t t = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; t < b.n_tiles;
+       t += static_cast<int64_t>(gridDim.x) * kGroups) {
+    int64_t cs, ce;
+    if (!chunk_in_tile(t, b.run_starts, nu, cs, ce)) continue;
+    for (int64_t cb = 0; cb < width; cb += LANES * VEC) {
+      const int64_t c  = cb + gl * VEC;
+      const bool act   = c < width;
+      const int64_t cl = act ? c : 0;
+      body(t, cs, ce, c, cl, act);
+    }
+  }
+}
+
+// grad_x of the agg_concat ops from the sum over the edges: + the self term grad[self_off ...] when `self` (s < n_dst);
+// a row without a term from any edge gets the self term alone, or +0.0
+template <int VEC>
+__device__ __forceinline__ fvec<VEC> with_self_term(const fvec<VEC>& acc, bool has, bool self, const float* grad,
+                                                    int64_t self_off)
+{
+  fvec<VEC> res;
+  if (self) {
+    const fvec<VEC> g = ldv<VEC>(grad + self_off);
+    res               = g;
+    if (has) {
+      res = acc;
+      add_to(res, g);
+    }
+  } else {
+    res = has ? acc : splat<VEC>(0.0f);
+  }
+  return res;
 }
 
 int rc_last() { return hipGetLastError() == hipSuccess ? 0 : -2; }

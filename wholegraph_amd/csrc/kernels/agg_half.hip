@@ -9,7 +9,8 @@
 // piece is 8 elements here: F = 128 is 16 pieces) or, on the element-wise path, from its elements; column ids loaded
 // coalesced and handed out with shuffles; the rows of a batch of kAggBatch edges issued back to back as raw pieces and
 // widened when they are added. The edge index, agg_bwd_prep_kernel and the fp32 partial rows of chunks are those of
-// kernels/agg.hip (agg_bwd_prepare).
+// kernels/agg.hip (agg_bwd_prepare); the walk over them is agg_common.cuh's. The self term stays here: the result is
+// narrowed once, and a self term without edges keeps its bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -119,21 +120,7 @@ __device__ __forceinline__ hraw<VEC> zero_raw()
   return r;
 }
 
-// fp32 pieces of a partial row (the workspace): VEC floats, as 16-byte accesses when VEC == 8
-template <int VEC>
-__device__ __forceinline__ fvec<VEC> ldp(const float* p)
-{
-  if constexpr (VEC == 8) {
-    const fvec<4> lo = ldv<4>(p), hi = ldv<4>(p + 4);
-    fvec<8> r;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) r.v[i] = lo.v[i], r.v[4 + i] = hi.v[i];
-    return r;
-  } else {
-    return ldv<VEC>(p);
-  }
-}
-
+// fp32 pieces of a partial row (the workspace), stored as ldp (agg_common.cuh) loads them
 template <int VEC>
 __device__ __forceinline__ void stp(float* p, const fvec<VEC>& a)
 {
@@ -226,31 +213,18 @@ __device__ __forceinline__ void fold_edges16(fvec<VEC>& acc, const wm_agg16_args
 template <class T, int VEC, int LANES>
 __global__ __launch_bounds__(kAggBlock) void agg16_bwd_chunk_kernel(wm_agg16_args p, wm_agg_bwd_state b)
 {
-  constexpr int kGroups = kAggBlock / LANES;
-  const int gl          = threadIdx.x % LANES;
-  const int64_t F       = p.dim;
-  const int64_t nu      = *b.n_unique;
-  if (nu == 0) return;
-  for (int64_t t = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; t < b.n_tiles;
-       t += static_cast<int64_t>(gridDim.x) * kGroups) {
-    int64_t cs, ce;
-    if (!chunk_in_tile(t, b.run_starts, nu, cs, ce)) continue;
-    for (int64_t cb = 0; cb < F; cb += LANES * VEC) {
-      const int64_t c  = cb + gl * VEC;
-      const bool act   = c < F;
-      const int64_t cl = act ? c : 0;
-      fvec<VEC> acc    = splat<VEC>(-0.0f);
-      fold_edges16<T, VEC, LANES>(acc, p, b.sorted_dst, cs, ce, cl, gl);
-      if (act) stp(b.partial + t * b.partial_stride + c, acc);   // (the partial row stays fp32)
-    }
-  }
+  const int gl = threadIdx.x % LANES;
+  for_chunk_pieces<VEC, LANES>(b, p.dim, [&](int64_t t, int64_t cs, int64_t ce, int64_t c, int64_t cl, bool act) {
+    fvec<VEC> acc = splat<VEC>(-0.0f);
+    fold_edges16<T, VEC, LANES>(acc, p, b.sorted_dst, cs, ce, cl, gl);
+    if (act) stp(b.partial + t * b.partial_stride + c, acc);   // (the partial row stays fp32)
+  });
 }
 
 template <class T, int VEC, int LANES>
 __global__ __launch_bounds__(kAggBlock) void agg16_bwd_fold_kernel(wm_agg16_args p, wm_agg_bwd_state b)
 {
   constexpr int kGroups = kAggBlock / LANES;
-  constexpr int64_t C   = kAggChunkEdges;
   const int gl          = threadIdx.x % LANES;
   const int64_t F       = p.dim;
   const int64_t nu      = *b.n_unique;
@@ -258,30 +232,16 @@ __global__ __launch_bounds__(kAggBlock) void agg16_bwd_fold_kernel(wm_agg16_args
   uint16_t* out         = static_cast<uint16_t*>(p.out);
   for (int64_t s = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; s < p.n_src;
        s += static_cast<int64_t>(gridDim.x) * kGroups) {
-    const int64_t u = b.run_of[s];   // (uninitialised unless s has edges: checked against unique_ids)
-    const bool has  = u >= 0 && u < nu && b.unique_ids[u] == s;
-    int64_t s0 = 0, s1 = 0;
-    if (has) s0 = b.run_starts[u], s1 = b.run_starts[u + 1];
-    const int64_t c0e     = s1 - s0 > C ? s0 + C : s1;
-    const int64_t nchunks = (s1 - s0 + C - 1) / C;
-    const bool self       = s < p.n_dst;
+    const src_run r = run_of_source(b, nu, s);
+    const bool has  = r.has;
+    const bool self = s < p.n_dst;
     for (int64_t cb = 0; cb < F; cb += LANES * VEC) {
       const int64_t c  = cb + gl * VEC;
       const bool act   = c < F;
       const int64_t cl = act ? c : 0;
       fvec<VEC> acc    = splat<VEC>(-0.0f);
-      fold_edges16<T, VEC, LANES>(acc, p, b.sorted_dst, s0, c0e, cl, gl);
-      for (int64_t k0 = 1; k0 < nchunks; k0 += kAggBatch) {   // partials in chunk order, a batch of them in flight
-        fvec<VEC> v[kAggBatch];
-#pragma unroll
-        for (int k = 0; k < kAggBatch; ++k) {
-          const int64_t kk = k0 + k < nchunks ? k0 + k : nchunks - 1;
-          v[k]             = ldp<VEC>(b.partial + ((s0 + kk * C) / C) * b.partial_stride + cl);
-        }
-#pragma unroll
-        for (int k = 0; k < kAggBatch; ++k)
-          if (k0 + k < nchunks) add_to(acc, v[k]);
-      }
+      fold_edges16<T, VEC, LANES>(acc, p, b.sorted_dst, r.s0, r.c0e, cl, gl);
+      add_partials(acc, b, r, cl);
       hraw<VEC> res = zero_raw<VEC>();
       if (self) {
         res = ldh<VEC>(grad + s * p.grad_stride + F + cl);   // only the self term: its bits
@@ -346,16 +306,10 @@ int hip_agg16_backward(const wm_agg16_args* a, const int32_t* order, const int32
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   if (a->dtype != WHOLEMEMORY_DT_HALF && a->dtype != WHOLEMEMORY_DT_BF16) return -1;
   if (a->n_src == 0 || a->dim == 0) return 0;
-  wm_agg_args ix{};   // the index part, all that the shared prepare step reads
-  ix.row_ptr = a->row_ptr;
-  ix.col_ind = a->col_ind;
-  ix.n_edges = a->n_edges;
-  ix.n_dst   = a->n_dst;
-  ix.n_src   = a->n_src;
-  ix.dim     = a->dim;
-  ix.mean    = a->mean;
   wm_agg_bwd_state b;
-  if (agg_bwd_prepare(&ix, order, run_starts, unique_ids, n_unique_dev, workspace, &b, stream_v) != 0) return -2;
+  if (agg_bwd_prepare(a->row_ptr, a->n_dst, a->n_edges, a->n_src, a->dim, order, run_starts, unique_ids, n_unique_dev,
+                      workspace, &b, stream_v) != 0)
+    return -2;
   const bool bf = a->dtype == WHOLEMEMORY_DT_BF16;
   const bool v8 = use_vec8(a->dim, a->grad, a->grad_stride, a->out, a->out_stride);
   if (b.n_tiles > 1) {   // (one tile holds no chunk k >= 1)

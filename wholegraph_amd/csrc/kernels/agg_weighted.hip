@@ -7,7 +7,8 @@
 //   and the weights of up to LANES edges are loaded coalesced and handed out with shuffles, the neighbour rows of a batch of
 //   kAggBatch edges are loaded back to back, then multiplied and added in edge order.
 // Backward into x (aggw_bwd_chunk_kernel / aggw_bwd_fold_kernel): the per-source sums of kernels/agg.hip over the same id
-//   sort, prep kernel and chunk tiles (agg_bwd_prepare); the term of sorted position j is w[order[j]] * t(order[j]).
+//   sort, prep kernel and chunk tiles (agg_bwd_prepare) with the walk of agg_common.cuh; the term of sorted position j is
+//   w[order[j]] * t(order[j]) (fold_edges_w).
 // Backward into w (aggw_bwd_weight_kernel): a group of LANES lanes per kAggBatch consecutive edge positions (CSC order, so
 //   the grad_out row of a target is reused from cache across its edges). Lane k < kAggBatch finds the target of edge k (a
 //   search in row_ptr); both rows of every edge of the batch are loaded back to back as pieces. The dot product of an edge
@@ -111,71 +112,33 @@ __device__ __forceinline__ void fold_edges_w(fvec<VEC>& acc, const wm_aggw_args&
 template <int VEC, int LANES>
 __global__ __launch_bounds__(kAggBlock) void aggw_bwd_chunk_kernel(wm_aggw_args p, wm_agg_bwd_state b)
 {
-  constexpr int kGroups = kAggBlock / LANES;
-  const int gl          = threadIdx.x % LANES;
-  const int64_t F       = p.dim;
-  const int64_t nu      = *b.n_unique;
-  if (nu == 0) return;
-  for (int64_t t = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; t < b.n_tiles;
-       t += static_cast<int64_t>(gridDim.x) * kGroups) {
-    int64_t cs, ce;
-    if (!chunk_in_tile(t, b.run_starts, nu, cs, ce)) continue;
-    for (int64_t cb = 0; cb < F; cb += LANES * VEC) {
-      const int64_t c  = cb + gl * VEC;
-      const bool act   = c < F;
-      const int64_t cl = act ? c : 0;
-      fvec<VEC> acc    = splat<VEC>(-0.0f);
-      fold_edges_w<VEC, LANES>(acc, p, b, cs, ce, cl, gl);
-      if (act) stv(b.partial + t * b.partial_stride + c, acc);
-    }
-  }
+  const int gl = threadIdx.x % LANES;
+  for_chunk_pieces<VEC, LANES>(b, p.dim, [&](int64_t t, int64_t cs, int64_t ce, int64_t c, int64_t cl, bool act) {
+    fvec<VEC> acc = splat<VEC>(-0.0f);
+    fold_edges_w<VEC, LANES>(acc, p, b, cs, ce, cl, gl);
+    if (act) stv(b.partial + t * b.partial_stride + c, acc);
+  });
 }
 
 template <int VEC, int LANES>
 __global__ __launch_bounds__(kAggBlock) void aggw_bwd_fold_kernel(wm_aggw_args p, wm_agg_bwd_state b)
 {
   constexpr int kGroups = kAggBlock / LANES;
-  constexpr int64_t C   = kAggChunkEdges;
   const int gl          = threadIdx.x % LANES;
   const int64_t F       = p.dim;
   const int64_t nu      = *b.n_unique;
   for (int64_t s = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; s < p.n_src;
        s += static_cast<int64_t>(gridDim.x) * kGroups) {
-    const int64_t u = b.run_of[s];   // (uninitialised unless s has edges: checked against unique_ids)
-    const bool has  = u >= 0 && u < nu && b.unique_ids[u] == s;
-    int64_t s0 = 0, s1 = 0;
-    if (has) s0 = b.run_starts[u], s1 = b.run_starts[u + 1];
-    const int64_t c0e     = s1 - s0 > C ? s0 + C : s1;
-    const int64_t nchunks = (s1 - s0 + C - 1) / C;
-    const bool self       = s < p.n_dst;
+    const src_run r = run_of_source(b, nu, s);
+    const bool self = s < p.n_dst;
     for (int64_t cb = 0; cb < F; cb += LANES * VEC) {
       const int64_t c  = cb + gl * VEC;
       const bool act   = c < F;
       const int64_t cl = act ? c : 0;
       fvec<VEC> acc    = splat<VEC>(-0.0f);
-      fold_edges_w<VEC, LANES>(acc, p, b, s0, c0e, cl, gl);
-      for (int64_t k0 = 1; k0 < nchunks; k0 += kAggBatch) {   // partials in chunk order, a batch of them in flight
-        fvec<VEC> v[kAggBatch];
-#pragma unroll
-        for (int k = 0; k < kAggBatch; ++k) {
-          const int64_t kk = k0 + k < nchunks ? k0 + k : nchunks - 1;
-          v[k]             = ldv<VEC>(b.partial + ((s0 + kk * C) / C) * b.partial_stride + cl);
-        }
-#pragma unroll
-        for (int k = 0; k < kAggBatch; ++k)
-          if (k0 + k < nchunks) add_to(acc, v[k]);
-      }
-      fvec<VEC> res;
-      if (self) {
-        const fvec<VEC> g = ldv<VEC>(p.grad + s * p.grad_stride + F + cl);
-        res               = g;
-        if (has) {
-          res = acc;
-          add_to(res, g);
-        }
-      } else {
-        res = has ? acc : splat<VEC>(0.0f);
-      }
+      fold_edges_w<VEC, LANES>(acc, p, b, r.s0, r.c0e, cl, gl);
+      add_partials(acc, b, r, cl);
+      const fvec<VEC> res = with_self_term(acc, r.has, self, p.grad, s * p.grad_stride + F + cl);
       if (act) stv(p.out + s * p.out_stride + c, res);
     }
   }
@@ -307,16 +270,10 @@ int hip_aggw_backward(const wm_aggw_args* a, const int32_t* order, const int32_t
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   if (a->dim == 0) return 0;
   if (a->out != nullptr && a->n_src > 0) {   // grad_x: the per-source sums over the id sort
-    wm_agg_args ia{};                        // (the index part is all agg_bwd_prepare reads)
-    ia.row_ptr = a->row_ptr;
-    ia.col_ind = a->col_ind;
-    ia.n_edges = a->n_edges;
-    ia.n_dst   = a->n_dst;
-    ia.n_src   = a->n_src;
-    ia.dim     = a->dim;
-    ia.mean    = a->mean;
     wm_agg_bwd_state b;
-    if (agg_bwd_prepare(&ia, order, run_starts, unique_ids, n_unique_dev, workspace, &b, stream_v) != 0) return -2;
+    if (agg_bwd_prepare(a->row_ptr, a->n_dst, a->n_edges, a->n_src, a->dim, order, run_starts, unique_ids, n_unique_dev,
+                        workspace, &b, stream_v) != 0)
+      return -2;
     const bool v4 = use_vec4(a->dim, a->grad, a->grad_stride, a->out, a->out_stride);
     if (b.n_tiles > 1) {   // (one tile holds no chunk k >= 1)
 #define WM_AGGW_CHUNK(V, L)                                                                                         \

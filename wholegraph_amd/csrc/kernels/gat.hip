@@ -5,8 +5,9 @@
 // Forward:
 //   gat_score_kernel: one thread per (node, head): s_src[j,k] = att[0,k,:] . h[j,k,:] for j < n_src, s_dst[d,k] with att[1]
 //     for d < n_dst, each a left-to-right sum over f.
-//   gat_fwd_kernel: one group of LANES lanes per target d (LANES = 16 / 32 / 64 from the row's pieces, as agg_forward_kernel).
-//     A lane owns VEC columns of one head hk and runs the softmax of that head itself: a pass over s_src for the max, one
+//   gat_fwd_kernel (its body, gat_fwd_body, is in gat_common.cuh: gat_edge.hip compiles it with the edge term): one group
+//     of LANES lanes per target d (LANES = 16 / 32 / 64 from the row's pieces, as agg_forward_kernel). A lane owns
+//     VEC columns of one head hk and runs the softmax of that head itself: a pass over s_src for the max, one
 //     for den = sum of expf(l - max) (left to right), then the pass over the neighbour rows, a batch of kAggBatch rows (and
 //     their s_src) loaded back to back, alpha = expf(l - max) / den recomputed per edge with the same operations (so every
 //     lane of head hk, and the alpha written out, hold the same bits). The lane at the head's first column writes alpha.
@@ -14,11 +15,12 @@
 //     forms ((o_0 + o_1) + ...) * fl(1/H).
 //
 // Backward (no atomics; one fixed order of every sum):
-//   1 gat_bwd_edge_kernel, one thread per (target, head): da = G_k . h[col[e], k, :] per edge (kept in dz[]), c = sum of
-//     alpha * da, then dz = LeakyReLU'(z) * alpha * (da - c) per edge and ds_dst = sum of dz.
+//   1 gat_bwd_edge_kernel (gat_bwd_dz_body in gat_common.cuh), one thread per (target, head): da = G_k . h[col[e], k, :]
+//     per edge (kept in dz[]), c = sum of alpha * da, then dz = LeakyReLU'(z) * alpha * (da - c) per edge and ds_dst = sum of dz.
 //   2 the library's id sort of col_ind (host), gat_bwd_prep_kernel: the target of each sorted position, run_of (as agg).
 //   3 gat_bwd_chunk_kernel / gat_bwd_fold_kernel: per source j, P(j) = sum of alpha * G_k[dst] and ds_src(j) = sum of dz
-//     over its edges in sorted order, cut into chunks of kAggChunkEdges exactly as the agg backward; the fold then writes
+//     over its edges in sorted order, cut into chunks of kAggChunkEdges exactly as the agg backward (the walk is
+//     agg_common.cuh's; a chunk's ds_src rides behind the columns of its partial row); the fold then writes
 //     grad_h[j] = (P + ds_src * att[0]) + ds_dst * att[1] (the last term for j < n_dst) and ds_src[j].
 //   4 gat_att_chunk_kernel / gat_att_fold_kernel: grad_att[0] = sum over j of ds_src[j] * h[j] and grad_att[1] over
 //     j < n_dst with ds_dst, in node chunks of kGatNodeChunk: each chunk left to right, the chunk sums in chunk order.
@@ -59,70 +61,7 @@ __global__ __launch_bounds__(kAggBlock) void gat_score_kernel(wm_gat_args p)
 template <int VEC, int LANES>
 __global__ __launch_bounds__(kAggBlock) void gat_fwd_kernel(wm_gat_args p, float* o, int64_t o_stride)
 {
-  constexpr int kGroups = kAggBlock / LANES;
-  const int gl          = threadIdx.x % LANES;
-  const int64_t H = p.heads, F = p.dim, HF = H * F;
-  const float* s_src = p.scores;
-  for (int64_t d = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; d < p.n_dst;
-       d += static_cast<int64_t>(gridDim.x) * kGroups) {
-    int64_t e0, e1;
-    edge_range(p.row_ptr, d, p.n_edges, e0, e1);
-    for (int64_t cb = 0; cb < HF; cb += LANES * VEC) {   // (group-uniform trip count: the shuffles below stay in step)
-      const int64_t c  = cb + gl * VEC;
-      const bool act   = c < HF;
-      const int64_t cl = act ? c : 0;
-      const int64_t hk = cl / F;   // (a piece never straddles two heads: VEC = 4 only when F % 4 == 0)
-      const bool writer = act && c == hk * F;
-      const float sd    = s_src[(p.n_src + d) * H + hk];
-      float m = -INFINITY, den = -0.0f;
-      for (int pass = 0; pass < 2; ++pass) {   // 0: the max of l, 1: den = sum of expf(l - max), left to right
-        for (int64_t eb = e0; eb < e1; eb += LANES) {
-          const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
-          const int my = gl < nb ? p.col_ind[eb + gl] : 0;
-          for (int j = 0; j < nb; j += kAggBatch) {
-            float s[kAggBatch];
-#pragma unroll
-            for (int k = 0; k < kAggBatch; ++k) {
-              const int src = __shfl(my, j + k < nb ? j + k : nb - 1, LANES);
-              s[k]          = s_src[static_cast<int64_t>(src) * H + hk];
-            }
-#pragma unroll
-            for (int k = 0; k < kAggBatch; ++k) {
-              if (j + k < nb) {
-                const float l = leaky(s[k] + sd, p.slope);
-                if (pass == 0) m = fmaxf(m, l);
-                else den = den + expf(l - m);
-              }
-            }
-          }
-        }
-      }
-      fvec<VEC> acc = splat<VEC>(-0.0f);
-      for (int64_t eb = e0; eb < e1; eb += LANES) {
-        const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
-        const int my = gl < nb ? p.col_ind[eb + gl] : 0;
-        for (int j = 0; j < nb; j += kAggBatch) {
-          fvec<VEC> v[kAggBatch];
-          float s[kAggBatch];
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k) {
-            const int src = __shfl(my, j + k < nb ? j + k : nb - 1, LANES);
-            v[k]          = ldv<VEC>(p.h + static_cast<int64_t>(src) * p.h_stride + cl);
-            s[k]          = s_src[static_cast<int64_t>(src) * H + hk];
-          }
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k) {
-            if (j + k < nb) {
-              const float a = expf(leaky(s[k] + sd, p.slope) - m) / den;
-              add_to(acc, scaled(v[k], a));
-              if (writer) p.alpha[(eb + j + k) * H + hk] = a;
-            }
-          }
-        }
-      }
-      if (act) stv(o + d * o_stride + c, e1 > e0 ? acc : splat<VEC>(0.0f));
-    }
-  }
+  gat_fwd_body<VEC, LANES, false>(p, nullptr, o, o_stride);
 }
 
 // out[d, f] = ((o[d, 0, f] + o[d, 1, f]) + ...) * fl(1 / H)
@@ -140,50 +79,18 @@ __global__ __launch_bounds__(kAggBlock) void gat_head_mean_kernel(wm_gat_args p,
   }
 }
 
-// one thread per (target d, head k): da[e] = G_k[d] . h[col[e], k] (into dz), c = sum of alpha * da, then dz and ds_dst
 template <int VEC>
 __global__ __launch_bounds__(kAggBlock) void gat_bwd_edge_kernel(wm_gat_args p, wm_gat_bwd_state b)
 {
-  const int64_t H = p.heads, F = p.dim, n = p.n_dst * H;
-  const float r   = 1.0f / static_cast<float>(H);
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n;
-       i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-    const int64_t d = i / H, k = i - d * H;
-    int64_t e0, e1;
-    edge_range(p.row_ptr, d, p.n_edges, e0, e1);
-    const float* g = p.grad + d * p.grad_stride + (p.concat ? k * F : 0);
-    float c        = -0.0f;
-    for (int64_t e = e0; e < e1; ++e) {
-      const float* x = p.h + static_cast<int64_t>(p.col_ind[e]) * p.h_stride + k * F;
-      float da       = -0.0f;
-#pragma unroll 4
-      for (int64_t f = 0; f < F; f += VEC) {
-        const fvec<VEC> gv = ldv<VEC>(g + f), xv = ldv<VEC>(x + f);
-#pragma unroll
-        for (int q = 0; q < VEC; ++q) da = da + (p.concat ? gv.v[q] : gv.v[q] * r) * xv.v[q];
-      }
-      b.dz[e * H + k] = da;
-      c               = c + p.alpha[e * H + k] * da;
-    }
-    const float sd = p.scores[(p.n_src + d) * H + k];
-    float dd       = -0.0f;
-    for (int64_t e = e0; e < e1; ++e) {
-      const float z  = p.scores[static_cast<int64_t>(p.col_ind[e]) * H + k] + sd;
-      const float dl = p.alpha[e * H + k] * (b.dz[e * H + k] - c);
-      const float dz = z > 0.0f ? dl : dl * p.slope;
-      b.dz[e * H + k] = dz;
-      dd              = dd + dz;
-    }
-    b.ds_dst[i] = e1 > e0 ? dd : 0.0f;
-  }
+  gat_bwd_dz_body<VEC, false>(p, nullptr, b);
 }
 
 __global__ __launch_bounds__(kAggBlock) void gat_bwd_prep_kernel(wm_gat_args p, wm_gat_bwd_state b)
 {
-  const int64_t nu = *b.n_unique;
+  const int64_t nu = *b.ix.n_unique;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < p.n_edges;
        i += static_cast<int64_t>(gridDim.x) * blockDim.x)
-    bwd_prep_at(i, p.row_ptr, p.n_dst, b.order, b.unique_ids, nu, b.sorted_dst, b.run_of);
+    bwd_prep_at(i, p.row_ptr, p.n_dst, b.ix.order, b.ix.unique_ids, nu, b.ix.sorted_dst, b.ix.run_of);
 }
 
 // acc += alpha[e, hk] * G_k[dst(e)] and ds += dz[e, hk] for the edges at sorted positions [eb0, ee), in that order
@@ -196,7 +103,7 @@ __device__ __forceinline__ void fold_gat_edges(fvec<VEC>& acc, float& ds, const 
   for (int64_t eb = eb0; eb < ee; eb += LANES) {
     const int nb = static_cast<int>(ee - eb < LANES ? ee - eb : LANES);
     int my_e = 0, my_d = 0;
-    if (gl < nb) my_e = b.order[eb + gl], my_d = b.sorted_dst[eb + gl];
+    if (gl < nb) my_e = b.ix.order[eb + gl], my_d = b.ix.sorted_dst[eb + gl];
     for (int j = 0; j < nb; j += kAggBatch) {
       fvec<VEC> v[kAggBatch];
       float a[kAggBatch], z[kAggBatch];
@@ -223,46 +130,38 @@ __device__ __forceinline__ void fold_gat_edges(fvec<VEC>& acc, float& ds, const 
 template <int VEC, int LANES>
 __global__ __launch_bounds__(kAggBlock) void gat_bwd_chunk_kernel(wm_gat_args p, wm_gat_bwd_state b)
 {
-  constexpr int kGroups = kAggBlock / LANES;
-  const int gl          = threadIdx.x % LANES;
-  const int64_t F = p.dim, HF = p.heads * F;
-  const int64_t nu = *b.n_unique;
-  if (nu == 0) return;
-  for (int64_t t = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; t < b.n_tiles;
-       t += static_cast<int64_t>(gridDim.x) * kGroups) {
-    int64_t cs, ce;
-    if (!chunk_in_tile(t, b.run_starts, nu, cs, ce)) continue;
-    for (int64_t cb = 0; cb < HF; cb += LANES * VEC) {
-      const int64_t c  = cb + gl * VEC;
-      const bool act   = c < HF;
-      const int64_t cl = act ? c : 0;
-      const int64_t hk = cl / F;
-      fvec<VEC> acc    = splat<VEC>(-0.0f);
-      float ds         = -0.0f;
-      fold_gat_edges<VEC, LANES>(acc, ds, p, b, cs, ce, p.concat ? cl : cl - hk * F, hk, gl);
-      float* prow = b.partial + t * b.partial_stride;
-      if (act) stv(prow + c, acc);
-      if (act && c == hk * F) prow[b.ds_off + hk] = ds;
-    }
-  }
+  const int gl    = threadIdx.x % LANES;
+  const int64_t F = p.dim;
+  for_chunk_pieces<VEC, LANES>(b.ix, p.heads * F, [&](int64_t t, int64_t cs, int64_t ce, int64_t c, int64_t cl, bool act) {
+    const int64_t hk = cl / F;
+    fvec<VEC> acc    = splat<VEC>(-0.0f);
+    float ds         = -0.0f;
+    fold_gat_edges<VEC, LANES>(acc, ds, p, b, cs, ce, p.concat ? cl : cl - hk * F, hk, gl);
+    float* prow = b.ix.partial + t * b.ix.partial_stride;
+    if (act) stv(prow + c, acc);
+    if (act && c == hk * F) prow[b.ds_off + hk] = ds;
+  });
 }
+
+// the ds_src of a chunk, kept behind the columns of its partial row: loaded and added with them (add_partials)
+struct partial_ds {
+  float& ds;
+  int64_t col;   // ds_off + hk
+  float pd[kAggBatch];
+  __device__ __forceinline__ void load(const float* prow, int k) { pd[k] = prow[col]; }
+  __device__ __forceinline__ void add(int k) { ds = ds + pd[k]; }
+};
 
 template <int VEC, int LANES>
 __global__ __launch_bounds__(kAggBlock) void gat_bwd_fold_kernel(wm_gat_args p, wm_gat_bwd_state b)
 {
   constexpr int kGroups = kAggBlock / LANES;
-  constexpr int64_t C   = kAggChunkEdges;
   const int gl          = threadIdx.x % LANES;
   const int64_t H = p.heads, F = p.dim, HF = H * F;
-  const int64_t nu = *b.n_unique;
+  const int64_t nu = *b.ix.n_unique;
   for (int64_t s = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; s < p.n_src;
        s += static_cast<int64_t>(gridDim.x) * kGroups) {
-    const int64_t u = b.run_of[s];   // (uninitialised unless s has edges: checked against unique_ids)
-    const bool has  = u >= 0 && u < nu && b.unique_ids[u] == s;
-    int64_t s0 = 0, s1 = 0;
-    if (has) s0 = b.run_starts[u], s1 = b.run_starts[u + 1];
-    const int64_t c0e     = s1 - s0 > C ? s0 + C : s1;
-    const int64_t nchunks = (s1 - s0 + C - 1) / C;
+    const src_run r = run_of_source(b.ix, nu, s);
     for (int64_t cb = 0; cb < HF; cb += LANES * VEC) {
       const int64_t c  = cb + gl * VEC;
       const bool act   = c < HF;
@@ -270,26 +169,9 @@ __global__ __launch_bounds__(kAggBlock) void gat_bwd_fold_kernel(wm_gat_args p, 
       const int64_t hk = cl / F;
       fvec<VEC> acc    = splat<VEC>(-0.0f);
       float ds         = -0.0f;
-      fold_gat_edges<VEC, LANES>(acc, ds, p, b, s0, c0e, p.concat ? cl : cl - hk * F, hk, gl);
-      for (int64_t k0 = 1; k0 < nchunks; k0 += kAggBatch) {   // partials in chunk order, a batch of them in flight
-        fvec<VEC> v[kAggBatch];
-        float pd[kAggBatch];
-#pragma unroll
-        for (int k = 0; k < kAggBatch; ++k) {
-          const int64_t kk   = k0 + k < nchunks ? k0 + k : nchunks - 1;
-          const float* prow  = b.partial + ((s0 + kk * C) / C) * b.partial_stride;
-          v[k]               = ldv<VEC>(prow + cl);
-          pd[k]              = prow[b.ds_off + hk];
-        }
-#pragma unroll
-        for (int k = 0; k < kAggBatch; ++k) {
-          if (k0 + k < nchunks) {
-            add_to(acc, v[k]);
-            ds = ds + pd[k];
-          }
-        }
-      }
-      if (!has) acc = splat<VEC>(0.0f), ds = 0.0f;
+      fold_gat_edges<VEC, LANES>(acc, ds, p, b, r.s0, r.c0e, p.concat ? cl : cl - hk * F, hk, gl);
+      add_partials(acc, b.ix, r, cl, partial_ds{ds, b.ds_off + hk});
+      if (!r.has) acc = splat<VEC>(0.0f), ds = 0.0f;
       fvec<VEC> res = acc;
       add_to(res, scaled(ldv<VEC>(p.att + cl), ds));
       if (s < p.n_dst) add_to(res, scaled(ldv<VEC>(p.att + HF + cl), b.ds_dst[s * H + hk]));
@@ -332,13 +214,12 @@ __global__ __launch_bounds__(kAggBlock) void gat_att_fold_kernel(wm_gat_args p, 
   p.grad_att[c] = nq > 0 ? acc : 0.0f;
 }
 
-int64_t up4(int64_t v) { return (v + 3) / 4 * 4; }
-
 }  // namespace
 
 size_t hip_gat_forward_workspace_bytes(const wm_gat_args* a)
 {
-  return a->concat ? 0 : static_cast<size_t>(a->n_dst * a->heads * a->dim) * 4 + 256;
+  const int64_t sizes[1] = {a->n_dst * a->heads * a->dim * 4};   // the per-head rows before the mean over heads
+  return a->concat ? 0 : ws_plan(sizes).bytes;
 }
 
 int gat_scores(const wm_gat_args* a, void* stream_v)
@@ -367,7 +248,7 @@ int hip_gat_forward(const wm_gat_args* a, void* workspace, void* stream_v)
   const bool f4   = F % 4 == 0 && aligned16(a->att);
   if (gat_scores(a, stream_v) != 0) return -2;
   if (a->n_dst == 0) return 0;
-  float* o         = a->concat ? a->out : reinterpret_cast<float*>(up256(reinterpret_cast<uintptr_t>(workspace)));
+  float* o         = a->concat ? a->out : ws_at<float>(workspace, 0);   // (the workspace's one region)
   const int64_t os = a->concat ? a->out_stride : HF;
   const bool v4    = f4 && use_vec4(HF, a->h, a->h_stride, o, os);
 #define WM_GAT_FWD(V, L)                                                                                                   \
@@ -383,10 +264,10 @@ int hip_gat_forward(const wm_gat_args* a, void* workspace, void* stream_v)
 namespace {
 struct gat_bwd_layout {
   int64_t n_tiles, partial_stride, ds_off, n_node_chunks;
-  size_t off[7], bytes;   // sorted_dst, run_of, dz, ds_dst, ds_src, partial, att_partial
+  ws_layout<8> ws;   // sorted_dst, run_of, dz, ds_dst, ds_src, partial, att_partial, the caller's extra region
 };
 
-gat_bwd_layout bwd_layout(const wm_gat_args* a)
+gat_bwd_layout bwd_layout(const wm_gat_args* a, int64_t extra_bytes)
 {
   gat_bwd_layout l;
   const int64_t H = a->heads, HF = H * a->dim, E = a->n_edges;
@@ -394,41 +275,36 @@ gat_bwd_layout bwd_layout(const wm_gat_args* a)
   l.ds_off         = up4(HF);
   l.partial_stride = l.ds_off + up4(H);
   l.n_node_chunks  = (a->n_src + kGatNodeChunk - 1) / kGatNodeChunk;
-  const int64_t sizes[7] = {E * 4, a->n_src * 4, E * H * 4, a->n_dst * H * 4, a->n_src * H * 4,
-                            l.n_tiles * l.partial_stride * 4, l.n_node_chunks * 2 * HF * 4};
-  size_t w = 0;
-  for (int i = 0; i < 7; ++i) {
-    l.off[i] = w;
-    w        = up256(w + static_cast<size_t>(sizes[i]));
-  }
-  l.bytes = w + 256;   // (+ the alignment of the workspace's start)
+  const int64_t sizes[8] = {E * 4, a->n_src * 4, E * H * 4, a->n_dst * H * 4, a->n_src * H * 4,
+                            l.n_tiles * l.partial_stride * 4, l.n_node_chunks * 2 * HF * 4, extra_bytes};
+  l.ws = ws_plan(sizes);
   return l;
 }
 }  // namespace
 
-size_t hip_gat_backward_workspace_bytes(const wm_gat_args* a) { return bwd_layout(a).bytes; }
+size_t gat_bwd_workspace_bytes(const wm_gat_args* a, int64_t extra_bytes) { return bwd_layout(a, extra_bytes).ws.bytes; }
+size_t hip_gat_backward_workspace_bytes(const wm_gat_args* a) { return gat_bwd_workspace_bytes(a, 0); }
 
-size_t gat_bwd_carve(const wm_gat_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                     const int64_t* n_unique_dev, void* workspace, wm_gat_bwd_state* b)
+void* gat_bwd_carve(const wm_gat_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                    const int64_t* n_unique_dev, void* workspace, int64_t extra_bytes, wm_gat_bwd_state* b)
 {
-  const gat_bwd_layout l = bwd_layout(a);
-  const uintptr_t w0     = up256(reinterpret_cast<uintptr_t>(workspace));
-  b->order          = order;
-  b->run_starts     = run_starts;
-  b->unique_ids     = unique_ids;
-  b->n_unique       = n_unique_dev;
-  b->sorted_dst     = reinterpret_cast<int32_t*>(w0 + l.off[0]);
-  b->run_of         = reinterpret_cast<int32_t*>(w0 + l.off[1]);
-  b->dz             = reinterpret_cast<float*>(w0 + l.off[2]);
-  b->ds_dst         = reinterpret_cast<float*>(w0 + l.off[3]);
-  b->ds_src         = reinterpret_cast<float*>(w0 + l.off[4]);
-  b->partial        = reinterpret_cast<float*>(w0 + l.off[5]);
-  b->att_partial    = reinterpret_cast<float*>(w0 + l.off[6]);
-  b->n_tiles        = l.n_tiles;
-  b->partial_stride = l.partial_stride;
-  b->ds_off         = l.ds_off;
-  b->n_node_chunks  = l.n_node_chunks;
-  return l.bytes - 256;
+  const gat_bwd_layout l = bwd_layout(a, extra_bytes);
+  b->ix.order          = order;
+  b->ix.run_starts     = run_starts;
+  b->ix.unique_ids     = unique_ids;
+  b->ix.n_unique       = n_unique_dev;
+  b->ix.sorted_dst     = ws_at<int32_t>(workspace, l.ws.off[0]);
+  b->ix.run_of         = ws_at<int32_t>(workspace, l.ws.off[1]);
+  b->dz                = ws_at<float>(workspace, l.ws.off[2]);
+  b->ds_dst            = ws_at<float>(workspace, l.ws.off[3]);
+  b->ds_src            = ws_at<float>(workspace, l.ws.off[4]);
+  b->ix.partial        = ws_at<float>(workspace, l.ws.off[5]);
+  b->att_partial       = ws_at<float>(workspace, l.ws.off[6]);
+  b->ix.n_tiles        = l.n_tiles;
+  b->ix.partial_stride = l.partial_stride;
+  b->ds_off            = l.ds_off;
+  b->n_node_chunks     = l.n_node_chunks;
+  return ws_at<void>(workspace, l.ws.off[7]);
 }
 
 int gat_bwd_after_dz(const wm_gat_args* a, const wm_gat_bwd_state* bp, void* stream_v)
@@ -443,9 +319,9 @@ int gat_bwd_after_dz(const wm_gat_args* a, const wm_gat_bwd_state* bp, void* str
       if (rc_last() != 0) return -2;
     }
     const bool v4 = gat_bwd_vec4(a) && use_vec4(HF, a->grad_h, a->grad_h_stride, a->grad_h, a->grad_h_stride);
-    if (b.n_tiles > 1) {   // (one tile holds no chunk k >= 1)
+    if (b.ix.n_tiles > 1) {   // (one tile holds no chunk k >= 1)
 #define WM_GAT_CHUNK(V, L)                                                                                                   \
-  hipLaunchKernelGGL((gat_bwd_chunk_kernel<V, L>), dim3(blocks_for(b.n_tiles, kAggBlock / (L))), dim3(kAggBlock), 0, stream, \
+  hipLaunchKernelGGL((gat_bwd_chunk_kernel<V, L>), dim3(blocks_for(b.ix.n_tiles, kAggBlock / (L))), dim3(kAggBlock), 0, stream, \
                      *a, b)
       WM_AGG_DISPATCH(v4, v4 ? HF / 4 : HF, WM_GAT_CHUNK);
 #undef WM_GAT_CHUNK
@@ -470,7 +346,7 @@ int hip_gat_backward(const wm_gat_args* a, const int32_t* order, const int32_t* 
 {
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   wm_gat_bwd_state b;
-  gat_bwd_carve(a, order, run_starts, unique_ids, n_unique_dev, workspace, &b);
+  gat_bwd_carve(a, order, run_starts, unique_ids, n_unique_dev, workspace, 0, &b);
   if (a->n_dst > 0) {
     const int blocks = blocks_for(a->n_dst * a->heads, kAggBlock);
     if (gat_bwd_vec4(a)) hipLaunchKernelGGL(gat_bwd_edge_kernel<4>, dim3(blocks), dim3(kAggBlock), 0, stream, *a, b);

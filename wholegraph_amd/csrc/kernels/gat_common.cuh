@@ -1,37 +1,35 @@
 // wholegraph_amd — what the two attention ops of a sampled CSC block share (kernels/gat.hip, the GAT `mha_gat_n2n` op, and
-// kernels/gat_edge.hip, the same op with an edge term in the logit): the scratch of the backward and the stages of gat.hip
+// kernels/gat_edge.hip, the same op with an edge term in the logit): the scratch of the backward; the stages of gat.hip
 // that do not see the logit — the node scores and the mean over heads of the forward, and everything of the backward
-// behind dz (wholegraph_amd_ext.h, section 2c). The kernels of those stages live in gat.hip alone.
+// behind dz (wholegraph_amd_ext.h, section 2c), whose kernels live in gat.hip alone; and the bodies of the two stages that
+// do see it (gat_fwd_body, gat_bwd_dz_body), with the edge term of section 2f compiled in or out.
 #pragma once
+#include <math.h>
+
 #include "agg_common.cuh"
 
 namespace wm {
 
-// backward scratch: the id sort's outputs and the op's workspace (gat_bwd_carve)
+// backward scratch: the index of the per-source walk and the op's own regions of the workspace (gat_bwd_carve)
 struct wm_gat_bwd_state {
-  const int32_t* order;        // [n_edges] edge positions, sorted by source (stable)
-  const int32_t* run_starts;   // [n_unique + 1]
-  const int32_t* unique_ids;   // [n_unique] sources with edges, ascending
-  const int64_t* n_unique;     // device scalar written by the sort
-  int32_t* sorted_dst;         // [n_edges]
-  int32_t* run_of;             // [n_src]
+  csc_bwd_index ix;            // partial: P of a chunk (ds_off columns), then its ds_src (heads)
   float* dz;                   // [n_edges, heads]: da, then dz
   float* ds_dst;               // [n_dst, heads]
   float* ds_src;               // [n_src, heads]
-  float* partial;              // [n_tiles, partial_stride]: P of a chunk (ds_off columns), then its ds_src (heads)
   float* att_partial;          // [n_node_chunks, 2 * heads * dim]
-  int64_t n_tiles, partial_stride, ds_off, n_node_chunks;
+  int64_t ds_off, n_node_chunks;
 };
 
 // forward: s_src / s_dst into a->scores
 int gat_scores(const wm_gat_args* a, void* stream);
 // forward, concat == 0: a->out from the per-head rows o [n_dst, o_stride]
 int gat_head_mean(const wm_gat_args* a, const float* o, int64_t o_stride, void* stream);
-size_t hip_gat_backward_workspace_bytes(const wm_gat_args* a);
-// backward: fills `b` from the id sort's outputs and `workspace` (hip_gat_backward_workspace_bytes); returns the bytes of
-// the 256-byte aligned workspace it took (what follows them is the caller's)
-size_t gat_bwd_carve(const wm_gat_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                     const int64_t* n_unique_dev, void* workspace, wm_gat_bwd_state* b);
+// the backward's workspace with a last region of `extra_bytes` for the caller (gat_edge.hip's chunk sums; 0: none)
+size_t gat_bwd_workspace_bytes(const wm_gat_args* a, int64_t extra_bytes);
+// backward: fills `b` from the id sort's outputs and `workspace` (gat_bwd_workspace_bytes with the same extra_bytes);
+// returns the caller's region
+void* gat_bwd_carve(const wm_gat_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                    const int64_t* n_unique_dev, void* workspace, int64_t extra_bytes, wm_gat_bwd_state* b);
 // backward behind b->dz and b->ds_dst (steps 2 - 4 of gat.hip): grad_h, ds_src and halves 0 and 1 of grad_att
 int gat_bwd_after_dz(const wm_gat_args* a, const wm_gat_bwd_state* b, void* stream);
 
@@ -39,7 +37,125 @@ namespace {
 
 __device__ __forceinline__ float leaky(float z, float slope) { return z > 0.0f ? z : slope * z; }
 
-uintptr_t up256(uintptr_t v) { return (v + 255) & ~static_cast<uintptr_t>(255); }
+// the softmax and the weighted sum of a target's neighbour rows (gat.hip, forward). EDGE: the logit is
+// (s_src[col[e]] + s_dst[d]) + edge_scores[e, hk], edge_scores loaded next to s_src in every batch
+template <int VEC, int LANES, bool EDGE>
+__device__ __forceinline__ void gat_fwd_body(const wm_gat_args& p, const float* edge_scores, float* o, int64_t o_stride)
+{
+  constexpr int kGroups = kAggBlock / LANES;
+  const int gl          = threadIdx.x % LANES;
+  const int64_t H = p.heads, F = p.dim, HF = H * F;
+  const float* s_src = p.scores;
+  for (int64_t d = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; d < p.n_dst;
+       d += static_cast<int64_t>(gridDim.x) * kGroups) {
+    int64_t e0, e1;
+    edge_range(p.row_ptr, d, p.n_edges, e0, e1);
+    for (int64_t cb = 0; cb < HF; cb += LANES * VEC) {   // (group-uniform trip count: the shuffles below stay in step)
+      const int64_t c  = cb + gl * VEC;
+      const bool act   = c < HF;
+      const int64_t cl = act ? c : 0;
+      const int64_t hk = cl / F;   // (a piece never straddles two heads: VEC = 4 only when F % 4 == 0)
+      const bool writer = act && c == hk * F;
+      const float sd    = s_src[(p.n_src + d) * H + hk];
+      float m = -INFINITY, den = -0.0f;
+      for (int pass = 0; pass < 2; ++pass) {   // 0: the max of l, 1: den = sum of expf(l - max), left to right
+        for (int64_t eb = e0; eb < e1; eb += LANES) {
+          const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
+          const int my = gl < nb ? p.col_ind[eb + gl] : 0;
+          for (int j = 0; j < nb; j += kAggBatch) {
+            float s[kAggBatch], se[kAggBatch];
+#pragma unroll
+            for (int k = 0; k < kAggBatch; ++k) {
+              const int from = j + k < nb ? j + k : nb - 1;
+              const int src  = __shfl(my, from, LANES);
+              s[k]           = s_src[static_cast<int64_t>(src) * H + hk];
+              if constexpr (EDGE) se[k] = edge_scores[(eb + from) * H + hk];
+            }
+#pragma unroll
+            for (int k = 0; k < kAggBatch; ++k) {
+              if (j + k < nb) {
+                float z = s[k] + sd;
+                if constexpr (EDGE) z = z + se[k];
+                const float l = leaky(z, p.slope);
+                if (pass == 0) m = fmaxf(m, l);
+                else den = den + expf(l - m);
+              }
+            }
+          }
+        }
+      }
+      fvec<VEC> acc = splat<VEC>(-0.0f);
+      for (int64_t eb = e0; eb < e1; eb += LANES) {
+        const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
+        const int my = gl < nb ? p.col_ind[eb + gl] : 0;
+        for (int j = 0; j < nb; j += kAggBatch) {
+          fvec<VEC> v[kAggBatch];
+          float s[kAggBatch], se[kAggBatch];
+#pragma unroll
+          for (int k = 0; k < kAggBatch; ++k) {
+            const int from = j + k < nb ? j + k : nb - 1;
+            const int src  = __shfl(my, from, LANES);
+            v[k]           = ldv<VEC>(p.h + static_cast<int64_t>(src) * p.h_stride + cl);
+            s[k]           = s_src[static_cast<int64_t>(src) * H + hk];
+            if constexpr (EDGE) se[k] = edge_scores[(eb + from) * H + hk];
+          }
+#pragma unroll
+          for (int k = 0; k < kAggBatch; ++k) {
+            if (j + k < nb) {
+              float z = s[k] + sd;
+              if constexpr (EDGE) z = z + se[k];
+              const float a = expf(leaky(z, p.slope) - m) / den;
+              add_to(acc, scaled(v[k], a));
+              if (writer) p.alpha[(eb + j + k) * H + hk] = a;
+            }
+          }
+        }
+      }
+      if (act) stv(o + d * o_stride + c, e1 > e0 ? acc : splat<VEC>(0.0f));
+    }
+  }
+}
+
+// one thread per (target d, head k): da[e] = G_k[d] . h[col[e], k] (into dz), c = sum of alpha * da, then dz and ds_dst;
+// EDGE: the recomputed z has the edge term of gat_fwd_body
+template <int VEC, bool EDGE>
+__device__ __forceinline__ void gat_bwd_dz_body(const wm_gat_args& p, const float* edge_scores, const wm_gat_bwd_state& b)
+{
+  const int64_t H = p.heads, F = p.dim, n = p.n_dst * H;
+  const float r   = 1.0f / static_cast<float>(H);
+  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n;
+       i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const int64_t d = i / H, k = i - d * H;
+    int64_t e0, e1;
+    edge_range(p.row_ptr, d, p.n_edges, e0, e1);
+    const float* g = p.grad + d * p.grad_stride + (p.concat ? k * F : 0);
+    float c        = -0.0f;
+    for (int64_t e = e0; e < e1; ++e) {
+      const float* x = p.h + static_cast<int64_t>(p.col_ind[e]) * p.h_stride + k * F;
+      float da       = -0.0f;
+#pragma unroll 4
+      for (int64_t f = 0; f < F; f += VEC) {
+        const fvec<VEC> gv = ldv<VEC>(g + f), xv = ldv<VEC>(x + f);
+#pragma unroll
+        for (int q = 0; q < VEC; ++q) da = da + (p.concat ? gv.v[q] : gv.v[q] * r) * xv.v[q];
+      }
+      b.dz[e * H + k] = da;
+      c               = c + p.alpha[e * H + k] * da;
+    }
+    const float sd = p.scores[(p.n_src + d) * H + k];
+    float dd       = -0.0f;
+    for (int64_t e = e0; e < e1; ++e) {
+      float z = p.scores[static_cast<int64_t>(p.col_ind[e]) * H + k] + sd;
+      if constexpr (EDGE) z = z + edge_scores[e * H + k];
+      const float dl = p.alpha[e * H + k] * (b.dz[e * H + k] - c);
+      const float dz = z > 0.0f ? dl : dl * p.slope;
+      b.dz[e * H + k] = dz;
+      dd              = dd + dz;
+    }
+    b.ds_dst[i] = e1 > e0 ? dd : 0.0f;
+  }
+}
+
 bool aligned16(const void* ptr) { return reinterpret_cast<uintptr_t>(ptr) % 16 == 0; }
 // 16-byte pieces in the backward: whole heads of F % 4 == 0 columns, every row start and att 16-byte aligned
 bool gat_bwd_vec4(const wm_gat_args* a)

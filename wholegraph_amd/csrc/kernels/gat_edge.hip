@@ -10,9 +10,11 @@
 //     memory order — neighbouring lanes read neighbouring addresses, 16-byte pieces when the rows allow — then each thread
 //     walks its own segment in LDS, left to right, adding att[2,k,f] * edge_feat[e,k,f]. A segment's LDS pitch is odd, so
 //     the 32 lanes of a ds_read_b32 group hit 32 banks.
-//   gat_edge_fwd_kernel: gat_fwd_kernel with edge_scores[e, hk] loaded next to s_src in every batch.
+//   gat_edge_fwd_kernel: gat_fwd_kernel with edge_scores[e, hk] loaded next to s_src in every batch: the same body
+//     (gat_fwd_body in gat_common.cuh) compiled with the edge term.
 // Backward:
-//   gat_edge_bwd_dz_kernel: gat_bwd_edge_kernel with the edge term in the recomputed z; then gat.hip's steps 2 - 4.
+//   gat_edge_bwd_dz_kernel: gat_bwd_edge_kernel with the edge term in the recomputed z (gat_bwd_dz_body, likewise); then
+//     gat.hip's steps 2 - 4.
 //   gat_edge_grad_chunk_kernel: one thread per (edge chunk q, piece of columns): grad_edge_feat[e] = dz[e,k] * att[2] for
 //     the chunk's edges and, from the same dz, the chunk's sum of dz[e,k] * edge_feat[e], left to right; chunks of
 //     kGatNodeChunk edges. gat_edge_att_fold_kernel adds the chunk sums in chunk order into grad_att[2].
@@ -72,115 +74,13 @@ __global__ __launch_bounds__(kAggBlock) void gat_edge_score_kernel(wm_gat_edge_a
 template <int VEC, int LANES>
 __global__ __launch_bounds__(kAggBlock) void gat_edge_fwd_kernel(wm_gat_edge_args pe, float* o, int64_t o_stride)
 {
-  constexpr int kGroups = kAggBlock / LANES;
-  const wm_gat_args& p  = pe.g;
-  const int gl          = threadIdx.x % LANES;
-  const int64_t H = p.heads, F = p.dim, HF = H * F;
-  const float* s_src = p.scores;
-  const float* s_edg = pe.edge_scores;
-  for (int64_t d = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; d < p.n_dst;
-       d += static_cast<int64_t>(gridDim.x) * kGroups) {
-    int64_t e0, e1;
-    edge_range(p.row_ptr, d, p.n_edges, e0, e1);
-    for (int64_t cb = 0; cb < HF; cb += LANES * VEC) {   // (group-uniform trip count: the shuffles below stay in step)
-      const int64_t c  = cb + gl * VEC;
-      const bool act   = c < HF;
-      const int64_t cl = act ? c : 0;
-      const int64_t hk = cl / F;   // (a piece never straddles two heads: VEC = 4 only when F % 4 == 0)
-      const bool writer = act && c == hk * F;
-      const float sd    = s_src[(p.n_src + d) * H + hk];
-      float m = -INFINITY, den = -0.0f;
-      for (int pass = 0; pass < 2; ++pass) {   // 0: the max of l, 1: den = sum of expf(l - max), left to right
-        for (int64_t eb = e0; eb < e1; eb += LANES) {
-          const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
-          const int my = gl < nb ? p.col_ind[eb + gl] : 0;
-          for (int j = 0; j < nb; j += kAggBatch) {
-            float s[kAggBatch], se[kAggBatch];
-#pragma unroll
-            for (int k = 0; k < kAggBatch; ++k) {
-              const int from = j + k < nb ? j + k : nb - 1;
-              const int src  = __shfl(my, from, LANES);
-              s[k]           = s_src[static_cast<int64_t>(src) * H + hk];
-              se[k]          = s_edg[(eb + from) * H + hk];
-            }
-#pragma unroll
-            for (int k = 0; k < kAggBatch; ++k) {
-              if (j + k < nb) {
-                const float l = leaky((s[k] + sd) + se[k], p.slope);
-                if (pass == 0) m = fmaxf(m, l);
-                else den = den + expf(l - m);
-              }
-            }
-          }
-        }
-      }
-      fvec<VEC> acc = splat<VEC>(-0.0f);
-      for (int64_t eb = e0; eb < e1; eb += LANES) {
-        const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
-        const int my = gl < nb ? p.col_ind[eb + gl] : 0;
-        for (int j = 0; j < nb; j += kAggBatch) {
-          fvec<VEC> v[kAggBatch];
-          float s[kAggBatch], se[kAggBatch];
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k) {
-            const int from = j + k < nb ? j + k : nb - 1;
-            const int src  = __shfl(my, from, LANES);
-            v[k]           = ldv<VEC>(p.h + static_cast<int64_t>(src) * p.h_stride + cl);
-            s[k]           = s_src[static_cast<int64_t>(src) * H + hk];
-            se[k]          = s_edg[(eb + from) * H + hk];
-          }
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k) {
-            if (j + k < nb) {
-              const float a = expf(leaky((s[k] + sd) + se[k], p.slope) - m) / den;
-              add_to(acc, scaled(v[k], a));
-              if (writer) p.alpha[(eb + j + k) * H + hk] = a;
-            }
-          }
-        }
-      }
-      if (act) stv(o + d * o_stride + c, e1 > e0 ? acc : splat<VEC>(0.0f));
-    }
-  }
+  gat_fwd_body<VEC, LANES, true>(pe.g, pe.edge_scores, o, o_stride);
 }
 
-// one thread per (target d, head k), as gat_bwd_edge_kernel: da (kept in dz[]), c, then dz from the z of section 2f, ds_dst
 template <int VEC>
 __global__ __launch_bounds__(kAggBlock) void gat_edge_bwd_dz_kernel(wm_gat_edge_args pe, wm_gat_bwd_state b)
 {
-  const wm_gat_args& p = pe.g;
-  const int64_t H = p.heads, F = p.dim, n = p.n_dst * H;
-  const float r   = 1.0f / static_cast<float>(H);
-  for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < n;
-       i += static_cast<int64_t>(gridDim.x) * blockDim.x) {
-    const int64_t d = i / H, k = i - d * H;
-    int64_t e0, e1;
-    edge_range(p.row_ptr, d, p.n_edges, e0, e1);
-    const float* g = p.grad + d * p.grad_stride + (p.concat ? k * F : 0);
-    float c        = -0.0f;
-    for (int64_t e = e0; e < e1; ++e) {
-      const float* x = p.h + static_cast<int64_t>(p.col_ind[e]) * p.h_stride + k * F;
-      float da       = -0.0f;
-#pragma unroll 4
-      for (int64_t f = 0; f < F; f += VEC) {
-        const fvec<VEC> gv = ldv<VEC>(g + f), xv = ldv<VEC>(x + f);
-#pragma unroll
-        for (int q = 0; q < VEC; ++q) da = da + (p.concat ? gv.v[q] : gv.v[q] * r) * xv.v[q];
-      }
-      b.dz[e * H + k] = da;
-      c               = c + p.alpha[e * H + k] * da;
-    }
-    const float sd = p.scores[(p.n_src + d) * H + k];
-    float dd       = -0.0f;
-    for (int64_t e = e0; e < e1; ++e) {
-      const float z  = (p.scores[static_cast<int64_t>(p.col_ind[e]) * H + k] + sd) + pe.edge_scores[e * H + k];
-      const float dl = p.alpha[e * H + k] * (b.dz[e * H + k] - c);
-      const float dz = z > 0.0f ? dl : dl * p.slope;
-      b.dz[e * H + k] = dz;
-      dd              = dd + dz;
-    }
-    b.ds_dst[i] = e1 > e0 ? dd : 0.0f;
-  }
+  gat_bwd_dz_body<VEC, true>(pe.g, pe.edge_scores, b);
 }
 
 // one thread per (edge chunk q, piece of VEC columns at c): grad_edge_feat[e, c..] = dz[e, k] * att[2, c..] for the edges
@@ -250,7 +150,7 @@ int hip_gat_edge_forward(const wm_gat_edge_args* ea, void* workspace, void* stre
     else hipLaunchKernelGGL(gat_edge_score_kernel<1>, dim3(blocks), dim3(kAggBlock), 0, stream, *ea);
     if (rc_last() != 0) return -2;
   }
-  float* o         = a->concat ? a->out : reinterpret_cast<float*>(up256(reinterpret_cast<uintptr_t>(workspace)));
+  float* o         = a->concat ? a->out : ws_at<float>(workspace, 0);   // (the workspace's one region)
   const int64_t os = a->concat ? a->out_stride : HF;
   const bool v4    = f4 && use_vec4(HF, a->h, a->h_stride, o, os);
 #define WM_GAT_EDGE_FWD(V, L)                                                                                         \
@@ -266,7 +166,7 @@ int hip_gat_edge_forward(const wm_gat_edge_args* ea, void* workspace, void* stre
 size_t hip_gat_edge_backward_workspace_bytes(const wm_gat_edge_args* ea)
 {
   const wm_gat_args* a = &ea->g;
-  return hip_gat_backward_workspace_bytes(a) + static_cast<size_t>(edge_chunks(a) * a->heads * a->dim) * 4;
+  return gat_bwd_workspace_bytes(a, edge_chunks(a) * a->heads * a->dim * 4);
 }
 
 int hip_gat_edge_backward(const wm_gat_edge_args* ea, const int32_t* order, const int32_t* run_starts,
@@ -276,9 +176,9 @@ int hip_gat_edge_backward(const wm_gat_edge_args* ea, const int32_t* order, cons
   const wm_gat_args* a = &ea->g;
   const int64_t HF     = a->heads * a->dim;
   wm_gat_bwd_state b;
-  const size_t used = gat_bwd_carve(a, order, run_starts, unique_ids, n_unique_dev, workspace, &b);
-  float* epart      = reinterpret_cast<float*>(up256(reinterpret_cast<uintptr_t>(workspace)) + used);   // [chunks, HF]
-  const bool f4     = gat_bwd_vec4(a);
+  float* epart  = static_cast<float*>(gat_bwd_carve(a, order, run_starts, unique_ids, n_unique_dev, workspace,
+                                                    edge_chunks(a) * HF * 4, &b));   // [chunks, HF]
+  const bool f4 = gat_bwd_vec4(a);
   if (a->n_dst > 0) {
     const int blocks = blocks_for(a->n_dst * a->heads, kAggBlock);
     if (f4) hipLaunchKernelGGL(gat_edge_bwd_dz_kernel<4>, dim3(blocks), dim3(kAggBlock), 0, stream, *ea, b);

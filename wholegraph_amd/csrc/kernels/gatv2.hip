@@ -26,7 +26,8 @@
 //   2 gatv2_att_chunk_kernel / gatv2_att_fold_kernel: grad_att = the A(d) summed in node chunks of kGatNodeChunk.
 //   3 the library's id sort of col_ind (host), gatv2_bwd_prep_kernel, then gatv2_bwd_chunk_kernel / gatv2_bwd_fold_kernel:
 //     per source j, the sum of (alpha * G_k[d]) + dl * g over its edges in sorted order, cut into chunks of kAggChunkEdges
-//     exactly as the agg backward. Per edge they read G[d], h_dst[d], alpha[e] and dl[e]; the source's own row once.
+//     exactly as the agg backward (the walk is agg_common.cuh's). Per edge they read G[d], h_dst[d], alpha[e] and dl[e];
+//     the source's own row once.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -37,20 +38,14 @@
 namespace wm {
 namespace {
 
-// backward scratch: the id sort's outputs and the op's workspace
+// backward scratch: the index of the per-source walk and the op's own regions of the workspace
 struct gatv2_bwd_state {
-  const int32_t* order;        // [n_edges] edge positions, sorted by source (stable)
-  const int32_t* run_starts;   // [n_unique + 1]
-  const int32_t* unique_ids;   // [n_unique] sources with edges, ascending
-  const int64_t* n_unique;     // device scalar written by the sort
-  int32_t* sorted_dst;         // [n_edges]
-  int32_t* run_of;             // [n_src]
+  csc_bwd_index ix;
   float* da;                   // [n_edges, heads]
   float* dl;                   // [n_edges, heads]
   float* arow;                 // [n_dst, heads * dim]: A(d)
   float* att_partial;          // [n_node_chunks, heads * dim]
-  float* partial;              // [n_tiles, partial_stride]
-  int64_t n_tiles, partial_stride, n_node_chunks;
+  int64_t n_node_chunks;
 };
 
 // the balanced tree of adjacent pairs over a stream of terms: push() them in order, 2^levels of them in all
@@ -318,10 +313,10 @@ __global__ __launch_bounds__(kAggBlock) void gatv2_att_fold_kernel(wm_gatv2_args
 
 __global__ __launch_bounds__(kAggBlock) void gatv2_bwd_prep_kernel(wm_gatv2_args p, gatv2_bwd_state b)
 {
-  const int64_t nu = *b.n_unique;
+  const int64_t nu = *b.ix.n_unique;
   for (int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; i < p.n_edges;
        i += static_cast<int64_t>(gridDim.x) * blockDim.x)
-    bwd_prep_at(i, p.row_ptr, p.n_dst, b.order, b.unique_ids, nu, b.sorted_dst, b.run_of);
+    bwd_prep_at(i, p.row_ptr, p.n_dst, b.ix.order, b.ix.unique_ids, nu, b.ix.sorted_dst, b.ix.run_of);
 }
 
 // acc += (alpha[e, hk] * G_k[dst(e)]) + dl[e, hk] * g for the edges at sorted positions [eb0, ee), in that order; hs is the
@@ -336,7 +331,7 @@ __device__ __forceinline__ void fold_gatv2_edges(fvec<VEC>& acc, const wm_gatv2_
   for (int64_t eb = eb0; eb < ee; eb += LANES) {
     const int nb = static_cast<int>(ee - eb < LANES ? ee - eb : LANES);
     int my_e = 0, my_d = 0;
-    if (gl < nb) my_e = b.order[eb + gl], my_d = b.sorted_dst[eb + gl];
+    if (gl < nb) my_e = b.ix.order[eb + gl], my_d = b.ix.sorted_dst[eb + gl];
     for (int j = 0; j < nb; j += kAggBatch) {
       fvec<VEC> gv[kAggBatch], hd[kAggBatch];
       float a[kAggBatch], x[kAggBatch];
@@ -369,45 +364,28 @@ __device__ __forceinline__ void fold_gatv2_edges(fvec<VEC>& acc, const wm_gatv2_
 template <int VEC, int LANES>
 __global__ __launch_bounds__(kAggBlock) void gatv2_bwd_chunk_kernel(wm_gatv2_args p, gatv2_bwd_state b)
 {
-  constexpr int kGroups = kAggBlock / LANES;
-  const int gl          = threadIdx.x % LANES;
-  const int64_t F = p.dim, HF = p.heads * F;
-  const int64_t nu = *b.n_unique;
-  if (nu == 0) return;
-  for (int64_t t = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; t < b.n_tiles;
-       t += static_cast<int64_t>(gridDim.x) * kGroups) {
-    int64_t cs, ce;
-    if (!chunk_in_tile(t, b.run_starts, nu, cs, ce)) continue;
-    const int64_t s = p.col_ind[b.order[cs]];   // the source this chunk belongs to
-    for (int64_t cb = 0; cb < HF; cb += LANES * VEC) {
-      const int64_t c  = cb + gl * VEC;
-      const bool act   = c < HF;
-      const int64_t cl = act ? c : 0;
-      const int64_t hk = cl / F;
-      const fvec<VEC> hs = ldv<VEC>(p.h_src + s * p.h_src_stride + cl), av = ldv<VEC>(p.att + cl);
-      fvec<VEC> acc = splat<VEC>(-0.0f);
-      fold_gatv2_edges<VEC, LANES>(acc, p, b, hs, av, cs, ce, p.concat ? cl : cl - hk * F, cl, hk, gl);
-      if (act) stv(b.partial + t * b.partial_stride + c, acc);
-    }
-  }
+  const int gl    = threadIdx.x % LANES;
+  const int64_t F = p.dim;
+  for_chunk_pieces<VEC, LANES>(b.ix, p.heads * F, [&](int64_t t, int64_t cs, int64_t ce, int64_t c, int64_t cl, bool act) {
+    const int64_t s    = p.col_ind[b.ix.order[cs]];   // the source this chunk belongs to
+    const int64_t hk   = cl / F;
+    const fvec<VEC> hs = ldv<VEC>(p.h_src + s * p.h_src_stride + cl), av = ldv<VEC>(p.att + cl);
+    fvec<VEC> acc = splat<VEC>(-0.0f);
+    fold_gatv2_edges<VEC, LANES>(acc, p, b, hs, av, cs, ce, p.concat ? cl : cl - hk * F, cl, hk, gl);
+    if (act) stv(b.ix.partial + t * b.ix.partial_stride + c, acc);
+  });
 }
 
 template <int VEC, int LANES>
 __global__ __launch_bounds__(kAggBlock) void gatv2_bwd_fold_kernel(wm_gatv2_args p, gatv2_bwd_state b)
 {
   constexpr int kGroups = kAggBlock / LANES;
-  constexpr int64_t C   = kAggChunkEdges;
   const int gl          = threadIdx.x % LANES;
   const int64_t F = p.dim, HF = p.heads * F;
-  const int64_t nu = *b.n_unique;
+  const int64_t nu = *b.ix.n_unique;
   for (int64_t s = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; s < p.n_src;
        s += static_cast<int64_t>(gridDim.x) * kGroups) {
-    const int64_t u = b.run_of[s];   // (uninitialised unless s has edges: checked against unique_ids)
-    const bool has  = u >= 0 && u < nu && b.unique_ids[u] == s;
-    int64_t s0 = 0, s1 = 0;
-    if (has) s0 = b.run_starts[u], s1 = b.run_starts[u + 1];
-    const int64_t c0e     = s1 - s0 > C ? s0 + C : s1;
-    const int64_t nchunks = (s1 - s0 + C - 1) / C;
+    const src_run r = run_of_source(b.ix, nu, s);
     for (int64_t cb = 0; cb < HF; cb += LANES * VEC) {
       const int64_t c  = cb + gl * VEC;
       const bool act   = c < HF;
@@ -415,25 +393,14 @@ __global__ __launch_bounds__(kAggBlock) void gatv2_bwd_fold_kernel(wm_gatv2_args
       const int64_t hk = cl / F;
       const fvec<VEC> hs = ldv<VEC>(p.h_src + s * p.h_src_stride + cl), av = ldv<VEC>(p.att + cl);
       fvec<VEC> acc = splat<VEC>(-0.0f);
-      fold_gatv2_edges<VEC, LANES>(acc, p, b, hs, av, s0, c0e, p.concat ? cl : cl - hk * F, cl, hk, gl);
-      for (int64_t k0 = 1; k0 < nchunks; k0 += kAggBatch) {   // partials in chunk order, a batch of them in flight
-        fvec<VEC> v[kAggBatch];
-#pragma unroll
-        for (int k = 0; k < kAggBatch; ++k) {
-          const int64_t kk = k0 + k < nchunks ? k0 + k : nchunks - 1;
-          v[k]             = ldv<VEC>(b.partial + ((s0 + kk * C) / C) * b.partial_stride + cl);
-        }
-#pragma unroll
-        for (int k = 0; k < kAggBatch; ++k)
-          if (k0 + k < nchunks) add_to(acc, v[k]);
-      }
-      if (!has) acc = splat<VEC>(0.0f);
+      fold_gatv2_edges<VEC, LANES>(acc, p, b, hs, av, r.s0, r.c0e, p.concat ? cl : cl - hk * F, cl, hk, gl);
+      add_partials(acc, b.ix, r, cl);
+      if (!r.has) acc = splat<VEC>(0.0f);
       if (act) stv(p.grad_h_src + s * p.grad_h_src_stride + c, acc);
     }
   }
 }
 
-int64_t up4(int64_t v) { return (v + 3) / 4 * 4; }
 bool row16(const void* ptr, int64_t stride) { return aligned16(ptr) && stride % 4 == 0; }
 
 // the lane-split tree: F a power of two in [4, 256] (a head is then an aligned power-of-two range of at most 64 lanes)
@@ -460,7 +427,7 @@ bool bwd_src_vec4(const wm_gatv2_args* a)
 
 struct gatv2_bwd_layout {
   int64_t n_tiles, partial_stride, n_node_chunks;
-  size_t off[7], bytes;   // sorted_dst, run_of, da, dl, arow, att_partial, partial
+  ws_layout<7> ws;   // sorted_dst, run_of, da, dl, arow, att_partial, partial
 };
 
 gatv2_bwd_layout bwd_layout(const wm_gatv2_args* a)
@@ -478,22 +445,23 @@ gatv2_bwd_layout bwd_layout(const wm_gatv2_args* a)
                             att ? a->n_dst * HF * 4 : 0,
                             att ? l.n_node_chunks * HF * 4 : 0,
                             src ? l.n_tiles * l.partial_stride * 4 : 0};
-  size_t w = 0;
-  for (int i = 0; i < 7; ++i) {
-    l.off[i] = w;
-    w        = up256(w + static_cast<size_t>(sizes[i]));
-  }
-  l.bytes = w + 256;   // (+ the alignment of the workspace's start)
+  l.ws = ws_plan(sizes);
   return l;
+}
+
+// forward: the per-head rows before the mean over heads (without concat), the logits (element-wise instantiations)
+ws_layout<2> fwd_layout(const wm_gatv2_args* a)
+{
+  const int64_t sizes[2] = {a->concat ? 0 : a->n_dst * a->heads * a->dim * 4, fwd_vec4(a) ? 0 : a->n_edges * a->heads * 4};
+  return ws_plan(sizes);
 }
 
 }  // namespace
 
 size_t hip_gatv2_forward_workspace_bytes(const wm_gatv2_args* a)
 {
-  const size_t rows   = a->concat ? 0 : up256(static_cast<size_t>(a->n_dst * a->heads * a->dim) * 4);
-  const size_t logits = fwd_vec4(a) ? 0 : static_cast<size_t>(a->n_edges * a->heads) * 4;
-  return rows + logits > 0 ? rows + logits + 256 : 0;
+  const bool rows = !a->concat && a->n_dst * a->heads * a->dim > 0, logits = !fwd_vec4(a) && a->n_edges * a->heads > 0;
+  return rows || logits ? fwd_layout(a).bytes : 0;
 }
 
 int hip_gatv2_forward(const wm_gatv2_args* a, void* workspace, void* stream_v)
@@ -501,12 +469,11 @@ int hip_gatv2_forward(const wm_gatv2_args* a, void* workspace, void* stream_v)
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   const int64_t H = a->heads, F = a->dim, HF = H * F;
   if (a->n_dst == 0) return 0;
-  const uintptr_t w0 = up256(reinterpret_cast<uintptr_t>(workspace));
-  const size_t rows  = a->concat ? 0 : up256(static_cast<size_t>(a->n_dst * HF) * 4);
-  float* o           = a->concat ? a->out : reinterpret_cast<float*>(w0);
-  const int64_t os   = a->concat ? a->out_stride : HF;
-  const bool v4      = fwd_vec4(a);
-  float* lbuf        = v4 ? a->alpha : reinterpret_cast<float*>(w0 + rows);
+  const ws_layout<2> l = fwd_layout(a);
+  float* o             = a->concat ? a->out : ws_at<float>(workspace, l.off[0]);
+  const int64_t os     = a->concat ? a->out_stride : HF;
+  const bool v4        = fwd_vec4(a);
+  float* lbuf          = v4 ? a->alpha : ws_at<float>(workspace, l.off[1]);
   if (!v4 && a->n_edges > 0) {
     hipLaunchKernelGGL(gatv2_dot_kernel<0>, dim3(blocks_for(a->n_dst * H, kAggBlock)), dim3(kAggBlock), 0, stream, *a, lbuf);
     if (rc_last() != 0) return -2;
@@ -529,30 +496,29 @@ int hip_gatv2_forward(const wm_gatv2_args* a, void* workspace, void* stream_v)
   return 0;
 }
 
-size_t hip_gatv2_backward_workspace_bytes(const wm_gatv2_args* a) { return bwd_layout(a).bytes; }
+size_t hip_gatv2_backward_workspace_bytes(const wm_gatv2_args* a) { return bwd_layout(a).ws.bytes; }
 
 int hip_gatv2_backward(const wm_gatv2_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
                        const int64_t* n_unique_dev, void* workspace, void* stream_v)
 {
   hipStream_t stream       = static_cast<hipStream_t>(stream_v);
   const gatv2_bwd_layout l = bwd_layout(a);
-  const uintptr_t w0       = up256(reinterpret_cast<uintptr_t>(workspace));
   const int64_t H = a->heads, HF = H * a->dim;
   gatv2_bwd_state b;
-  b.order          = order;
-  b.run_starts     = run_starts;
-  b.unique_ids     = unique_ids;
-  b.n_unique       = n_unique_dev;
-  b.sorted_dst     = reinterpret_cast<int32_t*>(w0 + l.off[0]);
-  b.run_of         = reinterpret_cast<int32_t*>(w0 + l.off[1]);
-  b.da             = reinterpret_cast<float*>(w0 + l.off[2]);
-  b.dl             = reinterpret_cast<float*>(w0 + l.off[3]);
-  b.arow           = reinterpret_cast<float*>(w0 + l.off[4]);
-  b.att_partial    = reinterpret_cast<float*>(w0 + l.off[5]);
-  b.partial        = reinterpret_cast<float*>(w0 + l.off[6]);
-  b.n_tiles        = l.n_tiles;
-  b.partial_stride = l.partial_stride;
-  b.n_node_chunks  = l.n_node_chunks;
+  b.ix.order          = order;
+  b.ix.run_starts     = run_starts;
+  b.ix.unique_ids     = unique_ids;
+  b.ix.n_unique       = n_unique_dev;
+  b.ix.sorted_dst     = ws_at<int32_t>(workspace, l.ws.off[0]);
+  b.ix.run_of         = ws_at<int32_t>(workspace, l.ws.off[1]);
+  b.da                = ws_at<float>(workspace, l.ws.off[2]);
+  b.dl                = ws_at<float>(workspace, l.ws.off[3]);
+  b.arow              = ws_at<float>(workspace, l.ws.off[4]);
+  b.att_partial       = ws_at<float>(workspace, l.ws.off[5]);
+  b.ix.partial        = ws_at<float>(workspace, l.ws.off[6]);
+  b.ix.n_tiles        = l.n_tiles;
+  b.ix.partial_stride = l.partial_stride;
+  b.n_node_chunks     = l.n_node_chunks;
   if (a->n_dst > 0) {
     const bool v4 = bwd_dst_vec4(a);
     if (!v4 && a->n_edges > 0) {
@@ -582,9 +548,9 @@ int hip_gatv2_backward(const wm_gatv2_args* a, const int32_t* order, const int32
       if (rc_last() != 0) return -2;
     }
     const bool v4 = bwd_src_vec4(a);
-    if (b.n_tiles > 1) {   // (one tile holds no chunk k >= 1)
+    if (b.ix.n_tiles > 1) {   // (one tile holds no chunk k >= 1)
 #define WM_GATV2_CHUNK(V, L)                                                                                   \
-  hipLaunchKernelGGL((gatv2_bwd_chunk_kernel<V, L>), dim3(blocks_for(b.n_tiles, kAggBlock / (L))), dim3(kAggBlock), 0, \
+  hipLaunchKernelGGL((gatv2_bwd_chunk_kernel<V, L>), dim3(blocks_for(b.ix.n_tiles, kAggBlock / (L))), dim3(kAggBlock), 0, \
                      stream, *a, b)
       WM_AGG_DISPATCH(v4, v4 ? HF / 4 : HF, WM_GATV2_CHUNK);
 #undef WM_GATV2_CHUNK

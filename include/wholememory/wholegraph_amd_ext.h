@@ -23,6 +23,8 @@
  *      it writes.
  *      (2j) the neighbour aggregation of (2b) whose rows are read, and dequantized, from a quantized table of (2i) by
  *      global id (forward).
+ *      (2k) the scaled dot-product multi-head attention of a sampled CSC block behind the TransformerConv layer (forward
+ *      and a deterministic backward).
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -926,6 +928,92 @@ enum wholememory_error_code_t wholememory_ext_csc_gather_dequantize_aggregate_fo
 /* wholememory_ext_csc_gather_dequantize_aggregate_forward calls that launched on the device backend (this process). A
  * counter for tests: it tells the fused route from the (2i) gather + (2b) composition. */
 int64_t wholememory_ext_gather_dequantize_aggregate_calls(void);
+
+/* ---- (2k) scaled dot-product multi-head attention of a sampled CSC block (`mha_simple_n2n`) -------------------------- */
+/* The block as for (2b): row_ptr int32 [n_dst + 1], col_ind int32 [n_edges] in [0, n_src). key fp32 [n_src, key_stride],
+ * value fp32 [n_src, value_stride] and query fp32 [n_dst, query_stride], row d of query belonging to target d (the layer's
+ * lin_key(x), lin_value(x) and lin_query(x[:n_dst])); each row uses H * F columns (H = heads, F = dim) and head h owns the
+ * columns [h*F, (h+1)*F). Strides in elements, all arrays DEVICE memory, all work queued on `stream`.
+ * The contract of (2c) / (2g): every `*` and `+` below is one fp32 operation, rounded on its own (no fused multiply-add), no
+ * atomics, one fixed order for every sum, results bitwise reproducible. A sum "left to right" starts from its first term; a
+ * sum with no term is +0.0. "Tree sum over f" is the balanced binary tree of adjacent pairs of (2d) / (2g), padded to the
+ * next power of two Fp >= F with +0.0; it does not depend on how the kernel is launched.
+ * The scale is s = fl(1.0f / fl(sqrtf((float)F))), computed once on the host, both operations correctly rounded. It applies
+ * only when norm_by_dim != 0; with norm_by_dim == 0 no multiplication takes place.
+ *
+ * forward: writes alpha [n_edges, H] and out. For edge e of target d (e = row_ptr[d] .. row_ptr[d+1] - 1), head h,
+ * j = col_ind[e]:
+ *   t[e,h] = tree sum over f of query[d,h,f] * key[j,h,f]. l[e,h] = t[e,h] * s (norm_by_dim), else l[e,h] = t[e,h].
+ *   m = max of l over the edges of d; w = expf(l - m) (the device's expf); den = sum of w over the edges of d, left to
+ *   right; alpha[e,h] = w / den: exactly as (2c).
+ *   o[d,h,:] = sum of alpha[e,h] * value[j,h,:] over the edges of d, left to right; +0.0 for a target without edges.
+ *   concat != 0: out [n_dst, out_stride >= H*F] = o. concat == 0: out [n_dst, out_stride >= F] =
+ *   ((o[d,0,:] + o[d,1,:]) + ...) * fl(1.0f / H), as (2g).
+ * backward: grad_out G [n_dst, grad_out_stride] (H*F columns with concat, else F) -> grad_query [n_dst, grad_query_stride],
+ * grad_key [n_src, grad_key_stride] and grad_value [n_src, grad_value_stride], each with a stride >= H*F and every row of a
+ * requested gradient written. Each of the three may be null and is then not computed (nothing is queued for it); all three
+ * null is INVALID_INPUT.
+ *   G_h[d,f] = G[d, h*F + f] with concat, else G[d,f] * fl(1.0f / H), as (2g).
+ *   da[e,h] = tree sum over f of G_h[d,f] * value[j,h,f]. c[d,h] = sum of alpha[e,h] * da[e,h] over the edges of d, left to
+ *   right. dl[e,h] = alpha[e,h] * (da[e,h] - c[d,h]). ds[e,h] = dl[e,h] * s (norm_by_dim), else ds[e,h] = dl[e,h].
+ *   grad_query[d,h,f] = sum of ds[e,h] * key[j,h,f] over the edges of d, left to right; +0.0 without edges.
+ *   grad_key[j,h,:] = sum over the edges with col_ind[e] = j, in ascending edge position, of ds[e,h] * query[d(e),h,:].
+ *   grad_value[j,h,:] = the same edges in the same order, of alpha[e,h] * G_h[d(e),:].
+ *   Both per-source sums: left to right when j has at most C edges, otherwise cut into consecutive chunks of C edges, each
+ *   chunk summed left to right and the chunk sums added in chunk order, exactly as (2b), with
+ *   C = wholememory_ext_csc_aggregate_chunk_edges(). A source without edges gets +0.0.
+ *   The edge index of grad_key and grad_value is built with the library's id sort, scratch from p_env_fns, and only when
+ *   one of the two is asked for.
+ * n_edges = 0 and n_dst = 0 are valid. INVALID_INPUT, before any device work and under every backend, for whatever (2g)
+ * rejects: null pointers (a null query with n_dst > 0 among them), negative sizes, heads < 1, dim < 1, n_dst > n_src and any
+ * stride smaller than its row (for out and grad_out the row is F without concat). NOT_SUPPORTED (nothing queued) when the
+ * device backend has no such kernels. */
+enum wholememory_error_code_t wholememory_ext_csc_mha_simple_forward(const int32_t* row_ptr,
+                                                                     const int32_t* col_ind,
+                                                                     int64_t n_edges,
+                                                                     int64_t n_dst,
+                                                                     int64_t n_src,
+                                                                     const float* key,
+                                                                     int64_t key_stride,
+                                                                     const float* query,
+                                                                     int64_t query_stride,
+                                                                     const float* value,
+                                                                     int64_t value_stride,
+                                                                     int64_t heads,
+                                                                     int64_t dim,
+                                                                     int norm_by_dim,
+                                                                     int concat,
+                                                                     float* out,
+                                                                     int64_t out_stride,
+                                                                     float* alpha,
+                                                                     struct wholememory_env_func_t* p_env_fns,
+                                                                     void* stream);
+enum wholememory_error_code_t wholememory_ext_csc_mha_simple_backward(const int32_t* row_ptr,
+                                                                      const int32_t* col_ind,
+                                                                      int64_t n_edges,
+                                                                      int64_t n_dst,
+                                                                      int64_t n_src,
+                                                                      const float* key,
+                                                                      int64_t key_stride,
+                                                                      const float* query,
+                                                                      int64_t query_stride,
+                                                                      const float* value,
+                                                                      int64_t value_stride,
+                                                                      int64_t heads,
+                                                                      int64_t dim,
+                                                                      int norm_by_dim,
+                                                                      int concat,
+                                                                      const float* alpha,
+                                                                      const float* grad_out,
+                                                                      int64_t grad_out_stride,
+                                                                      float* grad_key,
+                                                                      int64_t grad_key_stride,
+                                                                      float* grad_query,
+                                                                      int64_t grad_query_stride,
+                                                                      float* grad_value,
+                                                                      int64_t grad_value_stride,
+                                                                      struct wholememory_env_func_t* p_env_fns,
+                                                                      void* stream);
 
 /* ---- (3) testing seam ---------------------------------------------------------------------- */
 /* Replaces the device backend. Refuses (WHOLEMEMORY_NOT_SUPPORTED) unless the environment has

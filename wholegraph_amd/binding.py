@@ -310,6 +310,11 @@ PROTOTYPES = {
     "wholememory_ext_csc_gatv2_backward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64,
                                                C.c_float, _i, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _P(EnvFunc),
                                                _vp]),
+    "wholememory_ext_csc_mha_simple_forward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64,
+                                                   _i, _i, _vp, _i64, _vp, _P(EnvFunc), _vp]),
+    "wholememory_ext_csc_mha_simple_backward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64,
+                                                    _i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _P(EnvFunc),
+                                                    _vp]),
     "wholememory_ext_csc_rel_aggregate_forward": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i, _vp, _i64,
                                                       _vp, _P(EnvFunc), _vp]),
     "wholememory_ext_csc_rel_aggregate_backward": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i, _vp,

@@ -376,6 +376,34 @@ struct wm_qagg_args {
   int64_t out_stride;
 };
 
+// scaled dot-product attention of a sampled CSC block (kernels/tconv.hip, the `mha_simple_n2n` op, wholegraph_amd_ext.h
+// section 2k): rows / strides in ELEMENTS (fp32); head k owns columns [k * dim, (k + 1) * dim) of a row
+struct wm_tconv_args {
+  const int32_t* row_ptr;   // [n_dst + 1]
+  const int32_t* col_ind;   // [n_edges], ids in [0, n_src)
+  int64_t n_edges, n_dst, n_src, heads, dim;
+  int norm_by_dim;          // 1: the logits are multiplied by `scale`; 0: no multiplication
+  float scale;              // fl(1 / fl(sqrtf(dim))), computed on the host
+  int concat;               // 1: out [n_dst, heads * dim]; 0: the mean over heads, [n_dst, dim]
+  const float* key;         // [n_src, key_stride], heads * dim columns used
+  int64_t key_stride;
+  const float* query;       // [n_dst, query_stride]: row d belongs to target d
+  int64_t query_stride;
+  const float* value;       // [n_src, value_stride]
+  int64_t value_stride;
+  float* alpha;             // [n_edges, heads]: written by the forward, read by the backward
+  float* out;               // forward: [n_dst, out_stride]
+  int64_t out_stride;
+  const float* grad;        // backward: dL/dout [n_dst, grad_stride]
+  int64_t grad_stride;
+  float* grad_key;          // backward: [n_src, grad_key_stride] or nullptr
+  int64_t grad_key_stride;
+  float* grad_query;        // backward: [n_dst, grad_query_stride] or nullptr
+  int64_t grad_query_stride;
+  float* grad_value;        // backward: [n_src, grad_value_stride] or nullptr
+  int64_t grad_value_stride;
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -628,6 +656,16 @@ struct wm_device_backend {
   // ---- agg_forward over rows read from an 8-bit row-quantized table by global id (kernels/agg_quant.hip, wholegraph_amd_ext.h
   // section 2j); nullptr in a backend without it ----
   int (*qagg_forward)(const wm_qagg_args* a, void* stream);
+  // ---- scaled dot-product attention of a sampled CSC block (kernels/tconv.hip, wholegraph_amd_ext.h section 2k); nullptr in
+  // a backend without it ----
+  // forward: alpha and out; workspace of tconv_forward_workspace_bytes
+  size_t (*tconv_forward_workspace_bytes)(const wm_tconv_args* a);
+  int (*tconv_forward)(const wm_tconv_args* a, void* workspace, void* stream);
+  // backward: whichever of grad_key, grad_query and grad_value is not null. The index of gat_backward (read for grad_key and
+  // grad_value only: nullptr otherwise); workspace of tconv_backward_workspace_bytes
+  size_t (*tconv_backward_workspace_bytes)(const wm_tconv_args* a);
+  int (*tconv_backward)(const wm_tconv_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                        const int64_t* n_unique_dev, void* workspace, void* stream);
 };
 
 }  // extern "C"

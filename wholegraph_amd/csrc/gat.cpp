@@ -1,8 +1,11 @@
 // wholegraph_amd — host side of the multi-head graph attention of a sampled CSC block (wholegraph_amd_ext.h, section 2c,
-// section 2f: the same op with an edge term in the logit, and section 2g: GATv2): validation, scratch, the edge index of the
-// backward (the library's id sort over col_ind) and the launches of kernels/gat.hip / kernels/gat_edge.hip /
-// kernels/gatv2.hip. The semantics, and the one order of every fp32 sum, are stated in the header.
+// section 2f: the same op with an edge term in the logit, section 2g: GATv2, and section 2k: scaled dot-product attention):
+// validation, scratch, the edge index of the backward (the library's id sort over col_ind) and the launches of
+// kernels/gat.hip / kernels/gat_edge.hip / kernels/gatv2.hip / kernels/tconv.hip. The semantics, and the one order of every
+// fp32 sum, are stated in the header.
 #include <wholememory/wholegraph_amd_ext.h>
+
+#include <cmath>
 
 #include "csc_block.hpp"
 
@@ -79,6 +82,46 @@ wm_gatv2_args make_v2_args(const int32_t* row_ptr, const int32_t* col_ind, int64
   a.h_dst        = h_dst;
   a.h_dst_stride = h_dst_stride;
   a.att          = att;
+  a.alpha        = const_cast<float*>(alpha);   // (written by the forward only)
+  return a;
+}
+
+// what (2k) shares between its forward and backward: the checks of (2g) with key / query / value in place of h_src / h_dst
+// / att, and the scale, both of whose operations the host rounds correctly
+wm_tconv_args make_tconv_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src,
+                              const float* key, int64_t key_stride, const float* query, int64_t query_stride,
+                              const float* value, int64_t value_stride, int64_t heads, int64_t dim, int norm_by_dim,
+                              int concat, const float* alpha)
+{
+  auto bad = [](const char* what) { throw invalid_input(what); };
+  check_block(row_ptr, col_ind, n_edges, n_dst, n_src, n_edges > 0 && n_dst > 0, "key");
+  if (heads < 1) bad("heads must be >= 1");
+  if (dim < 1) bad("dim must be >= 1");
+  if (n_src > 0 && key == nullptr) bad("key is null");
+  if (n_src > 0 && value == nullptr) bad("value is null");
+  if (n_dst > 0 && query == nullptr) bad("query is null");
+  if (n_edges > 0 && n_dst > 0 && alpha == nullptr) bad("alpha is null");
+  if (key_stride < heads * dim) bad("key stride smaller than its row");
+  if (query_stride < heads * dim) bad("query stride smaller than its row");
+  if (value_stride < heads * dim) bad("value stride smaller than its row");
+  if (heads * dim >= (int64_t(1) << 30)) bad("heads * dim too large");
+  wm_tconv_args a{};
+  a.row_ptr      = row_ptr;
+  a.col_ind      = col_ind;
+  a.n_edges      = n_dst == 0 ? 0 : n_edges;   // (no target, no edge of any target)
+  a.n_dst        = n_dst;
+  a.n_src        = n_src;
+  a.heads        = heads;
+  a.dim          = dim;
+  a.norm_by_dim  = norm_by_dim ? 1 : 0;
+  a.scale        = 1.0f / sqrtf(static_cast<float>(dim));
+  a.concat       = concat ? 1 : 0;
+  a.key          = key;
+  a.key_stride   = key_stride;
+  a.query        = query;
+  a.query_stride = query_stride;
+  a.value        = value;
+  a.value_stride = value_stride;
   a.alpha        = const_cast<float*>(alpha);   // (written by the forward only)
   return a;
 }
@@ -279,6 +322,68 @@ wholememory_error_code_t wholememory_ext_csc_gatv2_backward(
   if (grad_h_src != nullptr && n_src > 0) sort_col_ind(&ix, col_ind, a.n_edges, n_src, stream);
   void* d_gws = gat_ws.device(static_cast<int64_t>(bk->gatv2_backward_workspace_bytes(&a)), WHOLEMEMORY_DT_INT8);
   WM_BK(bk->gatv2_backward(&a, ix.order, ix.starts, static_cast<const int32_t*>(ix.unique), ix.n_unique_dev, d_gws, stream));
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+wholememory_error_code_t wholememory_ext_csc_mha_simple_forward(
+  const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src, const float* key,
+  int64_t key_stride, const float* query, int64_t query_stride, const float* value, int64_t value_stride, int64_t heads,
+  int64_t dim, int norm_by_dim, int concat, float* out, int64_t out_stride, float* alpha, wholememory_env_func_t* p_env_fns,
+  void* stream)
+{
+  WM_API_BEGIN
+  const auto* bk  = backend();
+  wm_tconv_args a = make_tconv_args(row_ptr, col_ind, n_edges, n_dst, n_src, key, key_stride, query, query_stride, value,
+                                    value_stride, heads, dim, norm_by_dim, concat, alpha);
+  if (n_dst > 0 && out == nullptr) throw invalid_input("out is null");
+  if (out_stride < (concat ? heads * dim : dim)) throw invalid_input("out stride smaller than its row");
+  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
+  // (after the checks: a malformed call is INVALID_INPUT under every backend)
+  if (bk->tconv_forward == nullptr || bk->tconv_forward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  a.out        = out;
+  a.out_stride = out_stride;
+  temp_mem ws(p_env_fns);
+  const size_t wb = bk->tconv_forward_workspace_bytes(&a);
+  void* d_ws      = wb > 0 ? ws.device(static_cast<int64_t>(wb), WHOLEMEMORY_DT_INT8) : nullptr;
+  WM_BK(bk->tconv_forward(&a, d_ws, stream));
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+wholememory_error_code_t wholememory_ext_csc_mha_simple_backward(
+  const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src, const float* key,
+  int64_t key_stride, const float* query, int64_t query_stride, const float* value, int64_t value_stride, int64_t heads,
+  int64_t dim, int norm_by_dim, int concat, const float* alpha, const float* grad_out, int64_t grad_out_stride,
+  float* grad_key, int64_t grad_key_stride, float* grad_query, int64_t grad_query_stride, float* grad_value,
+  int64_t grad_value_stride, wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  const auto* bk  = backend();
+  wm_tconv_args a = make_tconv_args(row_ptr, col_ind, n_edges, n_dst, n_src, key, key_stride, query, query_stride, value,
+                                    value_stride, heads, dim, norm_by_dim, concat, alpha);
+  if (n_dst > 0 && grad_out == nullptr) throw invalid_input("grad_out is null");
+  if (grad_out_stride < (concat ? heads * dim : dim)) throw invalid_input("grad_out stride smaller than its row");
+  if (grad_key == nullptr && grad_query == nullptr && grad_value == nullptr) throw invalid_input("no gradient asked for");
+  if (grad_key != nullptr && grad_key_stride < heads * dim) throw invalid_input("grad_key stride smaller than its row");
+  if (grad_query != nullptr && grad_query_stride < heads * dim) throw invalid_input("grad_query stride smaller than its row");
+  if (grad_value != nullptr && grad_value_stride < heads * dim) throw invalid_input("grad_value stride smaller than its row");
+  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
+  if (bk->tconv_backward == nullptr || bk->tconv_backward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  a.grad              = grad_out;
+  a.grad_stride       = grad_out_stride;
+  a.grad_key          = grad_key;
+  a.grad_key_stride   = grad_key_stride;
+  a.grad_query        = grad_query;
+  a.grad_query_stride = grad_query_stride;
+  a.grad_value        = grad_value;
+  a.grad_value_stride = grad_value_stride;
+  // the edge index of grad_key and grad_value; without both, or without source rows: null pointers
+  sorted_ids ix(p_env_fns);
+  temp_mem tconv_ws(p_env_fns);
+  if ((grad_key != nullptr || grad_value != nullptr) && n_src > 0) sort_col_ind(&ix, col_ind, a.n_edges, n_src, stream);
+  void* d_ws = tconv_ws.device(static_cast<int64_t>(bk->tconv_backward_workspace_bytes(&a)), WHOLEMEMORY_DT_INT8);
+  WM_BK(bk->tconv_backward(&a, ix.order, ix.starts, static_cast<const int32_t*>(ix.unique), ix.n_unique_dev, d_ws, stream));
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }

@@ -1,6 +1,6 @@
 // wholegraph_amd — device and launch helpers shared by the ops of a sampled CSC block (kernels/agg.hip, agg_half.hip,
-// agg_weighted.hip and agg_rel.hip, the `agg_concat` family; kernels/gat.hip, gat_edge.hip and gatv2.hip, the attention
-// ops): fp32 pieces of a row, the clamped edge range of a target, the launch shape, and the walk of the deterministic
+// agg_weighted.hip and agg_rel.hip, the `agg_concat` family; kernels/gat.hip, gat_edge.hip, gatv2.hip and tconv.hip, the
+// attention ops): fp32 pieces of a row, the clamped edge range of a target, the launch shape, and the walk of the deterministic
 // per-source backward over the id sort: its index (csc_bwd_index), the run of a source (run_of_source), the partial rows
 // of a run's later chunks (add_partials), the tile loop of a chunk kernel (for_chunk_pieces) and the self term of the
 // agg_concat ops (with_self_term). What an op adds per edge, its fold_edges*, stays in the op's own file.

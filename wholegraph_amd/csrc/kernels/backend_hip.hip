@@ -102,6 +102,11 @@ int hip_relagg_backward(const wm_relagg_args* a, const int32_t* order, const int
 int hip_qrows_gather_dequant(const wm_qrows_args* a, void* stream);
 int hip_qrows_quantize_scatter(const wm_qrows_args* a, void* stream);
 int hip_qagg_forward(const wm_qagg_args* a, void* stream);
+size_t hip_tconv_forward_workspace_bytes(const wm_tconv_args* a);
+int hip_tconv_forward(const wm_tconv_args* a, void* workspace, void* stream);
+size_t hip_tconv_backward_workspace_bytes(const wm_tconv_args* a);
+int hip_tconv_backward(const wm_tconv_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                       const int64_t* n_unique_dev, void* workspace, void* stream);
 
 namespace {
 
@@ -294,6 +299,10 @@ const wm_device_backend kHipBackend = {
   hip_qrows_gather_dequant,
   hip_qrows_quantize_scatter,
   hip_qagg_forward,
+  hip_tconv_forward_workspace_bytes,
+  hip_tconv_forward,
+  hip_tconv_backward_workspace_bytes,
+  hip_tconv_backward,
 };
 
 }  // namespace

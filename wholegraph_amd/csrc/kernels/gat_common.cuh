@@ -2,7 +2,8 @@
 // kernels/gat_edge.hip, the same op with an edge term in the logit): the scratch of the backward; the stages of gat.hip
 // that do not see the logit — the node scores and the mean over heads of the forward, and everything of the backward
 // behind dz (wholegraph_amd_ext.h, section 2c), whose kernels live in gat.hip alone; and the bodies of the two stages that
-// do see it (gat_fwd_body, gat_bwd_dz_body), with the edge term of section 2f compiled in or out.
+// do see it (gat_fwd_body, gat_bwd_dz_body), with the edge term of section 2f compiled in or out. And what the two ops with
+// a dot product per edge and head share (kernels/gatv2.hip, kernels/tconv.hip): the balanced tree of adjacent pairs.
 #pragma once
 #include <math.h>
 
@@ -156,7 +157,50 @@ __device__ __forceinline__ void gat_bwd_dz_body(const wm_gat_args& p, const floa
   }
 }
 
+// ---- the per-edge, per-head dot product of kernels/gatv2.hip and kernels/tconv.hip: the "tree sum over f" of
+// wholegraph_amd_ext.h, sections 2g and 2k, in its two implementations that give the same bits ----
+
+// the balanced tree of adjacent pairs over a stream of terms: push() them in order, 2^levels of them in all
+struct pair_tree {
+  static constexpr int kLevels = 31;
+  float st[kLevels];
+  float top;
+  __device__ __forceinline__ void push(float q, uint32_t f)
+  {
+    bool carry = true;
+#pragma unroll
+    for (int lvl = 0; lvl < kLevels; ++lvl) {
+      if (carry) {
+        if ((f >> lvl) & 1u) {
+          q = st[lvl] + q;
+        } else {
+          st[lvl] = q;
+          carry   = false;
+        }
+      }
+    }
+    top = q;   // (after the last term of 2^levels: the root)
+  }
+};
+
+__device__ __forceinline__ uint32_t pow2_at_least(int64_t f)
+{
+  uint32_t p = 1;
+  while (p < f) p <<= 1;
+  return p;
+}
+
+// the tree over the F = 4 * lh columns of a head from the 4 products of each of its lh lanes
+template <int LANES>
+__device__ __forceinline__ float head_tree(const fvec<4>& q, int lh)
+{
+  float s = (q.v[0] + q.v[1]) + (q.v[2] + q.v[3]);
+  for (int w = 1; w < lh; w <<= 1) s = s + __shfl_xor(s, w, LANES);
+  return s;
+}
+
 bool aligned16(const void* ptr) { return reinterpret_cast<uintptr_t>(ptr) % 16 == 0; }
+bool row16(const void* ptr, int64_t stride) { return aligned16(ptr) && stride % 4 == 0; }
 // 16-byte pieces in the backward: whole heads of F % 4 == 0 columns, every row start and att 16-byte aligned
 bool gat_bwd_vec4(const wm_gat_args* a)
 {

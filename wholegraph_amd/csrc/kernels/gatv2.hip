@@ -3,7 +3,7 @@
 // owns columns [k*F, (k+1)*F) of a row. u = h_src[col[e]] + h_dst[d], v = LeakyReLU(u), l[e,k] = att[k] . v as a balanced
 // tree of adjacent pairs over Fp (the smallest power of two >= F, padded with +0.0).
 //
-// The tree has two implementations that give the same bits:
+// The tree has two implementations that give the same bits (pair_tree and head_tree of gat_common.cuh):
 //   * 16-byte instantiations (VEC = 4: F a power of two in [4, 256], every row and att 16-byte aligned): a lane owns 4
 //     adjacent columns, (q0 + q1) + (q2 + q3), and the F / 4 lanes of a head (an aligned power-of-two lane range of the
 //     group) combine with xor exchanges at distance 1, 2, 4, ...: every lane of the head ends with the tree's root.
@@ -48,36 +48,6 @@ struct gatv2_bwd_state {
   int64_t n_node_chunks;
 };
 
-// the balanced tree of adjacent pairs over a stream of terms: push() them in order, 2^levels of them in all
-struct pair_tree {
-  static constexpr int kLevels = 31;
-  float st[kLevels];
-  float top;
-  __device__ __forceinline__ void push(float q, uint32_t f)
-  {
-    bool carry = true;
-#pragma unroll
-    for (int lvl = 0; lvl < kLevels; ++lvl) {
-      if (carry) {
-        if ((f >> lvl) & 1u) {
-          q = st[lvl] + q;
-        } else {
-          st[lvl] = q;
-          carry   = false;
-        }
-      }
-    }
-    top = q;   // (after the last term of 2^levels: the root)
-  }
-};
-
-__device__ __forceinline__ uint32_t pow2_at_least(int64_t f)
-{
-  uint32_t p = 1;
-  while (p < f) p <<= 1;
-  return p;
-}
-
 // one thread per (target d, head k). MODE 0: dst[e, k] = l[e, k]; MODE 1: dst[e, k] = da[e, k] = tree of G_k[d] * h_src
 template <int MODE>
 __global__ __launch_bounds__(kAggBlock) void gatv2_dot_kernel(wm_gatv2_args p, float* dst)
@@ -107,15 +77,6 @@ __global__ __launch_bounds__(kAggBlock) void gatv2_dot_kernel(wm_gatv2_args p, f
       dst[e * H + k] = t.top;
     }
   }
-}
-
-// the tree over the F = 4 * lh columns of a head from the 4 products of each of its lh lanes
-template <int LANES>
-__device__ __forceinline__ float head_tree(const fvec<4>& q, int lh)
-{
-  float s = (q.v[0] + q.v[1]) + (q.v[2] + q.v[3]);
-  for (int w = 1; w < lh; w <<= 1) s = s + __shfl_xor(s, w, LANES);
-  return s;
 }
 
 template <int VEC, int LANES>
@@ -400,8 +361,6 @@ __global__ __launch_bounds__(kAggBlock) void gatv2_bwd_fold_kernel(wm_gatv2_args
     }
   }
 }
-
-bool row16(const void* ptr, int64_t stride) { return aligned16(ptr) && stride % 4 == 0; }
 
 // the lane-split tree: F a power of two in [4, 256] (a head is then an aligned power-of-two range of at most 64 lanes)
 bool tree_vec4(const wm_gatv2_args* a)

@@ -4,6 +4,8 @@ from .gat_conv import CuGraphGATConv
 from .gatv2_conv import GATv2Conv
 from .rgcn_conv import RGCNConv
 from .sage_conv import CuGraphSAGEConv
+from .transformer_conv import TransformerConv
 from .weighted_sage_conv import EdgeWeightedSAGEConv
 
-__all__ = ["CuGraphSAGEConv", "CuGraphGATConv", "EdgeGATConv", "GATv2Conv", "RGCNConv", "EdgeWeightedSAGEConv"]
+__all__ = ["CuGraphSAGEConv", "CuGraphGATConv", "EdgeGATConv", "GATv2Conv", "RGCNConv", "TransformerConv",
+           "EdgeWeightedSAGEConv"]

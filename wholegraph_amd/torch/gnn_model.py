@@ -1,7 +1,8 @@
 """The GNN model surface of ``pylibwholegraph.torch.gnn_model`` (``set_framework``, ``create_gnn_layers``,
 ``create_sub_graph``, ``layer_forward``, ``HomoGNNModel``) for the ``cugraph`` framework route with GraphSAGE layers, on the
 HIP aggregation op (``aggregation.py``), with GATv2 layers (model "gatv2": ``cugraphops.GATv2Conv`` on
-``gatv2_aggregation.py``) and, for graphs with typed edges, with RGCN layers (model "rgcn": ``cugraphops.RGCNConv`` on
+``gatv2_aggregation.py``), with transformer layers (model "transformer": ``cugraphops.TransformerConv`` on
+``transformer_aggregation.py``) and, for graphs with typed edges, with RGCN layers (model "rgcn": ``cugraphops.RGCNConv`` on
 ``rel_aggregation.py``, built by ``create_rgcn_layers``; the sampler delivers each block's edge types). The dgl / pyg / wg
 routes and the model "gat" are not part of this build (the GAT layer itself is ``cugraphops.CuGraphGATConv``).
 
@@ -55,8 +56,9 @@ def create_gnn_layers(in_feat_dim, hidden_feat_dim, class_count, num_layer, num_
     if model_type == "rgcn":
         raise ValueError("model 'rgcn' needs the number of relations: build its layers with create_rgcn_layers(in_feat_dim, "
                          "hidden_feat_dim, class_count, num_layer, num_relations, num_bases=None)")
-    if model_type not in ("sage", "gatv2"):
-        raise ValueError("model %r is not available on the cugraph route (only 'sage' and 'gatv2')" % (model_type,))
+    if model_type not in ("sage", "gatv2", "transformer"):
+        raise ValueError("model %r is not available on the cugraph route (only 'sage', 'gatv2' and 'transformer')"
+                         % (model_type,))
     gnn_layers = torch.nn.ModuleList()
     for i in range(num_layer):
         layer_output_dim = hidden_feat_dim // num_head if i != num_layer - 1 else class_count
@@ -64,6 +66,10 @@ def create_gnn_layers(in_feat_dim, hidden_feat_dim, class_count, num_layer, num_
         if model_type == "gatv2":   # (the reference's flow for "gat": heads concatenated, averaged in the last layer)
             from .cugraphops.gatv2_conv import GATv2Conv
             gnn_layers.append(GATv2Conv(layer_input_dim, layer_output_dim, heads=num_head, concat=i != num_layer - 1))
+        elif model_type == "transformer":   # (the same flow; the layer's root term is the target's own path)
+            from .cugraphops.transformer_conv import TransformerConv
+            gnn_layers.append(TransformerConv(layer_input_dim, layer_output_dim, heads=num_head,
+                                              concat=i != num_layer - 1))
         else:
             gnn_layers.append(SAGEConv(layer_input_dim, layer_output_dim))
     return gnn_layers
@@ -113,9 +119,9 @@ class HomoGNNModel(torch.nn.Module):
         self.num_layer = args.layernum
         self.hidden_feat_dim = args.hiddensize
         attention = args.model in ("gat", "gatv2")
-        if args.model == "gatv2" and getattr(args, "fuse_gather", False):
-            raise ValueError("fuse_gather reads layer 0's rows from the table: GraphSAGE only, not model 'gatv2'")
-        num_head = args.heads if attention else 1
+        if args.model in ("gatv2", "transformer") and getattr(args, "fuse_gather", False):
+            raise ValueError("fuse_gather reads layer 0's rows from the table: GraphSAGE only, not model %r" % args.model)
+        num_head = args.heads if attention or args.model == "transformer" else 1
         assert hidden_feat_dim % num_head == 0
         in_feat_dim = self.node_embedding.shape[1]
         self.edge_type_name = None

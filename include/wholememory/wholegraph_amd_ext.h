@@ -25,6 +25,8 @@
  *      global id (forward).
  *      (2k) the scaled dot-product multi-head attention of a sampled CSC block behind the TransformerConv layer (forward
  *      and a deterministic backward).
+ *      (2l) the multi-aggregator neighbour aggregation of a sampled CSC block behind the PNAConv layer: sum, mean, min, max
+ *      and std of the neighbour rows out of one read of them (forward and a deterministic backward).
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -1014,6 +1016,94 @@ enum wholememory_error_code_t wholememory_ext_csc_mha_simple_backward(const int3
                                                                       int64_t grad_value_stride,
                                                                       struct wholememory_env_func_t* p_env_fns,
                                                                       void* stream);
+
+/* ---- (2l) multi-aggregator neighbour aggregation of a sampled CSC block (`agg_concat_pna`) --------------------------- */
+/* The block as for (2b): row_ptr int32 [n_dst + 1], col_ind int32 [n_edges] in [0, n_src), x fp32 [n_src, x_stride] whose
+ * first n_dst rows are the targets themselves. Strides in elements, all arrays DEVICE memory, all work queued on `stream`.
+ * `aggregators` is a non-empty mask of the bits of wholememory_ext_pna_aggr_t, A of them set. A row of out, and of grad_out,
+ * has one slot of dim columns per selected aggregator, in the order SUM, MEAN, MIN, MAX, STD, and then the slot of the
+ * target's own row: (A + 1) * dim columns.
+ * Every `*`, `+`, `-` and `/` below is one fp32 operation, rounded on its own (no fused multiply-add); the square root is
+ * correctly rounded; no atomics, one fixed order for every sum, results bitwise reproducible.
+ *
+ * forward, for target d with the edges e0 = row_ptr[d] .. e1 - 1 = row_ptr[d+1] - 1, t_i = x[col_ind[e0 + i]], r = fl(1.0f /
+ * deg(d)), per column:
+ *   SUM   S = ((t_0 + t_1) + t_2) + ... , left to right from the first term: the S of (2b).
+ *   MEAN  S * r: the MEAN of (2b).
+ *   MIN   acc = t_0, arg = e0; then for i = 1, 2, ...: if t_i < acc then acc = t_i, arg = e0 + i. MAX the same with `>`.
+ *         Only a strict comparison replaces: among equal values, duplicate edges and -0.0 / +0.0 (which compare equal) the
+ *         lowest edge position wins and its bits are the result. A NaN compares false: a NaN in t_0 stays (acc = NaN,
+ *         arg = e0), a NaN in a later term is passed over.
+ *   STD   Q = ((t_0 * t_0 + t_1 * t_1) + t_2 * t_2) + ... , each square rounded, added left to right from the first one.
+ *         m = S * r. v = Q * r - m * m. std = sqrtf((v > 0 ? v : 0) + eps) (so a NaN v counts as 0).
+ *   A target without edges gets +0.0 in every aggregator slot, arg = -1, m = 0 and c = 0.
+ *   The last slot is x[d].
+ *   Saved for the backward, each [n_dst, dim] dense (row d at d * dim), each written only when its pointer is not null and
+ *   its aggregator is selected: arg_min, arg_max int32 (global edge positions), std_mean = m, std_coef = c =
+ *   (v > 0) ? r / std : 0.
+ * backward: grad_out G [n_dst, grad_out_stride] -> grad_x [n_src, grad_x_stride], every row written. With G_sum, G_mean,
+ * G_min, G_max, G_std and G_self the slots of a row of G, the term of edge e = (s -> d), per column f, is the sum of its
+ * parts in this order, starting from the first part that is present:
+ *   G_sum[d,f]; G_mean[d,f] * r(d); G_min[d,f] if arg_min[d,f] == e; G_max[d,f] if arg_max[d,f] == e;
+ *   (G_std[d,f] * c[d,f]) * (x[s,f] - m[d,f]).
+ *   A part whose aggregator is not selected, or whose arg is another edge, is absent: it is not added as a zero. An edge
+ *   with no part adds nothing.
+ *   P(s) = +0.0 + t(e_0) + t(e_1) + ... over the edges with col_ind[e] = s in ascending edge position, left to right, when s
+ *   has at most C edges; otherwise the edges are cut into consecutive chunks of C, each chunk summed in that way from its own
+ *   +0.0 and the chunk sums added in chunk order, with C = wholememory_ext_csc_aggregate_chunk_edges(). (Unlike (2b) the sums
+ *   start from +0.0, since an edge may add nothing.) grad_x[s] = P(s) + G_self[s] (the self term added last, only for
+ *   s < n_dst); with one side missing the other is copied, with neither the row is +0.0. No per-target pre-pass: the d-only
+ *   factors are read per edge as they stand. The edge index is built with the library's id sort, scratch from p_env_fns.
+ *   The backward reads x only when STD is selected, and arg_min / arg_max / std_mean / std_coef only for their aggregator.
+ * n_edges = 0 and n_dst = 0 are valid. INVALID_INPUT, before any device work and under every backend, for what (2b) rejects
+ * (null pointers, negative sizes, dim < 1, n_dst > n_src, a stride of out / grad_out below (A + 1) * dim or of x / grad_x
+ * below dim), a mask that is 0 or has other bits, eps < 0 or NaN, and in the backward a selected aggregator whose saved
+ * buffer is null (n_dst > 0), a selected STD with a null x (n_src > 0) and a null p_env_fns. NOT_SUPPORTED (nothing queued)
+ * when the device backend has no such kernels. */
+enum wholememory_ext_pna_aggr_t {
+  WHOLEMEMORY_EXT_PNA_SUM  = 1,
+  WHOLEMEMORY_EXT_PNA_MEAN = 2,
+  WHOLEMEMORY_EXT_PNA_MIN  = 4,
+  WHOLEMEMORY_EXT_PNA_MAX  = 8,
+  WHOLEMEMORY_EXT_PNA_STD  = 16,
+};
+enum wholememory_error_code_t wholememory_ext_csc_pna_aggregate_forward(const int32_t* row_ptr,
+                                                                        const int32_t* col_ind,
+                                                                        int64_t n_edges,
+                                                                        int64_t n_dst,
+                                                                        int64_t n_src,
+                                                                        const float* x,
+                                                                        int64_t x_stride,
+                                                                        int64_t dim,
+                                                                        int aggregators,
+                                                                        float eps, /* 1e-5f in the Python op */
+                                                                        float* out,
+                                                                        int64_t out_stride,
+                                                                        int32_t* arg_min,
+                                                                        int32_t* arg_max,
+                                                                        float* std_mean,
+                                                                        float* std_coef,
+                                                                        struct wholememory_env_func_t* p_env_fns,
+                                                                        void* stream);
+enum wholememory_error_code_t wholememory_ext_csc_pna_aggregate_backward(const int32_t* row_ptr,
+                                                                         const int32_t* col_ind,
+                                                                         int64_t n_edges,
+                                                                         int64_t n_dst,
+                                                                         int64_t n_src,
+                                                                         const float* x,
+                                                                         int64_t x_stride,
+                                                                         int64_t dim,
+                                                                         int aggregators,
+                                                                         const int32_t* arg_min,
+                                                                         const int32_t* arg_max,
+                                                                         const float* std_mean,
+                                                                         const float* std_coef,
+                                                                         const float* grad_out,
+                                                                         int64_t grad_out_stride,
+                                                                         float* grad_x,
+                                                                         int64_t grad_x_stride,
+                                                                         struct wholememory_env_func_t* p_env_fns,
+                                                                         void* stream);
 
 /* ---- (3) testing seam ---------------------------------------------------------------------- */
 /* Replaces the device backend. Refuses (WHOLEMEMORY_NOT_SUPPORTED) unless the environment has

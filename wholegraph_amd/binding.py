@@ -29,6 +29,8 @@ ML_NONE, ML_DEVICE, ML_HOST = range(3)
 (DT_UNKNOWN, DT_FLOAT, DT_HALF, DT_DOUBLE, DT_BF16, DT_INT, DT_INT64, DT_INT16, DT_INT8, DT_COUNT) = range(10)
 MA_NONE, MA_DEVICE, MA_HOST, MA_PINNED = range(4)
 AGGR_SUM, AGGR_MEAN = range(2)
+# the aggregator mask of wholememory_ext_csc_pna_aggregate_* (wholememory_ext_pna_aggr_t), in slot order
+PNA_AGGR = {"sum": 1, "mean": 2, "min": 4, "max": 8, "std": 16}
 OPT_NONE, OPT_SGD, OPT_LAZY_ADAM, OPT_RMSPROP, OPT_ADAGRAD = range(5)
 AT_NONE, AT_READONLY, AT_READWRITE = range(3)
 LEVEL_FATAL, LEVEL_ERROR, LEVEL_WARN, LEVEL_INFO, LEVEL_DEBUG, LEVEL_TRACE = range(6)
@@ -315,6 +317,10 @@ PROTOTYPES = {
     "wholememory_ext_csc_mha_simple_backward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64,
                                                     _i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _P(EnvFunc),
                                                     _vp]),
+    "wholememory_ext_csc_pna_aggregate_forward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i, _f, _vp, _i64, _vp,
+                                                       _vp, _vp, _vp, _P(EnvFunc), _vp]),
+    "wholememory_ext_csc_pna_aggregate_backward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i, _vp, _vp, _vp, _vp,
+                                                        _vp, _i64, _vp, _i64, _P(EnvFunc), _vp]),
     "wholememory_ext_csc_rel_aggregate_forward": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _i64, _i, _vp, _i64,
                                                       _vp, _P(EnvFunc), _vp]),
     "wholememory_ext_csc_rel_aggregate_backward": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i, _vp,

@@ -3,7 +3,8 @@
 // (fp32 rows), kernels/agg_half.hip (fp16 / bf16 rows, the _typed entry points) and kernels/agg_weighted.hip (a weight per
 // edge, section 2d, the _weighted entry points) and kernels/agg_gather.hip (rows read from a WholeMemory table by global id,
 // section 2e) and kernels/agg_quant.hip (the same from an 8-bit row-quantized table, section 2j) and kernels/agg_rel.hip (a
-// type per edge and a slot per relation, section 2h, the _rel_ entry points). The semantics, and the one order of every fp32 sum, are stated in the header.
+// type per edge and a slot per relation, section 2h, the _rel_ entry points) and kernels/pna.hip (sum, mean, min, max and std
+// out of one read of the neighbour rows, section 2l, the _pna_ entry points). The semantics, and the one order of every fp32 sum, are stated in the header.
 #include <atomic>
 
 #include <wholememory/wholegraph_amd_ext.h>
@@ -382,6 +383,112 @@ wholememory_error_code_t wholememory_ext_csc_rel_aggregate_backward(const int32_
                       [&](const int32_t* order, const int32_t* starts, const int32_t* unique, const int64_t* nu, void* ws) {
                         WM_BK(bk->relagg_backward(&a, order, starts, unique, nu, ws, stream));
                       });
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+}  // extern "C"
+
+namespace {
+
+// what the two _pna_ entry points check alike; `rows` / `rows_stride` / `rows_n`: the [n_dst, (A + 1) * dim] side (out, or
+// grad_out), `other` / `other_stride` / `other_n`: the [n_src, dim] side (x, or grad_x)
+wm_pna_args pna_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src,
+                     int64_t dim, int mask, const void* rows, int64_t rows_stride, const void* other, int64_t other_stride)
+{
+  auto bad = [](const char* what) { throw invalid_input(what); };
+  check_block(row_ptr, col_ind, n_edges, n_dst, n_src, n_edges > 0, "x");
+  if (dim < 1) bad("dim must be >= 1");
+  if (mask < 1 || mask > WM_PNA_ALL) bad("aggregators: a non-empty mask of the five WHOLEMEMORY_EXT_PNA_ bits");
+  int slots = 1;
+  for (int bit = 1; bit <= WM_PNA_STD; bit <<= 1) slots += (mask & bit) ? 1 : 0;
+  if (n_dst > 0 && rows == nullptr) bad("rows of the targets are null");
+  if (n_src > 0 && other == nullptr) bad("rows of the sources are null");
+  if (rows_stride < slots * dim) bad("stride of the targets' rows smaller than (aggregators + 1) * dim");
+  if (other_stride < dim) bad("stride of the sources' rows smaller than dim");
+  wm_pna_args a{};
+  a.row_ptr = row_ptr;
+  a.col_ind = col_ind;
+  a.n_edges = n_dst == 0 ? 0 : n_edges;   // (no target, no edge of any target)
+  a.n_dst   = n_dst;
+  a.n_src   = n_src;
+  a.dim     = dim;
+  a.mask    = mask;
+  return a;
+}
+
+}  // namespace
+
+extern "C" {
+
+wholememory_error_code_t wholememory_ext_csc_pna_aggregate_forward(const int32_t* row_ptr, const int32_t* col_ind,
+                                                                   int64_t n_edges, int64_t n_dst, int64_t n_src,
+                                                                   const float* x, int64_t x_stride, int64_t dim,
+                                                                   int aggregators, float eps, float* out,
+                                                                   int64_t out_stride, int32_t* arg_min, int32_t* arg_max,
+                                                                   float* std_mean, float* std_coef,
+                                                                   wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  (void)p_env_fns;   // (the forward needs no scratch)
+  // (the arguments are judged first: a malformed call is INVALID_INPUT under every backend)
+  auto a = pna_args(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggregators, out, out_stride, x, x_stride);
+  if (!(eps >= 0.0f)) throw invalid_input("eps must be >= 0");
+  const auto* bk = backend();
+  if (bk->pna_forward == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  a.eps        = eps;
+  a.in         = x;
+  a.in_stride  = x_stride;
+  a.out        = out;
+  a.out_stride = out_stride;
+  a.arg_min    = (aggregators & WM_PNA_MIN) ? arg_min : nullptr;
+  a.arg_max    = (aggregators & WM_PNA_MAX) ? arg_max : nullptr;
+  a.std_mean   = (aggregators & WM_PNA_STD) ? std_mean : nullptr;
+  a.std_coef   = (aggregators & WM_PNA_STD) ? std_coef : nullptr;
+  WM_BK(bk->pna_forward(&a, stream));
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+wholememory_error_code_t wholememory_ext_csc_pna_aggregate_backward(
+  const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src, const float* x,
+  int64_t x_stride, int64_t dim, int aggregators, const int32_t* arg_min, const int32_t* arg_max, const float* std_mean,
+  const float* std_coef, const float* grad_out, int64_t grad_out_stride, float* grad_x, int64_t grad_x_stride,
+  wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  auto a = pna_args(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggregators, grad_out, grad_out_stride, grad_x,
+                    grad_x_stride);
+  if (n_dst > 0) {   // what the forward saved for the selected aggregators
+    if ((aggregators & WM_PNA_MIN) && arg_min == nullptr) throw invalid_input("min is selected and arg_min is null");
+    if ((aggregators & WM_PNA_MAX) && arg_max == nullptr) throw invalid_input("max is selected and arg_max is null");
+    if ((aggregators & WM_PNA_STD) && (std_mean == nullptr || std_coef == nullptr))
+      throw invalid_input("std is selected and std_mean or std_coef is null");
+  }
+  if (aggregators & WM_PNA_STD) {   // the gradient of std reads the rows of x
+    if (n_src > 0 && x == nullptr) throw invalid_input("std is selected and x is null");
+    if (x_stride < dim) throw invalid_input("input stride smaller than its row");
+  }
+  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
+  const auto* bk = backend();
+  if (bk->pna_backward == nullptr || bk->pna_backward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  a.in          = x;
+  a.in_stride   = x_stride;
+  // (read only by the backward, and only for the selected aggregators)
+  a.arg_min     = (aggregators & WM_PNA_MIN) ? const_cast<int32_t*>(arg_min) : nullptr;
+  a.arg_max     = (aggregators & WM_PNA_MAX) ? const_cast<int32_t*>(arg_max) : nullptr;
+  a.std_mean    = (aggregators & WM_PNA_STD) ? const_cast<float*>(std_mean) : nullptr;
+  a.std_coef    = (aggregators & WM_PNA_STD) ? const_cast<float*>(std_coef) : nullptr;
+  a.grad        = grad_out;
+  a.grad_stride = grad_out_stride;
+  a.out         = grad_x;
+  a.out_stride  = grad_x_stride;
+  if (n_src == 0) return WHOLEMEMORY_SUCCESS;
+  sorted_ids ix(p_env_fns);
+  temp_mem ws(p_env_fns);
+  sort_col_ind(&ix, col_ind, a.n_edges, n_src, stream);
+  void* d_ws = ws.device(static_cast<int64_t>(bk->pna_backward_workspace_bytes(a.n_edges, n_src, dim)), WHOLEMEMORY_DT_INT8);
+  WM_BK(bk->pna_backward(&a, ix.order, ix.starts, static_cast<const int32_t*>(ix.unique), ix.n_unique_dev, d_ws, stream));
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }

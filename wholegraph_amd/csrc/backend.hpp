@@ -404,6 +404,31 @@ struct wm_tconv_args {
   int64_t grad_value_stride;
 };
 
+// multi-aggregator neighbour aggregation of a sampled CSC block (kernels/pna.hip, the `agg_concat_pna` op,
+// wholegraph_amd_ext.h section 2l): rows / strides in ELEMENTS (fp32). `mask` selects the aggregators (the bits of
+// wholememory_ext_pna_aggr_t); a row of out / grad has one slot of dim columns per selected aggregator, in the order of the
+// bits, then the target's own row
+enum wm_pna_bits : int { WM_PNA_SUM = 1, WM_PNA_MEAN = 2, WM_PNA_MIN = 4, WM_PNA_MAX = 8, WM_PNA_STD = 16, WM_PNA_ALL = 31 };
+struct wm_pna_args {
+  const int32_t* row_ptr;   // [n_dst + 1]
+  const int32_t* col_ind;   // [n_edges], ids in [0, n_src)
+  int64_t n_edges, n_dst, n_src, dim;
+  int mask;                 // 1 .. WM_PNA_ALL
+  float eps;                // std = sqrt(max(v, 0) + eps)
+  const float* in;          // x [n_src, in_stride] (the backward reads it for std only)
+  int64_t in_stride;
+  // saved by the forward for the backward, each [n_dst, dim] dense. Forward: written when not null; backward: read when the
+  // aggregator is selected
+  int32_t* arg_min;         // the edge position that holds the minimum (-1: no edge)
+  int32_t* arg_max;
+  float* std_mean;          // m
+  float* std_coef;          // c = (v > 0) ? r / std : 0
+  const float* grad;        // backward: dL/dout [n_dst, grad_stride]
+  int64_t grad_stride;
+  float* out;               // forward: out [n_dst, out_stride]; backward: grad_x [n_src, out_stride]
+  int64_t out_stride;
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -666,6 +691,13 @@ struct wm_device_backend {
   size_t (*tconv_backward_workspace_bytes)(const wm_tconv_args* a);
   int (*tconv_backward)(const wm_tconv_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
                         const int64_t* n_unique_dev, void* workspace, void* stream);
+  // ---- multi-aggregator neighbour aggregation of a sampled CSC block (kernels/pna.hip, wholegraph_amd_ext.h section 2l);
+  // nullptr in a backend without it. The forward needs no workspace; the backward takes the index of agg_backward and a
+  // workspace of pna_backward_workspace_bytes(n_edges, n_src, dim) ----
+  int (*pna_forward)(const wm_pna_args* a, void* stream);
+  size_t (*pna_backward_workspace_bytes)(int64_t n_edges, int64_t n_src, int64_t dim);
+  int (*pna_backward)(const wm_pna_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                      const int64_t* n_unique_dev, void* workspace, void* stream);
 };
 
 }  // extern "C"

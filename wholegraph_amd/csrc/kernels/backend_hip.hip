@@ -107,6 +107,10 @@ int hip_tconv_forward(const wm_tconv_args* a, void* workspace, void* stream);
 size_t hip_tconv_backward_workspace_bytes(const wm_tconv_args* a);
 int hip_tconv_backward(const wm_tconv_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
                        const int64_t* n_unique_dev, void* workspace, void* stream);
+int hip_pna_forward(const wm_pna_args* a, void* stream);
+size_t hip_pna_backward_workspace_bytes(int64_t n_edges, int64_t n_src, int64_t dim);
+int hip_pna_backward(const wm_pna_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
+                     const int64_t* n_unique_dev, void* workspace, void* stream);
 
 namespace {
 
@@ -303,6 +307,9 @@ const wm_device_backend kHipBackend = {
   hip_tconv_forward,
   hip_tconv_backward_workspace_bytes,
   hip_tconv_backward,
+  hip_pna_forward,
+  hip_pna_backward_workspace_bytes,
+  hip_pna_backward,
 };
 
 }  // namespace

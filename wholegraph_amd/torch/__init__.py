@@ -8,14 +8,15 @@ functors, neighbour sampling and GraphStructure, and for the GNN model surface o
 GraphSAGE layer ``cugraphops.EdgeWeightedSAGEConv`` on ``weighted_aggregation``, the GAT layer with edge features
 ``cugraphops.EdgeGATConv`` on ``edge_gat_aggregation``, the GATv2 layer ``cugraphops.GATv2Conv`` on ``gatv2_aggregation``
 (model name "gatv2"), the RGCN layer ``cugraphops.RGCNConv`` on ``rel_aggregation`` (model name "rgcn"), the transformer
-layer ``cugraphops.TransformerConv`` on ``transformer_aggregation`` (model name "transformer"), and
+layer ``cugraphops.TransformerConv`` on ``transformer_aggregation`` (model name "transformer"), the PNA layer
+``cugraphops.PNAConv`` on ``pna_aggregation`` (sum / mean / min / max / std in one pass; model name "pna"), and
 ``gather_aggregation``, layer 0's aggregation straight from a
 WholeMemory table, and ``quantized``, 8-bit row-quantized tables whose gather dequantizes the rows it reads). GAT in
 ``HomoGNNModel``, the dgl / pyg / wg routes, data loaders, launch helpers and option parsers of the reference are outside this build's scope.
 """
 from . import comm, embedding, graph_ops, graph_structure, initialize, tensor, utils, wholegraph_ops, wholememory_ops
 from . import aggregation, cugraphops, edge_gat_aggregation, gat_aggregation, gather_aggregation, gnn_model
-from . import gatv2_aggregation, quantized, rel_aggregation, transformer_aggregation, weighted_aggregation
+from . import gatv2_aggregation, pna_aggregation, quantized, rel_aggregation, transformer_aggregation, weighted_aggregation
 
 _PUBLIC = {
     comm: ("WholeMemoryCommunicator create_group_communicator destroy_communicator get_global_communicator "
@@ -30,14 +31,15 @@ _PUBLIC = {
     utils: "get_part_file_name get_part_file_list wholememory_dtype_to_torch_dtype torch_dtype_to_wholememory_dtype",
     wholememory_ops: "wholememory_gather_forward_functor wholememory_scatter_functor",
     graph_structure: "GraphStructure",
-    gnn_model: "set_framework create_gnn_layers create_rgcn_layers create_sub_graph HomoGNNModel",
+    gnn_model: "set_framework create_gnn_layers create_rgcn_layers create_pna_layers create_sub_graph HomoGNNModel",
     gather_aggregation: "gather_agg_concat",
+    pna_aggregation: "agg_concat_pna",
     quantized: ("WholeMemoryQuantizedTensor create_quantized_tensor quantized_row_bytes quantize_rows "
                 "dequantize_rows"),
 }
 __all__ = ["graph_ops", "wholegraph_ops", "aggregation", "cugraphops", "gat_aggregation", "gnn_model", "weighted_aggregation",
            "gather_aggregation", "edge_gat_aggregation", "gatv2_aggregation", "rel_aggregation", "quantized",
-           "transformer_aggregation"]
+           "transformer_aggregation", "pna_aggregation"]
 for _module, _names in _PUBLIC.items():
     for _name in _names.split():
         globals()[_name] = getattr(_module, _name)

@@ -2,7 +2,8 @@
 ``create_sub_graph``, ``layer_forward``, ``HomoGNNModel``) for the ``cugraph`` framework route with GraphSAGE layers, on the
 HIP aggregation op (``aggregation.py``), with GATv2 layers (model "gatv2": ``cugraphops.GATv2Conv`` on
 ``gatv2_aggregation.py``), with transformer layers (model "transformer": ``cugraphops.TransformerConv`` on
-``transformer_aggregation.py``) and, for graphs with typed edges, with RGCN layers (model "rgcn": ``cugraphops.RGCNConv`` on
+``transformer_aggregation.py``), with PNA layers (model "pna": ``cugraphops.PNAConv`` on ``pna_aggregation.py``, built by
+``create_pna_layers``) and, for graphs with typed edges, with RGCN layers (model "rgcn": ``cugraphops.RGCNConv`` on
 ``rel_aggregation.py``, built by ``create_rgcn_layers``; the sampler delivers each block's edge types). The dgl / pyg / wg
 routes and the model "gat" are not part of this build (the GAT layer itself is ``cugraphops.CuGraphGATConv``).
 
@@ -88,6 +89,24 @@ def create_rgcn_layers(in_feat_dim, hidden_feat_dim, class_count, num_layer, num
     return gnn_layers
 
 
+def create_pna_layers(in_feat_dim, hidden_feat_dim, class_count, num_layer, delta, aggregators=None, scalers=None):
+    """the layers of model "pna": PNAConv(in -> hidden) ... PNAConv(hidden -> class_count), each with the degree scalers'
+    `delta` (cugraphops.pna_delta of the training graph); `aggregators` / `scalers`: the layer's defaults when None"""
+    _require_framework()
+    from .cugraphops.pna_conv import PNAConv
+    choice = {}
+    if aggregators is not None:
+        choice["aggregators"] = aggregators
+    if scalers is not None:
+        choice["scalers"] = scalers
+    gnn_layers = torch.nn.ModuleList()
+    for i in range(num_layer):
+        layer_output_dim = hidden_feat_dim if i != num_layer - 1 else class_count
+        layer_input_dim = in_feat_dim if i == 0 else hidden_feat_dim
+        gnn_layers.append(PNAConv(layer_input_dim, layer_output_dim, delta=delta, **choice))
+    return gnn_layers
+
+
 def create_sub_graph(target_gid, target_gid_1, edge_data, csr_row_ptr, csr_col_ind, max_num_neighbors: int,
                      add_self_loop: bool):
     """[csr_row_ptr, csr_col_ind, max_num_neighbors] of one sampled block (the cugraph route's sub-graph)"""
@@ -107,7 +126,9 @@ class HomoGNNModel(torch.nn.Module):
     """Node classification model over a homogeneous graph: settings from an ``args`` namespace as the reference reads them
     (hiddensize, layernum, model, classnum, dropout, neighbors, inferencesample; heads for gat). Model "rgcn" (an
     extension) also reads num_relations, edge_type_name (an integer edge attribute registered with
-    ``graph_structure.set_edge_attribute``: the relation of every graph edge) and, optionally, num_bases.
+    ``graph_structure.set_edge_attribute``: the relation of every graph edge) and, optionally, num_bases. Model "pna" (an
+    extension) reads pna_delta (``cugraphops.pna_delta`` of the training graph) and, optionally, pna_aggregators and
+    pna_scalers.
     ``node_embedding`` may also be a ``WholeMemoryQuantizedTensor`` (an extension: 8-bit row-quantized, frozen features):
     the features then come from its ``gather``, or with ``args.fuse_gather`` from layer 0's aggregation itself."""
 
@@ -119,7 +140,7 @@ class HomoGNNModel(torch.nn.Module):
         self.num_layer = args.layernum
         self.hidden_feat_dim = args.hiddensize
         attention = args.model in ("gat", "gatv2")
-        if args.model in ("gatv2", "transformer") and getattr(args, "fuse_gather", False):
+        if args.model in ("gatv2", "transformer", "pna") and getattr(args, "fuse_gather", False):
             raise ValueError("fuse_gather reads layer 0's rows from the table: GraphSAGE only, not model %r" % args.model)
         num_head = args.heads if attention or args.model == "transformer" else 1
         assert hidden_feat_dim % num_head == 0
@@ -135,6 +156,11 @@ class HomoGNNModel(torch.nn.Module):
             self.edge_type_name = args.edge_type_name
             self.gnn_layers = create_rgcn_layers(in_feat_dim, hidden_feat_dim, args.classnum, args.layernum,
                                                  args.num_relations, getattr(args, "num_bases", None))
+        elif args.model == "pna":
+            if getattr(args, "pna_delta", None) is None:
+                raise ValueError("model 'pna' needs args.pna_delta (cugraphops.pna_delta of the training graph)")
+            self.gnn_layers = create_pna_layers(in_feat_dim, hidden_feat_dim, args.classnum, args.layernum, args.pna_delta,
+                                                getattr(args, "pna_aggregators", None), getattr(args, "pna_scalers", None))
         else:
             self.gnn_layers = create_gnn_layers(in_feat_dim, hidden_feat_dim, args.classnum, args.layernum, num_head,
                                                 args.model)

@@ -27,6 +27,7 @@
  *      and a deterministic backward).
  *      (2l) the multi-aggregator neighbour aggregation of a sampled CSC block behind the PNAConv layer: sum, mean, min, max
  *      and std of the neighbour rows out of one read of them (forward and a deterministic backward).
+ *      (2m) random walks over a CSR graph held in WholeMemory, uniform or by edge weight, as one launch for the whole batch.
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -1104,6 +1105,59 @@ enum wholememory_error_code_t wholememory_ext_csc_pna_aggregate_backward(const i
                                                                          int64_t grad_x_stride,
                                                                          struct wholememory_env_func_t* p_env_fns,
                                                                          void* stream);
+
+/* ---- (2m) random walks over a CSR graph held in WholeMemory ------------------------------------------------------------ */
+/* n walks of walk_length = L >= 1 steps over the graph row_ptr (int64, [n_nodes + 1]; n_nodes is its size minus one),
+ * col_ind (int32 or int64, [n_edges]) and, for the weighted form, one weight per edge position (float or double); start
+ * nodes int32 or int64, [n]; a 64-bit seed. The graph tensors are CONTINUOUS or CHUNKED WholeMemory tensors in device or host
+ * memory, or plain device arrays wrapped with wholememory_make_tensor_from_pointer; start nodes and outputs are device
+ * arrays. One launch on `stream`; nothing is allocated, nothing is read back and the call does not synchronise.
+ *
+ * Outputs. walks [n, L + 1] in col_ind's dtype and, optionally, edge_ids [n, L] int64 (positions in col_ind), each a dense
+ * block given as a 2-D tensor of that shape or a 1-D one of as many entries. Column 0 of walk w is its start node, or -1 when
+ * the start is outside [0, n_nodes). A walk ends when a step is not taken; from that step on walks and edge_ids hold -1. A
+ * step from v is not taken when
+ *   - deg(v) = row_ptr[v + 1] - row_ptr[v] is <= 0 or >= 2^31 (or the row's bounds do not lie in [0, n_edges]: a valid
+ *     graph has no such row);
+ *   - the weighted form finds no eligible neighbour;
+ *   - the chosen col_ind entry is outside [0, n_nodes): an id read from col_ind indexes row_ptr in the next step, so a
+ *     damaged graph ends a walk, it does not read out of bounds;
+ *   - the walk has already ended.
+ *
+ * Random streams. mix(z), all modulo 2^64:  z += 0x9E3779B97F4A7C15;  z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ * z = (z ^ z >> 27) * 0x94D049BB133111EB;  return z ^ z >> 31.  stream(seed, a, b) is the PCG-XSH-RR 64/32 generator of the
+ * samplers initialised as init(seed' = mix(mix(seed + a) + b), subsequence = a, offset = 0): state = 0, inc = (a << 1) | 1,
+ * one step, state += seed', one step. mix(0) = 0xe220a8397b1dcdaf; stream(42, 3, 0) starts 2748719185, 1404529248,
+ * 2891244060, 1914411027 and stream(42, 3, 5) starts 2746596618, 1305647937, 1544306493. (Streams told apart by the
+ * increment alone, without mix, gave correlated picks two steps apart in one walk.)
+ *
+ * Uniform step. Walk w has one generator, stream(seed, w, 0); step t (0-based) uses its t-th 32-bit output r, whether or
+ * not earlier steps were taken. The chosen neighbour is k = (uint64(r) * uint64(deg)) >> 32, the edge row_ptr[v] + k.
+ *
+ * Weighted step. A weight is converted to fp32 first; neighbour j is eligible when that value is > 0 (zero, negative and NaN
+ * weights are never chosen; +inf is not specified). The key of neighbour j at step t of walk w is the A-Res key of the
+ * weighted sampler, log2(u) * (1.0f / weight) with log2(u) from three draws of stream(seed, w * L + t, j + 1) (a 24-bit
+ * mantissa from the first, the exponent from the leading zeros of the 64 bits of the next two, low word first). The chosen
+ * neighbour is the eligible j with the largest key in an fp32 `>` comparison; ties go to the lowest j.
+ *
+ * The result depends on (seed, w, t, j) only, not on the launch geometry and not on n: the first 100 walks of a batch of 512
+ * equal a batch of those 100.
+ *
+ * INVALID_INPUT for a null row_ptr, col_ind, start nodes or walks tensor, a tensor among the first three that is not 1-D,
+ * walk_length < 1, n * (walk_length + 1) >= 2^31, an output of the wrong size, a weight tensor that is not one entry per edge,
+ * and HIERARCHY tensors. LOGIC_ERROR for a row_ptr that is not int64, col_ind or start nodes that are not int32 / int64,
+ * walks not in col_ind's dtype, edge ids not int64, weights not float / double. NOT_IMPLEMENTED for a DISTRIBUTED tensor.
+ * NOT_SUPPORTED, nothing queued, when the device backend has no walk kernels. n = 0 succeeds and queues nothing. Every
+ * answer other than SUCCESS comes before any device work. */
+enum wholememory_error_code_t wholememory_ext_csr_random_walk(wholememory_tensor_t wm_csr_row_ptr_tensor,
+                                                              wholememory_tensor_t wm_csr_col_ptr_tensor,
+                                                              wholememory_tensor_t wm_csr_weight_ptr_tensor, /* NULL: uniform */
+                                                              wholememory_tensor_t start_nodes_tensor,
+                                                              int walk_length,
+                                                              unsigned long long random_seed,
+                                                              wholememory_tensor_t output_walks_tensor,
+                                                              wholememory_tensor_t output_edge_ids_tensor, /* may be NULL */
+                                                              void* stream);
 
 /* ---- (3) testing seam ---------------------------------------------------------------------- */
 /* Replaces the device backend. Refuses (WHOLEMEMORY_NOT_SUPPORTED) unless the environment has

@@ -429,6 +429,26 @@ struct wm_pna_args {
   int64_t out_stride;
 };
 
+// random walks over a CSR graph whose arrays are mapped (flat or chunked) in this process (kernels/walk.hip,
+// wholegraph_amd_ext.h section 2m). One launch; nothing is allocated and nothing read back
+struct wm_walk_args {
+  wholememory_gref_t row_gref, col_gref;  // csr_row_ptr (int64), csr_col_ptr (col_dtype)
+  int64_t row_storage_offset, col_storage_offset;  // elements
+  wholememory_dtype_t col_dtype;
+  int64_t n_nodes, n_edges;
+  // walk_weighted only: per-edge weights (float / double), same indexing as csr_col_ptr
+  wholememory_gref_t weight_gref;
+  int64_t weight_storage_offset;
+  wholememory_dtype_t weight_dtype;
+  const void* starts;   // [n] device
+  wholememory_dtype_t start_dtype;
+  int64_t n;            // walks; n * (walk_length + 1) < 2^31
+  int walk_length;      // >= 1
+  uint64_t random_seed;
+  void* out_walks;        // [n, walk_length + 1] col_dtype
+  int64_t* out_edge_ids;  // [n, walk_length] or nullptr
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -698,6 +718,9 @@ struct wm_device_backend {
   size_t (*pna_backward_workspace_bytes)(int64_t n_edges, int64_t n_src, int64_t dim);
   int (*pna_backward)(const wm_pna_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
                       const int64_t* n_unique_dev, void* workspace, void* stream);
+  // ---- random walks (kernels/walk.hip, wholegraph_amd_ext.h section 2m); nullptr in a backend without them ----
+  int (*walk_uniform)(const wm_walk_args* a, void* stream);
+  int (*walk_weighted)(const wm_walk_args* a, void* stream);
 };
 
 }  // extern "C"

@@ -271,6 +271,120 @@ wholememory_error_code_t wholegraph_csr_weighted_sample_without_replacement(
   WM_API_END
 }
 
+// Random walks (extension, wholegraph_amd_ext.h section 2m; kernels/walk.hip): n walks of walk_length steps as ONE launch on
+// `stream`. The outputs are the caller's, their sizes known beforehand: nothing is allocated, nothing read back, the call
+// does not synchronise, and every answer but SUCCESS is given before any device work.
+wholememory_error_code_t wholememory_ext_csr_random_walk(
+  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor,
+  wholememory_tensor_t wm_csr_weight_ptr_tensor, wholememory_tensor_t start_nodes_tensor, int walk_length,
+  unsigned long long random_seed, wholememory_tensor_t output_walks_tensor, wholememory_tensor_t output_edge_ids_tensor,
+  void* stream)
+{
+  WM_API_BEGIN
+  if (output_walks_tensor == nullptr) return WHOLEMEMORY_INVALID_INPUT;
+  wholememory_error_code_t err = WHOLEMEMORY_SUCCESS;
+  wholememory_array_description_t row_desc, col_desc, start_desc;
+  if (!array_of(wm_csr_row_ptr_tensor, "wm_csr_row_ptr_tensor", &row_desc, &err)) return err;
+  if (!array_of(wm_csr_col_ptr_tensor, "wm_csr_col_ptr_tensor", &col_desc, &err)) return err;
+  if (!array_of(start_nodes_tensor, "start_nodes_tensor", &start_desc, &err)) return err;
+  if (walk_length < 1) {
+    WM_ERROR("walk_length must be at least 1, got %d", walk_length);
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  const int64_t n = start_desc.size, L = walk_length;
+  if (n < 0 || row_desc.size < 1 || n > ((INT64_C(1) << 31) - 1) / (L + 1)) {
+    WM_ERROR("%ld walks of %d steps: the outputs must hold fewer than 2^31 entries", static_cast<long>(n), walk_length);
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  // an output is the dense [n, width] block, given as a 2-D tensor of that shape or as a 1-D one of n * width entries
+  auto dense = [n](wholememory_tensor_t t, int64_t width) {
+    const auto d = *wholememory_tensor_get_tensor_description(t);
+    if (d.dim == 1) return d.sizes[0] == n * width && (d.strides[0] == 1 || d.sizes[0] <= 1);
+    return d.dim == 2 && d.sizes[0] == n && d.sizes[1] == width && d.strides[1] == 1 && (d.strides[0] == width || n <= 1);
+  };
+  if (!dense(output_walks_tensor, L + 1) || (output_edge_ids_tensor != nullptr && !dense(output_edge_ids_tensor, L))) {
+    WM_ERROR("output_walks_tensor must be [%ld, %ld] and output_edge_ids_tensor [%ld, %ld], dense", static_cast<long>(n),
+             static_cast<long>(L + 1), static_cast<long>(n), static_cast<long>(L));
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  const bool weighted = wm_csr_weight_ptr_tensor != nullptr;
+  wholememory_array_description_t weight_desc{};
+  if (weighted) {
+    if (!array_of(wm_csr_weight_ptr_tensor, "wm_csr_weight_ptr_tensor", &weight_desc, &err)) return err;
+    if (weight_desc.size != col_desc.size) {
+      WM_ERROR("wm_csr_weight_ptr_tensor must have one weight per edge (%ld vs %ld)", static_cast<long>(weight_desc.size),
+               static_cast<long>(col_desc.size));
+      return WHOLEMEMORY_INVALID_INPUT;
+    }
+  }
+  // dtype rules, as the samplers answer them
+  if (row_desc.dtype != WHOLEMEMORY_DT_INT64) {
+    WM_ERROR("wm_csr_row_ptr_tensor must be int64, got %d", static_cast<int>(row_desc.dtype));
+    return WHOLEMEMORY_LOGIC_ERROR;
+  }
+  if (!is_index_dtype(col_desc.dtype) || !is_index_dtype(start_desc.dtype)) {
+    WM_ERROR("start nodes and csr_col_ptr must be int32 or int64");
+    return WHOLEMEMORY_LOGIC_ERROR;
+  }
+  if (wholememory_tensor_get_tensor_description(output_walks_tensor)->dtype != col_desc.dtype) {
+    WM_ERROR("output_walks_tensor must have the dtype of wm_csr_col_ptr_tensor");
+    return WHOLEMEMORY_LOGIC_ERROR;
+  }
+  if (output_edge_ids_tensor != nullptr &&
+      wholememory_tensor_get_tensor_description(output_edge_ids_tensor)->dtype != WHOLEMEMORY_DT_INT64) {
+    WM_ERROR("output_edge_ids_tensor must be int64");
+    return WHOLEMEMORY_LOGIC_ERROR;
+  }
+  if (weighted && weight_desc.dtype != WHOLEMEMORY_DT_FLOAT && weight_desc.dtype != WHOLEMEMORY_DT_DOUBLE) {
+    WM_ERROR("wm_csr_weight_ptr_tensor must be float or double");
+    return WHOLEMEMORY_LOGIC_ERROR;
+  }
+  const wholememory_tensor_t graph_tensors[3] = {wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_weight_ptr_tensor};
+  for (int i = 0; i < (weighted ? 3 : 2); i++) {
+    if (memory_type_of(graph_tensors[i]) == WHOLEMEMORY_MT_HIERARCHY) {
+      WM_ERROR("Memory type not supported.");
+      return WHOLEMEMORY_INVALID_INPUT;
+    }
+  }
+  for (int i = 0; i < (weighted ? 3 : 2); i++) {
+    if (memory_type_of(graph_tensors[i]) == WHOLEMEMORY_MT_DISTRIBUTED) {
+      WM_ERROR("random walks on DISTRIBUTED tensors are not implemented: every step would be a collective gather");
+      return WHOLEMEMORY_NOT_IMPLEMENTED;
+    }
+  }
+  const auto* bk = backend();
+  if (bk->walk_uniform == nullptr || bk->walk_weighted == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  if (n == 0) return WHOLEMEMORY_SUCCESS;
+  wm_walk_args a{};
+  WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_row_ptr_tensor, &a.row_gref));
+  WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_col_ptr_tensor, &a.col_gref));
+  a.row_storage_offset = row_desc.storage_offset;
+  a.col_storage_offset = col_desc.storage_offset;
+  a.col_dtype          = col_desc.dtype;
+  a.n_nodes            = row_desc.size - 1;
+  a.n_edges            = col_desc.size;
+  if (weighted) {
+    WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_weight_ptr_tensor, &a.weight_gref));
+    a.weight_storage_offset = weight_desc.storage_offset;
+    a.weight_dtype          = weight_desc.dtype;
+  }
+  a.starts       = wholememory_tensor_get_data_pointer(start_nodes_tensor);
+  a.start_dtype  = start_desc.dtype;
+  a.n            = n;
+  a.walk_length  = walk_length;
+  a.random_seed  = random_seed;
+  a.out_walks    = wholememory_tensor_get_data_pointer(output_walks_tensor);
+  a.out_edge_ids = output_edge_ids_tensor != nullptr
+                     ? static_cast<int64_t*>(wholememory_tensor_get_data_pointer(output_edge_ids_tensor))
+                     : nullptr;
+  if (a.starts == nullptr || a.out_walks == nullptr || (output_edge_ids_tensor != nullptr && a.out_edge_ids == nullptr))
+    return WHOLEMEMORY_INVALID_INPUT;
+  WM_BK(weighted ? bk->walk_weighted(&a, stream) : bk->walk_uniform(&a, stream));
+  if (debug_sync_enabled()) WM_BK(bk->stream_sync(stream));
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
 wholememory_error_code_t generate_random_positive_int_cpu(int64_t random_seed, int64_t subsequence, wholememory_tensor_t output)
 {
   WM_API_BEGIN

@@ -111,6 +111,8 @@ int hip_pna_forward(const wm_pna_args* a, void* stream);
 size_t hip_pna_backward_workspace_bytes(int64_t n_edges, int64_t n_src, int64_t dim);
 int hip_pna_backward(const wm_pna_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
                      const int64_t* n_unique_dev, void* workspace, void* stream);
+int hip_walk_uniform(const wm_walk_args* a, void* stream);
+int hip_walk_weighted(const wm_walk_args* a, void* stream);
 
 namespace {
 
@@ -310,6 +312,8 @@ const wm_device_backend kHipBackend = {
   hip_pna_forward,
   hip_pna_backward_workspace_bytes,
   hip_pna_backward,
+  hip_walk_uniform,
+  hip_walk_weighted,
 };
 
 }  // namespace

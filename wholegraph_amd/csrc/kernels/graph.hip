@@ -26,6 +26,7 @@
 #include "../knobs.hpp"
 #include "../backend.hpp"
 #include "../pcg.hpp"
+#include "gref_view.cuh"
 
 #include <mutex>
 #include <unordered_map>
@@ -37,49 +38,6 @@ constexpr int kBlock        = 256;
 constexpr int kWavesPerBlk  = kBlock / 64;
 constexpr int kMaxSparse    = 1024;
 constexpr int kMaxWeighted  = 8192;  // weighted selection: candidate list of 2 M composite keys in LDS (<= 128 KiB)  // M <= 1024 on the sparse-recurrence path (the reference's small-sample limit)
-
-struct gref_view {
-  char* base;
-  char* const* rank_ptrs;
-  const size_t* rank_offsets;
-  size_t chunk_stride;
-  int world_size;
-  int same_chunk;
-};
-
-inline gref_view make_view(const wholememory_gref_t& g)
-{
-  gref_view v{};
-  v.chunk_stride = g.stride;
-  v.world_size   = g.world_size;
-  v.same_chunk   = g.same_chunk ? 1 : 0;
-  if (g.stride == 0) {
-    v.base = static_cast<char*>(g.pointer);
-  } else {
-    v.rank_ptrs    = static_cast<char* const*>(g.pointer);
-    v.rank_offsets = g.rank_memory_offsets;
-  }
-  return v;
-}
-
-template <typename T>
-__device__ __forceinline__ T gref_load(const gref_view& v, int64_t elem_index)
-{
-  const size_t off = static_cast<size_t>(elem_index) * sizeof(T);
-  if (v.chunk_stride == 0) return *reinterpret_cast<const T*>(v.base + off);
-  int rank;
-  size_t start;
-  if (v.same_chunk) {
-    rank  = static_cast<int>(off / v.chunk_stride);
-    start = static_cast<size_t>(rank) * v.chunk_stride;
-  } else {
-    rank = 0;
-    for (int r = 1; r < v.world_size; r++)
-      if (off >= v.rank_offsets[r]) rank = r;
-    start = v.rank_offsets[rank];
-  }
-  return *reinterpret_cast<const T*>(v.rank_ptrs[rank] + (off - start));
-}
 
 // ------------------------------------------------------------------------------------------------ single-launch scan
 // Exclusive int32 scan of v[i] = fn(i), i in [0, n), in ONE launch with no workspace to prepare (round 4; rocPRIM's look-back

@@ -26,6 +26,7 @@ struct pcg32 {
   uint64_t state;
   uint64_t inc;
 
+  pcg32() = default;   // not seeded: init() follows (walk_stream)
   // raft DeviceState{seed, base_subsequence} + per-thread subsequence
   WM_HD pcg32(uint64_t seed, uint64_t base_subsequence, uint64_t subsequence) { init(seed, base_subsequence + subsequence, subsequence); }
 
@@ -146,6 +147,44 @@ WM_HD uint32_t orderable_float(float v)
   uint32_t b;
   __builtin_memcpy(&b, &v, 4);
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
+// ---- random walks (wholegraph_amd_ext.h section 2m; kernels/walk.hip) ----
+// The streams of a walk are told apart by the SEED as well as by the PCG increment: stream(seed, a, b) =
+// init(mix(mix(seed + a) + b), subsequence a, offset 0), mix = the finalizer of splitmix64 (G. Steele, D. Lea, C. Flood,
+// "Fast Splittable Pseudorandom Number Generators", 2014). Streams that share a seed and differ in the increment alone gave
+// correlated picks two steps apart in one walk.
+WM_HD uint64_t walk_mix(uint64_t z)
+{
+  z += 0x9E3779B97F4A7C15ULL;
+  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+  z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+  return z ^ (z >> 31);
+}
+WM_HD pcg32 walk_stream(uint64_t seed, uint64_t a, uint64_t b)
+{
+  pcg32 g;
+  g.init(walk_mix(walk_mix(seed + a) + b), a, 0);
+  return g;
+}
+// uniform step: neighbour k of `degree` (1 .. 2^31 - 1) from one 32-bit draw
+WM_HD uint32_t walk_uniform_pick(uint32_t r, uint32_t degree)
+{
+  return static_cast<uint32_t>((static_cast<uint64_t>(r) * static_cast<uint64_t>(degree)) >> 32);
+}
+// weighted step t of walk w over L steps: a neighbour is eligible when its fp32 weight is > 0 (zero, negative and NaN
+// weights are never chosen); the key of neighbour j is the A-Res key above from stream(seed, w * L + t, j + 1)
+WM_HD bool walk_weight_eligible(float weight) { return weight > 0.0f; }
+WM_HD float walk_weighted_key(uint64_t seed, uint64_t walk, uint64_t walk_length, uint64_t step, uint64_t neighbour, float weight)
+{
+  pcg32 g = walk_stream(seed, walk * walk_length + step, neighbour + 1);
+  return weighted_sample_key(g, weight);
+}
+// does candidate (key, j) replace the best so far (best_j < 0: none yet)? The largest key in an fp32 `>` comparison wins,
+// equal keys go to the lowest j — an order that does not depend on how the neighbours are dealt to lanes
+WM_HD bool walk_key_replaces(float key, int j, float best_key, int best_j)
+{
+  return best_j < 0 || key > best_key || (key == best_key && j < best_j);
 }
 
 // Launch geometry the reference derives from max_sample_count (unweighted_sample_without_replacement_func.cuh:

@@ -145,6 +145,16 @@ class GraphStructure(object):
         return self._one_hop(center_nodes_tensor, max_sample_count, weight_name, random_seed, need_center_local_output,
                              need_edge_output)
 
+    # ------------------------------------------------------------------------------------------ random walks
+    def random_walk(self, start_nodes: torch.Tensor, walk_length: int, *, weight_name: Optional[str] = None,
+                    random_seed: Union[int, None] = None, need_edge_ids: bool = False):
+        """Extension: one random walk of walk_length steps from every start node, all of them in one launch
+        (``wholegraph_ops.random_walk``). -> walks [n, walk_length + 1][, edge_ids int64 [n, walk_length]]; -1 from the step at
+        which a walk ends. weight_name: steps are drawn with probability proportional to the named edge attribute."""
+        return wholegraph_ops.random_walk(self.csr_row_ptr.wmb_tensor, self.csr_col_ind.wmb_tensor, start_nodes, walk_length,
+                                          random_seed, wm_csr_weight_ptr_tensor=self._weights(weight_name),
+                                          need_edge_output=need_edge_ids)
+
     # ------------------------------------------------------------------------------------------ several hops
     def multilayer_sample_without_replacement(self, node_ids: torch.Tensor, max_neighbors: List[int],
                                               weight_name: Union[str, None] = None, *,

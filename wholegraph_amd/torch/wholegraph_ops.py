@@ -290,6 +290,35 @@ def weighted_sample_without_replacement(wm_csr_row_ptr_tensor, wm_csr_col_ptr_te
     return _sample_outputs(offset, dest, lid, egid, need_center_local_output, need_edge_output)
 
 
+def random_walk(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, start_nodes_tensor: torch.Tensor, walk_length: int,
+                random_seed: Union[int, None] = None, *, wm_csr_weight_ptr_tensor=None, need_edge_output: bool = False):
+    """Extension (wholememory_ext_csr_random_walk, include/wholememory/wholegraph_amd_ext.h section 2m): one random walk of
+    `walk_length` steps from every start node, as ONE launch with no host round trip. Returns walks [n, walk_length + 1] in
+    csr_col_ptr's dtype — column 0 the start node, -1 from the step at which a walk ends (no neighbour to go to, a start
+    outside the graph) — or (walks, edge_ids) with need_edge_output: int64 [n, walk_length], the position in csr_col_ptr of
+    every step taken, -1 elsewhere. A step goes to a neighbour picked uniformly, or, with wm_csr_weight_ptr_tensor (keyword;
+    float32 / float64, one per edge), with probability proportional to its weight among the neighbours of positive weight.
+    Walk w depends on (random_seed, w) alone, not on the size of the batch."""
+    if int(walk_length) < 1:
+        raise ValueError("walk_length must be at least 1, got %r" % (walk_length,))
+    if start_nodes_tensor.dim() != 1:
+        raise ValueError("start_nodes_tensor must be 1-D, got %d dimensions" % start_nodes_tensor.dim())
+    row, col = _handle(wm_csr_row_ptr_tensor), _handle(wm_csr_col_ptr_tensor)
+    wgt = None if wm_csr_weight_ptr_tensor is None else _handle(wm_csr_weight_ptr_tensor)
+    if random_seed is None:
+        random_seed = random.getrandbits(64)
+    n, steps = start_nodes_tensor.shape[0], int(walk_length)
+    col_dtype = wholememory_dtype_to_torch_dtype(wmb.lib().wholememory_tensor_get_tensor_description(col).contents.dtype)
+    walks = torch.empty((n, steps + 1), device=op_device(), dtype=col_dtype)
+    edge_ids = torch.empty((n, steps), device=op_device(), dtype=torch.int64) if need_edge_output else None
+    ws, ww = wrap_torch_tensor(start_nodes_tensor), wrap_torch_tensor(walks)
+    we = wrap_torch_tensor(edge_ids) if need_edge_output else None
+    wmb.check(wmb.lib().wholememory_ext_csr_random_walk(
+        row, col, wgt, ws.handle, steps, C.c_ulonglong(random_seed & 0xFFFFFFFFFFFFFFFF), ww.handle,
+        we.handle if we is not None else None, C.c_void_p(get_stream())))
+    return (walks, edge_ids) if need_edge_output else walks
+
+
 def generate_random_positive_int_cpu(random_seed, sub_sequence, output_random_value_count):
     output = torch.empty((output_random_value_count,), dtype=torch.int)
     w = wrap_torch_tensor(output)

@@ -28,6 +28,7 @@
  *      (2l) the multi-aggregator neighbour aggregation of a sampled CSC block behind the PNAConv layer: sum, mean, min, max
  *      and std of the neighbour rows out of one read of them (forward and a deterministic backward).
  *      (2m) random walks over a CSR graph held in WholeMemory, uniform or by edge weight, as one launch for the whole batch.
+ *      (2n) node2vec (p, q) second-order walks over the same graph, with or without edge weights, as one launch.
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -1158,6 +1159,55 @@ enum wholememory_error_code_t wholememory_ext_csr_random_walk(wholememory_tensor
                                                               wholememory_tensor_t output_walks_tensor,
                                                               wholememory_tensor_t output_edge_ids_tensor, /* may be NULL */
                                                               void* stream);
+
+/* ---- (2n) node2vec (p, q) second-order walks over a CSR graph held in WholeMemory ----------------------------------------- */
+/* n walks of walk_length = L >= 1 steps whose step depends on the previous node. Tensors and dtypes, memory types and
+ * locations, the outputs walks [n, L + 1] and edge_ids [n, L] with -1 behind a walk's end, when a step is not taken, and the
+ * random streams are as (2m), word for word; wm_csr_weight_ptr_tensor may be NULL, and then every edge has weight 1.0f. One
+ * launch on `stream`; nothing is allocated, nothing is read back and the call does not synchronise. Only the step rule is new.
+ *
+ * Step rule. inv_p = 1.0f / p and inv_q = 1.0f / q, one fp32 division each, done on the host. At step t of walk w the walker
+ * stands on v; the previous node is u = walks[w, t - 1] for t >= 1, and there is none at t = 0. Neighbour j of v is
+ * x = col_ind[row_ptr[v] + j]. Its bias a is
+ *   - 1.0f at t = 0;
+ *   - else inv_p when x == u;
+ *   - else 1.0f when x occurs in col_ind[row_ptr[u] : row_ptr[u + 1]];
+ *   - else inv_q.
+ * Only ids are compared: x is never used as an index before it is chosen and range-checked, so a damaged col_ind entry gets
+ * some class and causes no out-of-bounds read. The effective weight is ew = w32 * a, a single fp32 multiply with no
+ * contraction, w32 the edge weight converted to fp32 (1.0f without a weight tensor). Neighbour j is eligible when ew > 0; its
+ * key is the A-Res key of (2m) from stream(seed, w * L + t, j + 1) with ew as the weight, log2(u) * (1.0f / ew). The chosen
+ * neighbour is the eligible j with the largest key in an fp32 `>` comparison; ties go to the lowest j.
+ *
+ * Two consequences. With p = q = 1, ew == w32 bit for bit, and the walks equal wholememory_ext_csr_random_walk with the same
+ * weight tensor. Without a weight tensor, p = q = 1 gives the walks that wholememory_ext_csr_random_walk gives over a
+ * weight tensor of ones.
+ *
+ * The result depends on (seed, w, t, j) and the graph only: not on n, not on the launch geometry, and not on which search
+ * route answered the adjacency question.
+ *
+ * col_sorted. 0: the rows of col_ind may be in any order; membership in u's row is found by scanning it, which is right on
+ * every graph and costs deg(u) compares per neighbour. Non-zero: the caller promises that every row of col_ind is ascending,
+ * and membership is found by a binary search. On a graph whose rows are ascending both settings give identical outputs. If
+ * the promise is broken the walks still only follow edges and nothing is read out of bounds, but the class of a neighbour
+ * is not specified.
+ *
+ * Errors, all answered before any device work: everything (2m) lists, unchanged; INVALID_INPUT unless p, q, 1.0f / p and
+ * 1.0f / q are all finite and > 0 (that refuses 0, negatives, NaN, inf, and a subnormal p or q whose reciprocal overflows);
+ * NOT_IMPLEMENTED for a DISTRIBUTED tensor; NOT_SUPPORTED, nothing queued, when the device backend has no such kernel.
+ * n = 0 succeeds and queues nothing. */
+enum wholememory_error_code_t wholememory_ext_csr_node2vec_walk(wholememory_tensor_t wm_csr_row_ptr_tensor,
+                                                                wholememory_tensor_t wm_csr_col_ptr_tensor,
+                                                                wholememory_tensor_t wm_csr_weight_ptr_tensor, /* NULL: 1.0f */
+                                                                wholememory_tensor_t start_nodes_tensor,
+                                                                int walk_length,
+                                                                float p,
+                                                                float q,
+                                                                int col_sorted,
+                                                                unsigned long long random_seed,
+                                                                wholememory_tensor_t output_walks_tensor,
+                                                                wholememory_tensor_t output_edge_ids_tensor, /* may be NULL */
+                                                                void* stream);
 
 /* ---- (3) testing seam ---------------------------------------------------------------------- */
 /* Replaces the device backend. Refuses (WHOLEMEMORY_NOT_SUPPORTED) unless the environment has

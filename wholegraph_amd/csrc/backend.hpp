@@ -449,6 +449,14 @@ struct wm_walk_args {
   int64_t* out_edge_ids;  // [n, walk_length] or nullptr
 };
 
+// node2vec second-order walks (kernels/walk_n2v.hip, wholegraph_amd_ext.h section 2n): the arguments of a walk (weight_dtype
+// WHOLEMEMORY_DT_UNKNOWN and an empty weight_gref: every edge has weight 1.0f) and the step rule's own
+struct wm_n2v_args {
+  wm_walk_args walk;
+  float inv_p, inv_q;  // 1.0f / p, 1.0f / q: finite and > 0
+  int col_sorted;      // non-zero: every row of csr_col_ptr is ascending (the caller's promise)
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -721,6 +729,8 @@ struct wm_device_backend {
   // ---- random walks (kernels/walk.hip, wholegraph_amd_ext.h section 2m); nullptr in a backend without them ----
   int (*walk_uniform)(const wm_walk_args* a, void* stream);
   int (*walk_weighted)(const wm_walk_args* a, void* stream);
+  // ---- node2vec (p, q) walks (kernels/walk_n2v.hip, wholegraph_amd_ext.h section 2n); nullptr in a backend without them ----
+  int (*walk_node2vec)(const wm_n2v_args* a, void* stream);
 };
 
 }  // extern "C"

@@ -20,6 +20,7 @@
 #include "knobs.hpp"
 #include "ops_internal.hpp"
 #include "pcg.hpp"
+#include "walk_n2v.hpp"
 
 namespace {
 
@@ -271,19 +272,27 @@ wholememory_error_code_t wholegraph_csr_weighted_sample_without_replacement(
   WM_API_END
 }
 
-// Random walks (extension, wholegraph_amd_ext.h section 2m; kernels/walk.hip): n walks of walk_length steps as ONE launch on
-// `stream`. The outputs are the caller's, their sizes known beforehand: nothing is allocated, nothing read back, the call
-// does not synchronise, and every answer but SUCCESS is given before any device work.
-wholememory_error_code_t wholememory_ext_csr_random_walk(
-  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor,
-  wholememory_tensor_t wm_csr_weight_ptr_tensor, wholememory_tensor_t start_nodes_tensor, int walk_length,
-  unsigned long long random_seed, wholememory_tensor_t output_walks_tensor, wholememory_tensor_t output_edge_ids_tensor,
-  void* stream)
+// Random walks (extension, wholegraph_amd_ext.h sections 2m and 2n; kernels/walk.hip, kernels/walk_n2v.hip): n walks of
+// walk_length steps as ONE launch on `stream`. The outputs are the caller's, their sizes known beforehand: nothing is
+// allocated, nothing read back, the call does not synchronise, and every answer but SUCCESS is given before any device work.
+namespace {
+
+// one call's tensors: check() answers what section 2m lists, in its order, and touches no device; fill() maps the graph
+// tensors and fills the backend's argument block
+struct walk_call {
+  wholememory_tensor_t wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_weight_ptr_tensor, start_nodes_tensor;
+  int walk_length;
+  wholememory_tensor_t output_walks_tensor, output_edge_ids_tensor;
+  wholememory_array_description_t row_desc, col_desc, start_desc, weight_desc;
+
+  wholememory_error_code_t check();
+  wholememory_error_code_t fill(unsigned long long random_seed, wm_walk_args& a) const;
+};
+
+wholememory_error_code_t walk_call::check()
 {
-  WM_API_BEGIN
   if (output_walks_tensor == nullptr) return WHOLEMEMORY_INVALID_INPUT;
   wholememory_error_code_t err = WHOLEMEMORY_SUCCESS;
-  wholememory_array_description_t row_desc, col_desc, start_desc;
   if (!array_of(wm_csr_row_ptr_tensor, "wm_csr_row_ptr_tensor", &row_desc, &err)) return err;
   if (!array_of(wm_csr_col_ptr_tensor, "wm_csr_col_ptr_tensor", &col_desc, &err)) return err;
   if (!array_of(start_nodes_tensor, "start_nodes_tensor", &start_desc, &err)) return err;
@@ -308,7 +317,7 @@ wholememory_error_code_t wholememory_ext_csr_random_walk(
     return WHOLEMEMORY_INVALID_INPUT;
   }
   const bool weighted = wm_csr_weight_ptr_tensor != nullptr;
-  wholememory_array_description_t weight_desc{};
+  weight_desc         = wholememory_array_description_t{};
   if (weighted) {
     if (!array_of(wm_csr_weight_ptr_tensor, "wm_csr_weight_ptr_tensor", &weight_desc, &err)) return err;
     if (weight_desc.size != col_desc.size) {
@@ -352,10 +361,14 @@ wholememory_error_code_t wholememory_ext_csr_random_walk(
       return WHOLEMEMORY_NOT_IMPLEMENTED;
     }
   }
-  const auto* bk = backend();
-  if (bk->walk_uniform == nullptr || bk->walk_weighted == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
-  if (n == 0) return WHOLEMEMORY_SUCCESS;
-  wm_walk_args a{};
+  return WHOLEMEMORY_SUCCESS;
+}
+
+wholememory_error_code_t walk_call::fill(unsigned long long random_seed, wm_walk_args& a) const
+{
+  const bool weighted = wm_csr_weight_ptr_tensor != nullptr;
+  const int64_t n     = start_desc.size;
+  a                   = wm_walk_args{};
   WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_row_ptr_tensor, &a.row_gref));
   WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_col_ptr_tensor, &a.col_gref));
   a.row_storage_offset = row_desc.storage_offset;
@@ -379,7 +392,57 @@ wholememory_error_code_t wholememory_ext_csr_random_walk(
                      : nullptr;
   if (a.starts == nullptr || a.out_walks == nullptr || (output_edge_ids_tensor != nullptr && a.out_edge_ids == nullptr))
     return WHOLEMEMORY_INVALID_INPUT;
-  WM_BK(weighted ? bk->walk_weighted(&a, stream) : bk->walk_uniform(&a, stream));
+  return WHOLEMEMORY_SUCCESS;
+}
+
+}  // namespace
+
+wholememory_error_code_t wholememory_ext_csr_random_walk(
+  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor,
+  wholememory_tensor_t wm_csr_weight_ptr_tensor, wholememory_tensor_t start_nodes_tensor, int walk_length,
+  unsigned long long random_seed, wholememory_tensor_t output_walks_tensor, wholememory_tensor_t output_edge_ids_tensor,
+  void* stream)
+{
+  WM_API_BEGIN
+  walk_call c{wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_weight_ptr_tensor, start_nodes_tensor, walk_length,
+              output_walks_tensor, output_edge_ids_tensor};
+  WHOLEMEMORY_RETURN_ON_FAIL(c.check());
+  const auto* bk = backend();
+  if (bk->walk_uniform == nullptr || bk->walk_weighted == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  if (c.start_desc.size == 0) return WHOLEMEMORY_SUCCESS;
+  wm_walk_args a;
+  WHOLEMEMORY_RETURN_ON_FAIL(c.fill(random_seed, a));
+  WM_BK(wm_csr_weight_ptr_tensor != nullptr ? bk->walk_weighted(&a, stream) : bk->walk_uniform(&a, stream));
+  if (debug_sync_enabled()) WM_BK(bk->stream_sync(stream));
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+// node2vec (p, q) walks (section 2n): the tensors of section 2m, checked by the same code, and the step rule's own arguments
+wholememory_error_code_t wholememory_ext_csr_node2vec_walk(
+  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor,
+  wholememory_tensor_t wm_csr_weight_ptr_tensor, wholememory_tensor_t start_nodes_tensor, int walk_length,
+  float p, float q, int col_sorted, unsigned long long random_seed, wholememory_tensor_t output_walks_tensor,
+  wholememory_tensor_t output_edge_ids_tensor, void* stream)
+{
+  WM_API_BEGIN
+  walk_call c{wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_weight_ptr_tensor, start_nodes_tensor, walk_length,
+              output_walks_tensor, output_edge_ids_tensor};
+  WHOLEMEMORY_RETURN_ON_FAIL(c.check());
+  if (!wm::n2v_pq_ok(p, q)) {
+    WM_ERROR("p and q and their fp32 reciprocals must be finite and > 0, got p = %g, q = %g", static_cast<double>(p),
+             static_cast<double>(q));
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  const auto* bk = backend();
+  if (bk->walk_node2vec == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  if (c.start_desc.size == 0) return WHOLEMEMORY_SUCCESS;
+  wm_n2v_args a;
+  WHOLEMEMORY_RETURN_ON_FAIL(c.fill(random_seed, a.walk));
+  a.inv_p      = 1.0f / p;
+  a.inv_q      = 1.0f / q;
+  a.col_sorted = col_sorted;
+  WM_BK(bk->walk_node2vec(&a, stream));
   if (debug_sync_enabled()) WM_BK(bk->stream_sync(stream));
   return WHOLEMEMORY_SUCCESS;
   WM_API_END

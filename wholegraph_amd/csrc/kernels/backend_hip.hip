@@ -113,6 +113,7 @@ int hip_pna_backward(const wm_pna_args* a, const int32_t* order, const int32_t* 
                      const int64_t* n_unique_dev, void* workspace, void* stream);
 int hip_walk_uniform(const wm_walk_args* a, void* stream);
 int hip_walk_weighted(const wm_walk_args* a, void* stream);
+int hip_walk_node2vec(const wm_n2v_args* a, void* stream);
 
 namespace {
 
@@ -314,6 +315,7 @@ const wm_device_backend kHipBackend = {
   hip_pna_backward,
   hip_walk_uniform,
   hip_walk_weighted,
+  hip_walk_node2vec,
 };
 
 }  // namespace

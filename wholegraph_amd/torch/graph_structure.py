@@ -155,6 +155,17 @@ class GraphStructure(object):
                                           random_seed, wm_csr_weight_ptr_tensor=self._weights(weight_name),
                                           need_edge_output=need_edge_ids)
 
+    def node2vec_walk(self, start_nodes: torch.Tensor, walk_length: int, p: float, q: float, *,
+                      weight_name: Optional[str] = None, random_seed: Union[int, None] = None, col_sorted: bool = False,
+                      need_edge_ids: bool = False):
+        """Extension: one node2vec (p, q) walk of walk_length steps from every start node, all of them in one launch
+        (``wholegraph_ops.node2vec_walk``). -> walks [n, walk_length + 1][, edge_ids int64 [n, walk_length]]; -1 from the step
+        at which a walk ends. weight_name: the named edge attribute weighs the edges (else every edge weighs 1). col_sorted:
+        the caller's promise that every row of csr_col_ind is ascending."""
+        return wholegraph_ops.node2vec_walk(self.csr_row_ptr.wmb_tensor, self.csr_col_ind.wmb_tensor, start_nodes, walk_length,
+                                            p, q, random_seed, wm_csr_weight_ptr_tensor=self._weights(weight_name),
+                                            col_sorted=col_sorted, need_edge_output=need_edge_ids)
+
     # ------------------------------------------------------------------------------------------ several hops
     def multilayer_sample_without_replacement(self, node_ids: torch.Tensor, max_neighbors: List[int],
                                               weight_name: Union[str, None] = None, *,

@@ -4,6 +4,7 @@ Mirror of ``python/pylibwholegraph/pylibwholegraph/torch/wholegraph_ops.py:27-20
 ``include/wholememory/wholegraph_op.h``. `wm_csr_*_tensor` arguments are `wholememory_tensor_t` handles
 (``WholeMemoryTensor.wmb_tensor``), exactly what the reference functions take."""
 import ctypes as C
+import math
 import random
 from typing import Union
 
@@ -316,6 +317,39 @@ def random_walk(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, start_nodes_tensor
     wmb.check(wmb.lib().wholememory_ext_csr_random_walk(
         row, col, wgt, ws.handle, steps, C.c_ulonglong(random_seed & 0xFFFFFFFFFFFFFFFF), ww.handle,
         we.handle if we is not None else None, C.c_void_p(get_stream())))
+    return (walks, edge_ids) if need_edge_output else walks
+
+
+def node2vec_walk(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, start_nodes_tensor: torch.Tensor, walk_length: int, p: float,
+                  q: float, random_seed: Union[int, None] = None, *, wm_csr_weight_ptr_tensor=None, col_sorted: bool = False,
+                  need_edge_output: bool = False):
+    """Extension (wholememory_ext_csr_node2vec_walk, include/wholememory/wholegraph_amd_ext.h section 2n): one node2vec walk
+    of `walk_length` steps from every start node, as ONE launch with no host round trip. Outputs as `random_walk`. From the
+    second step on, the weight of a neighbour x of the current node (1 without wm_csr_weight_ptr_tensor) is multiplied by
+    1 / p when x is the previous node, by 1 when x is a neighbour of the previous node, and by 1 / q otherwise; p = q = 1 gives
+    the walks of `random_walk` with the same weights. col_sorted=True promises that every row of csr_col_ptr is ascending,
+    and the neighbour test becomes a binary search instead of a scan of the previous node's row."""
+    if int(walk_length) < 1:
+        raise ValueError("walk_length must be at least 1, got %r" % (walk_length,))
+    if start_nodes_tensor.dim() != 1:
+        raise ValueError("start_nodes_tensor must be 1-D, got %d dimensions" % start_nodes_tensor.dim())
+    for name, value in (("p", p), ("q", q)):
+        if not (math.isfinite(float(value)) and float(value) > 0):
+            raise ValueError("%s must be finite and positive, got %r" % (name, value))
+    row, col = _handle(wm_csr_row_ptr_tensor), _handle(wm_csr_col_ptr_tensor)
+    wgt = None if wm_csr_weight_ptr_tensor is None else _handle(wm_csr_weight_ptr_tensor)
+    if random_seed is None:
+        random_seed = random.getrandbits(64)
+    n, steps = start_nodes_tensor.shape[0], int(walk_length)
+    col_dtype = wholememory_dtype_to_torch_dtype(wmb.lib().wholememory_tensor_get_tensor_description(col).contents.dtype)
+    walks = torch.empty((n, steps + 1), device=op_device(), dtype=col_dtype)
+    edge_ids = torch.empty((n, steps), device=op_device(), dtype=torch.int64) if need_edge_output else None
+    ws, ww = wrap_torch_tensor(start_nodes_tensor), wrap_torch_tensor(walks)
+    we = wrap_torch_tensor(edge_ids) if need_edge_output else None
+    wmb.check(wmb.lib().wholememory_ext_csr_node2vec_walk(
+        row, col, wgt, ws.handle, steps, C.c_float(float(p)), C.c_float(float(q)), 1 if col_sorted else 0,
+        C.c_ulonglong(random_seed & 0xFFFFFFFFFFFFFFFF), ww.handle, we.handle if we is not None else None,
+        C.c_void_p(get_stream())))
     return (walks, edge_ids) if need_edge_output else walks
 
 

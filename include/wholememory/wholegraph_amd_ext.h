@@ -300,6 +300,13 @@ int64_t wholememory_ext_host_sorted_gathers(void);
  * is decided on the device and not visible here. A counter for tests and benchmarks. */
 int64_t wholememory_ext_split_sorts(void);
 
+/* Kernel launches of this process since the last call whose grid was sized by the block ops' shared helper (blocks_for() of
+ * csrc/kernels/agg_common.cuh: the agg_concat family, agg_concat_pna, the attention ops and their shared backward walk), and
+ * how many of them wanted more workgroups than the cap allowed and so run their grid-stride loop more than once
+ * ("truncated"). The cap is 2^20 workgroups, or min(WM_AGG_MAX_BLOCKS, 2^20) when that knob is a positive integer. Either
+ * pointer may be NULL. Reading resets both counters. A counter for tests. */
+void wholememory_ext_agg_grid_stats(int64_t* launches, int64_t* truncated);
+
 /* Duplicate runs of the last finished ORDERED gradient step on the current device that were summed through a dense transposed
  * copy of their gradient rows (csrc/kernels/long_dense.cuh: runs of at least WM_DENSE_FOLD_MIN rows, default 131072, while
  * 3 n / 8 rows of copies last; WM_DENSE_FOLD=0 switches the route off). Read after a synchronise. A counter for tests. */

@@ -8,10 +8,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <atomic>
+#include <cstdlib>
+
 #include "../backend.hpp"
 #include "../csc_workspace.hpp"
+#include "../knobs.hpp"
 
 namespace wm {
+
+extern std::atomic<int64_t> g_agg_grid_launches, g_agg_grid_truncated;   // wm_common.cpp: bumped by blocks_for()
 
 // index of the per-source backward: the id sort's outputs and what the prep kernel derives from them (in the op's workspace)
 struct csc_bwd_index {
@@ -252,11 +258,29 @@ __device__ __forceinline__ fvec<VEC> with_self_term(const fvec<VEC>& acc, bool h
 
 int rc_last() { return hipGetLastError() == hipSuccess ? 0 : -2; }
 
+// the most workgroups of a launch: kAggMaxBlocks, or min(WM_AGG_MAX_BLOCKS, kAggMaxBlocks) when that knob is a positive
+// integer. The knob exists for tests: with a cap of a few blocks a small CSC block runs the later trips of every grid-stride
+// loop. Unset (every launch of a normal process) this is one pointer test.
+int64_t agg_max_blocks()
+{
+  const char* s = WM_KNOB("WM_AGG_MAX_BLOCKS");
+  if (s == nullptr) return kAggMaxBlocks;
+  char* end         = nullptr;
+  const long long v = strtoll(s, &end, 10);
+  if (end == s || *end != '\0' || v < 1) return kAggMaxBlocks;
+  return v < kAggMaxBlocks ? static_cast<int64_t>(v) : kAggMaxBlocks;
+}
+
+// workgroups for `groups` units of work at `groups_per_block` a block, at most agg_max_blocks(): every kernel launched with
+// this grid strides over its work by the grid. Counted for wholememory_ext_agg_grid_stats.
 int blocks_for(int64_t groups, int groups_per_block)
 {
   int64_t n = (groups + groups_per_block - 1) / groups_per_block;
   if (n < 1) n = 1;
-  return static_cast<int>(n < kAggMaxBlocks ? n : kAggMaxBlocks);
+  const int64_t cap = agg_max_blocks();
+  g_agg_grid_launches.fetch_add(1, std::memory_order_relaxed);
+  if (n > cap) g_agg_grid_truncated.fetch_add(1, std::memory_order_relaxed);
+  return static_cast<int>(n < cap ? n : cap);
 }
 
 // 16-byte pieces when every row start is 16-byte aligned; group width from the number of pieces (or floats) of a row

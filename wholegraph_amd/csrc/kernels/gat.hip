@@ -204,14 +204,15 @@ __global__ __launch_bounds__(kAggBlock) void gat_att_chunk_kernel(wm_gat_args p,
 __global__ __launch_bounds__(kAggBlock) void gat_att_fold_kernel(wm_gat_args p, wm_gat_bwd_state b)
 {
   const int64_t HF = p.heads * p.dim, W = 2 * HF;
-  const int64_t c = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (c >= W) return;
-  const int64_t rows = c >= HF ? p.n_dst : p.n_src;
-  const int64_t nq   = (rows + kGatNodeChunk - 1) / kGatNodeChunk;
-  float acc          = -0.0f;
+  for (int64_t c = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; c < W;
+       c += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    const int64_t rows = c >= HF ? p.n_dst : p.n_src;
+    const int64_t nq   = (rows + kGatNodeChunk - 1) / kGatNodeChunk;
+    float acc          = -0.0f;
 #pragma unroll 8
-  for (int64_t q = 0; q < nq; ++q) acc = acc + b.att_partial[q * W + c];
-  p.grad_att[c] = nq > 0 ? acc : 0.0f;
+    for (int64_t q = 0; q < nq; ++q) acc = acc + b.att_partial[q * W + c];
+    p.grad_att[c] = nq > 0 ? acc : 0.0f;
+  }
 }
 
 }  // namespace

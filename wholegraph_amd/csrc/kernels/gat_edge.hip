@@ -123,12 +123,13 @@ __global__ __launch_bounds__(kAggBlock) void gat_edge_att_fold_kernel(wm_gat_edg
                                                                       int64_t n_chunks)
 {
   const int64_t HF = pe.g.heads * pe.g.dim;
-  const int64_t c  = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (c >= HF) return;
-  float acc = -0.0f;
+  for (int64_t c = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; c < HF;
+       c += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    float acc = -0.0f;
 #pragma unroll 8
-  for (int64_t q = 0; q < n_chunks; ++q) acc = acc + partial[q * HF + c];
-  pe.g.grad_att[2 * HF + c] = n_chunks > 0 ? acc : 0.0f;
+    for (int64_t q = 0; q < n_chunks; ++q) acc = acc + partial[q * HF + c];
+    pe.g.grad_att[2 * HF + c] = n_chunks > 0 ? acc : 0.0f;
+  }
 }
 
 int64_t edge_chunks(const wm_gat_args* a) { return (a->n_edges + kGatNodeChunk - 1) / kGatNodeChunk; }

@@ -264,12 +264,13 @@ __global__ __launch_bounds__(kAggBlock) void gatv2_att_chunk_kernel(wm_gatv2_arg
 __global__ __launch_bounds__(kAggBlock) void gatv2_att_fold_kernel(wm_gatv2_args p, gatv2_bwd_state b)
 {
   const int64_t HF = p.heads * p.dim;
-  const int64_t c  = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-  if (c >= HF) return;
-  float acc = -0.0f;
+  for (int64_t c = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x; c < HF;
+       c += static_cast<int64_t>(gridDim.x) * blockDim.x) {
+    float acc = -0.0f;
 #pragma unroll 8
-  for (int64_t q = 0; q < b.n_node_chunks; ++q) acc = acc + b.att_partial[q * HF + c];
-  p.grad_att[c] = b.n_node_chunks > 0 ? acc : 0.0f;
+    for (int64_t q = 0; q < b.n_node_chunks; ++q) acc = acc + b.att_partial[q * HF + c];
+    p.grad_att[c] = b.n_node_chunks > 0 ? acc : 0.0f;
+  }
 }
 
 __global__ __launch_bounds__(kAggBlock) void gatv2_bwd_prep_kernel(wm_gatv2_args p, gatv2_bwd_state b)

@@ -16,6 +16,9 @@ namespace wm {
 
 std::atomic<unsigned> g_knob_generation{0};
 std::mutex g_knob_mutex;
+// launches sized by blocks_for() (kernels/agg_common.cuh) and those of them whose grid the cap cut short
+std::atomic<int64_t> g_agg_grid_launches{0};
+std::atomic<int64_t> g_agg_grid_truncated{0};
 
 namespace {
 std::mutex g_gref_mu;
@@ -111,6 +114,14 @@ extern "C" wholememory_error_code_t wholememory_ext_reload_knobs()
 {
   wm::reload_knobs();
   return WHOLEMEMORY_SUCCESS;
+}
+
+extern "C" void wholememory_ext_agg_grid_stats(int64_t* launches, int64_t* truncated)
+{
+  const int64_t l = wm::g_agg_grid_launches.exchange(0, std::memory_order_relaxed);
+  const int64_t t = wm::g_agg_grid_truncated.exchange(0, std::memory_order_relaxed);
+  if (launches != nullptr) *launches = l;
+  if (truncated != nullptr) *truncated = t;
 }
 
 extern "C" wholememory_error_code_t wholememory_ext_set_async_completion(int on)

@@ -29,6 +29,7 @@
  *      and std of the neighbour rows out of one read of them (forward and a deterministic backward).
  *      (2m) random walks over a CSR graph held in WholeMemory, uniform or by edge weight, as one launch for the whole batch.
  *      (2n) node2vec (p, q) second-order walks over the same graph, with or without edge weights, as one launch.
+ *      (2o) negative sampling over the same graph: per source node, K nodes that are not its neighbours, as one launch.
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -1215,6 +1216,54 @@ enum wholememory_error_code_t wholememory_ext_csr_node2vec_walk(wholememory_tens
                                                                 wholememory_tensor_t output_walks_tensor,
                                                                 wholememory_tensor_t output_edge_ids_tensor, /* may be NULL */
                                                                 void* stream);
+
+/* ---- (2o) negative sampling over a CSR graph held in WholeMemory ---------------------------------------------------------- */
+/* For each of n source nodes, num_negatives = K nodes drawn at random that are not the source and not in its row — the
+ * negatives of skip-gram training over the walks above, and of link prediction. Graph tensors are as (2m): row_ptr int64
+ * [n_nodes + 1], col_ind int32 or int64 [n_edges], both CONTINUOUS or CHUNKED, in device or host memory, or plain device
+ * arrays wrapped with wholememory_make_tensor_from_pointer. src_nodes is int32 or int64 [n], on the device.
+ * output_negatives is [n, K] in col_ind's dtype, given as 2-D or as 1-D with n * K entries. One launch on `stream`; nothing
+ * is allocated, nothing is read back and the call does not synchronise.
+ *
+ * Sample (i, k), with source u = src_nodes[i]. Its generator is stream(seed, i * K + k, 0) of (2m). Attempt a (0-based,
+ * a < max_tries = T) uses r, the a-th 64-bit draw of that generator, made of two 32-bit outputs, low word first, as
+ * pcg32::next_u64 does; attempt a takes that draw whether or not earlier attempts were rejected. The candidate c is
+ *   - mode 0 (uniform): c = (r * n_nodes) >> 64, a 128-bit product;
+ *   - mode 1 (by degree): pos = (r * n_edges) >> 64 and c = col_ind[pos], so that a node is drawn in proportion to how often
+ *     it occurs in col_ind. With n_edges = 0 every attempt is rejected.
+ * Attempt a is rejected when
+ *   - c is outside [0, n_nodes) (a damaged col_ind entry), or
+ *   - exclude & 2 is set and c == u, or
+ *   - exclude & 1 is set and c occurs in col_ind[row_ptr[u] : row_ptr[u + 1]].
+ * The first attempt that is not rejected is the output; if all T attempts are rejected the output is -1. All K outputs of a
+ * source are -1 when u is outside [0, n_nodes). A source whose row bounds are not a valid row excludes no edge; a row is valid
+ * when 0 <= s <= e <= n_edges and e - s < 2^31. Samples are drawn with replacement: the K negatives of one source may repeat.
+ *
+ * col_sorted. 0: the rows of col_ind may be in any order; membership in u's row is found by scanning it, which is right on
+ * every graph. Non-zero: the caller promises that every row of col_ind is ascending, and membership is found by a binary
+ * search. On a graph whose rows are ascending both settings give identical outputs. If the promise is broken nothing is read
+ * outside the row, but the class of a candidate is not specified. Only ids are compared: a candidate is never used as an
+ * index before it is range-checked.
+ *
+ * The result depends on (seed, i, k, a), K and the graph only: not on n, not on the launch geometry, and not on which search
+ * route answered.
+ *
+ * Errors, all answered before any device work. INVALID_INPUT: a NULL row_ptr, col_ind, src_nodes or output; one of the first
+ * three not 1-D; num_negatives < 1; max_tries outside [1, 64]; mode not 0 or 1; exclude outside [0, 3]; n * K >= 2^31; an
+ * output of the wrong size; a HIERARCHY tensor. LOGIC_ERROR, the dtype cases of (2m): row_ptr not int64, col_ind or src_nodes
+ * not int32 / int64, the output not in col_ind's dtype. NOT_IMPLEMENTED for a DISTRIBUTED tensor. NOT_SUPPORTED, nothing
+ * queued, when the device backend has no such kernel. n = 0 succeeds and queues nothing. */
+enum wholememory_error_code_t wholememory_ext_csr_negative_sample(wholememory_tensor_t wm_csr_row_ptr_tensor,
+                                                                  wholememory_tensor_t wm_csr_col_ptr_tensor,
+                                                                  wholememory_tensor_t src_nodes_tensor,
+                                                                  int num_negatives,
+                                                                  int mode,    /* 0: uniform, 1: by degree */
+                                                                  int exclude, /* bit 0: neighbours, bit 1: the source */
+                                                                  int max_tries,
+                                                                  int col_sorted,
+                                                                  unsigned long long random_seed,
+                                                                  wholememory_tensor_t output_negatives_tensor,
+                                                                  void* stream);
 
 /* ---- (3) testing seam ---------------------------------------------------------------------- */
 /* Replaces the device backend. Refuses (WHOLEMEMORY_NOT_SUPPORTED) unless the environment has

@@ -457,6 +457,25 @@ struct wm_n2v_args {
   int col_sorted;      // non-zero: every row of csr_col_ptr is ascending (the caller's promise)
 };
 
+// negative sampling over the same kind of graph (kernels/neg_sample.hip, wholegraph_amd_ext.h section 2o). One launch; nothing
+// is allocated and nothing read back
+struct wm_neg_args {
+  wholememory_gref_t row_gref, col_gref;  // csr_row_ptr (int64), csr_col_ptr (col_dtype)
+  int64_t row_storage_offset, col_storage_offset;  // elements
+  wholememory_dtype_t col_dtype;
+  int64_t n_nodes, n_edges;
+  const void* src;      // [n] device
+  wholememory_dtype_t src_dtype;
+  int64_t n;            // sources; n * num_negatives < 2^31
+  int num_negatives;    // >= 1
+  int mode;             // 0: uniform over the nodes; 1: by how often a node occurs in csr_col_ptr
+  int exclude;          // bit 0: the source's neighbours; bit 1: the source itself
+  int max_tries;        // 1 .. 64
+  int col_sorted;       // non-zero: every row of csr_col_ptr is ascending (the caller's promise)
+  uint64_t random_seed;
+  void* out;            // [n, num_negatives] col_dtype
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -731,6 +750,8 @@ struct wm_device_backend {
   int (*walk_weighted)(const wm_walk_args* a, void* stream);
   // ---- node2vec (p, q) walks (kernels/walk_n2v.hip, wholegraph_amd_ext.h section 2n); nullptr in a backend without them ----
   int (*walk_node2vec)(const wm_n2v_args* a, void* stream);
+  // ---- negative sampling (kernels/neg_sample.hip, wholegraph_amd_ext.h section 2o); nullptr in a backend without it ----
+  int (*negative_sample)(const wm_neg_args* a, void* stream);
 };
 
 }  // extern "C"

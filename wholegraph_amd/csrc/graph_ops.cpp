@@ -18,6 +18,7 @@
 #include <wholememory/wholememory_op.h>
 
 #include "knobs.hpp"
+#include "neg_sample.hpp"
 #include "ops_internal.hpp"
 #include "pcg.hpp"
 #include "walk_n2v.hpp"
@@ -443,6 +444,95 @@ wholememory_error_code_t wholememory_ext_csr_node2vec_walk(
   a.inv_q      = 1.0f / q;
   a.col_sorted = col_sorted;
   WM_BK(bk->walk_node2vec(&a, stream));
+  if (debug_sync_enabled()) WM_BK(bk->stream_sync(stream));
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+// Negative sampling (extension, wholegraph_amd_ext.h section 2o; kernels/neg_sample.hip): num_negatives nodes per source that
+// are not the source and not in its row, as ONE launch on `stream`. The output is the caller's: nothing is allocated, nothing
+// read back, the call does not synchronise, and every answer but SUCCESS is given before any device work.
+wholememory_error_code_t wholememory_ext_csr_negative_sample(
+  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor, wholememory_tensor_t src_nodes_tensor,
+  int num_negatives, int mode, int exclude, int max_tries, int col_sorted, unsigned long long random_seed,
+  wholememory_tensor_t output_negatives_tensor, void* stream)
+{
+  WM_API_BEGIN
+  if (output_negatives_tensor == nullptr) return WHOLEMEMORY_INVALID_INPUT;
+  wholememory_error_code_t err = WHOLEMEMORY_SUCCESS;
+  wholememory_array_description_t row_desc, col_desc, src_desc;
+  if (!array_of(wm_csr_row_ptr_tensor, "wm_csr_row_ptr_tensor", &row_desc, &err)) return err;
+  if (!array_of(wm_csr_col_ptr_tensor, "wm_csr_col_ptr_tensor", &col_desc, &err)) return err;
+  if (!array_of(src_nodes_tensor, "src_nodes_tensor", &src_desc, &err)) return err;
+  if (!wm::neg_scalars_ok(num_negatives, mode, exclude, max_tries)) {
+    WM_ERROR("num_negatives must be >= 1, mode 0 or 1, exclude in [0, 3] and max_tries in [1, 64], got %d, %d, %d, %d",
+             num_negatives, mode, exclude, max_tries);
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  const int64_t n = src_desc.size, K = num_negatives;
+  if (n < 0 || row_desc.size < 1 || n > ((INT64_C(1) << 31) - 1) / K) {
+    WM_ERROR("%ld sources of %d negatives: the output must hold fewer than 2^31 entries", static_cast<long>(n), num_negatives);
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  // the output is the dense [n, K] block, given as a 2-D tensor of that shape or as a 1-D one of n * K entries
+  const auto out_desc = *wholememory_tensor_get_tensor_description(output_negatives_tensor);
+  const bool dense =
+    out_desc.dim == 1 ? out_desc.sizes[0] == n * K && (out_desc.strides[0] == 1 || out_desc.sizes[0] <= 1)
+                      : out_desc.dim == 2 && out_desc.sizes[0] == n && out_desc.sizes[1] == K && out_desc.strides[1] == 1 &&
+                          (out_desc.strides[0] == K || n <= 1);
+  if (!dense) {
+    WM_ERROR("output_negatives_tensor must be [%ld, %ld], dense", static_cast<long>(n), static_cast<long>(K));
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  // dtype rules, as the walks answer them
+  if (row_desc.dtype != WHOLEMEMORY_DT_INT64) {
+    WM_ERROR("wm_csr_row_ptr_tensor must be int64, got %d", static_cast<int>(row_desc.dtype));
+    return WHOLEMEMORY_LOGIC_ERROR;
+  }
+  if (!is_index_dtype(col_desc.dtype) || !is_index_dtype(src_desc.dtype)) {
+    WM_ERROR("source nodes and csr_col_ptr must be int32 or int64");
+    return WHOLEMEMORY_LOGIC_ERROR;
+  }
+  if (out_desc.dtype != col_desc.dtype) {
+    WM_ERROR("output_negatives_tensor must have the dtype of wm_csr_col_ptr_tensor");
+    return WHOLEMEMORY_LOGIC_ERROR;
+  }
+  const wholememory_tensor_t graph_tensors[2] = {wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor};
+  for (int i = 0; i < 2; i++) {
+    if (memory_type_of(graph_tensors[i]) == WHOLEMEMORY_MT_HIERARCHY) {
+      WM_ERROR("Memory type not supported.");
+      return WHOLEMEMORY_INVALID_INPUT;
+    }
+  }
+  for (int i = 0; i < 2; i++) {
+    if (memory_type_of(graph_tensors[i]) == WHOLEMEMORY_MT_DISTRIBUTED) {
+      WM_ERROR("negative sampling on DISTRIBUTED tensors is not implemented: every membership test would be a collective gather");
+      return WHOLEMEMORY_NOT_IMPLEMENTED;
+    }
+  }
+  const auto* bk = backend();
+  if (bk->negative_sample == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  if (n == 0) return WHOLEMEMORY_SUCCESS;
+  wm_neg_args a{};
+  WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_row_ptr_tensor, &a.row_gref));
+  WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_col_ptr_tensor, &a.col_gref));
+  a.row_storage_offset = row_desc.storage_offset;
+  a.col_storage_offset = col_desc.storage_offset;
+  a.col_dtype          = col_desc.dtype;
+  a.n_nodes            = row_desc.size - 1;
+  a.n_edges            = col_desc.size;
+  a.src                = wholememory_tensor_get_data_pointer(src_nodes_tensor);
+  a.src_dtype          = src_desc.dtype;
+  a.n                  = n;
+  a.num_negatives      = num_negatives;
+  a.mode               = mode;
+  a.exclude            = exclude;
+  a.max_tries          = max_tries;
+  a.col_sorted         = col_sorted;
+  a.random_seed        = random_seed;
+  a.out                = wholememory_tensor_get_data_pointer(output_negatives_tensor);
+  if (a.src == nullptr || a.out == nullptr) return WHOLEMEMORY_INVALID_INPUT;
+  WM_BK(bk->negative_sample(&a, stream));
   if (debug_sync_enabled()) WM_BK(bk->stream_sync(stream));
   return WHOLEMEMORY_SUCCESS;
   WM_API_END

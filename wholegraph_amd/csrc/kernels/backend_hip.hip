@@ -114,6 +114,7 @@ int hip_pna_backward(const wm_pna_args* a, const int32_t* order, const int32_t* 
 int hip_walk_uniform(const wm_walk_args* a, void* stream);
 int hip_walk_weighted(const wm_walk_args* a, void* stream);
 int hip_walk_node2vec(const wm_n2v_args* a, void* stream);
+int hip_negative_sample(const wm_neg_args* a, void* stream);
 
 namespace {
 
@@ -316,6 +317,7 @@ const wm_device_backend kHipBackend = {
   hip_walk_uniform,
   hip_walk_weighted,
   hip_walk_node2vec,
+  hip_negative_sample,
 };
 
 }  // namespace

@@ -166,6 +166,18 @@ class GraphStructure(object):
                                             p, q, random_seed, wm_csr_weight_ptr_tensor=self._weights(weight_name),
                                             col_sorted=col_sorted, need_edge_output=need_edge_ids)
 
+    def negative_sample(self, src_nodes: torch.Tensor, num_negatives: int, *, mode: str = "uniform", exclude_edges: bool = True,
+                        exclude_self: bool = True, max_tries: int = 8, random_seed: Union[int, None] = None,
+                        col_sorted: bool = False):
+        """Extension: num_negatives nodes per source node that are not its neighbours (exclude_edges) and not the node itself
+        (exclude_self), all of them in one launch (``wholegraph_ops.negative_sample``). -> [n, num_negatives] in csr_col_ind's
+        dtype; -1 where max_tries draws were all rejected or the source is not a node. mode: "uniform" over the nodes or
+        "degree", by how often a node occurs in csr_col_ind. col_sorted: the caller's promise that every row of csr_col_ind
+        is ascending."""
+        return wholegraph_ops.negative_sample(self.csr_row_ptr.wmb_tensor, self.csr_col_ind.wmb_tensor, src_nodes, num_negatives,
+                                              random_seed, mode=mode, exclude_edges=exclude_edges, exclude_self=exclude_self,
+                                              max_tries=max_tries, col_sorted=col_sorted)
+
     # ------------------------------------------------------------------------------------------ several hops
     def multilayer_sample_without_replacement(self, node_ids: torch.Tensor, max_neighbors: List[int],
                                               weight_name: Union[str, None] = None, *,

@@ -353,6 +353,39 @@ def node2vec_walk(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, start_nodes_tens
     return (walks, edge_ids) if need_edge_output else walks
 
 
+NEGATIVE_MODES = {"uniform": 0, "degree": 1}
+
+
+def negative_sample(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, src_nodes_tensor: torch.Tensor, num_negatives: int,
+                    random_seed: Union[int, None] = None, *, mode: str = "uniform", exclude_edges: bool = True,
+                    exclude_self: bool = True, max_tries: int = 8, col_sorted: bool = False):
+    """Extension (wholememory_ext_csr_negative_sample, include/wholememory/wholegraph_amd_ext.h section 2o): for every source
+    node `num_negatives` nodes that are not its neighbours (exclude_edges) and not the node itself (exclude_self), as ONE
+    launch with no host round trip -> [n, num_negatives] in csr_col_ptr's dtype. mode "uniform" draws over the nodes, "degree"
+    in proportion to how often a node occurs in csr_col_ptr. A sample takes at most `max_tries` (1 .. 64) draws and is -1 when
+    all were rejected, or when the source is not a node; samples are drawn with replacement. col_sorted=True promises that
+    every row of csr_col_ptr is ascending, and the neighbour test becomes a binary search instead of a scan of the row."""
+    if int(num_negatives) < 1:
+        raise ValueError("num_negatives must be at least 1, got %r" % (num_negatives,))
+    if not 1 <= int(max_tries) <= 64:
+        raise ValueError("max_tries must lie in 1 .. 64, got %r" % (max_tries,))
+    if mode not in NEGATIVE_MODES:
+        raise ValueError("mode must be one of %s, got %r" % (sorted(NEGATIVE_MODES), mode))
+    if src_nodes_tensor.dim() != 1:
+        raise ValueError("src_nodes_tensor must be 1-D, got %d dimensions" % src_nodes_tensor.dim())
+    row, col = _handle(wm_csr_row_ptr_tensor), _handle(wm_csr_col_ptr_tensor)
+    if random_seed is None:
+        random_seed = random.getrandbits(64)
+    n, k = src_nodes_tensor.shape[0], int(num_negatives)
+    col_dtype = wholememory_dtype_to_torch_dtype(wmb.lib().wholememory_tensor_get_tensor_description(col).contents.dtype)
+    negatives = torch.empty((n, k), device=op_device(), dtype=col_dtype)
+    ws, wn = wrap_torch_tensor(src_nodes_tensor), wrap_torch_tensor(negatives)
+    wmb.check(wmb.lib().wholememory_ext_csr_negative_sample(
+        row, col, ws.handle, k, NEGATIVE_MODES[mode], (1 if exclude_edges else 0) | (2 if exclude_self else 0), int(max_tries),
+        1 if col_sorted else 0, C.c_ulonglong(random_seed & 0xFFFFFFFFFFFFFFFF), wn.handle, C.c_void_p(get_stream())))
+    return negatives
+
+
 def generate_random_positive_int_cpu(random_seed, sub_sequence, output_random_value_count):
     output = torch.empty((output_random_value_count,), dtype=torch.int)
     w = wrap_torch_tensor(output)

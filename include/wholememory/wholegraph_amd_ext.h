@@ -356,8 +356,10 @@ int64_t wholememory_ext_combined_gradient_calls(void);
  *   part missing the other is copied, with neither the row is +0.0. C = wholememory_ext_csc_aggregate_chunk_edges(). The
  *   order is fixed: results are bitwise reproducible, no atomics. The edge index is built with the library's id sort, scratch
  *   from p_env_fns.
- * n_edges = 0 and n_dst = 0 are valid. INVALID_INPUT for null pointers, negative sizes, dim < 1, n_dst > n_src, strides
- * smaller than the row, an unknown aggr; NOT_SUPPORTED (nothing queued) when the device backend has no such kernels. */
+ * n_edges = 0 and n_dst = 0 are valid. INVALID_INPUT, before any device work and under every backend, for null pointers,
+ * negative sizes, dim < 1, n_dst > n_src, strides smaller than the row, an unknown aggr; then NOT_SUPPORTED (nothing queued)
+ * when the device backend has no such kernels. Every entry point over a sampled block (2b - 2l) answers in this order: the
+ * arguments are judged first, then the backend's capability, then (where there is a table) the table's memory type. */
 enum wholememory_ext_aggr_t {
   WHOLEMEMORY_EXT_AGGR_SUM  = 0,
   WHOLEMEMORY_EXT_AGGR_MEAN = 1,
@@ -470,8 +472,9 @@ enum wholememory_error_code_t wholememory_ext_csc_aggregate_backward_typed(const
  *   right, the chunk sums added in chunk order.
  *   The order is fixed: results are bitwise reproducible, no atomics. The edge index is built with the library's id sort,
  *   scratch from p_env_fns.
- * n_edges = 0 and n_dst = 0 are valid. INVALID_INPUT for null pointers, negative sizes, heads < 1, dim < 1, n_dst > n_src,
- * strides smaller than the row; NOT_SUPPORTED (nothing queued) when the device backend has no such kernels. */
+ * n_edges = 0 and n_dst = 0 are valid. INVALID_INPUT, before any device work and under every backend, for null pointers,
+ * negative sizes, heads < 1, dim < 1, n_dst > n_src, strides smaller than the row; then NOT_SUPPORTED (nothing queued) when
+ * the device backend has no such kernels. */
 enum wholememory_error_code_t wholememory_ext_csc_gat_forward(const int32_t* row_ptr,
                                                               const int32_t* col_ind,
                                                               int64_t n_edges,
@@ -536,8 +539,9 @@ int64_t wholememory_ext_csc_gat_node_chunk(void);
  * A NaN stays a NaN (payload not specified). No atomics; results are bitwise reproducible. The edge index of grad_x is
  * built with the library's id sort, scratch from p_env_fns.
  * grad_x or grad_w may be null (that gradient is then not computed, and nothing is queued for it); both null is
- * INVALID_INPUT. The backward reads x only for grad_w. n_edges = 0 and n_dst = 0 are valid. INVALID_INPUT for what (2b)
- * rejects and for a null w with n_edges > 0; NOT_SUPPORTED (nothing queued) when the device backend has no such kernels. */
+ * INVALID_INPUT. The backward reads x only for grad_w. n_edges = 0 and n_dst = 0 are valid. INVALID_INPUT, before any
+ * device work and under every backend, for what (2b) rejects and for a null w with n_edges > 0; then NOT_SUPPORTED (nothing
+ * queued) when the device backend has no such kernels. */
 enum wholememory_error_code_t wholememory_ext_csc_aggregate_weighted_forward(const int32_t* row_ptr,
                                                                              const int32_t* col_ind,
                                                                              const float* w,
@@ -587,9 +591,9 @@ enum wholememory_error_code_t wholememory_ext_csc_aggregate_weighted_backward(co
  * CONTINUOUS and CHUNKED tables (device- or host-located) and pointer-backed tensors are read through their global
  * reference, by the calling rank alone; DISTRIBUTED and HIERARCHY tables are NOT_SUPPORTED (nothing queued): gather, then
  * (2b). There is no backward entry point: the gradient with respect to x is wholememory_ext_csc_aggregate_backward.
- * INVALID_INPUT, before any device work, for what (2b) rejects and for a null table, a table that is not 2-D or whose dtype
+ * INVALID_INPUT, before any device work and under every backend, for what (2b) rejects and for a null table, a table that is not 2-D or whose dtype
  * is not FLOAT / HALF / BF16, a node_id_dtype other than INT / INT64, null node_ids with n_src > 0, out_stride < 2 * dim.
- * NOT_SUPPORTED (nothing queued) when the device backend has no such kernel. */
+ * Then NOT_SUPPORTED (nothing queued) when the device backend has no such kernel, then for a DISTRIBUTED or HIERARCHY table. */
 enum wholememory_error_code_t wholememory_ext_csc_gather_aggregate_forward(wholememory_tensor_t table,
                                                                            const void* node_ids,
                                                                            int node_id_dtype,
@@ -634,7 +638,8 @@ int64_t wholememory_ext_gather_aggregate_calls(void);
  * those of (2c) over att[0:2], bit for bit.
  * n_edges = 0 and n_dst = 0 are valid. INVALID_INPUT, before any device work, for everything (2c) rejects, for a null
  * edge_feat, edge_scores or grad_edge_feat with n_edges > 0 and n_dst > 0, and for an ef_stride or grad_ef_stride smaller
- * than H*F. NOT_SUPPORTED (nothing queued) when the device backend has no such kernels. */
+ * than H*F, all before any device work and under every backend; then NOT_SUPPORTED (nothing queued) when the device backend
+ * has no such kernels. */
 enum wholememory_error_code_t wholememory_ext_csc_gat_edge_forward(const int32_t* row_ptr,
                                                                    const int32_t* col_ind,
                                                                    int64_t n_edges,

@@ -147,6 +147,12 @@ fwd = L.wholememory_ext_csc_gat_edge_forward(row_ptr, col, E, nd, ns, h, H * F, 
 bwd = L.wholememory_ext_csc_gat_edge_backward(row_ptr, col, E, nd, ns, h, H * F, att, ef, H * F, H, F, 0.2, 1, alpha, scores,
                                               es, out, H * F, gh, H * F, ga, gef, H * F, env, None)
 print("RESULT", fwd, bwd)
+# a malformed call is judged before the backend is asked: a null row_ptr, a grad_edge_feat stride one short of the row
+bad_fwd = L.wholememory_ext_csc_gat_edge_forward(None, col, E, nd, ns, h, H * F, att, ef, H * F, H, F, 0.2, 1, out, H * F,
+                                                 alpha, scores, es, env, None)
+bad_bwd = L.wholememory_ext_csc_gat_edge_backward(row_ptr, col, E, nd, ns, h, H * F, att, ef, H * F, H, F, 0.2, 1, alpha,
+                                                  scores, es, out, H * F, gh, H * F, ga, gef, H * F - 1, env, None)
+print("MALFORMED", bad_fwd, bad_bwd)
 '''
 
 
@@ -159,6 +165,8 @@ def test_entry_points_not_supported_under_cpu_test_backend(wm_lib):
     fwd, bwd = (int(v) for v in line.split()[1:])
     from wholegraph_amd import binding
     assert fwd == binding.NOT_SUPPORTED and bwd == binding.NOT_SUPPORTED
+    malformed = [l for l in p.stdout.splitlines() if l.startswith("MALFORMED")][-1]
+    assert [int(v) for v in malformed.split()[1:]] == [6, 6]   # WHOLEMEMORY_INVALID_INPUT
 
 
 def test_entry_points_validate_arguments(wm_lib):

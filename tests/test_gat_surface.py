@@ -85,6 +85,12 @@ fwd = L.wholememory_ext_csc_gat_forward(row_ptr, col, 2, nd, ns, h, H * F, att, 
 bwd = L.wholememory_ext_csc_gat_backward(row_ptr, col, 2, nd, ns, h, H * F, att, H, F, 0.2, 1, alpha, scores, out, H * F,
                                          gh, H * F, ga, env, None)
 print("RESULT", fwd, bwd, L.wholememory_ext_csc_gat_node_chunk())
+# a malformed call is judged before the backend is asked: a null row_ptr, a grad_h stride one short of the row
+bad_fwd = L.wholememory_ext_csc_gat_forward(None, col, 2, nd, ns, h, H * F, att, H, F, 0.2, 1, out, H * F, alpha, scores, env,
+                                            None)
+bad_bwd = L.wholememory_ext_csc_gat_backward(row_ptr, col, 2, nd, ns, h, H * F, att, H, F, 0.2, 1, alpha, scores, out, H * F,
+                                             gh, H * F - 1, ga, env, None)
+print("MALFORMED", bad_fwd, bad_bwd)
 '''
 
 
@@ -98,6 +104,8 @@ def test_entry_points_not_supported_under_cpu_test_backend(wm_lib):
     from wholegraph_amd import binding
     assert fwd == binding.NOT_SUPPORTED and bwd == binding.NOT_SUPPORTED
     assert chunk >= 1
+    malformed = [l for l in p.stdout.splitlines() if l.startswith("MALFORMED")][-1]
+    assert [int(v) for v in malformed.split()[1:]] == [6, 6]   # WHOLEMEMORY_INVALID_INPUT
 
 
 def test_entry_points_validate_arguments(wm_lib):

@@ -155,6 +155,13 @@ before = L.wholememory_ext_gather_aggregate_calls()
 fwd = L.wholememory_ext_csc_gather_aggregate_forward(t, ids, wmb.DT_INT64, row_ptr, col, 2, 2, 3, wmb.AGGR_MEAN, out, 2 * F,
                                                      env, None)
 print("RESULT", fwd, before, L.wholememory_ext_gather_aggregate_calls())
+# a malformed call is judged before the backend is asked (the op has a forward only): a null row_ptr, an out stride one
+# short of the row
+bad_ptr = L.wholememory_ext_csc_gather_aggregate_forward(t, ids, wmb.DT_INT64, None, col, 2, 2, 3, wmb.AGGR_MEAN, out, 2 * F,
+                                                         env, None)
+bad_stride = L.wholememory_ext_csc_gather_aggregate_forward(t, ids, wmb.DT_INT64, row_ptr, col, 2, 2, 3, wmb.AGGR_MEAN, out,
+                                                            2 * F - 1, env, None)
+print("MALFORMED", bad_ptr, bad_stride)
 '''
 
 
@@ -168,3 +175,5 @@ def test_entry_points_under_cpu_test_backend(wm_lib):
     from wholegraph_amd import binding
     assert fwd == binding.NOT_SUPPORTED
     assert before == 0 and after == 0
+    malformed = [l for l in p.stdout.splitlines() if l.startswith("MALFORMED")][-1]
+    assert [int(v) for v in malformed.split()[1:]] == [6, 6]   # WHOLEMEMORY_INVALID_INPUT

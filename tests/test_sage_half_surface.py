@@ -52,6 +52,12 @@ for dt in (wmb.DT_HALF, wmb.DT_BF16):
     res.append(L.wholememory_ext_csc_aggregate_backward_typed(row_ptr, col, 2, nd, ns, out, 2 * F, F, wmb.AGGR_SUM, gx, F, dt,
                                                               env, None))
 print("RESULT", *res)
+# a malformed call is judged before the backend is asked: a null row_ptr, a grad_x stride one short of the row
+bad_fwd = L.wholememory_ext_csc_aggregate_forward_typed(None, col, 2, nd, ns, x, F, F, wmb.AGGR_MEAN, out, 2 * F, wmb.DT_HALF,
+                                                        env, None)
+bad_bwd = L.wholememory_ext_csc_aggregate_backward_typed(row_ptr, col, 2, nd, ns, out, 2 * F, F, wmb.AGGR_SUM, gx, F - 1,
+                                                         wmb.DT_BF16, env, None)
+print("MALFORMED", bad_fwd, bad_bwd)
 '''
 
 
@@ -63,6 +69,8 @@ def test_typed_entry_points_not_supported_under_cpu_test_backend(wm_lib):
     line = [l for l in p.stdout.splitlines() if l.startswith("RESULT")][-1]
     from wholegraph_amd import binding
     assert [int(v) for v in line.split()[1:]] == [binding.NOT_SUPPORTED] * 4
+    malformed = [l for l in p.stdout.splitlines() if l.startswith("MALFORMED")][-1]
+    assert [int(v) for v in malformed.split()[1:]] == [6, 6]   # WHOLEMEMORY_INVALID_INPUT
 
 
 def test_typed_entry_points_validate_arguments(wm_lib):

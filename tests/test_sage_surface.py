@@ -92,6 +92,10 @@ env = L.wholememory_get_default_env_func()
 fwd = L.wholememory_ext_csc_aggregate_forward(row_ptr, col, 2, nd, ns, x, F, F, wmb.AGGR_MEAN, out, 2 * F, env, None)
 bwd = L.wholememory_ext_csc_aggregate_backward(row_ptr, col, 2, nd, ns, out, 2 * F, F, wmb.AGGR_SUM, gx, F, env, None)
 print("RESULT", fwd, bwd, L.wholememory_ext_csc_aggregate_chunk_edges())
+# a malformed call is judged before the backend is asked: a null row_ptr, a grad_x stride one short of the row
+bad_fwd = L.wholememory_ext_csc_aggregate_forward(None, col, 2, nd, ns, x, F, F, wmb.AGGR_MEAN, out, 2 * F, env, None)
+bad_bwd = L.wholememory_ext_csc_aggregate_backward(row_ptr, col, 2, nd, ns, out, 2 * F, F, wmb.AGGR_SUM, gx, F - 1, env, None)
+print("MALFORMED", bad_fwd, bad_bwd)
 '''
 
 
@@ -105,6 +109,8 @@ def test_entry_points_not_supported_under_cpu_test_backend(wm_lib):
     from wholegraph_amd import binding
     assert fwd == binding.NOT_SUPPORTED and bwd == binding.NOT_SUPPORTED
     assert chunk >= 1
+    malformed = [l for l in p.stdout.splitlines() if l.startswith("MALFORMED")][-1]
+    assert [int(v) for v in malformed.split()[1:]] == [6, 6]   # WHOLEMEMORY_INVALID_INPUT
 
 
 def test_entry_points_validate_arguments(wm_lib):

@@ -121,6 +121,11 @@ fwd = L.wholememory_ext_csc_aggregate_weighted_forward(row_ptr, col, w, 2, nd, n
 bwd = L.wholememory_ext_csc_aggregate_weighted_backward(row_ptr, col, 2, nd, ns, x, F, w, out, 2 * F, F, 1, gx, F, gw, env,
                                                         None)
 print("RESULT", fwd, bwd)
+# a malformed call is judged before the backend is asked: a null row_ptr, a grad_out stride one short of the row
+bad_fwd = L.wholememory_ext_csc_aggregate_weighted_forward(None, col, w, 2, nd, ns, x, F, F, 1, out, 2 * F, env, None)
+bad_bwd = L.wholememory_ext_csc_aggregate_weighted_backward(row_ptr, col, 2, nd, ns, x, F, w, out, 2 * F - 1, F, 1, gx, F, gw,
+                                                            env, None)
+print("MALFORMED", bad_fwd, bad_bwd)
 '''
 
 
@@ -133,6 +138,8 @@ def test_entry_points_not_supported_under_cpu_test_backend(wm_lib):
     fwd, bwd = (int(v) for v in line.split()[1:])
     from wholegraph_amd import binding
     assert fwd == binding.NOT_SUPPORTED and bwd == binding.NOT_SUPPORTED
+    malformed = [l for l in p.stdout.splitlines() if l.startswith("MALFORMED")][-1]
+    assert [int(v) for v in malformed.split()[1:]] == [6, 6]   # WHOLEMEMORY_INVALID_INPUT
 
 
 def test_entry_points_validate_arguments(wm_lib):

@@ -16,31 +16,45 @@ namespace {
 
 using namespace wm;
 
-void check_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src,
-                const void* in, int64_t in_stride, int64_t in_cols, int64_t dim, int aggr, const void* out,
-                int64_t out_stride, int64_t out_cols, int64_t in_rows, int64_t out_rows)
+// what the agg_concat entry points check alike, and the args they fill alike: the block, dim and aggr; the rows that are
+// read (`in`, [in_rows, in_cols]) and the rows that are written (`out`, [out_rows, out_cols])
+template <class Args>
+Args checked_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src,
+                  const void* in, int64_t in_stride, int64_t in_cols, int64_t dim, int aggr, const void* out,
+                  int64_t out_stride, int64_t out_cols, int64_t in_rows, int64_t out_rows)
 {
-  auto bad = [](const char* what) { throw invalid_input(what); };
-  check_block(row_ptr, col_ind, n_edges, n_dst, n_src, n_edges > 0, "x");
-  if (dim < 1) bad("dim must be >= 1");
-  if (aggr != WHOLEMEMORY_EXT_AGGR_SUM && aggr != WHOLEMEMORY_EXT_AGGR_MEAN) bad("aggr must be SUM or MEAN");
-  if (in_rows > 0 && in == nullptr) bad("input rows are null");
-  if (out_rows > 0 && out == nullptr) bad("output rows are null");
-  if (in_stride < in_cols) bad("input stride smaller than its row");
-  if (out_stride < out_cols) bad("output stride smaller than its row");
+  Args a{};
+  static_cast<wm_csc_block&>(a) = checked_block(row_ptr, col_ind, n_edges, n_dst, n_src, n_edges > 0, "x");
+  if (dim < 1) throw invalid_input("dim must be >= 1");
+  if (aggr != WHOLEMEMORY_EXT_AGGR_SUM && aggr != WHOLEMEMORY_EXT_AGGR_MEAN) throw invalid_input("aggr must be SUM or MEAN");
+  check_rows(in, in_rows > 0, in_stride, in_cols, "input");
+  check_rows(out, out_rows > 0, out_stride, out_cols, "output");
+  a.dim  = dim;
+  a.mean = aggr == WHOLEMEMORY_EXT_AGGR_MEAN ? 1 : 0;
+  return a;
 }
 
-// the edge index of a backward (sort_col_ind), then launch(order, run_starts, unique_ids, n_unique_dev, workspace) with the
-// workspace of agg_backward_workspace_bytes
-template <class Launch>
-void backward_over_index(const wm_device_backend* bk, const int32_t* col_ind, int64_t E, int64_t n_src, int64_t dim,
-                         wholememory_env_func_t* p_env_fns, void* stream, Launch launch)
+// the backward of the agg_concat family: nothing to do without source rows, else the edge index, the workspace of
+// agg_backward_workspace_bytes and `entry` (the backend's *_backward named `name`)
+template <class Args>
+void agg_backward(const char* name, int (*entry)(const Args*, const wm_edge_index&, void*, void*), const Args& a,
+                  wholememory_env_func_t* p_env_fns, void* stream)
 {
-  sorted_ids ix(p_env_fns);
-  temp_mem agg_ws(p_env_fns);
-  sort_col_ind(&ix, col_ind, E, n_src, stream);
-  void* d_aws = agg_ws.device(static_cast<int64_t>(bk->agg_backward_workspace_bytes(E, n_src, dim)), WHOLEMEMORY_DT_INT8);
-  launch(ix.order, ix.starts, static_cast<const int32_t*>(ix.unique), ix.n_unique_dev, d_aws);
+  if (a.n_src == 0) return;
+  backward_over_index(a, true, backend()->agg_backward_workspace_bytes(a.n_edges, a.n_src, a.dim), p_env_fns, stream,
+                      [&](const wm_edge_index& ix, void* ws) {
+                        const int rc = entry(&a, ix, ws, stream);
+                        if (rc != 0) throw hip_error(format_string("%s failed with code %d", name, rc));
+                      });
+}
+
+// the memory types whose rows the fused gathers read with plain loads
+bool table_is_mapped(wholememory_tensor_t table)
+{
+  if (!wholememory_tensor_has_handle(table)) return true;
+  const auto mt = wholememory_get_memory_type(wholememory_tensor_get_memory_handle(table));
+  if (mt != WHOLEMEMORY_MT_CONTINUOUS && mt != WHOLEMEMORY_MT_CHUNKED) return false;
+  return !mapped_via_exchange(table, mt);   // (served by a collective, not by loads)
 }
 
 bool rows16(wholememory_dtype_t dtype) { return dtype == WHOLEMEMORY_DT_HALF || dtype == WHOLEMEMORY_DT_BF16; }
@@ -48,7 +62,7 @@ bool rows16(wholememory_dtype_t dtype) { return dtype == WHOLEMEMORY_DT_HALF || 
 std::atomic<int64_t> g_gather_agg_calls{0};   // fused forwards that reached the backend
 std::atomic<int64_t> g_qagg_calls{0};         // the same over a quantized table (section 2j)
 
-// what the two _rel_ entry points check alike, ahead of check_args
+// what the two _rel_ entry points check alike, ahead of checked_args
 void check_rel(const int32_t* edge_type, int64_t n_edges, int64_t num_relations, int aggr, const float* edge_scale)
 {
   if (num_relations < 1) throw invalid_input("num_relations must be >= 1");
@@ -70,10 +84,10 @@ wholememory_error_code_t wholememory_ext_csc_aggregate_forward(const int32_t* ro
 {
   WM_API_BEGIN
   (void)p_env_fns;   // (the forward needs no scratch)
+  auto a = checked_args<wm_agg_args>(row_ptr, col_ind, n_edges, n_dst, n_src, x, x_stride, dim, dim, aggr, out, out_stride,
+                                     2 * dim, n_src, n_dst);
   const auto* bk = backend();
   if (bk->agg_forward == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
-  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, x, x_stride, dim, dim, aggr, out, out_stride, 2 * dim, n_src, n_dst);
-  auto a = block_args<wm_agg_args>(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
   a.in            = x;
   a.in_stride     = x_stride;
   a.out           = out;
@@ -90,21 +104,16 @@ wholememory_error_code_t wholememory_ext_csc_aggregate_backward(const int32_t* r
                                                                 void* stream)
 {
   WM_API_BEGIN
+  auto a = checked_args<wm_agg_args>(row_ptr, col_ind, n_edges, n_dst, n_src, grad_out, grad_out_stride, 2 * dim, dim, aggr,
+                                     grad_x, grad_x_stride, dim, n_dst, n_src);
+  check_env(p_env_fns);
   const auto* bk = backend();
   if (bk->agg_backward == nullptr || bk->agg_backward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
-  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, grad_out, grad_out_stride, 2 * dim, dim, aggr, grad_x, grad_x_stride,
-             dim, n_dst, n_src);
-  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
-  auto a = block_args<wm_agg_args>(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
   a.grad        = grad_out;
   a.grad_stride = grad_out_stride;
   a.out         = grad_x;
   a.out_stride  = grad_x_stride;
-  if (n_src == 0) return WHOLEMEMORY_SUCCESS;
-  backward_over_index(bk, col_ind, a.n_edges, n_src, dim, p_env_fns, stream,
-                      [&](const int32_t* order, const int32_t* starts, const int32_t* unique, const int64_t* nu, void* ws) {
-                        WM_BK(bk->agg_backward(&a, order, starts, unique, nu, ws, stream));
-                      });
+  agg_backward("agg_backward", bk->agg_backward, a, p_env_fns, stream);
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }
@@ -121,10 +130,10 @@ wholememory_error_code_t wholememory_ext_csc_aggregate_forward_typed(const int32
   WM_API_BEGIN
   (void)p_env_fns;
   if (!rows16(dtype)) throw invalid_input("dtype must be FLOAT, HALF or BF16");
+  auto a = checked_args<wm_agg16_args>(row_ptr, col_ind, n_edges, n_dst, n_src, x, x_stride, dim, dim, aggr, out, out_stride,
+                                       2 * dim, n_src, n_dst);
   const auto* bk = backend();
   if (bk->agg16_forward == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
-  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, x, x_stride, dim, dim, aggr, out, out_stride, 2 * dim, n_src, n_dst);
-  auto a = block_args<wm_agg16_args>(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
   a.dtype         = dtype;
   a.in            = x;
   a.in_stride     = x_stride;
@@ -148,22 +157,17 @@ wholememory_error_code_t wholememory_ext_csc_aggregate_backward_typed(const int3
                                                   static_cast<float*>(grad_x), grad_x_stride, p_env_fns, stream);
   WM_API_BEGIN
   if (!rows16(dtype)) throw invalid_input("dtype must be FLOAT, HALF or BF16");
+  auto a = checked_args<wm_agg16_args>(row_ptr, col_ind, n_edges, n_dst, n_src, grad_out, grad_out_stride, 2 * dim, dim, aggr,
+                                       grad_x, grad_x_stride, dim, n_dst, n_src);
+  check_env(p_env_fns);
   const auto* bk = backend();
   if (bk->agg16_backward == nullptr || bk->agg_backward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
-  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, grad_out, grad_out_stride, 2 * dim, dim, aggr, grad_x, grad_x_stride,
-             dim, n_dst, n_src);
-  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
-  auto a = block_args<wm_agg16_args>(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
   a.dtype         = dtype;
   a.grad          = grad_out;
   a.grad_stride   = grad_out_stride;
   a.out           = grad_x;
   a.out_stride    = grad_x_stride;
-  if (n_src == 0) return WHOLEMEMORY_SUCCESS;
-  backward_over_index(bk, col_ind, a.n_edges, n_src, dim, p_env_fns, stream,
-                      [&](const int32_t* order, const int32_t* starts, const int32_t* unique, const int64_t* nu, void* ws) {
-                        WM_BK(bk->agg16_backward(&a, order, starts, unique, nu, ws, stream));
-                      });
+  agg_backward("agg16_backward", bk->agg16_backward, a, p_env_fns, stream);
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }
@@ -176,11 +180,11 @@ wholememory_error_code_t wholememory_ext_csc_aggregate_weighted_forward(const in
 {
   WM_API_BEGIN
   (void)p_env_fns;   // (the forward needs no scratch)
+  auto a = checked_args<wm_aggw_args>(row_ptr, col_ind, n_edges, n_dst, n_src, x, x_stride, dim, dim, aggr, out, out_stride,
+                                      2 * dim, n_src, n_dst);
+  if (n_edges > 0 && w == nullptr) throw invalid_input("w is null");
   const auto* bk = backend();
   if (bk->aggw_forward == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
-  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, x, x_stride, dim, dim, aggr, out, out_stride, 2 * dim, n_src, n_dst);
-  if (n_edges > 0 && w == nullptr) throw invalid_input("w is null");
-  auto a = block_args<wm_aggw_args>(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
   a.w            = w;
   a.in           = x;
   a.in_stride    = x_stride;
@@ -197,19 +201,16 @@ wholememory_error_code_t wholememory_ext_csc_aggregate_weighted_backward(
   int64_t grad_x_stride, float* grad_w, wholememory_env_func_t* p_env_fns, void* stream)
 {
   WM_API_BEGIN
-  const auto* bk = backend();
-  if (bk->aggw_backward == nullptr || bk->agg_backward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
   // (grad_x may be null: its rows and stride are checked only when it is asked for)
-  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, grad_out, grad_out_stride, 2 * dim, dim, aggr, grad_x,
-             grad_x != nullptr ? grad_x_stride : dim, dim, n_dst, grad_x != nullptr ? n_src : 0);
+  auto a = checked_args<wm_aggw_args>(row_ptr, col_ind, n_edges, n_dst, n_src, grad_out, grad_out_stride, 2 * dim, dim, aggr,
+                                      grad_x, grad_x != nullptr ? grad_x_stride : dim, dim, n_dst,
+                                      grad_x != nullptr ? n_src : 0);
   if (grad_x == nullptr && grad_w == nullptr) throw invalid_input("grad_x and grad_w are both null");
   if (n_edges > 0 && w == nullptr) throw invalid_input("w is null");
-  if (grad_w != nullptr) {   // the gradient of the weights reads the rows of x
-    if (n_src > 0 && x == nullptr) throw invalid_input("x is null");
-    if (x_stride < dim) throw invalid_input("input stride smaller than its row");
-  }
-  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
-  auto a = block_args<wm_aggw_args>(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
+  if (grad_w != nullptr) check_rows(x, n_src > 0, x_stride, dim, "x");   // the gradient of the weights reads the rows of x
+  check_env(p_env_fns);
+  const auto* bk = backend();
+  if (bk->aggw_backward == nullptr || bk->agg_backward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
   a.w            = w;
   a.in           = x;
   a.in_stride    = x_stride;
@@ -219,13 +220,10 @@ wholememory_error_code_t wholememory_ext_csc_aggregate_weighted_backward(
   a.out_stride   = grad_x_stride;
   a.grad_w       = grad_w;
   if (grad_x != nullptr && n_src > 0) {
-    backward_over_index(bk, col_ind, a.n_edges, n_src, dim, p_env_fns, stream,
-                        [&](const int32_t* order, const int32_t* starts, const int32_t* unique, const int64_t* nu, void* ws) {
-                          WM_BK(bk->aggw_backward(&a, order, starts, unique, nu, ws, stream));
-                        });
-  } else if (grad_w != nullptr) {
+    agg_backward("aggw_backward", bk->aggw_backward, a, p_env_fns, stream);
+  } else if (grad_w != nullptr) {   // (no gradient walks the sources: no index, no workspace)
     a.out = nullptr;
-    WM_BK(bk->aggw_backward(&a, nullptr, nullptr, nullptr, nullptr, nullptr, stream));
+    WM_BK(bk->aggw_backward(&a, wm_edge_index{}, nullptr, stream));
   }
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
@@ -241,8 +239,6 @@ wholememory_error_code_t wholememory_ext_csc_gather_aggregate_forward(wholememor
 {
   WM_API_BEGIN
   (void)p_env_fns;   // (the forward needs no scratch)
-  const auto* bk = backend();
-  if (bk->gather_agg_forward == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
   if (table == nullptr) throw invalid_input("table is null");
   const wholememory_tensor_description_t td = *wholememory_tensor_get_tensor_description(table);
   if (td.dim != 2) throw invalid_input("the table must be a 2-D tensor");
@@ -252,14 +248,11 @@ wholememory_error_code_t wholememory_ext_csc_gather_aggregate_forward(wholememor
     throw invalid_input("node_id_dtype must be INT or INT64");
   const int64_t dim = td.sizes[1];
   // (the virtual x: n_src rows of `dim` elements behind node_ids)
-  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, node_ids, dim, dim, dim, aggr, out, out_stride, 2 * dim, n_src, n_dst);
+  auto a = checked_args<wm_gather_agg_args>(row_ptr, col_ind, n_edges, n_dst, n_src, node_ids, dim, dim, dim, aggr, out,
+                                            out_stride, 2 * dim, n_src, n_dst);
   if (n_src > 0 && td.sizes[0] < 1) throw invalid_input("node ids into a table without rows");
-  if (wholememory_tensor_has_handle(table)) {
-    const auto mt = wholememory_get_memory_type(wholememory_tensor_get_memory_handle(table));
-    if (mt != WHOLEMEMORY_MT_CONTINUOUS && mt != WHOLEMEMORY_MT_CHUNKED) return WHOLEMEMORY_NOT_SUPPORTED;
-    if (mapped_via_exchange(table, mt)) return WHOLEMEMORY_NOT_SUPPORTED;   // (served by a collective, not by loads)
-  }
-  auto a = block_args<wm_gather_agg_args>(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
+  const auto* bk = backend();
+  if (bk->gather_agg_forward == nullptr || !table_is_mapped(table)) return WHOLEMEMORY_NOT_SUPPORTED;
   WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(table, &a.gref));
   a.table_dtype          = td.dtype;
   a.table_rows           = td.sizes[0];
@@ -284,7 +277,6 @@ wholememory_error_code_t wholememory_ext_csc_gather_dequantize_aggregate_forward
 {
   WM_API_BEGIN
   (void)p_env_fns;   // (the forward needs no scratch)
-  // (the arguments are judged first: a malformed call is INVALID_INPUT under every backend)
   if (table == nullptr) throw invalid_input("table is null");
   const wholememory_tensor_description_t td = *wholememory_tensor_get_tensor_description(table);
   if (td.dim != 2) throw invalid_input("the table must be a 2-D tensor");
@@ -301,16 +293,11 @@ wholememory_error_code_t wholememory_ext_csc_gather_dequantize_aggregate_forward
   if (node_id_dtype != WHOLEMEMORY_DT_INT && node_id_dtype != WHOLEMEMORY_DT_INT64)
     throw invalid_input("node_id_dtype must be INT or INT64");
   // (the virtual x: n_src rows of `dim` values behind node_ids)
-  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, node_ids, dim, dim, dim, aggr, out, out_stride, 2 * dim, n_src, n_dst);
+  auto a = checked_args<wm_qagg_args>(row_ptr, col_ind, n_edges, n_dst, n_src, node_ids, dim, dim, dim, aggr, out, out_stride,
+                                      2 * dim, n_src, n_dst);
   if (n_src > 0 && td.sizes[0] < 1) throw invalid_input("node ids into a table without rows");
   const auto* bk = backend();
-  if (bk->qagg_forward == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
-  if (wholememory_tensor_has_handle(table)) {
-    const auto mt = wholememory_get_memory_type(wholememory_tensor_get_memory_handle(table));
-    if (mt != WHOLEMEMORY_MT_CONTINUOUS && mt != WHOLEMEMORY_MT_CHUNKED) return WHOLEMEMORY_NOT_SUPPORTED;
-    if (mapped_via_exchange(table, mt)) return WHOLEMEMORY_NOT_SUPPORTED;   // (served by a collective, not by loads)
-  }
-  auto a = block_args<wm_qagg_args>(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
+  if (bk->qagg_forward == nullptr || !table_is_mapped(table)) return WHOLEMEMORY_NOT_SUPPORTED;
   WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(table, &a.gref));
   a.table_rows           = td.sizes[0];
   a.table_stride         = td.strides[0];
@@ -335,14 +322,12 @@ wholememory_error_code_t wholememory_ext_csc_rel_aggregate_forward(const int32_t
                                                                    wholememory_env_func_t* p_env_fns, void* stream)
 {
   WM_API_BEGIN
-  // (the arguments are judged first: a malformed call is INVALID_INPUT under every backend)
   check_rel(edge_type, n_edges, num_relations, aggr, edge_scale);
-  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, x, x_stride, dim, dim, aggr, out, out_stride,
-             (num_relations + 1) * dim, n_src, n_dst);
-  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");   // (as the backward; the forward needs no scratch)
+  auto a = checked_args<wm_relagg_args>(row_ptr, col_ind, n_edges, n_dst, n_src, x, x_stride, dim, dim, aggr, out, out_stride,
+                                        (num_relations + 1) * dim, n_src, n_dst);
+  check_env(p_env_fns);   // (as the backward; the forward needs no scratch)
   const auto* bk = backend();
   if (bk->relagg_forward == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
-  auto a = block_args<wm_relagg_args>(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
   a.edge_type     = edge_type;
   a.num_relations = num_relations;
   a.edge_scale    = a.mean ? edge_scale : nullptr;
@@ -365,12 +350,11 @@ wholememory_error_code_t wholememory_ext_csc_rel_aggregate_backward(const int32_
 {
   WM_API_BEGIN
   check_rel(edge_type, n_edges, num_relations, aggr, edge_scale);
-  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, grad_out, grad_out_stride, (num_relations + 1) * dim, dim, aggr, grad_x,
-             grad_x_stride, dim, n_dst, n_src);
-  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
+  auto a = checked_args<wm_relagg_args>(row_ptr, col_ind, n_edges, n_dst, n_src, grad_out, grad_out_stride,
+                                        (num_relations + 1) * dim, dim, aggr, grad_x, grad_x_stride, dim, n_dst, n_src);
+  check_env(p_env_fns);
   const auto* bk = backend();
   if (bk->relagg_backward == nullptr || bk->agg_backward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
-  auto a = block_args<wm_relagg_args>(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggr);
   a.edge_type     = edge_type;
   a.num_relations = num_relations;
   a.edge_scale    = a.mean ? const_cast<float*>(edge_scale) : nullptr;   // (read only by the backward)
@@ -378,11 +362,7 @@ wholememory_error_code_t wholememory_ext_csc_rel_aggregate_backward(const int32_
   a.grad_stride   = grad_out_stride;
   a.out           = grad_x;
   a.out_stride    = grad_x_stride;
-  if (n_src == 0) return WHOLEMEMORY_SUCCESS;
-  backward_over_index(bk, col_ind, a.n_edges, n_src, dim, p_env_fns, stream,
-                      [&](const int32_t* order, const int32_t* starts, const int32_t* unique, const int64_t* nu, void* ws) {
-                        WM_BK(bk->relagg_backward(&a, order, starts, unique, nu, ws, stream));
-                      });
+  agg_backward("relagg_backward", bk->relagg_backward, a, p_env_fns, stream);
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }
@@ -396,24 +376,16 @@ namespace {
 wm_pna_args pna_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src,
                      int64_t dim, int mask, const void* rows, int64_t rows_stride, const void* other, int64_t other_stride)
 {
-  auto bad = [](const char* what) { throw invalid_input(what); };
-  check_block(row_ptr, col_ind, n_edges, n_dst, n_src, n_edges > 0, "x");
-  if (dim < 1) bad("dim must be >= 1");
-  if (mask < 1 || mask > WM_PNA_ALL) bad("aggregators: a non-empty mask of the five WHOLEMEMORY_EXT_PNA_ bits");
+  wm_pna_args a{};
+  static_cast<wm_csc_block&>(a) = checked_block(row_ptr, col_ind, n_edges, n_dst, n_src, n_edges > 0, "x");
+  if (dim < 1) throw invalid_input("dim must be >= 1");
+  if (mask < 1 || mask > WM_PNA_ALL) throw invalid_input("aggregators: a non-empty mask of the five WHOLEMEMORY_EXT_PNA_ bits");
   int slots = 1;
   for (int bit = 1; bit <= WM_PNA_STD; bit <<= 1) slots += (mask & bit) ? 1 : 0;
-  if (n_dst > 0 && rows == nullptr) bad("rows of the targets are null");
-  if (n_src > 0 && other == nullptr) bad("rows of the sources are null");
-  if (rows_stride < slots * dim) bad("stride of the targets' rows smaller than (aggregators + 1) * dim");
-  if (other_stride < dim) bad("stride of the sources' rows smaller than dim");
-  wm_pna_args a{};
-  a.row_ptr = row_ptr;
-  a.col_ind = col_ind;
-  a.n_edges = n_dst == 0 ? 0 : n_edges;   // (no target, no edge of any target)
-  a.n_dst   = n_dst;
-  a.n_src   = n_src;
-  a.dim     = dim;
-  a.mask    = mask;
+  check_rows(rows, n_dst > 0, rows_stride, slots * dim, "the targets' rows ((aggregators + 1) * dim columns)");
+  check_rows(other, n_src > 0, other_stride, dim, "the sources' rows");
+  a.dim  = dim;
+  a.mask = mask;
   return a;
 }
 
@@ -431,7 +403,6 @@ wholememory_error_code_t wholememory_ext_csc_pna_aggregate_forward(const int32_t
 {
   WM_API_BEGIN
   (void)p_env_fns;   // (the forward needs no scratch)
-  // (the arguments are judged first: a malformed call is INVALID_INPUT under every backend)
   auto a = pna_args(row_ptr, col_ind, n_edges, n_dst, n_src, dim, aggregators, out, out_stride, x, x_stride);
   if (!(eps >= 0.0f)) throw invalid_input("eps must be >= 0");
   const auto* bk = backend();
@@ -465,11 +436,8 @@ wholememory_error_code_t wholememory_ext_csc_pna_aggregate_backward(
     if ((aggregators & WM_PNA_STD) && (std_mean == nullptr || std_coef == nullptr))
       throw invalid_input("std is selected and std_mean or std_coef is null");
   }
-  if (aggregators & WM_PNA_STD) {   // the gradient of std reads the rows of x
-    if (n_src > 0 && x == nullptr) throw invalid_input("std is selected and x is null");
-    if (x_stride < dim) throw invalid_input("input stride smaller than its row");
-  }
-  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
+  if (aggregators & WM_PNA_STD) check_rows(x, n_src > 0, x_stride, dim, "x (read for std)");   // the gradient of std reads x
+  check_env(p_env_fns);
   const auto* bk = backend();
   if (bk->pna_backward == nullptr || bk->pna_backward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
   a.in          = x;
@@ -484,11 +452,8 @@ wholememory_error_code_t wholememory_ext_csc_pna_aggregate_backward(
   a.out         = grad_x;
   a.out_stride  = grad_x_stride;
   if (n_src == 0) return WHOLEMEMORY_SUCCESS;
-  sorted_ids ix(p_env_fns);
-  temp_mem ws(p_env_fns);
-  sort_col_ind(&ix, col_ind, a.n_edges, n_src, stream);
-  void* d_ws = ws.device(static_cast<int64_t>(bk->pna_backward_workspace_bytes(a.n_edges, n_src, dim)), WHOLEMEMORY_DT_INT8);
-  WM_BK(bk->pna_backward(&a, ix.order, ix.starts, static_cast<const int32_t*>(ix.unique), ix.n_unique_dev, d_ws, stream));
+  backward_over_index(a, true, bk->pna_backward_workspace_bytes(a.n_edges, n_src, dim), p_env_fns, stream,
+                      [&](const wm_edge_index& ix, void* ws) { WM_BK(bk->pna_backward(&a, ix, ws, stream)); });
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }

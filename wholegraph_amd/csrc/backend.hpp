@@ -181,11 +181,26 @@ struct wm_cache_args {
   int64_t raw2_row_stride_bytes;
 };
 
-// neighbour aggregation of a sampled CSC block (kernels/agg.hip): rows / strides / dim in ELEMENTS (fp32)
-struct wm_agg_args {
+// a sampled block in CSC form, the first fields of the args of every op over one (`p.row_ptr`, `p.n_dst`, ...): the edges of
+// target d are col_ind[row_ptr[d] : row_ptr[d + 1]], the targets are the first n_dst of the n_src source rows
+struct wm_csc_block {
   const int32_t* row_ptr;   // [n_dst + 1]
   const int32_t* col_ind;   // [n_edges], ids in [0, n_src)
-  int64_t n_edges, n_dst, n_src, dim;
+  int64_t n_edges, n_dst, n_src;   // n_edges is 0 when n_dst is (no target, no edge of any target)
+};
+
+// the edge index of a per-source backward: dedup_ids over col_ind (int32, key_upper_bound = n_src), a stable sort by source.
+// All null: no index was built (the op's call does not walk the sources)
+struct wm_edge_index {
+  const int32_t* order;          // [n_edges] edge positions, sorted by source
+  const int32_t* run_starts;     // [n_unique + 1]
+  const int32_t* unique_ids;     // [n_unique] sources with edges, ascending
+  const int64_t* n_unique_dev;   // device scalar written by the sort
+};
+
+// neighbour aggregation of a sampled CSC block (kernels/agg.hip): rows / strides / dim in ELEMENTS (fp32)
+struct wm_agg_args : wm_csc_block {
+  int64_t dim;
   int mean;                 // 1: "mean" (sum times fl(1 / degree)), 0: "sum"
   const float* in;          // forward: x [n_src, in_stride]
   int64_t in_stride;
@@ -197,10 +212,8 @@ struct wm_agg_args {
 
 // the same op on rows of 16-bit floats (kernels/agg_half.hip): `dtype` is WHOLEMEMORY_DT_HALF or WHOLEMEMORY_DT_BF16 and is
 // the type of in, grad and out alike; strides / dim in ELEMENTS of it. Sums are fp32, each output element rounded once.
-struct wm_agg16_args {
-  const int32_t* row_ptr;   // [n_dst + 1]
-  const int32_t* col_ind;   // [n_edges], ids in [0, n_src)
-  int64_t n_edges, n_dst, n_src, dim;
+struct wm_agg16_args : wm_csc_block {
+  int64_t dim;
   int mean;
   wholememory_dtype_t dtype;
   const void* in;           // forward: x [n_src, in_stride]
@@ -213,10 +226,8 @@ struct wm_agg16_args {
 
 // multi-head graph attention of a sampled CSC block (kernels/gat.hip, the GAT `mha_gat_n2n` op): rows / strides in
 // ELEMENTS (fp32); head k owns columns [k * dim, (k + 1) * dim) of a row of h
-struct wm_gat_args {
-  const int32_t* row_ptr;   // [n_dst + 1]
-  const int32_t* col_ind;   // [n_edges], ids in [0, n_src)
-  int64_t n_edges, n_dst, n_src, heads, dim;
+struct wm_gat_args : wm_csc_block {
+  int64_t heads, dim;
   float slope;              // LeakyReLU negative slope
   int concat;               // 1: out [n_dst, heads * dim]; 0: the mean over heads, [n_dst, dim]
   const float* h;           // [n_src, h_stride], heads * dim columns used
@@ -235,11 +246,9 @@ struct wm_gat_args {
 
 // edge-weighted neighbour aggregation of a sampled CSC block (kernels/agg_weighted.hip): wm_agg_args plus one fp32 weight
 // per edge position; rows / strides / dim in ELEMENTS (fp32)
-struct wm_aggw_args {
-  const int32_t* row_ptr;   // [n_dst + 1]
-  const int32_t* col_ind;   // [n_edges], ids in [0, n_src)
+struct wm_aggw_args : wm_csc_block {
   const float* w;           // [n_edges]
-  int64_t n_edges, n_dst, n_src, dim;
+  int64_t dim;
   int mean;                 // 1: "mean" (sum times fl(1 / degree)), 0: "sum"
   const float* in;          // x [n_src, in_stride] (forward; backward into w)
   int64_t in_stride;
@@ -269,7 +278,7 @@ struct wm_edge_attr_args {
 // agg_concat over rows that come from a WholeMemory table by global id (kernels/agg_gather.hip, wholegraph_amd_ext.h section
 // 2e): x[i] = fp32(table[node_ids[i]]) for i < n_src is never materialised. `gref` addresses the table (continuous or
 // chunked); stride / offset / dim in ELEMENTS of table_dtype (FLOAT, HALF or BF16); out is fp32
-struct wm_gather_agg_args {
+struct wm_gather_agg_args : wm_csc_block {
   wholememory_gref_t gref;
   wholememory_dtype_t table_dtype;
   int64_t table_rows;               // rows of the (sub)tensor: ids are in [0, table_rows)
@@ -277,9 +286,7 @@ struct wm_gather_agg_args {
   int64_t table_storage_offset;     // elements
   const void* node_ids;             // [n_src] int32 / int64, device
   wholememory_dtype_t node_id_dtype;
-  const int32_t* row_ptr;           // [n_dst + 1]
-  const int32_t* col_ind;           // [n_edges], ids in [0, n_src)
-  int64_t n_edges, n_dst, n_src, dim;
+  int64_t dim;
   int mean;                         // 1: "mean" (sum times fl(1 / degree)), 0: "sum"
   float* out;                       // [n_dst, out_stride] (2 * dim columns)
   int64_t out_stride;
@@ -298,10 +305,8 @@ struct wm_gat_edge_args {
 
 // GATv2 multi-head graph attention of a sampled CSC block (kernels/gatv2.hip, wholegraph_amd_ext.h section 2g): rows /
 // strides in ELEMENTS (fp32); head k owns columns [k * dim, (k + 1) * dim) of a row
-struct wm_gatv2_args {
-  const int32_t* row_ptr;   // [n_dst + 1]
-  const int32_t* col_ind;   // [n_edges], ids in [0, n_src)
-  int64_t n_edges, n_dst, n_src, heads, dim;
+struct wm_gatv2_args : wm_csc_block {
+  int64_t heads, dim;
   float slope;              // LeakyReLU negative slope
   int concat;               // 1: out [n_dst, heads * dim]; 0: the mean over heads, [n_dst, dim]
   const float* h_src;       // [n_src, h_src_stride], heads * dim columns used
@@ -324,11 +329,9 @@ struct wm_gatv2_args {
 // relation-typed neighbour aggregation of a sampled CSC block (kernels/agg_rel.hip, wholegraph_amd_ext.h section 2h):
 // wm_agg_args plus one int32 type per edge position; slot r of an out / grad row is columns [r * dim, (r + 1) * dim), the
 // self slot is slot num_relations. rows / strides / dim in ELEMENTS (fp32)
-struct wm_relagg_args {
-  const int32_t* row_ptr;     // [n_dst + 1]
-  const int32_t* col_ind;     // [n_edges], ids in [0, n_src)
+struct wm_relagg_args : wm_csc_block {
   const int32_t* edge_type;   // [n_edges]; a type outside [0, num_relations) contributes nothing and forms no address
-  int64_t n_edges, n_dst, n_src, dim, num_relations;
+  int64_t dim, num_relations;
   int mean;                   // 1: "mean" (a slot's sum times fl(1 / edges of that relation)), 0: "sum"
   float* edge_scale;          // [n_edges]: mean only (else nullptr); written by the forward, read by the backward
   const float* in;            // forward: x [n_src, in_stride]
@@ -361,16 +364,14 @@ struct wm_qrows_args {
 // agg_concat over rows that come from an 8-bit row-quantized table by global id (kernels/agg_quant.hip, wholegraph_amd_ext.h
 // section 2j): x[i] = dequantize(table row node_ids[i]) for i < n_src is never materialised. The table as in wm_qrows_args
 // (stride / offset in BYTES), the block and out as in wm_gather_agg_args
-struct wm_qagg_args {
+struct wm_qagg_args : wm_csc_block {
   wholememory_gref_t gref;            // the table's bytes (continuous or chunked)
   int64_t table_stride;               // BYTES between rows: >= round_up(dim, 4) + 8, a multiple of 4
   int64_t table_storage_offset;       // BYTES, a multiple of 4
   int64_t table_rows;                 // rows of the (sub)tensor: ids are in [0, table_rows)
   const void* node_ids;               // [n_src] int32 / int64, device
   wholememory_dtype_t node_id_dtype;
-  const int32_t* row_ptr;             // [n_dst + 1]
-  const int32_t* col_ind;             // [n_edges], ids in [0, n_src)
-  int64_t n_edges, n_dst, n_src, dim; // dim: values per row
+  int64_t dim;                        // values per row
   int mean;                           // 1: "mean" (sum times fl(1 / degree)), 0: "sum"
   float* out;                         // [n_dst, out_stride] (2 * dim columns), fp32
   int64_t out_stride;
@@ -378,10 +379,8 @@ struct wm_qagg_args {
 
 // scaled dot-product attention of a sampled CSC block (kernels/tconv.hip, the `mha_simple_n2n` op, wholegraph_amd_ext.h
 // section 2k): rows / strides in ELEMENTS (fp32); head k owns columns [k * dim, (k + 1) * dim) of a row
-struct wm_tconv_args {
-  const int32_t* row_ptr;   // [n_dst + 1]
-  const int32_t* col_ind;   // [n_edges], ids in [0, n_src)
-  int64_t n_edges, n_dst, n_src, heads, dim;
+struct wm_tconv_args : wm_csc_block {
+  int64_t heads, dim;
   int norm_by_dim;          // 1: the logits are multiplied by `scale`; 0: no multiplication
   float scale;              // fl(1 / fl(sqrtf(dim))), computed on the host
   int concat;               // 1: out [n_dst, heads * dim]; 0: the mean over heads, [n_dst, dim]
@@ -409,10 +408,8 @@ struct wm_tconv_args {
 // wholememory_ext_pna_aggr_t); a row of out / grad has one slot of dim columns per selected aggregator, in the order of the
 // bits, then the target's own row
 enum wm_pna_bits : int { WM_PNA_SUM = 1, WM_PNA_MEAN = 2, WM_PNA_MIN = 4, WM_PNA_MAX = 8, WM_PNA_STD = 16, WM_PNA_ALL = 31 };
-struct wm_pna_args {
-  const int32_t* row_ptr;   // [n_dst + 1]
-  const int32_t* col_ind;   // [n_edges], ids in [0, n_src)
-  int64_t n_edges, n_dst, n_src, dim;
+struct wm_pna_args : wm_csc_block {
+  int64_t dim;
   int mask;                 // 1 .. WM_PNA_ALL
   float eps;                // std = sqrt(max(v, 0) + eps)
   const float* in;          // x [n_src, in_stride] (the backward reads it for std only)
@@ -661,36 +658,31 @@ struct wm_device_backend {
   // ---- neighbour aggregation of a sampled CSC block (kernels/agg.hip); nullptr in a backend that does not provide it ----
   // out[d] = (sum or mean of x[col_ind[e]] over the edges of d, x[d]) — the order of every sum: wholegraph_amd_ext.h
   int (*agg_forward)(const wm_agg_args* a, void* stream);
-  // grad_x from dL/dout. order / run_starts / unique_ids / n_unique_dev: dedup_ids over col_ind (int32, key_upper_bound =
-  // n_src); workspace of agg_backward_workspace_bytes(n_edges, n_src, dim). Edges whose run is longer than kAggChunkEdges are
-  // summed in chunks of that many edges, the chunk sums added in chunk order.
+  // grad_x from dL/dout. ix: the edge index of the block; workspace of agg_backward_workspace_bytes(n_edges, n_src, dim).
+  // Edges whose run is longer than kAggChunkEdges are summed in chunks of that many edges, the chunk sums added in chunk order.
   size_t (*agg_backward_workspace_bytes)(int64_t n_edges, int64_t n_src, int64_t dim);
-  int (*agg_backward)(const wm_agg_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                      const int64_t* n_unique_dev, void* workspace, void* stream);
+  int (*agg_backward)(const wm_agg_args* a, const wm_edge_index& ix, void* workspace, void* stream);
   // ---- multi-head graph attention of a sampled CSC block (kernels/gat.hip); nullptr in a backend without it ----
   // forward: node scores, alpha and out (the order of every sum: wholegraph_amd_ext.h, section 2c); workspace of
   // gat_forward_workspace_bytes (the per-head rows before the mean over heads)
   size_t (*gat_forward_workspace_bytes)(const wm_gat_args* a);
   int (*gat_forward)(const wm_gat_args* a, void* workspace, void* stream);
-  // backward: grad_h and grad_att from dL/dout, alpha and the scores of the forward. order / run_starts / unique_ids /
-  // n_unique_dev as for agg_backward; workspace of gat_backward_workspace_bytes
+  // backward: grad_h and grad_att from dL/dout, alpha and the scores of the forward. ix as for agg_backward (all null in a
+  // block without source rows); workspace of gat_backward_workspace_bytes
   size_t (*gat_backward_workspace_bytes)(const wm_gat_args* a);
-  int (*gat_backward)(const wm_gat_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                      const int64_t* n_unique_dev, void* workspace, void* stream);
+  int (*gat_backward)(const wm_gat_args* a, const wm_edge_index& ix, void* workspace, void* stream);
   // ---- agg_forward / agg_backward on fp16 / bf16 rows (kernels/agg_half.hip); nullptr in a backend without them ----
   // the same sums in fp32 in the same order, one rounding per output element; the backward takes the index and the
   // workspace of agg_backward (agg_backward_workspace_bytes: the partial rows of chunks stay fp32)
   int (*agg16_forward)(const wm_agg16_args* a, void* stream);
-  int (*agg16_backward)(const wm_agg16_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                        const int64_t* n_unique_dev, void* workspace, void* stream);
+  int (*agg16_backward)(const wm_agg16_args* a, const wm_edge_index& ix, void* workspace, void* stream);
   // ---- agg_forward / agg_backward with a weight per edge (kernels/agg_weighted.hip, wholegraph_amd_ext.h section 2d);
   // nullptr in a backend without them ----
   int (*aggw_forward)(const wm_aggw_args* a, void* stream);
   // a->out != nullptr: grad_x, with the index and the workspace of agg_backward (agg_backward_workspace_bytes);
-  // a->grad_w != nullptr: the gradient of the weights (needs a->in; no index). With a->out == nullptr the index arguments
-  // and the workspace are not read and may be nullptr.
-  int (*aggw_backward)(const wm_aggw_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                       const int64_t* n_unique_dev, void* workspace, void* stream);
+  // a->grad_w != nullptr: the gradient of the weights (needs a->in; no index). With a->out == nullptr the index and the
+  // workspace are not read and may be null.
+  int (*aggw_backward)(const wm_aggw_args* a, const wm_edge_index& ix, void* workspace, void* stream);
   // ---- attributes of sampled edges (kernels/graph.hip: edge_attr_gather_kernel); nullptr in a backend without it ----
   int (*edge_attr_gather)(const wm_edge_attr_args* a, void* stream);
   // ---- agg_forward over rows read from a WholeMemory table by global id (kernels/agg_gather.hip); nullptr in a backend
@@ -703,25 +695,23 @@ struct wm_device_backend {
   // backward: also grad_edge_feat and half 2 of grad_att; the index of gat_backward, workspace of
   // gat_edge_backward_workspace_bytes
   size_t (*gat_edge_backward_workspace_bytes)(const wm_gat_edge_args* a);
-  int (*gat_edge_backward)(const wm_gat_edge_args* a, const int32_t* order, const int32_t* run_starts,
-                           const int32_t* unique_ids, const int64_t* n_unique_dev, void* workspace, void* stream);
+  int (*gat_edge_backward)(const wm_gat_edge_args* a, const wm_edge_index& ix, void* workspace, void* stream);
   // ---- GATv2 attention of a sampled CSC block (kernels/gatv2.hip, wholegraph_amd_ext.h section 2g); nullptr in a backend
   // without it ----
   // forward: alpha and out; workspace of gatv2_forward_workspace_bytes
   size_t (*gatv2_forward_workspace_bytes)(const wm_gatv2_args* a);
   int (*gatv2_forward)(const wm_gatv2_args* a, void* workspace, void* stream);
   // backward: whichever of grad_h_src, grad_h_dst and grad_att is not null. The index of gat_backward (read for grad_h_src
-  // only: nullptr otherwise); workspace of gatv2_backward_workspace_bytes
+  // only: all null otherwise); workspace of gatv2_backward_workspace_bytes
   size_t (*gatv2_backward_workspace_bytes)(const wm_gatv2_args* a);
-  int (*gatv2_backward)(const wm_gatv2_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                        const int64_t* n_unique_dev, void* workspace, void* stream);
+  int (*gatv2_backward)(const wm_gatv2_args* a, const wm_edge_index& ix, void* workspace, void* stream);
   // ---- relation-typed aggregation of a sampled CSC block (kernels/agg_rel.hip, wholegraph_amd_ext.h section 2h); nullptr
   // in a backend without it ----
   // forward: out and, for mean, edge_scale. backward: grad_x, with the index and the workspace of agg_backward
   // (agg_backward_workspace_bytes)
   int (*relagg_forward)(const wm_relagg_args* a, void* stream);
-  int (*relagg_backward)(const wm_relagg_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                         const int64_t* n_unique_dev, void* workspace, void* stream);  // ---- 8-bit row-quantized tables (kernels/qrows.hip, wholegraph_amd_ext.h section 2i); nullptr in a backend without
+  int (*relagg_backward)(const wm_relagg_args* a, const wm_edge_index& ix, void* workspace, void* stream);
+  // ---- 8-bit row-quantized tables (kernels/qrows.hip, wholegraph_amd_ext.h section 2i); nullptr in a backend without
   // them ----
   int (*qrows_gather_dequant)(const wm_qrows_args* a, void* stream);
   int (*qrows_quantize_scatter)(const wm_qrows_args* a, void* stream);
@@ -734,17 +724,15 @@ struct wm_device_backend {
   size_t (*tconv_forward_workspace_bytes)(const wm_tconv_args* a);
   int (*tconv_forward)(const wm_tconv_args* a, void* workspace, void* stream);
   // backward: whichever of grad_key, grad_query and grad_value is not null. The index of gat_backward (read for grad_key and
-  // grad_value only: nullptr otherwise); workspace of tconv_backward_workspace_bytes
+  // grad_value only: all null otherwise); workspace of tconv_backward_workspace_bytes
   size_t (*tconv_backward_workspace_bytes)(const wm_tconv_args* a);
-  int (*tconv_backward)(const wm_tconv_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                        const int64_t* n_unique_dev, void* workspace, void* stream);
+  int (*tconv_backward)(const wm_tconv_args* a, const wm_edge_index& ix, void* workspace, void* stream);
   // ---- multi-aggregator neighbour aggregation of a sampled CSC block (kernels/pna.hip, wholegraph_amd_ext.h section 2l);
   // nullptr in a backend without it. The forward needs no workspace; the backward takes the index of agg_backward and a
   // workspace of pna_backward_workspace_bytes(n_edges, n_src, dim) ----
   int (*pna_forward)(const wm_pna_args* a, void* stream);
   size_t (*pna_backward_workspace_bytes)(int64_t n_edges, int64_t n_src, int64_t dim);
-  int (*pna_backward)(const wm_pna_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                      const int64_t* n_unique_dev, void* workspace, void* stream);
+  int (*pna_backward)(const wm_pna_args* a, const wm_edge_index& ix, void* workspace, void* stream);
   // ---- random walks (kernels/walk.hip, wholegraph_amd_ext.h section 2m); nullptr in a backend without them ----
   int (*walk_uniform)(const wm_walk_args* a, void* stream);
   int (*walk_weighted)(const wm_walk_args* a, void* stream);

@@ -13,116 +13,99 @@ namespace {
 
 using namespace wm;
 
-void check_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src,
-                const float* h, int64_t h_stride, const float* att, int64_t heads, int64_t dim, const float* alpha,
-                const float* scores)
+constexpr int64_t kMaxRow = int64_t(1) << 31, kMaxRowTconv = int64_t(1) << 30;   // heads * dim stays below these
+
+// what the args of every attention op hold alike, checked: the block (col_ind and alpha are read when a target has an
+// edge), heads, dim (heads * dim below `max_row`) and concat. rows: what the op calls its source rows
+template <class Args>
+Args attention_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src,
+                    const char* rows, int64_t heads, int64_t dim, int64_t max_row, int concat, const float* alpha)
 {
-  auto bad = [](const char* what) { throw invalid_input(what); };
-  check_block(row_ptr, col_ind, n_edges, n_dst, n_src, n_edges > 0 && n_dst > 0, "h");
-  if (heads < 1) bad("heads must be >= 1");
-  if (dim < 1) bad("dim must be >= 1");
-  if (n_src > 0 && h == nullptr) bad("h is null");
-  if (att == nullptr) bad("att is null");
-  if (n_edges > 0 && n_dst > 0 && alpha == nullptr) bad("alpha is null");
-  if (n_src > 0 && scores == nullptr) bad("scores is null");
-  if (h_stride < heads * dim) bad("h stride smaller than its row");
-  if (heads * dim >= (int64_t(1) << 31)) bad("heads * dim too large");
+  Args a{};
+  static_cast<wm_csc_block&>(a) = checked_block(row_ptr, col_ind, n_edges, n_dst, n_src, n_edges > 0 && n_dst > 0, rows);
+  checked_heads(heads, dim, max_row);
+  if (a.n_edges > 0 && alpha == nullptr) throw invalid_input("alpha is null");
+  a.heads  = heads;
+  a.dim    = dim;
+  a.concat = concat ? 1 : 0;
+  a.alpha  = const_cast<float*>(alpha);   // (written by the forward only)
+  return a;
 }
 
+// a gradient that may be left out: only its stride is judged, and only when it is asked for
+void check_optional_rows(const void* p, int64_t stride, int64_t row, const char* what)
+{
+  if (p != nullptr) check_rows(p, false, stride, row, what);
+}
+
+// what (2c) and (2f) share between forward and backward: h, att and the scores
 wm_gat_args make_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src,
                       const float* h, int64_t h_stride, const float* att, int64_t heads, int64_t dim, float slope,
                       int concat, const float* alpha, const float* scores)
 {
-  wm_gat_args a{};
-  a.row_ptr  = row_ptr;
-  a.col_ind  = col_ind;
-  a.n_edges  = n_dst == 0 ? 0 : n_edges;   // (no target, no edge of any target)
-  a.n_dst    = n_dst;
-  a.n_src    = n_src;
-  a.heads    = heads;
-  a.dim      = dim;
+  auto a = attention_args<wm_gat_args>(row_ptr, col_ind, n_edges, n_dst, n_src, "h", heads, dim, kMaxRow, concat, alpha);
+  check_rows(h, n_src > 0, h_stride, heads * dim, "h");
+  if (att == nullptr) throw invalid_input("att is null");
+  if (n_src > 0 && scores == nullptr) throw invalid_input("scores is null");
   a.slope    = slope;
-  a.concat   = concat ? 1 : 0;
   a.h        = h;
   a.h_stride = h_stride;
   a.att      = att;
-  a.alpha    = const_cast<float*>(alpha);    // (written by the forward only)
   a.scores   = const_cast<float*>(scores);   // (written by the forward only)
   return a;
 }
 
-// what (2g) shares between its forward and backward: the checks of (2c), minus the scores, plus h_dst
+// what (2f) adds to make_args in forward and backward: the rows and the scores of the edges
+wm_gat_edge_args make_edge_args(const wm_gat_args& g, const float* edge_feat, int64_t ef_stride, const float* edge_scores)
+{
+  check_rows(edge_feat, g.n_edges > 0, ef_stride, g.heads * g.dim, "edge_feat");
+  if (g.n_edges > 0 && edge_scores == nullptr) throw invalid_input("edge_scores is null");
+  wm_gat_edge_args a{};
+  a.g           = g;
+  a.edge_feat   = edge_feat;
+  a.ef_stride   = ef_stride;
+  a.edge_scores = const_cast<float*>(edge_scores);   // (written by the forward only)
+  return a;
+}
+
+// what (2g) shares between its forward and backward: h_src, h_dst and att
 wm_gatv2_args make_v2_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src,
                            const float* h_src, int64_t h_src_stride, const float* h_dst, int64_t h_dst_stride,
                            const float* att, int64_t heads, int64_t dim, float slope, int concat, const float* alpha)
 {
-  auto bad = [](const char* what) { throw invalid_input(what); };
-  check_block(row_ptr, col_ind, n_edges, n_dst, n_src, n_edges > 0 && n_dst > 0, "h_src");
-  if (heads < 1) bad("heads must be >= 1");
-  if (dim < 1) bad("dim must be >= 1");
-  if (n_src > 0 && h_src == nullptr) bad("h_src is null");
-  if (n_dst > 0 && h_dst == nullptr) bad("h_dst is null");
-  if (att == nullptr) bad("att is null");
-  if (n_edges > 0 && n_dst > 0 && alpha == nullptr) bad("alpha is null");
-  if (h_src_stride < heads * dim) bad("h_src stride smaller than its row");
-  if (h_dst_stride < heads * dim) bad("h_dst stride smaller than its row");
-  if (heads * dim >= (int64_t(1) << 31)) bad("heads * dim too large");
-  wm_gatv2_args a{};
-  a.row_ptr      = row_ptr;
-  a.col_ind      = col_ind;
-  a.n_edges      = n_dst == 0 ? 0 : n_edges;   // (no target, no edge of any target)
-  a.n_dst        = n_dst;
-  a.n_src        = n_src;
-  a.heads        = heads;
-  a.dim          = dim;
+  auto a = attention_args<wm_gatv2_args>(row_ptr, col_ind, n_edges, n_dst, n_src, "h_src", heads, dim, kMaxRow, concat, alpha);
+  check_rows(h_src, n_src > 0, h_src_stride, heads * dim, "h_src");
+  check_rows(h_dst, n_dst > 0, h_dst_stride, heads * dim, "h_dst");
+  if (att == nullptr) throw invalid_input("att is null");
   a.slope        = slope;
-  a.concat       = concat ? 1 : 0;
   a.h_src        = h_src;
   a.h_src_stride = h_src_stride;
   a.h_dst        = h_dst;
   a.h_dst_stride = h_dst_stride;
   a.att          = att;
-  a.alpha        = const_cast<float*>(alpha);   // (written by the forward only)
   return a;
 }
 
-// what (2k) shares between its forward and backward: the checks of (2g) with key / query / value in place of h_src / h_dst
-// / att, and the scale, both of whose operations the host rounds correctly
+// what (2k) shares between its forward and backward: key, query and value, and the scale, both of whose operations the
+// host rounds correctly
 wm_tconv_args make_tconv_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src,
                               const float* key, int64_t key_stride, const float* query, int64_t query_stride,
                               const float* value, int64_t value_stride, int64_t heads, int64_t dim, int norm_by_dim,
                               int concat, const float* alpha)
 {
-  auto bad = [](const char* what) { throw invalid_input(what); };
-  check_block(row_ptr, col_ind, n_edges, n_dst, n_src, n_edges > 0 && n_dst > 0, "key");
-  if (heads < 1) bad("heads must be >= 1");
-  if (dim < 1) bad("dim must be >= 1");
-  if (n_src > 0 && key == nullptr) bad("key is null");
-  if (n_src > 0 && value == nullptr) bad("value is null");
-  if (n_dst > 0 && query == nullptr) bad("query is null");
-  if (n_edges > 0 && n_dst > 0 && alpha == nullptr) bad("alpha is null");
-  if (key_stride < heads * dim) bad("key stride smaller than its row");
-  if (query_stride < heads * dim) bad("query stride smaller than its row");
-  if (value_stride < heads * dim) bad("value stride smaller than its row");
-  if (heads * dim >= (int64_t(1) << 30)) bad("heads * dim too large");
-  wm_tconv_args a{};
-  a.row_ptr      = row_ptr;
-  a.col_ind      = col_ind;
-  a.n_edges      = n_dst == 0 ? 0 : n_edges;   // (no target, no edge of any target)
-  a.n_dst        = n_dst;
-  a.n_src        = n_src;
-  a.heads        = heads;
-  a.dim          = dim;
+  auto a = attention_args<wm_tconv_args>(row_ptr, col_ind, n_edges, n_dst, n_src, "key", heads, dim, kMaxRowTconv, concat,
+                                         alpha);
+  check_rows(key, n_src > 0, key_stride, heads * dim, "key");
+  check_rows(value, n_src > 0, value_stride, heads * dim, "value");
+  check_rows(query, n_dst > 0, query_stride, heads * dim, "query");
   a.norm_by_dim  = norm_by_dim ? 1 : 0;
   a.scale        = 1.0f / sqrtf(static_cast<float>(dim));
-  a.concat       = concat ? 1 : 0;
   a.key          = key;
   a.key_stride   = key_stride;
   a.query        = query;
   a.query_stride = query_stride;
   a.value        = value;
   a.value_stride = value_stride;
-  a.alpha        = const_cast<float*>(alpha);   // (written by the forward only)
   return a;
 }
 
@@ -137,20 +120,16 @@ wholememory_error_code_t wholememory_ext_csc_gat_forward(const int32_t* row_ptr,
                                                          float* scores, wholememory_env_func_t* p_env_fns, void* stream)
 {
   WM_API_BEGIN
-  const auto* bk = backend();
-  if (bk->gat_forward == nullptr || bk->gat_forward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
-  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, h, h_stride, att, heads, dim, alpha, scores);
-  if (n_dst > 0 && out == nullptr) throw invalid_input("out is null");
-  if (out_stride < (concat ? heads * dim : dim)) throw invalid_input("out stride smaller than its row");
-  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
   wm_gat_args a = make_args(row_ptr, col_ind, n_edges, n_dst, n_src, h, h_stride, att, heads, dim, negative_slope, concat,
                             alpha, scores);
-  a.out         = out;
-  a.out_stride  = out_stride;
-  temp_mem ws(p_env_fns);
-  const size_t wb = bk->gat_forward_workspace_bytes(&a);
-  void* d_ws      = wb > 0 ? ws.device(static_cast<int64_t>(wb), WHOLEMEMORY_DT_INT8) : nullptr;
-  WM_BK(bk->gat_forward(&a, d_ws, stream));
+  check_out_rows(out, out_stride, n_dst, concat, heads, dim, "out");
+  check_env(p_env_fns);
+  const auto* bk = backend();
+  if (bk->gat_forward == nullptr || bk->gat_forward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  a.out        = out;
+  a.out_stride = out_stride;
+  forward_with_workspace(bk->gat_forward_workspace_bytes(&a), p_env_fns,
+                         [&](void* ws) { WM_BK(bk->gat_forward(&a, ws, stream)); });
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }
@@ -164,27 +143,21 @@ wholememory_error_code_t wholememory_ext_csc_gat_backward(const int32_t* row_ptr
                                                           float* grad_att, wholememory_env_func_t* p_env_fns, void* stream)
 {
   WM_API_BEGIN
+  wm_gat_args a = make_args(row_ptr, col_ind, n_edges, n_dst, n_src, h, h_stride, att, heads, dim, negative_slope, concat,
+                            alpha, scores);
+  check_out_rows(grad_out, grad_out_stride, n_dst, concat, heads, dim, "grad_out");
+  check_rows(grad_h, n_src > 0, grad_h_stride, heads * dim, "grad_h");
+  if (grad_att == nullptr) throw invalid_input("grad_att is null");
+  check_env(p_env_fns);
   const auto* bk = backend();
   if (bk->gat_backward == nullptr || bk->gat_backward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
-  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, h, h_stride, att, heads, dim, alpha, scores);
-  if (n_dst > 0 && grad_out == nullptr) throw invalid_input("grad_out is null");
-  if (grad_out_stride < (concat ? heads * dim : dim)) throw invalid_input("grad_out stride smaller than its row");
-  if (n_src > 0 && grad_h == nullptr) throw invalid_input("grad_h is null");
-  if (grad_h_stride < heads * dim) throw invalid_input("grad_h stride smaller than its row");
-  if (grad_att == nullptr) throw invalid_input("grad_att is null");
-  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
-  wm_gat_args a   = make_args(row_ptr, col_ind, n_edges, n_dst, n_src, h, h_stride, att, heads, dim, negative_slope, concat,
-                              alpha, scores);
   a.grad          = grad_out;
   a.grad_stride   = grad_out_stride;
   a.grad_h        = grad_h;
   a.grad_h_stride = grad_h_stride;
   a.grad_att      = grad_att;
-  sorted_ids ix(p_env_fns);   // the edge index; a block without source rows has none: null pointers
-  temp_mem gat_ws(p_env_fns);
-  if (n_src > 0) sort_col_ind(&ix, col_ind, a.n_edges, n_src, stream);
-  void* d_gws = gat_ws.device(static_cast<int64_t>(bk->gat_backward_workspace_bytes(&a)), WHOLEMEMORY_DT_INT8);
-  WM_BK(bk->gat_backward(&a, ix.order, ix.starts, static_cast<const int32_t*>(ix.unique), ix.n_unique_dev, d_gws, stream));
+  backward_over_index(a, true, bk->gat_backward_workspace_bytes(&a), p_env_fns, stream,
+                      [&](const wm_edge_index& ix, void* ws) { WM_BK(bk->gat_backward(&a, ix, ws, stream)); });
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }
@@ -196,27 +169,17 @@ wholememory_error_code_t wholememory_ext_csc_gat_edge_forward(
   wholememory_env_func_t* p_env_fns, void* stream)
 {
   WM_API_BEGIN
+  wm_gat_edge_args a = make_edge_args(make_args(row_ptr, col_ind, n_edges, n_dst, n_src, h, h_stride, att, heads, dim,
+                                                negative_slope, concat, alpha, scores),
+                                      edge_feat, ef_stride, edge_scores);
+  check_out_rows(out, out_stride, n_dst, concat, heads, dim, "out");
+  check_env(p_env_fns);
   const auto* bk = backend();
   if (bk->gat_edge_forward == nullptr || bk->gat_forward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
-  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, h, h_stride, att, heads, dim, alpha, scores);
-  if (n_edges > 0 && n_dst > 0 && edge_feat == nullptr) throw invalid_input("edge_feat is null");
-  if (n_edges > 0 && n_dst > 0 && edge_scores == nullptr) throw invalid_input("edge_scores is null");
-  if (ef_stride < heads * dim) throw invalid_input("edge_feat stride smaller than its row");
-  if (n_dst > 0 && out == nullptr) throw invalid_input("out is null");
-  if (out_stride < (concat ? heads * dim : dim)) throw invalid_input("out stride smaller than its row");
-  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
-  wm_gat_edge_args a{};
-  a.g = make_args(row_ptr, col_ind, n_edges, n_dst, n_src, h, h_stride, att, heads, dim, negative_slope, concat, alpha,
-                  scores);
   a.g.out        = out;
   a.g.out_stride = out_stride;
-  a.edge_feat    = edge_feat;
-  a.ef_stride    = ef_stride;
-  a.edge_scores  = edge_scores;
-  temp_mem ws(p_env_fns);
-  const size_t wb = bk->gat_forward_workspace_bytes(&a.g);
-  void* d_ws      = wb > 0 ? ws.device(static_cast<int64_t>(wb), WHOLEMEMORY_DT_INT8) : nullptr;
-  WM_BK(bk->gat_edge_forward(&a, d_ws, stream));
+  forward_with_workspace(bk->gat_forward_workspace_bytes(&a.g), p_env_fns,
+                         [&](void* ws) { WM_BK(bk->gat_edge_forward(&a, ws, stream)); });
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }
@@ -229,39 +192,26 @@ wholememory_error_code_t wholememory_ext_csc_gat_edge_backward(
   float* grad_edge_feat, int64_t grad_ef_stride, wholememory_env_func_t* p_env_fns, void* stream)
 {
   WM_API_BEGIN
+  wm_gat_edge_args a = make_edge_args(make_args(row_ptr, col_ind, n_edges, n_dst, n_src, h, h_stride, att, heads, dim,
+                                                negative_slope, concat, alpha, scores),
+                                      edge_feat, ef_stride, edge_scores);
+  check_rows(grad_edge_feat, a.g.n_edges > 0, grad_ef_stride, heads * dim, "grad_edge_feat");
+  check_out_rows(grad_out, grad_out_stride, n_dst, concat, heads, dim, "grad_out");
+  check_rows(grad_h, n_src > 0, grad_h_stride, heads * dim, "grad_h");
+  if (grad_att == nullptr) throw invalid_input("grad_att is null");
+  check_env(p_env_fns);
   const auto* bk = backend();
   if (bk->gat_edge_backward == nullptr || bk->gat_edge_backward_workspace_bytes == nullptr)
     return WHOLEMEMORY_NOT_SUPPORTED;
-  check_args(row_ptr, col_ind, n_edges, n_dst, n_src, h, h_stride, att, heads, dim, alpha, scores);
-  if (n_edges > 0 && n_dst > 0 && edge_feat == nullptr) throw invalid_input("edge_feat is null");
-  if (n_edges > 0 && n_dst > 0 && edge_scores == nullptr) throw invalid_input("edge_scores is null");
-  if (n_edges > 0 && n_dst > 0 && grad_edge_feat == nullptr) throw invalid_input("grad_edge_feat is null");
-  if (ef_stride < heads * dim) throw invalid_input("edge_feat stride smaller than its row");
-  if (grad_ef_stride < heads * dim) throw invalid_input("grad_edge_feat stride smaller than its row");
-  if (n_dst > 0 && grad_out == nullptr) throw invalid_input("grad_out is null");
-  if (grad_out_stride < (concat ? heads * dim : dim)) throw invalid_input("grad_out stride smaller than its row");
-  if (n_src > 0 && grad_h == nullptr) throw invalid_input("grad_h is null");
-  if (grad_h_stride < heads * dim) throw invalid_input("grad_h stride smaller than its row");
-  if (grad_att == nullptr) throw invalid_input("grad_att is null");
-  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
-  wm_gat_edge_args a{};
-  a.g = make_args(row_ptr, col_ind, n_edges, n_dst, n_src, h, h_stride, att, heads, dim, negative_slope, concat, alpha,
-                  scores);
   a.g.grad          = grad_out;
   a.g.grad_stride   = grad_out_stride;
   a.g.grad_h        = grad_h;
   a.g.grad_h_stride = grad_h_stride;
   a.g.grad_att      = grad_att;
-  a.edge_feat       = edge_feat;
-  a.ef_stride       = ef_stride;
-  a.edge_scores     = const_cast<float*>(edge_scores);   // (written by the forward only)
   a.grad_edge_feat  = grad_edge_feat;
   a.grad_ef_stride  = grad_ef_stride;
-  sorted_ids ix(p_env_fns);   // the edge index; a block without source rows has none: null pointers
-  temp_mem gat_ws(p_env_fns);
-  if (n_src > 0) sort_col_ind(&ix, col_ind, a.g.n_edges, n_src, stream);
-  void* d_gws = gat_ws.device(static_cast<int64_t>(bk->gat_edge_backward_workspace_bytes(&a)), WHOLEMEMORY_DT_INT8);
-  WM_BK(bk->gat_edge_backward(&a, ix.order, ix.starts, static_cast<const int32_t*>(ix.unique), ix.n_unique_dev, d_gws, stream));
+  backward_over_index(a.g, true, bk->gat_edge_backward_workspace_bytes(&a), p_env_fns, stream,
+                      [&](const wm_edge_index& ix, void* ws) { WM_BK(bk->gat_edge_backward(&a, ix, ws, stream)); });
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }
@@ -274,20 +224,16 @@ wholememory_error_code_t wholememory_ext_csc_gatv2_forward(const int32_t* row_pt
                                                            float* alpha, wholememory_env_func_t* p_env_fns, void* stream)
 {
   WM_API_BEGIN
-  const auto* bk = backend();
   wm_gatv2_args a = make_v2_args(row_ptr, col_ind, n_edges, n_dst, n_src, h_src, h_src_stride, h_dst, h_dst_stride, att,
                                  heads, dim, negative_slope, concat, alpha);
-  if (n_dst > 0 && out == nullptr) throw invalid_input("out is null");
-  if (out_stride < (concat ? heads * dim : dim)) throw invalid_input("out stride smaller than its row");
-  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
-  // (after the checks: a malformed call is INVALID_INPUT under every backend)
+  check_out_rows(out, out_stride, n_dst, concat, heads, dim, "out");
+  check_env(p_env_fns);
+  const auto* bk = backend();
   if (bk->gatv2_forward == nullptr || bk->gatv2_forward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
   a.out        = out;
   a.out_stride = out_stride;
-  temp_mem ws(p_env_fns);
-  const size_t wb = bk->gatv2_forward_workspace_bytes(&a);
-  void* d_ws      = wb > 0 ? ws.device(static_cast<int64_t>(wb), WHOLEMEMORY_DT_INT8) : nullptr;
-  WM_BK(bk->gatv2_forward(&a, d_ws, stream));
+  forward_with_workspace(bk->gatv2_forward_workspace_bytes(&a), p_env_fns,
+                         [&](void* ws) { WM_BK(bk->gatv2_forward(&a, ws, stream)); });
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }
@@ -300,15 +246,14 @@ wholememory_error_code_t wholememory_ext_csc_gatv2_backward(
   wholememory_env_func_t* p_env_fns, void* stream)
 {
   WM_API_BEGIN
-  const auto* bk = backend();
   wm_gatv2_args a = make_v2_args(row_ptr, col_ind, n_edges, n_dst, n_src, h_src, h_src_stride, h_dst, h_dst_stride, att,
                                  heads, dim, negative_slope, concat, alpha);
-  if (n_dst > 0 && grad_out == nullptr) throw invalid_input("grad_out is null");
-  if (grad_out_stride < (concat ? heads * dim : dim)) throw invalid_input("grad_out stride smaller than its row");
+  check_out_rows(grad_out, grad_out_stride, n_dst, concat, heads, dim, "grad_out");
   if (grad_h_src == nullptr && grad_h_dst == nullptr && grad_att == nullptr) throw invalid_input("no gradient asked for");
-  if (grad_h_src != nullptr && grad_h_src_stride < heads * dim) throw invalid_input("grad_h_src stride smaller than its row");
-  if (grad_h_dst != nullptr && grad_h_dst_stride < heads * dim) throw invalid_input("grad_h_dst stride smaller than its row");
-  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
+  check_optional_rows(grad_h_src, grad_h_src_stride, heads * dim, "grad_h_src");
+  check_optional_rows(grad_h_dst, grad_h_dst_stride, heads * dim, "grad_h_dst");
+  check_env(p_env_fns);
+  const auto* bk = backend();
   if (bk->gatv2_backward == nullptr || bk->gatv2_backward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
   a.grad              = grad_out;
   a.grad_stride       = grad_out_stride;
@@ -317,11 +262,9 @@ wholememory_error_code_t wholememory_ext_csc_gatv2_backward(
   a.grad_h_dst        = grad_h_dst;
   a.grad_h_dst_stride = grad_h_dst_stride;
   a.grad_att          = grad_att;
-  sorted_ids ix(p_env_fns);   // the edge index of grad_h_src; without that gradient, or without source rows: null pointers
-  temp_mem gat_ws(p_env_fns);
-  if (grad_h_src != nullptr && n_src > 0) sort_col_ind(&ix, col_ind, a.n_edges, n_src, stream);
-  void* d_gws = gat_ws.device(static_cast<int64_t>(bk->gatv2_backward_workspace_bytes(&a)), WHOLEMEMORY_DT_INT8);
-  WM_BK(bk->gatv2_backward(&a, ix.order, ix.starts, static_cast<const int32_t*>(ix.unique), ix.n_unique_dev, d_gws, stream));
+  // (the edge index is read for grad_h_src only)
+  backward_over_index(a, grad_h_src != nullptr, bk->gatv2_backward_workspace_bytes(&a), p_env_fns, stream,
+                      [&](const wm_edge_index& ix, void* ws) { WM_BK(bk->gatv2_backward(&a, ix, ws, stream)); });
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }
@@ -333,20 +276,16 @@ wholememory_error_code_t wholememory_ext_csc_mha_simple_forward(
   void* stream)
 {
   WM_API_BEGIN
-  const auto* bk  = backend();
   wm_tconv_args a = make_tconv_args(row_ptr, col_ind, n_edges, n_dst, n_src, key, key_stride, query, query_stride, value,
                                     value_stride, heads, dim, norm_by_dim, concat, alpha);
-  if (n_dst > 0 && out == nullptr) throw invalid_input("out is null");
-  if (out_stride < (concat ? heads * dim : dim)) throw invalid_input("out stride smaller than its row");
-  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
-  // (after the checks: a malformed call is INVALID_INPUT under every backend)
+  check_out_rows(out, out_stride, n_dst, concat, heads, dim, "out");
+  check_env(p_env_fns);
+  const auto* bk = backend();
   if (bk->tconv_forward == nullptr || bk->tconv_forward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
   a.out        = out;
   a.out_stride = out_stride;
-  temp_mem ws(p_env_fns);
-  const size_t wb = bk->tconv_forward_workspace_bytes(&a);
-  void* d_ws      = wb > 0 ? ws.device(static_cast<int64_t>(wb), WHOLEMEMORY_DT_INT8) : nullptr;
-  WM_BK(bk->tconv_forward(&a, d_ws, stream));
+  forward_with_workspace(bk->tconv_forward_workspace_bytes(&a), p_env_fns,
+                         [&](void* ws) { WM_BK(bk->tconv_forward(&a, ws, stream)); });
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }
@@ -359,16 +298,15 @@ wholememory_error_code_t wholememory_ext_csc_mha_simple_backward(
   int64_t grad_value_stride, wholememory_env_func_t* p_env_fns, void* stream)
 {
   WM_API_BEGIN
-  const auto* bk  = backend();
   wm_tconv_args a = make_tconv_args(row_ptr, col_ind, n_edges, n_dst, n_src, key, key_stride, query, query_stride, value,
                                     value_stride, heads, dim, norm_by_dim, concat, alpha);
-  if (n_dst > 0 && grad_out == nullptr) throw invalid_input("grad_out is null");
-  if (grad_out_stride < (concat ? heads * dim : dim)) throw invalid_input("grad_out stride smaller than its row");
+  check_out_rows(grad_out, grad_out_stride, n_dst, concat, heads, dim, "grad_out");
   if (grad_key == nullptr && grad_query == nullptr && grad_value == nullptr) throw invalid_input("no gradient asked for");
-  if (grad_key != nullptr && grad_key_stride < heads * dim) throw invalid_input("grad_key stride smaller than its row");
-  if (grad_query != nullptr && grad_query_stride < heads * dim) throw invalid_input("grad_query stride smaller than its row");
-  if (grad_value != nullptr && grad_value_stride < heads * dim) throw invalid_input("grad_value stride smaller than its row");
-  if (p_env_fns == nullptr) throw invalid_input("p_env_fns is null");
+  check_optional_rows(grad_key, grad_key_stride, heads * dim, "grad_key");
+  check_optional_rows(grad_query, grad_query_stride, heads * dim, "grad_query");
+  check_optional_rows(grad_value, grad_value_stride, heads * dim, "grad_value");
+  check_env(p_env_fns);
+  const auto* bk = backend();
   if (bk->tconv_backward == nullptr || bk->tconv_backward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
   a.grad              = grad_out;
   a.grad_stride       = grad_out_stride;
@@ -378,12 +316,9 @@ wholememory_error_code_t wholememory_ext_csc_mha_simple_backward(
   a.grad_query_stride = grad_query_stride;
   a.grad_value        = grad_value;
   a.grad_value_stride = grad_value_stride;
-  // the edge index of grad_key and grad_value; without both, or without source rows: null pointers
-  sorted_ids ix(p_env_fns);
-  temp_mem tconv_ws(p_env_fns);
-  if ((grad_key != nullptr || grad_value != nullptr) && n_src > 0) sort_col_ind(&ix, col_ind, a.n_edges, n_src, stream);
-  void* d_ws = tconv_ws.device(static_cast<int64_t>(bk->tconv_backward_workspace_bytes(&a)), WHOLEMEMORY_DT_INT8);
-  WM_BK(bk->tconv_backward(&a, ix.order, ix.starts, static_cast<const int32_t*>(ix.unique), ix.n_unique_dev, d_ws, stream));
+  // (the edge index is read for grad_key and grad_value only)
+  backward_over_index(a, grad_key != nullptr || grad_value != nullptr, bk->tconv_backward_workspace_bytes(&a), p_env_fns,
+                      stream, [&](const wm_edge_index& ix, void* ws) { WM_BK(bk->tconv_backward(&a, ix, ws, stream)); });
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }

@@ -170,40 +170,33 @@ size_t hip_agg_backward_workspace_bytes(int64_t n_edges, int64_t n_src, int64_t 
   return agg_bwd_plan(n_edges, n_src, dim, kAggChunkEdges).ws.bytes;
 }
 
-int agg_bwd_prepare(const int32_t* row_ptr, int64_t n_dst, int64_t n_edges, int64_t n_src, int64_t dim, const int32_t* order,
-                    const int32_t* run_starts, const int32_t* unique_ids, const int64_t* n_unique_dev, void* workspace,
-                    csc_bwd_index* bp, void* stream_v)
+int agg_bwd_prepare(const wm_csc_block& blk, int64_t dim, const wm_edge_index& ix, void* workspace, csc_bwd_index* bp,
+                    void* stream_v)
 {
   hipStream_t stream     = static_cast<hipStream_t>(stream_v);
-  const agg_bwd_layout l = agg_bwd_plan(n_edges, n_src, dim, kAggChunkEdges);
+  const agg_bwd_layout l = agg_bwd_plan(blk.n_edges, blk.n_src, dim, kAggChunkEdges);
   csc_bwd_index& b       = *bp;
-  b.order                = order;
-  b.run_starts           = run_starts;
-  b.unique_ids           = unique_ids;
-  b.n_unique             = n_unique_dev;
+  set_sorted(b, ix);
   b.sorted_dst           = ws_at<int32_t>(workspace, l.ws.off[0]);
   b.run_of               = ws_at<int32_t>(workspace, l.ws.off[1]);
   b.partial              = ws_at<float>(workspace, l.ws.off[2]);
   b.n_tiles              = l.n_tiles;
   b.partial_stride       = l.partial_stride;
-  if (n_edges > 0) {
-    const int blocks = blocks_for(n_edges, kAggBlock);
-    hipLaunchKernelGGL(agg_bwd_prep_kernel, dim3(blocks < 8192 ? blocks : 8192), dim3(kAggBlock), 0, stream, row_ptr, n_dst,
-                       n_edges, b);
+  if (blk.n_edges > 0) {
+    const int blocks = blocks_for(blk.n_edges, kAggBlock);
+    hipLaunchKernelGGL(agg_bwd_prep_kernel, dim3(blocks < 8192 ? blocks : 8192), dim3(kAggBlock), 0, stream, blk.row_ptr,
+                       blk.n_dst, blk.n_edges, b);
     if (rc_last() != 0) return -2;
   }
   return 0;
 }
 
-int hip_agg_backward(const wm_agg_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                     const int64_t* n_unique_dev, void* workspace, void* stream_v)
+int hip_agg_backward(const wm_agg_args* a, const wm_edge_index& ix, void* workspace, void* stream_v)
 {
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   if (a->n_src == 0 || a->dim == 0) return 0;
   wm_agg_bwd_state b;
-  if (agg_bwd_prepare(a->row_ptr, a->n_dst, a->n_edges, a->n_src, a->dim, order, run_starts, unique_ids, n_unique_dev,
-                      workspace, &b, stream_v) != 0)
-    return -2;
+  if (agg_bwd_prepare(*a, a->dim, ix, workspace, &b, stream_v) != 0) return -2;
   const bool v4 = use_vec4(a->dim, a->grad, a->grad_stride, a->out, a->out_stride);
   if (b.n_tiles > 1) {   // (one tile holds no chunk k >= 1)
 #define WM_AGG_CHUNK(V, L)                                                                                                   \

@@ -1,7 +1,8 @@
 // wholegraph_amd — device and launch helpers shared by the ops of a sampled CSC block (kernels/agg.hip, agg_half.hip,
-// agg_weighted.hip and agg_rel.hip, the `agg_concat` family; kernels/gat.hip, gat_edge.hip, gatv2.hip and tconv.hip, the
-// attention ops): fp32 pieces of a row, the clamped edge range of a target, the launch shape, and the walk of the deterministic
-// per-source backward over the id sort: its index (csc_bwd_index), the run of a source (run_of_source), the partial rows
+// agg_weighted.hip, agg_rel.hip, agg_gather.hip, agg_quant.hip and pna.hip, the `agg_concat` family; kernels/gat.hip,
+// gat_edge.hip, gatv2.hip and tconv.hip, the attention ops), whose args all begin with the wm_csc_block of backend.hpp:
+// fp32 pieces of a row, the clamped edge range of a target, the launch shape, and the walk of the deterministic per-source
+// backward over the host's wm_edge_index: its index (csc_bwd_index), the run of a source (run_of_source), the partial rows
 // of a run's later chunks (add_partials), the tile loop of a chunk kernel (for_chunk_pieces) and the self term of the
 // agg_concat ops (with_self_term). What an op adds per edge, its fold_edges*, stays in the op's own file.
 #pragma once
@@ -32,11 +33,19 @@ struct csc_bwd_index {
 };
 using wm_agg_bwd_state = csc_bwd_index;   // the agg_concat ops need nothing more
 
-// fills `b` from the id sort's outputs and `workspace` (hip_agg_backward_workspace_bytes: agg_bwd_plan lays out both) for
-// partial rows of `dim` columns and queues agg_bwd_prep_kernel (kernels/agg.hip). 0 or -2.
-int agg_bwd_prepare(const int32_t* row_ptr, int64_t n_dst, int64_t n_edges, int64_t n_src, int64_t dim, const int32_t* order,
-                    const int32_t* run_starts, const int32_t* unique_ids, const int64_t* n_unique_dev, void* workspace,
-                    csc_bwd_index* b, void* stream);
+// the id sort's outputs, as the host hands them over, into the index
+inline void set_sorted(csc_bwd_index& b, const wm_edge_index& ix)
+{
+  b.order      = ix.order;
+  b.run_starts = ix.run_starts;
+  b.unique_ids = ix.unique_ids;
+  b.n_unique   = ix.n_unique_dev;
+}
+
+// fills `b` from the edge index and `workspace` (hip_agg_backward_workspace_bytes: agg_bwd_plan lays out both) for partial
+// rows of `dim` columns and queues agg_bwd_prep_kernel (kernels/agg.hip). 0 or -2.
+int agg_bwd_prepare(const wm_csc_block& blk, int64_t dim, const wm_edge_index& ix, void* workspace, csc_bwd_index* b,
+                    void* stream);
 
 namespace {
 

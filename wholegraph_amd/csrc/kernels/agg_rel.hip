@@ -280,15 +280,12 @@ int hip_relagg_forward(const wm_relagg_args* a, void* stream_v)
   return rc_last();
 }
 
-int hip_relagg_backward(const wm_relagg_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                        const int64_t* n_unique_dev, void* workspace, void* stream_v)
+int hip_relagg_backward(const wm_relagg_args* a, const wm_edge_index& ix, void* workspace, void* stream_v)
 {
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   if (a->n_src == 0 || a->dim == 0) return 0;
   wm_agg_bwd_state b;
-  if (agg_bwd_prepare(a->row_ptr, a->n_dst, a->n_edges, a->n_src, a->dim, order, run_starts, unique_ids, n_unique_dev,
-                      workspace, &b, stream_v) != 0)
-    return -2;
+  if (agg_bwd_prepare(*a, a->dim, ix, workspace, &b, stream_v) != 0) return -2;
   const bool v4 = use_vec4(a->dim, a->grad, a->grad_stride, a->out, a->out_stride);
   if (b.n_tiles > 1) {   // (one tile holds no chunk k >= 1)
 #define WM_RELAGG_CHUNK(V, L)                                                                                            \

@@ -72,45 +72,36 @@ int hip_sort_ids(const void* ids, wholememory_dtype_t index_dtype, int64_t n, in
                  void* sorted_ids, int64_t* raw, void* workspace, void* stream);
 int hip_agg_forward(const wm_agg_args* a, void* stream);
 size_t hip_agg_backward_workspace_bytes(int64_t n_edges, int64_t n_src, int64_t dim);
-int hip_agg_backward(const wm_agg_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                     const int64_t* n_unique_dev, void* workspace, void* stream);
+int hip_agg_backward(const wm_agg_args* a, const wm_edge_index& ix, void* workspace, void* stream);
 int hip_agg16_forward(const wm_agg16_args* a, void* stream);
-int hip_agg16_backward(const wm_agg16_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                       const int64_t* n_unique_dev, void* workspace, void* stream);
+int hip_agg16_backward(const wm_agg16_args* a, const wm_edge_index& ix, void* workspace, void* stream);
 int hip_aggw_forward(const wm_aggw_args* a, void* stream);
-int hip_aggw_backward(const wm_aggw_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                      const int64_t* n_unique_dev, void* workspace, void* stream);
+int hip_aggw_backward(const wm_aggw_args* a, const wm_edge_index& ix, void* workspace, void* stream);
 int hip_edge_attr_gather(const wm_edge_attr_args* a, void* stream);
 int hip_gather_agg_forward(const wm_gather_agg_args* a, void* stream);
 size_t hip_gat_forward_workspace_bytes(const wm_gat_args* a);
 int hip_gat_forward(const wm_gat_args* a, void* workspace, void* stream);
 size_t hip_gat_backward_workspace_bytes(const wm_gat_args* a);
-int hip_gat_backward(const wm_gat_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                     const int64_t* n_unique_dev, void* workspace, void* stream);
+int hip_gat_backward(const wm_gat_args* a, const wm_edge_index& ix, void* workspace, void* stream);
 int hip_gat_edge_forward(const wm_gat_edge_args* a, void* workspace, void* stream);
 size_t hip_gat_edge_backward_workspace_bytes(const wm_gat_edge_args* a);
-int hip_gat_edge_backward(const wm_gat_edge_args* a, const int32_t* order, const int32_t* run_starts,
-                          const int32_t* unique_ids, const int64_t* n_unique_dev, void* workspace, void* stream);
+int hip_gat_edge_backward(const wm_gat_edge_args* a, const wm_edge_index& ix, void* workspace, void* stream);
 size_t hip_gatv2_forward_workspace_bytes(const wm_gatv2_args* a);
 int hip_gatv2_forward(const wm_gatv2_args* a, void* workspace, void* stream);
 size_t hip_gatv2_backward_workspace_bytes(const wm_gatv2_args* a);
-int hip_gatv2_backward(const wm_gatv2_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                       const int64_t* n_unique_dev, void* workspace, void* stream);
+int hip_gatv2_backward(const wm_gatv2_args* a, const wm_edge_index& ix, void* workspace, void* stream);
 int hip_relagg_forward(const wm_relagg_args* a, void* stream);
-int hip_relagg_backward(const wm_relagg_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                        const int64_t* n_unique_dev, void* workspace, void* stream);
+int hip_relagg_backward(const wm_relagg_args* a, const wm_edge_index& ix, void* workspace, void* stream);
 int hip_qrows_gather_dequant(const wm_qrows_args* a, void* stream);
 int hip_qrows_quantize_scatter(const wm_qrows_args* a, void* stream);
 int hip_qagg_forward(const wm_qagg_args* a, void* stream);
 size_t hip_tconv_forward_workspace_bytes(const wm_tconv_args* a);
 int hip_tconv_forward(const wm_tconv_args* a, void* workspace, void* stream);
 size_t hip_tconv_backward_workspace_bytes(const wm_tconv_args* a);
-int hip_tconv_backward(const wm_tconv_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                       const int64_t* n_unique_dev, void* workspace, void* stream);
+int hip_tconv_backward(const wm_tconv_args* a, const wm_edge_index& ix, void* workspace, void* stream);
 int hip_pna_forward(const wm_pna_args* a, void* stream);
 size_t hip_pna_backward_workspace_bytes(int64_t n_edges, int64_t n_src, int64_t dim);
-int hip_pna_backward(const wm_pna_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                     const int64_t* n_unique_dev, void* workspace, void* stream);
+int hip_pna_backward(const wm_pna_args* a, const wm_edge_index& ix, void* workspace, void* stream);
 int hip_walk_uniform(const wm_walk_args* a, void* stream);
 int hip_walk_weighted(const wm_walk_args* a, void* stream);
 int hip_walk_node2vec(const wm_n2v_args* a, void* stream);

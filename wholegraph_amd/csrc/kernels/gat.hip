@@ -286,14 +286,11 @@ gat_bwd_layout bwd_layout(const wm_gat_args* a, int64_t extra_bytes)
 size_t gat_bwd_workspace_bytes(const wm_gat_args* a, int64_t extra_bytes) { return bwd_layout(a, extra_bytes).ws.bytes; }
 size_t hip_gat_backward_workspace_bytes(const wm_gat_args* a) { return gat_bwd_workspace_bytes(a, 0); }
 
-void* gat_bwd_carve(const wm_gat_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                    const int64_t* n_unique_dev, void* workspace, int64_t extra_bytes, wm_gat_bwd_state* b)
+void* gat_bwd_carve(const wm_gat_args* a, const wm_edge_index& ix, void* workspace, int64_t extra_bytes,
+                    wm_gat_bwd_state* b)
 {
   const gat_bwd_layout l = bwd_layout(a, extra_bytes);
-  b->ix.order          = order;
-  b->ix.run_starts     = run_starts;
-  b->ix.unique_ids     = unique_ids;
-  b->ix.n_unique       = n_unique_dev;
+  set_sorted(b->ix, ix);
   b->ix.sorted_dst     = ws_at<int32_t>(workspace, l.ws.off[0]);
   b->ix.run_of         = ws_at<int32_t>(workspace, l.ws.off[1]);
   b->dz                = ws_at<float>(workspace, l.ws.off[2]);
@@ -342,12 +339,11 @@ int gat_bwd_after_dz(const wm_gat_args* a, const wm_gat_bwd_state* bp, void* str
   return rc_last();
 }
 
-int hip_gat_backward(const wm_gat_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                     const int64_t* n_unique_dev, void* workspace, void* stream_v)
+int hip_gat_backward(const wm_gat_args* a, const wm_edge_index& ix, void* workspace, void* stream_v)
 {
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   wm_gat_bwd_state b;
-  gat_bwd_carve(a, order, run_starts, unique_ids, n_unique_dev, workspace, 0, &b);
+  gat_bwd_carve(a, ix, workspace, 0, &b);
   if (a->n_dst > 0) {
     const int blocks = blocks_for(a->n_dst * a->heads, kAggBlock);
     if (gat_bwd_vec4(a)) hipLaunchKernelGGL(gat_bwd_edge_kernel<4>, dim3(blocks), dim3(kAggBlock), 0, stream, *a, b);

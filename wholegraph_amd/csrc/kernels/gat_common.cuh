@@ -1,5 +1,5 @@
-// wholegraph_amd — what the two attention ops of a sampled CSC block share (kernels/gat.hip, the GAT `mha_gat_n2n` op, and
-// kernels/gat_edge.hip, the same op with an edge term in the logit): the scratch of the backward; the stages of gat.hip
+// wholegraph_amd — what the attention ops of a sampled CSC block share. Two of them (kernels/gat.hip, the GAT `mha_gat_n2n`
+// op, and kernels/gat_edge.hip, the same op with an edge term in the logit): the scratch of the backward; the stages of gat.hip
 // that do not see the logit — the node scores and the mean over heads of the forward, and everything of the backward
 // behind dz (wholegraph_amd_ext.h, section 2c), whose kernels live in gat.hip alone; and the bodies of the two stages that
 // do see it (gat_fwd_body, gat_bwd_dz_body), with the edge term of section 2f compiled in or out. And what the two ops with
@@ -27,10 +27,10 @@ int gat_scores(const wm_gat_args* a, void* stream);
 int gat_head_mean(const wm_gat_args* a, const float* o, int64_t o_stride, void* stream);
 // the backward's workspace with a last region of `extra_bytes` for the caller (gat_edge.hip's chunk sums; 0: none)
 size_t gat_bwd_workspace_bytes(const wm_gat_args* a, int64_t extra_bytes);
-// backward: fills `b` from the id sort's outputs and `workspace` (gat_bwd_workspace_bytes with the same extra_bytes);
-// returns the caller's region
-void* gat_bwd_carve(const wm_gat_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                    const int64_t* n_unique_dev, void* workspace, int64_t extra_bytes, wm_gat_bwd_state* b);
+// backward: fills `b` from the edge index and `workspace` (gat_bwd_workspace_bytes with the same extra_bytes); returns the
+// caller's region
+void* gat_bwd_carve(const wm_gat_args* a, const wm_edge_index& ix, void* workspace, int64_t extra_bytes,
+                    wm_gat_bwd_state* b);
 // backward behind b->dz and b->ds_dst (steps 2 - 4 of gat.hip): grad_h, ds_src and halves 0 and 1 of grad_att
 int gat_bwd_after_dz(const wm_gat_args* a, const wm_gat_bwd_state* b, void* stream);
 

@@ -170,15 +170,13 @@ size_t hip_gat_edge_backward_workspace_bytes(const wm_gat_edge_args* ea)
   return gat_bwd_workspace_bytes(a, edge_chunks(a) * a->heads * a->dim * 4);
 }
 
-int hip_gat_edge_backward(const wm_gat_edge_args* ea, const int32_t* order, const int32_t* run_starts,
-                          const int32_t* unique_ids, const int64_t* n_unique_dev, void* workspace, void* stream_v)
+int hip_gat_edge_backward(const wm_gat_edge_args* ea, const wm_edge_index& ix, void* workspace, void* stream_v)
 {
   hipStream_t stream   = static_cast<hipStream_t>(stream_v);
   const wm_gat_args* a = &ea->g;
   const int64_t HF     = a->heads * a->dim;
   wm_gat_bwd_state b;
-  float* epart  = static_cast<float*>(gat_bwd_carve(a, order, run_starts, unique_ids, n_unique_dev, workspace,
-                                                    edge_chunks(a) * HF * 4, &b));   // [chunks, HF]
+  float* epart  = static_cast<float*>(gat_bwd_carve(a, ix, workspace, edge_chunks(a) * HF * 4, &b));   // [chunks, HF]
   const bool f4 = gat_bwd_vec4(a);
   if (a->n_dst > 0) {
     const int blocks = blocks_for(a->n_dst * a->heads, kAggBlock);

@@ -458,17 +458,13 @@ int hip_gatv2_forward(const wm_gatv2_args* a, void* workspace, void* stream_v)
 
 size_t hip_gatv2_backward_workspace_bytes(const wm_gatv2_args* a) { return bwd_layout(a).ws.bytes; }
 
-int hip_gatv2_backward(const wm_gatv2_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                       const int64_t* n_unique_dev, void* workspace, void* stream_v)
+int hip_gatv2_backward(const wm_gatv2_args* a, const wm_edge_index& ix, void* workspace, void* stream_v)
 {
   hipStream_t stream       = static_cast<hipStream_t>(stream_v);
   const gatv2_bwd_layout l = bwd_layout(a);
   const int64_t H = a->heads, HF = H * a->dim;
   gatv2_bwd_state b;
-  b.ix.order          = order;
-  b.ix.run_starts     = run_starts;
-  b.ix.unique_ids     = unique_ids;
-  b.ix.n_unique       = n_unique_dev;
+  set_sorted(b.ix, ix);
   b.ix.sorted_dst     = ws_at<int32_t>(workspace, l.ws.off[0]);
   b.ix.run_of         = ws_at<int32_t>(workspace, l.ws.off[1]);
   b.da                = ws_at<float>(workspace, l.ws.off[2]);

@@ -309,15 +309,12 @@ size_t hip_pna_backward_workspace_bytes(int64_t n_edges, int64_t n_src, int64_t 
   return agg_bwd_plan(n_edges, n_src, dim, kAggChunkEdges).ws.bytes;
 }
 
-int hip_pna_backward(const wm_pna_args* a, const int32_t* order, const int32_t* run_starts, const int32_t* unique_ids,
-                     const int64_t* n_unique_dev, void* workspace, void* stream_v)
+int hip_pna_backward(const wm_pna_args* a, const wm_edge_index& ix, void* workspace, void* stream_v)
 {
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   if (a->n_src == 0 || a->dim == 0) return 0;
   wm_agg_bwd_state b;
-  if (agg_bwd_prepare(a->row_ptr, a->n_dst, a->n_edges, a->n_src, a->dim, order, run_starts, unique_ids, n_unique_dev,
-                      workspace, &b, stream_v) != 0)
-    return -2;
+  if (agg_bwd_prepare(*a, a->dim, ix, workspace, &b, stream_v) != 0) return -2;
   const bool std_rows = (a->mask & WM_PNA_STD) != 0;   // (x is read for std only)
   const bool v4       = use_vec4(a->dim, a->grad, a->grad_stride, a->out, a->out_stride) && saved_vec4(a) &&
                   (!std_rows || (a->in_stride % 4 == 0 && aligned16(a->in)));

@@ -61,6 +61,44 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def _opt_ptr(t):
+    """None stays None: the null pointer of a tensor that is left out"""
+    return _ptr(t) if t is not None else None
+
+
+def _stride(t: torch.Tensor, width: int) -> int:
+    """the row stride the library is told: a tensor without rows has none worth trusting, so the width of a row"""
+    return t.stride(0) if t.shape[0] else width
+
+
+def _widen(t: torch.Tensor) -> torch.Tensor:
+    """what custom_fwd's cast_inputs does, ahead of the dtype checks of an fp32-only op: inside autocast a 16-bit GPU
+    tensor is widened"""
+    if t.is_cuda and t.dtype in (torch.float16, torch.bfloat16) and torch.is_autocast_enabled("cuda"):
+        return t.float()
+    return t
+
+
+def _block(csr_row_ptr: torch.Tensor, csr_col_ind: torch.Tensor, device, **rows):
+    """(row_ptr, col_ind) as int32 on `device`; every tensor of `rows` (by the name the caller's signature gives it) holds a
+    row per target"""
+    row_ptr = _index(csr_row_ptr, "csr_row_ptr", device)
+    col_ind = _index(csr_col_ind, "csr_col_ind", device)
+    if row_ptr.shape[0] < 1:
+        raise ValueError("csr_row_ptr needs n_dst + 1 >= 1 entries")
+    for name, t in rows.items():
+        if row_ptr.shape[0] - 1 > t.shape[0]:
+            raise ValueError("more targets (%d) than rows of %s (%d)" % (row_ptr.shape[0] - 1, name, t.shape[0]))
+    return row_ptr, col_ind
+
+
+def _call(entry: str, *args, what: str = None, lib=None):
+    """wholememory_ext_<entry>(*args, env functions, stream), checked; `what` names the call in the error, `lib` is the
+    library handle of a module that resolves its own (pna_aggregation: its tests watch the calls through it)"""
+    fn = getattr(lib if lib is not None else wmb.lib(), "wholememory_ext_" + entry)
+    wmb.check(fn(*args, get_wholegraph_env_fns(), C.c_void_p(get_stream())), what or entry)
+
+
 class CscAggregateConcat(torch.autograd.Function):
     """autograd over the two entry points; the edge index of the backward is built only when x needs a gradient (the
     backward runs only then)"""
@@ -70,10 +108,9 @@ class CscAggregateConcat(torch.autograd.Function):
         n_src, dim = x.shape
         n_dst = row_ptr.shape[0] - 1
         out = torch.empty((n_dst, 2 * dim), dtype=x.dtype, device=x.device)
-        wmb.check(wmb.lib().wholememory_ext_csc_aggregate_forward_typed(
-            _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, _ptr(x), x.stride(0) if n_src else dim, dim,
-            aggr_code_, _ptr(out), out.stride(0) if n_dst else 2 * dim, _ROW_DTYPES[x.dtype], get_wholegraph_env_fns(),
-            C.c_void_p(get_stream())), "csc_aggregate_forward")
+        _call("csc_aggregate_forward_typed", _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, _ptr(x),
+              _stride(x, dim), dim, aggr_code_, _ptr(out), _stride(out, 2 * dim), _ROW_DTYPES[x.dtype],
+              what="csc_aggregate_forward")
         ctx.save_for_backward(row_ptr, col_ind)
         ctx.shape = (n_src, dim)
         ctx.dtype = x.dtype
@@ -89,10 +126,9 @@ class CscAggregateConcat(torch.autograd.Function):
         n_dst = row_ptr.shape[0] - 1
         grad_out = _rows(grad_out, "grad_out", (ctx.dtype,))   # (autograd hands over the dtype of out)
         grad_x = torch.empty((n_src, dim), dtype=ctx.dtype, device=grad_out.device)
-        wmb.check(wmb.lib().wholememory_ext_csc_aggregate_backward_typed(
-            _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, _ptr(grad_out),
-            grad_out.stride(0) if n_dst else 2 * dim, dim, ctx.aggr, _ptr(grad_x), dim, _ROW_DTYPES[ctx.dtype],
-            get_wholegraph_env_fns(), C.c_void_p(get_stream())), "csc_aggregate_backward")
+        _call("csc_aggregate_backward_typed", _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, _ptr(grad_out),
+              _stride(grad_out, 2 * dim), dim, ctx.aggr, _ptr(grad_x), dim, _ROW_DTYPES[ctx.dtype],
+              what="csc_aggregate_backward")
         return grad_x, None, None, None
 
 
@@ -105,12 +141,7 @@ def agg_concat(x: torch.Tensor, csr_row_ptr: torch.Tensor, csr_col_ind: torch.Te
     x = _rows(x, "x", tuple(_ROW_DTYPES))
     if not x.is_cuda:
         raise ValueError("x must be a GPU tensor")
-    row_ptr = _index(csr_row_ptr, "csr_row_ptr", x.device)
-    col_ind = _index(csr_col_ind, "csr_col_ind", x.device)
-    if row_ptr.shape[0] < 1:
-        raise ValueError("csr_row_ptr needs n_dst + 1 >= 1 entries")
-    if row_ptr.shape[0] - 1 > x.shape[0]:
-        raise ValueError("more targets (%d) than rows of x (%d)" % (row_ptr.shape[0] - 1, x.shape[0]))
+    row_ptr, col_ind = _block(csr_row_ptr, csr_col_ind, x.device, x=x)
     if x.shape[1] < 1:
         raise ValueError("x needs at least one column")
     return CscAggregateConcat.apply(x, row_ptr, col_ind, code)

@@ -12,14 +12,10 @@ the op is ``gat_aggregation.mha_gat_n2n`` over ``att[:2*H*F]``, bit for bit.
 
 The op is fp32 only. Inside a ``torch.autocast("cuda")`` region a 16-bit ``h`` / ``edge_feat`` (what an autocast ``Linear``
 returns) is cast to fp32 on the way in and the op runs in fp32 with autocast off; outside autocast it is a ``TypeError``."""
-import ctypes as C
-
 import torch
 
-from .. import binding as wmb
-from .aggregation import _index, _ptr, _rows
+from .aggregation import _block, _call, _ptr, _rows, _stride, _widen
 from .gat_aggregation import node_chunk  # noqa: F401  (N of grad_att's chunks: nodes for halves 0 and 1, edges for half 2)
-from .wholegraph_env import get_stream, get_wholegraph_env_fns
 
 
 class CscGatEdgeConv(torch.autograd.Function):
@@ -35,11 +31,9 @@ class CscGatEdgeConv(torch.autograd.Function):
         alpha = torch.empty((n_edges, heads), dtype=torch.float32, device=h.device)
         scores = torch.empty((n_src + n_dst, heads), dtype=torch.float32, device=h.device)
         edge_scores = torch.empty((n_edges, heads), dtype=torch.float32, device=h.device)
-        wmb.check(wmb.lib().wholememory_ext_csc_gat_edge_forward(
-            _ptr(row_ptr), _ptr(col_ind), n_edges, n_dst, n_src, _ptr(h), h.stride(0) if n_src else hf, _ptr(att),
-            _ptr(edge_feat), edge_feat.stride(0) if n_edges else hf, heads, dim, float(negative_slope),
-            int(bool(concat)), _ptr(out), out.shape[1], _ptr(alpha), _ptr(scores), _ptr(edge_scores),
-            get_wholegraph_env_fns(), C.c_void_p(get_stream())), "csc_gat_edge_forward")
+        _call("csc_gat_edge_forward", _ptr(row_ptr), _ptr(col_ind), n_edges, n_dst, n_src, _ptr(h), _stride(h, hf),
+              _ptr(att), _ptr(edge_feat), _stride(edge_feat, hf), heads, dim, float(negative_slope), int(bool(concat)),
+              _ptr(out), out.shape[1], _ptr(alpha), _ptr(scores), _ptr(edge_scores))
         ctx.save_for_backward(h, att, edge_feat, row_ptr, col_ind, alpha, scores, edge_scores)
         ctx.conf = (heads, dim, float(negative_slope), bool(concat))
         ctx.mark_non_differentiable(alpha, edge_scores)
@@ -59,21 +53,12 @@ class CscGatEdgeConv(torch.autograd.Function):
         grad_att = torch.empty((3 * hf,), dtype=torch.float32, device=h.device)
         # (a block without targets has no edge of any target: nothing is written there)
         grad_ef = (torch.empty if n_dst else torch.zeros)((n_edges, hf), dtype=torch.float32, device=h.device)
-        wmb.check(wmb.lib().wholememory_ext_csc_gat_edge_backward(
-            _ptr(row_ptr), _ptr(col_ind), n_edges, n_dst, n_src, _ptr(h), h.stride(0) if n_src else hf, _ptr(att),
-            _ptr(edge_feat), edge_feat.stride(0) if n_edges else hf, heads, dim, slope, int(concat), _ptr(alpha),
-            _ptr(scores), _ptr(edge_scores), _ptr(grad_out), grad_out.stride(0) if n_dst else grad_out.shape[1],
-            _ptr(grad_h), hf, _ptr(grad_att), _ptr(grad_ef), hf, get_wholegraph_env_fns(), C.c_void_p(get_stream())),
-            "csc_gat_edge_backward")
+        _call("csc_gat_edge_backward", _ptr(row_ptr), _ptr(col_ind), n_edges, n_dst, n_src, _ptr(h), _stride(h, hf),
+              _ptr(att), _ptr(edge_feat), _stride(edge_feat, hf), heads, dim, slope, int(concat), _ptr(alpha), _ptr(scores),
+              _ptr(edge_scores), _ptr(grad_out), _stride(grad_out, grad_out.shape[1]), _ptr(grad_h), hf, _ptr(grad_att),
+              _ptr(grad_ef), hf)
         return (grad_h if ctx.needs_input_grad[0] else None, grad_att if ctx.needs_input_grad[1] else None,
                 grad_ef if ctx.needs_input_grad[2] else None, None, None, None, None, None)
-
-
-def _widen(t: torch.Tensor) -> torch.Tensor:
-    """what custom_fwd's cast_inputs does, ahead of the dtype checks (the op is fp32)"""
-    if t.is_cuda and t.dtype in (torch.float16, torch.bfloat16) and torch.is_autocast_enabled("cuda"):
-        return t.float()
-    return t
 
 
 def mha_gat_n2n_edge(h: torch.Tensor, att: torch.Tensor, edge_feat: torch.Tensor, csr_row_ptr: torch.Tensor,
@@ -103,11 +88,6 @@ def mha_gat_n2n_edge(h: torch.Tensor, att: torch.Tensor, edge_feat: torch.Tensor
     if edge_feat.device != h.device:
         raise ValueError("edge_feat is on %s, h on %s" % (edge_feat.device, h.device))
     att = att.reshape(-1).contiguous()
-    row_ptr = _index(csr_row_ptr, "csr_row_ptr", h.device)
-    col_ind = _index(csr_col_ind, "csr_col_ind", h.device)
-    if row_ptr.shape[0] < 1:
-        raise ValueError("csr_row_ptr needs n_dst + 1 >= 1 entries")
-    if row_ptr.shape[0] - 1 > h.shape[0]:
-        raise ValueError("more targets (%d) than rows of h (%d)" % (row_ptr.shape[0] - 1, h.shape[0]))
+    row_ptr, col_ind = _block(csr_row_ptr, csr_col_ind, h.device, h=h)
     out, alpha, _ = CscGatEdgeConv.apply(h, att, edge_feat, row_ptr, col_ind, heads, float(negative_slope), bool(concat))
     return (out, alpha) if return_alpha else out

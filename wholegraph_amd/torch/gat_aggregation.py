@@ -10,13 +10,10 @@ reproducible.
 
 The op is fp32 only. Inside a ``torch.autocast("cuda")`` region a 16-bit ``h`` (what an autocast ``Linear`` returns) is
 cast to fp32 on the way in and the op runs in fp32 with autocast off; outside autocast a 16-bit ``h`` is a ``TypeError``."""
-import ctypes as C
-
 import torch
 
 from .. import binding as wmb
-from .aggregation import _index, _ptr, _rows
-from .wholegraph_env import get_stream, get_wholegraph_env_fns
+from .aggregation import _block, _call, _ptr, _rows, _stride, _widen
 
 
 def node_chunk() -> int:
@@ -36,10 +33,8 @@ class CscGatConv(torch.autograd.Function):
         out = torch.empty((n_dst, hf if concat else dim), dtype=torch.float32, device=h.device)
         alpha = torch.empty((n_edges, heads), dtype=torch.float32, device=h.device)
         scores = torch.empty((n_src + n_dst, heads), dtype=torch.float32, device=h.device)
-        wmb.check(wmb.lib().wholememory_ext_csc_gat_forward(
-            _ptr(row_ptr), _ptr(col_ind), n_edges, n_dst, n_src, _ptr(h), h.stride(0) if n_src else hf, _ptr(att), heads,
-            dim, float(negative_slope), int(bool(concat)), _ptr(out), out.shape[1], _ptr(alpha), _ptr(scores),
-            get_wholegraph_env_fns(), C.c_void_p(get_stream())), "csc_gat_forward")
+        _call("csc_gat_forward", _ptr(row_ptr), _ptr(col_ind), n_edges, n_dst, n_src, _ptr(h), _stride(h, hf), _ptr(att),
+              heads, dim, float(negative_slope), int(bool(concat)), _ptr(out), out.shape[1], _ptr(alpha), _ptr(scores))
         ctx.save_for_backward(h, att, row_ptr, col_ind, alpha, scores)
         ctx.conf = (heads, dim, float(negative_slope), bool(concat))
         ctx.mark_non_differentiable(alpha)
@@ -57,11 +52,9 @@ class CscGatConv(torch.autograd.Function):
         grad_out = _rows(grad_out, "grad_out")
         grad_h = torch.empty((n_src, hf), dtype=torch.float32, device=h.device)
         grad_att = torch.empty((2 * hf,), dtype=torch.float32, device=h.device)
-        wmb.check(wmb.lib().wholememory_ext_csc_gat_backward(
-            _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, _ptr(h), h.stride(0) if n_src else hf,
-            _ptr(att), heads, dim, slope, int(concat), _ptr(alpha), _ptr(scores), _ptr(grad_out),
-            grad_out.stride(0) if n_dst else grad_out.shape[1], _ptr(grad_h), hf, _ptr(grad_att),
-            get_wholegraph_env_fns(), C.c_void_p(get_stream())), "csc_gat_backward")
+        _call("csc_gat_backward", _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, _ptr(h), _stride(h, hf),
+              _ptr(att), heads, dim, slope, int(concat), _ptr(alpha), _ptr(scores), _ptr(grad_out),
+              _stride(grad_out, grad_out.shape[1]), _ptr(grad_h), hf, _ptr(grad_att))
         return (grad_h if ctx.needs_input_grad[0] else None, grad_att if ctx.needs_input_grad[1] else None,
                 None, None, None, None, None)
 
@@ -76,9 +69,7 @@ def mha_gat_n2n(h: torch.Tensor, att: torch.Tensor, csr_row_ptr: torch.Tensor, c
     heads = int(heads)
     if heads < 1:
         raise ValueError("heads must be >= 1 (got %d)" % heads)
-    if h.is_cuda and h.dtype in (torch.float16, torch.bfloat16) and torch.is_autocast_enabled("cuda"):
-        h = h.float()   # (what custom_fwd's cast_inputs does, ahead of the checks below; the op is fp32)
-    h = _rows(h, "h")
+    h = _rows(_widen(h), "h")
     if not h.is_cuda:
         raise ValueError("h must be a GPU tensor")
     if h.shape[1] < 1 or h.shape[1] % heads:
@@ -86,11 +77,6 @@ def mha_gat_n2n(h: torch.Tensor, att: torch.Tensor, csr_row_ptr: torch.Tensor, c
     if att.dtype != torch.float32 or att.numel() != 2 * h.shape[1] or att.device != h.device:
         raise ValueError("att must be fp32 with 2 * heads * F = %d elements on %s" % (2 * h.shape[1], h.device))
     att = att.reshape(-1).contiguous()
-    row_ptr = _index(csr_row_ptr, "csr_row_ptr", h.device)
-    col_ind = _index(csr_col_ind, "csr_col_ind", h.device)
-    if row_ptr.shape[0] < 1:
-        raise ValueError("csr_row_ptr needs n_dst + 1 >= 1 entries")
-    if row_ptr.shape[0] - 1 > h.shape[0]:
-        raise ValueError("more targets (%d) than rows of h (%d)" % (row_ptr.shape[0] - 1, h.shape[0]))
+    row_ptr, col_ind = _block(csr_row_ptr, csr_col_ind, h.device, h=h)
     out, alpha = CscGatConv.apply(h, att, row_ptr, col_ind, heads, float(negative_slope), bool(concat))
     return (out, alpha) if return_alpha else out

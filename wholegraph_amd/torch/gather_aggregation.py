@@ -24,16 +24,14 @@ in device memory is read by one kernel (``wholememory_ext_csc_gather_dequantize_
 host-located table takes the composition (the fused kernel would pull a row across PCIe once per edge, the gather pulls
 each of the n_src rows once), as do DISTRIBUTED and HIERARCHY tables. Quantized tables are frozen features: the output
 carries no autograd node and ``is_training`` is ignored."""
-import ctypes as C
-
 import torch
 
 from .. import binding as wmb
-from .aggregation import _index, _ptr, _rows, agg_concat, aggr_code
+from .aggregation import _block, _call, _ptr, _rows, _stride, agg_concat, aggr_code
 from .embedding import EmbeddingLookupFn, WholeMemoryEmbedding
 from .quantized import WholeMemoryQuantizedTensor
 from .tensor import WholeMemoryTensor
-from .wholegraph_env import get_stream, get_wholegraph_env_fns, op_device
+from .wholegraph_env import op_device
 
 _TABLE_DTYPES = (torch.float32, torch.float16, torch.bfloat16)
 _ID_DTYPES = {torch.int32: wmb.DT_INT, torch.int64: wmb.DT_INT64}
@@ -85,10 +83,8 @@ class GatherAggregateConcat(torch.autograd.Function):
         n_src, dim = node_ids.shape[0], table.shape[1]
         n_dst = row_ptr.shape[0] - 1
         out = torch.empty((n_dst, 2 * dim), dtype=torch.float32, device=node_ids.device)
-        wmb.check(wmb.lib().wholememory_ext_csc_gather_aggregate_forward(
-            table.wmb_tensor, _ptr(node_ids), _ID_DTYPES[node_ids.dtype], _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0],
-            n_dst, n_src, aggr_code_, _ptr(out), 2 * dim, get_wholegraph_env_fns(), C.c_void_p(get_stream())),
-            "csc_gather_aggregate_forward")
+        _call("csc_gather_aggregate_forward", table.wmb_tensor, _ptr(node_ids), _ID_DTYPES[node_ids.dtype], _ptr(row_ptr),
+              _ptr(col_ind), col_ind.shape[0], n_dst, n_src, aggr_code_, _ptr(out), 2 * dim)
         trains = isinstance(source, WholeMemoryEmbedding) and source.wmb_optimizer is not None and bool(is_training)
         ctx.target = source if trains else None
         ctx.dummy_like = (tuple(dummy_input.shape), dummy_input.dtype, dummy_input.device)
@@ -108,10 +104,8 @@ class GatherAggregateConcat(torch.autograd.Function):
         n_dst = row_ptr.shape[0] - 1
         grad_out = _rows(grad_out, "grad_out")
         grad_x = torch.empty((n_src, dim), dtype=torch.float32, device=grad_out.device)
-        wmb.check(wmb.lib().wholememory_ext_csc_aggregate_backward_typed(
-            _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, _ptr(grad_out),
-            grad_out.stride(0) if n_dst else 2 * dim, dim, ctx.aggr, _ptr(grad_x), dim, wmb.DT_FLOAT,
-            get_wholegraph_env_fns(), C.c_void_p(get_stream())), "csc_aggregate_backward")
+        _call("csc_aggregate_backward_typed", _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, _ptr(grad_out),
+              _stride(grad_out, 2 * dim), dim, ctx.aggr, _ptr(grad_x), dim, wmb.DT_FLOAT, what="csc_aggregate_backward")
         target.add_gradients(node_ids, grad_x)
         target.need_apply = True
         shape, dtype, device = ctx.dummy_like
@@ -122,10 +116,9 @@ def _quantized_forward(source, node_ids, row_ptr, col_ind, aggr_code_):
     n_src, dim = node_ids.shape[0], source.shape[1]
     n_dst = row_ptr.shape[0] - 1
     out = torch.empty((n_dst, 2 * dim), dtype=torch.float32, device=node_ids.device)
-    wmb.check(wmb.lib().wholememory_ext_csc_gather_dequantize_aggregate_forward(
-        source.storage.wmb_tensor, dim, _ptr(node_ids), _ID_DTYPES[node_ids.dtype], _ptr(row_ptr), _ptr(col_ind),
-        col_ind.shape[0], n_dst, n_src, aggr_code_, _ptr(out), 2 * dim, get_wholegraph_env_fns(), C.c_void_p(get_stream())),
-        "csc_gather_dequantize_aggregate_forward")
+    _call("csc_gather_dequantize_aggregate_forward", source.storage.wmb_tensor, dim, _ptr(node_ids),
+          _ID_DTYPES[node_ids.dtype], _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, aggr_code_, _ptr(out),
+          2 * dim)
     return out
 
 
@@ -155,10 +148,7 @@ def gather_agg_concat(source, node_ids: torch.Tensor, csr_row_ptr: torch.Tensor,
     if not node_ids.is_cuda:
         node_ids = node_ids.to(op_device())
     node_ids = node_ids.contiguous()
-    row_ptr = _index(csr_row_ptr, "csr_row_ptr", node_ids.device)
-    col_ind = _index(csr_col_ind, "csr_col_ind", node_ids.device)
-    if row_ptr.shape[0] < 1:
-        raise ValueError("csr_row_ptr needs n_dst + 1 >= 1 entries")
+    row_ptr, col_ind = _block(csr_row_ptr, csr_col_ind, node_ids.device)
     if row_ptr.shape[0] - 1 > node_ids.shape[0]:
         raise ValueError("more targets (%d) than node ids (%d)" % (row_ptr.shape[0] - 1, node_ids.shape[0]))
     if table.shape[1] < 1:

@@ -11,13 +11,9 @@ one fixed order (stated in ``include/wholememory/wholegraph_amd_ext.h``, section
 The op is fp32 only. Inside a ``torch.autocast("cuda")`` region 16-bit ``h_src`` / ``h_dst`` (what an autocast ``Linear``
 returns) are cast to fp32 on the way in and the op runs in fp32 with autocast off; outside autocast a 16-bit input is a
 ``TypeError``."""
-import ctypes as C
-
 import torch
 
-from .. import binding as wmb
-from .aggregation import _index, _ptr, _rows
-from .wholegraph_env import get_stream, get_wholegraph_env_fns
+from .aggregation import _block, _call, _opt_ptr, _ptr, _rows, _stride, _widen
 
 
 class CscGatV2Conv(torch.autograd.Function):
@@ -31,11 +27,9 @@ class CscGatV2Conv(torch.autograd.Function):
         n_dst, n_edges = row_ptr.shape[0] - 1, col_ind.shape[0]
         out = torch.empty((n_dst, hf if concat else dim), dtype=torch.float32, device=h_src.device)
         alpha = torch.empty((n_edges, heads), dtype=torch.float32, device=h_src.device)
-        wmb.check(wmb.lib().wholememory_ext_csc_gatv2_forward(
-            _ptr(row_ptr), _ptr(col_ind), n_edges, n_dst, n_src, _ptr(h_src), h_src.stride(0) if n_src else hf,
-            _ptr(h_dst), h_dst.stride(0) if h_dst.shape[0] else hf, _ptr(att), heads, dim, float(negative_slope),
-            int(bool(concat)), _ptr(out), out.shape[1], _ptr(alpha), get_wholegraph_env_fns(),
-            C.c_void_p(get_stream())), "csc_gatv2_forward")
+        _call("csc_gatv2_forward", _ptr(row_ptr), _ptr(col_ind), n_edges, n_dst, n_src, _ptr(h_src), _stride(h_src, hf),
+              _ptr(h_dst), _stride(h_dst, hf), _ptr(att), heads, dim, float(negative_slope), int(bool(concat)), _ptr(out),
+              out.shape[1], _ptr(alpha))
         ctx.save_for_backward(h_src, h_dst, att, row_ptr, col_ind, alpha)
         ctx.conf = (heads, dim, float(negative_slope), bool(concat))
         ctx.mark_non_differentiable(alpha)
@@ -57,13 +51,10 @@ class CscGatV2Conv(torch.autograd.Function):
         # (rows of h_dst behind the targets take no part in the op: their gradient is zero)
         grad_h_dst = torch.zeros((h_dst.shape[0], hf), dtype=torch.float32, device=dev) if need[1] else None
         grad_att = torch.empty((hf,), dtype=torch.float32, device=dev) if need[2] else None
-        wmb.check(wmb.lib().wholememory_ext_csc_gatv2_backward(
-            _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, _ptr(h_src), h_src.stride(0) if n_src else hf,
-            _ptr(h_dst), h_dst.stride(0) if h_dst.shape[0] else hf, _ptr(att), heads, dim, slope, int(concat),
-            _ptr(alpha), _ptr(grad_out), grad_out.stride(0) if n_dst else grad_out.shape[1],
-            _ptr(grad_h_src) if need[0] else None, hf, _ptr(grad_h_dst) if need[1] else None, hf,
-            _ptr(grad_att) if need[2] else None, get_wholegraph_env_fns(), C.c_void_p(get_stream())),
-            "csc_gatv2_backward")
+        _call("csc_gatv2_backward", _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, _ptr(h_src),
+              _stride(h_src, hf), _ptr(h_dst), _stride(h_dst, hf), _ptr(att), heads, dim, slope, int(concat), _ptr(alpha),
+              _ptr(grad_out), _stride(grad_out, grad_out.shape[1]), _opt_ptr(grad_h_src), hf, _opt_ptr(grad_h_dst), hf,
+              _opt_ptr(grad_att))
         return grad_h_src, grad_h_dst, grad_att, None, None, None, None, None
 
 
@@ -78,13 +69,8 @@ def mha_gat_v2_n2n(h_src: torch.Tensor, h_dst: torch.Tensor, att: torch.Tensor, 
     heads = int(heads)
     if heads < 1:
         raise ValueError("heads must be >= 1 (got %d)" % heads)
-    if torch.is_autocast_enabled("cuda"):   # (what custom_fwd's cast_inputs does, ahead of the checks below; the op is fp32)
-        if h_src.is_cuda and h_src.dtype in (torch.float16, torch.bfloat16):
-            h_src = h_src.float()
-        if h_dst.is_cuda and h_dst.dtype in (torch.float16, torch.bfloat16):
-            h_dst = h_dst.float()
-    h_src = _rows(h_src, "h_src")
-    h_dst = _rows(h_dst, "h_dst")
+    h_src = _rows(_widen(h_src), "h_src")
+    h_dst = _rows(_widen(h_dst), "h_dst")
     if not h_src.is_cuda:
         raise ValueError("h_src must be a GPU tensor")
     if h_src.shape[1] < 1 or h_src.shape[1] % heads:
@@ -94,13 +80,6 @@ def mha_gat_v2_n2n(h_src: torch.Tensor, h_dst: torch.Tensor, att: torch.Tensor, 
     if att.dtype != torch.float32 or att.numel() != h_src.shape[1] or att.device != h_src.device:
         raise ValueError("att must be fp32 with heads * F = %d elements on %s" % (h_src.shape[1], h_src.device))
     att = att.reshape(-1).contiguous()
-    row_ptr = _index(csr_row_ptr, "csr_row_ptr", h_src.device)
-    col_ind = _index(csr_col_ind, "csr_col_ind", h_src.device)
-    if row_ptr.shape[0] < 1:
-        raise ValueError("csr_row_ptr needs n_dst + 1 >= 1 entries")
-    if row_ptr.shape[0] - 1 > h_src.shape[0]:
-        raise ValueError("more targets (%d) than rows of h_src (%d)" % (row_ptr.shape[0] - 1, h_src.shape[0]))
-    if row_ptr.shape[0] - 1 > h_dst.shape[0]:
-        raise ValueError("more targets (%d) than rows of h_dst (%d)" % (row_ptr.shape[0] - 1, h_dst.shape[0]))
+    row_ptr, col_ind = _block(csr_row_ptr, csr_col_ind, h_src.device, h_src=h_src, h_dst=h_dst)
     out, alpha = CscGatV2Conv.apply(h_src, h_dst, att, row_ptr, col_ind, heads, float(negative_slope), bool(concat))
     return (out, alpha) if return_alpha else out

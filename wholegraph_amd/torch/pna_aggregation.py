@@ -12,13 +12,10 @@ bitwise reproducible. With ``["max"]`` alone the op is GraphSAGE's max aggregati
 The op is fp32 only. Inside a ``torch.autocast("cuda")`` region a 16-bit ``x`` (what an autocast ``Linear`` returns) is cast
 to fp32 on the way in and the op runs in fp32 with autocast off; outside autocast a 16-bit or float64 ``x`` is a
 ``TypeError``."""
-import ctypes as C
-
 import torch
 
 from .. import binding as wmb
-from .aggregation import _index, _ptr, _rows
-from .wholegraph_env import get_stream, get_wholegraph_env_fns
+from .aggregation import _block, _call, _opt_ptr, _ptr, _rows, _stride, _widen
 
 AGGREGATORS = tuple(wmb.PNA_AGGR)   # canonical (slot) order
 EPS = 1e-5
@@ -62,10 +59,8 @@ class CscAggregatePNA(torch.autograd.Function):
             for i, (bit, dt) in enumerate(((4, torch.int32), (8, torch.int32), (16, torch.float32), (16, torch.float32))):
                 if mask & bit:
                     saved[i] = torch.empty((n_dst, dim), dtype=dt, device=x.device)
-        wmb.check(wmb.lib().wholememory_ext_csc_pna_aggregate_forward(
-            _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, _ptr(x), x.stride(0) if n_src else dim, dim, mask,
-            eps, _ptr(out), slots * dim, *(_ptr(t) if t is not None else None for t in saved), get_wholegraph_env_fns(),
-            C.c_void_p(get_stream())), "csc_pna_aggregate_forward")
+        _call("csc_pna_aggregate_forward", _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, _ptr(x),
+              _stride(x, dim), dim, mask, eps, _ptr(out), slots * dim, *map(_opt_ptr, saved), lib=wmb.lib())
         ctx.save_for_backward(x if mask & 16 else None, row_ptr, col_ind, *saved)
         ctx.conf = (n_src, dim, mask)
         return out
@@ -81,11 +76,9 @@ class CscAggregatePNA(torch.autograd.Function):
         slots = bin(mask).count("1") + 1
         grad_out = _rows(grad_out, "grad_out")
         grad_x = torch.empty((n_src, dim), dtype=torch.float32, device=grad_out.device)
-        wmb.check(wmb.lib().wholememory_ext_csc_pna_aggregate_backward(
-            _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, _ptr(x) if x is not None else None,
-            x.stride(0) if x is not None and n_src else dim, dim, mask, *(_ptr(t) if t is not None else None for t in saved),
-            _ptr(grad_out), grad_out.stride(0) if n_dst else slots * dim, _ptr(grad_x), dim, get_wholegraph_env_fns(),
-            C.c_void_p(get_stream())), "csc_pna_aggregate_backward")
+        _call("csc_pna_aggregate_backward", _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, _opt_ptr(x),
+              _stride(x, dim) if x is not None else dim, dim, mask, *map(_opt_ptr, saved), _ptr(grad_out),
+              _stride(grad_out, slots * dim), _ptr(grad_x), dim, lib=wmb.lib())
         return grad_x, None, None, None, None, None
 
 
@@ -96,17 +89,10 @@ def agg_concat_pna(x: torch.Tensor, csr_row_ptr: torch.Tensor, csr_col_ind: torc
     describe the block in CSC form: the edges of target d are csr_col_ind[csr_row_ptr[d] : csr_row_ptr[d + 1]], row
     positions in x. x: float32 [n_src, F], n_src >= n_dst. aggregators: a non-empty list of distinct names."""
     mask = aggregator_mask(aggregators)
-    if torch.is_autocast_enabled("cuda") and x.is_cuda and x.dtype in (torch.float16, torch.bfloat16):
-        x = x.float()   # (what custom_fwd's cast_inputs does, ahead of the checks below; the op is fp32)
-    x = _rows(x, "x")
+    x = _rows(_widen(x), "x")
     if not x.is_cuda:
         raise ValueError("x must be a GPU tensor")
-    row_ptr = _index(csr_row_ptr, "csr_row_ptr", x.device)
-    col_ind = _index(csr_col_ind, "csr_col_ind", x.device)
-    if row_ptr.shape[0] < 1:
-        raise ValueError("csr_row_ptr needs n_dst + 1 >= 1 entries")
-    if row_ptr.shape[0] - 1 > x.shape[0]:
-        raise ValueError("more targets (%d) than rows of x (%d)" % (row_ptr.shape[0] - 1, x.shape[0]))
+    row_ptr, col_ind = _block(csr_row_ptr, csr_col_ind, x.device, x=x)
     if x.shape[1] < 1:
         raise ValueError("x needs at least one column")
     if not eps >= 0:

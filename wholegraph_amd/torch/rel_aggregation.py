@@ -12,17 +12,10 @@ there are no atomics: results are bitwise reproducible.
 
 The op is fp32 only. Inside a ``torch.autocast("cuda")`` region a 16-bit ``x`` (what an autocast ``Linear`` returns) is
 cast to fp32 on the way in and the op runs in fp32 with autocast off; outside autocast a 16-bit ``x`` is a ``TypeError``."""
-import ctypes as C
-
 import torch
 
 from .. import binding as wmb
-from .aggregation import _index, _ptr, _rows, aggr_code
-from .wholegraph_env import get_stream, get_wholegraph_env_fns
-
-
-def _opt_ptr(t):
-    return C.c_void_p(t.data_ptr() if t is not None else None)
+from .aggregation import _block, _call, _opt_ptr, _ptr, _rows, _stride, _widen, aggr_code
 
 
 class CscAggregateConcatRel(torch.autograd.Function):
@@ -38,10 +31,8 @@ class CscAggregateConcatRel(torch.autograd.Function):
         # (a block without targets has no edge of any target: nothing is written then)
         scale = (torch.empty if n_dst else torch.zeros)((n_edges,), dtype=torch.float32, device=x.device) \
             if aggr_code_ == wmb.AGGR_MEAN else None
-        wmb.check(wmb.lib().wholememory_ext_csc_rel_aggregate_forward(
-            _ptr(row_ptr), _ptr(col_ind), _ptr(edge_type), n_edges, n_dst, n_src, num_relations, _ptr(x),
-            x.stride(0) if n_src else dim, dim, aggr_code_, _ptr(out), out.stride(0) if n_dst else width, _opt_ptr(scale),
-            get_wholegraph_env_fns(), C.c_void_p(get_stream())), "csc_rel_aggregate_forward")
+        _call("csc_rel_aggregate_forward", _ptr(row_ptr), _ptr(col_ind), _ptr(edge_type), n_edges, n_dst, n_src,
+              num_relations, _ptr(x), _stride(x, dim), dim, aggr_code_, _ptr(out), _stride(out, width), _opt_ptr(scale))
         ctx.save_for_backward(row_ptr, col_ind, edge_type, scale)
         ctx.shape = (n_src, dim)
         ctx.num_relations = num_relations
@@ -59,10 +50,8 @@ class CscAggregateConcatRel(torch.autograd.Function):
         width = (ctx.num_relations + 1) * dim
         grad_out = _rows(grad_out, "grad_out")
         grad_x = torch.empty((n_src, dim), dtype=torch.float32, device=grad_out.device)
-        wmb.check(wmb.lib().wholememory_ext_csc_rel_aggregate_backward(
-            _ptr(row_ptr), _ptr(col_ind), _ptr(edge_type), col_ind.shape[0], n_dst, n_src, ctx.num_relations,
-            _opt_ptr(scale), _ptr(grad_out), grad_out.stride(0) if n_dst else width, dim, ctx.aggr, _ptr(grad_x), dim,
-            get_wholegraph_env_fns(), C.c_void_p(get_stream())), "csc_rel_aggregate_backward")
+        _call("csc_rel_aggregate_backward", _ptr(row_ptr), _ptr(col_ind), _ptr(edge_type), col_ind.shape[0], n_dst, n_src,
+              ctx.num_relations, _opt_ptr(scale), _ptr(grad_out), _stride(grad_out, width), dim, ctx.aggr, _ptr(grad_x), dim)
         return grad_x, None, None, None, None, None
 
 
@@ -91,18 +80,11 @@ def agg_concat_rel(x: torch.Tensor, csr_row_ptr: torch.Tensor, csr_col_ind: torc
         raise TypeError("num_relations must be an int (got %s)" % type(num_relations).__name__)
     if num_relations < 1:
         raise ValueError("num_relations must be >= 1 (got %d)" % num_relations)
-    if x.is_cuda and x.dtype in (torch.float16, torch.bfloat16) and torch.is_autocast_enabled("cuda"):
-        x = x.float()   # (what custom_fwd's cast_inputs does, ahead of the checks below; the op is fp32)
-    x = _rows(x, "x")
-    row_ptr = _index(csr_row_ptr, "csr_row_ptr", x.device)
-    col_ind = _index(csr_col_ind, "csr_col_ind", x.device)
+    x = _rows(_widen(x), "x")
+    row_ptr, col_ind = _block(csr_row_ptr, csr_col_ind, x.device, x=x)
     types = _edge_types(edge_type, num_relations, x.device)
     if types.shape[0] != col_ind.shape[0]:
         raise ValueError("edge_type has %d entries, csr_col_ind %d" % (types.shape[0], col_ind.shape[0]))
-    if row_ptr.shape[0] < 1:
-        raise ValueError("csr_row_ptr needs n_dst + 1 >= 1 entries")
-    if row_ptr.shape[0] - 1 > x.shape[0]:
-        raise ValueError("more targets (%d) than rows of x (%d)" % (row_ptr.shape[0] - 1, x.shape[0]))
     if x.shape[1] < 1:
         raise ValueError("x needs at least one column")
     if not x.is_cuda:

@@ -10,13 +10,9 @@ fp32 sum, forward and backward, is taken in one fixed order (stated in ``include
 
 The op is fp32 only. Inside a ``torch.autocast("cuda")`` region 16-bit inputs (what an autocast ``Linear`` returns) are cast
 to fp32 on the way in and the op runs in fp32 with autocast off; outside autocast a 16-bit input is a ``TypeError``."""
-import ctypes as C
-
 import torch
 
-from .. import binding as wmb
-from .aggregation import _index, _ptr, _rows
-from .wholegraph_env import get_stream, get_wholegraph_env_fns
+from .aggregation import _block, _call, _opt_ptr, _ptr, _rows, _stride, _widen
 
 
 class CscMhaSimple(torch.autograd.Function):
@@ -30,11 +26,9 @@ class CscMhaSimple(torch.autograd.Function):
         n_dst, n_edges = row_ptr.shape[0] - 1, col_ind.shape[0]
         out = torch.empty((n_dst, hf if concat else dim), dtype=torch.float32, device=key.device)
         alpha = torch.empty((n_edges, heads), dtype=torch.float32, device=key.device)
-        wmb.check(wmb.lib().wholememory_ext_csc_mha_simple_forward(
-            _ptr(row_ptr), _ptr(col_ind), n_edges, n_dst, n_src, _ptr(key), key.stride(0) if n_src else hf, _ptr(query),
-            query.stride(0) if query.shape[0] else hf, _ptr(value), value.stride(0) if n_src else hf, heads, dim,
-            int(bool(norm_by_dim)), int(bool(concat)), _ptr(out), out.shape[1], _ptr(alpha), get_wholegraph_env_fns(),
-            C.c_void_p(get_stream())), "csc_mha_simple_forward")
+        _call("csc_mha_simple_forward", _ptr(row_ptr), _ptr(col_ind), n_edges, n_dst, n_src, _ptr(key), _stride(key, hf),
+              _ptr(query), _stride(query, hf), _ptr(value), _stride(value, hf), heads, dim, int(bool(norm_by_dim)),
+              int(bool(concat)), _ptr(out), out.shape[1], _ptr(alpha))
         ctx.save_for_backward(key, query, value, row_ptr, col_ind, alpha)
         ctx.conf = (heads, dim, bool(concat), bool(norm_by_dim))
         ctx.mark_non_differentiable(alpha)
@@ -56,13 +50,10 @@ class CscMhaSimple(torch.autograd.Function):
         # (rows of query behind the targets take no part in the op: their gradient is zero)
         grad_query = torch.zeros((query.shape[0], hf), dtype=torch.float32, device=dev) if need[1] else None
         grad_value = torch.empty((n_src, hf), dtype=torch.float32, device=dev) if need[2] else None
-        wmb.check(wmb.lib().wholememory_ext_csc_mha_simple_backward(
-            _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, _ptr(key), key.stride(0) if n_src else hf,
-            _ptr(query), query.stride(0) if query.shape[0] else hf, _ptr(value), value.stride(0) if n_src else hf, heads,
-            dim, int(norm_by_dim), int(concat), _ptr(alpha), _ptr(grad_out),
-            grad_out.stride(0) if n_dst else grad_out.shape[1], _ptr(grad_key) if need[0] else None, hf,
-            _ptr(grad_query) if need[1] else None, hf, _ptr(grad_value) if need[2] else None, hf,
-            get_wholegraph_env_fns(), C.c_void_p(get_stream())), "csc_mha_simple_backward")
+        _call("csc_mha_simple_backward", _ptr(row_ptr), _ptr(col_ind), col_ind.shape[0], n_dst, n_src, _ptr(key),
+              _stride(key, hf), _ptr(query), _stride(query, hf), _ptr(value), _stride(value, hf), heads, dim,
+              int(norm_by_dim), int(concat), _ptr(alpha), _ptr(grad_out), _stride(grad_out, grad_out.shape[1]),
+              _opt_ptr(grad_key), hf, _opt_ptr(grad_query), hf, _opt_ptr(grad_value), hf)
         return grad_key, grad_query, grad_value, None, None, None, None, None
 
 
@@ -78,12 +69,9 @@ def mha_simple_n2n(key_emb: torch.Tensor, query_emb: torch.Tensor, value_emb: to
     heads = int(heads)
     if heads < 1:
         raise ValueError("heads must be >= 1 (got %d)" % heads)
-    if torch.is_autocast_enabled("cuda"):   # (what custom_fwd's cast_inputs does, ahead of the checks below; the op is fp32)
-        key_emb, query_emb, value_emb = (t.float() if t.is_cuda and t.dtype in (torch.float16, torch.bfloat16) else t
-                                         for t in (key_emb, query_emb, value_emb))
-    key = _rows(key_emb, "key_emb")
-    query = _rows(query_emb, "query_emb")
-    value = _rows(value_emb, "value_emb")
+    key = _rows(_widen(key_emb), "key_emb")
+    query = _rows(_widen(query_emb), "query_emb")
+    value = _rows(_widen(value_emb), "value_emb")
     if not key.is_cuda:
         raise ValueError("key_emb must be a GPU tensor")
     if key.shape[1] < 1 or key.shape[1] % heads:
@@ -94,13 +82,6 @@ def mha_simple_n2n(key_emb: torch.Tensor, query_emb: torch.Tensor, value_emb: to
         raise ValueError("value_emb must have the %d columns of key_emb and live on %s" % (key.shape[1], key.device))
     if value.shape[0] != key.shape[0]:
         raise ValueError("value_emb has %d rows, key_emb %d" % (value.shape[0], key.shape[0]))
-    row_ptr = _index(csr_row_ptr, "csr_row_ptr", key.device)
-    col_ind = _index(csr_col_ind, "csr_col_ind", key.device)
-    if row_ptr.shape[0] < 1:
-        raise ValueError("csr_row_ptr needs n_dst + 1 >= 1 entries")
-    if row_ptr.shape[0] - 1 > key.shape[0]:
-        raise ValueError("more targets (%d) than rows of key_emb (%d)" % (row_ptr.shape[0] - 1, key.shape[0]))
-    if row_ptr.shape[0] - 1 > query.shape[0]:
-        raise ValueError("more targets (%d) than rows of query_emb (%d)" % (row_ptr.shape[0] - 1, query.shape[0]))
+    row_ptr, col_ind = _block(csr_row_ptr, csr_col_ind, key.device, key_emb=key, query_emb=query)
     out, alpha = CscMhaSimple.apply(key, query, value, row_ptr, col_ind, heads, bool(concat), bool(norm_by_dim))
     return (out, alpha) if return_alpha else out

@@ -30,6 +30,8 @@
  *      (2m) random walks over a CSR graph held in WholeMemory, uniform or by edge weight, as one launch for the whole batch.
  *      (2n) node2vec (p, q) second-order walks over the same graph, with or without edge weights, as one launch.
  *      (2o) negative sampling over the same graph: per source node, K nodes that are not its neighbours, as one launch.
+ *      (2p) the dot product of the two endpoint rows of every edge of a sampled CSC block: the score of skip-gram training
+ *      over the walks and negatives above and of link prediction (forward and a deterministic backward).
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -1269,6 +1271,64 @@ enum wholememory_error_code_t wholememory_ext_csr_negative_sample(wholememory_te
                                                                   unsigned long long random_seed,
                                                                   wholememory_tensor_t output_negatives_tensor,
                                                                   void* stream);
+
+/* ---- (2p) edge dot product of a sampled CSC block (`edge_dot_n2n`) ---------------------------------------------------- */
+/* The block: row_ptr int32 [n_dst + 1], col_ind int32 [n_edges] in [0, n_src). x_src fp32 [n_src, x_src_stride] and x_dst fp32
+ * [n_dst, x_dst_stride], row d of x_dst belonging to target d; each row uses F = dim columns. Unlike (2b) .. (2l) the targets
+ * are not among the source rows: n_dst may exceed n_src (the centre positions of a batch of walks against the distinct
+ * context nodes). Strides in elements, all arrays DEVICE memory, all work queued on `stream`.
+ * The contract of (2k): every `*` and `+` below is one fp32 operation, rounded on its own (no fused multiply-add), no atomics,
+ * one fixed order for every sum, results bitwise reproducible. "Tree sum over f" is the balanced binary tree of adjacent pairs
+ * of (2g) / (2k), padded to the next power of two Fp >= F with +0.0; it does not depend on how the kernel is launched. There
+ * are no heads and no scale.
+ *
+ * forward: writes score [n_edges]. For edge e of target d (e = row_ptr[d] .. row_ptr[d+1] - 1), j = col_ind[e]:
+ *   score[e] = tree sum over f of x_dst[d,f] * x_src[j,f].
+ * backward: grad_score g [n_edges] -> grad_dst [n_dst, grad_dst_stride] and grad_src [n_src, grad_src_stride], each with a
+ * stride >= F and every row of a requested gradient written. Either may be null and is then not computed (nothing is queued
+ * for it); both null is INVALID_INPUT.
+ *   grad_dst[d,:] = sum of g[e] * x_src[j,:] over the edges of d, left to right from the first term; +0.0 without edges.
+ *   grad_src[j,:] = sum over the edges with col_ind[e] = j, in ascending edge position, of g[e] * x_dst[d(e),:]: left to right
+ *   when j has at most C edges, otherwise cut into consecutive chunks of C edges, each chunk summed left to right and the
+ *   chunk sums added in chunk order, exactly as (2b), with C = wholememory_ext_csc_aggregate_chunk_edges(). A source without
+ *   edges gets +0.0.
+ *   The edge index of grad_src is built with the library's id sort, scratch from p_env_fns, and only when grad_src is asked
+ *   for and n_src > 0.
+ * n_edges = 0 and n_dst = 0 are valid: what there is to write (the rows of the requested gradients, +0.0) is written. A
+ * col_ind entry outside [0, n_src) is treated as by (2k): it is not looked for. INVALID_INPUT, before any device work and
+ * under every backend: null pointers (row_ptr; col_ind, score and grad_score when there are edges; x_src with n_src > 0; x_dst
+ * with n_dst > 0; p_env_fns), negative sizes, 2^31 or more edges, targets or source rows, dim outside [1, 2^31 / 4) and any
+ * stride smaller than dim. NOT_SUPPORTED (nothing queued) when the device backend has no such kernels. */
+enum wholememory_error_code_t wholememory_ext_csc_edge_dot_forward(const int32_t* row_ptr,
+                                                                   const int32_t* col_ind,
+                                                                   int64_t n_edges,
+                                                                   int64_t n_dst,
+                                                                   int64_t n_src,
+                                                                   const float* x_src,
+                                                                   int64_t x_src_stride,
+                                                                   const float* x_dst,
+                                                                   int64_t x_dst_stride,
+                                                                   int64_t dim,
+                                                                   float* score,
+                                                                   struct wholememory_env_func_t* p_env_fns,
+                                                                   void* stream);
+enum wholememory_error_code_t wholememory_ext_csc_edge_dot_backward(const int32_t* row_ptr,
+                                                                    const int32_t* col_ind,
+                                                                    int64_t n_edges,
+                                                                    int64_t n_dst,
+                                                                    int64_t n_src,
+                                                                    const float* x_src,
+                                                                    int64_t x_src_stride,
+                                                                    const float* x_dst,
+                                                                    int64_t x_dst_stride,
+                                                                    int64_t dim,
+                                                                    const float* grad_score,
+                                                                    float* grad_src,
+                                                                    int64_t grad_src_stride,
+                                                                    float* grad_dst,
+                                                                    int64_t grad_dst_stride,
+                                                                    struct wholememory_env_func_t* p_env_fns,
+                                                                    void* stream);
 
 /* ---- (3) testing seam ---------------------------------------------------------------------- */
 /* Replaces the device backend. Refuses (WHOLEMEMORY_NOT_SUPPORTED) unless the environment has

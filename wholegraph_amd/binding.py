@@ -321,6 +321,10 @@ PROTOTYPES = {
     "wholememory_ext_csc_mha_simple_backward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64,
                                                     _i, _i, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _P(EnvFunc),
                                                     _vp]),
+    "wholememory_ext_csc_edge_dot_forward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _P(EnvFunc),
+                                                 _vp]),
+    "wholememory_ext_csc_edge_dot_backward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _i64,
+                                                  _vp, _i64, _P(EnvFunc), _vp]),
     "wholememory_ext_csc_pna_aggregate_forward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i, _f, _vp, _i64, _vp,
                                                        _vp, _vp, _vp, _P(EnvFunc), _vp]),
     "wholememory_ext_csc_pna_aggregate_backward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i, _vp, _vp, _vp, _vp,

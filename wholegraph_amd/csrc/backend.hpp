@@ -403,6 +403,23 @@ struct wm_tconv_args : wm_csc_block {
   int64_t grad_value_stride;
 };
 
+// the dot product of the two endpoint rows of every edge of a sampled CSC block (kernels/edot.hip, the `edge_dot_n2n` op,
+// wholegraph_amd_ext.h section 2p): rows / strides in ELEMENTS (fp32). The targets have rows of their own (x_dst), so the
+// block may hold more targets than source rows
+struct wm_edot_args : wm_csc_block {
+  int64_t dim;
+  const float* x_src;       // [n_src, x_src_stride], dim columns used
+  int64_t x_src_stride;
+  const float* x_dst;       // [n_dst, x_dst_stride]: row d belongs to target d
+  int64_t x_dst_stride;
+  float* score;             // forward: [n_edges]
+  const float* grad;        // backward: dL/dscore [n_edges]
+  float* grad_src;          // backward: [n_src, grad_src_stride] or nullptr
+  int64_t grad_src_stride;
+  float* grad_dst;          // backward: [n_dst, grad_dst_stride] or nullptr
+  int64_t grad_dst_stride;
+};
+
 // multi-aggregator neighbour aggregation of a sampled CSC block (kernels/pna.hip, the `agg_concat_pna` op,
 // wholegraph_amd_ext.h section 2l): rows / strides in ELEMENTS (fp32). `mask` selects the aggregators (the bits of
 // wholememory_ext_pna_aggr_t); a row of out / grad has one slot of dim columns per selected aggregator, in the order of the
@@ -740,6 +757,13 @@ struct wm_device_backend {
   int (*walk_node2vec)(const wm_n2v_args* a, void* stream);
   // ---- negative sampling (kernels/neg_sample.hip, wholegraph_amd_ext.h section 2o); nullptr in a backend without it ----
   int (*negative_sample)(const wm_neg_args* a, void* stream);
+  // ---- edge dot product of a sampled CSC block (kernels/edot.hip, wholegraph_amd_ext.h section 2p); nullptr in a backend
+  // without it ----
+  // forward: score. backward: whichever of grad_src and grad_dst is not null. The index of gat_backward (read for grad_src
+  // only: all null otherwise); workspace of edot_backward_workspace_bytes
+  int (*edot_forward)(const wm_edot_args* a, void* stream);
+  size_t (*edot_backward_workspace_bytes)(const wm_edot_args* a);
+  int (*edot_backward)(const wm_edot_args* a, const wm_edge_index& ix, void* workspace, void* stream);
 };
 
 }  // extern "C"

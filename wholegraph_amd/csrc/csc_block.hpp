@@ -9,12 +9,15 @@
 namespace wm {
 
 // the block of an op's args, checked. col_ind_needed: the op's own rule for when col_ind is read; rows: what the op calls
-// its source rows ("x", "h")
+// its source rows ("x", "h"). targets_among_sources: the targets are the first n_dst of the source rows (every op but the
+// edge dot product, whose targets have rows of their own and may outnumber the sources)
 inline wm_csc_block checked_block(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst,
-                                  int64_t n_src, bool col_ind_needed, const char* rows)
+                                  int64_t n_src, bool col_ind_needed, const char* rows, bool targets_among_sources = true)
 {
   if (n_edges < 0 || n_dst < 0 || n_src < 0) throw invalid_input("negative size");
-  if (n_dst > n_src) throw invalid_input(format_string("n_dst > n_src: the targets are the first rows of %s", rows));
+  if (targets_among_sources && n_dst > n_src)
+    throw invalid_input(format_string("n_dst > n_src: the targets are the first rows of %s", rows));
+  if (n_dst >= (int64_t(1) << 31)) throw invalid_input("more than 2^31 - 1 targets");
   if (row_ptr == nullptr) throw invalid_input("row_ptr is null");
   if (col_ind_needed && col_ind == nullptr) throw invalid_input("col_ind is null");
   if (n_edges >= (int64_t(1) << 31) || n_src >= (int64_t(1) << 31)) throw invalid_input("more than 2^31 - 1 edges or rows");

@@ -1,8 +1,8 @@
 // wholegraph_amd — host side of the multi-head graph attention of a sampled CSC block (wholegraph_amd_ext.h, section 2c,
-// section 2f: the same op with an edge term in the logit, section 2g: GATv2, and section 2k: scaled dot-product attention):
-// validation, scratch, the edge index of the backward (the library's id sort over col_ind) and the launches of
-// kernels/gat.hip / kernels/gat_edge.hip / kernels/gatv2.hip / kernels/tconv.hip. The semantics, and the one order of every
-// fp32 sum, are stated in the header.
+// section 2f: the same op with an edge term in the logit, section 2g: GATv2, and section 2k: scaled dot-product attention)
+// and of the edge dot product (section 2p), the logit of (2k) on its own: validation, scratch, the edge index of the backward
+// (the library's id sort over col_ind) and the launches of kernels/gat.hip / kernels/gat_edge.hip / kernels/gatv2.hip /
+// kernels/tconv.hip / kernels/edot.hip. The semantics, and the one order of every fp32 sum, are stated in the header.
 #include <wholememory/wholegraph_amd_ext.h>
 
 #include <cmath>
@@ -14,6 +14,7 @@ namespace {
 using namespace wm;
 
 constexpr int64_t kMaxRow = int64_t(1) << 31, kMaxRowTconv = int64_t(1) << 30;   // heads * dim stays below these
+constexpr int64_t kMaxRowEdot = (int64_t(1) << 31) / 4;                             // dim of (2p) stays below this
 
 // what the args of every attention op hold alike, checked: the block (col_ind and alpha are read when a target has an
 // edge), heads, dim (heads * dim below `max_row`) and concat. rows: what the op calls its source rows
@@ -106,6 +107,24 @@ wm_tconv_args make_tconv_args(const int32_t* row_ptr, const int32_t* col_ind, in
   a.query_stride = query_stride;
   a.value        = value;
   a.value_stride = value_stride;
+  return a;
+}
+
+// what (2p) shares between its forward and backward: the block, whose targets have rows of their own, x_src and x_dst
+wm_edot_args make_edot_args(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges, int64_t n_dst, int64_t n_src,
+                            const float* x_src, int64_t x_src_stride, const float* x_dst, int64_t x_dst_stride, int64_t dim)
+{
+  wm_edot_args a{};
+  static_cast<wm_csc_block&>(a) =
+    checked_block(row_ptr, col_ind, n_edges, n_dst, n_src, n_edges > 0 && n_dst > 0, "x_src", false);
+  if (dim < 1 || dim >= kMaxRowEdot) throw invalid_input("dim must be in [1, 2^29)");
+  check_rows(x_src, n_src > 0, x_src_stride, dim, "x_src");
+  check_rows(x_dst, n_dst > 0, x_dst_stride, dim, "x_dst");
+  a.dim          = dim;
+  a.x_src        = x_src;
+  a.x_src_stride = x_src_stride;
+  a.x_dst        = x_dst;
+  a.x_dst_stride = x_dst_stride;
   return a;
 }
 
@@ -319,6 +338,53 @@ wholememory_error_code_t wholememory_ext_csc_mha_simple_backward(
   // (the edge index is read for grad_key and grad_value only)
   backward_over_index(a, grad_key != nullptr || grad_value != nullptr, bk->tconv_backward_workspace_bytes(&a), p_env_fns,
                       stream, [&](const wm_edge_index& ix, void* ws) { WM_BK(bk->tconv_backward(&a, ix, ws, stream)); });
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+wholememory_error_code_t wholememory_ext_csc_edge_dot_forward(const int32_t* row_ptr, const int32_t* col_ind, int64_t n_edges,
+                                                              int64_t n_dst, int64_t n_src, const float* x_src,
+                                                              int64_t x_src_stride, const float* x_dst, int64_t x_dst_stride,
+                                                              int64_t dim, float* score, wholememory_env_func_t* p_env_fns,
+                                                              void* stream)
+{
+  WM_API_BEGIN
+  wm_edot_args a = make_edot_args(row_ptr, col_ind, n_edges, n_dst, n_src, x_src, x_src_stride, x_dst, x_dst_stride, dim);
+  if (a.n_edges > 0 && score == nullptr) throw invalid_input("score is null");
+  check_env(p_env_fns);
+  const auto* bk = backend();
+  if (bk->edot_forward == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  a.score = score;
+  WM_BK(bk->edot_forward(&a, stream));
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+wholememory_error_code_t wholememory_ext_csc_edge_dot_backward(const int32_t* row_ptr, const int32_t* col_ind,
+                                                               int64_t n_edges, int64_t n_dst, int64_t n_src,
+                                                               const float* x_src, int64_t x_src_stride, const float* x_dst,
+                                                               int64_t x_dst_stride, int64_t dim, const float* grad_score,
+                                                               float* grad_src, int64_t grad_src_stride, float* grad_dst,
+                                                               int64_t grad_dst_stride, wholememory_env_func_t* p_env_fns,
+                                                               void* stream)
+{
+  WM_API_BEGIN
+  wm_edot_args a = make_edot_args(row_ptr, col_ind, n_edges, n_dst, n_src, x_src, x_src_stride, x_dst, x_dst_stride, dim);
+  if (a.n_edges > 0 && grad_score == nullptr) throw invalid_input("grad_score is null");
+  if (grad_src == nullptr && grad_dst == nullptr) throw invalid_input("no gradient asked for");
+  check_optional_rows(grad_src, grad_src_stride, dim, "grad_src");
+  check_optional_rows(grad_dst, grad_dst_stride, dim, "grad_dst");
+  check_env(p_env_fns);
+  const auto* bk = backend();
+  if (bk->edot_backward == nullptr || bk->edot_backward_workspace_bytes == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  a.grad            = grad_score;
+  a.grad_src        = grad_src;
+  a.grad_src_stride = grad_src_stride;
+  a.grad_dst        = grad_dst;
+  a.grad_dst_stride = grad_dst_stride;
+  // (the edge index is read for grad_src only)
+  backward_over_index(a, grad_src != nullptr, bk->edot_backward_workspace_bytes(&a), p_env_fns, stream,
+                      [&](const wm_edge_index& ix, void* ws) { WM_BK(bk->edot_backward(&a, ix, ws, stream)); });
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }

@@ -106,6 +106,9 @@ int hip_walk_uniform(const wm_walk_args* a, void* stream);
 int hip_walk_weighted(const wm_walk_args* a, void* stream);
 int hip_walk_node2vec(const wm_n2v_args* a, void* stream);
 int hip_negative_sample(const wm_neg_args* a, void* stream);
+int hip_edot_forward(const wm_edot_args* a, void* stream);
+size_t hip_edot_backward_workspace_bytes(const wm_edot_args* a);
+int hip_edot_backward(const wm_edot_args* a, const wm_edge_index& ix, void* workspace, void* stream);
 
 namespace {
 
@@ -309,6 +312,9 @@ const wm_device_backend kHipBackend = {
   hip_walk_weighted,
   hip_walk_node2vec,
   hip_negative_sample,
+  hip_edot_forward,
+  hip_edot_backward_workspace_bytes,
+  hip_edot_backward,
 };
 
 }  // namespace

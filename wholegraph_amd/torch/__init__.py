@@ -11,12 +11,15 @@ GraphSAGE layer ``cugraphops.EdgeWeightedSAGEConv`` on ``weighted_aggregation``,
 layer ``cugraphops.TransformerConv`` on ``transformer_aggregation`` (model name "transformer"), the PNA layer
 ``cugraphops.PNAConv`` on ``pna_aggregation`` (sum / mean / min / max / std in one pass; model name "pna"), and
 ``gather_aggregation``, layer 0's aggregation straight from a
-WholeMemory table, and ``quantized``, 8-bit row-quantized tables whose gather dequantizes the rows it reads). GAT in
+WholeMemory table, and ``quantized``, 8-bit row-quantized tables whose gather dequantizes the rows it reads; and
+``edge_dot.edge_dot_n2n``, the score of an edge as the dot product of its endpoint rows, with ``skipgram.skipgram_block`` and
+the ``node2vec.Node2Vec`` model that train embeddings on the walks and negatives of ``GraphStructure``). GAT in
 ``HomoGNNModel``, the dgl / pyg / wg routes, data loaders, launch helpers and option parsers of the reference are outside this build's scope.
 """
 from . import comm, embedding, graph_ops, graph_structure, initialize, tensor, utils, wholegraph_ops, wholememory_ops
 from . import aggregation, cugraphops, edge_gat_aggregation, gat_aggregation, gather_aggregation, gnn_model
 from . import gatv2_aggregation, pna_aggregation, quantized, rel_aggregation, transformer_aggregation, weighted_aggregation
+from . import edge_dot, node2vec, skipgram
 
 _PUBLIC = {
     comm: ("WholeMemoryCommunicator create_group_communicator destroy_communicator get_global_communicator "
@@ -34,12 +37,15 @@ _PUBLIC = {
     gnn_model: "set_framework create_gnn_layers create_rgcn_layers create_pna_layers create_sub_graph HomoGNNModel",
     gather_aggregation: "gather_agg_concat",
     pna_aggregation: "agg_concat_pna",
+    edge_dot: "edge_dot_n2n",
+    skipgram: "skipgram_block centers_of",
+    node2vec: "Node2Vec",
     quantized: ("WholeMemoryQuantizedTensor create_quantized_tensor quantized_row_bytes quantize_rows "
                 "dequantize_rows"),
 }
 __all__ = ["graph_ops", "wholegraph_ops", "aggregation", "cugraphops", "gat_aggregation", "gnn_model", "weighted_aggregation",
            "gather_aggregation", "edge_gat_aggregation", "gatv2_aggregation", "rel_aggregation", "quantized",
-           "transformer_aggregation", "pna_aggregation"]
+           "transformer_aggregation", "pna_aggregation", "edge_dot", "skipgram", "node2vec"]
 for _module, _names in _PUBLIC.items():
     for _name in _names.split():
         globals()[_name] = getattr(_module, _name)

@@ -111,11 +111,24 @@ struct wm_optimizer_args {
   int inputs_behind_sort;
 };
 
-// neighbour sampling on a CSR graph whose arrays are mapped (flat or chunked) in this process
-struct wm_sample_args {
+// a CSR graph in WholeMemory whose arrays are mapped (flat or chunked) in this process, the first fields of the args of every
+// op that reads one (`a->row_gref`, `a->n_edges`, ...): the neighbours of node v are csr_col_ptr[csr_row_ptr[v] :
+// csr_row_ptr[v + 1]]. The host fills it in one place (csr_graph.hpp: checked_graph::fill), the kernels read it through one
+// view (kernels/csr_view.cuh)
+struct wm_csr_graph {
   wholememory_gref_t row_gref, col_gref;  // csr_row_ptr (int64), csr_col_ptr (col_dtype)
   int64_t row_storage_offset, col_storage_offset;  // elements
   wholememory_dtype_t col_dtype;
+  int64_t n_nodes, n_edges;
+  // optional per-edge weights (float / double), same indexing as csr_col_ptr; WHOLEMEMORY_DT_UNKNOWN and an empty weight_gref
+  // where the call has none
+  wholememory_gref_t weight_gref;
+  int64_t weight_storage_offset;
+  wholememory_dtype_t weight_dtype;
+};
+
+// neighbour sampling on such a graph (the weights: sample_weighted only)
+struct wm_sample_args : wm_csr_graph {
   const int64_t* row_pairs;  // optional [2 * n_center] device: (row_ptr[c], row_ptr[c + 1]) fetched beforehand (DISTRIBUTED
                              // CSR); then out_ids must be nullptr and only out_edge_gid / out_center_lid are written
   const void* centers;  // [n_center] device
@@ -127,10 +140,6 @@ struct wm_sample_args {
   void* out_ids;              // [total] col_dtype
   int* out_center_lid;        // [total] or nullptr
   int64_t* out_edge_gid;      // [total] or nullptr
-  // weighted sampling only: per-edge weights (float / double), same indexing as csr_col_ptr
-  wholememory_gref_t weight_gref;
-  int64_t weight_storage_offset;
-  wholememory_dtype_t weight_dtype;
   // optional (device): the number of centres in use when `centers` / `sample_offsets` are sized for an upper bound n_center
   // (the frontier of the previous hop of a bounded multi-hop call); nullptr = n_center
   const int* n_center_dev;
@@ -443,17 +452,9 @@ struct wm_pna_args : wm_csc_block {
   int64_t out_stride;
 };
 
-// random walks over a CSR graph whose arrays are mapped (flat or chunked) in this process (kernels/walk.hip,
-// wholegraph_amd_ext.h section 2m). One launch; nothing is allocated and nothing read back
-struct wm_walk_args {
-  wholememory_gref_t row_gref, col_gref;  // csr_row_ptr (int64), csr_col_ptr (col_dtype)
-  int64_t row_storage_offset, col_storage_offset;  // elements
-  wholememory_dtype_t col_dtype;
-  int64_t n_nodes, n_edges;
-  // walk_weighted only: per-edge weights (float / double), same indexing as csr_col_ptr
-  wholememory_gref_t weight_gref;
-  int64_t weight_storage_offset;
-  wholememory_dtype_t weight_dtype;
+// random walks over such a graph (kernels/walk.hip, wholegraph_amd_ext.h section 2m; the weights: walk_weighted only). One
+// launch; nothing is allocated and nothing read back
+struct wm_walk_args : wm_csr_graph {
   const void* starts;   // [n] device
   wholememory_dtype_t start_dtype;
   int64_t n;            // walks; n * (walk_length + 1) < 2^31
@@ -471,13 +472,9 @@ struct wm_n2v_args {
   int col_sorted;      // non-zero: every row of csr_col_ptr is ascending (the caller's promise)
 };
 
-// negative sampling over the same kind of graph (kernels/neg_sample.hip, wholegraph_amd_ext.h section 2o). One launch; nothing
-// is allocated and nothing read back
-struct wm_neg_args {
-  wholememory_gref_t row_gref, col_gref;  // csr_row_ptr (int64), csr_col_ptr (col_dtype)
-  int64_t row_storage_offset, col_storage_offset;  // elements
-  wholememory_dtype_t col_dtype;
-  int64_t n_nodes, n_edges;
+// negative sampling over such a graph (kernels/neg_sample.hip, wholegraph_amd_ext.h section 2o; the weights stay empty). One
+// launch; nothing is allocated and nothing read back
+struct wm_neg_args : wm_csr_graph {
   const void* src;      // [n] device
   wholememory_dtype_t src_dtype;
   int64_t n;            // sources; n * num_negatives < 2^31

@@ -17,6 +17,7 @@
 #include <wholememory/wholegraph_op.h>
 #include <wholememory/wholememory_op.h>
 
+#include "csr_graph.hpp"
 #include "knobs.hpp"
 #include "neg_sample.hpp"
 #include "ops_internal.hpp"
@@ -38,35 +39,6 @@ void* output_alloc(wholememory_env_func_t* env, void* memory_context, int64_t co
   d.dtype          = dtype;
   d.storage_offset = 0;
   return env->output_fns.malloc_fn(&d, WHOLEMEMORY_MA_DEVICE, memory_context, env->output_fns.global_context);
-}
-
-bool array_of(wholememory_tensor_t t, const char* what, wholememory_array_description_t* out, wholememory_error_code_t* err)
-{
-  if (t == nullptr) {
-    *err = WHOLEMEMORY_INVALID_INPUT;
-    return false;
-  }
-  auto desc = *wholememory_tensor_get_tensor_description(t);
-  auto* td  = &desc;
-  if (td->dim != 1) {
-    WM_ERROR("%s should be 1D tensor.", what);
-    *err = WHOLEMEMORY_INVALID_INPUT;
-    return false;
-  }
-  if (!wholememory_convert_tensor_desc_to_array(out, td)) {
-    WM_ERROR("%s convert to array failed.", what);
-    *err = WHOLEMEMORY_LOGIC_ERROR;
-    return false;
-  }
-  return true;
-}
-
-bool is_index_dtype(wholememory_dtype_t d) { return d == WHOLEMEMORY_DT_INT || d == WHOLEMEMORY_DT_INT64; }
-
-wholememory_memory_type_t memory_type_of(wholememory_tensor_t t)
-{
-  if (!wholememory_tensor_has_handle(t)) return WHOLEMEMORY_MT_NONE;
-  return wholememory_get_memory_type(wholememory_tensor_get_memory_handle(t));
 }
 
 // a caller-side device array wrapped as a wholememory_tensor_t for the duration of one call
@@ -98,6 +70,15 @@ const wm_device_backend* graph_backend()
   return bk;
 }
 
+constexpr int kMaxWeightedFanout = 8192;   // what the weighted sampler takes
+
+// counts[0 .. n_center): what the sampler will emit per centre (row bounds from a.row_pairs when the graph is DISTRIBUTED)
+int sample_counts(const wm_device_backend* bk, const wm_sample_args& a, const int* n_dev, int* counts, void* stream)
+{
+  return bk->sample_counts(a.row_pairs != nullptr ? nullptr : &a.row_gref, a.row_storage_offset, a.row_pairs, a.centers,
+                           a.center_dtype, a.n_center, n_dev, a.max_sample_count, counts, stream);
+}
+
 // shared body of the two samplers; wm_csr_weight_ptr_tensor == nullptr selects the unweighted one
 wholememory_error_code_t sample_without_replacement(
   wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor,
@@ -110,36 +91,25 @@ wholememory_error_code_t sample_without_replacement(
   if (bk == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
   if (p_env_fns == nullptr || output_dest_memory_context == nullptr) return WHOLEMEMORY_INVALID_INPUT;
   wholememory_error_code_t err = WHOLEMEMORY_SUCCESS;
-  wholememory_array_description_t row_desc, col_desc, center_desc, offset_desc;
-  if (!array_of(wm_csr_row_ptr_tensor, "wm_csr_row_ptr_tensor", &row_desc, &err)) return err;
-  if (!array_of(wm_csr_col_ptr_tensor, "wm_csr_col_ptr_tensor", &col_desc, &err)) return err;
+  checked_graph g{wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_weight_ptr_tensor, false};
+  wholememory_array_description_t center_desc, offset_desc;
+  WHOLEMEMORY_RETURN_ON_FAIL(g.arrays());
   if (!array_of(center_nodes_tensor, "center_nodes_tensor", &center_desc, &err)) return err;
   if (!array_of(output_sample_offset_tensor, "output_sample_offset_tensor", &offset_desc, &err)) return err;
-  const auto row_mt = memory_type_of(wm_csr_row_ptr_tensor), col_mt = memory_type_of(wm_csr_col_ptr_tensor);
-  if (row_mt == WHOLEMEMORY_MT_HIERARCHY || col_mt == WHOLEMEMORY_MT_HIERARCHY) {
-    WM_ERROR("Memory type not supported.");
-    return WHOLEMEMORY_INVALID_INPUT;
-  }
   // DISTRIBUTED CSR (reference ..._impl_nccl.cu / ..._nccl_func.cuh:196-390): the arrays are not addressable from this
   // rank, so row bounds and sampled columns travel through wholememory_gather (collective over the CSR's communicator)
-  const bool via_gather = row_mt == WHOLEMEMORY_MT_DISTRIBUTED || col_mt == WHOLEMEMORY_MT_DISTRIBUTED;
+  bool via_gather = false;
+  WHOLEMEMORY_RETURN_ON_FAIL(g.placement(csr_tensors::row_col, nullptr, &via_gather));
   if (via_gather && weighted) {
     WM_ERROR("weighted sampling on DISTRIBUTED CSR tensors is not implemented (the reference has no such path either)");
     return WHOLEMEMORY_NOT_IMPLEMENTED;
   }
-  // dtype rules of ..._func.cuh:304-314 and the dispatch table of ..._impl_mapped.cu (logic_error there)
-  if (row_desc.dtype != WHOLEMEMORY_DT_INT64) {
-    WM_ERROR("wm_csr_row_ptr_tensor must be int64, got %d", static_cast<int>(row_desc.dtype));
-    return WHOLEMEMORY_LOGIC_ERROR;
-  }
+  WHOLEMEMORY_RETURN_ON_FAIL(g.row_dtype());
   if (offset_desc.dtype != WHOLEMEMORY_DT_INT) {
     WM_ERROR("output_sample_offset_tensor must be int32, got %d", static_cast<int>(offset_desc.dtype));
     return WHOLEMEMORY_LOGIC_ERROR;
   }
-  if (!is_index_dtype(col_desc.dtype) || !is_index_dtype(center_desc.dtype)) {
-    WM_ERROR("center nodes and csr_col_ptr must be int32 or int64");
-    return WHOLEMEMORY_LOGIC_ERROR;
-  }
+  WHOLEMEMORY_RETURN_ON_FAIL(g.col_and_id_dtype(center_desc.dtype, "center nodes"));
   const int64_t n = center_desc.size;
   if (n >= (INT64_C(1) << 31) - 1) return WHOLEMEMORY_INVALID_INPUT;
   if (offset_desc.size < n + 1) {
@@ -147,43 +117,22 @@ wholememory_error_code_t sample_without_replacement(
              static_cast<long>(offset_desc.size));
     return WHOLEMEMORY_INVALID_INPUT;
   }
-  wm_sample_args a{};
   if (weighted) {
-    wholememory_array_description_t weight_desc;
-    if (!array_of(wm_csr_weight_ptr_tensor, "wm_csr_weight_ptr_tensor", &weight_desc, &err)) return err;
-    const auto wmt = memory_type_of(wm_csr_weight_ptr_tensor);
-    if (wmt == WHOLEMEMORY_MT_HIERARCHY) return WHOLEMEMORY_INVALID_INPUT;
-    if (wmt == WHOLEMEMORY_MT_DISTRIBUTED) {
-      WM_ERROR("WEIGHTED sampling with a DISTRIBUTED weight tensor is not implemented (the reference has no such path either; "
-               "unweighted sampling on a DISTRIBUTED CSR is: see via_gather above)");
-      return WHOLEMEMORY_NOT_IMPLEMENTED;
-    }
-    if (weight_desc.dtype != WHOLEMEMORY_DT_FLOAT && weight_desc.dtype != WHOLEMEMORY_DT_DOUBLE) {
-      WM_ERROR("wm_csr_weight_ptr_tensor must be float or double");
-      return WHOLEMEMORY_LOGIC_ERROR;
-    }
-    if (weight_desc.size != col_desc.size) {
-      WM_ERROR("wm_csr_weight_ptr_tensor must have one weight per edge (%ld vs %ld)", static_cast<long>(weight_desc.size),
-               static_cast<long>(col_desc.size));
-      return WHOLEMEMORY_INVALID_INPUT;
-    }
-    if (max_sample_count > 8192) {
+    WHOLEMEMORY_RETURN_ON_FAIL(g.weight_array());
+    WHOLEMEMORY_RETURN_ON_FAIL(g.placement(
+      csr_tensors::weights, "WEIGHTED sampling with a DISTRIBUTED weight tensor is not implemented (the reference has no such "
+                            "path either; unweighted sampling on a DISTRIBUTED CSR is: see via_gather above)"));
+    WHOLEMEMORY_RETURN_ON_FAIL(g.weight_dtype());
+    WHOLEMEMORY_RETURN_ON_FAIL(g.one_weight_per_edge());
+    if (max_sample_count > kMaxWeightedFanout) {
       // reference: key generation + cub segmented sort for > 256 samples (func.cuh:470-560); the in-LDS selection
       // built here covers 1..8192 (a candidate list of 2 M keys must fit the 160 KiB of LDS)
       WM_ERROR("weighted sampling with max_sample_count > 8192 is not implemented in this build");
       return WHOLEMEMORY_NOT_IMPLEMENTED;
     }
-    WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_weight_ptr_tensor, &a.weight_gref));
-    a.weight_storage_offset = weight_desc.storage_offset;
-    a.weight_dtype          = weight_desc.dtype;
   }
-  if (!via_gather) {
-    WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_row_ptr_tensor, &a.row_gref));
-    WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_col_ptr_tensor, &a.col_gref));
-  }
-  a.row_storage_offset = row_desc.storage_offset;
-  a.col_storage_offset = col_desc.storage_offset;
-  a.col_dtype          = col_desc.dtype;
+  wm_sample_args a{};
+  WHOLEMEMORY_RETURN_ON_FAIL(g.fill(&a));
   a.centers            = wholememory_tensor_get_data_pointer(center_nodes_tensor);
   a.center_dtype       = center_desc.dtype;
   a.n_center           = static_cast<int>(n);
@@ -207,14 +156,13 @@ wholememory_error_code_t sample_without_replacement(
     WHOLEMEMORY_RETURN_ON_FAIL(wholememory_gather(wm_csr_row_ptr_tensor, ids_t.handle, pairs_t.handle, p_env_fns, stream, -1));
     a.row_pairs = pairs;
   }
-  WM_BK(bk->sample_counts(via_gather ? nullptr : &a.row_gref, a.row_storage_offset, a.row_pairs, a.centers, a.center_dtype,
-                          a.n_center, nullptr, max_sample_count, counts, stream));
+  WM_BK(sample_counts(bk, a, nullptr, counts, stream));
   WM_BK(bk->exclusive_scan_i32(counts, offsets, n + 1, scan_ws_ptr, scan_ws, stream));
   int total = 0;
   WM_BK(bk->memcpy_async(&total, offsets + n, sizeof(int), stream));
   WM_BK(bk->stream_sync(stream));
 
-  a.out_ids = output_alloc(p_env_fns, output_dest_memory_context, total, col_desc.dtype);
+  a.out_ids = output_alloc(p_env_fns, output_dest_memory_context, total, a.col_dtype);
   if (output_center_localid_memory_context != nullptr)
     a.out_center_lid = static_cast<int*>(output_alloc(p_env_fns, output_center_localid_memory_context, total, WHOLEMEMORY_DT_INT));
   if (output_edge_gid_memory_context != nullptr)
@@ -226,7 +174,7 @@ wholememory_error_code_t sample_without_replacement(
     a.out_ids     = nullptr;
     if (a.out_edge_gid == nullptr) a.out_edge_gid = static_cast<int64_t*>(egid_mem.device(total, WHOLEMEMORY_DT_INT64));
     if (total > 0) WM_BK(bk->sample_unweighted(&a, stream));
-    local_tensor egid_t(a.out_edge_gid, total, WHOLEMEMORY_DT_INT64), out_t(out_ids, total, col_desc.dtype);
+    local_tensor egid_t(a.out_edge_gid, total, WHOLEMEMORY_DT_INT64), out_t(out_ids, total, a.col_dtype);
     WHOLEMEMORY_RETURN_ON_FAIL(wholememory_gather(wm_csr_col_ptr_tensor, egid_t.handle, out_t.handle, p_env_fns, stream, -1));
   } else if (total > 0) {
     WM_BK(weighted ? bk->sample_weighted(&a, stream) : bk->sample_unweighted(&a, stream));
@@ -278,13 +226,22 @@ wholememory_error_code_t wholegraph_csr_weighted_sample_without_replacement(
 // allocated, nothing read back, the call does not synchronise, and every answer but SUCCESS is given before any device work.
 namespace {
 
-// one call's tensors: check() answers what section 2m lists, in its order, and touches no device; fill() maps the graph
-// tensors and fills the backend's argument block
+// an output that is the dense [n, width] block, given as a 2-D tensor of that shape or as a 1-D one of n * width entries
+bool dense_block(wholememory_tensor_t t, int64_t n, int64_t width)
+{
+  const auto d = *wholememory_tensor_get_tensor_description(t);
+  if (d.dim == 1) return d.sizes[0] == n * width && (d.strides[0] == 1 || d.sizes[0] <= 1);
+  return d.dim == 2 && d.sizes[0] == n && d.sizes[1] == width && d.strides[1] == 1 && (d.strides[0] == width || n <= 1);
+}
+
+// the walks' own tensors, next to the graph: check() answers what section 2m lists, in its order, and touches no device;
+// fill() fills the backend's argument block
 struct walk_call {
-  wholememory_tensor_t wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_weight_ptr_tensor, start_nodes_tensor;
+  checked_graph g;
+  wholememory_tensor_t start_nodes_tensor;
   int walk_length;
   wholememory_tensor_t output_walks_tensor, output_edge_ids_tensor;
-  wholememory_array_description_t row_desc, col_desc, start_desc, weight_desc;
+  wholememory_array_description_t start_desc;
 
   wholememory_error_code_t check();
   wholememory_error_code_t fill(unsigned long long random_seed, wm_walk_args& a) const;
@@ -294,49 +251,31 @@ wholememory_error_code_t walk_call::check()
 {
   if (output_walks_tensor == nullptr) return WHOLEMEMORY_INVALID_INPUT;
   wholememory_error_code_t err = WHOLEMEMORY_SUCCESS;
-  if (!array_of(wm_csr_row_ptr_tensor, "wm_csr_row_ptr_tensor", &row_desc, &err)) return err;
-  if (!array_of(wm_csr_col_ptr_tensor, "wm_csr_col_ptr_tensor", &col_desc, &err)) return err;
+  WHOLEMEMORY_RETURN_ON_FAIL(g.arrays());
   if (!array_of(start_nodes_tensor, "start_nodes_tensor", &start_desc, &err)) return err;
   if (walk_length < 1) {
     WM_ERROR("walk_length must be at least 1, got %d", walk_length);
     return WHOLEMEMORY_INVALID_INPUT;
   }
   const int64_t n = start_desc.size, L = walk_length;
-  if (n < 0 || row_desc.size < 1 || n > ((INT64_C(1) << 31) - 1) / (L + 1)) {
+  if (n < 0 || g.row_desc.size < 1 || n > ((INT64_C(1) << 31) - 1) / (L + 1)) {
     WM_ERROR("%ld walks of %d steps: the outputs must hold fewer than 2^31 entries", static_cast<long>(n), walk_length);
     return WHOLEMEMORY_INVALID_INPUT;
   }
-  // an output is the dense [n, width] block, given as a 2-D tensor of that shape or as a 1-D one of n * width entries
-  auto dense = [n](wholememory_tensor_t t, int64_t width) {
-    const auto d = *wholememory_tensor_get_tensor_description(t);
-    if (d.dim == 1) return d.sizes[0] == n * width && (d.strides[0] == 1 || d.sizes[0] <= 1);
-    return d.dim == 2 && d.sizes[0] == n && d.sizes[1] == width && d.strides[1] == 1 && (d.strides[0] == width || n <= 1);
-  };
-  if (!dense(output_walks_tensor, L + 1) || (output_edge_ids_tensor != nullptr && !dense(output_edge_ids_tensor, L))) {
+  if (!dense_block(output_walks_tensor, n, L + 1) ||
+      (output_edge_ids_tensor != nullptr && !dense_block(output_edge_ids_tensor, n, L))) {
     WM_ERROR("output_walks_tensor must be [%ld, %ld] and output_edge_ids_tensor [%ld, %ld], dense", static_cast<long>(n),
              static_cast<long>(L + 1), static_cast<long>(n), static_cast<long>(L));
     return WHOLEMEMORY_INVALID_INPUT;
   }
-  const bool weighted = wm_csr_weight_ptr_tensor != nullptr;
-  weight_desc         = wholememory_array_description_t{};
+  const bool weighted = g.weight != nullptr;
   if (weighted) {
-    if (!array_of(wm_csr_weight_ptr_tensor, "wm_csr_weight_ptr_tensor", &weight_desc, &err)) return err;
-    if (weight_desc.size != col_desc.size) {
-      WM_ERROR("wm_csr_weight_ptr_tensor must have one weight per edge (%ld vs %ld)", static_cast<long>(weight_desc.size),
-               static_cast<long>(col_desc.size));
-      return WHOLEMEMORY_INVALID_INPUT;
-    }
+    WHOLEMEMORY_RETURN_ON_FAIL(g.weight_array());
+    WHOLEMEMORY_RETURN_ON_FAIL(g.one_weight_per_edge());
   }
-  // dtype rules, as the samplers answer them
-  if (row_desc.dtype != WHOLEMEMORY_DT_INT64) {
-    WM_ERROR("wm_csr_row_ptr_tensor must be int64, got %d", static_cast<int>(row_desc.dtype));
-    return WHOLEMEMORY_LOGIC_ERROR;
-  }
-  if (!is_index_dtype(col_desc.dtype) || !is_index_dtype(start_desc.dtype)) {
-    WM_ERROR("start nodes and csr_col_ptr must be int32 or int64");
-    return WHOLEMEMORY_LOGIC_ERROR;
-  }
-  if (wholememory_tensor_get_tensor_description(output_walks_tensor)->dtype != col_desc.dtype) {
+  WHOLEMEMORY_RETURN_ON_FAIL(g.row_dtype());
+  WHOLEMEMORY_RETURN_ON_FAIL(g.col_and_id_dtype(start_desc.dtype, "start nodes"));
+  if (wholememory_tensor_get_tensor_description(output_walks_tensor)->dtype != g.col_desc.dtype) {
     WM_ERROR("output_walks_tensor must have the dtype of wm_csr_col_ptr_tensor");
     return WHOLEMEMORY_LOGIC_ERROR;
   }
@@ -345,46 +284,18 @@ wholememory_error_code_t walk_call::check()
     WM_ERROR("output_edge_ids_tensor must be int64");
     return WHOLEMEMORY_LOGIC_ERROR;
   }
-  if (weighted && weight_desc.dtype != WHOLEMEMORY_DT_FLOAT && weight_desc.dtype != WHOLEMEMORY_DT_DOUBLE) {
-    WM_ERROR("wm_csr_weight_ptr_tensor must be float or double");
-    return WHOLEMEMORY_LOGIC_ERROR;
-  }
-  const wholememory_tensor_t graph_tensors[3] = {wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_weight_ptr_tensor};
-  for (int i = 0; i < (weighted ? 3 : 2); i++) {
-    if (memory_type_of(graph_tensors[i]) == WHOLEMEMORY_MT_HIERARCHY) {
-      WM_ERROR("Memory type not supported.");
-      return WHOLEMEMORY_INVALID_INPUT;
-    }
-  }
-  for (int i = 0; i < (weighted ? 3 : 2); i++) {
-    if (memory_type_of(graph_tensors[i]) == WHOLEMEMORY_MT_DISTRIBUTED) {
-      WM_ERROR("random walks on DISTRIBUTED tensors are not implemented: every step would be a collective gather");
-      return WHOLEMEMORY_NOT_IMPLEMENTED;
-    }
-  }
-  return WHOLEMEMORY_SUCCESS;
+  if (weighted) WHOLEMEMORY_RETURN_ON_FAIL(g.weight_dtype());
+  return g.placement(csr_tensors::all,
+                     "random walks on DISTRIBUTED tensors are not implemented: every step would be a collective gather");
 }
 
 wholememory_error_code_t walk_call::fill(unsigned long long random_seed, wm_walk_args& a) const
 {
-  const bool weighted = wm_csr_weight_ptr_tensor != nullptr;
-  const int64_t n     = start_desc.size;
-  a                   = wm_walk_args{};
-  WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_row_ptr_tensor, &a.row_gref));
-  WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_col_ptr_tensor, &a.col_gref));
-  a.row_storage_offset = row_desc.storage_offset;
-  a.col_storage_offset = col_desc.storage_offset;
-  a.col_dtype          = col_desc.dtype;
-  a.n_nodes            = row_desc.size - 1;
-  a.n_edges            = col_desc.size;
-  if (weighted) {
-    WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_weight_ptr_tensor, &a.weight_gref));
-    a.weight_storage_offset = weight_desc.storage_offset;
-    a.weight_dtype          = weight_desc.dtype;
-  }
+  a = wm_walk_args{};
+  WHOLEMEMORY_RETURN_ON_FAIL(g.fill(&a));
   a.starts       = wholememory_tensor_get_data_pointer(start_nodes_tensor);
   a.start_dtype  = start_desc.dtype;
-  a.n            = n;
+  a.n            = start_desc.size;
   a.walk_length  = walk_length;
   a.random_seed  = random_seed;
   a.out_walks    = wholememory_tensor_get_data_pointer(output_walks_tensor);
@@ -405,7 +316,7 @@ wholememory_error_code_t wholememory_ext_csr_random_walk(
   void* stream)
 {
   WM_API_BEGIN
-  walk_call c{wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_weight_ptr_tensor, start_nodes_tensor, walk_length,
+  walk_call c{{wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_weight_ptr_tensor, false}, start_nodes_tensor, walk_length,
               output_walks_tensor, output_edge_ids_tensor};
   WHOLEMEMORY_RETURN_ON_FAIL(c.check());
   const auto* bk = backend();
@@ -427,7 +338,7 @@ wholememory_error_code_t wholememory_ext_csr_node2vec_walk(
   wholememory_tensor_t output_edge_ids_tensor, void* stream)
 {
   WM_API_BEGIN
-  walk_call c{wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_weight_ptr_tensor, start_nodes_tensor, walk_length,
+  walk_call c{{wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_weight_ptr_tensor, false}, start_nodes_tensor, walk_length,
               output_walks_tensor, output_edge_ids_tensor};
   WHOLEMEMORY_RETURN_ON_FAIL(c.check());
   if (!wm::n2v_pq_ok(p, q)) {
@@ -460,9 +371,9 @@ wholememory_error_code_t wholememory_ext_csr_negative_sample(
   WM_API_BEGIN
   if (output_negatives_tensor == nullptr) return WHOLEMEMORY_INVALID_INPUT;
   wholememory_error_code_t err = WHOLEMEMORY_SUCCESS;
-  wholememory_array_description_t row_desc, col_desc, src_desc;
-  if (!array_of(wm_csr_row_ptr_tensor, "wm_csr_row_ptr_tensor", &row_desc, &err)) return err;
-  if (!array_of(wm_csr_col_ptr_tensor, "wm_csr_col_ptr_tensor", &col_desc, &err)) return err;
+  checked_graph g{wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, nullptr, false};
+  wholememory_array_description_t src_desc;
+  WHOLEMEMORY_RETURN_ON_FAIL(g.arrays());
   if (!array_of(src_nodes_tensor, "src_nodes_tensor", &src_desc, &err)) return err;
   if (!wm::neg_scalars_ok(num_negatives, mode, exclude, max_tries)) {
     WM_ERROR("num_negatives must be >= 1, mode 0 or 1, exclude in [0, 3] and max_tries in [1, 64], got %d, %d, %d, %d",
@@ -470,57 +381,28 @@ wholememory_error_code_t wholememory_ext_csr_negative_sample(
     return WHOLEMEMORY_INVALID_INPUT;
   }
   const int64_t n = src_desc.size, K = num_negatives;
-  if (n < 0 || row_desc.size < 1 || n > ((INT64_C(1) << 31) - 1) / K) {
+  if (n < 0 || g.row_desc.size < 1 || n > ((INT64_C(1) << 31) - 1) / K) {
     WM_ERROR("%ld sources of %d negatives: the output must hold fewer than 2^31 entries", static_cast<long>(n), num_negatives);
     return WHOLEMEMORY_INVALID_INPUT;
   }
-  // the output is the dense [n, K] block, given as a 2-D tensor of that shape or as a 1-D one of n * K entries
-  const auto out_desc = *wholememory_tensor_get_tensor_description(output_negatives_tensor);
-  const bool dense =
-    out_desc.dim == 1 ? out_desc.sizes[0] == n * K && (out_desc.strides[0] == 1 || out_desc.sizes[0] <= 1)
-                      : out_desc.dim == 2 && out_desc.sizes[0] == n && out_desc.sizes[1] == K && out_desc.strides[1] == 1 &&
-                          (out_desc.strides[0] == K || n <= 1);
-  if (!dense) {
+  if (!dense_block(output_negatives_tensor, n, K)) {
     WM_ERROR("output_negatives_tensor must be [%ld, %ld], dense", static_cast<long>(n), static_cast<long>(K));
     return WHOLEMEMORY_INVALID_INPUT;
   }
-  // dtype rules, as the walks answer them
-  if (row_desc.dtype != WHOLEMEMORY_DT_INT64) {
-    WM_ERROR("wm_csr_row_ptr_tensor must be int64, got %d", static_cast<int>(row_desc.dtype));
-    return WHOLEMEMORY_LOGIC_ERROR;
-  }
-  if (!is_index_dtype(col_desc.dtype) || !is_index_dtype(src_desc.dtype)) {
-    WM_ERROR("source nodes and csr_col_ptr must be int32 or int64");
-    return WHOLEMEMORY_LOGIC_ERROR;
-  }
-  if (out_desc.dtype != col_desc.dtype) {
+  WHOLEMEMORY_RETURN_ON_FAIL(g.row_dtype());
+  WHOLEMEMORY_RETURN_ON_FAIL(g.col_and_id_dtype(src_desc.dtype, "source nodes"));
+  if (wholememory_tensor_get_tensor_description(output_negatives_tensor)->dtype != g.col_desc.dtype) {
     WM_ERROR("output_negatives_tensor must have the dtype of wm_csr_col_ptr_tensor");
     return WHOLEMEMORY_LOGIC_ERROR;
   }
-  const wholememory_tensor_t graph_tensors[2] = {wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor};
-  for (int i = 0; i < 2; i++) {
-    if (memory_type_of(graph_tensors[i]) == WHOLEMEMORY_MT_HIERARCHY) {
-      WM_ERROR("Memory type not supported.");
-      return WHOLEMEMORY_INVALID_INPUT;
-    }
-  }
-  for (int i = 0; i < 2; i++) {
-    if (memory_type_of(graph_tensors[i]) == WHOLEMEMORY_MT_DISTRIBUTED) {
-      WM_ERROR("negative sampling on DISTRIBUTED tensors is not implemented: every membership test would be a collective gather");
-      return WHOLEMEMORY_NOT_IMPLEMENTED;
-    }
-  }
+  WHOLEMEMORY_RETURN_ON_FAIL(g.placement(
+    csr_tensors::row_col,
+    "negative sampling on DISTRIBUTED tensors is not implemented: every membership test would be a collective gather"));
   const auto* bk = backend();
   if (bk->negative_sample == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
   if (n == 0) return WHOLEMEMORY_SUCCESS;
   wm_neg_args a{};
-  WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_row_ptr_tensor, &a.row_gref));
-  WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_col_ptr_tensor, &a.col_gref));
-  a.row_storage_offset = row_desc.storage_offset;
-  a.col_storage_offset = col_desc.storage_offset;
-  a.col_dtype          = col_desc.dtype;
-  a.n_nodes            = row_desc.size - 1;
-  a.n_edges            = col_desc.size;
+  WHOLEMEMORY_RETURN_ON_FAIL(g.fill(&a));
   a.src                = wholememory_tensor_get_data_pointer(src_nodes_tensor);
   a.src_dtype          = src_desc.dtype;
   a.n                  = n;
@@ -668,32 +550,19 @@ int hop_offsets(const wm_device_backend* bk, const wm_sample_args& a, const int*
                                       a.max_sample_count, offsets, scan_ws, scan_ws_bytes, ws_is_ones, stream);
     if (rc != -3) return rc;
   }
-  int rc = bk->sample_counts(&a.row_gref, a.row_storage_offset, nullptr, a.centers, a.center_dtype, a.n_center, n_dev,
-                             a.max_sample_count, counts, stream);
+  const int rc = sample_counts(bk, a, n_dev, counts, stream);
   if (rc != 0) return rc;
   return bk->exclusive_scan_i32(counts, offsets, static_cast<int64_t>(a.n_center) + 1, scan_ws, scan_ws_bytes, stream);
 }
 
-// the weight tensor of a weighted fused hop / chain: one float or double per edge, mapped into this rank. SUCCESS fills the
-// weight fields of `a`; NOT_SUPPORTED = the caller takes the two-op route, which reports what is wrong with the tensor
-wholememory_error_code_t ext_weights(wholememory_tensor_t weight_tensor, const wholememory_array_description_t& col_desc,
-                                     wm_sample_args* a)
+// the weight tensor of a weighted fused hop / chain: one float or double per edge, mapped into this rank, or the op declines
+wholememory_error_code_t declined_weights(checked_graph& g)
 {
-  wholememory_error_code_t err = WHOLEMEMORY_SUCCESS;
-  wholememory_array_description_t weight_desc;
-  if (!array_of(weight_tensor, "wm_csr_weight_ptr_tensor", &weight_desc, &err)) return err;
-  const auto wmt = memory_type_of(weight_tensor);
-  if (wmt == WHOLEMEMORY_MT_HIERARCHY || wmt == WHOLEMEMORY_MT_DISTRIBUTED ||
-      (weight_desc.dtype != WHOLEMEMORY_DT_FLOAT && weight_desc.dtype != WHOLEMEMORY_DT_DOUBLE) || weight_desc.size != col_desc.size)
-    return WHOLEMEMORY_NOT_SUPPORTED;
-  if (a != nullptr) {
-    WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(weight_tensor, &a->weight_gref));
-    a->weight_storage_offset = weight_desc.storage_offset;
-    a->weight_dtype          = weight_desc.dtype;
-  }
-  return WHOLEMEMORY_SUCCESS;
+  WHOLEMEMORY_RETURN_ON_FAIL(g.weight_array());
+  WHOLEMEMORY_RETURN_ON_FAIL(g.placement(csr_tensors::weights, nullptr));
+  WHOLEMEMORY_RETURN_ON_FAIL(g.weight_dtype());
+  return g.one_weight_per_edge();
 }
-constexpr int kMaxWeightedFanout = 8192;   // what the weighted sampler takes (sample_without_replacement above)
 
 // an edge attribute the chain fetches on the device (kernels/graph.hip: edge_attr_gather_kernel): 1-D, 4- or 8-byte elements,
 // one per edge, mapped into this rank. SUCCESS fills *out (when given); NOT_SUPPORTED = the caller gathers it itself
@@ -702,16 +571,14 @@ struct edge_attr {
   int64_t storage_offset;
   int elt_bytes;
 };
-wholememory_error_code_t ext_edge_attr(wholememory_tensor_t t, const wholememory_array_description_t& col_desc, edge_attr* out)
+wholememory_error_code_t ext_edge_attr(wholememory_tensor_t t, int64_t n_edges, edge_attr* out)
 {
   if (t == nullptr) return WHOLEMEMORY_INVALID_INPUT;
   auto td = *wholememory_tensor_get_tensor_description(t);
   wholememory_array_description_t desc;
   if (td.dim != 1 || !wholememory_convert_tensor_desc_to_array(&desc, &td)) return WHOLEMEMORY_NOT_SUPPORTED;
-  const auto mt       = memory_type_of(t);
-  const size_t elt    = wholememory_dtype_get_element_size(desc.dtype);
-  if (mt == WHOLEMEMORY_MT_HIERARCHY || mt == WHOLEMEMORY_MT_DISTRIBUTED || (elt != 4 && elt != 8) || desc.size != col_desc.size)
-    return WHOLEMEMORY_NOT_SUPPORTED;
+  const size_t elt = wholememory_dtype_get_element_size(desc.dtype);
+  if (placement_of({t}) != csr_placement::mapped || (elt != 4 && elt != 8) || desc.size != n_edges) return WHOLEMEMORY_NOT_SUPPORTED;
   if (out != nullptr) {
     WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(t, &out->gref));
     out->storage_offset = desc.storage_offset;
@@ -751,31 +618,25 @@ static wholememory_error_code_t sample_append_unique_body(
       output_center_localid_memory_context == nullptr)
     return WHOLEMEMORY_INVALID_INPUT;
   wholememory_error_code_t err = WHOLEMEMORY_SUCCESS;
-  wholememory_array_description_t row_desc, col_desc, center_desc, offset_desc;
-  if (!array_of(wm_csr_row_ptr_tensor, "wm_csr_row_ptr_tensor", &row_desc, &err)) return err;
-  if (!array_of(wm_csr_col_ptr_tensor, "wm_csr_col_ptr_tensor", &col_desc, &err)) return err;
+  checked_graph g{wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_weight_ptr_tensor, true};
+  wholememory_array_description_t center_desc, offset_desc;
+  WHOLEMEMORY_RETURN_ON_FAIL(g.arrays());
   if (!array_of(center_nodes_tensor, "center_nodes_tensor", &center_desc, &err)) return err;
   if (!array_of(output_sample_offset_tensor, "output_sample_offset_tensor", &offset_desc, &err)) return err;
   if (weighted && wm_csr_weight_ptr_tensor == nullptr) return WHOLEMEMORY_INVALID_INPUT;
-  const auto row_mt = memory_type_of(wm_csr_row_ptr_tensor), col_mt = memory_type_of(wm_csr_col_ptr_tensor);
-  const bool mapped = row_mt != WHOLEMEMORY_MT_HIERARCHY && col_mt != WHOLEMEMORY_MT_HIERARCHY &&
-                      row_mt != WHOLEMEMORY_MT_DISTRIBUTED && col_mt != WHOLEMEMORY_MT_DISTRIBUTED;
+  WHOLEMEMORY_RETURN_ON_FAIL(g.placement(csr_tensors::row_col, nullptr));
+  WHOLEMEMORY_RETURN_ON_FAIL(g.row_dtype());
   const int64_t n = center_desc.size;
   const int64_t room = n * static_cast<int64_t>(std::max(max_sample_count, 0));
-  if (!mapped || max_sample_count <= 0 || row_desc.dtype != WHOLEMEMORY_DT_INT64 || offset_desc.dtype != WHOLEMEMORY_DT_INT ||
-      !is_index_dtype(center_desc.dtype) || col_desc.dtype != center_desc.dtype || offset_desc.size < n + 1 || n == 0 ||
-      n + room >= (INT64_C(1) << 31) - 1)
+  if (max_sample_count <= 0 || offset_desc.dtype != WHOLEMEMORY_DT_INT || !is_index_dtype(center_desc.dtype) ||
+      g.col_desc.dtype != center_desc.dtype || offset_desc.size < n + 1 || n == 0 || n + room >= (INT64_C(1) << 31) - 1)
     return WHOLEMEMORY_NOT_SUPPORTED;
-  wm_sample_args a{};
   if (weighted) {
-    WHOLEMEMORY_RETURN_ON_FAIL(ext_weights(wm_csr_weight_ptr_tensor, col_desc, &a));
+    WHOLEMEMORY_RETURN_ON_FAIL(declined_weights(g));
     if (max_sample_count > kMaxWeightedFanout) return WHOLEMEMORY_NOT_SUPPORTED;
   }
-  WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_row_ptr_tensor, &a.row_gref));
-  WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_col_ptr_tensor, &a.col_gref));
-  a.row_storage_offset = row_desc.storage_offset;
-  a.col_storage_offset = col_desc.storage_offset;
-  a.col_dtype          = col_desc.dtype;
+  wm_sample_args a{};
+  WHOLEMEMORY_RETURN_ON_FAIL(g.fill(&a));
   a.centers            = wholememory_tensor_get_data_pointer(center_nodes_tensor);
   a.center_dtype       = center_desc.dtype;
   a.n_center           = static_cast<int>(n);
@@ -790,7 +651,7 @@ static wholememory_error_code_t sample_append_unique_body(
   int* counts          = static_cast<int*>(counts_mem.device(n + 1, WHOLEMEMORY_DT_INT));
   const size_t scan_ws = bk->scan_i32_workspace_bytes(n + 1);
   void* scan_ws_ptr    = scan_mem.device(static_cast<int64_t>(scan_ws), WHOLEMEMORY_DT_INT8);
-  void* ids            = ids_mem.device(room, col_desc.dtype);
+  void* ids            = ids_mem.device(room, a.col_dtype);
   int* lid             = static_cast<int*>(lid_mem.device(room, WHOLEMEMORY_DT_INT));
   int64_t* egid        = nullptr;
   if (output_edge_gid_memory_context != nullptr) egid = static_cast<int64_t*>(egid_mem.device(room, WHOLEMEMORY_DT_INT64));
@@ -932,22 +793,18 @@ static wholememory_error_code_t multilayer_sample_body(
     return WHOLEMEMORY_INVALID_INPUT;
   if (!query && edges && (edge_gid == nullptr || (n_attrs > 0 && attr_out == nullptr))) return WHOLEMEMORY_INVALID_INPUT;
   wholememory_error_code_t err = WHOLEMEMORY_SUCCESS;
-  wholememory_array_description_t row_desc, col_desc, seed_desc;
-  if (!array_of(wm_csr_row_ptr_tensor, "wm_csr_row_ptr_tensor", &row_desc, &err)) return err;
-  if (!array_of(wm_csr_col_ptr_tensor, "wm_csr_col_ptr_tensor", &col_desc, &err)) return err;
+  checked_graph g{wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_weight_ptr_tensor, true};
+  wholememory_array_description_t seed_desc;
+  WHOLEMEMORY_RETURN_ON_FAIL(g.arrays());
   if (!array_of(seed_nodes_tensor, "seed_nodes_tensor", &seed_desc, &err)) return err;
   if (weighted && wm_csr_weight_ptr_tensor == nullptr) return WHOLEMEMORY_INVALID_INPUT;
-  const auto row_mt = memory_type_of(wm_csr_row_ptr_tensor), col_mt = memory_type_of(wm_csr_col_ptr_tensor);
-  const bool mapped = row_mt != WHOLEMEMORY_MT_HIERARCHY && col_mt != WHOLEMEMORY_MT_HIERARCHY &&
-                      row_mt != WHOLEMEMORY_MT_DISTRIBUTED && col_mt != WHOLEMEMORY_MT_DISTRIBUTED;
-  if (!mapped || row_desc.dtype != WHOLEMEMORY_DT_INT64 || !is_index_dtype(seed_desc.dtype) || col_desc.dtype != seed_desc.dtype ||
-      seed_desc.size == 0)
-    return WHOLEMEMORY_NOT_SUPPORTED;
-  wm_sample_args a{};
-  if (weighted) WHOLEMEMORY_RETURN_ON_FAIL(ext_weights(wm_csr_weight_ptr_tensor, col_desc, query ? nullptr : &a));
+  WHOLEMEMORY_RETURN_ON_FAIL(g.placement(csr_tensors::row_col, nullptr));
+  WHOLEMEMORY_RETURN_ON_FAIL(g.row_dtype());
+  if (!is_index_dtype(seed_desc.dtype) || g.col_desc.dtype != seed_desc.dtype || seed_desc.size == 0) return WHOLEMEMORY_NOT_SUPPORTED;
+  if (weighted) WHOLEMEMORY_RETURN_ON_FAIL(declined_weights(g));
   std::vector<edge_attr> attrs(n_attrs);
   for (int k = 0; k < n_attrs; k++)
-    WHOLEMEMORY_RETURN_ON_FAIL(ext_edge_attr(attr_tensors[k], col_desc, query ? nullptr : &attrs[k]));
+    WHOLEMEMORY_RETURN_ON_FAIL(ext_edge_attr(attr_tensors[k], g.col_desc.size, query ? nullptr : &attrs[k]));
   std::vector<int64_t> cap_c(hops + 1), cap_s(hops);
   cap_c[0] = seed_desc.size;
   for (int h = 0; h < hops; h++) {
@@ -959,12 +816,9 @@ static wholememory_error_code_t multilayer_sample_body(
       return WHOLEMEMORY_NOT_SUPPORTED;
   }
   if (query) return WHOLEMEMORY_SUCCESS;
-  WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_row_ptr_tensor, &a.row_gref));
-  WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(wm_csr_col_ptr_tensor, &a.col_gref));
-  a.row_storage_offset = row_desc.storage_offset;
-  a.col_storage_offset = col_desc.storage_offset;
-  a.col_dtype          = col_desc.dtype;
-  a.center_dtype       = seed_desc.dtype;
+  wm_sample_args a{};
+  WHOLEMEMORY_RETURN_ON_FAIL(g.fill(&a));
+  a.center_dtype = seed_desc.dtype;
 
   // scratch of all hops at once (the kernels are queued back to back; nothing may be reused before the last one has run)
   temp_mem n_dev_mem(p_env_fns);
@@ -1000,7 +854,7 @@ static wholememory_error_code_t multilayer_sample_body(
     int* counts        = static_cast<int*>(scratch(nc + 1, WHOLEMEMORY_DT_INT));
     const size_t scan_ws = scan_bytes[h];
     void* scan_ws_ptr  = scan_block + scan_at[h];
-    void* ids          = scratch(ns, col_desc.dtype);
+    void* ids          = scratch(ns, a.col_dtype);
     void* ws = scratch(static_cast<int64_t>(bk->append_unique_workspace_bytes(nc, ns, seed_desc.dtype)), WHOLEMEMORY_DT_INT8);
     WM_BK(hop_offsets(bk, a, centres_in_use, counts, offsets, scan_ws_ptr, scan_ws, stream, 1));   // offsets[nc] = samples of the hop
     a.out_ids        = ids;

@@ -26,7 +26,7 @@
 #include "../knobs.hpp"
 #include "../backend.hpp"
 #include "../pcg.hpp"
-#include "gref_view.cuh"
+#include "csr_view.cuh"
 
 #include <mutex>
 #include <unordered_map>
@@ -280,8 +280,7 @@ __global__ void sample_count_kernel(gref_view row_ptr, int64_t row_off, const in
 
 // ------------------------------------------------------------------------------------------------ sampling
 struct sample_params {
-  gref_view row_ptr, col_ptr;
-  int64_t row_off, col_off;  // storage offsets (elements)
+  csr_view g;
   const int64_t* pairs;  // optional [2n]: (row_ptr[c], row_ptr[c+1]) already fetched (DISTRIBUTED CSR); then
                          // out_ids must be nullptr and the kernels only emit positions (edge ids)
   const void* centers;
@@ -320,8 +319,8 @@ __device__ __forceinline__ void row_bounds(const sample_params& p, int center, i
     return;
   }
   const int64_t nid = static_cast<int64_t>(static_cast<const IdT*>(p.centers)[center]);
-  *s                = gref_load<int64_t>(p.row_ptr, p.row_off + nid);
-  *e                = gref_load<int64_t>(p.row_ptr, p.row_off + nid + 1);
+  *s                = gref_load<int64_t>(p.g.row_ptr, p.g.row_off + nid);
+  *e                = gref_load<int64_t>(p.g.row_ptr, p.g.row_off + nid + 1);
 }
 
 template <typename IdT, typename ColT>
@@ -346,7 +345,7 @@ __global__ __launch_bounds__(kBlock) void sample_sparse_kernel(sample_params p)
   const int off = p.offsets[center];
   if (M <= 0 || N <= M) {  // every neighbour (reference sample_all_kernel / the `neighbor_count <= max` branches)
     for (int i = lane; i < N; i += 64) {
-      if (out) out[off + i] = gref_load<ColT>(p.col_ptr, p.col_off + s + i);
+      if (out) out[off + i] = gref_load<ColT>(p.g.col_ptr, p.g.col_off + s + i);
       if (p.out_lid) p.out_lid[off + i] = center;
       if (p.out_egid) p.out_egid[off + i] = s + i;
     }
@@ -399,7 +398,7 @@ __global__ __launch_bounds__(kBlock) void sample_sparse_kernel(sample_params p)
   }
   for (int i = lane; i < M; i += 64) {
     const int ai = a_s[i];
-    if (out) out[off + i] = gref_load<ColT>(p.col_ptr, p.col_off + s + ai);
+    if (out) out[off + i] = gref_load<ColT>(p.g.col_ptr, p.g.col_off + s + ai);
     if (p.out_lid) p.out_lid[off + i] = center;
     if (p.out_egid) p.out_egid[off + i] = s + ai;
   }
@@ -471,7 +470,7 @@ __global__ __launch_bounds__(kBlock) void sample_small_kernel(sample_params p)
   const int my_a       = px < 0 ? my_x : N - 1 - root_of_px;
   const int pos        = all ? gl : my_a;            // neighbour position this lane emits
   if ((all && gl < N) || (draw && gl < M)) {
-    if (out) out[off + gl] = gref_load<ColT>(p.col_ptr, p.col_off + s + pos);
+    if (out) out[off + gl] = gref_load<ColT>(p.g.col_ptr, p.g.col_off + s + pos);
     if (p.out_lid) p.out_lid[off + gl] = center;
     if (p.out_egid) p.out_egid[off + gl] = s + pos;
   }
@@ -496,7 +495,7 @@ __global__ __launch_bounds__(64) void sample_large_kernel(sample_params p)
   const int off = p.offsets[center];
   if (N <= M) {
     for (int i = lane; i < N; i += 64) {
-      if (out) out[off + i] = gref_load<ColT>(p.col_ptr, p.col_off + s + i);
+      if (out) out[off + i] = gref_load<ColT>(p.g.col_ptr, p.g.col_off + s + i);
       if (p.out_lid) p.out_lid[off + i] = center;
       if (p.out_egid) p.out_egid[off + i] = s + i;
     }
@@ -519,7 +518,7 @@ __global__ __launch_bounds__(64) void sample_large_kernel(sample_params p)
   __syncthreads();
   for (int i = lane; i < M; i += 64) {
     const int ai = __hip_atomic_load(slot(i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (out) out[off + i] = gref_load<ColT>(p.col_ptr, p.col_off + s + ai);
+    if (out) out[off + i] = gref_load<ColT>(p.g.col_ptr, p.g.col_off + s + ai);
     if (p.out_egid) p.out_egid[off + i] = s + ai;
   }
 }
@@ -561,8 +560,7 @@ int launch_sample(sample_params p, hipStream_t stream)
 // reference leaves the order to its queues and its tests compare per-center sets).
 struct weighted_params {
   sample_params sp;
-  gref_view weight_ptr;
-  int64_t weight_off;
+  csr_weights wt;
   int vthreads;
   int capacity;  // P: power of two >= 2 * max_sample, >= 128
 };
@@ -603,7 +601,7 @@ __global__ __launch_bounds__(64) void sample_weighted_kernel(weighted_params w)
   const int off = p.offsets[center];
   if (M <= 0 || N <= M) {
     for (int i = lane; i < N; i += 64) {
-      if (out) out[off + i] = gref_load<ColT>(p.col_ptr, p.col_off + s + i);
+      if (out) out[off + i] = gref_load<ColT>(p.g.col_ptr, p.g.col_off + s + i);
       if (p.out_lid) p.out_lid[off + i] = center;
       if (p.out_egid) p.out_egid[off + i] = s + i;
     }
@@ -630,7 +628,7 @@ __global__ __launch_bounds__(64) void sample_weighted_kernel(weighted_params w)
       bool accept  = false;
       uint64_t comp = 0;
       if (id < N) {
-        const float wt  = static_cast<float>(gref_load<WT>(w.weight_ptr, w.weight_off + s + id));
+        const float wt  = static_cast<float>(gref_load<WT>(w.wt.weight_ptr, w.wt.weight_off + s + id));
         const float key = weighted_sample_key(rng, wt);
         comp            = (static_cast<uint64_t>(orderable_float(key)) << 32) | (0xffffffffu - static_cast<uint32_t>(id));
         accept          = comp > threshold;
@@ -645,7 +643,7 @@ __global__ __launch_bounds__(64) void sample_weighted_kernel(weighted_params w)
   compact();
   for (int i = lane; i < M; i += 64) {
     const int ai = static_cast<int>(0xffffffffu - static_cast<uint32_t>(cand[i]));
-    if (out) out[off + i] = gref_load<ColT>(p.col_ptr, p.col_off + s + ai);
+    if (out) out[off + i] = gref_load<ColT>(p.g.col_ptr, p.g.col_off + s + ai);
     if (p.out_lid) p.out_lid[off + i] = center;
     if (p.out_egid) p.out_egid[off + i] = s + ai;
   }
@@ -721,7 +719,7 @@ __global__ __launch_bounds__(kBlock) void sample_weighted_small_kernel(weighted_
   if (draw) {
 #pragma unroll
     for (int k = 0; k < kStreams; k++)
-      wt0[k] = static_cast<float>(gref_load<WT>(w.weight_ptr, w.weight_off + s + min(k * G + gl, N - 1)));
+      wt0[k] = static_cast<float>(gref_load<WT>(w.wt.weight_ptr, w.wt.weight_off + s + min(k * G + gl, N - 1)));
   }
 #pragma unroll
   for (int k = 0; k < kStreams; k++) {
@@ -733,7 +731,7 @@ __global__ __launch_bounds__(kBlock) void sample_weighted_small_kernel(weighted_
       const int id  = id0 + gl;
       uint64_t comp = 0;
       if (id < n_draw) {
-        const float wt  = id0 == vbase ? wt0[k] : static_cast<float>(gref_load<WT>(w.weight_ptr, w.weight_off + s + id));
+        const float wt  = id0 == vbase ? wt0[k] : static_cast<float>(gref_load<WT>(w.wt.weight_ptr, w.wt.weight_off + s + id));
         const float key = weighted_sample_key(rng, wt);
         comp            = (static_cast<uint64_t>(orderable_float(key)) << 32) | (0xffffffffu - static_cast<uint32_t>(id));
       }
@@ -743,7 +741,7 @@ __global__ __launch_bounds__(kBlock) void sample_weighted_small_kernel(weighted_
   }
   const int pos = all ? gl : static_cast<int>(0xffffffffu - static_cast<uint32_t>(top));
   if ((all && gl < N) || (draw && gl < M)) {
-    if (out) out[off + gl] = gref_load<ColT>(p.col_ptr, p.col_off + s + pos);
+    if (out) out[off + gl] = gref_load<ColT>(p.g.col_ptr, p.g.col_off + s + pos);
     if (p.out_lid) p.out_lid[off + gl] = center;
     if (p.out_egid) p.out_egid[off + gl] = s + pos;
   }
@@ -778,15 +776,6 @@ int launch_weighted(weighted_params w, hipStream_t stream)
   }
   hipLaunchKernelGGL((sample_weighted_kernel<IdT, ColT, WT>), dim3(w.sp.n_center), dim3(64), lds, stream, w);
   return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-template <typename WT>
-int dispatch_weighted(const weighted_params& w, bool id32, bool col32, hipStream_t stream)
-{
-  if (id32 && col32) return launch_weighted<int32_t, int32_t, WT>(w, stream);
-  if (id32) return launch_weighted<int32_t, int64_t, WT>(w, stream);
-  if (col32) return launch_weighted<int64_t, int32_t, WT>(w, stream);
-  return launch_weighted<int64_t, int64_t, WT>(w, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ append_unique
@@ -1549,32 +1538,34 @@ int hip_exclusive_scan_i32(const int* in, int* out, int64_t n, void* ws, size_t 
                                  static_cast<hipStream_t>(stream)) == hipSuccess ? 0 : -2;
 }
 
+// the samplers' kernel arguments; false (the launcher answers -1) for a side fill that is not made of 16-byte pieces
+static bool sample_params_of(const wm_sample_args* a, sample_params* p)
+{
+  p->g       = csr_view_of(*a);
+  p->pairs   = a->row_pairs;
+  p->centers = a->centers, p->n_center = a->n_center, p->max_sample = a->max_sample_count;
+  p->seed = a->random_seed, p->offsets = a->sample_offsets;
+  p->out_ids = a->out_ids, p->out_lid = a->out_center_lid, p->out_egid = a->out_edge_gid;
+  p->n_center_dev = a->n_center_dev;
+  if (a->fill_ff_ptr != nullptr && a->fill_ff_bytes > 0) {
+    if ((reinterpret_cast<uintptr_t>(a->fill_ff_ptr) | a->fill_ff_bytes) & 15) return false;
+    p->fill_ptr = a->fill_ff_ptr, p->fill_vecs = a->fill_ff_bytes / 16;
+  }
+  return true;
+}
+
 int hip_sample_unweighted(const wm_sample_args* a, void* stream_v)
 {
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   sample_params p{};
-  p.centers = a->centers, p.n_center = a->n_center, p.max_sample = a->max_sample_count;
-  p.seed = a->random_seed, p.offsets = a->sample_offsets;
-  p.out_ids = a->out_ids, p.out_lid = a->out_center_lid, p.out_egid = a->out_edge_gid;
-  p.n_center_dev = a->n_center_dev;
-  if (a->fill_ff_ptr != nullptr && a->fill_ff_bytes > 0) {
-    if ((reinterpret_cast<uintptr_t>(a->fill_ff_ptr) | a->fill_ff_bytes) & 15) return -1;
-    p.fill_ptr = a->fill_ff_ptr, p.fill_vecs = a->fill_ff_bytes / 16;
-  }
+  if (!sample_params_of(a, &p)) return -1;
   if (a->row_pairs != nullptr) {
     // positions only: row bounds come from the fetched pairs, the caller gathers the columns by edge id afterwards
     if (a->out_ids != nullptr || a->out_edge_gid == nullptr) return -1;
-    p.pairs = a->row_pairs;
     return launch_sample<int64_t, int64_t>(p, stream);
   }
-  p.row_ptr = make_view(a->row_gref), p.col_ptr = make_view(a->col_gref);
-  p.row_off = a->row_storage_offset, p.col_off = a->col_storage_offset;
-  const bool id32 = a->center_dtype == WHOLEMEMORY_DT_INT, col32 = a->col_dtype == WHOLEMEMORY_DT_INT;
-  if ((!id32 && a->center_dtype != WHOLEMEMORY_DT_INT64) || (!col32 && a->col_dtype != WHOLEMEMORY_DT_INT64)) return -1;
-  if (id32 && col32) return launch_sample<int32_t, int32_t>(p, stream);
-  if (id32) return launch_sample<int32_t, int64_t>(p, stream);
-  if (col32) return launch_sample<int64_t, int32_t>(p, stream);
-  return launch_sample<int64_t, int64_t>(p, stream);
+  return dispatch_id_col(a->center_dtype, a->col_dtype,
+                         [&](auto id, auto col) { return launch_sample<decltype(id), decltype(col)>(p, stream); });
 }
 
 int hip_sample_weighted(const wm_sample_args* a, void* stream_v)
@@ -1582,28 +1573,15 @@ int hip_sample_weighted(const wm_sample_args* a, void* stream_v)
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   if (a->max_sample_count > kMaxWeighted) return -3;  // host side reports NOT_IMPLEMENTED before getting here
   weighted_params w{};
-  sample_params& p = w.sp;
-  p.row_ptr = make_view(a->row_gref), p.col_ptr = make_view(a->col_gref);
-  p.row_off = a->row_storage_offset, p.col_off = a->col_storage_offset;
-  p.centers = a->centers, p.n_center = a->n_center, p.max_sample = a->max_sample_count;
-  p.seed = a->random_seed, p.offsets = a->sample_offsets;
-  p.out_ids = a->out_ids, p.out_lid = a->out_center_lid, p.out_egid = a->out_edge_gid;
-  p.n_center_dev = a->n_center_dev;
-  if (a->fill_ff_ptr != nullptr && a->fill_ff_bytes > 0) {
-    if ((reinterpret_cast<uintptr_t>(a->fill_ff_ptr) | a->fill_ff_bytes) & 15) return -1;
-    p.fill_ptr = a->fill_ff_ptr, p.fill_vecs = a->fill_ff_bytes / 16;
-  }
-  w.weight_ptr = make_view(a->weight_gref);
-  w.weight_off = a->weight_storage_offset;
-  w.vthreads   = a->max_sample_count > 256 ? 256 : 128;  // reference block sizes (func.cuh:540-560, test utils :597-598)
-  int P        = 128;
+  if (!sample_params_of(a, &w.sp)) return -1;
+  w.wt       = csr_weights_of(*a);
+  w.vthreads = a->max_sample_count > 256 ? 256 : 128;  // reference block sizes (func.cuh:540-560, test utils :597-598)
+  int P      = 128;
   while (P < 2 * a->max_sample_count) P <<= 1;
-  w.capacity      = P;
-  const bool id32 = a->center_dtype == WHOLEMEMORY_DT_INT, col32 = a->col_dtype == WHOLEMEMORY_DT_INT;
-  if ((!id32 && a->center_dtype != WHOLEMEMORY_DT_INT64) || (!col32 && a->col_dtype != WHOLEMEMORY_DT_INT64)) return -1;
-  if (a->weight_dtype == WHOLEMEMORY_DT_FLOAT) return dispatch_weighted<float>(w, id32, col32, stream);
-  if (a->weight_dtype == WHOLEMEMORY_DT_DOUBLE) return dispatch_weighted<double>(w, id32, col32, stream);
-  return -1;
+  w.capacity = P;
+  return dispatch_id_col_weight(a->center_dtype, a->col_dtype, a->weight_dtype, [&](auto id, auto col, auto wt) {
+    return launch_weighted<decltype(id), decltype(col), decltype(wt)>(w, stream);
+  });
 }
 
 // the part of an append_unique workspace that has to be all-ones before phase 1 (the empty hash table); -3: the sort route

@@ -18,7 +18,7 @@
 #include "../backend.hpp"
 #include "../neg_sample.hpp"
 #include "../pcg.hpp"
-#include "gref_view.cuh"
+#include "csr_view.cuh"
 
 namespace wm {
 namespace {
@@ -30,33 +30,13 @@ constexpr int kNegBlock = 256;  // lanes per block
 constexpr int kNegGroup = 8;
 
 struct neg_params {
-  gref_view row_ptr, col_ptr;
-  int64_t row_off, col_off;  // storage offsets (elements)
-  int64_t n_nodes, n_edges;
+  csr_view g;
   const void* src;
   int64_t n;
   int num_negatives, mode, exclude, max_tries, col_sorted;
   uint64_t seed;
   void* out;  // ColT [n, K]
 };
-
-// does c occur in col_ind[s, e)? The group scans the row together: all lanes of the group call this with the same (s, e).
-template <typename ColT, int G>
-__device__ __forceinline__ bool neg_group_scan(const neg_params& p, int64_t s, int64_t e, int64_t c, int gl)
-{
-  bool found = false;
-  for (int64_t r = s; r < e; r += G) {
-    const int64_t pos = r + gl;
-    const ColT y      = pos < e ? gref_load<ColT>(p.col_ptr, p.col_off + pos) : ColT(0);
-    const int cnt     = e - r < G ? static_cast<int>(e - r) : G;
-#pragma unroll
-    for (int k = 0; k < G; k++) {
-      const ColT yk = __shfl(y, k, G);
-      found |= (k < cnt) & (static_cast<int64_t>(yk) == c);
-    }
-  }
-  return found;
-}
 
 template <typename IdT, typename ColT, int G>
 __global__ __launch_bounds__(kNegBlock) void neg_sample_kernel(neg_params p)
@@ -70,15 +50,15 @@ __global__ __launch_bounds__(kNegBlock) void neg_sample_kernel(neg_params p)
   const bool edges  = (p.exclude & 1) != 0;   // the same in every lane of the launch, as is sorted
   const bool sorted = p.col_sorted != 0;
   int64_t u         = live ? static_cast<int64_t>(static_cast<const IdT*>(p.src)[i]) : -1;
-  if (u < 0 || u >= p.n_nodes) u = -1;
+  if (u < 0 || u >= p.g.n_nodes) u = -1;
   int64_t s = 0, e = 0;   // the row that excludes its entries; empty where the bounds are not a row
   if (edges && u >= 0) {
-    s = gref_load<int64_t>(p.row_ptr, p.row_off + u);
-    e = gref_load<int64_t>(p.row_ptr, p.row_off + u + 1);
-    if (!neg_row_valid(s, e, p.n_edges)) s = e = 0;
+    s = gref_load<int64_t>(p.g.row_ptr, p.g.row_off + u);
+    e = gref_load<int64_t>(p.g.row_ptr, p.g.row_off + u + 1);
+    if (!neg_row_valid(s, e, p.g.n_edges)) s = e = 0;
   }
   ColT* out       = static_cast<ColT*>(p.out) + (live ? i * K : 0);
-  const auto load = [&](int64_t pos) { return static_cast<int64_t>(gref_load<ColT>(p.col_ptr, p.col_off + pos)); };
+  const auto load = [&](int64_t pos) { return static_cast<int64_t>(gref_load<ColT>(p.g.col_ptr, p.g.col_off + pos)); };
   for (int k0 = 0; k0 < K; k0 += G) {
     const int k     = k0 + gl;
     const bool mine = live && k < K;
@@ -91,8 +71,8 @@ __global__ __launch_bounds__(kNegBlock) void neg_sample_kernel(neg_params p)
       int64_t c = -1;
       bool kept = false;   // the candidate is in range and is not an excluded source
       if (open) {
-        c    = neg_candidate(load, g.next_u64(), p.mode, p.n_nodes, p.n_edges);
-        kept = !neg_rejected_early(c, u, p.n_nodes, p.exclude);
+        c    = neg_candidate(load, g.next_u64(), p.mode, p.g.n_nodes, p.g.n_edges);
+        kept = !neg_rejected_early(c, u, p.g.n_nodes, p.exclude);
       }
       bool in_row = false;
       if (edges) {
@@ -101,7 +81,7 @@ __global__ __launch_bounds__(kNegBlock) void neg_sample_kernel(neg_params p)
           if (look) in_row = n2v_row_has_sorted(load, s, e, c);
         } else {
           const unsigned long long vote = __ballot(look);
-          if (((vote >> first) & ((1ull << G) - 1ull)) != 0) in_row = neg_group_scan<ColT, G>(p, s, e, c, gl);
+          if (((vote >> first) & ((1ull << G) - 1ull)) != 0) in_row = csr_group_scan<ColT, G>(p.g, s, e, c, gl);
         }
       }
       if (kept && !in_row) result = c, open = false;
@@ -113,6 +93,7 @@ __global__ __launch_bounds__(kNegBlock) void neg_sample_kernel(neg_params p)
 template <typename IdT, typename ColT>
 int launch_neg(const neg_params& p, hipStream_t stream)
 {
+  if (p.n == 0) return 0;
   constexpr int per_block = kNegBlock / kNegGroup;
   const unsigned blocks   = static_cast<unsigned>((p.n + per_block - 1) / per_block);   // n < 2^31: below 2^28 blocks
   hipLaunchKernelGGL((neg_sample_kernel<IdT, ColT, kNegGroup>), dim3(blocks), dim3(kNegBlock), 0, stream, p);
@@ -128,22 +109,14 @@ int hip_negative_sample(const wm_neg_args* a, void* stream_v)
   if (a == nullptr || a->n < 0 || a->n_nodes < 0 || a->n_edges < 0) return -1;
   if (!neg_scalars_ok(a->num_negatives, a->mode, a->exclude, a->max_tries)) return -1;
   if (a->n * static_cast<int64_t>(a->num_negatives) >= (INT64_C(1) << 31)) return -1;
-  if (a->src_dtype != WHOLEMEMORY_DT_INT && a->src_dtype != WHOLEMEMORY_DT_INT64) return -1;
-  if (a->col_dtype != WHOLEMEMORY_DT_INT && a->col_dtype != WHOLEMEMORY_DT_INT64) return -1;
-  if (a->n == 0) return 0;
-  if (a->src == nullptr || a->out == nullptr) return -1;
+  if (a->n > 0 && (a->src == nullptr || a->out == nullptr)) return -1;
   neg_params p{};
-  p.row_ptr = make_view(a->row_gref), p.col_ptr = make_view(a->col_gref);
-  p.row_off = a->row_storage_offset, p.col_off = a->col_storage_offset;
-  p.n_nodes = a->n_nodes, p.n_edges = a->n_edges;
+  p.g   = csr_view_of(*a);
   p.src = a->src, p.n = a->n;
   p.num_negatives = a->num_negatives, p.mode = a->mode, p.exclude = a->exclude, p.max_tries = a->max_tries;
   p.col_sorted = a->col_sorted, p.seed = a->random_seed, p.out = a->out;
-  const bool id32 = a->src_dtype == WHOLEMEMORY_DT_INT, col32 = a->col_dtype == WHOLEMEMORY_DT_INT;
-  if (id32 && col32) return launch_neg<int32_t, int32_t>(p, stream);
-  if (id32) return launch_neg<int32_t, int64_t>(p, stream);
-  if (col32) return launch_neg<int64_t, int32_t>(p, stream);
-  return launch_neg<int64_t, int64_t>(p, stream);
+  return dispatch_id_col(a->src_dtype, a->col_dtype,
+                         [&](auto id, auto col) { return launch_neg<decltype(id), decltype(col)>(p, stream); });
 }
 
 }  // namespace wm

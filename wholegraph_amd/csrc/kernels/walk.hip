@@ -54,8 +54,8 @@ __global__ __launch_bounds__(kWalkBlock) void rwalk_uniform_kernel(walk_params p
       int deg;
       if (walk_row(p, v, &s, &deg)) {
         const int64_t pos = s + walk_uniform_pick(r, static_cast<uint32_t>(deg));
-        const int64_t c   = static_cast<int64_t>(gref_load<ColT>(p.col_ptr, p.col_off + pos));
-        if (c >= 0 && c < p.n_nodes) next = c, eid = pos;
+        const int64_t c   = static_cast<int64_t>(gref_load<ColT>(p.g.col_ptr, p.g.col_off + pos));
+        if (c >= 0 && c < p.g.n_nodes) next = c, eid = pos;
       }
     }
     out[t + 1] = static_cast<ColT>(next);
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(kWalkWBlock) void rwalk_weighted_kernel(walk_params
     float best_key = 0.f;
     int best_j     = -1;
     for (int j = gl; j < deg; j += G) {   // j ascending in a lane: the comparison alone keeps the lowest j of equal keys
-      const float wt = static_cast<float>(gref_load<WT>(p.weight_ptr, p.weight_off + s + j));
+      const float wt = static_cast<float>(gref_load<WT>(p.wt.weight_ptr, p.wt.weight_off + s + j));
       if (walk_weight_eligible(wt)) {
         const float key = walk_weighted_key(p.seed, static_cast<uint64_t>(w), static_cast<uint64_t>(L), static_cast<uint64_t>(t),
                                             static_cast<uint64_t>(j), wt);
@@ -99,8 +99,8 @@ __global__ __launch_bounds__(kWalkWBlock) void rwalk_weighted_kernel(walk_params
     int64_t next = -1, eid = -1;
     if (best_j >= 0) {   // (every lane of the group reads the one address)
       const int64_t pos = s + best_j;
-      const int64_t c   = static_cast<int64_t>(gref_load<ColT>(p.col_ptr, p.col_off + pos));
-      if (c >= 0 && c < p.n_nodes) next = c, eid = pos;
+      const int64_t c   = static_cast<int64_t>(gref_load<ColT>(p.g.col_ptr, p.g.col_off + pos));
+      if (c >= 0 && c < p.g.n_nodes) next = c, eid = pos;
     }
     if (live && gl == 0) {
       out[t + 1] = static_cast<ColT>(next);
@@ -113,6 +113,7 @@ __global__ __launch_bounds__(kWalkWBlock) void rwalk_weighted_kernel(walk_params
 template <typename IdT, typename ColT>
 int launch_uniform(const walk_params& p, hipStream_t stream)
 {
+  if (p.n == 0) return 0;
   const unsigned blocks = static_cast<unsigned>((p.n + kWalkBlock - 1) / kWalkBlock);
   hipLaunchKernelGGL((rwalk_uniform_kernel<IdT, ColT>), dim3(blocks), dim3(kWalkBlock), 0, stream, p);
   return hipGetLastError() == hipSuccess ? 0 : -2;
@@ -121,19 +122,11 @@ int launch_uniform(const walk_params& p, hipStream_t stream)
 template <typename IdT, typename ColT, typename WT>
 int launch_weighted(const walk_params& p, hipStream_t stream)
 {
+  if (p.n == 0) return 0;
   constexpr int per_block = kWalkWBlock / kWalkGroup;
   const unsigned blocks   = static_cast<unsigned>((p.n + per_block - 1) / per_block);   // n < 2^30: below 2^26 blocks
   hipLaunchKernelGGL((rwalk_weighted_kernel<IdT, ColT, WT, kWalkGroup>), dim3(blocks), dim3(kWalkWBlock), 0, stream, p);
   return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-template <typename WT>
-int dispatch_weighted(const walk_params& p, bool id32, bool col32, hipStream_t stream)
-{
-  if (id32 && col32) return launch_weighted<int32_t, int32_t, WT>(p, stream);
-  if (id32) return launch_weighted<int32_t, int64_t, WT>(p, stream);
-  if (col32) return launch_weighted<int64_t, int32_t, WT>(p, stream);
-  return launch_weighted<int64_t, int64_t, WT>(p, stream);
 }
 
 }  // namespace
@@ -142,25 +135,19 @@ int hip_walk_uniform(const wm_walk_args* a, void* stream_v)
 {
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   if (!walk_args_ok(a)) return -1;
-  if (a->n == 0) return 0;
-  const walk_params p = walk_params_of(a, false);
-  const bool id32 = a->start_dtype == WHOLEMEMORY_DT_INT, col32 = a->col_dtype == WHOLEMEMORY_DT_INT;
-  if (id32 && col32) return launch_uniform<int32_t, int32_t>(p, stream);
-  if (id32) return launch_uniform<int32_t, int64_t>(p, stream);
-  if (col32) return launch_uniform<int64_t, int32_t>(p, stream);
-  return launch_uniform<int64_t, int64_t>(p, stream);
+  const walk_params p = walk_params_of(a);
+  return dispatch_id_col(a->start_dtype, a->col_dtype,
+                         [&](auto id, auto col) { return launch_uniform<decltype(id), decltype(col)>(p, stream); });
 }
 
 int hip_walk_weighted(const wm_walk_args* a, void* stream_v)
 {
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   if (!walk_args_ok(a)) return -1;
-  if (a->weight_dtype != WHOLEMEMORY_DT_FLOAT && a->weight_dtype != WHOLEMEMORY_DT_DOUBLE) return -1;
-  if (a->n == 0) return 0;
-  const walk_params p = walk_params_of(a, true);
-  const bool id32 = a->start_dtype == WHOLEMEMORY_DT_INT, col32 = a->col_dtype == WHOLEMEMORY_DT_INT;
-  if (a->weight_dtype == WHOLEMEMORY_DT_FLOAT) return dispatch_weighted<float>(p, id32, col32, stream);
-  return dispatch_weighted<double>(p, id32, col32, stream);
+  const walk_params p = walk_params_of(a);
+  return dispatch_id_col_weight(a->start_dtype, a->col_dtype, a->weight_dtype, [&](auto id, auto col, auto wt) {
+    return launch_weighted<decltype(id), decltype(col), decltype(wt)>(p, stream);
+  });
 }
 
 }  // namespace wm

@@ -5,14 +5,13 @@
 #include <stdint.h>
 
 #include "../backend.hpp"
-#include "gref_view.cuh"
+#include "csr_view.cuh"
 
 namespace wm {
 
 struct walk_params {
-  gref_view row_ptr, col_ptr, weight_ptr;
-  int64_t row_off, col_off, weight_off;  // storage offsets (elements)
-  int64_t n_nodes, n_edges;
+  csr_view g;
+  csr_weights wt;
   const void* starts;
   int64_t n;
   int walk_length;
@@ -25,9 +24,9 @@ struct walk_params {
 // reads are issued before either is used.
 __device__ __forceinline__ bool walk_row(const walk_params& p, int64_t v, int64_t* s_out, int* deg_out)
 {
-  const int64_t s = gref_load<int64_t>(p.row_ptr, p.row_off + v);
-  const int64_t e = gref_load<int64_t>(p.row_ptr, p.row_off + v + 1);
-  const bool ok   = s >= 0 && e > s && e <= p.n_edges && e - s < (INT64_C(1) << 31);
+  const int64_t s = gref_load<int64_t>(p.g.row_ptr, p.g.row_off + v);
+  const int64_t e = gref_load<int64_t>(p.g.row_ptr, p.g.row_off + v + 1);
+  const bool ok   = s >= 0 && e > s && e <= p.g.n_edges && e - s < (INT64_C(1) << 31);
   *s_out          = s;
   *deg_out        = ok ? static_cast<int>(e - s) : 0;
   return ok;
@@ -37,16 +36,13 @@ template <typename IdT>
 __device__ __forceinline__ int64_t walk_start(const walk_params& p, int64_t w)
 {
   const int64_t v = static_cast<int64_t>(static_cast<const IdT*>(p.starts)[w]);
-  return v >= 0 && v < p.n_nodes ? v : -1;
+  return v >= 0 && v < p.g.n_nodes ? v : -1;
 }
 
-inline walk_params walk_params_of(const wm_walk_args* a, bool weighted)
+inline walk_params walk_params_of(const wm_walk_args* a)
 {
   walk_params p{};
-  p.row_ptr = make_view(a->row_gref), p.col_ptr = make_view(a->col_gref);
-  p.row_off = a->row_storage_offset, p.col_off = a->col_storage_offset;
-  if (weighted) p.weight_ptr = make_view(a->weight_gref), p.weight_off = a->weight_storage_offset;
-  p.n_nodes = a->n_nodes, p.n_edges = a->n_edges;
+  p.g = csr_view_of(*a), p.wt = csr_weights_of(*a);
   p.starts = a->starts, p.n = a->n, p.walk_length = a->walk_length, p.seed = a->random_seed;
   p.out_walks = a->out_walks, p.out_edge_ids = a->out_edge_ids;
   return p;
@@ -57,8 +53,6 @@ inline bool walk_args_ok(const wm_walk_args* a)
 {
   if (a == nullptr || a->n < 0 || a->walk_length < 1 || a->n * (static_cast<int64_t>(a->walk_length) + 1) >= (INT64_C(1) << 31)) return false;
   if (a->n_nodes < 0 || a->n_edges < 0) return false;
-  if (a->start_dtype != WHOLEMEMORY_DT_INT && a->start_dtype != WHOLEMEMORY_DT_INT64) return false;
-  if (a->col_dtype != WHOLEMEMORY_DT_INT && a->col_dtype != WHOLEMEMORY_DT_INT64) return false;
   return a->n == 0 || (a->starts != nullptr && a->out_walks != nullptr);
 }
 

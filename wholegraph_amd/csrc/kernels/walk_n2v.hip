@@ -40,24 +40,6 @@ struct n2v_params {
   int col_sorted;
 };
 
-// does x occur in col_ind[us, ue)? The group scans the row together: all lanes of the group call this with the same (us, ue).
-template <typename ColT, int G>
-__device__ __forceinline__ bool n2v_group_scan(const walk_params& p, int64_t us, int64_t ue, ColT x, int gl)
-{
-  bool found = false;
-  for (int64_t r = us; r < ue; r += G) {
-    const int64_t pos = r + gl;
-    const ColT y      = pos < ue ? gref_load<ColT>(p.col_ptr, p.col_off + pos) : ColT(0);
-    const int cnt     = ue - r < G ? static_cast<int>(ue - r) : G;
-#pragma unroll
-    for (int k = 0; k < G; k++) {
-      const ColT yk = __shfl(y, k, G);
-      found |= (k < cnt) & (yk == x);
-    }
-  }
-  return found;
-}
-
 // WT = void: no weight tensor, every edge has weight 1.0f
 template <typename IdT, typename ColT, typename WT, int G>
 __global__ __launch_bounds__(kN2vBlock) void n2v_walk_kernel(n2v_params q)
@@ -92,11 +74,11 @@ __global__ __launch_bounds__(kN2vBlock) void n2v_walk_kernel(n2v_params q)
         x[b]        = ColT(-1);
         wt[b]       = 0.f;
         if (j < deg) {
-          x[b] = gref_load<ColT>(p.col_ptr, p.col_off + s + j);
+          x[b] = gref_load<ColT>(p.g.col_ptr, p.g.col_off + s + j);
           if constexpr (std::is_void<WT>::value) {
             wt[b] = 1.0f;
           } else {
-            wt[b] = static_cast<float>(gref_load<WT>(p.weight_ptr, p.weight_off + s + j));
+            wt[b] = static_cast<float>(gref_load<WT>(p.wt.weight_ptr, p.wt.weight_off + s + j));
           }
         }
       }
@@ -108,10 +90,10 @@ __global__ __launch_bounds__(kN2vBlock) void n2v_walk_kernel(n2v_params q)
           if (sorted) {
             if (j < deg && static_cast<int64_t>(x[b]) != u)
               in_row = n2v_row_has_sorted(
-                [&](int64_t pos) { return static_cast<int64_t>(gref_load<ColT>(p.col_ptr, p.col_off + pos)); }, us, ue,
+                [&](int64_t pos) { return static_cast<int64_t>(gref_load<ColT>(p.g.col_ptr, p.g.col_off + pos)); }, us, ue,
                 static_cast<int64_t>(x[b]));
           } else {
-            in_row = n2v_group_scan<ColT, G>(p, us, ue, x[b], gl);
+            in_row = csr_group_scan<ColT, G>(p.g, us, ue, x[b], gl);
           }
         }
         if (j < deg) {
@@ -135,7 +117,7 @@ __global__ __launch_bounds__(kN2vBlock) void n2v_walk_kernel(n2v_params q)
     int64_t next = -1, eid = -1;
     if (best_j >= 0) {
       const int64_t c = static_cast<int64_t>(best_x);
-      if (c >= 0 && c < p.n_nodes) next = c, eid = s + best_j;
+      if (c >= 0 && c < p.g.n_nodes) next = c, eid = s + best_j;
     }
     if (live && gl == 0) {
       out[t + 1] = static_cast<ColT>(next);
@@ -149,19 +131,11 @@ __global__ __launch_bounds__(kN2vBlock) void n2v_walk_kernel(n2v_params q)
 template <typename IdT, typename ColT, typename WT>
 int launch_n2v(const n2v_params& q, hipStream_t stream)
 {
+  if (q.walk.n == 0) return 0;
   constexpr int per_block = kN2vBlock / kN2vGroup;
   const unsigned blocks   = static_cast<unsigned>((q.walk.n + per_block - 1) / per_block);   // n < 2^30: below 2^26 blocks
   hipLaunchKernelGGL((n2v_walk_kernel<IdT, ColT, WT, kN2vGroup>), dim3(blocks), dim3(kN2vBlock), 0, stream, q);
   return hipGetLastError() == hipSuccess ? 0 : -2;
-}
-
-template <typename WT>
-int dispatch_n2v(const n2v_params& q, bool id32, bool col32, hipStream_t stream)
-{
-  if (id32 && col32) return launch_n2v<int32_t, int32_t, WT>(q, stream);
-  if (id32) return launch_n2v<int32_t, int64_t, WT>(q, stream);
-  if (col32) return launch_n2v<int64_t, int32_t, WT>(q, stream);
-  return launch_n2v<int64_t, int64_t, WT>(q, stream);
 }
 
 }  // namespace
@@ -170,18 +144,18 @@ int hip_walk_node2vec(const wm_n2v_args* a, void* stream_v)
 {
   hipStream_t stream = static_cast<hipStream_t>(stream_v);
   if (a == nullptr || !walk_args_ok(&a->walk)) return -1;
-  const wholememory_dtype_t wdt = a->walk.weight_dtype;
-  if (wdt != WHOLEMEMORY_DT_UNKNOWN && wdt != WHOLEMEMORY_DT_FLOAT && wdt != WHOLEMEMORY_DT_DOUBLE) return -1;
   const float big = 3.402823466e+38f;
   if (!(a->inv_p > 0.0f && a->inv_p <= big && a->inv_q > 0.0f && a->inv_q <= big)) return -1;
-  if (a->walk.n == 0) return 0;
   n2v_params q{};
-  q.walk  = walk_params_of(&a->walk, wdt != WHOLEMEMORY_DT_UNKNOWN);
+  q.walk  = walk_params_of(&a->walk);
   q.inv_p = a->inv_p, q.inv_q = a->inv_q, q.col_sorted = a->col_sorted;
-  const bool id32 = a->walk.start_dtype == WHOLEMEMORY_DT_INT, col32 = a->walk.col_dtype == WHOLEMEMORY_DT_INT;
-  if (wdt == WHOLEMEMORY_DT_FLOAT) return dispatch_n2v<float>(q, id32, col32, stream);
-  if (wdt == WHOLEMEMORY_DT_DOUBLE) return dispatch_n2v<double>(q, id32, col32, stream);
-  return dispatch_n2v<void>(q, id32, col32, stream);
+  const wm_walk_args& w = a->walk;
+  if (w.weight_dtype == WHOLEMEMORY_DT_UNKNOWN)
+    return dispatch_id_col(w.start_dtype, w.col_dtype,
+                           [&](auto id, auto col) { return launch_n2v<decltype(id), decltype(col), void>(q, stream); });
+  return dispatch_id_col_weight(w.start_dtype, w.col_dtype, w.weight_dtype, [&](auto id, auto col, auto wt) {
+    return launch_n2v<decltype(id), decltype(col), decltype(wt)>(q, stream);
+  });
 }
 
 }  // namespace wm

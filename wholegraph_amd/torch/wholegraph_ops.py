@@ -23,6 +23,18 @@ def _tensor_dim(h):
     return int(wmb.lib().wholememory_tensor_get_tensor_description(h).contents.dim)
 
 
+def _seed64(random_seed):
+    """the seed as the C ABI takes it; 64 random bits when the caller gave none"""
+    if random_seed is None:
+        random_seed = random.getrandbits(64)
+    return C.c_ulonglong(int(random_seed) & 0xFFFFFFFFFFFFFFFF)
+
+
+def _col_dtype(col_handle):
+    """the torch dtype of csr_col_ptr, which is that of every output that holds node ids"""
+    return wholememory_dtype_to_torch_dtype(wmb.lib().wholememory_tensor_get_tensor_description(col_handle).contents.dtype)
+
+
 def _sample_outputs(offset, dest, lid, egid, need_center_local_output, need_edge_output):
     if need_edge_output and need_center_local_output:
         return offset, dest.get_tensor(), lid.get_tensor(), egid.get_tensor()
@@ -42,8 +54,6 @@ def unweighted_sample_without_replacement(wm_csr_row_ptr_tensor, wm_csr_col_ptr_
     assert _tensor_dim(row) == 1
     assert _tensor_dim(col) == 1
     assert center_nodes_tensor.dim() == 1
-    if random_seed is None:
-        random_seed = random.getrandbits(64)
     offset = torch.empty(center_nodes_tensor.shape[0] + 1, device=op_device(), dtype=torch.int)
     dest = TorchMemoryContext()
     lid = TorchMemoryContext() if need_center_local_output else None
@@ -52,7 +62,7 @@ def unweighted_sample_without_replacement(wm_csr_row_ptr_tensor, wm_csr_col_ptr_
     wmb.check(wmb.lib().wholegraph_csr_unweighted_sample_without_replacement(
         row, col, wc.handle, int(max_sample_count), wo.handle, C.c_void_p(dest.get_c_context()),
         C.c_void_p(lid.get_c_context() if lid else 0), C.c_void_p(egid.get_c_context() if egid else 0),
-        C.c_ulonglong(random_seed & 0xFFFFFFFFFFFFFFFF), get_wholegraph_env_fns(), C.c_void_p(get_stream())))
+        _seed64(random_seed), get_wholegraph_env_fns(), C.c_void_p(get_stream())))
     return _sample_outputs(offset, dest, lid, egid, need_center_local_output, need_edge_output)
 
 
@@ -68,12 +78,10 @@ def sample_append_unique(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, center_no
     (wholememory_ext_sample_append_unique_edges); declined in the same cases."""
     row, col = _handle(wm_csr_row_ptr_tensor), _handle(wm_csr_col_ptr_tensor)
     assert center_nodes_tensor.dim() == 1
-    if random_seed is None:
-        random_seed = random.getrandbits(64)
     offset = torch.empty(center_nodes_tensor.shape[0] + 1, device=op_device(), dtype=torch.int)
     uniq, pos, lid = TorchMemoryContext(), TorchMemoryContext(), TorchMemoryContext()
     wc, wo = wrap_torch_tensor(center_nodes_tensor), wrap_torch_tensor(offset)
-    tail = (int(max_sample_count), C.c_ulonglong(random_seed & 0xFFFFFFFFFFFFFFFF), wo.handle, C.c_void_p(uniq.get_c_context()),
+    tail = (int(max_sample_count), _seed64(random_seed), wo.handle, C.c_void_p(uniq.get_c_context()),
             C.c_void_p(pos.get_c_context()), C.c_void_p(lid.get_c_context()), get_wholegraph_env_fns(), C.c_void_p(get_stream()))
     egid = TorchMemoryContext() if need_edge_output else None
     if need_edge_output:
@@ -277,8 +285,6 @@ def weighted_sample_without_replacement(wm_csr_row_ptr_tensor, wm_csr_col_ptr_te
     (wm_csr_weight_ptr_tensor: float32/float64, one per edge). max_sample_count <= 8192."""
     row, col, wgt = _handle(wm_csr_row_ptr_tensor), _handle(wm_csr_col_ptr_tensor), _handle(wm_csr_weight_ptr_tensor)
     assert center_nodes_tensor.dim() == 1
-    if random_seed is None:
-        random_seed = random.getrandbits(64)
     offset = torch.empty(center_nodes_tensor.shape[0] + 1, device=op_device(), dtype=torch.int)
     dest = TorchMemoryContext()
     lid = TorchMemoryContext() if need_center_local_output else None
@@ -287,8 +293,31 @@ def weighted_sample_without_replacement(wm_csr_row_ptr_tensor, wm_csr_col_ptr_te
     wmb.check(wmb.lib().wholegraph_csr_weighted_sample_without_replacement(
         row, col, wgt, wc.handle, int(max_sample_count), wo.handle, C.c_void_p(dest.get_c_context()),
         C.c_void_p(lid.get_c_context() if lid else 0), C.c_void_p(egid.get_c_context() if egid else 0),
-        C.c_ulonglong(random_seed & 0xFFFFFFFFFFFFFFFF), get_wholegraph_env_fns(), C.c_void_p(get_stream())))
+        _seed64(random_seed), get_wholegraph_env_fns(), C.c_void_p(get_stream())))
     return _sample_outputs(offset, dest, lid, egid, need_center_local_output, need_edge_output)
+
+
+def _check_walk_arguments(start_nodes_tensor, walk_length):
+    if int(walk_length) < 1:
+        raise ValueError("walk_length must be at least 1, got %r" % (walk_length,))
+    if start_nodes_tensor.dim() != 1:
+        raise ValueError("start_nodes_tensor must be 1-D, got %d dimensions" % start_nodes_tensor.dim())
+
+
+def _walk(entry, wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_weight_ptr_tensor, start_nodes_tensor, walk_length,
+          step_rule, random_seed, need_edge_output):
+    """The library call of random_walk and node2vec_walk. `entry` takes the graph, the starts and the length, then
+    `step_rule` (the step rule's own arguments: none for random_walk), then the seed, the two outputs and the stream."""
+    row, col = _handle(wm_csr_row_ptr_tensor), _handle(wm_csr_col_ptr_tensor)
+    wgt = None if wm_csr_weight_ptr_tensor is None else _handle(wm_csr_weight_ptr_tensor)
+    n, steps = start_nodes_tensor.shape[0], int(walk_length)
+    walks = torch.empty((n, steps + 1), device=op_device(), dtype=_col_dtype(col))
+    edge_ids = torch.empty((n, steps), device=op_device(), dtype=torch.int64) if need_edge_output else None
+    ws, ww = wrap_torch_tensor(start_nodes_tensor), wrap_torch_tensor(walks)
+    we = wrap_torch_tensor(edge_ids) if need_edge_output else None
+    wmb.check(entry(row, col, wgt, ws.handle, steps, *step_rule, _seed64(random_seed), ww.handle,
+                    we.handle if we is not None else None, C.c_void_p(get_stream())))
+    return (walks, edge_ids) if need_edge_output else walks
 
 
 def random_walk(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, start_nodes_tensor: torch.Tensor, walk_length: int,
@@ -300,24 +329,9 @@ def random_walk(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, start_nodes_tensor
     every step taken, -1 elsewhere. A step goes to a neighbour picked uniformly, or, with wm_csr_weight_ptr_tensor (keyword;
     float32 / float64, one per edge), with probability proportional to its weight among the neighbours of positive weight.
     Walk w depends on (random_seed, w) alone, not on the size of the batch."""
-    if int(walk_length) < 1:
-        raise ValueError("walk_length must be at least 1, got %r" % (walk_length,))
-    if start_nodes_tensor.dim() != 1:
-        raise ValueError("start_nodes_tensor must be 1-D, got %d dimensions" % start_nodes_tensor.dim())
-    row, col = _handle(wm_csr_row_ptr_tensor), _handle(wm_csr_col_ptr_tensor)
-    wgt = None if wm_csr_weight_ptr_tensor is None else _handle(wm_csr_weight_ptr_tensor)
-    if random_seed is None:
-        random_seed = random.getrandbits(64)
-    n, steps = start_nodes_tensor.shape[0], int(walk_length)
-    col_dtype = wholememory_dtype_to_torch_dtype(wmb.lib().wholememory_tensor_get_tensor_description(col).contents.dtype)
-    walks = torch.empty((n, steps + 1), device=op_device(), dtype=col_dtype)
-    edge_ids = torch.empty((n, steps), device=op_device(), dtype=torch.int64) if need_edge_output else None
-    ws, ww = wrap_torch_tensor(start_nodes_tensor), wrap_torch_tensor(walks)
-    we = wrap_torch_tensor(edge_ids) if need_edge_output else None
-    wmb.check(wmb.lib().wholememory_ext_csr_random_walk(
-        row, col, wgt, ws.handle, steps, C.c_ulonglong(random_seed & 0xFFFFFFFFFFFFFFFF), ww.handle,
-        we.handle if we is not None else None, C.c_void_p(get_stream())))
-    return (walks, edge_ids) if need_edge_output else walks
+    _check_walk_arguments(start_nodes_tensor, walk_length)
+    return _walk(wmb.lib().wholememory_ext_csr_random_walk, wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor,
+                 wm_csr_weight_ptr_tensor, start_nodes_tensor, walk_length, (), random_seed, need_edge_output)
 
 
 def node2vec_walk(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, start_nodes_tensor: torch.Tensor, walk_length: int, p: float,
@@ -329,28 +343,13 @@ def node2vec_walk(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, start_nodes_tens
     1 / p when x is the previous node, by 1 when x is a neighbour of the previous node, and by 1 / q otherwise; p = q = 1 gives
     the walks of `random_walk` with the same weights. col_sorted=True promises that every row of csr_col_ptr is ascending,
     and the neighbour test becomes a binary search instead of a scan of the previous node's row."""
-    if int(walk_length) < 1:
-        raise ValueError("walk_length must be at least 1, got %r" % (walk_length,))
-    if start_nodes_tensor.dim() != 1:
-        raise ValueError("start_nodes_tensor must be 1-D, got %d dimensions" % start_nodes_tensor.dim())
+    _check_walk_arguments(start_nodes_tensor, walk_length)
     for name, value in (("p", p), ("q", q)):
         if not (math.isfinite(float(value)) and float(value) > 0):
             raise ValueError("%s must be finite and positive, got %r" % (name, value))
-    row, col = _handle(wm_csr_row_ptr_tensor), _handle(wm_csr_col_ptr_tensor)
-    wgt = None if wm_csr_weight_ptr_tensor is None else _handle(wm_csr_weight_ptr_tensor)
-    if random_seed is None:
-        random_seed = random.getrandbits(64)
-    n, steps = start_nodes_tensor.shape[0], int(walk_length)
-    col_dtype = wholememory_dtype_to_torch_dtype(wmb.lib().wholememory_tensor_get_tensor_description(col).contents.dtype)
-    walks = torch.empty((n, steps + 1), device=op_device(), dtype=col_dtype)
-    edge_ids = torch.empty((n, steps), device=op_device(), dtype=torch.int64) if need_edge_output else None
-    ws, ww = wrap_torch_tensor(start_nodes_tensor), wrap_torch_tensor(walks)
-    we = wrap_torch_tensor(edge_ids) if need_edge_output else None
-    wmb.check(wmb.lib().wholememory_ext_csr_node2vec_walk(
-        row, col, wgt, ws.handle, steps, C.c_float(float(p)), C.c_float(float(q)), 1 if col_sorted else 0,
-        C.c_ulonglong(random_seed & 0xFFFFFFFFFFFFFFFF), ww.handle, we.handle if we is not None else None,
-        C.c_void_p(get_stream())))
-    return (walks, edge_ids) if need_edge_output else walks
+    step_rule = (C.c_float(float(p)), C.c_float(float(q)), 1 if col_sorted else 0)
+    return _walk(wmb.lib().wholememory_ext_csr_node2vec_walk, wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor,
+                 wm_csr_weight_ptr_tensor, start_nodes_tensor, walk_length, step_rule, random_seed, need_edge_output)
 
 
 NEGATIVE_MODES = {"uniform": 0, "degree": 1}
@@ -374,15 +373,12 @@ def negative_sample(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, src_nodes_tens
     if src_nodes_tensor.dim() != 1:
         raise ValueError("src_nodes_tensor must be 1-D, got %d dimensions" % src_nodes_tensor.dim())
     row, col = _handle(wm_csr_row_ptr_tensor), _handle(wm_csr_col_ptr_tensor)
-    if random_seed is None:
-        random_seed = random.getrandbits(64)
     n, k = src_nodes_tensor.shape[0], int(num_negatives)
-    col_dtype = wholememory_dtype_to_torch_dtype(wmb.lib().wholememory_tensor_get_tensor_description(col).contents.dtype)
-    negatives = torch.empty((n, k), device=op_device(), dtype=col_dtype)
+    negatives = torch.empty((n, k), device=op_device(), dtype=_col_dtype(col))
     ws, wn = wrap_torch_tensor(src_nodes_tensor), wrap_torch_tensor(negatives)
     wmb.check(wmb.lib().wholememory_ext_csr_negative_sample(
         row, col, ws.handle, k, NEGATIVE_MODES[mode], (1 if exclude_edges else 0) | (2 if exclude_self else 0), int(max_tries),
-        1 if col_sorted else 0, C.c_ulonglong(random_seed & 0xFFFFFFFFFFFFFFFF), wn.handle, C.c_void_p(get_stream())))
+        1 if col_sorted else 0, _seed64(random_seed), wn.handle, C.c_void_p(get_stream())))
     return negatives
 
 

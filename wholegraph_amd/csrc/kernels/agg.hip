@@ -5,7 +5,9 @@
 //                  term, times r(d) = fl(1 / deg(d)) for "mean"; +0.0 for a target without neighbours
 //   out[d, F:2F] = x[d]
 // The group loads the column ids of up to LANES edges with one coalesced load and hands them out with shuffles; the
-// neighbour rows of a batch of kAggBatch edges are then loaded back to back (16-byte pieces when the rows allow it).
+// neighbour rows of a batch of kAggBatch edges are then loaded back to back (16-byte pieces when the rows allow it). That
+// walk is agg_common.cuh's (for_target_pieces, for_edge_batches), as in every per-target kernel of the block ops; the
+// kernel says what a lane fetches, what a slot loads and what it adds.
 //
 // Backward (grad_x[s] for every source row s; no atomics, one fixed order of every sum):
 //   1 the existing id sort (dedup_ids, called by the host) sorts col_ind: runs of equal sources, positions ascending
@@ -19,7 +21,8 @@
 // run_of[] is not initialised: a value is used only when 0 <= u < n_unique and unique[u] == s (a sparse-set check).
 // Steps 1 and 2 do not depend on the op: agg_bwd_prepare (below) is shared with kernels/agg_half.hip, agg_weighted.hip and
 // agg_rel.hip. The walk of steps 3 and 4 (tiles, the run of a source, the partials in chunk order, the self term) is
-// agg_common.cuh's, shared with those files and with the attention ops; fold_edges, the per-edge term, is this op's own.
+// agg_common.cuh's, shared with those files and with the attention ops; fold_edges, the per-edge term, is this op's own
+// (its loop over the sorted positions is written out: agg_common.cuh's header has the reason).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -35,44 +38,29 @@ namespace {
 template <int VEC, int LANES>
 __global__ __launch_bounds__(kAggBlock) void agg_forward_kernel(wm_agg_args p)
 {
-  constexpr int kGroups = kAggBlock / LANES;
-  const int gl          = threadIdx.x % LANES;
-  const int64_t F       = p.dim;
-  for (int64_t d = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; d < p.n_dst;
-       d += static_cast<int64_t>(gridDim.x) * kGroups) {
-    int64_t e0, e1;
-    edge_range(p.row_ptr, d, p.n_edges, e0, e1);
+  const int gl    = threadIdx.x % LANES;
+  const int64_t F = p.dim;
+  for_target_pieces<VEC, LANES>(p, F, [&](int64_t d, int64_t e0, int64_t e1, int64_t c, int64_t cl, bool act) {
     const int64_t deg = e1 - e0;
     const float r     = deg > 0 ? 1.0f / static_cast<float>(deg) : 0.0f;
     const float* self = p.in + d * p.in_stride;
     float* orow       = p.out + d * p.out_stride;
-    for (int64_t cb = 0; cb < F; cb += LANES * VEC) {   // (group-uniform trip count: the shuffles below stay in step)
-      const int64_t c  = cb + gl * VEC;
-      const bool act   = c < F;
-      const int64_t cl = act ? c : 0;
-      fvec<VEC> acc    = splat<VEC>(-0.0f);
-      for (int64_t eb = e0; eb < e1; eb += LANES) {
-        const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
-        const int my = gl < nb ? p.col_ind[eb + gl] : 0;
-        for (int j = 0; j < nb; j += kAggBatch) {
-          fvec<VEC> v[kAggBatch];
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k) {
-            const int src = __shfl(my, j + k < nb ? j + k : nb - 1, LANES);
-            v[k]          = ldv<VEC>(p.in + static_cast<int64_t>(src) * p.in_stride + cl);
-          }
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k)
-            if (j + k < nb) add_to(acc, v[k]);
-        }
-      }
-      if (act) {
-        const fvec<VEC> a = deg == 0 ? splat<VEC>(0.0f) : (p.mean ? scaled(acc, r) : acc);
-        stv(orow + c, a);
-        stv(orow + F + c, ldv<VEC>(self + c));
-      }
+    fvec<VEC> acc     = splat<VEC>(-0.0f);
+    int my            = 0;
+    fvec<VEC> v[kAggBatch];
+    for_edge_batches<LANES>(
+        e0, e1, gl, [&](int64_t e, bool in) { my = in ? p.col_ind[e] : 0; },
+        [&](int k, int from, int64_t) {
+          const int src = __shfl(my, from, LANES);
+          v[k]          = ldv<VEC>(p.in + static_cast<int64_t>(src) * p.in_stride + cl);
+        },
+        [&](int k, int64_t) { add_to(acc, v[k]); });
+    if (act) {
+      const fvec<VEC> a = deg == 0 ? splat<VEC>(0.0f) : (p.mean ? scaled(acc, r) : acc);
+      stv(orow + c, a);
+      stv(orow + F + c, ldv<VEC>(self + c));
     }
-  }
+  });
 }
 
 // acc += t(e) for the edges at sorted positions [eb0, ee), in that order (LANES lanes, this lane's columns at cl)
@@ -80,7 +68,7 @@ template <int VEC, int LANES>
 __device__ __forceinline__ void fold_edges(fvec<VEC>& acc, const wm_agg_args& p, const int32_t* sorted_dst, int64_t eb0,
                                            int64_t ee, int64_t cl, int gl)
 {
-  for (int64_t eb = eb0; eb < ee; eb += LANES) {
+  for (int64_t eb = eb0; eb < ee; eb += LANES) {   // (written out: on for_edge_batches agg_bwd_fold_kernel measured slower)
     const int nb = static_cast<int>(ee - eb < LANES ? ee - eb : LANES);
     int my_d     = 0;
     float my_r   = 1.0f;

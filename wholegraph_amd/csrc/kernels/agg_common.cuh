@@ -1,10 +1,31 @@
 // wholegraph_amd — device and launch helpers shared by the ops of a sampled CSC block (kernels/agg.hip, agg_half.hip,
 // agg_weighted.hip, agg_rel.hip, agg_gather.hip, agg_quant.hip and pna.hip, the `agg_concat` family; kernels/gat.hip,
-// gat_edge.hip, gatv2.hip and tconv.hip, the attention ops), whose args all begin with the wm_csc_block of backend.hpp:
-// fp32 pieces of a row, the clamped edge range of a target, the launch shape, and the walk of the deterministic per-source
-// backward over the host's wm_edge_index: its index (csc_bwd_index), the run of a source (run_of_source), the partial rows
-// of a run's later chunks (add_partials), the tile loop of a chunk kernel (for_chunk_pieces) and the self term of the
-// agg_concat ops (with_self_term). What an op adds per edge, its fold_edges*, stays in the op's own file.
+// gat_edge.hip, gatv2.hip and tconv.hip, the attention ops; kernels/edot.hip), whose args all begin with the wm_csc_block of
+// backend.hpp:
+// fp32 pieces of a row, the clamped edge range of a target, the launch shape, and the two walks every op is built from.
+//   * The per-target walk of every forward and every per-target backward: a lane group per target and its column pieces
+//     (for_target_pieces), and within it the walk over a range of positions, LANES at a time, the rows of kAggBatch of them
+//     loaded back to back (for_edge_batches). for_edge_batches alone decides which positions a lane may fetch, which lane a
+//     slot reads from and which slots are used; the fold_*_edges of the per-source walk run on it too (all but three, below).
+//   * The walk of the deterministic per-source backward over the host's wm_edge_index: its index (csc_bwd_index), the run of
+//     a source (run_of_source), the partial rows of a run's later chunks (add_partials), the tile loop of a chunk kernel
+//     (for_chunk_pieces) and the self term of the agg_concat ops (with_self_term).
+// What stays in the op's own file: what a lane fetches for its position, the loads of a slot and what a slot adds (the three
+// callables of for_edge_batches, in the kernels and in fold_edges*), and everything per target around them.
+// Loops over LANES positions that are written out where they stand, and why:
+//   * pna.hip, pna_fold_edges: a batch loads up to nine rows per edge, one loop over the batch per aggregator part, so that
+//     the branch on the mask stays outside the row loads; with the loads of a slot in one callable the chunk kernel kept 3
+//     row loads in flight instead of 12. Its batch is kPnaBwdBatch.
+//   * agg.hip, fold_edges, and agg_rel.hip, fold_edges_rel: the same loads and arithmetic, but hipcc schedules and allocates
+//     the fold kernels differently on the helper (relagg_fold_bwd_kernel<4, *> 91 -> 97 VGPRs), and they measured slower in
+//     every run against the parent: agg_bwd_fold_kernel by 2 to 7 %, the agg_concat_rel backward by 7 to 9 %
+//     (profiles/target_walk_refactor_bench.json). Written out, both kernels are the parent's instruction for instruction.
+//   * agg_rel.hip, relagg_fwd_kernel with more than LANES edges, two loops: the count of a relation's edges (one ballot per
+//     LANES positions, no row loads) and the walk of a batch's matching lanes, whose slots are filled in ballot order, not
+//     from consecutive positions.
+// (aggw_bwd_weight_kernel of agg_weighted.hip is no such walk: a group takes kAggBatch edges, shuffles once and then walks
+// column blocks.) Frames that stay with their kernel: aggg_forward_kernel and aggq_forward_kernel resolve the target's own
+// table row once per target, ahead of the column loop; edot_fwd_kernel has no column loop; relagg_fwd_kernel runs rounds.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -241,6 +262,58 @@ __device__ __forceinline__ void for_chunk_pieces(const csc_bwd_index& b, int64_t
       const bool act   = c < width;
       const int64_t cl = act ? c : 0;
       body(t, cs, ce, c, cl, act);
+    }
+  }
+}
+
+// the walk of a per-target kernel, the twin of for_chunk_pieces: a group of LANES lanes per target d of the block (anything
+// with row_ptr, n_dst and n_edges); with its clamped edge range [e0, e1), body(d, e0, e1, c, cl, act) once per piece of
+// `width` columns of this lane. The trip count of the column loop is the same in every lane of the group, so the shuffles of
+// an edge walk inside the body stay in step.
+template <int VEC, int LANES, class Block, class Body>
+__device__ __forceinline__ void for_target_pieces(const Block& blk, int64_t width, Body body)
+{
+  constexpr int kGroups = kAggBlock / LANES;
+  const int gl          = threadIdx.x % LANES;
+  for (int64_t d = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; d < blk.n_dst;
+       d += static_cast<int64_t>(gridDim.x) * kGroups) {
+    int64_t e0, e1;
+    edge_range(blk.row_ptr, d, blk.n_edges, e0, e1);
+    for (int64_t cb = 0; cb < width; cb += LANES * VEC) {
+      const int64_t c  = cb + gl * VEC;
+      const bool act   = c < width;
+      const int64_t cl = act ? c : 0;
+      body(d, e0, e1, c, cl, act);
+    }
+  }
+}
+
+// the walk of a group of LANES lanes (this one is lane gl) over the positions [begin, end): a target's edges, or sorted
+// positions of the per-source backward. LANES positions at a time:
+//   lane_fetch(pos, in_range)  once per lane: what this lane holds of its own position pos = eb + gl for the others to
+//                              fetch with __shfl(..., from, LANES). Only with in_range is pos inside [begin, end): without
+//                              it the op loads nothing and keeps a harmless default.
+//   load_slot(k, from, pos)    for the slots k = 0 .. kAggBatch-1 back to back: the loads of position pos, which lane
+//                              `from` holds. A ragged last batch names its last position again, never one past it.
+//   use_slot(k, pos)           for the slots that hold a position of their own, in position order.
+// No bound of an array enters anywhere else: an op's loads are inside its arrays when lane_fetch honours in_range and
+// load_slot forms its addresses from `pos` and from what it shuffles.
+template <int LANES, class Fetch, class Load, class Use>
+__device__ __forceinline__ void for_edge_batches(int64_t begin, int64_t end, int gl, Fetch lane_fetch, Load load_slot,
+                                                 Use use_slot)
+{
+  for (int64_t eb = begin; eb < end; eb += LANES) {
+    const int nb = static_cast<int>(end - eb < LANES ? end - eb : LANES);
+    lane_fetch(eb + gl, gl < nb);
+    for (int j = 0; j < nb; j += kAggBatch) {
+#pragma unroll
+      for (int k = 0; k < kAggBatch; ++k) {
+        const int from = j + k < nb ? j + k : nb - 1;
+        load_slot(k, from, eb + from);
+      }
+#pragma unroll
+      for (int k = 0; k < kAggBatch; ++k)
+        if (j + k < nb) use_slot(k, eb + j + k);
     }
   }
 }

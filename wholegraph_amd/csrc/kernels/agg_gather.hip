@@ -9,7 +9,8 @@
 // Same structure as agg_forward_kernel / agg16_forward_kernel: one group of 16 / 32 / 64 lanes per target, sized from the
 // row's 16-byte pieces (or, on the element-wise path, its elements); the column ids of up to LANES edges loaded with one
 // coalesced load; the rows of a batch of kAggBatch edges issued back to back as raw pieces and widened when they are added,
-// in edge order, into fp32 accumulators that are stored once. What is new is the address chain in front of the row loads,
+// in edge order, into fp32 accumulators that are stored once (for_edge_batches of agg_common.cuh; the frame around it stays
+// here, because the target's own row is resolved once per target). What is new is the address chain in front of the row loads,
 // taken from kernels/rows.hip, where each lane resolves its own row: lane k loads node_ids[col_ind[eb + k]] and resolves
 // that row's address in the table (continuous base; chunked: owner by multiply-high when every rank holds the same amount,
 // else the search over the rank offsets), and the group then fetches each 64-bit address with two shuffles. The id lookup
@@ -173,6 +174,7 @@ __global__ __launch_bounds__(kAggBlock) void aggg_forward_kernel(aggg_params p)
   const int gl          = threadIdx.x % LANES;
   const int64_t F       = p.dim;
   const int64_t last    = p.n_src - 1;
+  // (its own frame, not for_target_pieces: the resolve of the target's own row is a chain of loads, done once per target)
   for (int64_t d = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; d < p.n_dst;
        d += static_cast<int64_t>(gridDim.x) * kGroups) {
     int64_t e0, e1;
@@ -186,26 +188,20 @@ __global__ __launch_bounds__(kAggBlock) void aggg_forward_kernel(aggg_params p)
       const bool act    = c < F;
       const uint64_t cl = static_cast<uint64_t>(act ? c : 0) * kElt;
       fvec<VEC> acc     = splat<VEC>(-0.0f);
-      for (int64_t eb = e0; eb < e1; eb += LANES) {
-        const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
-        uint64_t my  = 0;
-        if (gl < nb) {
-          int64_t src = p.col_ind[eb + gl];
-          src         = src < 0 ? 0 : (src > last ? last : src);   // (as the ids: no load outside node_ids)
-          my          = row_address(p, src);
-        }
-        for (int j = 0; j < nb; j += kAggBatch) {
-          graw<VEC> v[kAggBatch];
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k) {
-            const uint64_t row = shfl_address<LANES>(my, j + k < nb ? j + k : nb - 1);
-            v[k]               = ldrow<T, VEC>(row + cl);
-          }
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k)
-            if (j + k < nb) add_to(acc, widened_row<T, VEC>(v[k]));
-        }
-      }
+      uint64_t my       = 0;
+      graw<VEC> v[kAggBatch];
+      for_edge_batches<LANES>(
+          e0, e1, gl,
+          [&](int64_t e, bool in) {
+            my = 0;
+            if (in) {
+              int64_t src = p.col_ind[e];
+              src         = src < 0 ? 0 : (src > last ? last : src);   // (as the ids: no load outside node_ids)
+              my          = row_address(p, src);
+            }
+          },
+          [&](int k, int from, int64_t) { v[k] = ldrow<T, VEC>(shfl_address<LANES>(my, from) + cl); },
+          [&](int k, int64_t) { add_to(acc, widened_row<T, VEC>(v[k])); });
       if (act) {
         const fvec<VEC> a = deg == 0 ? splat<VEC>(0.0f) : (p.mean ? scaled(acc, r) : acc);
         stout(orow + c, a);

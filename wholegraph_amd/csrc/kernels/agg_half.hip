@@ -8,9 +8,10 @@
 // Same structure as the fp32 kernels: one group of 16 / 32 / 64 lanes per row, sized from the row's 16-byte pieces (a
 // piece is 8 elements here: F = 128 is 16 pieces) or, on the element-wise path, from its elements; column ids loaded
 // coalesced and handed out with shuffles; the rows of a batch of kAggBatch edges issued back to back as raw pieces and
-// widened when they are added. The edge index, agg_bwd_prep_kernel and the fp32 partial rows of chunks are those of
-// kernels/agg.hip (agg_bwd_prepare); the walk over them is agg_common.cuh's. The self term stays here: the result is
-// narrowed once, and a self term without edges keeps its bits.
+// widened when they are added (the walk of agg_common.cuh: for_target_pieces, for_edge_batches). The edge index,
+// agg_bwd_prep_kernel and the fp32 partial rows of chunks are those of kernels/agg.hip (agg_bwd_prepare); the walk over
+// them is agg_common.cuh's. The self term stays here: the result is narrowed once, and a self term without edges keeps its
+// bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -138,45 +139,30 @@ __device__ __forceinline__ void stp(float* p, const fvec<VEC>& a)
 template <class T, int VEC, int LANES>
 __global__ __launch_bounds__(kAggBlock) void agg16_forward_kernel(wm_agg16_args p)
 {
-  constexpr int kGroups = kAggBlock / LANES;
-  const int gl          = threadIdx.x % LANES;
-  const int64_t F       = p.dim;
-  const uint16_t* in    = static_cast<const uint16_t*>(p.in);
-  uint16_t* out         = static_cast<uint16_t*>(p.out);
-  for (int64_t d = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; d < p.n_dst;
-       d += static_cast<int64_t>(gridDim.x) * kGroups) {
-    int64_t e0, e1;
-    edge_range(p.row_ptr, d, p.n_edges, e0, e1);
+  const int gl       = threadIdx.x % LANES;
+  const int64_t F    = p.dim;
+  const uint16_t* in = static_cast<const uint16_t*>(p.in);
+  uint16_t* out      = static_cast<uint16_t*>(p.out);
+  for_target_pieces<VEC, LANES>(p, F, [&](int64_t d, int64_t e0, int64_t e1, int64_t c, int64_t cl, bool act) {
     const int64_t deg    = e1 - e0;
     const float r        = deg > 0 ? 1.0f / static_cast<float>(deg) : 0.0f;
     const uint16_t* self = in + d * p.in_stride;
     uint16_t* orow       = out + d * p.out_stride;
-    for (int64_t cb = 0; cb < F; cb += LANES * VEC) {   // (group-uniform trip count: the shuffles below stay in step)
-      const int64_t c  = cb + gl * VEC;
-      const bool act   = c < F;
-      const int64_t cl = act ? c : 0;
-      fvec<VEC> acc    = splat<VEC>(-0.0f);
-      for (int64_t eb = e0; eb < e1; eb += LANES) {
-        const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
-        const int my = gl < nb ? p.col_ind[eb + gl] : 0;
-        for (int j = 0; j < nb; j += kAggBatch) {
-          hraw<VEC> v[kAggBatch];
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k) {
-            const int src = __shfl(my, j + k < nb ? j + k : nb - 1, LANES);
-            v[k]          = ldh<VEC>(in + static_cast<int64_t>(src) * p.in_stride + cl);
-          }
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k)
-            if (j + k < nb) add_to(acc, widened<T, VEC>(v[k]));
-        }
-      }
-      if (act) {
-        sth(orow + c, deg == 0 ? zero_raw<VEC>() : narrowed<T, VEC>(p.mean ? scaled(acc, r) : acc));
-        sth(orow + F + c, ldh<VEC>(self + c));
-      }
+    fvec<VEC> acc        = splat<VEC>(-0.0f);
+    int my               = 0;
+    hraw<VEC> v[kAggBatch];
+    for_edge_batches<LANES>(
+        e0, e1, gl, [&](int64_t e, bool in_range) { my = in_range ? p.col_ind[e] : 0; },
+        [&](int k, int from, int64_t) {
+          const int src = __shfl(my, from, LANES);
+          v[k]          = ldh<VEC>(in + static_cast<int64_t>(src) * p.in_stride + cl);
+        },
+        [&](int k, int64_t) { add_to(acc, widened<T, VEC>(v[k])); });
+    if (act) {
+      sth(orow + c, deg == 0 ? zero_raw<VEC>() : narrowed<T, VEC>(p.mean ? scaled(acc, r) : acc));
+      sth(orow + F + c, ldh<VEC>(self + c));
     }
-  }
+  });
 }
 
 // acc += t(e) for the edges at sorted positions [eb0, ee), in that order (LANES lanes, this lane's columns at cl)
@@ -185,29 +171,25 @@ __device__ __forceinline__ void fold_edges16(fvec<VEC>& acc, const wm_agg16_args
                                              int64_t ee, int64_t cl, int gl)
 {
   const uint16_t* grad = static_cast<const uint16_t*>(p.grad);
-  for (int64_t eb = eb0; eb < ee; eb += LANES) {
-    const int nb = static_cast<int>(ee - eb < LANES ? ee - eb : LANES);
-    int my_d     = 0;
-    float my_r   = 1.0f;
-    if (gl < nb) {
-      my_d = sorted_dst[eb + gl];
-      if (p.mean) my_r = 1.0f / static_cast<float>(p.row_ptr[my_d + 1] - p.row_ptr[my_d]);
-    }
-    for (int j = 0; j < nb; j += kAggBatch) {
-      hraw<VEC> v[kAggBatch];
-      float rs[kAggBatch];
-#pragma unroll
-      for (int k = 0; k < kAggBatch; ++k) {
-        const int from = j + k < nb ? j + k : nb - 1;
-        const int d    = __shfl(my_d, from, LANES);
-        rs[k]          = __shfl(my_r, from, LANES);
-        v[k]           = ldh<VEC>(grad + static_cast<int64_t>(d) * p.grad_stride + cl);
-      }
-#pragma unroll
-      for (int k = 0; k < kAggBatch; ++k)
-        if (j + k < nb) add_to(acc, p.mean ? scaled(widened<T, VEC>(v[k]), rs[k]) : widened<T, VEC>(v[k]));
-    }
-  }
+  int my_d   = 0;
+  float my_r = 1.0f;
+  hraw<VEC> v[kAggBatch];
+  float rs[kAggBatch];
+  for_edge_batches<LANES>(
+      eb0, ee, gl,
+      [&](int64_t i, bool in) {
+        my_d = 0, my_r = 1.0f;
+        if (in) {
+          my_d = sorted_dst[i];
+          if (p.mean) my_r = 1.0f / static_cast<float>(p.row_ptr[my_d + 1] - p.row_ptr[my_d]);
+        }
+      },
+      [&](int k, int from, int64_t) {
+        const int d = __shfl(my_d, from, LANES);
+        rs[k]       = __shfl(my_r, from, LANES);
+        v[k]        = ldh<VEC>(grad + static_cast<int64_t>(d) * p.grad_stride + cl);
+      },
+      [&](int k, int64_t) { add_to(acc, p.mean ? scaled(widened<T, VEC>(v[k]), rs[k]) : widened<T, VEC>(v[k])); });
 }
 
 template <class T, int VEC, int LANES>

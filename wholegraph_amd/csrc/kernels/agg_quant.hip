@@ -18,7 +18,8 @@
 // offsets; ids and column indices folded into range so that no load leaves the table) and the group fetches each 64-bit
 // address with two shuffles. The loads of a batch of kAggBatch edges — the lane's code dword, and scale and bias at the
 // group-uniform address row + Q, as kernels/qrows.hip loads them (DESIGN.md section 3.14 has the choice) — are issued back to
-// back as global loads; a batch shorter than kAggBatch repeats its last edge's loads and skips the add.
+// back as global loads; a batch shorter than kAggBatch repeats its last edge's loads and skips the add (for_edge_batches of
+// agg_common.cuh).
 //
 // Table rows are only 4-byte aligned by format (a 136-byte stride): dword loads are always legal, so there is no aligned /
 // unaligned split on the table side. VEC == 1, the element-wise instantiation (dim % 4 != 0, or an out whose rows are not
@@ -141,6 +142,7 @@ __global__ __launch_bounds__(kAggBlock) void aggq_forward_kernel(aggq_params p)
   const int64_t W       = p.words;
   const uint64_t q      = static_cast<uint64_t>(W) * 4;
   const int64_t last    = p.n_src - 1;
+  // (its own frame, not for_target_pieces: the resolve of the target's own row is a chain of loads, done once per target)
   for (int64_t d = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; d < p.n_dst;
        d += static_cast<int64_t>(gridDim.x) * kGroups) {
     int64_t e0, e1;
@@ -154,26 +156,20 @@ __global__ __launch_bounds__(kAggBlock) void aggq_forward_kernel(aggq_params p)
       const bool act    = c < W;
       const uint64_t cl = static_cast<uint64_t>(act ? c : 0) * 4;   // (a lane past the row's codes repeats dword 0)
       fvec<4> acc       = splat<4>(-0.0f);
-      for (int64_t eb = e0; eb < e1; eb += LANES) {
-        const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
-        uint64_t my  = 0;
-        if (gl < nb) {
-          int64_t src = p.col_ind[eb + gl];
-          src         = src < 0 ? 0 : (src > last ? last : src);   // (as the ids: no load outside node_ids)
-          my          = row_address(p, src);
-        }
-        for (int j = 0; j < nb; j += kAggBatch) {
-          qraw v[kAggBatch];
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k) {
-            const uint64_t row = shfl_address<LANES>(my, j + k < nb ? j + k : nb - 1);
-            v[k]               = ldrow(row, cl, q);
-          }
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k)
-            if (j + k < nb) add_to(acc, dequantized(v[k]));
-        }
-      }
+      uint64_t my       = 0;
+      qraw v[kAggBatch];
+      for_edge_batches<LANES>(
+          e0, e1, gl,
+          [&](int64_t e, bool in) {
+            my = 0;
+            if (in) {
+              int64_t src = p.col_ind[e];
+              src         = src < 0 ? 0 : (src > last ? last : src);   // (as the ids: no load outside node_ids)
+              my          = row_address(p, src);
+            }
+          },
+          [&](int k, int from, int64_t) { v[k] = ldrow(shfl_address<LANES>(my, from), cl, q); },
+          [&](int k, int64_t) { add_to(acc, dequantized(v[k])); });
       if (act) {
         const fvec<4> a    = deg == 0 ? splat<4>(0.0f) : (p.mean ? scaled(acc, r) : acc);
         const int64_t left = F - c * 4;   // columns of the row from this lane's first on (>= 1)

@@ -15,7 +15,8 @@
 //     without an edge are filled with +0.0 afterwards (one ballot per relation).
 //   * more than LANES edges: R rounds, one per relation r: the edges of type r are counted over the batches of LANES edge
 //     positions (ballot + popcount), then each batch's matching lanes are walked in position order, kAggBatch row loads
-//     back to back, and the slot is stored once.
+//     back to back, and the slot is stored once. Both loops go by ballots, not by consecutive positions, and are written
+//     out here (agg_common.cuh's header names them, and fold_edges_rel of the backward).
 // Backward (relagg_chunk_bwd_kernel / relagg_fold_bwd_kernel): the per-source sums of kernels/agg_weighted.hip over the same
 //   id sort, prep kernel and chunk tiles (agg_bwd_prepare) and with the walk of agg_common.cuh, with w := edge_scale (mean)
 //   and the grad_out column offset type * dim per edge (fold_edges_rel); an edge with a type out of range keeps its sorted
@@ -186,7 +187,7 @@ __device__ __forceinline__ bool fold_edges_rel(fvec<VEC>& acc, const wm_relagg_a
 {
   const int R = static_cast<int>(p.num_relations);
   bool any    = false;
-  for (int64_t eb = eb0; eb < ee; eb += LANES) {
+  for (int64_t eb = eb0; eb < ee; eb += LANES) {   // (written out: on for_edge_batches the fold kernel measured slower)
     const int nb = static_cast<int>(ee - eb < LANES ? ee - eb : LANES);
     int my_d     = 0;
     int my_t     = -1;   // the type, or -1 for one out of range

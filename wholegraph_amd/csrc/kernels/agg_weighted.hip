@@ -5,7 +5,8 @@
 //
 // Forward (aggw_forward_kernel, the structure of agg_forward_kernel): a group of LANES lanes per target row; the column ids
 //   and the weights of up to LANES edges are loaded coalesced and handed out with shuffles, the neighbour rows of a batch of
-//   kAggBatch edges are loaded back to back, then multiplied and added in edge order.
+//   kAggBatch edges are loaded back to back, then multiplied and added in edge order (the walk of agg_common.cuh:
+//   for_target_pieces, for_edge_batches; a lane fetches the column id and the weight of its position).
 // Backward into x (aggw_bwd_chunk_kernel / aggw_bwd_fold_kernel): the per-source sums of kernels/agg.hip over the same id
 //   sort, prep kernel and chunk tiles (agg_bwd_prepare) with the walk of agg_common.cuh; the term of sorted position j is
 //   w[order[j]] * t(order[j]) (fold_edges_w).
@@ -32,48 +33,32 @@ constexpr int kAggwStack = 20;   // levels of the block-sum stack: 2^20 blocks o
 template <int VEC, int LANES>
 __global__ __launch_bounds__(kAggBlock) void aggw_forward_kernel(wm_aggw_args p)
 {
-  constexpr int kGroups = kAggBlock / LANES;
-  const int gl          = threadIdx.x % LANES;
-  const int64_t F       = p.dim;
-  for (int64_t d = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; d < p.n_dst;
-       d += static_cast<int64_t>(gridDim.x) * kGroups) {
-    int64_t e0, e1;
-    edge_range(p.row_ptr, d, p.n_edges, e0, e1);
+  const int gl    = threadIdx.x % LANES;
+  const int64_t F = p.dim;
+  for_target_pieces<VEC, LANES>(p, F, [&](int64_t d, int64_t e0, int64_t e1, int64_t c, int64_t cl, bool act) {
     const int64_t deg = e1 - e0;
     const float r     = deg > 0 ? 1.0f / static_cast<float>(deg) : 0.0f;
     const float* self = p.in + d * p.in_stride;
     float* orow       = p.out + d * p.out_stride;
-    for (int64_t cb = 0; cb < F; cb += LANES * VEC) {   // (group-uniform trip count: the shuffles below stay in step)
-      const int64_t c  = cb + gl * VEC;
-      const bool act   = c < F;
-      const int64_t cl = act ? c : 0;
-      fvec<VEC> acc    = splat<VEC>(-0.0f);
-      for (int64_t eb = e0; eb < e1; eb += LANES) {
-        const int nb     = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
-        const int my     = gl < nb ? p.col_ind[eb + gl] : 0;
-        const float my_w = gl < nb ? p.w[eb + gl] : 0.0f;
-        for (int j = 0; j < nb; j += kAggBatch) {
-          fvec<VEC> v[kAggBatch];
-          float ws[kAggBatch];
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k) {
-            const int from = j + k < nb ? j + k : nb - 1;
-            const int src  = __shfl(my, from, LANES);
-            ws[k]          = __shfl(my_w, from, LANES);
-            v[k]           = ldv<VEC>(p.in + static_cast<int64_t>(src) * p.in_stride + cl);
-          }
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k)
-            if (j + k < nb) add_to(acc, scaled(v[k], ws[k]));
-        }
-      }
-      if (act) {
-        const fvec<VEC> a = deg == 0 ? splat<VEC>(0.0f) : (p.mean ? scaled(acc, r) : acc);
-        stv(orow + c, a);
-        stv(orow + F + c, ldv<VEC>(self + c));
-      }
+    fvec<VEC> acc     = splat<VEC>(-0.0f);
+    int my            = 0;
+    float my_w        = 0.0f;
+    fvec<VEC> v[kAggBatch];
+    float ws[kAggBatch];
+    for_edge_batches<LANES>(
+        e0, e1, gl, [&](int64_t e, bool in) { my = in ? p.col_ind[e] : 0, my_w = in ? p.w[e] : 0.0f; },
+        [&](int k, int from, int64_t) {
+          const int src = __shfl(my, from, LANES);
+          ws[k]         = __shfl(my_w, from, LANES);
+          v[k]          = ldv<VEC>(p.in + static_cast<int64_t>(src) * p.in_stride + cl);
+        },
+        [&](int k, int64_t) { add_to(acc, scaled(v[k], ws[k])); });
+    if (act) {
+      const fvec<VEC> a = deg == 0 ? splat<VEC>(0.0f) : (p.mean ? scaled(acc, r) : acc);
+      stv(orow + c, a);
+      stv(orow + F + c, ldv<VEC>(self + c));
     }
-  }
+  });
 }
 
 // acc += w[order[j]] * t(order[j]) for the sorted positions j in [eb0, ee), in that order (this lane's columns at cl)
@@ -81,32 +66,27 @@ template <int VEC, int LANES>
 __device__ __forceinline__ void fold_edges_w(fvec<VEC>& acc, const wm_aggw_args& p, const wm_agg_bwd_state& b, int64_t eb0,
                                              int64_t ee, int64_t cl, int gl)
 {
-  for (int64_t eb = eb0; eb < ee; eb += LANES) {
-    const int nb = static_cast<int>(ee - eb < LANES ? ee - eb : LANES);
-    int my_d     = 0;
-    float my_r   = 1.0f;
-    float my_w   = 0.0f;
-    if (gl < nb) {
-      my_d = b.sorted_dst[eb + gl];
-      my_w = p.w[b.order[eb + gl]];
-      if (p.mean) my_r = 1.0f / static_cast<float>(p.row_ptr[my_d + 1] - p.row_ptr[my_d]);
-    }
-    for (int j = 0; j < nb; j += kAggBatch) {
-      fvec<VEC> v[kAggBatch];
-      float rs[kAggBatch], ws[kAggBatch];
-#pragma unroll
-      for (int k = 0; k < kAggBatch; ++k) {
-        const int from = j + k < nb ? j + k : nb - 1;
-        const int d    = __shfl(my_d, from, LANES);
-        rs[k]          = __shfl(my_r, from, LANES);
-        ws[k]          = __shfl(my_w, from, LANES);
-        v[k]           = ldv<VEC>(p.grad + static_cast<int64_t>(d) * p.grad_stride + cl);
-      }
-#pragma unroll
-      for (int k = 0; k < kAggBatch; ++k)
-        if (j + k < nb) add_to(acc, scaled(p.mean ? scaled(v[k], rs[k]) : v[k], ws[k]));
-    }
-  }
+  int my_d   = 0;
+  float my_r = 1.0f, my_w = 0.0f;
+  fvec<VEC> v[kAggBatch];
+  float rs[kAggBatch], ws[kAggBatch];
+  for_edge_batches<LANES>(
+      eb0, ee, gl,
+      [&](int64_t i, bool in) {
+        my_d = 0, my_r = 1.0f, my_w = 0.0f;
+        if (in) {
+          my_d = b.sorted_dst[i];
+          my_w = p.w[b.order[i]];
+          if (p.mean) my_r = 1.0f / static_cast<float>(p.row_ptr[my_d + 1] - p.row_ptr[my_d]);
+        }
+      },
+      [&](int k, int from, int64_t) {
+        const int d = __shfl(my_d, from, LANES);
+        rs[k]       = __shfl(my_r, from, LANES);
+        ws[k]       = __shfl(my_w, from, LANES);
+        v[k]        = ldv<VEC>(p.grad + static_cast<int64_t>(d) * p.grad_stride + cl);
+      },
+      [&](int k, int64_t) { add_to(acc, scaled(p.mean ? scaled(v[k], rs[k]) : v[k], ws[k])); });
 }
 
 template <int VEC, int LANES>

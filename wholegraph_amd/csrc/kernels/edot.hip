@@ -7,7 +7,8 @@
 // gat_common.cuh that give the same bits:
 //   * VEC = 4 (F a power of two in [4, 256], both rows 16-byte aligned): a lane owns 4 adjacent columns, the target's piece
 //     of x_dst stays in registers over the edge loop, the source rows are loaded a batch of kAggBatch back to back, the F / 4
-//     lanes of the row combine with xor exchanges (head_tree) and the lane at column 0 stores score[e];
+//     lanes of the row combine with xor exchanges (head_tree) and the lane at column 0 stores score[e] (for_edge_batches of
+//     agg_common.cuh; the kernel keeps its frame, which has no column loop);
 //   * VEC = 1, everything else: a lane of the group takes every LANES-th edge of the target and pushes the Fp products
 //     through pair_tree, as tconv_dot_kernel does per (target, head).
 //
@@ -41,28 +42,21 @@ __global__ __launch_bounds__(kAggBlock) void edot_fwd_kernel(wm_edot_args p)
       const int lh      = static_cast<int>(F / 4);
       const int64_t cl  = gl < lh ? gl * 4 : 0;
       const fvec<4> xd  = ldv<4>(p.x_dst + d * p.x_dst_stride + cl);
-      for (int64_t eb = e0; eb < e1; eb += LANES) {
-        const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
-        const int my = gl < nb ? p.col_ind[eb + gl] : 0;
-        for (int j = 0; j < nb; j += kAggBatch) {
-          fvec<4> v[kAggBatch];
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k) {
-            const int src = __shfl(my, j + k < nb ? j + k : nb - 1, LANES);
+      int my            = 0;
+      fvec<4> v[kAggBatch];
+      for_edge_batches<LANES>(
+          e0, e1, gl, [&](int64_t e, bool in) { my = in ? p.col_ind[e] : 0; },
+          [&](int k, int from, int64_t) {
+            const int src = __shfl(my, from, LANES);
             v[k]          = ldv<4>(p.x_src + static_cast<int64_t>(src) * p.x_src_stride + cl);
-          }
+          },
+          [&](int k, int64_t e) {
+            fvec<4> q;
 #pragma unroll
-          for (int k = 0; k < kAggBatch; ++k) {
-            if (j + k < nb) {
-              fvec<4> q;
-#pragma unroll
-              for (int t = 0; t < 4; ++t) q.v[t] = xd.v[t] * v[k].v[t];
-              const float s = head_tree<LANES>(q, lh);
-              if (gl == 0) p.score[eb + j + k] = s;
-            }
-          }
-        }
-      }
+            for (int t = 0; t < 4; ++t) q.v[t] = xd.v[t] * v[k].v[t];
+            const float s = head_tree<LANES>(q, lh);
+            if (gl == 0) p.score[e] = s;
+          });
     } else {
       const uint32_t Fp = pow2_at_least(F);
       const float* y    = p.x_dst + d * p.x_dst_stride;
@@ -80,41 +74,27 @@ __global__ __launch_bounds__(kAggBlock) void edot_fwd_kernel(wm_edot_args p)
 template <int VEC, int LANES>
 __global__ __launch_bounds__(kAggBlock) void edot_bwd_dst_kernel(wm_edot_args p)
 {
-  constexpr int kGroups = kAggBlock / LANES;
-  const int gl          = threadIdx.x % LANES;
-  const int64_t F       = p.dim;
-  for (int64_t d = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; d < p.n_dst;
-       d += static_cast<int64_t>(gridDim.x) * kGroups) {
-    int64_t e0, e1;
-    edge_range(p.row_ptr, d, p.n_edges, e0, e1);
-    for (int64_t cb = 0; cb < F; cb += LANES * VEC) {   // (group-uniform trip count: the shuffles below stay in step)
-      const int64_t c  = cb + gl * VEC;
-      const bool act   = c < F;
-      const int64_t cl = act ? c : 0;
-      fvec<VEC> acc    = splat<VEC>(-0.0f);
-      for (int64_t eb = e0; eb < e1; eb += LANES) {
-        const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
-        int my       = 0;
-        float my_g   = 0.0f;
-        if (gl < nb) my = p.col_ind[eb + gl], my_g = p.grad[eb + gl];
-        for (int j = 0; j < nb; j += kAggBatch) {
-          fvec<VEC> v[kAggBatch];
-          float g[kAggBatch];
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k) {
-            const int from = j + k < nb ? j + k : nb - 1;
-            const int src  = __shfl(my, from, LANES);
-            g[k]           = __shfl(my_g, from, LANES);
-            v[k]           = ldv<VEC>(p.x_src + static_cast<int64_t>(src) * p.x_src_stride + cl);
-          }
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k)
-            if (j + k < nb) add_to(acc, scaled(v[k], g[k]));
-        }
-      }
-      if (act) stv(p.grad_dst + d * p.grad_dst_stride + c, e1 > e0 ? acc : splat<VEC>(0.0f));
-    }
-  }
+  const int gl = threadIdx.x % LANES;
+  for_target_pieces<VEC, LANES>(p, p.dim, [&](int64_t d, int64_t e0, int64_t e1, int64_t c, int64_t cl, bool act) {
+    fvec<VEC> acc = splat<VEC>(-0.0f);
+    int my        = 0;
+    float my_g    = 0.0f;
+    fvec<VEC> v[kAggBatch];
+    float g[kAggBatch];
+    for_edge_batches<LANES>(
+        e0, e1, gl,
+        [&](int64_t e, bool in) {
+          my = 0, my_g = 0.0f;
+          if (in) my = p.col_ind[e], my_g = p.grad[e];
+        },
+        [&](int k, int from, int64_t) {
+          const int src = __shfl(my, from, LANES);
+          g[k]          = __shfl(my_g, from, LANES);
+          v[k]          = ldv<VEC>(p.x_src + static_cast<int64_t>(src) * p.x_src_stride + cl);
+        },
+        [&](int k, int64_t) { add_to(acc, scaled(v[k], g[k])); });
+    if (act) stv(p.grad_dst + d * p.grad_dst_stride + c, e1 > e0 ? acc : splat<VEC>(0.0f));
+  });
 }
 
 // acc += g[order[i]] * x_dst[sorted_dst[i]] for the sorted positions i in [eb0, ee), in that order (this lane's columns at cl)
@@ -122,26 +102,22 @@ template <int VEC, int LANES>
 __device__ __forceinline__ void fold_edot_edges(fvec<VEC>& acc, const wm_edot_args& p, const csc_bwd_index& b, int64_t eb0,
                                                 int64_t ee, int64_t cl, int gl)
 {
-  for (int64_t eb = eb0; eb < ee; eb += LANES) {
-    const int nb = static_cast<int>(ee - eb < LANES ? ee - eb : LANES);
-    int my_d     = 0;
-    float my_g   = 0.0f;
-    if (gl < nb) my_d = b.sorted_dst[eb + gl], my_g = p.grad[b.order[eb + gl]];
-    for (int j = 0; j < nb; j += kAggBatch) {
-      fvec<VEC> v[kAggBatch];
-      float g[kAggBatch];
-#pragma unroll
-      for (int k = 0; k < kAggBatch; ++k) {
-        const int from = j + k < nb ? j + k : nb - 1;
-        const int dst  = __shfl(my_d, from, LANES);
-        g[k]           = __shfl(my_g, from, LANES);
-        v[k]           = ldv<VEC>(p.x_dst + static_cast<int64_t>(dst) * p.x_dst_stride + cl);
-      }
-#pragma unroll
-      for (int k = 0; k < kAggBatch; ++k)
-        if (j + k < nb) add_to(acc, scaled(v[k], g[k]));
-    }
-  }
+  int my_d   = 0;
+  float my_g = 0.0f;
+  fvec<VEC> v[kAggBatch];
+  float g[kAggBatch];
+  for_edge_batches<LANES>(
+      eb0, ee, gl,
+      [&](int64_t i, bool in) {
+        my_d = 0, my_g = 0.0f;
+        if (in) my_d = b.sorted_dst[i], my_g = p.grad[b.order[i]];
+      },
+      [&](int k, int from, int64_t) {
+        const int dst = __shfl(my_d, from, LANES);
+        g[k]          = __shfl(my_g, from, LANES);
+        v[k]          = ldv<VEC>(p.x_dst + static_cast<int64_t>(dst) * p.x_dst_stride + cl);
+      },
+      [&](int k, int64_t) { add_to(acc, scaled(v[k], g[k])); });
 }
 
 template <int VEC, int LANES>

@@ -11,6 +11,7 @@
 //     for den = sum of expf(l - max) (left to right), then the pass over the neighbour rows, a batch of kAggBatch rows (and
 //     their s_src) loaded back to back, alpha = expf(l - max) / den recomputed per edge with the same operations (so every
 //     lane of head hk, and the alpha written out, hold the same bits). The lane at the head's first column writes alpha.
+//     All three passes are walks of agg_common.cuh (for_target_pieces around three for_edge_batches).
 //     With concat the group writes out; otherwise it writes the per-head rows to the workspace and gat_head_mean_kernel
 //     forms ((o_0 + o_1) + ...) * fl(1/H).
 //
@@ -100,31 +101,26 @@ __device__ __forceinline__ void fold_gat_edges(fvec<VEC>& acc, float& ds, const 
 {
   const int64_t H = p.heads;
   const float r   = 1.0f / static_cast<float>(H);
-  for (int64_t eb = eb0; eb < ee; eb += LANES) {
-    const int nb = static_cast<int>(ee - eb < LANES ? ee - eb : LANES);
-    int my_e = 0, my_d = 0;
-    if (gl < nb) my_e = b.ix.order[eb + gl], my_d = b.ix.sorted_dst[eb + gl];
-    for (int j = 0; j < nb; j += kAggBatch) {
-      fvec<VEC> v[kAggBatch];
-      float a[kAggBatch], z[kAggBatch];
-#pragma unroll
-      for (int k = 0; k < kAggBatch; ++k) {
-        const int from = j + k < nb ? j + k : nb - 1;
+  int my_e = 0, my_d = 0;
+  fvec<VEC> v[kAggBatch];
+  float a[kAggBatch], z[kAggBatch];
+  for_edge_batches<LANES>(
+      eb0, ee, gl,
+      [&](int64_t i, bool in) {
+        my_e = 0, my_d = 0;
+        if (in) my_e = b.ix.order[i], my_d = b.ix.sorted_dst[i];
+      },
+      [&](int k, int from, int64_t) {
         const int64_t e = __shfl(my_e, from, LANES);
         const int dst   = __shfl(my_d, from, LANES);
         v[k]            = ldv<VEC>(p.grad + static_cast<int64_t>(dst) * p.grad_stride + gcol);
         a[k]            = p.alpha[e * H + hk];
         z[k]            = b.dz[e * H + hk];
-      }
-#pragma unroll
-      for (int k = 0; k < kAggBatch; ++k) {
-        if (j + k < nb) {
-          add_to(acc, scaled(p.concat ? v[k] : scaled(v[k], r), a[k]));
-          ds = ds + z[k];
-        }
-      }
-    }
-  }
+      },
+      [&](int k, int64_t) {
+        add_to(acc, scaled(p.concat ? v[k] : scaled(v[k], r), a[k]));
+        ds = ds + z[k];
+      });
 }
 
 template <int VEC, int LANES>

@@ -38,83 +38,59 @@ namespace {
 
 __device__ __forceinline__ float leaky(float z, float slope) { return z > 0.0f ? z : slope * z; }
 
-// the softmax and the weighted sum of a target's neighbour rows (gat.hip, forward). EDGE: the logit is
-// (s_src[col[e]] + s_dst[d]) + edge_scores[e, hk], edge_scores loaded next to s_src in every batch
+// the softmax and the weighted sum of a target's neighbour rows (gat.hip, forward): three walks over the target's edges
+// (for_edge_batches), the max, den and the rows. EDGE: the logit is (s_src[col[e]] + s_dst[d]) + edge_scores[e, hk],
+// edge_scores loaded next to s_src in every batch
 template <int VEC, int LANES, bool EDGE>
 __device__ __forceinline__ void gat_fwd_body(const wm_gat_args& p, const float* edge_scores, float* o, int64_t o_stride)
 {
-  constexpr int kGroups = kAggBlock / LANES;
-  const int gl          = threadIdx.x % LANES;
+  const int gl    = threadIdx.x % LANES;
   const int64_t H = p.heads, F = p.dim, HF = H * F;
   const float* s_src = p.scores;
-  for (int64_t d = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; d < p.n_dst;
-       d += static_cast<int64_t>(gridDim.x) * kGroups) {
-    int64_t e0, e1;
-    edge_range(p.row_ptr, d, p.n_edges, e0, e1);
-    for (int64_t cb = 0; cb < HF; cb += LANES * VEC) {   // (group-uniform trip count: the shuffles below stay in step)
-      const int64_t c  = cb + gl * VEC;
-      const bool act   = c < HF;
-      const int64_t cl = act ? c : 0;
-      const int64_t hk = cl / F;   // (a piece never straddles two heads: VEC = 4 only when F % 4 == 0)
-      const bool writer = act && c == hk * F;
-      const float sd    = s_src[(p.n_src + d) * H + hk];
-      float m = -INFINITY, den = -0.0f;
-      for (int pass = 0; pass < 2; ++pass) {   // 0: the max of l, 1: den = sum of expf(l - max), left to right
-        for (int64_t eb = e0; eb < e1; eb += LANES) {
-          const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
-          const int my = gl < nb ? p.col_ind[eb + gl] : 0;
-          for (int j = 0; j < nb; j += kAggBatch) {
-            float s[kAggBatch], se[kAggBatch];
-#pragma unroll
-            for (int k = 0; k < kAggBatch; ++k) {
-              const int from = j + k < nb ? j + k : nb - 1;
-              const int src  = __shfl(my, from, LANES);
-              s[k]           = s_src[static_cast<int64_t>(src) * H + hk];
-              if constexpr (EDGE) se[k] = edge_scores[(eb + from) * H + hk];
-            }
-#pragma unroll
-            for (int k = 0; k < kAggBatch; ++k) {
-              if (j + k < nb) {
-                float z = s[k] + sd;
-                if constexpr (EDGE) z = z + se[k];
-                const float l = leaky(z, p.slope);
-                if (pass == 0) m = fmaxf(m, l);
-                else den = den + expf(l - m);
-              }
-            }
-          }
-        }
-      }
-      fvec<VEC> acc = splat<VEC>(-0.0f);
-      for (int64_t eb = e0; eb < e1; eb += LANES) {
-        const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
-        const int my = gl < nb ? p.col_ind[eb + gl] : 0;
-        for (int j = 0; j < nb; j += kAggBatch) {
-          fvec<VEC> v[kAggBatch];
-          float s[kAggBatch], se[kAggBatch];
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k) {
-            const int from = j + k < nb ? j + k : nb - 1;
-            const int src  = __shfl(my, from, LANES);
-            v[k]           = ldv<VEC>(p.h + static_cast<int64_t>(src) * p.h_stride + cl);
-            s[k]           = s_src[static_cast<int64_t>(src) * H + hk];
-            if constexpr (EDGE) se[k] = edge_scores[(eb + from) * H + hk];
-          }
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k) {
-            if (j + k < nb) {
-              float z = s[k] + sd;
-              if constexpr (EDGE) z = z + se[k];
-              const float a = expf(leaky(z, p.slope) - m) / den;
-              add_to(acc, scaled(v[k], a));
-              if (writer) p.alpha[(eb + j + k) * H + hk] = a;
-            }
-          }
-        }
-      }
-      if (act) stv(o + d * o_stride + c, e1 > e0 ? acc : splat<VEC>(0.0f));
+  for_target_pieces<VEC, LANES>(p, HF, [&](int64_t d, int64_t e0, int64_t e1, int64_t c, int64_t cl, bool act) {
+    const int64_t hk  = cl / F;   // (a piece never straddles two heads: VEC = 4 only when F % 4 == 0)
+    const bool writer = act && c == hk * F;
+    const float sd    = s_src[(p.n_src + d) * H + hk];
+    float m = -INFINITY, den = -0.0f;
+    int my = 0;
+    fvec<VEC> v[kAggBatch];
+    float s[kAggBatch], se[kAggBatch];
+    const auto fetch = [&](int64_t e, bool in) { my = in ? p.col_ind[e] : 0; };
+    const auto z_of  = [&](int k) {
+      float z = s[k] + sd;
+      if constexpr (EDGE) z = z + se[k];
+      return z;
+    };
+    for (int pass = 0; pass < 2; ++pass) {   // 0: the max of l, 1: den = sum of expf(l - max), left to right
+      for_edge_batches<LANES>(
+          e0, e1, gl, fetch,
+          [&](int k, int from, int64_t e) {
+            const int src = __shfl(my, from, LANES);
+            s[k]          = s_src[static_cast<int64_t>(src) * H + hk];
+            if constexpr (EDGE) se[k] = edge_scores[e * H + hk];
+          },
+          [&](int k, int64_t) {
+            const float l = leaky(z_of(k), p.slope);
+            if (pass == 0) m = fmaxf(m, l);
+            else den = den + expf(l - m);
+          });
     }
-  }
+    fvec<VEC> acc = splat<VEC>(-0.0f);
+    for_edge_batches<LANES>(
+        e0, e1, gl, fetch,
+        [&](int k, int from, int64_t e) {
+          const int src = __shfl(my, from, LANES);
+          v[k]          = ldv<VEC>(p.h + static_cast<int64_t>(src) * p.h_stride + cl);
+          s[k]          = s_src[static_cast<int64_t>(src) * H + hk];
+          if constexpr (EDGE) se[k] = edge_scores[e * H + hk];
+        },
+        [&](int k, int64_t e) {
+          const float a = expf(leaky(z_of(k), p.slope) - m) / den;
+          add_to(acc, scaled(v[k], a));
+          if (writer) p.alpha[e * H + hk] = a;
+        });
+    if (act) stv(o + d * o_stride + c, e1 > e0 ? acc : splat<VEC>(0.0f));
+  });
 }
 
 // one thread per (target d, head k): da[e] = G_k[d] . h[col[e], k] (into dz), c = sum of alpha * da, then dz and ds_dst;

@@ -4,16 +4,18 @@
 //
 // Forward (kernels/agg.hip's shape: one group of LANES lanes per target row d, LANES = 16 / 32 / 64 from the row width; the
 // column ids of up to LANES edges come with one coalesced load and are handed out with shuffles; the neighbour rows of a
-// batch of kAggBatch edges are loaded back to back): per lane the running sum S, the running sum of squares Q, the running
-// minimum and maximum and the edge positions that hold them. Which of them are kept is the 5-bit mask of the call: the
-// branches on it are the same for every lane of the grid (one instantiation serves every subset). The slots of the selected
-// aggregators follow each other in the order sum, mean, min, max, std; the target's own row comes last.
+// batch of kAggBatch edges are loaded back to back; for_target_pieces and for_edge_batches of agg_common.cuh): per lane the
+// running sum S, the running sum of squares Q, the running minimum and maximum and the edge positions that hold them. Which
+// of them are kept is the 5-bit mask of the call: the branches on it are the same for every lane of the grid (one
+// instantiation serves every subset). The slots of the selected aggregators follow each other in the order sum, mean, min,
+// max, std; the target's own row comes last.
 //
 // Backward (grad_x[s] for every source row s; no atomics): the walk of kernels/agg.hip (agg_bwd_prepare, then a chunk
 // kernel over the tiles of the sorted positions and a fold kernel per source row, both through agg_common.cuh) with this
 // op's own per-edge term, pna_fold_edges: up to nine rows of the target per edge (four gradient slots, the two arg rows, the
-// std gradient, its mean and its coefficient), kPnaBwdBatch edges in flight. x[s] is constant over a source's run and is
-// loaded once per source (fold) or chunk.
+// std gradient, its mean and its coefficient), kPnaBwdBatch edges in flight. Its loop over the sorted positions is written
+// out (one loop over the batch per aggregator part; agg_common.cuh's header has the reason). x[s] is constant over a
+// source's run and is loaded once per source (fold) or chunk.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -76,95 +78,79 @@ __device__ __forceinline__ void sti(int32_t* p, const ivec<VEC>& a)
 template <int VEC, int LANES>
 __global__ __launch_bounds__(kAggBlock) void pna_fwd_kernel(wm_pna_args p)
 {
-  constexpr int kGroups = kAggBlock / LANES;
-  const int gl          = threadIdx.x % LANES;
-  const int64_t F       = p.dim;
-  const pna_slots sl    = slots_of(p.mask);
-  const bool want_std   = p.mask & WM_PNA_STD;
-  const bool want_s     = p.mask & (WM_PNA_SUM | WM_PNA_MEAN | WM_PNA_STD);
-  const bool want_min   = p.mask & WM_PNA_MIN;
-  const bool want_max   = p.mask & WM_PNA_MAX;
-  for (int64_t d = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; d < p.n_dst;
-       d += static_cast<int64_t>(gridDim.x) * kGroups) {
-    int64_t e0, e1;
-    edge_range(p.row_ptr, d, p.n_edges, e0, e1);
+  const int gl        = threadIdx.x % LANES;
+  const int64_t F     = p.dim;
+  const pna_slots sl  = slots_of(p.mask);
+  const bool want_std = p.mask & WM_PNA_STD;
+  const bool want_s   = p.mask & (WM_PNA_SUM | WM_PNA_MEAN | WM_PNA_STD);
+  const bool want_min = p.mask & WM_PNA_MIN;
+  const bool want_max = p.mask & WM_PNA_MAX;
+  for_target_pieces<VEC, LANES>(p, F, [&](int64_t d, int64_t e0, int64_t e1, int64_t c, int64_t cl, bool act) {
     const int64_t deg = e1 - e0;
     const float r     = deg > 0 ? 1.0f / static_cast<float>(deg) : 0.0f;
     const float* self = p.in + d * p.in_stride;
     float* orow       = p.out + d * p.out_stride;
-    for (int64_t cb = 0; cb < F; cb += LANES * VEC) {   // (group-uniform trip count: the shuffles below stay in step)
-      const int64_t c  = cb + gl * VEC;
-      const bool act   = c < F;
-      const int64_t cl = act ? c : 0;
-      fvec<VEC> S = splat<VEC>(-0.0f), Q = splat<VEC>(-0.0f), mn = splat<VEC>(0.0f), mx = splat<VEC>(0.0f);
-      ivec<VEC> amin, amax;
+    fvec<VEC> S = splat<VEC>(-0.0f), Q = splat<VEC>(-0.0f), mn = splat<VEC>(0.0f), mx = splat<VEC>(0.0f);
+    ivec<VEC> amin, amax;
 #pragma unroll
-      for (int i = 0; i < VEC; ++i) amin.v[i] = -1, amax.v[i] = -1;
-      for (int64_t eb = e0; eb < e1; eb += LANES) {
-        const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
-        const int my = gl < nb ? p.col_ind[eb + gl] : 0;
-        for (int j = 0; j < nb; j += kAggBatch) {
-          fvec<VEC> v[kAggBatch];
+    for (int i = 0; i < VEC; ++i) amin.v[i] = -1, amax.v[i] = -1;
+    int my = 0;
+    fvec<VEC> v[kAggBatch];
+    for_edge_batches<LANES>(
+        e0, e1, gl, [&](int64_t pos, bool in) { my = in ? p.col_ind[pos] : 0; },
+        [&](int k, int from, int64_t) {
+          const int src = __shfl(my, from, LANES);
+          v[k]          = ldv<VEC>(p.in + static_cast<int64_t>(src) * p.in_stride + cl);
+        },
+        [&](int k, int64_t pos) {
+          const int e      = static_cast<int>(pos);
+          const bool first = pos == e0;   // the first term is taken as it is (a NaN too)
+          if (want_s) add_to(S, v[k]);
+          if (want_std) {
 #pragma unroll
-          for (int k = 0; k < kAggBatch; ++k) {
-            const int src = __shfl(my, j + k < nb ? j + k : nb - 1, LANES);
-            v[k]          = ldv<VEC>(p.in + static_cast<int64_t>(src) * p.in_stride + cl);
+            for (int i = 0; i < VEC; ++i) Q.v[i] = Q.v[i] + v[k].v[i] * v[k].v[i];
           }
+          if (want_min) {
 #pragma unroll
-          for (int k = 0; k < kAggBatch; ++k) {
-            if (j + k < nb) {
-              const int e      = static_cast<int>(eb) + j + k;
-              const bool first = eb + j + k == e0;   // the first term is taken as it is (a NaN too)
-              if (want_s) add_to(S, v[k]);
-              if (want_std) {
-#pragma unroll
-                for (int i = 0; i < VEC; ++i) Q.v[i] = Q.v[i] + v[k].v[i] * v[k].v[i];
-              }
-              if (want_min) {
-#pragma unroll
-                for (int i = 0; i < VEC; ++i)
-                  if (first || v[k].v[i] < mn.v[i]) mn.v[i] = v[k].v[i], amin.v[i] = e;
-              }
-              if (want_max) {
-#pragma unroll
-                for (int i = 0; i < VEC; ++i)
-                  if (first || v[k].v[i] > mx.v[i]) mx.v[i] = v[k].v[i], amax.v[i] = e;
-              }
-            }
+            for (int i = 0; i < VEC; ++i)
+              if (first || v[k].v[i] < mn.v[i]) mn.v[i] = v[k].v[i], amin.v[i] = e;
           }
-        }
-      }
-      if (!act) continue;
-      const bool any = deg > 0;
-      if (p.mask & WM_PNA_SUM) stv(orow + sl.sum * F + c, any ? S : splat<VEC>(0.0f));
-      if (p.mask & WM_PNA_MEAN) stv(orow + sl.mean * F + c, any ? scaled(S, r) : splat<VEC>(0.0f));
-      if (want_min) {
-        stv(orow + sl.min * F + c, mn);
-        if (p.arg_min != nullptr) sti(p.arg_min + d * F + c, amin);
-      }
-      if (want_max) {
-        stv(orow + sl.max * F + c, mx);
-        if (p.arg_max != nullptr) sti(p.arg_max + d * F + c, amax);
-      }
-      if (want_std) {
-        fvec<VEC> sd = splat<VEC>(0.0f), m = splat<VEC>(0.0f), co = splat<VEC>(0.0f);
-        if (any) {
+          if (want_max) {
 #pragma unroll
-          for (int i = 0; i < VEC; ++i) {
-            m.v[i]        = S.v[i] * r;
-            const float q = Q.v[i] * r;
-            const float v = q - m.v[i] * m.v[i];
-            sd.v[i]       = sqrtf((v > 0.0f ? v : 0.0f) + p.eps);
-            co.v[i]       = v > 0.0f ? r / sd.v[i] : 0.0f;
+            for (int i = 0; i < VEC; ++i)
+              if (first || v[k].v[i] > mx.v[i]) mx.v[i] = v[k].v[i], amax.v[i] = e;
           }
-        }
-        stv(orow + sl.std * F + c, sd);
-        if (p.std_mean != nullptr) stv(p.std_mean + d * F + c, m);
-        if (p.std_coef != nullptr) stv(p.std_coef + d * F + c, co);
-      }
-      stv(orow + sl.self * F + c, ldv<VEC>(self + c));
+        });
+    if (!act) return;
+    const bool any = deg > 0;
+    if (p.mask & WM_PNA_SUM) stv(orow + sl.sum * F + c, any ? S : splat<VEC>(0.0f));
+    if (p.mask & WM_PNA_MEAN) stv(orow + sl.mean * F + c, any ? scaled(S, r) : splat<VEC>(0.0f));
+    if (want_min) {
+      stv(orow + sl.min * F + c, mn);
+      if (p.arg_min != nullptr) sti(p.arg_min + d * F + c, amin);
     }
-  }
+    if (want_max) {
+      stv(orow + sl.max * F + c, mx);
+      if (p.arg_max != nullptr) sti(p.arg_max + d * F + c, amax);
+    }
+    if (want_std) {
+      fvec<VEC> sd = splat<VEC>(0.0f), m = splat<VEC>(0.0f), co = splat<VEC>(0.0f);
+      if (any) {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) {
+          m.v[i]         = S.v[i] * r;
+          const float q  = Q.v[i] * r;
+          const float va = q - m.v[i] * m.v[i];
+          sd.v[i]        = sqrtf((va > 0.0f ? va : 0.0f) + p.eps);
+          co.v[i]        = va > 0.0f ? r / sd.v[i] : 0.0f;
+        }
+      }
+      stv(orow + sl.std * F + c, sd);
+      if (p.std_mean != nullptr) stv(p.std_mean + d * F + c, m);
+      if (p.std_coef != nullptr) stv(p.std_coef + d * F + c, co);
+    }
+    stv(orow + sl.self * F + c, ldv<VEC>(self + c));
+  });
 }
 
 // acc += t(e) for the edges at sorted positions [eb0, ee), in that order (LANES lanes, this lane's columns at cl); xs: this

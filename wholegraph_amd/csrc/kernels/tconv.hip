@@ -15,7 +15,8 @@
 // head's first column stores l into alpha[e, k] (the forward owns alpha until it writes it), the max m is taken on the way.
 // Pass 2 reads the logits back for den = sum of expf(l - m), left to right; pass 3 reads the VALUE rows,
 // alpha = expf(l - m) / den, o += alpha * row, and writes alpha over l. With VEC = 1 a head may span several column blocks
-// of the group, so the logits live in the workspace instead of alpha.
+// of the group, so the logits live in the workspace instead of alpha. Passes 1 and 3, and both row passes of the per-target
+// backward, are walks of agg_common.cuh (for_edge_batches inside for_target_pieces).
 //
 // Backward (no atomics; one fixed order of every sum):
 //   1 tconv_bwd_dst_kernel<VEC, LANES>, a lane group per target (only when grad_query or grad_key is asked for): da by the
@@ -80,161 +81,111 @@ __global__ __launch_bounds__(kAggBlock) void tconv_dot_kernel(wm_tconv_args p, f
 template <int VEC, int LANES>
 __global__ __launch_bounds__(kAggBlock) void tconv_fwd_kernel(wm_tconv_args p, float* o, int64_t o_stride, float* lbuf)
 {
-  constexpr int kGroups = kAggBlock / LANES;
-  const int gl          = threadIdx.x % LANES;
+  const int gl    = threadIdx.x % LANES;
   const int64_t H = p.heads, F = p.dim, HF = H * F;
   const int lh = static_cast<int>(F / 4);   // (VEC = 4) lanes of a head
-  for (int64_t d = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; d < p.n_dst;
-       d += static_cast<int64_t>(gridDim.x) * kGroups) {
-    int64_t e0, e1;
-    edge_range(p.row_ptr, d, p.n_edges, e0, e1);
-    for (int64_t cb = 0; cb < HF; cb += LANES * VEC) {   // (group-uniform trip count: the shuffles below stay in step)
-      const int64_t c  = cb + gl * VEC;
-      const bool act   = c < HF;
-      const int64_t cl = act ? c : 0;
-      const int64_t hk = cl / F;   // (a piece never straddles two heads: VEC = 4 only when F % 4 == 0)
-      const bool writer = act && c == hk * F;
-      float m = -INFINITY, den = -0.0f;
-      if constexpr (VEC == 4) {   // pass 1: the logits, kept in lbuf (= alpha); a head lies within this column block
-        const fvec<4> qd = ldv<4>(p.query + d * p.query_stride + cl);
-        for (int64_t eb = e0; eb < e1; eb += LANES) {
-          const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
-          const int my = gl < nb ? p.col_ind[eb + gl] : 0;
-          for (int j = 0; j < nb; j += kAggBatch) {
-            fvec<4> v[kAggBatch];
+  for_target_pieces<VEC, LANES>(p, HF, [&](int64_t d, int64_t e0, int64_t e1, int64_t c, int64_t cl, bool act) {
+    const int64_t hk  = cl / F;   // (a piece never straddles two heads: VEC = 4 only when F % 4 == 0)
+    const bool writer = act && c == hk * F;
+    float m = -INFINITY, den = -0.0f;
+    int my = 0;
+    fvec<VEC> v[kAggBatch];
+    float l[kAggBatch];
+    const auto fetch = [&](int64_t e, bool in) { my = in ? p.col_ind[e] : 0; };
+    if constexpr (VEC == 4) {   // pass 1: the logits, kept in lbuf (= alpha); a head lies within this column block
+      const fvec<4> qd = ldv<4>(p.query + d * p.query_stride + cl);
+      for_edge_batches<LANES>(
+          e0, e1, gl, fetch,
+          [&](int k, int from, int64_t) {
+            const int src = __shfl(my, from, LANES);
+            v[k]          = ldv<4>(p.key + static_cast<int64_t>(src) * p.key_stride + cl);
+          },
+          [&](int k, int64_t e) {
+            fvec<4> q;
 #pragma unroll
-            for (int k = 0; k < kAggBatch; ++k) {
-              const int src = __shfl(my, j + k < nb ? j + k : nb - 1, LANES);
-              v[k]          = ldv<4>(p.key + static_cast<int64_t>(src) * p.key_stride + cl);
-            }
-#pragma unroll
-            for (int k = 0; k < kAggBatch; ++k) {
-              if (j + k < nb) {
-                fvec<4> q;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) q.v[t] = qd.v[t] * v[k].v[t];
-                float l = head_tree<LANES>(q, lh);
-                if (p.norm_by_dim) l = l * p.scale;
-                m = fmaxf(m, l);
-                if (writer) lbuf[(eb + j + k) * H + hk] = l;
-              }
-            }
-          }
-        }
-        __threadfence_block();   // the head's other lanes read the logits back below
-      } else {
+            for (int t = 0; t < 4; ++t) q.v[t] = qd.v[t] * v[k].v[t];
+            float lg = head_tree<LANES>(q, lh);
+            if (p.norm_by_dim) lg = lg * p.scale;
+            m = fmaxf(m, lg);
+            if (writer) lbuf[e * H + hk] = lg;
+          });
+      __threadfence_block();   // the head's other lanes read the logits back below
+    } else {
 #pragma unroll 4
-        for (int64_t e = e0; e < e1; ++e) m = fmaxf(m, lbuf[e * H + hk]);
-      }
-#pragma unroll 4
-      for (int64_t e = e0; e < e1; ++e) den = den + expf(lbuf[e * H + hk] - m);   // pass 2, left to right
-      fvec<VEC> acc = splat<VEC>(-0.0f);
-      for (int64_t eb = e0; eb < e1; eb += LANES) {   // pass 3: the value rows
-        const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
-        const int my = gl < nb ? p.col_ind[eb + gl] : 0;
-        for (int j = 0; j < nb; j += kAggBatch) {
-          fvec<VEC> v[kAggBatch];
-          float l[kAggBatch];
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k) {
-            const int from = j + k < nb ? j + k : nb - 1;
-            const int src  = __shfl(my, from, LANES);
-            v[k]           = ldv<VEC>(p.value + static_cast<int64_t>(src) * p.value_stride + cl);
-            l[k]           = lbuf[(eb + from) * H + hk];
-          }
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k) {
-            if (j + k < nb) {
-              const float a = expf(l[k] - m) / den;
-              add_to(acc, scaled(v[k], a));
-              if (writer) p.alpha[(eb + j + k) * H + hk] = a;
-            }
-          }
-        }
-      }
-      if (act) stv(o + d * o_stride + c, e1 > e0 ? acc : splat<VEC>(0.0f));
+      for (int64_t e = e0; e < e1; ++e) m = fmaxf(m, lbuf[e * H + hk]);
     }
-  }
+#pragma unroll 4
+    for (int64_t e = e0; e < e1; ++e) den = den + expf(lbuf[e * H + hk] - m);   // pass 2, left to right
+    fvec<VEC> acc = splat<VEC>(-0.0f);
+    for_edge_batches<LANES>(   // pass 3: the value rows
+        e0, e1, gl, fetch,
+        [&](int k, int from, int64_t e) {
+          const int src = __shfl(my, from, LANES);
+          v[k]          = ldv<VEC>(p.value + static_cast<int64_t>(src) * p.value_stride + cl);
+          l[k]          = lbuf[e * H + hk];
+        },
+        [&](int k, int64_t e) {
+          const float a = expf(l[k] - m) / den;
+          add_to(acc, scaled(v[k], a));
+          if (writer) p.alpha[e * H + hk] = a;
+        });
+    if (act) stv(o + d * o_stride + c, e1 > e0 ? acc : splat<VEC>(0.0f));
+  });
 }
 
 template <int VEC, int LANES>
 __global__ __launch_bounds__(kAggBlock) void tconv_bwd_dst_kernel(wm_tconv_args p, tconv_bwd_state b)
 {
-  constexpr int kGroups = kAggBlock / LANES;
-  const int gl          = threadIdx.x % LANES;
+  const int gl    = threadIdx.x % LANES;
   const int64_t H = p.heads, F = p.dim, HF = H * F;
   const int lh  = static_cast<int>(F / 4);
   const float r = 1.0f / static_cast<float>(H);
   const bool gq = p.grad_query != nullptr;
-  for (int64_t d = static_cast<int64_t>(blockIdx.x) * kGroups + threadIdx.x / LANES; d < p.n_dst;
-       d += static_cast<int64_t>(gridDim.x) * kGroups) {
-    int64_t e0, e1;
-    edge_range(p.row_ptr, d, p.n_edges, e0, e1);
-    for (int64_t cb = 0; cb < HF; cb += LANES * VEC) {
-      const int64_t c  = cb + gl * VEC;
-      const bool act   = c < HF;
-      const int64_t cl = act ? c : 0;
-      const int64_t hk = cl / F;
-      const bool writer = act && c == hk * F;
-      if constexpr (VEC == 4) {   // da by the tree, kept in b.da; a head lies within this column block
-        fvec<4> gv = ldv<4>(p.grad + d * p.grad_stride + (p.concat ? cl : cl - hk * F));
-        if (!p.concat) gv = scaled(gv, r);
-        for (int64_t eb = e0; eb < e1; eb += LANES) {
-          const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
-          const int my = gl < nb ? p.col_ind[eb + gl] : 0;
-          for (int j = 0; j < nb; j += kAggBatch) {
-            fvec<4> v[kAggBatch];
+  for_target_pieces<VEC, LANES>(p, HF, [&](int64_t d, int64_t e0, int64_t e1, int64_t c, int64_t cl, bool act) {
+    const int64_t hk  = cl / F;
+    const bool writer = act && c == hk * F;
+    int my = 0;
+    fvec<VEC> v[kAggBatch];
+    float a[kAggBatch], x[kAggBatch];
+    const auto fetch = [&](int64_t e, bool in) { my = in ? p.col_ind[e] : 0; };
+    if constexpr (VEC == 4) {   // da by the tree, kept in b.da; a head lies within this column block
+      fvec<4> gv = ldv<4>(p.grad + d * p.grad_stride + (p.concat ? cl : cl - hk * F));
+      if (!p.concat) gv = scaled(gv, r);
+      for_edge_batches<LANES>(
+          e0, e1, gl, fetch,
+          [&](int k, int from, int64_t) {
+            const int src = __shfl(my, from, LANES);
+            v[k]          = ldv<4>(p.value + static_cast<int64_t>(src) * p.value_stride + cl);
+          },
+          [&](int k, int64_t e) {
+            fvec<4> q;
 #pragma unroll
-            for (int k = 0; k < kAggBatch; ++k) {
-              const int src = __shfl(my, j + k < nb ? j + k : nb - 1, LANES);
-              v[k]          = ldv<4>(p.value + static_cast<int64_t>(src) * p.value_stride + cl);
-            }
-#pragma unroll
-            for (int k = 0; k < kAggBatch; ++k) {
-              if (j + k < nb) {
-                fvec<4> q;
-#pragma unroll
-                for (int t = 0; t < 4; ++t) q.v[t] = gv.v[t] * v[k].v[t];
-                const float da = head_tree<LANES>(q, lh);
-                if (writer) b.da[(eb + j + k) * H + hk] = da;
-              }
-            }
-          }
-        }
-        __threadfence_block();   // the head's other lanes read da back below
-      }
-      float cs = -0.0f;
-#pragma unroll 4
-      for (int64_t e = e0; e < e1; ++e) cs = cs + p.alpha[e * H + hk] * b.da[e * H + hk];
-      fvec<VEC> gd = splat<VEC>(-0.0f);
-      for (int64_t eb = e0; eb < e1; eb += LANES) {   // ds, and grad_query from the key rows
-        const int nb = static_cast<int>(e1 - eb < LANES ? e1 - eb : LANES);
-        const int my = gl < nb ? p.col_ind[eb + gl] : 0;
-        for (int j = 0; j < nb; j += kAggBatch) {
-          fvec<VEC> v[kAggBatch];
-          float a[kAggBatch], x[kAggBatch];
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k) {
-            const int from = j + k < nb ? j + k : nb - 1;
-            const int src  = __shfl(my, from, LANES);
-            v[k]           = gq ? ldv<VEC>(p.key + static_cast<int64_t>(src) * p.key_stride + cl) : splat<VEC>(0.0f);
-            a[k]           = p.alpha[(eb + from) * H + hk];
-            x[k]           = b.da[(eb + from) * H + hk];
-          }
-#pragma unroll
-          for (int k = 0; k < kAggBatch; ++k) {
-            if (j + k < nb) {
-              const float dl = a[k] * (x[k] - cs);
-              const float ds = p.norm_by_dim ? dl * p.scale : dl;
-              add_to(gd, scaled(v[k], ds));
-              if (writer) b.ds[(eb + j + k) * H + hk] = ds;
-            }
-          }
-        }
-      }
-      if (act && gq) stv(p.grad_query + d * p.grad_query_stride + c, e1 > e0 ? gd : splat<VEC>(0.0f));
+            for (int t = 0; t < 4; ++t) q.v[t] = gv.v[t] * v[k].v[t];
+            const float da = head_tree<LANES>(q, lh);
+            if (writer) b.da[e * H + hk] = da;
+          });
+      __threadfence_block();   // the head's other lanes read da back below
     }
-  }
+    float cs = -0.0f;
+#pragma unroll 4
+    for (int64_t e = e0; e < e1; ++e) cs = cs + p.alpha[e * H + hk] * b.da[e * H + hk];
+    fvec<VEC> gd = splat<VEC>(-0.0f);
+    for_edge_batches<LANES>(   // ds, and grad_query from the key rows
+        e0, e1, gl, fetch,
+        [&](int k, int from, int64_t e) {
+          const int src = __shfl(my, from, LANES);
+          v[k]          = gq ? ldv<VEC>(p.key + static_cast<int64_t>(src) * p.key_stride + cl) : splat<VEC>(0.0f);
+          a[k]          = p.alpha[e * H + hk];
+          x[k]          = b.da[e * H + hk];
+        },
+        [&](int k, int64_t e) {
+          const float dl = a[k] * (x[k] - cs);
+          const float ds = p.norm_by_dim ? dl * p.scale : dl;
+          add_to(gd, scaled(v[k], ds));
+          if (writer) b.ds[e * H + hk] = ds;
+        });
+    if (act && gq) stv(p.grad_query + d * p.grad_query_stride + c, e1 > e0 ? gd : splat<VEC>(0.0f));
+  });
 }
 
 __global__ __launch_bounds__(kAggBlock) void tconv_bwd_prep_kernel(wm_tconv_args p, tconv_bwd_state b)
@@ -275,27 +226,22 @@ __device__ __forceinline__ void fold_tconv_edges(fvec<VEC>& acc, const wm_tconv_
 {
   const int64_t H = p.heads;
   const float r   = 1.0f / static_cast<float>(H);
-  for (int64_t eb = eb0; eb < ee; eb += LANES) {
-    const int nb = static_cast<int>(ee - eb < LANES ? ee - eb : LANES);
-    int my_e = 0, my_d = 0;
-    if (gl < nb) my_e = b.ix.order[eb + gl], my_d = b.ix.sorted_dst[eb + gl];
-    for (int j = 0; j < nb; j += kAggBatch) {
-      fvec<VEC> v[kAggBatch];
-      float a[kAggBatch];
-#pragma unroll
-      for (int k = 0; k < kAggBatch; ++k) {
-        const int from  = j + k < nb ? j + k : nb - 1;
+  int my_e = 0, my_d = 0;
+  fvec<VEC> v[kAggBatch];
+  float a[kAggBatch];
+  for_edge_batches<LANES>(
+      eb0, ee, gl,
+      [&](int64_t i, bool in) {
+        my_e = 0, my_d = 0;
+        if (in) my_e = b.ix.order[i], my_d = b.ix.sorted_dst[i];
+      },
+      [&](int k, int from, int64_t) {
         const int64_t e = __shfl(my_e, from, LANES);
         const int dst   = __shfl(my_d, from, LANES);
         v[k]            = ldv<VEC>(q.rows + static_cast<int64_t>(dst) * q.stride + q.col);
         a[k]            = q.sc[e * H + q.hk];
-      }
-#pragma unroll
-      for (int k = 0; k < kAggBatch; ++k) {
-        if (j + k < nb) add_to(acc, scaled(q.mean ? scaled(v[k], r) : v[k], a[k]));
-      }
-    }
-  }
+      },
+      [&](int k, int64_t) { add_to(acc, scaled(q.mean ? scaled(v[k], r) : v[k], a[k])); });
 }
 
 template <int VEC, int LANES>

@@ -32,6 +32,8 @@
  *      (2o) negative sampling over the same graph: per source node, K nodes that are not its neighbours, as one launch.
  *      (2p) the dot product of the two endpoint rows of every edge of a sampled CSC block: the score of skip-gram training
  *      over the walks and negatives above and of link prediction (forward and a deterministic backward).
+ *      (2q) the node-induced subgraph of a CSR graph held in WholeMemory: all graph edges among a set of nodes as one local
+ *      block, the batch of subgraph-wise training (GraphSAINT, ShaDow-GNN, Cluster-GCN).
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -1329,6 +1331,48 @@ enum wholememory_error_code_t wholememory_ext_csc_edge_dot_backward(const int32_
                                                                     int64_t grad_dst_stride,
                                                                     struct wholememory_env_func_t* p_env_fns,
                                                                     void* stream);
+
+/* ---- (2q) node-induced subgraph of a CSR graph held in WholeMemory -------------------------------------------------------- */
+/* The block of subgraph-wise training: for a list of n nodes, every graph edge whose two ends are in the list, as local CSR
+ * arrays that the block ops of (2b) .. (2p) take with n_dst = n_src = n. Graph tensors are as (2m): row_ptr int64
+ * [n_nodes + 1], col_ind int32 or int64 [n_edges], both CONTINUOUS or CHUNKED, in device or host memory, or plain device
+ * arrays wrapped with wholememory_make_tensor_from_pointer. nodes is int32 or int64 [n], on the device. The shape of the
+ * samplers: output_offset_tensor is the caller's, int32 with at least n + 1 entries, on the device; col int32 [m] and, with a
+ * context for them, edge_gid int64 [m] are allocated through p_env_fns once m is known.
+ *
+ * Definition. A node v is a member when 0 <= v < n_nodes and v occurs in nodes. Its local id is first(v), the lowest i with
+ * nodes[i] == v. Duplicates in nodes are allowed: every position gets a row. Row i, with u = nodes[i]:
+ *   - the row is empty when u is outside [0, n_nodes);
+ *   - the row is empty when (s, e) = (row_ptr[u], row_ptr[u + 1]) does not satisfy 0 <= s <= e <= n_edges and e - s < 2^31
+ *     (a valid graph has no such row);
+ *   - otherwise, for pos = s .. e - 1 ascending with c = col_ind[pos]: if c is a member, the row gets the entry
+ *     (first(c), pos).
+ * Multi-edges and self-loops are kept, and the graph's order within a row is kept. offsets is the exclusive prefix of the row
+ * lengths, offsets[n] = m. col[k] is the local id of entry k, edge_gid[k] its position in col_ind. A col_ind value is only
+ * ever compared, never used as an index: damaged entries (-1, n_nodes, 2^31 - 1) never match, even when nodes holds those
+ * same values, because such values are not members. The result is a function of the graph and nodes alone: it does not
+ * depend on the launch geometry, on the capacity of the membership table, on the order of the inserts or on the memory type.
+ *
+ * The call makes one host round trip, for m: table and count are queued, the stream is synchronised, the outputs are
+ * allocated, the fill is queued. It then returns with the outputs complete, or, after
+ * wholememory_ext_set_async_completion(1), with the fill queued on `stream`, exactly as the samplers do.
+ *
+ * Errors, in this order; all but the last are answered before any device work. INVALID_INPUT: a NULL row_ptr, col_ind, nodes,
+ * offset tensor, p_env_fns or output_col_memory_context; one of the four tensors not 1-D; n >= 2^31 - 1; an offset tensor
+ * with fewer than n + 1 entries. LOGIC_ERROR, the dtype cases of (2m): row_ptr not int64, col_ind or nodes not int32 / int64,
+ * offsets not int32. INVALID_INPUT for a HIERARCHY tensor. NOT_IMPLEMENTED for a DISTRIBUTED tensor: every membership probe
+ * would be a collective gather. NOT_SUPPORTED, nothing queued, when the device backend has no such kernels. INVALID_INPUT when
+ * m >= 2^31: answered after the count, with no output allocated. n = 0 succeeds: it writes offsets[0] = 0 and allocates empty
+ * outputs. */
+enum wholememory_error_code_t wholememory_ext_csr_induced_subgraph(
+  wholememory_tensor_t wm_csr_row_ptr_tensor,
+  wholememory_tensor_t wm_csr_col_ptr_tensor,
+  wholememory_tensor_t nodes_tensor,         /* [n] int32 / int64, device */
+  wholememory_tensor_t output_offset_tensor, /* int32, at least n + 1 entries, device */
+  void* output_col_memory_context,           /* int32 [m]: local positions */
+  void* output_edge_gid_memory_context,      /* int64 [m] or NULL: positions in csr_col_ptr */
+  wholememory_env_func_t* p_env_fns,
+  void* stream);
 
 /* ---- (3) testing seam ---------------------------------------------------------------------- */
 /* Replaces the device backend. Refuses (WHOLEMEMORY_NOT_SUPPORTED) unless the environment has

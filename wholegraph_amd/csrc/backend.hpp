@@ -487,6 +487,21 @@ struct wm_neg_args : wm_csr_graph {
   void* out;            // [n, num_negatives] col_dtype
 };
 
+// the node-induced subgraph of such a graph (kernels/isub.hip, wholegraph_amd_ext.h section 2q; the weights stay empty): row i of
+// the result holds, in the graph's order, the entries of row nodes[i] that occur in `nodes`, as positions in `nodes`. Three
+// steps around the host learning the size: build (the membership table), count, fill
+struct wm_isub_args : wm_csr_graph {
+  const void* nodes;    // [n] device
+  wholememory_dtype_t node_dtype;
+  int64_t n;            // rows; n < 2^31 - 1
+  void* workspace;      // isub_workspace_bytes(n, &table_bytes) bytes; the first table_bytes of them 0xFF before build
+  int* counts;          // [n + 1] device: entries per row, counts[n] = 0 (written by count)
+  int64_t* total;       // one word the device can write (pinned or device): the sum of counts in 64 bits (written by count)
+  const int* offsets;   // [n + 1] device: exclusive prefix of counts (read by fill)
+  int* out_col;         // [total] positions in `nodes` (written by fill)
+  int64_t* out_edge_gid;  // [total] positions in csr_col_ptr, or nullptr
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -761,6 +776,13 @@ struct wm_device_backend {
   int (*edot_forward)(const wm_edot_args* a, void* stream);
   size_t (*edot_backward_workspace_bytes)(const wm_edot_args* a);
   int (*edot_backward)(const wm_edot_args* a, const wm_edge_index& ix, void* workspace, void* stream);
+  // ---- node-induced subgraph (kernels/isub.hip, wholegraph_amd_ext.h section 2q); nullptr in a backend without it ----
+  // the workspace of a call over n rows; its first *table_bytes bytes (a multiple of 16) are the membership table, which the
+  // caller sets to 0xFF before isub_build. build inserts the nodes, count writes a->counts and a->total, fill the outputs
+  size_t (*isub_workspace_bytes)(int64_t n, size_t* table_bytes);
+  int (*isub_build)(const wm_isub_args* a, void* stream);
+  int (*isub_count)(const wm_isub_args* a, void* stream);
+  int (*isub_fill)(const wm_isub_args* a, void* stream);
 };
 
 }  // extern "C"

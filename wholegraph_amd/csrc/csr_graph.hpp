@@ -1,9 +1,9 @@
 // wholegraph_amd — what the ops over the WholeMemory CSR graph share on the host (graph_ops.cpp: the two samplers, the fused
-// hop, the multi-hop chain, the random walks, the node2vec walks, negative sampling): the graph tensors of one call, checked,
-// and the one place that turns them into the backend's wm_csr_graph. The checks are separate steps because every entry point
-// keeps its own ORDER of answers (the samplers judge placement before dtypes before sizes, as the reference does; the walks and
-// the negatives judge shapes and sizes before dtypes before placement: wholegraph_amd_ext.h sections 2m - 2o), and a call with
-// two faults gets the answer of the step its entry makes first.
+// hop, the multi-hop chain, the random walks, the node2vec walks, negative sampling, the induced subgraph): the graph tensors of
+// one call, checked, and the one place that turns them into the backend's wm_csr_graph. The checks are separate steps because
+// every entry point keeps its own ORDER of answers (the samplers judge placement before dtypes before sizes, as the reference
+// does; the walks, the negatives and the induced subgraph judge shapes and sizes before dtypes before placement:
+// wholegraph_amd_ext.h sections 2m - 2o and 2q), and a call with two faults gets the answer of the step its entry makes first.
 #pragma once
 
 #include <initializer_list>

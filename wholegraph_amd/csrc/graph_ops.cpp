@@ -420,6 +420,98 @@ wholememory_error_code_t wholememory_ext_csr_negative_sample(
   WM_API_END
 }
 
+// Node-induced subgraph (extension, wholegraph_amd_ext.h section 2q; kernels/isub.hip): the block of subgraph-wise training,
+// every graph edge among `nodes`, as local CSR arrays. The sampler's shape: count per row, scan into the caller's offsets, ONE
+// host round trip for the size, outputs from the caller's allocator, fill. Every answer about the arguments comes before any
+// device work; the answer about the size (2^31 entries or more) comes after the count, with no output allocated.
+wholememory_error_code_t wholememory_ext_csr_induced_subgraph(
+  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor, wholememory_tensor_t nodes_tensor,
+  wholememory_tensor_t output_offset_tensor, void* output_col_memory_context, void* output_edge_gid_memory_context,
+  wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  if (p_env_fns == nullptr || output_col_memory_context == nullptr) return WHOLEMEMORY_INVALID_INPUT;
+  wholememory_error_code_t err = WHOLEMEMORY_SUCCESS;
+  checked_graph g{wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, nullptr, false};
+  wholememory_array_description_t nodes_desc, offset_desc;
+  WHOLEMEMORY_RETURN_ON_FAIL(g.arrays());
+  if (!array_of(nodes_tensor, "nodes_tensor", &nodes_desc, &err)) return err;
+  if (!array_of(output_offset_tensor, "output_offset_tensor", &offset_desc, &err)) return err;
+  const int64_t n = nodes_desc.size;
+  if (n < 0 || g.row_desc.size < 1 || n >= (INT64_C(1) << 31) - 1) {
+    WM_ERROR("%ld nodes: the subgraph must have fewer than 2^31 - 1 rows", static_cast<long>(n));
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  if (offset_desc.size < n + 1) {
+    WM_ERROR("output_offset_tensor needs %ld entries, has %ld", static_cast<long>(n + 1), static_cast<long>(offset_desc.size));
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  WHOLEMEMORY_RETURN_ON_FAIL(g.row_dtype());
+  WHOLEMEMORY_RETURN_ON_FAIL(g.col_and_id_dtype(nodes_desc.dtype, "nodes"));
+  if (offset_desc.dtype != WHOLEMEMORY_DT_INT) {
+    WM_ERROR("output_offset_tensor must be int32, got %d", static_cast<int>(offset_desc.dtype));
+    return WHOLEMEMORY_LOGIC_ERROR;
+  }
+  WHOLEMEMORY_RETURN_ON_FAIL(g.placement(
+    csr_tensors::row_col,
+    "the induced subgraph of DISTRIBUTED tensors is not implemented: every membership probe would be a collective gather"));
+  const auto* bk = backend();
+  if (bk->isub_workspace_bytes == nullptr || bk->isub_build == nullptr || bk->isub_count == nullptr || bk->isub_fill == nullptr ||
+      bk->exclusive_scan_i32 == nullptr)
+    return WHOLEMEMORY_NOT_SUPPORTED;
+  int* offsets = static_cast<int*>(wholememory_tensor_get_data_pointer(output_offset_tensor));
+  if (offsets == nullptr) return WHOLEMEMORY_INVALID_INPUT;
+  const bool drain = !async_completion_enabled() || debug_sync_enabled();
+  if (n == 0) {
+    WM_BK(bk->memset_async(offsets, 0, sizeof(int), stream));
+    (void)output_alloc(p_env_fns, output_col_memory_context, 0, WHOLEMEMORY_DT_INT);
+    if (output_edge_gid_memory_context != nullptr) (void)output_alloc(p_env_fns, output_edge_gid_memory_context, 0, WHOLEMEMORY_DT_INT64);
+    if (drain) WM_BK(bk->stream_sync(stream));
+    return WHOLEMEMORY_SUCCESS;
+  }
+  wm_isub_args a{};
+  WHOLEMEMORY_RETURN_ON_FAIL(g.fill(&a));
+  a.nodes      = wholememory_tensor_get_data_pointer(nodes_tensor);
+  a.node_dtype = nodes_desc.dtype;
+  a.n          = n;
+  a.offsets    = offsets;
+  if (a.nodes == nullptr) return WHOLEMEMORY_INVALID_INPUT;
+
+  temp_mem ws_mem(p_env_fns), counts_mem(p_env_fns), scan_mem(p_env_fns), host_mem(p_env_fns);
+  size_t table_bytes    = 0;
+  const size_t ws_bytes = bk->isub_workspace_bytes(n, &table_bytes);
+  a.workspace           = ws_mem.device(static_cast<int64_t>(ws_bytes), WHOLEMEMORY_DT_INT8);
+  a.counts              = static_cast<int*>(counts_mem.device(n + 1, WHOLEMEMORY_DT_INT));
+  const size_t scan_ws  = bk->scan_i32_workspace_bytes(n + 1);
+  void* scan_ws_ptr     = scan_mem.device(static_cast<int64_t>(scan_ws), WHOLEMEMORY_DT_INT8);
+  a.total               = static_cast<int64_t*>(host_mem.pinned(1, WHOLEMEMORY_DT_INT64));   // written by the count's last kernel
+  if (a.workspace == nullptr || a.counts == nullptr || scan_ws_ptr == nullptr || a.total == nullptr) return WHOLEMEMORY_OUT_OF_MEMORY;
+
+  // table, rows counted, offsets, and the 64-bit total on the host: the one round trip of the call
+  WM_BK(bk->fill_ff_async != nullptr ? bk->fill_ff_async(a.workspace, table_bytes, stream)
+                                     : bk->memset_async(a.workspace, 0xFF, table_bytes, stream));
+  WM_BK(bk->isub_build(&a, stream));
+  WM_BK(bk->isub_count(&a, stream));
+  WM_BK(bk->exclusive_scan_i32(a.counts, offsets, n + 1, scan_ws_ptr, scan_ws, stream));
+  WM_BK(bk->stream_sync(stream));
+  const int64_t m = *a.total;
+  if (m < 0 || m >= (INT64_C(1) << 31)) {
+    WM_ERROR("the induced subgraph of these %ld nodes has %ld entries: the outputs must hold fewer than 2^31", static_cast<long>(n),
+             static_cast<long>(m));
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  a.out_col = static_cast<int*>(output_alloc(p_env_fns, output_col_memory_context, m, WHOLEMEMORY_DT_INT));
+  if (output_edge_gid_memory_context != nullptr)
+    a.out_edge_gid = static_cast<int64_t*>(output_alloc(p_env_fns, output_edge_gid_memory_context, m, WHOLEMEMORY_DT_INT64));
+  if (m > 0 && (a.out_col == nullptr || (output_edge_gid_memory_context != nullptr && a.out_edge_gid == nullptr)))
+    return WHOLEMEMORY_OUT_OF_MEMORY;
+  if (m > 0) WM_BK(bk->isub_fill(&a, stream));
+  // as the sampler: complete on return, unless the host framework has declared its allocator ordered on `stream`
+  if (drain) WM_BK(bk->stream_sync(stream));
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
 wholememory_error_code_t generate_random_positive_int_cpu(int64_t random_seed, int64_t subsequence, wholememory_tensor_t output)
 {
   WM_API_BEGIN

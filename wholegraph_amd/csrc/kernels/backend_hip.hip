@@ -109,6 +109,10 @@ int hip_negative_sample(const wm_neg_args* a, void* stream);
 int hip_edot_forward(const wm_edot_args* a, void* stream);
 size_t hip_edot_backward_workspace_bytes(const wm_edot_args* a);
 int hip_edot_backward(const wm_edot_args* a, const wm_edge_index& ix, void* workspace, void* stream);
+size_t hip_isub_workspace_bytes(int64_t n, size_t* table_bytes);
+int hip_isub_build(const wm_isub_args* a, void* stream);
+int hip_isub_count(const wm_isub_args* a, void* stream);
+int hip_isub_fill(const wm_isub_args* a, void* stream);
 
 namespace {
 
@@ -315,6 +319,10 @@ const wm_device_backend kHipBackend = {
   hip_edot_forward,
   hip_edot_backward_workspace_bytes,
   hip_edot_backward,
+  hip_isub_workspace_bytes,
+  hip_isub_build,
+  hip_isub_count,
+  hip_isub_fill,
 };
 
 }  // namespace

@@ -1,5 +1,5 @@
 // wholegraph_amd — the CSR graph of a wm_csr_graph as the kernels read it, shared by the units that do (graph.hip: the
-// samplers; walk.hip, walk_n2v.hip: the walks; neg_sample.hip): the views of the arrays with their storage offsets, filled in
+// samplers; walk.hip, walk_n2v.hip: the walks; neg_sample.hip; isub.hip): the views of the arrays with their storage offsets, filled in
 // one place, and the launchers' dispatch on the dtypes of the node ids and of csr_col_ptr.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -27,6 +27,7 @@
 #include "../backend.hpp"
 #include "../pcg.hpp"
 #include "csr_view.cuh"
+#include "id_hash.cuh"
 
 #include <mutex>
 #include <unordered_map>
@@ -828,14 +829,7 @@ au_layout<KeyT> au_plan(void* ws, int nt, int nn)
   return l;
 }
 
-__device__ __forceinline__ uint32_t au_hash(uint64_t k)
-{
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 29;
-  return static_cast<uint32_t>(k);
-}
-
+// (au_hash: id_hash.cuh, shared with the membership table of isub.hip)
 __device__ __forceinline__ uint32_t au_cas(uint32_t* a, uint32_t expect, uint32_t v) { return atomicCAS(a, expect, v); }
 __device__ __forceinline__ uint64_t au_cas(uint64_t* a, uint64_t expect, uint64_t v)
 {

@@ -178,6 +178,32 @@ class GraphStructure(object):
                                               random_seed, mode=mode, exclude_edges=exclude_edges, exclude_self=exclude_self,
                                               max_tries=max_tries, col_sorted=col_sorted)
 
+    # ------------------------------------------------------------------------------------------ subgraphs
+    def induced_subgraph(self, nodes: torch.Tensor, *, need_edge_output: bool = False,
+                         edge_attr_names: Optional[Sequence[str]] = None):
+        """Extension: every graph edge among `nodes` as one local CSR block (``wholegraph_ops.induced_subgraph``), the batch
+        of subgraph-wise training. -> offsets int32 [n + 1], col int32 [m][, edge ids int64 [m]][, {name: attribute of the kept
+        edges}]. Row i belongs to nodes[i]; col holds positions in `nodes`. edge_attr_names: the named edge attributes (or
+        "__edge_id__") at the kept edges, aligned with col."""
+        names = None if edge_attr_names is None else self._checked_edge_attr_names(edge_attr_names)
+        out = wholegraph_ops.induced_subgraph(self.csr_row_ptr.wmb_tensor, self.csr_col_ind.wmb_tensor, nodes,
+                                              need_edge_output=need_edge_output or names is not None)
+        if names is None:
+            return out
+        offsets, col, edge_id = out
+        attrs = self._edge_attr_dict(names, edge_id)
+        return (offsets, col, edge_id, attrs) if need_edge_output else (offsets, col, attrs)
+
+    def saint_random_walk_subgraph(self, roots: torch.Tensor, walk_length: int, *, random_seed: Union[int, None] = None,
+                                   weight_name: Optional[str] = None, need_edge_output: bool = False):
+        """Extension: the GraphSAINT random-walk sampler. One walk of walk_length steps from every root (``random_walk``), the
+        distinct nodes the walks visit in ascending order, and the subgraph they induce (``induced_subgraph``).
+        -> nodes, offsets int32 [n + 1], col int32 [m][, edge ids int64 [m]]. The node order, and with it the whole result,
+        depends on the roots and the seed alone. The loss-normalisation coefficients of GraphSAINT are not computed here."""
+        walks = self.random_walk(roots, walk_length, weight_name=weight_name, random_seed=random_seed)
+        nodes = torch.unique(walks[walks >= 0])     # (sorted)
+        return (nodes,) + tuple(self.induced_subgraph(nodes, need_edge_output=need_edge_output))
+
     # ------------------------------------------------------------------------------------------ several hops
     def multilayer_sample_without_replacement(self, node_ids: torch.Tensor, max_neighbors: List[int],
                                               weight_name: Union[str, None] = None, *,

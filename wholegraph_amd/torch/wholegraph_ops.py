@@ -382,6 +382,27 @@ def negative_sample(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, src_nodes_tens
     return negatives
 
 
+def induced_subgraph(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, nodes_tensor: torch.Tensor, *, need_edge_output: bool = False):
+    """Extension (wholememory_ext_csr_induced_subgraph, include/wholememory/wholegraph_amd_ext.h section 2q): every graph edge
+    among `nodes` as one local CSR block, the batch of subgraph-wise training. Returns (offsets int32 [n + 1], col int32 [m][,
+    edge ids int64 [m]]): row i lists, in the graph's order, the entries of row nodes[i] whose node occurs in `nodes`, each as
+    the lowest position it occurs at; the edge ids are their positions in csr_col_ptr. Nodes outside the graph get empty rows
+    and are never referred to; duplicates get a row each. One host round trip, for m."""
+    if nodes_tensor.dim() != 1:
+        raise ValueError("nodes_tensor must be 1-D, got %d dimensions" % nodes_tensor.dim())
+    row, col = _handle(wm_csr_row_ptr_tensor), _handle(wm_csr_col_ptr_tensor)
+    offset = torch.empty(nodes_tensor.shape[0] + 1, device=op_device(), dtype=torch.int)
+    out_col = TorchMemoryContext()
+    egid = TorchMemoryContext() if need_edge_output else None
+    wn, wo = wrap_torch_tensor(nodes_tensor), wrap_torch_tensor(offset)
+    wmb.check(wmb.lib().wholememory_ext_csr_induced_subgraph(
+        row, col, wn.handle, wo.handle, C.c_void_p(out_col.get_c_context()), C.c_void_p(egid.get_c_context() if egid else 0),
+        get_wholegraph_env_fns(), C.c_void_p(get_stream())))
+    if need_edge_output:
+        return offset, out_col.get_tensor(), egid.get_tensor()
+    return offset, out_col.get_tensor()
+
+
 def generate_random_positive_int_cpu(random_seed, sub_sequence, output_random_value_count):
     output = torch.empty((output_random_value_count,), dtype=torch.int)
     w = wrap_torch_tensor(output)

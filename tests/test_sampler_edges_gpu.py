@@ -261,9 +261,9 @@ def _weighted_structure(comm, mt, col_dtype, weights):
 @pytest.mark.parametrize("mt,center_dtype,col_dtype,fanouts", [
     ("continuous", np.int64, np.int64, WEIGHTED_FANOUTS), ("continuous", np.int32, np.int32, WEIGHTED_FANOUTS),
     ("continuous", np.int64, np.int32, WEIGHTED_SUBSET), ("continuous", np.int32, np.int64, WEIGHTED_SUBSET),
-    ("chunked", np.int64, np.int64, WEIGHTED_SUBSET)],
+    ("chunked", np.int64, np.int64, WEIGHTED_SUBSET), ("distributed", np.int32, np.int64, WEIGHTED_SUBSET)],
     ids=["continuous-i64-i64-full", "continuous-i32-i32-full", "continuous-i64-i32-subset", "continuous-i32-i64-subset",
-         "chunked-i64-i64-subset"])
+         "chunked-i64-i64-subset", "distributed-i32-i64-subset"])
 def test_weighted_ladder_equals_the_oracle(gpu_env, cls, mt, center_dtype, col_dtype, fanouts):
     import torch
     row_ptr, col, centers = ladder_graph()

@@ -277,14 +277,52 @@ def multilayer_sample(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, seed_nodes_t
     return None if pending is None else pending.finish()
 
 
+def _is_distributed(h):
+    L = wmb.lib()
+    return bool(L.wholememory_tensor_has_handle(h)) and \
+        L.wholememory_get_memory_type(C.c_void_p(L.wholememory_tensor_get_memory_handle(h))) == wmb.MT_DISTRIBUTED
+
+
+def _weighted_sample_via_gather(row, col, wgt, center_nodes_tensor, max_sample_count, random_seed):
+    """Weighted sampling where csr_row_ptr / csr_col_ptr or the weights are DISTRIBUTED, from the ops that reach such tensors.
+    The unweighted sampler with max_sample_count -1 brings every neighbour of the centres in row order (on a DISTRIBUTED graph
+    through its gather route) with its edge id; a gather brings their weights; those three arrays are a CSR graph on this
+    device whose node i is centre i, and the weighted sampler runs on it. Its keys depend on the seed, on a centre's position
+    in the batch and on a neighbour's position in its row, all unchanged, so the samples are those of a mapped graph.
+    Collective (every rank calls it, with its own centres); it moves the centres' whole rows.
+    -> (sample_offset, sampled node ids, center local id, edge id)"""
+    from .tensor import WholeMemoryTensor
+    if random_seed is None:
+        random_seed = random.getrandbits(64)
+    desc = wmb.lib().wholememory_tensor_get_tensor_description
+    if _tensor_dim(wgt) != 1 or int(desc(wgt).contents.sizes[0]) != int(desc(col).contents.sizes[0]):
+        wmb.check(6, "wm_csr_weight_ptr_tensor must have one weight per edge")      # WHOLEMEMORY_INVALID_INPUT
+    offset, neighbours, edge_id = unweighted_sample_without_replacement(row, col, center_nodes_tensor, -1, 0, False, True)
+    weights = WholeMemoryTensor(wgt).gather(edge_id)
+    n = center_nodes_tensor.shape[0]
+    if edge_id.shape[0] == 0:      # (no centre, or none with a neighbour: offset is n + 1 zeros)
+        return (offset, neighbours, torch.empty(0, device=op_device(), dtype=torch.int),
+                torch.empty(0, device=op_device(), dtype=torch.int64))
+    local = [wrap_torch_tensor(t) for t in (offset.to(torch.int64), neighbours, weights)]
+    centres = torch.arange(n, device=center_nodes_tensor.device, dtype=center_nodes_tensor.dtype)
+    offset, ids, lid, local_edge = weighted_sample_without_replacement(*[w.handle for w in local], centres, max_sample_count,
+                                                                       random_seed, True, True)
+    return offset, ids, lid, edge_id[local_edge]
+
+
 def weighted_sample_without_replacement(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_weight_ptr_tensor,
                                         center_nodes_tensor: torch.Tensor, max_sample_count: int,
                                         random_seed: Union[int, None] = None, need_center_local_output: bool = False,
                                         need_edge_output: bool = False):
     """A-Res weighted sampling: neighbours are kept with probability proportional to their edge weight
-    (wm_csr_weight_ptr_tensor: float32/float64, one per edge). max_sample_count <= 8192."""
+    (wm_csr_weight_ptr_tensor: float32/float64, one per edge). max_sample_count <= 8192.
+    A graph or weight tensor that is DISTRIBUTED (extension; the C entry point answers NOT_IMPLEMENTED) is sampled through
+    `_weighted_sample_via_gather`: a collective, the same samples as on a mapped graph."""
     row, col, wgt = _handle(wm_csr_row_ptr_tensor), _handle(wm_csr_col_ptr_tensor), _handle(wm_csr_weight_ptr_tensor)
     assert center_nodes_tensor.dim() == 1
+    if any(_is_distributed(h) for h in (row, col, wgt)):
+        out = _weighted_sample_via_gather(row, col, wgt, center_nodes_tensor, max_sample_count, random_seed)
+        return out[:2] + ((out[2],) if need_center_local_output else ()) + ((out[3],) if need_edge_output else ())
     offset = torch.empty(center_nodes_tensor.shape[0] + 1, device=op_device(), dtype=torch.int)
     dest = TorchMemoryContext()
     lid = TorchMemoryContext() if need_center_local_output else None

@@ -34,6 +34,8 @@
  *      over the walks and negatives above and of link prediction (forward and a deterministic backward).
  *      (2q) the node-induced subgraph of a CSR graph held in WholeMemory: all graph edges among a set of nodes as one local
  *      block, the batch of subgraph-wise training (GraphSAINT, ShaDow-GNN, Cluster-GCN).
+ *      (2r) temporal neighbour sampling over the same graph with a timestamp per edge: per (node, time) centre, up to M
+ *      neighbours whose edge is not in the centre's future, uniformly or the latest (TGN, TGAT).
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -1371,6 +1373,72 @@ enum wholememory_error_code_t wholememory_ext_csr_induced_subgraph(
   wholememory_tensor_t output_offset_tensor, /* int32, at least n + 1 entries, device */
   void* output_col_memory_context,           /* int32 [m]: local positions */
   void* output_edge_gid_memory_context,      /* int64 [m] or NULL: positions in csr_col_ptr */
+  wholememory_env_func_t* p_env_fns,
+  void* stream);
+
+/* ---- (2r) temporal neighbour sampling over a CSR graph held in WholeMemory ------------------------------------------------- */
+/* The sampler of a model that trains on an interaction graph (TGN, TGAT; PyG's NeighborLoader with time_attr): a centre is a
+ * node WITH a time, and only edges that are not in that time's future may be aggregated. For centre i the op returns the
+ * neighbours of center_nodes[i] whose edge time passes the rule below against center_times[i], at most max_sample_count of
+ * them. Graph tensors are as (2m): row_ptr int64 [n_nodes + 1], col_ind int32 or int64 [n_edges], and edge_time int64
+ * [n_edges], one entry per edge position; all three CONTINUOUS or CHUNKED, in device or host memory, or plain device arrays
+ * wrapped with wholememory_make_tensor_from_pointer. center_nodes is int32 or int64 [n], center_times int64 [n], both on the
+ * device. The outputs follow the samplers: output_offset_tensor is the caller's, int32 with at least n + 1 entries, on the
+ * device; dest (col_ind's dtype) and, with a context for them, center_localid int32 and edge_gid int64 are allocated through
+ * p_env_fns once the total is known.
+ *
+ * Row of centre i, with u = center_nodes[i] and t = center_times[i]:
+ *   - the row is empty when u is outside [0, n_nodes);
+ *   - the row is empty when (s, e) = (row_ptr[u], row_ptr[u + 1]) does not satisfy 0 <= s <= e <= n_edges and e - s < 2^31
+ *     (the rule of (2o) and (2q));
+ *   - a col_ind entry is copied, never used as an index.
+ * Eligibility. Neighbour j sits at position s + j, with ts = edge_time[s + j]. It is eligible when both hold:
+ *   - ts <= t when inclusive != 0, ts < t when inclusive == 0;
+ *   - time_window < 0, or (uint64)t - (uint64)ts <= (uint64)time_window. With ts <= t that difference is the exact distance
+ *     of any two int64 values: there is no overflow case.
+ * E_i is the number of eligible neighbours of centre i.
+ * Counts. c_i = E_i when max_sample_count <= 0 (every eligible neighbour), else c_i = min(E_i, M) with M = max_sample_count.
+ * M > 64 is INVALID_INPUT: the selection holds its M candidates in the registers of one wave. offsets is the exclusive prefix
+ * of the c_i, offsets[n] the total.
+ * Selection when E_i > M.
+ *   - strategy 0 (uniform without replacement): r(i, j) is the first 32-bit output of stream(seed, i, j + 1) of (2m). The M
+ *     eligible neighbours with the largest composite (uint64(r) << 32) | (0xFFFFFFFF - j) are chosen: the largest draws, ties to
+ *     the lowest j. An ineligible neighbour draws nothing and shifts no one else's draw.
+ *   - strategy 1 (last): the M eligible neighbours with the largest ts, ties to the lowest j.
+ * Output order. Within a centre the output is in ascending j, whatever the strategy and whether or not a selection took place;
+ * for a row stored in time order that is chronological order. center_localid[k] = i, edge_gid[k] = s + j. The result depends
+ * on (seed, i, j), the graph and the times only, not on n or on the launch geometry: the rows of the first 100 centres of a
+ * batch of 512 equal a batch of those 100.
+ *
+ * The call makes one host round trip, for the total: the count is queued, the stream is synchronised, the outputs are
+ * allocated, the selection is queued. It then returns with the outputs complete, or, after
+ * wholememory_ext_set_async_completion(1), with the selection queued on `stream`, exactly as the samplers do.
+ *
+ * Errors, in this order; all but the last are answered before any device work. INVALID_INPUT: a NULL row_ptr, col_ind,
+ * edge_time, center_nodes, center_times, offset tensor, p_env_fns or output_dest_memory_context; one of the six tensors not
+ * 1-D; max_sample_count > 64; strategy not 0 or 1; n >= 2^31 - 1; edge_time not one entry per edge; center_times not n
+ * entries; an offset tensor with fewer than n + 1 entries. LOGIC_ERROR: row_ptr not int64, col_ind or center_nodes not int32 /
+ * int64, edge_time or center_times not int64, offsets not int32. INVALID_INPUT for a HIERARCHY tensor. NOT_IMPLEMENTED for a
+ * DISTRIBUTED tensor: Python composes that route (the all-neighbour sampler brings the centres' rows with their edge ids, a
+ * gather their times, and this op runs on them as a device CSR with centres 0 .. n - 1, which preserves i and j and so the
+ * samples). NOT_SUPPORTED, nothing queued, when the device backend has no such kernels. INVALID_INPUT when the total is
+ * >= 2^31, reachable with max_sample_count <= 0 only: answered after the count, with no output allocated. n = 0 succeeds: it
+ * writes offsets[0] = 0 and allocates empty outputs. */
+enum wholememory_error_code_t wholememory_ext_csr_temporal_sample(
+  wholememory_tensor_t wm_csr_row_ptr_tensor,
+  wholememory_tensor_t wm_csr_col_ptr_tensor,
+  wholememory_tensor_t wm_csr_edge_time_tensor, /* int64, one entry per edge */
+  wholememory_tensor_t center_nodes_tensor,     /* [n] int32 / int64, device */
+  wholememory_tensor_t center_times_tensor,     /* [n] int64, device */
+  int max_sample_count,                         /* <= 0: every eligible neighbour, else at most 64 */
+  int strategy,                                 /* 0: uniform, 1: last */
+  int inclusive,
+  long long time_window,                        /* < 0: none */
+  unsigned long long random_seed,
+  wholememory_tensor_t output_offset_tensor,    /* int32, at least n + 1 entries, device */
+  void* output_dest_memory_context,             /* col_ind's dtype [total] */
+  void* output_center_localid_memory_context,   /* int32 [total] or NULL */
+  void* output_edge_gid_memory_context,         /* int64 [total] or NULL: positions in csr_col_ptr */
   wholememory_env_func_t* p_env_fns,
   void* stream);
 

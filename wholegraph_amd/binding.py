@@ -286,6 +286,8 @@ PROTOTYPES = {
     "wholememory_ext_csr_node2vec_walk": (_i, [_vp, _vp, _vp, _vp, _i, C.c_float, C.c_float, _i, C.c_ulonglong, _vp, _vp, _vp]),
     "wholememory_ext_csr_negative_sample": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_ulonglong, _vp, _vp]),
     "wholememory_ext_csr_induced_subgraph": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _P(EnvFunc), _vp]),
+    "wholememory_ext_csr_temporal_sample": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, C.c_longlong, C.c_ulonglong, _vp, _vp, _vp,
+                                                _vp, _P(EnvFunc), _vp]),
     "wholememory_ext_csc_aggregate_forward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i, _vp, _i64, _P(EnvFunc),
                                                   _vp]),
     "wholememory_ext_csc_aggregate_backward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i, _vp, _i64, _P(EnvFunc),

@@ -125,6 +125,9 @@ struct wm_csr_graph {
   wholememory_gref_t weight_gref;
   int64_t weight_storage_offset;
   wholememory_dtype_t weight_dtype;
+  // optional per-edge timestamps (int64), same indexing as csr_col_ptr; an empty time_gref where the call has none
+  wholememory_gref_t time_gref;
+  int64_t time_storage_offset;
 };
 
 // neighbour sampling on such a graph (the weights: sample_weighted only)
@@ -502,6 +505,28 @@ struct wm_isub_args : wm_csr_graph {
   int64_t* out_edge_gid;  // [total] positions in csr_col_ptr, or nullptr
 };
 
+// temporal neighbour sampling on such a graph (kernels/tsample.hip, wholegraph_amd_ext.h section 2r; the weights stay empty, the
+// timestamps are set): per centre i the neighbours of centers[i] whose timestamp passes the rule against center_times[i], at
+// most max_sample_count of them, in row order. Two steps around the host learning the size: count, select
+struct wm_tsample_args : wm_csr_graph {
+  const void* centers;          // [n] device
+  wholememory_dtype_t center_dtype;
+  const int64_t* center_times;  // [n] device
+  int64_t n;                    // centres; 0 < n < 2^31 - 1
+  int max_sample_count;         // <= 0: every eligible neighbour; at most 64
+  int strategy;                 // 0: uniform without replacement; 1: the latest
+  int inclusive;                // non-zero: ts <= t is eligible, else ts < t
+  int64_t time_window;          // < 0: none
+  uint64_t random_seed;
+  void* workspace;              // tsample_workspace_bytes(n) bytes
+  int* counts;                  // [n + 1] device: entries per centre, counts[n] = 0 (written by count)
+  int64_t* total;               // one word the device can write (pinned or device): the sum of counts in 64 bits (written by count)
+  const int* offsets;           // [n + 1] device: exclusive prefix of counts (read by select)
+  void* out_ids;                // [total] col_dtype
+  int* out_center_lid;          // [total] or nullptr
+  int64_t* out_edge_gid;        // [total] or nullptr
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -783,6 +808,11 @@ struct wm_device_backend {
   int (*isub_build)(const wm_isub_args* a, void* stream);
   int (*isub_count)(const wm_isub_args* a, void* stream);
   int (*isub_fill)(const wm_isub_args* a, void* stream);
+  // ---- temporal neighbour sampling (kernels/tsample.hip, wholegraph_amd_ext.h section 2r); nullptr in a backend without it ----
+  // count writes a->counts and a->total (its partial sums go through the workspace), select the outputs
+  size_t (*tsample_workspace_bytes)(int64_t n);
+  int (*tsample_count)(const wm_tsample_args* a, void* stream);
+  int (*tsample_select)(const wm_tsample_args* a, void* stream);
 };
 
 }  // extern "C"

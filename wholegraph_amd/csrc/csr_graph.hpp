@@ -1,9 +1,11 @@
 // wholegraph_amd — what the ops over the WholeMemory CSR graph share on the host (graph_ops.cpp: the two samplers, the fused
-// hop, the multi-hop chain, the random walks, the node2vec walks, negative sampling, the induced subgraph): the graph tensors of
+// hop, the multi-hop chain, the random walks, the node2vec walks, negative sampling, the induced subgraph, the temporal sampler):
+// the graph tensors of
 // one call, checked, and the one place that turns them into the backend's wm_csr_graph. The checks are separate steps because
 // every entry point keeps its own ORDER of answers (the samplers judge placement before dtypes before sizes, as the reference
-// does; the walks, the negatives and the induced subgraph judge shapes and sizes before dtypes before placement:
-// wholegraph_amd_ext.h sections 2m - 2o and 2q), and a call with two faults gets the answer of the step its entry makes first.
+// does; the walks, the negatives, the induced subgraph and the temporal sampler judge shapes and sizes before dtypes before
+// placement: wholegraph_amd_ext.h sections 2m - 2o, 2q and 2r), and a call with two faults gets the answer of the step its entry
+// makes first.
 #pragma once
 
 #include <initializer_list>
@@ -57,7 +59,7 @@ inline csr_placement placement_of(std::initializer_list<wholememory_tensor_t> te
   return worst;
 }
 
-enum class csr_tensors { row_col, weights, all };   // which of a graph's tensors a placement step judges
+enum class csr_tensors { row_col, weights, all, row_col_time };   // which of a graph's tensors a placement step judges
 
 // The graph tensors of one call. Every step answers SUCCESS or what is wrong; the plain ops report it (the code the step
 // names, with a message), the fused hop and the chain DECLINE it (`declines`: NOT_SUPPORTED, no message — the caller takes
@@ -65,7 +67,9 @@ enum class csr_tensors { row_col, weights, all };   // which of a graph's tensor
 struct checked_graph {
   wholememory_tensor_t row, col, weight;   // weight: nullptr when the call has no weights
   bool declines;
-  wholememory_array_description_t row_desc{}, col_desc{}, weight_desc{};
+  // per-edge timestamps, set by name after the braces (`g.time = ...`) by the one entry that has them: nullptr otherwise
+  wholememory_tensor_t time = nullptr;
+  wholememory_array_description_t row_desc{}, col_desc{}, weight_desc{}, time_desc{};
 
 #define WM_CSR_ANSWER(code, ...)                          \
   do {                                                    \
@@ -88,7 +92,20 @@ struct checked_graph {
     return array_of(weight, "wm_csr_weight_ptr_tensor", &weight_desc, &err) ? WHOLEMEMORY_SUCCESS : err;
   }
 
+  wholememory_error_code_t time_array()
+  {
+    wholememory_error_code_t err = WHOLEMEMORY_SUCCESS;
+    return array_of(time, "wm_csr_edge_time_tensor", &time_desc, &err) ? WHOLEMEMORY_SUCCESS : err;
+  }
+
   // (b)
+  wholememory_error_code_t one_time_per_edge() const
+  {
+    if (time_desc.size != col_desc.size)
+      WM_CSR_ANSWER(WHOLEMEMORY_INVALID_INPUT, "wm_csr_edge_time_tensor must have one timestamp per edge (%ld vs %ld)",
+                    static_cast<long>(time_desc.size), static_cast<long>(col_desc.size));
+    return WHOLEMEMORY_SUCCESS;
+  }
   wholememory_error_code_t one_weight_per_edge() const
   {
     if (weight_desc.size != col_desc.size)
@@ -118,13 +135,21 @@ struct checked_graph {
     return WHOLEMEMORY_SUCCESS;
   }
 
+  wholememory_error_code_t time_dtype() const
+  {
+    if (time_desc.dtype != WHOLEMEMORY_DT_INT64)
+      WM_CSR_ANSWER(WHOLEMEMORY_LOGIC_ERROR, "wm_csr_edge_time_tensor must be int64, got %d", static_cast<int>(time_desc.dtype));
+    return WHOLEMEMORY_SUCCESS;
+  }
+
   // (d) HIERARCHY is INVALID_INPUT. DISTRIBUTED is the caller's where it has a gather route (*via_gather says whether to
   // take it), else NOT_IMPLEMENTED with the caller's sentence
   wholememory_error_code_t placement(csr_tensors which, const char* no_route, bool* via_gather = nullptr) const
   {
-    const csr_placement p = which == csr_tensors::row_col   ? placement_of({row, col})
-                            : which == csr_tensors::weights ? placement_of({weight})
-                                                            : placement_of({row, col, weight});
+    const csr_placement p = which == csr_tensors::row_col        ? placement_of({row, col})
+                            : which == csr_tensors::weights      ? placement_of({weight})
+                            : which == csr_tensors::row_col_time ? placement_of({row, col, time})
+                                                                 : placement_of({row, col, weight});
     if (p == csr_placement::hierarchy) WM_CSR_ANSWER(WHOLEMEMORY_INVALID_INPUT, "Memory type not supported.");
     if (via_gather != nullptr) {
       *via_gather = p == csr_placement::distributed;
@@ -152,6 +177,10 @@ struct checked_graph {
       WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(weight, &g->weight_gref));
       g->weight_storage_offset = weight_desc.storage_offset;
       g->weight_dtype          = weight_desc.dtype;
+    }
+    if (time != nullptr) {
+      WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(time, &g->time_gref));
+      g->time_storage_offset = time_desc.storage_offset;
     }
     return WHOLEMEMORY_SUCCESS;
   }

@@ -22,6 +22,7 @@
 #include "neg_sample.hpp"
 #include "ops_internal.hpp"
 #include "pcg.hpp"
+#include "tsample.hpp"
 #include "walk_n2v.hpp"
 
 namespace {
@@ -506,6 +507,129 @@ wholememory_error_code_t wholememory_ext_csr_induced_subgraph(
   if (m > 0 && (a.out_col == nullptr || (output_edge_gid_memory_context != nullptr && a.out_edge_gid == nullptr)))
     return WHOLEMEMORY_OUT_OF_MEMORY;
   if (m > 0) WM_BK(bk->isub_fill(&a, stream));
+  // as the sampler: complete on return, unless the host framework has declared its allocator ordered on `stream`
+  if (drain) WM_BK(bk->stream_sync(stream));
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+// Temporal neighbour sampling (extension, wholegraph_amd_ext.h section 2r; kernels/tsample.hip): per centre, the neighbours whose
+// edge time passes the rule against the centre's time, at most max_sample_count of them. The flow of the induced subgraph:
+// count per centre, scan into the caller's offsets, ONE host round trip for the size, outputs from the caller's allocator,
+// select. Every answer about the arguments comes before any device work; the answer about the size (2^31 entries or more,
+// reachable with max_sample_count <= 0 only) comes after the count, with no output allocated.
+wholememory_error_code_t wholememory_ext_csr_temporal_sample(
+  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor, wholememory_tensor_t wm_csr_edge_time_tensor,
+  wholememory_tensor_t center_nodes_tensor, wholememory_tensor_t center_times_tensor, int max_sample_count, int strategy,
+  int inclusive, long long time_window, unsigned long long random_seed, wholememory_tensor_t output_offset_tensor,
+  void* output_dest_memory_context, void* output_center_localid_memory_context, void* output_edge_gid_memory_context,
+  wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  if (p_env_fns == nullptr || output_dest_memory_context == nullptr) return WHOLEMEMORY_INVALID_INPUT;
+  wholememory_error_code_t err = WHOLEMEMORY_SUCCESS;
+  checked_graph g{wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, nullptr, false};
+  g.time = wm_csr_edge_time_tensor;
+  wholememory_array_description_t center_desc, ctime_desc, offset_desc;
+  WHOLEMEMORY_RETURN_ON_FAIL(g.arrays());
+  WHOLEMEMORY_RETURN_ON_FAIL(g.time_array());
+  if (!array_of(center_nodes_tensor, "center_nodes_tensor", &center_desc, &err)) return err;
+  if (!array_of(center_times_tensor, "center_times_tensor", &ctime_desc, &err)) return err;
+  if (!array_of(output_offset_tensor, "output_offset_tensor", &offset_desc, &err)) return err;
+  if (!wm::ts_scalars_ok(max_sample_count, strategy)) {
+    WM_ERROR("max_sample_count must be at most %d and strategy 0 (uniform) or 1 (last), got %d and %d", wm::kTsampleMaxFanout,
+             max_sample_count, strategy);
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  const int64_t n = center_desc.size;
+  if (g.row_desc.size < 1) {
+    WM_ERROR("wm_csr_row_ptr_tensor has no entry: a graph of n_nodes nodes has n_nodes + 1");
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  if (n < 0 || n >= (INT64_C(1) << 31) - 1) {
+    WM_ERROR("%ld centres: a batch must have fewer than 2^31 - 1", static_cast<long>(n));
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  WHOLEMEMORY_RETURN_ON_FAIL(g.one_time_per_edge());
+  if (ctime_desc.size != n) {
+    WM_ERROR("center_times_tensor must have one time per centre (%ld vs %ld)", static_cast<long>(ctime_desc.size), static_cast<long>(n));
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  if (offset_desc.size < n + 1) {
+    WM_ERROR("output_offset_tensor needs %ld entries, has %ld", static_cast<long>(n + 1), static_cast<long>(offset_desc.size));
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  WHOLEMEMORY_RETURN_ON_FAIL(g.row_dtype());
+  WHOLEMEMORY_RETURN_ON_FAIL(g.col_and_id_dtype(center_desc.dtype, "center nodes"));
+  WHOLEMEMORY_RETURN_ON_FAIL(g.time_dtype());
+  if (ctime_desc.dtype != WHOLEMEMORY_DT_INT64) {
+    WM_ERROR("center_times_tensor must be int64, got %d", static_cast<int>(ctime_desc.dtype));
+    return WHOLEMEMORY_LOGIC_ERROR;
+  }
+  if (offset_desc.dtype != WHOLEMEMORY_DT_INT) {
+    WM_ERROR("output_offset_tensor must be int32, got %d", static_cast<int>(offset_desc.dtype));
+    return WHOLEMEMORY_LOGIC_ERROR;
+  }
+  WHOLEMEMORY_RETURN_ON_FAIL(g.placement(
+    csr_tensors::row_col_time,
+    "temporal sampling on DISTRIBUTED tensors is not implemented here: Python composes the route from the all-neighbour sampler, "
+    "a gather of the times and this op on the gathered rows (wholegraph_ops.temporal_sample_without_replacement)"));
+  const auto* bk = backend();
+  if (bk->tsample_workspace_bytes == nullptr || bk->tsample_count == nullptr || bk->tsample_select == nullptr ||
+      bk->exclusive_scan_i32 == nullptr)
+    return WHOLEMEMORY_NOT_SUPPORTED;
+  int* offsets = static_cast<int*>(wholememory_tensor_get_data_pointer(output_offset_tensor));
+  if (offsets == nullptr) return WHOLEMEMORY_INVALID_INPUT;
+  const bool drain = !async_completion_enabled() || debug_sync_enabled();
+  if (n == 0) {
+    WM_BK(bk->memset_async(offsets, 0, sizeof(int), stream));
+    (void)output_alloc(p_env_fns, output_dest_memory_context, 0, g.col_desc.dtype);
+    if (output_center_localid_memory_context != nullptr) (void)output_alloc(p_env_fns, output_center_localid_memory_context, 0, WHOLEMEMORY_DT_INT);
+    if (output_edge_gid_memory_context != nullptr) (void)output_alloc(p_env_fns, output_edge_gid_memory_context, 0, WHOLEMEMORY_DT_INT64);
+    if (drain) WM_BK(bk->stream_sync(stream));
+    return WHOLEMEMORY_SUCCESS;
+  }
+  wm_tsample_args a{};
+  WHOLEMEMORY_RETURN_ON_FAIL(g.fill(&a));
+  a.centers          = wholememory_tensor_get_data_pointer(center_nodes_tensor);
+  a.center_dtype     = center_desc.dtype;
+  a.center_times     = static_cast<const int64_t*>(wholememory_tensor_get_data_pointer(center_times_tensor));
+  a.n                = n;
+  a.max_sample_count = max_sample_count;
+  a.strategy         = strategy;
+  a.inclusive        = inclusive;
+  a.time_window      = time_window;
+  a.random_seed      = random_seed;
+  a.offsets          = offsets;
+  if (a.centers == nullptr || a.center_times == nullptr) return WHOLEMEMORY_INVALID_INPUT;
+
+  temp_mem ws_mem(p_env_fns), counts_mem(p_env_fns), scan_mem(p_env_fns), host_mem(p_env_fns);
+  a.workspace          = ws_mem.device(static_cast<int64_t>(bk->tsample_workspace_bytes(n)), WHOLEMEMORY_DT_INT8);
+  a.counts             = static_cast<int*>(counts_mem.device(n + 1, WHOLEMEMORY_DT_INT));
+  const size_t scan_ws = bk->scan_i32_workspace_bytes(n + 1);
+  void* scan_ws_ptr    = scan_mem.device(static_cast<int64_t>(scan_ws), WHOLEMEMORY_DT_INT8);
+  a.total              = static_cast<int64_t*>(host_mem.pinned(1, WHOLEMEMORY_DT_INT64));   // written by the count's last kernel
+  if (a.workspace == nullptr || a.counts == nullptr || scan_ws_ptr == nullptr || a.total == nullptr) return WHOLEMEMORY_OUT_OF_MEMORY;
+
+  // centres counted, offsets, and the 64-bit total on the host: the one round trip of the call
+  WM_BK(bk->tsample_count(&a, stream));
+  WM_BK(bk->exclusive_scan_i32(a.counts, offsets, n + 1, scan_ws_ptr, scan_ws, stream));
+  WM_BK(bk->stream_sync(stream));
+  const int64_t m = *a.total;
+  if (m < 0 || m >= (INT64_C(1) << 31)) {
+    WM_ERROR("the temporal sample of these %ld centres has %ld entries: the outputs must hold fewer than 2^31", static_cast<long>(n),
+             static_cast<long>(m));
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  a.out_ids = output_alloc(p_env_fns, output_dest_memory_context, m, a.col_dtype);
+  if (output_center_localid_memory_context != nullptr)
+    a.out_center_lid = static_cast<int*>(output_alloc(p_env_fns, output_center_localid_memory_context, m, WHOLEMEMORY_DT_INT));
+  if (output_edge_gid_memory_context != nullptr)
+    a.out_edge_gid = static_cast<int64_t*>(output_alloc(p_env_fns, output_edge_gid_memory_context, m, WHOLEMEMORY_DT_INT64));
+  if (m > 0 && (a.out_ids == nullptr || (output_center_localid_memory_context != nullptr && a.out_center_lid == nullptr) ||
+                (output_edge_gid_memory_context != nullptr && a.out_edge_gid == nullptr)))
+    return WHOLEMEMORY_OUT_OF_MEMORY;
+  if (m > 0) WM_BK(bk->tsample_select(&a, stream));
   // as the sampler: complete on return, unless the host framework has declared its allocator ordered on `stream`
   if (drain) WM_BK(bk->stream_sync(stream));
   return WHOLEMEMORY_SUCCESS;

@@ -113,6 +113,9 @@ size_t hip_isub_workspace_bytes(int64_t n, size_t* table_bytes);
 int hip_isub_build(const wm_isub_args* a, void* stream);
 int hip_isub_count(const wm_isub_args* a, void* stream);
 int hip_isub_fill(const wm_isub_args* a, void* stream);
+size_t hip_tsample_workspace_bytes(int64_t n);
+int hip_tsample_count(const wm_tsample_args* a, void* stream);
+int hip_tsample_select(const wm_tsample_args* a, void* stream);
 
 namespace {
 
@@ -323,6 +326,9 @@ const wm_device_backend kHipBackend = {
   hip_isub_build,
   hip_isub_count,
   hip_isub_fill,
+  hip_tsample_workspace_bytes,
+  hip_tsample_count,
+  hip_tsample_select,
 };
 
 }  // namespace

@@ -1,5 +1,5 @@
 // wholegraph_amd — the CSR graph of a wm_csr_graph as the kernels read it, shared by the units that do (graph.hip: the
-// samplers; walk.hip, walk_n2v.hip: the walks; neg_sample.hip; isub.hip): the views of the arrays with their storage offsets, filled in
+// samplers; walk.hip, walk_n2v.hip: the walks; neg_sample.hip; isub.hip; tsample.hip): the views of the arrays with their storage offsets, filled in
 // one place, and the launchers' dispatch on the dtypes of the node ids and of csr_col_ptr.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -48,6 +48,14 @@ __device__ __forceinline__ bool csr_group_scan(const csr_view& g, int64_t s, int
   }
   return found;
 }
+
+struct csr_times {
+  gref_view time_ptr;
+  int64_t time_off;  // storage offset (elements)
+};
+
+// (an empty time_gref gives an empty view: only the temporal sampler reads it)
+inline csr_times csr_times_of(const wm_csr_graph& g) { return {make_view(g.time_gref), g.time_storage_offset}; }
 
 // f(IdT(), ColT()) with the integer types of the caller's node ids and of csr_col_ptr; -1 (nothing queued) for a dtype that
 // is neither int32 nor int64

@@ -28,6 +28,7 @@
 #include "../pcg.hpp"
 #include "csr_view.cuh"
 #include "id_hash.cuh"
+#include "top_merge.cuh"
 
 #include <mutex>
 #include <unordered_map>
@@ -660,29 +661,7 @@ __global__ __launch_bounds__(64) void sample_weighted_kernel(weighted_params w)
 // composite keys in descending order are a function of the key SET alone, so the output equals sample_weighted_kernel's
 // position for position. Stream / draw of a neighbour as there: lane gl plays the virtual threads gl, gl + G, ... < 128, each
 // a PCG stream of its own that serves neighbours vt, vt + 128, ...
-template <int G>
-__device__ __forceinline__ uint64_t top_merge(uint64_t top, uint64_t b, int gl)
-{
-  using u64 = unsigned long long;
-#pragma unroll
-  for (int k = 2; k <= G; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const uint64_t o    = __shfl_xor(static_cast<u64>(b), j, 64);
-      const bool keep_max = ((gl & k) == 0) == ((gl & j) == 0);   // descending where (gl & k) == 0; k == G: everywhere
-      b                   = keep_max ? max(b, o) : min(b, o);
-    }
-  }
-  const uint64_t r = __shfl_xor(static_cast<u64>(b), G - 1, 64);   // the batch in ascending order
-  top              = max(top, r);
-#pragma unroll
-  for (int j = G >> 1; j > 0; j >>= 1) {
-    const uint64_t o = __shfl_xor(static_cast<u64>(top), j, 64);
-    top              = (gl & j) == 0 ? max(top, o) : min(top, o);
-  }
-  return top;
-}
-
+// (top_merge<G>: top_merge.cuh, shared with the temporal sampler of tsample.hip)
 template <typename IdT, typename ColT, typename WT, int G>
 __global__ __launch_bounds__(kBlock) void sample_weighted_small_kernel(weighted_params w)
 {

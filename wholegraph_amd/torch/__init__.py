@@ -15,13 +15,15 @@ WholeMemory table, and ``quantized``, 8-bit row-quantized tables whose gather de
 ``edge_dot.edge_dot_n2n``, the score of an edge as the dot product of its endpoint rows, with ``skipgram.skipgram_block`` and
 the ``node2vec.Node2Vec`` model that train embeddings on the walks and negatives of ``GraphStructure``; and
 ``saint.SubgraphGNNModel``, the layers above on the induced subgraphs of ``GraphStructure.induced_subgraph`` and
-``GraphStructure.saint_random_walk_subgraph``: subgraph-wise training). GAT in
+``GraphStructure.saint_random_walk_subgraph``: subgraph-wise training; and ``temporal.TimeEncoder`` and
+``temporal.TemporalGNNModel``, ``EdgeGATConv`` layers over the temporal trees of ``GraphStructure.multilayer_temporal_sample``,
+whose edges never lie in their centre's future). GAT in
 ``HomoGNNModel``, the dgl / pyg / wg routes, data loaders, launch helpers and option parsers of the reference are outside this build's scope.
 """
 from . import comm, embedding, graph_ops, graph_structure, initialize, tensor, utils, wholegraph_ops, wholememory_ops
 from . import aggregation, cugraphops, edge_gat_aggregation, gat_aggregation, gather_aggregation, gnn_model
 from . import gatv2_aggregation, pna_aggregation, quantized, rel_aggregation, transformer_aggregation, weighted_aggregation
-from . import edge_dot, node2vec, saint, skipgram
+from . import edge_dot, node2vec, saint, skipgram, temporal
 
 _PUBLIC = {
     comm: ("WholeMemoryCommunicator create_group_communicator destroy_communicator get_global_communicator "
@@ -43,12 +45,13 @@ _PUBLIC = {
     skipgram: "skipgram_block centers_of",
     node2vec: "Node2Vec",
     saint: "SubgraphGNNModel",
+    temporal: "TimeEncoder TemporalGNNModel",
     quantized: ("WholeMemoryQuantizedTensor create_quantized_tensor quantized_row_bytes quantize_rows "
                 "dequantize_rows"),
 }
 __all__ = ["graph_ops", "wholegraph_ops", "aggregation", "cugraphops", "gat_aggregation", "gnn_model", "weighted_aggregation",
            "gather_aggregation", "edge_gat_aggregation", "gatv2_aggregation", "rel_aggregation", "quantized",
-           "transformer_aggregation", "pna_aggregation", "edge_dot", "skipgram", "node2vec", "saint"]
+           "transformer_aggregation", "pna_aggregation", "edge_dot", "skipgram", "node2vec", "saint", "temporal"]
 for _module, _names in _PUBLIC.items():
     for _name in _names.split():
         globals()[_name] = getattr(_module, _name)

@@ -204,6 +204,70 @@ class GraphStructure(object):
         nodes = torch.unique(walks[walks >= 0])     # (sorted)
         return (nodes,) + tuple(self.induced_subgraph(nodes, need_edge_output=need_edge_output))
 
+    # ------------------------------------------------------------------------------------------ temporal sampling
+    def _edge_times(self, time_name: str):
+        assert time_name in self.edge_attributes, "no edge attribute named %r" % time_name
+        times = self.edge_attributes[time_name]
+        assert times.dim() == 1 and times.dtype == torch.int64, "edge attribute %r must be 1-D int64 timestamps" % time_name
+        return times
+
+    def temporal_sample_one_hop(self, time_name: str, center_nodes_tensor: torch.Tensor, center_times_tensor: torch.Tensor,
+                                max_sample_count: int, *, strategy: str = "uniform", inclusive: bool = True,
+                                time_window: Union[int, None] = None, random_seed: Union[int, None] = None,
+                                need_center_local_output: bool = False, need_edge_output: bool = False):
+        """Extension: for centre i, the node center_nodes_tensor[i] at the time center_times_tensor[i], up to max_sample_count
+        neighbours whose edge is not in that time's future (``wholegraph_ops.temporal_sample_without_replacement``);
+        `time_name` names the int64 edge attribute that holds the edge times.
+        -> csr_row_ptr, sampled_nodes[, center_node_local_id][, edge_index]"""
+        return wholegraph_ops.temporal_sample_without_replacement(
+            self.csr_row_ptr.wmb_tensor, self.csr_col_ind.wmb_tensor, self._edge_times(time_name).wmb_tensor, center_nodes_tensor,
+            center_times_tensor, max_sample_count, random_seed, need_center_local_output, need_edge_output, strategy=strategy,
+            inclusive=inclusive, time_window=time_window)
+
+    def multilayer_temporal_sample(self, node_ids: torch.Tensor, node_times: torch.Tensor, max_neighbors: List[int],
+                                   time_name: str, *, strategy: str = "uniform", inclusive: bool = True,
+                                   time_window: Union[int, None] = None, propagate: str = "seed",
+                                   random_seeds: Optional[Sequence[int]] = None,
+                                   edge_attr_names: Optional[Sequence[str]] = None):
+        """Extension: len(max_neighbors) temporal hops outwards from the (node, time) seeds, sampled as DISJOINT TREES, which
+        is what temporal sampling requires (PyG's NeighborLoader with time_attr): the same node reached under two different
+        times is two computational nodes, so nothing is de-duplicated. Hop h has the centres C_h at the times T_h, C_0 =
+        node_ids; C_{h+1} = cat(C_h, neighbours_h) and T_{h+1} = cat(T_h, inherited), where a neighbour inherits the time of
+        its centre (propagate="seed", the PyG rule) or the time of the edge that led to it ("edge", the TGAT rule: a deeper
+        edge is never later than the edge above it). The block of hop h is csr_row_ptr = the sampler's offsets and csr_col_ind
+        = len(C_h) + arange(E_h) in int32. Returns lists indexed by layer, OUTERMOST layer first, as
+        multilayer_sample_without_replacement does: target_gids and target_times (hops + 1 entries, the last ones node_ids and
+        node_times), edge_indice [2, E_h] (row 0 the position of the neighbour, row 1 of its centre, in target_gids[i]),
+        csr_row_ptr, csr_col_ind, edge_ids (int64 positions in the graph's csr_col_ind) and, with edge_attr_names, the
+        attribute dicts of multilayer_sample_with_edge_attributes."""
+        if propagate not in ("seed", "edge"):
+            raise ValueError("propagate must be 'seed' or 'edge', got %r" % (propagate,))
+        hops = len(max_neighbors)
+        if random_seeds is not None:
+            assert len(random_seeds) == hops, "one seed per hop"
+        names = None if edge_attr_names is None else self._checked_edge_attr_names(edge_attr_names)
+        times = self._edge_times(time_name)
+        gids, gtimes = [node_ids], [node_times]
+        edge_indice, row_ptrs, col_inds, edge_ids, attrs = [], [], [], [], []
+        for depth, fanout in enumerate(max_neighbors):          # depth 0 = next to the seeds = layer hops - 1
+            centres, centre_times = gids[0], gtimes[0]
+            offsets, neighbours, centre_lid, edge_id = self.temporal_sample_one_hop(
+                time_name, centres, centre_times, fanout, strategy=strategy, inclusive=inclusive, time_window=time_window,
+                random_seed=None if random_seeds is None else random_seeds[depth], need_center_local_output=True,
+                need_edge_output=True)
+            inherited = centre_times[centre_lid.long()] if propagate == "seed" else times.gather(edge_id)
+            col = centres.shape[0] + torch.arange(neighbours.shape[0], device=neighbours.device, dtype=torch.int32)
+            gids.insert(0, torch.cat([centres, neighbours.to(centres.dtype)]))
+            gtimes.insert(0, torch.cat([centre_times, inherited]))
+            edge_indice.insert(0, torch.stack([col, centre_lid]))
+            row_ptrs.insert(0, offsets)
+            col_inds.insert(0, col)
+            edge_ids.insert(0, edge_id)
+            if names is not None:
+                attrs.insert(0, self._edge_attr_dict(names, edge_id))
+        out = (gids, gtimes, edge_indice, row_ptrs, col_inds, edge_ids)
+        return out if names is None else out + (attrs,)
+
     # ------------------------------------------------------------------------------------------ several hops
     def multilayer_sample_without_replacement(self, node_ids: torch.Tensor, max_neighbors: List[int],
                                               weight_name: Union[str, None] = None, *,

@@ -441,6 +441,100 @@ def induced_subgraph(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, nodes_tensor:
     return offset, out_col.get_tensor()
 
 
+TEMPORAL_STRATEGIES = {"uniform": 0, "last": 1}
+TEMPORAL_MAX_FANOUT = 64
+
+
+def _check_temporal_arguments(center_nodes_tensor, center_times_tensor, max_sample_count, strategy, time_window):
+    """-> (strategy code, time_window as the C ABI takes it: -1 for None)"""
+    if strategy not in TEMPORAL_STRATEGIES:
+        raise ValueError("strategy must be one of %s, got %r" % (sorted(TEMPORAL_STRATEGIES), strategy))
+    if int(max_sample_count) > TEMPORAL_MAX_FANOUT:
+        raise ValueError("max_sample_count must be at most %d, got %r" % (TEMPORAL_MAX_FANOUT, max_sample_count))
+    if time_window is not None and not 0 <= int(time_window) < (1 << 63):
+        raise ValueError("time_window must be None or lie in [0, 2^63), got %r" % (time_window,))
+    if center_nodes_tensor.dim() != 1 or center_times_tensor.dim() != 1:
+        raise ValueError("center_nodes_tensor and center_times_tensor must be 1-D")
+    if center_times_tensor.shape[0] != center_nodes_tensor.shape[0]:
+        raise ValueError("center_times_tensor must have one time per centre, got %d for %d centres"
+                         % (center_times_tensor.shape[0], center_nodes_tensor.shape[0]))
+    if center_times_tensor.dtype != torch.int64:
+        raise ValueError("center_times_tensor must be int64, got %s" % center_times_tensor.dtype)
+    return TEMPORAL_STRATEGIES[strategy], -1 if time_window is None else int(time_window)
+
+
+def _temporal_sample_via_gather(row, col, tim, center_nodes_tensor, center_times_tensor, max_sample_count, random_seed, rule):
+    """Temporal sampling where the graph or the time tensor is DISTRIBUTED, as `_weighted_sample_via_gather`: the unweighted
+    sampler with max_sample_count -1 brings every neighbour of the centres in row order with its edge id, a gather brings
+    their times, and the op runs on those three arrays as a device CSR whose node i is centre i. A centre's position in the
+    batch and a neighbour's position in its row are unchanged, so the samples are those of a mapped graph. Collective.
+    -> (sample_offset, sampled node ids, center local id, edge id)"""
+    from .tensor import WholeMemoryTensor
+    desc = wmb.lib().wholememory_tensor_get_tensor_description
+    if _tensor_dim(tim) != 1 or int(desc(tim).contents.sizes[0]) != int(desc(col).contents.sizes[0]):
+        wmb.check(6, "wm_csr_edge_time_tensor must have one timestamp per edge")      # WHOLEMEMORY_INVALID_INPUT
+    if wholememory_dtype_to_torch_dtype(desc(tim).contents.dtype) != torch.int64:      # (before any collective work)
+        wmb.check(3, "wm_csr_edge_time_tensor must be int64")      # WHOLEMEMORY_LOGIC_ERROR
+    # the unweighted sampler reads the row bounds of whatever id it is given: a centre that is no node (an empty row here) is
+    # fetched as node 0 and handed to the op below as centre -1, which is no node of the gathered rows either
+    n = center_nodes_tensor.shape[0]
+    is_node = (center_nodes_tensor >= 0) & (center_nodes_tensor < int(desc(row).contents.sizes[0]) - 1)
+    fetched = torch.where(is_node, center_nodes_tensor, torch.zeros_like(center_nodes_tensor))
+    offset, neighbours, edge_id = unweighted_sample_without_replacement(row, col, fetched, -1, 0, False, True)
+    times = WholeMemoryTensor(tim).gather(edge_id)
+    if edge_id.shape[0] == 0:      # (no centre, or none with a neighbour: offset is n + 1 zeros)
+        return (offset, neighbours, torch.empty(0, device=op_device(), dtype=torch.int),
+                torch.empty(0, device=op_device(), dtype=torch.int64))
+    local = [wrap_torch_tensor(t) for t in (offset.to(torch.int64), neighbours, times)]
+    centres = torch.arange(n, device=center_nodes_tensor.device, dtype=center_nodes_tensor.dtype)
+    centres = torch.where(is_node, centres, torch.full_like(centres, -1))
+    offset, ids, lid, local_edge = _temporal_sample_mapped(*[w.handle for w in local], centres, center_times_tensor,
+                                                           max_sample_count, random_seed, True, True, rule)
+    return offset, ids, lid, edge_id[local_edge]
+
+
+def _temporal_sample_mapped(row, col, tim, center_nodes_tensor, center_times_tensor, max_sample_count, random_seed,
+                            need_center_local_output, need_edge_output, rule):
+    offset = torch.empty(center_nodes_tensor.shape[0] + 1, device=op_device(), dtype=torch.int)
+    dest = TorchMemoryContext()
+    lid = TorchMemoryContext() if need_center_local_output else None
+    egid = TorchMemoryContext() if need_edge_output else None
+    wc, wt, wo = wrap_torch_tensor(center_nodes_tensor), wrap_torch_tensor(center_times_tensor), wrap_torch_tensor(offset)
+    strategy, inclusive, window = rule
+    wmb.check(wmb.lib().wholememory_ext_csr_temporal_sample(
+        row, col, tim, wc.handle, wt.handle, int(max_sample_count), strategy, 1 if inclusive else 0, C.c_longlong(window),
+        _seed64(random_seed), wo.handle, C.c_void_p(dest.get_c_context()), C.c_void_p(lid.get_c_context() if lid else 0),
+        C.c_void_p(egid.get_c_context() if egid else 0), get_wholegraph_env_fns(), C.c_void_p(get_stream())))
+    return _sample_outputs(offset, dest, lid, egid, need_center_local_output, need_edge_output)
+
+
+def temporal_sample_without_replacement(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_edge_time_tensor,
+                                        center_nodes_tensor: torch.Tensor, center_times_tensor: torch.Tensor,
+                                        max_sample_count: int, random_seed: Union[int, None] = None,
+                                        need_center_local_output: bool = False, need_edge_output: bool = False, *,
+                                        strategy: str = "uniform", inclusive: bool = True, time_window: Union[int, None] = None):
+    """Extension (wholememory_ext_csr_temporal_sample, include/wholememory/wholegraph_amd_ext.h section 2r): for centre i — the
+    node center_nodes_tensor[i] at the time center_times_tensor[i] (int64) — the neighbours whose edge time
+    (wm_csr_edge_time_tensor: int64, one per edge) is not later than that time (earlier, with inclusive=False) and, with
+    time_window, at most time_window before it; min(eligible, max_sample_count) of them, all eligible ones when
+    max_sample_count <= 0. max_sample_count <= 64. strategy "uniform" keeps a uniform sample without replacement, "last" the
+    latest edges; either way a centre's neighbours come in row order. Returns what the other samplers return:
+    (sample_offset int32 [n + 1], sampled node ids[, center local id int32][, edge id int64]). Centre i's samples depend on
+    (random_seed, i) and its row alone, not on the size of the batch. One host round trip, for the total.
+    A graph or time tensor that is DISTRIBUTED (the C entry point answers NOT_IMPLEMENTED) is sampled through
+    `_temporal_sample_via_gather`: a collective, the same samples as on a mapped graph."""
+    code, window = _check_temporal_arguments(center_nodes_tensor, center_times_tensor, max_sample_count, strategy, time_window)
+    rule = (code, bool(inclusive), window)
+    row, col, tim = _handle(wm_csr_row_ptr_tensor), _handle(wm_csr_col_ptr_tensor), _handle(wm_csr_edge_time_tensor)
+    if random_seed is None:
+        random_seed = random.getrandbits(64)
+    if any(_is_distributed(h) for h in (row, col, tim)):
+        out = _temporal_sample_via_gather(row, col, tim, center_nodes_tensor, center_times_tensor, max_sample_count, random_seed, rule)
+        return out[:2] + ((out[2],) if need_center_local_output else ()) + ((out[3],) if need_edge_output else ())
+    return _temporal_sample_mapped(row, col, tim, center_nodes_tensor, center_times_tensor, max_sample_count, random_seed,
+                                   need_center_local_output, need_edge_output, rule)
+
+
 def generate_random_positive_int_cpu(random_seed, sub_sequence, output_random_value_count):
     output = torch.empty((output_random_value_count,), dtype=torch.int)
     w = wrap_torch_tensor(output)

@@ -210,7 +210,10 @@ int h_ipc_close(void* dev_ptr) { return rc(hipIpcCloseMemHandle(dev_ptr)); }
 int h_host_register(void* host_ptr, size_t bytes, void** dev_ptr)
 {
   hipError_t e = hipHostRegister(host_ptr, bytes, hipHostRegisterMapped | hipHostRegisterPortable);
-  if (e != hipSuccess) return rc(e);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();   // (or the next launch reports it)
+    return rc(e);
+  }
   return rc(hipHostGetDevicePointer(dev_ptr, host_ptr, 0));
 }
 int h_host_unregister(void* host_ptr) { return rc(hipHostUnregister(host_ptr)); }

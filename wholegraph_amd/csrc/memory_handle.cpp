@@ -11,6 +11,10 @@
 //  * DISTRIBUTED = local shard only; rows move by RCCL all-to-all-v (ops.cpp);
 //  * HOST = one POSIX shared-memory segment mapped by every rank and registered with HIP, so the
 //    same gref shapes work for host-resident tables;
+//  * where the HIP runtime cannot put the ranks' memory into one range — no hipHostRegister of a mapped segment or no
+//    import of a peer's VMM handle, as in some virtual machines — a mapped table of several ranks is stored like device
+//    CHUNKED: every rank allocates its shard (hipHostMalloc for HOST), the peers map it with hipIpc, and kernels get the
+//    per-rank reference; such a table has no flat global pointer;
 //  * with ONE rank every type degenerates to a flat allocation and the ops layer hands kernels a
 //    continuous gref (no per-row owner lookup).
 //  * multi-rank CONTINUOUS/DEVICE = HIP VMM: each rank creates its page run (hipMemCreate), exports it as
@@ -56,6 +60,7 @@ struct wholememory_handle_ {
   // mapped views
   void* global_base = nullptr;        // CONTINUOUS (and HOST chunked): flat pointer usable on device
   std::vector<void*> rank_ptrs;       // CHUNKED: per-rank bases as seen from this process
+  bool ipc_mapped = false;            // the peers' entries of rank_ptrs are hipIpc mappings, to be closed
   void** dev_rank_ptrs     = nullptr; // device copy of rank_ptrs
   size_t* dev_rank_offsets = nullptr; // device copy of part_offsets
   // host shm
@@ -132,6 +137,9 @@ void alloc_local(wholememory_handle_* h)
   h->local_alloc  = std::max<size_t>(h->part_sizes[rank], 16);
   h->local_is_pinned = h->location == WHOLEMEMORY_ML_HOST;
   if (h->local_is_pinned) {
+    // whole 64 KiB pages: hipIpcGetMemHandle refuses a pinned host block whose size is not a whole number of pages (invalid
+    // value), and a HOST shard of several ranks may have to be exported to the peers (create_memory)
+    h->local_alloc = round_up<size_t>(h->local_alloc, size_t(64) << 10);
     WM_BK(bk->malloc_pinned(&h->local_ptr, h->local_alloc));
     return;
   }
@@ -293,13 +301,15 @@ void map_chunked_device(wholememory_handle_* h)
       if (r == rank) continue;
       WM_BK(bk->ipc_open_handle(&h->rank_ptrs[r], handles.data() + static_cast<size_t>(r) * 64));
     }
+    h->ipc_mapped = true;
     h->comm->barrier();
   }
   upload_tables(h);
 }
 
-// one shm segment holding the whole table; rank 0 names it, everyone maps + registers it
-void map_host_shared(wholememory_handle_* h)
+// one shm segment holding the whole table; rank 0 names it, everyone maps + registers it. False when the HIP runtime of
+// some rank cannot register the segment: every rank then returns false, with the segment detached
+bool map_host_shared(wholememory_handle_* h)
 {
   const auto* bk = backend();
   const int W    = h->comm->world_size;
@@ -348,14 +358,25 @@ void map_host_shared(wholememory_handle_* h)
     if (p != MAP_FAILED) munmap(p, h->shm_bytes);
     throw logic_error("attaching the shared host segment failed on at least one rank");
   }
+  void* dev            = nullptr;
+  const int registered = bk->host_register(p, h->shm_bytes, &dev);
+  if (!all_ok(registered == 0)) {
+    if (registered == 0) bk->host_unregister(p);
+    munmap(p, h->shm_bytes);
+    static std::once_flag told;
+    std::call_once(told, [] {
+      WM_WARN("the HIP runtime cannot register a shared host segment here: HOST tables of several ranks are pinned shards "
+              "mapped between the ranks with hipIpc, without a global pointer");
+    });
+    return false;
+  }
   h->shm_host_ptr = p;
-  void* dev       = nullptr;
-  WM_BK(bk->host_register(p, h->shm_bytes, &dev));
-  h->global_base = dev;
+  h->global_base  = dev;
   h->local_ptr   = static_cast<char*>(dev) + h->part_offsets[rank];
   h->rank_ptrs.assign(W, nullptr);
   for (int r = 0; r < W; r++) h->rank_ptrs[r] = static_cast<char*>(dev) + h->part_offsets[r];
   upload_tables(h);
+  return true;
 }
 
 void create_memory(wholememory_handle_* h)
@@ -385,7 +406,9 @@ void create_memory(wholememory_handle_* h)
     return;
   }
   if (h->location == WHOLEMEMORY_ML_HOST) {
-    map_host_shared(h);
+    if (map_host_shared(h)) return;
+    alloc_local(h);   // pinned shards, mapped like device CHUNKED
+    map_chunked_device(h);
     return;
   }
   if (h->type == WHOLEMEMORY_MT_CHUNKED) {
@@ -395,7 +418,16 @@ void create_memory(wholememory_handle_* h)
   }
   // multi-rank CONTINUOUS in HBM: every rank's pages stitched into one VA range (memory_vmm.cpp)
   if (backend() != hip_backend()) throw logic_error("multi-rank CONTINUOUS device memory needs the HIP backend");
-  vmm_continuous_create(h->comm, h->total_size, &h->vmm);
+  if (!vmm_continuous_create(h->comm, h->total_size, &h->vmm)) {
+    static std::once_flag told;
+    std::call_once(told, [] {
+      WM_WARN("the HIP runtime cannot share virtual-memory handles between the ranks here: CONTINUOUS device tables of several "
+              "ranks are stored like CHUNKED ones (hipIpc mappings), without a global pointer");
+    });
+    alloc_local(h);
+    map_chunked_device(h);
+    return;
+  }
   h->global_base = h->vmm.base;
   h->local_ptr   = static_cast<char*>(h->vmm.base) + h->part_offsets[h->comm->world_rank];
   h->rank_ptrs.assign(W, nullptr);
@@ -422,7 +454,7 @@ void destroy_memory(wholememory_handle_* h) noexcept
     bk->host_unregister(h->shm_host_ptr);
     munmap(h->shm_host_ptr, h->shm_bytes);
   } else {
-    if (h->type == WHOLEMEMORY_MT_CHUNKED && W > 1) {
+    if (h->ipc_mapped) {
       for (int r = 0; r < W; r++)
         if (r != rank && h->rank_ptrs.size() == static_cast<size_t>(W) && h->rank_ptrs[r]) bk->ipc_close_handle(h->rank_ptrs[r]);
       try {
@@ -617,12 +649,12 @@ wholememory_error_code_t wholememory_get_global_pointer(void** global_ptr, whole
 wholememory_error_code_t wholememory_get_global_reference(wholememory_gref_t* gref, wholememory_handle_t h)
 {
   if (gref == nullptr || h == nullptr) return WHOLEMEMORY_INVALID_INPUT;
-  if (h->type == WHOLEMEMORY_MT_CONTINUOUS) {
+  if (h->type == WHOLEMEMORY_MT_CONTINUOUS && !h->ipc_mapped) {
     *gref = wholememory_create_continuous_global_reference(h->global_base);
     gref->world_size = h->comm->world_size;
     return h->global_base ? WHOLEMEMORY_SUCCESS : WHOLEMEMORY_INVALID_INPUT;
   }
-  if (h->type == WHOLEMEMORY_MT_CHUNKED) {  // reference memory_handle.cpp:1174-1185
+  if (h->type == WHOLEMEMORY_MT_CHUNKED || h->type == WHOLEMEMORY_MT_CONTINUOUS) {  // reference memory_handle.cpp:1174-1185
     gref->pointer             = h->dev_rank_ptrs;
     gref->rank_memory_offsets = h->dev_rank_offsets;
     gref->world_size          = h->comm->world_size;

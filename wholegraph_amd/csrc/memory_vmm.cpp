@@ -91,9 +91,51 @@ int recv_fd(int sock, int* from_rank)
   return fd;
 }
 
+// true when `mine` holds on every rank; doubles as a barrier between the steps of the creation
+bool on_every_rank(wholememory_comm_t comm, bool mine)
+{
+  char flag = mine ? 1 : 0;
+  std::vector<char> flags(static_cast<size_t>(comm->world_size), 0);
+  comm->allgather_host(&flag, flags.data(), 1);
+  for (char f : flags)
+    if (f == 0) return false;
+  return true;
+}
+
+// The osHandle convention of hipMemImportFromShareableHandle differs between HIP runtimes: up to 7.1 (7.0 is what torch
+// 2.10+rocm7.0 bundles, and what this library meets inside python) it takes a POINTER to the descriptor, from 7.2 on the
+// descriptor's VALUE cast to void* (CUDA style). The form is chosen by the version of the runtime that is loaded and the
+// other one is never tried: a runtime that dereferences osHandle takes a descriptor's value for an address and faults.
+hipError_t import_fd(hipMemGenericAllocationHandle_t* handle, int fd)
+{
+  int runtime = 0;
+  hipError_t e = hipRuntimeGetVersion(&runtime);
+  if (e != hipSuccess) return e;
+  if (runtime >= 70200000)
+    return hipMemImportFromShareableHandle(handle, reinterpret_cast<void*>(static_cast<intptr_t>(fd)),
+                                           hipMemHandleTypePosixFileDescriptor);
+  return hipMemImportFromShareableHandle(handle, &fd, hipMemHandleTypePosixFileDescriptor);
+}
+
+// gives back whatever a creation that did not complete had made; the range was never used by a kernel, so it can be freed
+void undo_create(vmm_mapping* m, const std::vector<char>& mapped, int my_fd, const std::vector<int>& peer_fds)
+{
+  for (size_t r = 0; r < m->handles.size(); r++) {
+    if (r < mapped.size() && mapped[r]) (void)hipMemUnmap(static_cast<char*>(m->base) + m->alloc_offsets[r], m->alloc_sizes[r]);
+    if (m->handles[r] != nullptr) (void)hipMemRelease(m->handles[r]);
+  }
+  if (m->base != nullptr) (void)hipMemAddressFree(m->base, m->total_alloc);
+  if (my_fd >= 0) close(my_fd);
+  for (int fd : peer_fds)
+    if (fd >= 0) close(fd);
+  (void)hipGetLastError();
+  m->handles.clear();
+  m->base = nullptr;
+}
+
 }  // namespace
 
-void vmm_continuous_create(wholememory_comm_t comm, size_t total_size, vmm_mapping* m)
+bool vmm_continuous_create(wholememory_comm_t comm, size_t total_size, vmm_mapping* m)
 {
   const int W = comm->world_size, rank = comm->world_rank;
   int dev = 0;
@@ -144,10 +186,25 @@ void vmm_continuous_create(wholememory_comm_t comm, size_t total_size, vmm_mappi
   m->handles.assign(W, nullptr);
 
   // 1. own physical pages + exportable fd
+  // What the HIP runtime refuses on one rank (a driver without shareable handles, a virtual machine that cannot import
+  // them) is agreed on by all ranks before anybody goes on: they give up together, with nothing left behind.
   int my_fd = -1;
+  std::vector<char> mapped(W, 0);
+  std::vector<int> peer_fds(W, -1);
+  hipError_t err  = hipSuccess;
+  const char* did = "";
   if (m->alloc_sizes[rank] > 0) {
-    WM_HIP_TRY(hipMemCreate(&m->handles[rank], m->alloc_sizes[rank], &prop, 0));
-    WM_HIP_TRY(hipMemExportToShareableHandle(&my_fd, m->handles[rank], hipMemHandleTypePosixFileDescriptor, 0));
+    did = "hipMemCreate";
+    err = hipMemCreate(&m->handles[rank], m->alloc_sizes[rank], &prop, 0);
+    if (err == hipSuccess) {
+      did = "hipMemExportToShareableHandle";
+      err = hipMemExportToShareableHandle(&my_fd, m->handles[rank], hipMemHandleTypePosixFileDescriptor, 0);
+    }
+  }
+  if (err != hipSuccess) WM_INFO("CONTINUOUS device memory: %s -> %s", did, hipGetErrorString(err));
+  if (!on_every_rank(comm, err == hipSuccess)) {
+    undo_create(m, mapped, my_fd, peer_fds);
+    return false;
   }
   // 2. pass fds around: one abstract datagram socket per rank, named after a token minted by rank 0
   char token[32] = {0};
@@ -167,7 +224,6 @@ void vmm_continuous_create(wholememory_comm_t comm, size_t total_size, vmm_mappi
     throw logic_error("bind of the VMM handle-passing socket failed");
   }
   comm->barrier();  // every socket is bound
-  std::vector<int> peer_fds(W, -1);
   try {
     for (int r = 0; r < W; r++) {
       if (r == rank || my_fd < 0) continue;
@@ -186,38 +242,43 @@ void vmm_continuous_create(wholememory_comm_t comm, size_t total_size, vmm_mappi
     }
   } catch (...) {
     close(sock);
+    undo_create(m, mapped, my_fd, peer_fds);
     throw;
   }
   comm->barrier();
   close(sock);
 
   // 3. one VA range, every rank's pages mapped at its page offset, access granted to this device
-  WM_HIP_TRY(hipMemAddressReserve(&m->base, m->total_alloc, page, nullptr, 0));
-  for (int r = 0; r < W; r++) {
+  did = "hipMemAddressReserve";
+  err = hipMemAddressReserve(&m->base, m->total_alloc, page, nullptr, 0);
+  for (int r = 0; r < W && err == hipSuccess; r++) {
     if (m->alloc_sizes[r] == 0) continue;
     if (r != rank) {
-      // osHandle convention differs between HIP runtimes: 7.0 (bundled with torch 2.10+rocm7.0) takes a
-      // POINTER to the fd, 7.2 takes the fd VALUE cast to void* (CUDA style). The pointer form is safe to try
-      // first on both (a value-style runtime just sees a bogus fd number and returns an error).
-      int fd       = peer_fds[r];
-      hipError_t e = hipMemImportFromShareableHandle(&m->handles[r], &fd, hipMemHandleTypePosixFileDescriptor);
-      if (e != hipSuccess) {
-        (void)hipGetLastError();
-        e = hipMemImportFromShareableHandle(&m->handles[r], reinterpret_cast<void*>(static_cast<intptr_t>(fd)),
-                                            hipMemHandleTypePosixFileDescriptor);
-      }
-      if (e != hipSuccess) throw hip_error(format_string("hipMemImportFromShareableHandle -> %s", hipGetErrorString(e)));
-      close(peer_fds[r]);
+      did = "hipMemImportFromShareableHandle";
+      err = import_fd(&m->handles[r], peer_fds[r]);
+      if (err != hipSuccess) break;
     }
-    WM_HIP_TRY(hipMemMap(static_cast<char*>(m->base) + m->alloc_offsets[r], m->alloc_sizes[r], 0, m->handles[r], 0));
+    did = "hipMemMap";
+    err = hipMemMap(static_cast<char*>(m->base) + m->alloc_offsets[r], m->alloc_sizes[r], 0, m->handles[r], 0);
+    mapped[r] = err == hipSuccess ? 1 : 0;
+  }
+  if (err == hipSuccess) {
+    hipMemAccessDesc access{};
+    access.location.type = hipMemLocationTypeDevice;
+    access.location.id   = dev;
+    access.flags         = hipMemAccessFlagsProtReadWrite;
+    did = "hipMemSetAccess";
+    err = hipMemSetAccess(m->base, m->total_alloc, &access, 1);
+  }
+  if (err != hipSuccess) WM_INFO("CONTINUOUS device memory: %s -> %s", did, hipGetErrorString(err));
+  if (!on_every_rank(comm, err == hipSuccess)) {
+    undo_create(m, mapped, my_fd, peer_fds);
+    return false;
   }
   if (my_fd >= 0) close(my_fd);
-  hipMemAccessDesc access{};
-  access.location.type = hipMemLocationTypeDevice;
-  access.location.id   = dev;
-  access.flags         = hipMemAccessFlagsProtReadWrite;
-  WM_HIP_TRY(hipMemSetAccess(m->base, m->total_alloc, &access, 1));
-  comm->barrier();
+  for (int fd : peer_fds)
+    if (fd >= 0) close(fd);
+  return true;
 }
 
 void vmm_continuous_destroy(wholememory_comm_t comm, vmm_mapping* m) noexcept

@@ -17,8 +17,9 @@ struct vmm_mapping {
   std::vector<hipMemGenericAllocationHandle_t> handles;    // own + imported
 };
 
-// Collective over comm. Throws on failure.
-void vmm_continuous_create(wholememory_comm_t comm, size_t total_size, vmm_mapping* m);
+// Collective over comm. False when the HIP runtime of some rank cannot create, share or map the handles: every rank then
+// returns false with nothing left behind (the caller has another layout for that). Throws on any other failure.
+bool vmm_continuous_create(wholememory_comm_t comm, size_t total_size, vmm_mapping* m);
 void vmm_continuous_destroy(wholememory_comm_t comm, vmm_mapping* m) noexcept;
 
 }  // namespace wm

@@ -147,6 +147,12 @@ class WholeMemoryTensor(object):
         L = wmb.lib()
         comm = self.get_comm()
         W = comm.get_size()
+        if host_view and W > 1 and not self._location_is_device():
+            gp = C.c_void_p()
+            if L.wholememory_get_global_pointer(C.byref(gp), self._handle()) != wmb.WHOLEMEMORY_SUCCESS:
+                # stored as per-rank pinned shards mapped with hipIpc (no shared segment on this system): a peer's shard is
+                # mapped for the device only
+                raise ValueError("host views of the peers' shards are not available for this HOST WholeMemory")
         offs = (C.c_size_t * (W + 1))()
         wmb.check(L.wholememory_tensor_get_entry_offsets(offs, self.wmb_tensor))
         es = torch.tensor([], dtype=self.dtype).element_size()

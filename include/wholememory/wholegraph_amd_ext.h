@@ -36,6 +36,8 @@
  *      block, the batch of subgraph-wise training (GraphSAINT, ShaDow-GNN, Cluster-GCN).
  *      (2r) temporal neighbour sampling over the same graph with a timestamp per edge: per (node, time) centre, up to M
  *      neighbours whose edge is not in the centre's future, uniformly or the latest (TGN, TGAT).
+ *      (2s) PinSAGE importance neighbourhoods over the same graph: per seed, random walks with restart, the visits counted,
+ *      and the T most visited nodes with their counts, as one launch (also a Monte-Carlo personalised PageRank).
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -1441,6 +1443,55 @@ enum wholememory_error_code_t wholememory_ext_csr_temporal_sample(
   void* output_edge_gid_memory_context,         /* int64 [total] or NULL: positions in csr_col_ptr */
   wholememory_env_func_t* p_env_fns,
   void* stream);
+
+/* ---- (2s) PinSAGE importance neighbourhoods over a CSR graph held in WholeMemory ------------------------------------------- */
+/* The neighbourhood of PinSAGE (Ying et al., KDD 2018): for each of n seeds, R = num_walks random walks with restart of
+ * L = walk_length steps; the visited nodes are counted, and the T = num_neighbors most visited become the seed's neighbours
+ * with the visit counts as edge weights. The same counts are a Monte-Carlo estimate of personalised PageRank. Graph tensors,
+ * dtypes, memory types and locations are exactly those of (2m): row_ptr int64 [n_nodes + 1], col_ind int32 or int64
+ * [n_edges], both CONTINUOUS or CHUNKED, in device or host memory, or plain device arrays wrapped with
+ * wholememory_make_tensor_from_pointer. seed_nodes is int32 or int64 [n], on the device. One launch on `stream`; nothing is
+ * allocated, nothing is read back and the call does not synchronise.
+ *
+ * Parameter limits. R = num_walks >= 1; L = walk_length >= 1; V = R * L <= 2048 (the visits of a seed are counted in one
+ * on-chip table); T = num_neighbors in 1 .. 64; n * T < 2^31; n * R < 2^31; n_nodes <= 2^52 (a visit count and a node id
+ * share one 64-bit key).
+ *
+ * Restart threshold. thr = (uint64)(restart_prob * 4294967296.0): one double multiplication, done on the host, exact.
+ * restart_prob lies in [0, 1).
+ *
+ * Walk rule. Walk r of seed i (node s) owns the generator stream(seed, i * R + r, 0) of (2m). Step t (0-based) consumes the
+ * generator's outputs 2t (call it a) and 2t + 1 (call it b), whether or not they are used. The walker starts on s.
+ *   - If uint64(a) < thr, the walker returns to s. This is a restart. Nothing is counted.
+ *   - Otherwise the walker takes the uniform step of (2m) from its node v: k = (uint64(b) * uint64(deg)) >> 32.
+ *   - A step is not taken when the row is not steppable (deg <= 0 or >= 2^31, or bounds outside [0, n_edges]) or when the
+ *     chosen col_ind entry is outside [0, n_nodes). In that case the walker also returns to s and nothing is counted: the
+ *     dangling-node rule of personalised PageRank. It also means a damaged graph costs visits and never reads out of bounds.
+ *   - When the step is taken, the walker stands on c. c receives one visit unless c == s: arrivals at the seed itself are
+ *     never counted, because the layer has a root term.
+ *
+ * Output. nodes is [n, T] in col_ind's dtype and counts is int32 [n, T], each a dense block given as a 2-D tensor of that
+ * shape or a 1-D one of as many entries. Row i holds the visited nodes of seed i, ordered by count descending and then by node
+ * id ascending, and cut at T. Behind the last visited node the row holds -1 in nodes and 0 in counts. A seed outside
+ * [0, n_nodes) gets a row that is all -1 / 0. The result is a function of (seed, i, r, t) alone: it does not depend on the
+ * launch geometry or on n, and the first 100 seeds of a batch of 512 equal a batch of those 100.
+ *
+ * Errors, every answer before any device work. INVALID_INPUT: a NULL row_ptr, col_ind, seed_nodes, nodes or counts tensor; one
+ * of the first three not 1-D; any limit above broken; restart_prob not in [0, 1) or NaN; an output of the wrong size; a
+ * HIERARCHY tensor. LOGIC_ERROR: row_ptr not int64, col_ind or seed_nodes not int32 / int64, nodes not in col_ind's dtype,
+ * counts not int32. NOT_IMPLEMENTED for a DISTRIBUTED tensor. NOT_SUPPORTED, nothing queued, when the device backend has no
+ * such kernel. n = 0 succeeds and queues nothing. */
+enum wholememory_error_code_t wholememory_ext_csr_rwr_top_neighbors(wholememory_tensor_t wm_csr_row_ptr_tensor,
+                                                                    wholememory_tensor_t wm_csr_col_ptr_tensor,
+                                                                    wholememory_tensor_t seed_nodes_tensor,
+                                                                    int num_walks,
+                                                                    int walk_length,
+                                                                    double restart_prob,
+                                                                    int num_neighbors,
+                                                                    unsigned long long random_seed,
+                                                                    wholememory_tensor_t output_nodes_tensor,
+                                                                    wholememory_tensor_t output_counts_tensor,
+                                                                    void* stream);
 
 /* ---- (3) testing seam ---------------------------------------------------------------------- */
 /* Replaces the device backend. Refuses (WHOLEMEMORY_NOT_SUPPORTED) unless the environment has

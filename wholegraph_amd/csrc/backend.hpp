@@ -527,6 +527,22 @@ struct wm_tsample_args : wm_csr_graph {
   int64_t* out_edge_gid;        // [total] or nullptr
 };
 
+// PinSAGE importance neighbourhoods on such a graph (kernels/rwr.hip, wholegraph_amd_ext.h section 2s; the weights stay empty):
+// per seed, num_walks random walks with restart of walk_length steps, the visits counted, the num_neighbors most visited nodes
+// with their counts. One launch; nothing is allocated and nothing read back
+struct wm_rwr_args : wm_csr_graph {
+  const void* seeds;    // [n] device
+  wholememory_dtype_t seed_dtype;
+  int64_t n;            // seeds; n * num_walks < 2^31 and n * num_neighbors < 2^31
+  int num_walks;        // R >= 1
+  int walk_length;      // L >= 1, R * L <= 2048
+  uint64_t restart_threshold;   // (uint64)(restart_prob * 2^32): a step restarts when its first draw is below it
+  int num_neighbors;    // T in 1 .. 64
+  uint64_t random_seed;
+  void* out_nodes;      // [n, T] col_dtype: -1 behind the last visited node
+  int* out_counts;      // [n, T]: 0 there
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -813,6 +829,8 @@ struct wm_device_backend {
   size_t (*tsample_workspace_bytes)(int64_t n);
   int (*tsample_count)(const wm_tsample_args* a, void* stream);
   int (*tsample_select)(const wm_tsample_args* a, void* stream);
+  // ---- PinSAGE importance neighbourhoods (kernels/rwr.hip, wholegraph_amd_ext.h section 2s); nullptr in a backend without it ----
+  int (*rwr_top)(const wm_rwr_args* a, void* stream);
 };
 
 }  // extern "C"

@@ -22,6 +22,7 @@
 #include "neg_sample.hpp"
 #include "ops_internal.hpp"
 #include "pcg.hpp"
+#include "rwr.hpp"
 #include "tsample.hpp"
 #include "walk_n2v.hpp"
 
@@ -632,6 +633,76 @@ wholememory_error_code_t wholememory_ext_csr_temporal_sample(
   if (m > 0) WM_BK(bk->tsample_select(&a, stream));
   // as the sampler: complete on return, unless the host framework has declared its allocator ordered on `stream`
   if (drain) WM_BK(bk->stream_sync(stream));
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+// PinSAGE importance neighbourhoods (extension, wholegraph_amd_ext.h section 2s; kernels/rwr.hip): per seed, num_walks random
+// walks with restart, the visits counted, the num_neighbors most visited nodes and their counts, as ONE launch on `stream`. The
+// outputs are the caller's: nothing is allocated, nothing read back, the call does not synchronise, and every answer but SUCCESS
+// is given before any device work.
+wholememory_error_code_t wholememory_ext_csr_rwr_top_neighbors(
+  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor, wholememory_tensor_t seed_nodes_tensor,
+  int num_walks, int walk_length, double restart_prob, int num_neighbors, unsigned long long random_seed,
+  wholememory_tensor_t output_nodes_tensor, wholememory_tensor_t output_counts_tensor, void* stream)
+{
+  WM_API_BEGIN
+  if (output_nodes_tensor == nullptr || output_counts_tensor == nullptr) return WHOLEMEMORY_INVALID_INPUT;
+  wholememory_error_code_t err = WHOLEMEMORY_SUCCESS;
+  checked_graph g{wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, nullptr, false};
+  wholememory_array_description_t seed_desc;
+  WHOLEMEMORY_RETURN_ON_FAIL(g.arrays());
+  if (!array_of(seed_nodes_tensor, "seed_nodes_tensor", &seed_desc, &err)) return err;
+  if (!wm::rwr_scalars_ok(num_walks, walk_length, restart_prob, num_neighbors)) {
+    WM_ERROR("num_walks and walk_length must be >= 1 with num_walks * walk_length <= %d, num_neighbors in [1, %d] and restart_prob "
+             "in [0, 1), got %d, %d, %d, %g", wm::kRwrMaxVisits, wm::kRwrMaxTop, num_walks, walk_length, num_neighbors, restart_prob);
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  const int64_t n = seed_desc.size, R = num_walks, T = num_neighbors;
+  if (n < 0 || g.row_desc.size < 1 || n > ((INT64_C(1) << 31) - 1) / R || n > ((INT64_C(1) << 31) - 1) / T) {
+    WM_ERROR("%ld seeds of %d walks and %d neighbours: n * num_walks and n * num_neighbors must stay below 2^31", static_cast<long>(n),
+             num_walks, num_neighbors);
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  if (g.row_desc.size - 1 > (INT64_C(1) << wm::kRwrNodeBits)) {
+    WM_ERROR("a graph of more than 2^52 nodes: a visit count and a node id must share one 64-bit key");
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  if (!dense_block(output_nodes_tensor, n, T) || !dense_block(output_counts_tensor, n, T)) {
+    WM_ERROR("output_nodes_tensor and output_counts_tensor must be [%ld, %ld], dense", static_cast<long>(n), static_cast<long>(T));
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  WHOLEMEMORY_RETURN_ON_FAIL(g.row_dtype());
+  WHOLEMEMORY_RETURN_ON_FAIL(g.col_and_id_dtype(seed_desc.dtype, "seed nodes"));
+  if (wholememory_tensor_get_tensor_description(output_nodes_tensor)->dtype != g.col_desc.dtype) {
+    WM_ERROR("output_nodes_tensor must have the dtype of wm_csr_col_ptr_tensor");
+    return WHOLEMEMORY_LOGIC_ERROR;
+  }
+  if (wholememory_tensor_get_tensor_description(output_counts_tensor)->dtype != WHOLEMEMORY_DT_INT) {
+    WM_ERROR("output_counts_tensor must be int32");
+    return WHOLEMEMORY_LOGIC_ERROR;
+  }
+  WHOLEMEMORY_RETURN_ON_FAIL(g.placement(
+    csr_tensors::row_col,
+    "importance neighbourhoods on DISTRIBUTED tensors are not implemented: every step would be a collective gather"));
+  const auto* bk = backend();
+  if (bk->rwr_top == nullptr) return WHOLEMEMORY_NOT_SUPPORTED;
+  if (n == 0) return WHOLEMEMORY_SUCCESS;
+  wm_rwr_args a{};
+  WHOLEMEMORY_RETURN_ON_FAIL(g.fill(&a));
+  a.seeds             = wholememory_tensor_get_data_pointer(seed_nodes_tensor);
+  a.seed_dtype        = seed_desc.dtype;
+  a.n                 = n;
+  a.num_walks         = num_walks;
+  a.walk_length       = walk_length;
+  a.restart_threshold = wm::rwr_threshold(restart_prob);
+  a.num_neighbors     = num_neighbors;
+  a.random_seed       = random_seed;
+  a.out_nodes         = wholememory_tensor_get_data_pointer(output_nodes_tensor);
+  a.out_counts        = static_cast<int*>(wholememory_tensor_get_data_pointer(output_counts_tensor));
+  if (a.seeds == nullptr || a.out_nodes == nullptr || a.out_counts == nullptr) return WHOLEMEMORY_INVALID_INPUT;
+  WM_BK(bk->rwr_top(&a, stream));
+  if (debug_sync_enabled()) WM_BK(bk->stream_sync(stream));
   return WHOLEMEMORY_SUCCESS;
   WM_API_END
 }

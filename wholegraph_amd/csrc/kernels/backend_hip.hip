@@ -116,6 +116,7 @@ int hip_isub_fill(const wm_isub_args* a, void* stream);
 size_t hip_tsample_workspace_bytes(int64_t n);
 int hip_tsample_count(const wm_tsample_args* a, void* stream);
 int hip_tsample_select(const wm_tsample_args* a, void* stream);
+int hip_rwr_top(const wm_rwr_args* a, void* stream);
 
 namespace {
 
@@ -332,6 +333,7 @@ const wm_device_backend kHipBackend = {
   hip_tsample_workspace_bytes,
   hip_tsample_count,
   hip_tsample_select,
+  hip_rwr_top,
 };
 
 }  // namespace

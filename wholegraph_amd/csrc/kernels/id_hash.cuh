@@ -1,5 +1,6 @@
 // wholegraph_amd — the hash of a node id, shared by the open-addressing tables that are keyed by one (graph.hip:
-// append_unique's table; isub.hip: the membership table of the induced subgraph). The low bits pick the slot.
+// append_unique's table; isub.hip: the membership table of the induced subgraph; rwr.hip: a seed's visit table in LDS). The
+// low bits pick the slot.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

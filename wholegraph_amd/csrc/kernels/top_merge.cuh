@@ -1,9 +1,9 @@
 // wholegraph_amd — the running top-G of a group of G lanes, shared by the units that select the largest keys of a row without
-// LDS (graph.hip: sample_weighted_small_kernel, a 64-bit key; tsample.hip: a two-word key). The key type K brings
-// top_key_max, top_key_min and top_key_xor (the key of the lane j away) with it; those of uint64_t are here. Lane i of the
-// group holds the i-th largest key seen so far; a batch of G keys, one per lane, is sorted across the lanes (bitonic network
-// of shuffles) and merged: top[i] = max(top[i], batch[G - 1 - i]) holds the G largest of both as a bitonic sequence, which
-// log2 G compare-exchanges put back in descending order. All lanes of a group call this together.
+// LDS (graph.hip: sample_weighted_small_kernel, a 64-bit key; tsample.hip: a two-word key; rwr.hip: a 64-bit key). The key
+// type K brings top_key_max, top_key_min and top_key_xor (the key of the lane j away) with it; those of uint64_t are here.
+// Lane i of the group holds the i-th largest key seen so far; a batch of G keys, one per lane, is sorted across the lanes
+// (bitonic network of shuffles) and merged: top[i] = max(top[i], batch[G - 1 - i]) holds the G largest of both as a bitonic
+// sequence, which log2 G compare-exchanges put back in descending order. All lanes of a group call this together.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,5 +1,6 @@
 // wholegraph_amd — what the random-walk units share (walk.hip: first-order walks, section 2m; walk_n2v.hip: node2vec walks,
-// section 2n): the kernel argument block, the row of a node, the start of a walk, and the launchers' argument checks.
+// section 2n; rwr.hip: walks with restart, section 2s, the row only): the kernel argument block, the row of a node, the start
+// of a walk, and the launchers' argument checks.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,15 +22,19 @@ struct walk_params {
 };
 
 // the row of v: true when a step can be taken from it (1 .. 2^31 - 1 neighbours, bounds inside the edge arrays). Both
-// reads are issued before either is used.
-__device__ __forceinline__ bool walk_row(const walk_params& p, int64_t v, int64_t* s_out, int* deg_out)
+// reads are issued before either is used. (Over the graph alone: rwr.hip walks without a walk_params.)
+__device__ __forceinline__ bool walk_row(const csr_view& g, int64_t v, int64_t* s_out, int* deg_out)
 {
-  const int64_t s = gref_load<int64_t>(p.g.row_ptr, p.g.row_off + v);
-  const int64_t e = gref_load<int64_t>(p.g.row_ptr, p.g.row_off + v + 1);
-  const bool ok   = s >= 0 && e > s && e <= p.g.n_edges && e - s < (INT64_C(1) << 31);
+  const int64_t s = gref_load<int64_t>(g.row_ptr, g.row_off + v);
+  const int64_t e = gref_load<int64_t>(g.row_ptr, g.row_off + v + 1);
+  const bool ok   = s >= 0 && e > s && e <= g.n_edges && e - s < (INT64_C(1) << 31);
   *s_out          = s;
   *deg_out        = ok ? static_cast<int>(e - s) : 0;
   return ok;
+}
+__device__ __forceinline__ bool walk_row(const walk_params& p, int64_t v, int64_t* s_out, int* deg_out)
+{
+  return walk_row(p.g, v, s_out, deg_out);
 }
 
 template <typename IdT>

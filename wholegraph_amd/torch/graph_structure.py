@@ -178,6 +178,53 @@ class GraphStructure(object):
                                               random_seed, mode=mode, exclude_edges=exclude_edges, exclude_self=exclude_self,
                                               max_tries=max_tries, col_sorted=col_sorted)
 
+    # ------------------------------------------------------------------------------------------ importance neighbourhoods
+    def pinsage_neighbors(self, seed_nodes: torch.Tensor, num_neighbors: int, *, num_walks: int, walk_length: int,
+                          restart_prob: float = 0.5, random_seed: Union[int, None] = None):
+        """Extension: the PinSAGE neighbourhood of every seed (``wholegraph_ops.rwr_top_neighbors``): num_walks random walks
+        with restart of walk_length steps, and the num_neighbors most visited nodes. -> nodes [n, num_neighbors] in
+        csr_col_ind's dtype (-1 behind the last visited node), counts int32 [n, num_neighbors] (0 there)."""
+        return wholegraph_ops.rwr_top_neighbors(self.csr_row_ptr.wmb_tensor, self.csr_col_ind.wmb_tensor, seed_nodes, num_walks,
+                                                walk_length, restart_prob, num_neighbors, random_seed)
+
+    def pinsage_sample_one_hop(self, center_nodes: torch.Tensor, num_neighbors: int, *, num_walks: int, walk_length: int,
+                               restart_prob: float = 0.5, random_seed: Union[int, None] = None,
+                               need_center_local_output: bool = False):
+        """Extension: ``pinsage_neighbors`` in the layout of the one-hop samplers.
+        -> csr_row_ptr int32 [n + 1], sampled_nodes[, center_node_local_id], importance fp32 [E]: the kept neighbours in row
+        order (most visited first) and, per neighbour, its visit count over the sum of its centre's kept counts."""
+        nodes, counts = self.pinsage_neighbors(center_nodes, num_neighbors, num_walks=num_walks, walk_length=walk_length,
+                                               restart_prob=restart_prob, random_seed=random_seed)
+        kept = nodes >= 0
+        offsets = torch.zeros(nodes.shape[0] + 1, device=nodes.device, dtype=torch.int32)
+        offsets[1:] = torch.cumsum(kept.sum(dim=1), 0)
+        importance = (counts.float() / counts.sum(dim=1, keepdim=True).clamp(min=1).float())[kept]
+        out = (offsets, nodes[kept])
+        if need_center_local_output:
+            out += (torch.nonzero(kept)[:, 0].to(torch.int32),)
+        return out + (importance,)
+
+    def multilayer_pinsage_sample(self, node_ids: torch.Tensor, num_neighbors: List[int], *, num_walks: int, walk_length: int,
+                                  restart_prob: float = 0.5, random_seeds: Optional[Sequence[int]] = None):
+        """Extension: len(num_neighbors) hops of importance neighbourhoods outwards from node_ids, hop by hop with
+        append_unique. Returns the four lists of ``multilayer_sample_without_replacement`` (OUTERMOST layer first) and a fifth:
+        per layer the importance fp32 [E] aligned with that layer's csr_col_ind, the weights of an edge-weighted layer."""
+        hops = len(num_neighbors)
+        if random_seeds is not None:
+            assert len(random_seeds) == hops, "one seed per hop"
+        layers, importances = [None] * hops, [None] * hops
+        frontier = node_ids
+        for depth, fanout in enumerate(num_neighbors):          # depth 0 = next to the seeds = layer hops - 1
+            offsets, neighbours, centre_lid, importance = self.pinsage_sample_one_hop(
+                frontier, fanout, num_walks=num_walks, walk_length=walk_length, restart_prob=restart_prob,
+                random_seed=None if random_seeds is None else random_seeds[depth], need_center_local_output=True)
+            widened, neighbour_pos = graph_ops.append_unique(frontier, neighbours.to(frontier.dtype),
+                                                             need_neighbor_raw_to_unique=True)
+            layers[hops - 1 - depth] = _Hop(widened, torch.stack([neighbour_pos, centre_lid]), offsets, neighbour_pos)
+            importances[hops - 1 - depth] = importance
+            frontier = widened
+        return _layer_lists(layers, node_ids) + (importances,)
+
     # ------------------------------------------------------------------------------------------ subgraphs
     def induced_subgraph(self, nodes: torch.Tensor, *, need_edge_output: bool = False,
                          edge_attr_names: Optional[Sequence[str]] = None):

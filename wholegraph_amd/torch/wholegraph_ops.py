@@ -420,6 +420,37 @@ def negative_sample(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, src_nodes_tens
     return negatives
 
 
+RWR_MAX_VISITS, RWR_MAX_NEIGHBORS = 2048, 64
+
+
+def rwr_top_neighbors(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, seed_nodes_tensor: torch.Tensor, num_walks: int,
+                      walk_length: int, restart_prob: float, num_neighbors: int, random_seed: Union[int, None] = None):
+    """Extension (wholememory_ext_csr_rwr_top_neighbors, include/wholememory/wholegraph_amd_ext.h section 2s): the importance
+    neighbourhood of PinSAGE. From every seed `num_walks` random walks with restart of `walk_length` steps (at most 2048 steps
+    per seed), the visits counted on chip, as ONE launch with no host round trip. Returns (nodes [n, num_neighbors] in
+    csr_col_ptr's dtype, counts int32 [n, num_neighbors]): per seed the most visited nodes, by count descending, then by id;
+    -1 / 0 behind the last visited node and for a seed that is not a node. Arrivals at the seed itself are not counted; a walker
+    that cannot step returns to the seed. Row i depends on (random_seed, i) alone, not on the size of the batch."""
+    if int(num_walks) < 1 or int(walk_length) < 1 or int(num_walks) * int(walk_length) > RWR_MAX_VISITS:
+        raise ValueError("num_walks and walk_length must be at least 1 and num_walks * walk_length at most %d, got %r and %r"
+                         % (RWR_MAX_VISITS, num_walks, walk_length))
+    if not 1 <= int(num_neighbors) <= RWR_MAX_NEIGHBORS:
+        raise ValueError("num_neighbors must lie in 1 .. %d, got %r" % (RWR_MAX_NEIGHBORS, num_neighbors))
+    if not 0.0 <= float(restart_prob) < 1.0:
+        raise ValueError("restart_prob must lie in [0, 1), got %r" % (restart_prob,))
+    if seed_nodes_tensor.dim() != 1:
+        raise ValueError("seed_nodes_tensor must be 1-D, got %d dimensions" % seed_nodes_tensor.dim())
+    row, col = _handle(wm_csr_row_ptr_tensor), _handle(wm_csr_col_ptr_tensor)
+    n, top = seed_nodes_tensor.shape[0], int(num_neighbors)
+    nodes = torch.empty((n, top), device=op_device(), dtype=_col_dtype(col))
+    counts = torch.empty((n, top), device=op_device(), dtype=torch.int32)
+    ws, wn, wc = wrap_torch_tensor(seed_nodes_tensor), wrap_torch_tensor(nodes), wrap_torch_tensor(counts)
+    wmb.check(wmb.lib().wholememory_ext_csr_rwr_top_neighbors(
+        row, col, ws.handle, int(num_walks), int(walk_length), C.c_double(float(restart_prob)), top, _seed64(random_seed),
+        wn.handle, wc.handle, C.c_void_p(get_stream())))
+    return nodes, counts
+
+
 def induced_subgraph(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, nodes_tensor: torch.Tensor, *, need_edge_output: bool = False):
     """Extension (wholememory_ext_csr_induced_subgraph, include/wholememory/wholegraph_amd_ext.h section 2q): every graph edge
     among `nodes` as one local CSR block, the batch of subgraph-wise training. Returns (offsets int32 [n + 1], col int32 [m][,

@@ -38,6 +38,8 @@
  *      neighbours whose edge is not in the centre's future, uniformly or the latest (TGN, TGAT).
  *      (2s) PinSAGE importance neighbourhoods over the same graph: per seed, random walks with restart, the visits counted,
  *      and the T most visited nodes with their counts, as one launch (also a Monte-Carlo personalised PageRank).
+ *      (2t) per-relation fan-out neighbour sampling over the same graph with a relation per edge: per centre, up to f_r
+ *      neighbours of every relation r, uniformly without replacement (the sampler of RGCN; DGL's per-etype fan-outs).
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -1492,6 +1494,63 @@ enum wholememory_error_code_t wholememory_ext_csr_rwr_top_neighbors(wholememory_
                                                                     wholememory_tensor_t output_nodes_tensor,
                                                                     wholememory_tensor_t output_counts_tensor,
                                                                     void* stream);
+
+/* ---- (2t) per-relation fan-out neighbour sampling over a CSR graph held in WholeMemory ------------------------------------- */
+/* The sampler of a model that trains on a typed graph (RGCN; DGL's per-etype fan-outs, PyG's hetero NeighborLoader): every
+ * relation r has a fan-out f_r of its own, so that a relation which holds few of a row's edges is still sampled. For centre i
+ * the op returns up to f_r neighbours of center_nodes[i] of every relation r. Graph tensors are as (2r): row_ptr int64
+ * [n_nodes + 1], col_ind int32 or int64 [n_edges], and edge_type int32 [n_edges], one entry per edge position; all three
+ * CONTINUOUS or CHUNKED, in device or host memory, or plain device arrays wrapped with wholememory_make_tensor_from_pointer.
+ * center_nodes is int32 or int64 [n], on the device. The outputs follow the samplers: output_offset_tensor is the caller's,
+ * int32 with at least n + 1 entries, on the device; dest (col_ind's dtype) and, with a context for them, center_localid int32,
+ * edge_gid int64 and edge_type_out int32 are allocated through p_env_fns once the total is known.
+ *
+ * Parameter limits. R = num_relations in 1 .. 64; fanouts is a host array of R ints, each f_r in 0 .. 64, with F = sum f_r in
+ * 1 .. 64 (the selection holds its F candidates in the registers of one wave); n * F < 2^31, so that the total fits the int32
+ * scan. f_r = 0: relation r is never sampled.
+ *
+ * Row of centre i, with u = center_nodes[i]:
+ *   - the row is empty when u is outside [0, n_nodes);
+ *   - the row is empty when (s, e) = (row_ptr[u], row_ptr[u + 1]) does not satisfy 0 <= s <= e <= n_edges and e - s < 2^31
+ *     (the rule of (2o), (2q) and (2r));
+ *   - a col_ind entry is copied, never used as an index.
+ * Liveness. Neighbour j sits at position s + j, with ty = edge_type[s + j]. It is live when 0 <= ty < R and f_ty > 0. A type
+ * outside [0, R) contributes nothing: the rule of (2j).
+ * E_ir is the number of live neighbours of centre i with relation r.
+ * Counts. c_i = sum over r of min(E_ir, f_r). offsets is the exclusive prefix of the c_i, offsets[n] the total.
+ * Selection where E_ir > f_r. r(i, j) is the first 32-bit output of stream(seed, i, j + 1) of (2m). The f_r live neighbours of
+ * relation r with the largest composite (uint64(r(i, j)) << 32) | (0xFFFFFFFF - j) are chosen: the largest draws, ties to the
+ * lowest j. That is the strategy-0 key of (2r): with R = 1 and fanouts = {M} the op IS (2r) with every edge eligible, bit for
+ * bit. A neighbour that is not live shifts no one else's draw.
+ * Output order. Within a centre the output is in ascending j, whether or not a selection took place. center_localid[k] = i,
+ * edge_gid[k] = s + j, edge_type_out[k] = edge_type[s + j]. The result depends on (seed, i, j), the graph and the types only,
+ * not on n or on the launch geometry: the rows of the first 100 centres of a batch of 512 equal a batch of those 100.
+ *
+ * The call makes one host round trip, for the total: the count is queued, the stream is synchronised, the outputs are
+ * allocated, the selection is queued. It then returns with the outputs complete, or, after
+ * wholememory_ext_set_async_completion(1), with the selection queued on `stream`, exactly as the samplers do.
+ *
+ * Errors, in this order; every answer before any device work. INVALID_INPUT: a NULL row_ptr, col_ind, edge_type,
+ * center_nodes, offset tensor, fanouts, p_env_fns or output_dest_memory_context; one of the five tensors not 1-D; R, an f_r
+ * or F outside the limits; n >= 2^31 - 1 or n * F >= 2^31; edge_type not one entry per edge; an offset tensor with fewer than
+ * n + 1 entries. LOGIC_ERROR: row_ptr not int64, col_ind or center_nodes not int32 / int64, edge_type or offsets not int32.
+ * INVALID_INPUT for a HIERARCHY tensor. NOT_IMPLEMENTED for a DISTRIBUTED tensor. NOT_SUPPORTED, nothing queued, when the
+ * device backend has no such kernels. n = 0 succeeds: it writes offsets[0] = 0 and allocates empty outputs. */
+enum wholememory_error_code_t wholememory_ext_csr_typed_sample(
+  wholememory_tensor_t wm_csr_row_ptr_tensor,
+  wholememory_tensor_t wm_csr_col_ptr_tensor,
+  wholememory_tensor_t wm_csr_edge_type_tensor, /* int32, one entry per edge */
+  wholememory_tensor_t center_nodes_tensor,     /* [n] int32 / int64, device */
+  int num_relations,                            /* R in 1 .. 64 */
+  const int* fanouts,                           /* host [R], each 0 .. 64, their sum 1 .. 64 */
+  unsigned long long random_seed,
+  wholememory_tensor_t output_offset_tensor,    /* int32, at least n + 1 entries, device */
+  void* output_dest_memory_context,             /* col_ind's dtype [total] */
+  void* output_center_localid_memory_context,   /* int32 [total] or NULL */
+  void* output_edge_gid_memory_context,         /* int64 [total] or NULL: positions in csr_col_ptr */
+  void* output_edge_type_memory_context,        /* int32 [total] or NULL: the relation of each sampled edge */
+  wholememory_env_func_t* p_env_fns,
+  void* stream);
 
 /* ---- (3) testing seam ---------------------------------------------------------------------- */
 /* Replaces the device backend. Refuses (WHOLEMEMORY_NOT_SUPPORTED) unless the environment has

@@ -128,6 +128,9 @@ struct wm_csr_graph {
   // optional per-edge timestamps (int64), same indexing as csr_col_ptr; an empty time_gref where the call has none
   wholememory_gref_t time_gref;
   int64_t time_storage_offset;
+  // optional per-edge relation types (int32), same indexing as csr_col_ptr; an empty type_gref where the call has none
+  wholememory_gref_t type_gref;
+  int64_t type_storage_offset;
 };
 
 // neighbour sampling on such a graph (the weights: sample_weighted only)
@@ -527,6 +530,25 @@ struct wm_tsample_args : wm_csr_graph {
   int64_t* out_edge_gid;        // [total] or nullptr
 };
 
+// per-relation fan-out neighbour sampling on such a graph (kernels/tysample.hip, wholegraph_amd_ext.h section 2t; the weights
+// and timestamps stay empty, the types are set): per centre i and relation r the live neighbours of centers[i] of type r, at
+// most fanouts[r] of them, all relations together in row order. Two steps around the host learning the size: count, select
+struct wm_tysample_args : wm_csr_graph {
+  const void* centers;          // [n] device
+  wholememory_dtype_t center_dtype;
+  int64_t n;                    // centres; n > 0 and n * F < 2^31
+  int num_relations;            // R in 1 .. 64
+  const int* fanouts;           // host [R]: each 0 .. 64, their sum F in 1 .. 64
+  uint64_t random_seed;
+  void* workspace;              // tysample_workspace_bytes(n) bytes (written by count, read by select)
+  int* counts;                  // [n + 1] device: entries per centre, counts[n] = 0 (written by count)
+  const int* offsets;           // [n + 1] device: exclusive prefix of counts (read by select)
+  void* out_ids;                // [total] col_dtype
+  int* out_center_lid;          // [total] or nullptr
+  int64_t* out_edge_gid;        // [total] or nullptr
+  int* out_edge_type;           // [total] or nullptr
+};
+
 // PinSAGE importance neighbourhoods on such a graph (kernels/rwr.hip, wholegraph_amd_ext.h section 2s; the weights stay empty):
 // per seed, num_walks random walks with restart of walk_length steps, the visits counted, the num_neighbors most visited nodes
 // with their counts. One launch; nothing is allocated and nothing read back
@@ -831,6 +853,11 @@ struct wm_device_backend {
   int (*tsample_select)(const wm_tsample_args* a, void* stream);
   // ---- PinSAGE importance neighbourhoods (kernels/rwr.hip, wholegraph_amd_ext.h section 2s); nullptr in a backend without it ----
   int (*rwr_top)(const wm_rwr_args* a, void* stream);
+  // ---- per-relation fan-out neighbour sampling (kernels/tysample.hip, wholegraph_amd_ext.h section 2t); nullptr in a backend
+  // without it ---- count writes a->counts and the workspace's flag bytes, select the outputs
+  size_t (*tysample_workspace_bytes)(int64_t n);
+  int (*tysample_count)(const wm_tysample_args* a, void* stream);
+  int (*tysample_select)(const wm_tysample_args* a, void* stream);
 };
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // wholegraph_amd — what the ops over the WholeMemory CSR graph share on the host (graph_ops.cpp: the two samplers, the fused
 // hop, the multi-hop chain, the random walks, the node2vec walks, negative sampling, the induced subgraph, the temporal
-// sampler, the importance neighbourhoods): the graph tensors of one call, checked, and the one place that turns them into the
+// sampler, the importance neighbourhoods, the per-relation sampler): the graph tensors of one call, checked, and the one place that turns them into the
 // backend's wm_csr_graph. The checks are separate steps because every entry point keeps its own ORDER of answers (the samplers
 // judge placement before dtypes before sizes, as the reference does; the walks, the negatives, the induced subgraph and the
 // temporal sampler judge shapes and sizes before dtypes before placement: wholegraph_amd_ext.h sections 2m - 2o, 2q and 2r),
@@ -58,7 +58,7 @@ inline csr_placement placement_of(std::initializer_list<wholememory_tensor_t> te
   return worst;
 }
 
-enum class csr_tensors { row_col, weights, all, row_col_time };   // which of a graph's tensors a placement step judges
+enum class csr_tensors { row_col, weights, all, row_col_time, row_col_type };   // which of a graph's tensors a placement step judges
 
 // The graph tensors of one call. Every step answers SUCCESS or what is wrong; the plain ops report it (the code the step
 // names, with a message), the fused hop and the chain DECLINE it (`declines`: NOT_SUPPORTED, no message — the caller takes
@@ -68,7 +68,9 @@ struct checked_graph {
   bool declines;
   // per-edge timestamps, set by name after the braces (`g.time = ...`) by the one entry that has them: nullptr otherwise
   wholememory_tensor_t time = nullptr;
-  wholememory_array_description_t row_desc{}, col_desc{}, weight_desc{}, time_desc{};
+  // per-edge relation types, likewise (`g.type = ...`)
+  wholememory_tensor_t type = nullptr;
+  wholememory_array_description_t row_desc{}, col_desc{}, weight_desc{}, time_desc{}, type_desc{};
 
 #define WM_CSR_ANSWER(code, ...)                          \
   do {                                                    \
@@ -97,7 +99,20 @@ struct checked_graph {
     return array_of(time, "wm_csr_edge_time_tensor", &time_desc, &err) ? WHOLEMEMORY_SUCCESS : err;
   }
 
+  wholememory_error_code_t type_array()
+  {
+    wholememory_error_code_t err = WHOLEMEMORY_SUCCESS;
+    return array_of(type, "wm_csr_edge_type_tensor", &type_desc, &err) ? WHOLEMEMORY_SUCCESS : err;
+  }
+
   // (b)
+  wholememory_error_code_t one_type_per_edge() const
+  {
+    if (type_desc.size != col_desc.size)
+      WM_CSR_ANSWER(WHOLEMEMORY_INVALID_INPUT, "wm_csr_edge_type_tensor must have one type per edge (%ld vs %ld)",
+                    static_cast<long>(type_desc.size), static_cast<long>(col_desc.size));
+    return WHOLEMEMORY_SUCCESS;
+  }
   wholememory_error_code_t one_time_per_edge() const
   {
     if (time_desc.size != col_desc.size)
@@ -141,6 +156,13 @@ struct checked_graph {
     return WHOLEMEMORY_SUCCESS;
   }
 
+  wholememory_error_code_t type_dtype() const
+  {
+    if (type_desc.dtype != WHOLEMEMORY_DT_INT)
+      WM_CSR_ANSWER(WHOLEMEMORY_LOGIC_ERROR, "wm_csr_edge_type_tensor must be int32, got %d", static_cast<int>(type_desc.dtype));
+    return WHOLEMEMORY_SUCCESS;
+  }
+
   // (d) HIERARCHY is INVALID_INPUT. DISTRIBUTED is the caller's where it has a gather route (*via_gather says whether to
   // take it), else NOT_IMPLEMENTED with the caller's sentence
   wholememory_error_code_t placement(csr_tensors which, const char* no_route, bool* via_gather = nullptr) const
@@ -148,6 +170,7 @@ struct checked_graph {
     const csr_placement p = which == csr_tensors::row_col        ? placement_of({row, col})
                             : which == csr_tensors::weights      ? placement_of({weight})
                             : which == csr_tensors::row_col_time ? placement_of({row, col, time})
+                            : which == csr_tensors::row_col_type ? placement_of({row, col, type})
                                                                  : placement_of({row, col, weight});
     if (p == csr_placement::hierarchy) WM_CSR_ANSWER(WHOLEMEMORY_INVALID_INPUT, "Memory type not supported.");
     if (via_gather != nullptr) {
@@ -180,6 +203,10 @@ struct checked_graph {
     if (time != nullptr) {
       WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(time, &g->time_gref));
       g->time_storage_offset = time_desc.storage_offset;
+    }
+    if (type != nullptr) {
+      WHOLEMEMORY_RETURN_ON_FAIL(tensor_mapped_gref(type, &g->type_gref));
+      g->type_storage_offset = type_desc.storage_offset;
     }
     return WHOLEMEMORY_SUCCESS;
   }

@@ -24,6 +24,7 @@
 #include "pcg.hpp"
 #include "rwr.hpp"
 #include "tsample.hpp"
+#include "tysample.hpp"
 #include "walk_n2v.hpp"
 
 namespace {
@@ -631,6 +632,116 @@ wholememory_error_code_t wholememory_ext_csr_temporal_sample(
                 (output_edge_gid_memory_context != nullptr && a.out_edge_gid == nullptr)))
     return WHOLEMEMORY_OUT_OF_MEMORY;
   if (m > 0) WM_BK(bk->tsample_select(&a, stream));
+  // as the sampler: complete on return, unless the host framework has declared its allocator ordered on `stream`
+  if (drain) WM_BK(bk->stream_sync(stream));
+  return WHOLEMEMORY_SUCCESS;
+  WM_API_END
+}
+
+// Per-relation fan-out neighbour sampling (extension, wholegraph_amd_ext.h section 2t; kernels/tysample.hip): per centre and
+// relation r, the live neighbours of type r, at most fanouts[r] of them. The flow of the temporal sampler: count per centre,
+// scan into the caller's offsets, ONE host round trip for the size, outputs from the caller's allocator, select. n * F < 2^31
+// is answered with the arguments, so the scan's last entry is the total and every answer comes before any device work.
+wholememory_error_code_t wholememory_ext_csr_typed_sample(
+  wholememory_tensor_t wm_csr_row_ptr_tensor, wholememory_tensor_t wm_csr_col_ptr_tensor, wholememory_tensor_t wm_csr_edge_type_tensor,
+  wholememory_tensor_t center_nodes_tensor, int num_relations, const int* fanouts, unsigned long long random_seed,
+  wholememory_tensor_t output_offset_tensor, void* output_dest_memory_context, void* output_center_localid_memory_context,
+  void* output_edge_gid_memory_context, void* output_edge_type_memory_context, wholememory_env_func_t* p_env_fns, void* stream)
+{
+  WM_API_BEGIN
+  if (p_env_fns == nullptr || output_dest_memory_context == nullptr || fanouts == nullptr) return WHOLEMEMORY_INVALID_INPUT;
+  wholememory_error_code_t err = WHOLEMEMORY_SUCCESS;
+  checked_graph g{wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, nullptr, false};
+  g.type = wm_csr_edge_type_tensor;
+  wholememory_array_description_t center_desc, offset_desc;
+  WHOLEMEMORY_RETURN_ON_FAIL(g.arrays());
+  WHOLEMEMORY_RETURN_ON_FAIL(g.type_array());
+  if (!array_of(center_nodes_tensor, "center_nodes_tensor", &center_desc, &err)) return err;
+  if (!array_of(output_offset_tensor, "output_offset_tensor", &offset_desc, &err)) return err;
+  wm::ty_fanouts f{};
+  if (!wm::ty_fanouts_ok(num_relations, fanouts, &f)) {
+    WM_ERROR("num_relations must be in [1, %d], every fan-out in [0, %d] and their sum in [1, %d] (num_relations = %d)",
+             wm::kTysampleMaxRelations, wm::kTysampleMaxFanout, wm::kTysampleMaxFanout, num_relations);
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  const int64_t n = center_desc.size;
+  if (g.row_desc.size < 1) {
+    WM_ERROR("wm_csr_row_ptr_tensor has no entry: a graph of n_nodes nodes has n_nodes + 1");
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  if (n < 0 || n >= (INT64_C(1) << 31) - 1 || n > ((INT64_C(1) << 31) - 1) / f.total) {
+    WM_ERROR("%ld centres with fan-outs of %d in all: n must be below 2^31 - 1 and n * F below 2^31", static_cast<long>(n), f.total);
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  WHOLEMEMORY_RETURN_ON_FAIL(g.one_type_per_edge());
+  if (offset_desc.size < n + 1) {
+    WM_ERROR("output_offset_tensor needs %ld entries, has %ld", static_cast<long>(n + 1), static_cast<long>(offset_desc.size));
+    return WHOLEMEMORY_INVALID_INPUT;
+  }
+  WHOLEMEMORY_RETURN_ON_FAIL(g.row_dtype());
+  WHOLEMEMORY_RETURN_ON_FAIL(g.col_and_id_dtype(center_desc.dtype, "center nodes"));
+  WHOLEMEMORY_RETURN_ON_FAIL(g.type_dtype());
+  if (offset_desc.dtype != WHOLEMEMORY_DT_INT) {
+    WM_ERROR("output_offset_tensor must be int32, got %d", static_cast<int>(offset_desc.dtype));
+    return WHOLEMEMORY_LOGIC_ERROR;
+  }
+  WHOLEMEMORY_RETURN_ON_FAIL(g.placement(csr_tensors::row_col_type,
+                                         "per-relation fan-out sampling on DISTRIBUTED tensors is not implemented"));
+  const auto* bk = backend();
+  if (bk->tysample_workspace_bytes == nullptr || bk->tysample_count == nullptr || bk->tysample_select == nullptr ||
+      bk->exclusive_scan_i32 == nullptr)
+    return WHOLEMEMORY_NOT_SUPPORTED;
+  int* offsets = static_cast<int*>(wholememory_tensor_get_data_pointer(output_offset_tensor));
+  if (offsets == nullptr) return WHOLEMEMORY_INVALID_INPUT;
+  const bool drain = !async_completion_enabled() || debug_sync_enabled();
+  void* const optional_ctx[3]            = {output_center_localid_memory_context, output_edge_gid_memory_context, output_edge_type_memory_context};
+  const wholememory_dtype_t optional_dt[3] = {WHOLEMEMORY_DT_INT, WHOLEMEMORY_DT_INT64, WHOLEMEMORY_DT_INT};
+  if (n == 0) {
+    WM_BK(bk->memset_async(offsets, 0, sizeof(int), stream));
+    (void)output_alloc(p_env_fns, output_dest_memory_context, 0, g.col_desc.dtype);
+    for (int k = 0; k < 3; k++)
+      if (optional_ctx[k] != nullptr) (void)output_alloc(p_env_fns, optional_ctx[k], 0, optional_dt[k]);
+    if (drain) WM_BK(bk->stream_sync(stream));
+    return WHOLEMEMORY_SUCCESS;
+  }
+  wm_tysample_args a{};
+  WHOLEMEMORY_RETURN_ON_FAIL(g.fill(&a));
+  a.centers       = wholememory_tensor_get_data_pointer(center_nodes_tensor);
+  a.center_dtype  = center_desc.dtype;
+  a.n             = n;
+  a.num_relations = num_relations;
+  a.fanouts       = fanouts;
+  a.random_seed   = random_seed;
+  a.offsets       = offsets;
+  if (a.centers == nullptr) return WHOLEMEMORY_INVALID_INPUT;
+
+  temp_mem ws_mem(p_env_fns), counts_mem(p_env_fns), scan_mem(p_env_fns), host_mem(p_env_fns);
+  a.workspace          = ws_mem.device(static_cast<int64_t>(bk->tysample_workspace_bytes(n)), WHOLEMEMORY_DT_INT8);
+  a.counts             = static_cast<int*>(counts_mem.device(n + 1, WHOLEMEMORY_DT_INT));
+  const size_t scan_ws = bk->scan_i32_workspace_bytes(n + 1);
+  void* scan_ws_ptr    = scan_mem.device(static_cast<int64_t>(scan_ws), WHOLEMEMORY_DT_INT8);
+  int* total           = static_cast<int*>(host_mem.pinned(1, WHOLEMEMORY_DT_INT));
+  if (a.workspace == nullptr || a.counts == nullptr || scan_ws_ptr == nullptr || total == nullptr) return WHOLEMEMORY_OUT_OF_MEMORY;
+
+  // centres counted, offsets, and their last entry on the host: the one round trip of the call
+  WM_BK(bk->tysample_count(&a, stream));
+  WM_BK(bk->exclusive_scan_i32(a.counts, offsets, n + 1, scan_ws_ptr, scan_ws, stream));
+  WM_BK(bk->memcpy_async(total, offsets + n, sizeof(int), stream));
+  WM_BK(bk->stream_sync(stream));
+  const int64_t m = *total;
+  if (m < 0) return WHOLEMEMORY_LOGIC_ERROR;   // (n * F < 2^31: the scan cannot have wrapped)
+  a.out_ids = output_alloc(p_env_fns, output_dest_memory_context, m, a.col_dtype);
+  void* optional_out[3] = {nullptr, nullptr, nullptr};
+  for (int k = 0; k < 3; k++) {
+    if (optional_ctx[k] == nullptr) continue;
+    optional_out[k] = output_alloc(p_env_fns, optional_ctx[k], m, optional_dt[k]);
+    if (m > 0 && optional_out[k] == nullptr) return WHOLEMEMORY_OUT_OF_MEMORY;
+  }
+  if (m > 0 && a.out_ids == nullptr) return WHOLEMEMORY_OUT_OF_MEMORY;
+  a.out_center_lid = static_cast<int*>(optional_out[0]);
+  a.out_edge_gid   = static_cast<int64_t*>(optional_out[1]);
+  a.out_edge_type  = static_cast<int*>(optional_out[2]);
+  if (m > 0) WM_BK(bk->tysample_select(&a, stream));
   // as the sampler: complete on return, unless the host framework has declared its allocator ordered on `stream`
   if (drain) WM_BK(bk->stream_sync(stream));
   return WHOLEMEMORY_SUCCESS;

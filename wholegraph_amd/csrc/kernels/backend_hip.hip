@@ -117,6 +117,9 @@ size_t hip_tsample_workspace_bytes(int64_t n);
 int hip_tsample_count(const wm_tsample_args* a, void* stream);
 int hip_tsample_select(const wm_tsample_args* a, void* stream);
 int hip_rwr_top(const wm_rwr_args* a, void* stream);
+size_t hip_tysample_workspace_bytes(int64_t n);
+int hip_tysample_count(const wm_tysample_args* a, void* stream);
+int hip_tysample_select(const wm_tysample_args* a, void* stream);
 
 namespace {
 
@@ -334,6 +337,9 @@ const wm_device_backend kHipBackend = {
   hip_tsample_count,
   hip_tsample_select,
   hip_rwr_top,
+  hip_tysample_workspace_bytes,
+  hip_tysample_count,
+  hip_tysample_select,
 };
 
 }  // namespace

@@ -38,14 +38,6 @@ static_assert(kTsCountGroup >= 2 && kTsCountGroup <= 64 && (kTsCountGroup & (kTs
 
 }  // namespace
 
-// the two-word key of tsample.hpp as top_merge.cuh's key type
-__device__ __forceinline__ ts_key top_key_max(ts_key a, ts_key b) { return ts_key_max(a, b); }
-__device__ __forceinline__ ts_key top_key_min(ts_key a, ts_key b) { return ts_key_min(a, b); }
-__device__ __forceinline__ ts_key top_key_xor(ts_key a, int j)
-{
-  return {__shfl_xor(static_cast<unsigned long long>(a.hi), j, 64), __shfl_xor(a.lo, j, 64)};
-}
-
 namespace {
 
 constexpr size_t ts_align(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
@@ -153,22 +145,6 @@ __global__ __launch_bounds__(64) void tsample_total_kernel(const int64_t* wave_s
   if (threadIdx.x == 0) *total = sum;
 }
 
-// v of the G lanes of a group in ascending order, lane 0 the smallest
-template <int G>
-__device__ __forceinline__ uint32_t ts_sort_ascending(uint32_t v, int gl)
-{
-#pragma unroll
-  for (int k = 2; k <= G; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const uint32_t o    = __shfl_xor(v, j, 64);
-      const bool keep_min = ((gl & k) == 0) == ((gl & j) == 0);   // ascending where (gl & k) == 0; k == G: everywhere
-      v                   = keep_min ? min(v, o) : max(v, o);
-    }
-  }
-  return v;
-}
-
 template <typename IdT, typename ColT, int G>
 __global__ __launch_bounds__(kTsBlock) void tsample_select_kernel(ts_params p)
 {
@@ -227,7 +203,7 @@ __global__ __launch_bounds__(kTsBlock) void tsample_select_kernel(ts_params p)
     }
     if (__any(pick)) {
       // the winners in ascending position; with fewer than M keys (the graph changed under the call) the rest are kNoPos
-      const uint32_t j = ts_sort_ascending<G>(pick && gl < p.M && top.lo != 0 ? ts_key_position(top) : kNoPos, gl);
+      const uint32_t j = top_sort_ascending<G>(pick && gl < p.M && top.lo != 0 ? ts_key_position(top) : kNoPos, gl);
       if (pick && gl < p.M && j < static_cast<uint32_t>(N)) emit(gl, j);
     }
   }

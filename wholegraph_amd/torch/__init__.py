@@ -18,7 +18,9 @@ the ``node2vec.Node2Vec`` model that train embeddings on the walks and negatives
 ``GraphStructure.saint_random_walk_subgraph``: subgraph-wise training; and ``temporal.TimeEncoder`` and
 ``temporal.TemporalGNNModel``, ``EdgeGATConv`` layers over the temporal trees of ``GraphStructure.multilayer_temporal_sample``,
 whose edges never lie in their centre's future; and ``pinsage.PinSAGEModel``, ``EdgeWeightedSAGEConv`` layers over the
-importance neighbourhoods of ``GraphStructure.multilayer_pinsage_sample``). GAT in
+importance neighbourhoods of ``GraphStructure.multilayer_pinsage_sample``; and, for model "rgcn", a fan-out per relation:
+``GraphStructure.multilayer_typed_sample`` on ``wholegraph_ops.typed_sample_without_replacement``, chosen by
+``args.relation_fanouts``). GAT in
 ``HomoGNNModel``, the dgl / pyg / wg routes, data loaders, launch helpers and option parsers of the reference are outside this build's scope.
 """
 from . import comm, embedding, graph_ops, graph_structure, initialize, tensor, utils, wholegraph_ops, wholememory_ops

@@ -122,11 +122,26 @@ def layer_forward(layer, x_feat, x_target_feat, sub_graph):
     return layer(x_feat, sub_graph[0], sub_graph[1], sub_graph[2])
 
 
+def _checked_relation_fanouts(relation_fanouts, num_layer, num_relations):
+    """args.relation_fanouts of model "rgcn": None, or one list of num_relations fan-outs per layer (entry 0 the hop next to
+    the seeds, as args.neighbors), each list what ``wholegraph_ops.typed_sample_without_replacement`` takes"""
+    if relation_fanouts is None:
+        return None
+    layers = [[int(f) for f in fanouts] for fanouts in relation_fanouts]
+    if len(layers) != num_layer or any(len(fanouts) != num_relations for fanouts in layers):
+        raise ValueError("relation_fanouts must hold %d lists of %d fan-outs, got %r" % (num_layer, num_relations, relation_fanouts))
+    for fanouts in layers:
+        if min(fanouts) < 0 or not 1 <= sum(fanouts) <= 64:
+            raise ValueError("the fan-outs of a layer must be >= 0 and sum to 1 .. 64, got %r" % (fanouts,))
+    return layers
+
+
 class HomoGNNModel(torch.nn.Module):
     """Node classification model over a homogeneous graph: settings from an ``args`` namespace as the reference reads them
     (hiddensize, layernum, model, classnum, dropout, neighbors, inferencesample; heads for gat). Model "rgcn" (an
     extension) also reads num_relations, edge_type_name (an integer edge attribute registered with
-    ``graph_structure.set_edge_attribute``: the relation of every graph edge) and, optionally, num_bases. Model "pna" (an
+    ``graph_structure.set_edge_attribute``: the relation of every graph edge) and, optionally, num_bases and relation_fanouts (one list of num_relations fan-outs per
+    layer: the blocks are then sampled with ``GraphStructure.multilayer_typed_sample`` instead of args.neighbors). Model "pna" (an
     extension) reads pna_delta (``cugraphops.pna_delta`` of the training graph) and, optionally, pna_aggregators and
     pna_scalers.
     ``node_embedding`` may also be a ``WholeMemoryQuantizedTensor`` (an extension: 8-bit row-quantized, frozen features):
@@ -145,7 +160,7 @@ class HomoGNNModel(torch.nn.Module):
         num_head = args.heads if attention or args.model == "transformer" else 1
         assert hidden_feat_dim % num_head == 0
         in_feat_dim = self.node_embedding.shape[1]
-        self.edge_type_name = None
+        self.edge_type_name = self.relation_fanouts = None
         if args.model == "rgcn":
             if getattr(args, "fuse_gather", False):
                 raise ValueError("fuse_gather reads layer 0's rows from the table: GraphSAGE only, not model 'rgcn'")
@@ -154,6 +169,8 @@ class HomoGNNModel(torch.nn.Module):
             if getattr(args, "edge_type_name", None) is None:
                 raise ValueError("model 'rgcn' needs args.edge_type_name (an edge attribute of the graph structure)")
             self.edge_type_name = args.edge_type_name
+            self.relation_fanouts = _checked_relation_fanouts(getattr(args, "relation_fanouts", None), args.layernum,
+                                                              args.num_relations)
             self.gnn_layers = create_rgcn_layers(in_feat_dim, hidden_feat_dim, args.classnum, args.layernum,
                                                  args.num_relations, getattr(args, "num_bases", None))
         elif args.model == "pna":
@@ -179,7 +196,11 @@ class HomoGNNModel(torch.nn.Module):
         max_neighbors = self.max_neighbors if self.training else self.max_inference_neighbors
         ids = ids.to(self.graph_structure.csr_col_ind.dtype).cuda()
         edge_attrs = None
-        if self.edge_type_name is not None:   # (model "rgcn": the relation of every sampled edge comes with its block)
+        if self.relation_fanouts is not None:   # (model "rgcn" with a fan-out per relation: the sampler delivers the relations)
+            max_neighbors = [sum(fanouts) for fanouts in self.relation_fanouts]
+            target_gids, edge_indice, csr_row_ptrs, csr_col_inds, edge_attrs = \
+                self.graph_structure.multilayer_typed_sample(ids, self.relation_fanouts, self.edge_type_name)
+        elif self.edge_type_name is not None:   # (model "rgcn": the relation of every sampled edge comes with its block)
             target_gids, edge_indice, csr_row_ptrs, csr_col_inds, edge_attrs = \
                 self.graph_structure.multilayer_sample_with_edge_attributes(ids, max_neighbors, [self.edge_type_name])
         else:

@@ -315,6 +315,44 @@ class GraphStructure(object):
         out = (gids, gtimes, edge_indice, row_ptrs, col_inds, edge_ids)
         return out if names is None else out + (attrs,)
 
+    # ------------------------------------------------------------------------------------------ per-relation fan-outs
+    def _edge_types(self, type_name: str):
+        assert type_name in self.edge_attributes, "no edge attribute named %r" % type_name
+        types = self.edge_attributes[type_name]
+        assert types.dim() == 1 and types.dtype == torch.int32, "edge attribute %r must be 1-D int32 relations" % type_name
+        return types
+
+    def typed_sample_one_hop(self, type_name: str, center_nodes_tensor: torch.Tensor, fanouts: Sequence[int], *,
+                             random_seed: Union[int, None] = None, need_center_local_output: bool = False,
+                             need_edge_output: bool = False, need_type_output: bool = True):
+        """Extension: for every centre up to fanouts[r] neighbours of every relation r
+        (``wholegraph_ops.typed_sample_without_replacement``); `type_name` names the int32 edge attribute that holds the
+        relation of every edge. -> csr_row_ptr, sampled_nodes[, center_node_local_id][, edge_index][, edge_type]"""
+        return wholegraph_ops.typed_sample_without_replacement(
+            self.csr_row_ptr.wmb_tensor, self.csr_col_ind.wmb_tensor, self._edge_types(type_name).wmb_tensor,
+            center_nodes_tensor, fanouts, random_seed, need_center_local_output, need_edge_output, need_type_output)
+
+    def multilayer_typed_sample(self, node_ids: torch.Tensor, fanouts_per_layer: Sequence[Sequence[int]], type_name: str, *,
+                                random_seeds: Optional[Sequence[int]] = None):
+        """Extension: len(fanouts_per_layer) hops outwards from node_ids, hop h with the per-relation fan-outs
+        fanouts_per_layer[h] (entry 0 is the hop next to the seeds), hop by hop with append_unique. Returns what
+        ``multilayer_sample_with_edge_attributes(node_ids, ..., [type_name])`` returns — its four lists and, per layer, the
+        dict {type_name: int32 [n_edges]} —, the relations being the sampler's own output, not a gather."""
+        hops = len(fanouts_per_layer)
+        if random_seeds is not None:
+            assert len(random_seeds) == hops, "one seed per hop"
+        layers, attrs = [None] * hops, [None] * hops
+        frontier = node_ids
+        for depth, fanouts in enumerate(fanouts_per_layer):          # depth 0 = next to the seeds = layer hops - 1
+            offsets, neighbours, centre_lid, edge_type = self.typed_sample_one_hop(
+                type_name, frontier, fanouts, random_seed=None if random_seeds is None else random_seeds[depth],
+                need_center_local_output=True)
+            widened, neighbour_pos = graph_ops.append_unique(frontier, neighbours, need_neighbor_raw_to_unique=True)
+            layers[hops - 1 - depth] = _Hop(widened, torch.stack([neighbour_pos, centre_lid]), offsets, neighbour_pos)
+            attrs[hops - 1 - depth] = {type_name: edge_type}
+            frontier = widened
+        return _layer_lists(layers, node_ids) + (attrs,)
+
     # ------------------------------------------------------------------------------------------ several hops
     def multilayer_sample_without_replacement(self, node_ids: torch.Tensor, max_neighbors: List[int],
                                               weight_name: Union[str, None] = None, *,

@@ -566,6 +566,49 @@ def temporal_sample_without_replacement(wm_csr_row_ptr_tensor, wm_csr_col_ptr_te
                                    need_center_local_output, need_edge_output, rule)
 
 
+TYPED_MAX_RELATIONS = 64
+TYPED_MAX_FANOUT = 64
+
+
+def _checked_fanouts(fanouts):
+    fanouts = [int(f) for f in fanouts]
+    if not 1 <= len(fanouts) <= TYPED_MAX_RELATIONS:
+        raise ValueError("fanouts must name 1 to %d relations, got %d" % (TYPED_MAX_RELATIONS, len(fanouts)))
+    if min(fanouts) < 0 or not 1 <= sum(fanouts) <= TYPED_MAX_FANOUT:
+        raise ValueError("every fan-out must be >= 0 and their sum lie in [1, %d], got %r" % (TYPED_MAX_FANOUT, fanouts))
+    return fanouts
+
+
+def typed_sample_without_replacement(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, wm_csr_edge_type_tensor,
+                                     center_nodes_tensor: torch.Tensor, fanouts, random_seed: Union[int, None] = None,
+                                     need_center_local_output: bool = False, need_edge_output: bool = False,
+                                     need_type_output: bool = True):
+    """Extension (wholememory_ext_csr_typed_sample, include/wholememory/wholegraph_amd_ext.h section 2t): per-relation fan-outs,
+    the sampler of RGCN. wm_csr_edge_type_tensor is int32, one relation per edge; fanouts[r] is the fan-out of relation r
+    (0: never sampled; at most 64 relations, the fan-outs summing to at most 64). For every centre, min(f_r, live neighbours of
+    relation r) neighbours of every relation, uniformly without replacement, all relations together in row order; an edge whose
+    type is outside [0, len(fanouts)) is never sampled. Returns (sample_offset int32 [n + 1], sampled node ids[, center local
+    id int32][, edge id int64][, edge type int32]). Centre i's samples depend on (random_seed, i) and its row alone; with one
+    relation they are those of ``temporal_sample_without_replacement`` with every edge eligible. One host round trip."""
+    fanouts = _checked_fanouts(fanouts)
+    if center_nodes_tensor.dim() != 1:
+        raise ValueError("center_nodes_tensor must be 1-D")
+    row, col, typ = _handle(wm_csr_row_ptr_tensor), _handle(wm_csr_col_ptr_tensor), _handle(wm_csr_edge_type_tensor)
+    offset = torch.empty(center_nodes_tensor.shape[0] + 1, device=op_device(), dtype=torch.int)
+    dest = TorchMemoryContext()
+    lid = TorchMemoryContext() if need_center_local_output else None
+    egid = TorchMemoryContext() if need_edge_output else None
+    etype = TorchMemoryContext() if need_type_output else None
+    wc, wo = wrap_torch_tensor(center_nodes_tensor), wrap_torch_tensor(offset)
+    wmb.check(wmb.lib().wholememory_ext_csr_typed_sample(
+        row, col, typ, wc.handle, len(fanouts), (C.c_int * len(fanouts))(*fanouts), _seed64(random_seed), wo.handle,
+        C.c_void_p(dest.get_c_context()), C.c_void_p(lid.get_c_context() if lid else 0),
+        C.c_void_p(egid.get_c_context() if egid else 0), C.c_void_p(etype.get_c_context() if etype else 0),
+        get_wholegraph_env_fns(), C.c_void_p(get_stream())))
+    out = _sample_outputs(offset, dest, lid, egid, need_center_local_output, need_edge_output)
+    return out + ((etype.get_tensor(),) if need_type_output else ())
+
+
 def generate_random_positive_int_cpu(random_seed, sub_sequence, output_random_value_count):
     output = torch.empty((output_random_value_count,), dtype=torch.int)
     w = wrap_torch_tensor(output)

@@ -40,6 +40,9 @@
  *      and the T most visited nodes with their counts, as one launch (also a Monte-Carlo personalised PageRank).
  *      (2t) per-relation fan-out neighbour sampling over the same graph with a relation per edge: per centre, up to f_r
  *      neighbours of every relation r, uniformly without replacement (the sampler of RGCN; DGL's per-etype fan-outs).
+ *      (2u) the relation-typed score of every edge of a sampled CSC block: the decoder of the knowledge-graph embedding
+ *      models TransE, DistMult, ComplEx and RotatE (forward and a deterministic backward into both row tensors and the
+ *      relation table).
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -1551,6 +1554,104 @@ enum wholememory_error_code_t wholememory_ext_csr_typed_sample(
   void* output_edge_type_memory_context,        /* int32 [total] or NULL: the relation of each sampled edge */
   wholememory_env_func_t* p_env_fns,
   void* stream);
+
+/* ---- (2u) relation-typed edge score of a sampled CSC block (`kge_score_n2n`) -------------------------------------------- */
+/* The decoder of the knowledge-graph embedding models. The block, x_src and x_dst are those of (2p): the targets have rows of
+ * their own and n_dst may exceed n_src. rel is fp32 [num_relations, rel_stride], edge_type int32 [n_edges]; every row uses
+ * F = dim columns. model: 0 distmult, 1 transe_l1, 2 transe_l2, 3 complex, 4 rotate. head_src = 0: the head h of edge e of
+ * target d is x_dst[d] and the tail t is x_src[col_ind[e]]; head_src != 0 swaps the roles. r = rel[edge_type[e]].
+ * The complex models (3, 4) read a row as [re | im]: F is even, D = F / 2 complex columns, column c is paired with column
+ * c + D, in rel too (for rotate the caller passes cat(cos(phase), sin(phase))).
+ * The contract of (2p): every `*`, `+`, `-`, `/` and sqrt below is one fp32 operation, rounded on its own (no fused
+ * multiply-add), no atomics, one fixed order for every sum, results bitwise reproducible.
+ *
+ * Every model is a compose step followed by a measure step.
+ *   compose u:  mul   u_c = h_c * r_c
+ *               add   u_c = h_c + r_c
+ *               cmul  u_re = h_re*r_re - h_im*r_im, u_im = h_re*r_im + h_im*r_re
+ *   measure:    dot   term_c = u_c * t_c; for complex rows term_c = u_re*t_re + u_im*t_im, one term per complex column.
+ *                     score = tree(term).
+ *               l1    with d = u - t: term_c = abs(d_c), score = -tree(term).
+ *               l2    with d = u - t: term_c = d_c*d_c; for complex rows term_c = d_re*d_re + d_im*d_im.
+ *                     n = sqrt(tree(term)), score = -n.
+ *   distmult = (mul, dot), transe_l1 = (add, l1), transe_l2 = (add, l2), complex = (cmul, dot), rotate = (cmul, l2).
+ * tree is the balanced tree of adjacent pairs over pow2_at_least(number of terms), absent terms +0.0: the tree of (2g), (2k)
+ * and (2p).
+ *
+ * forward: writes score [n_edges].
+ * backward: grad_score g [n_edges] and the forward's score (read by the l2 models: n = -score) -> grad_dst [n_dst,
+ * grad_dst_stride], grad_src [n_src, grad_src_stride] and grad_rel [num_relations, grad_rel_stride], each with a stride >= F.
+ * Any of them may be null and is then not computed; all null is INVALID_INPUT. Every row of a requested one is written. u is
+ * recomputed. First the gradients with respect to u and t:
+ *   dot: du_c = g * t_c, dt_c = g * u_c.
+ *   l1:  q_c = g * sgn(d_c) with sgn(0) = 0. Then du = -q, dt = q.
+ *   l2:  q_c = g * (d_c / n), and q_c = +0.0 when n == 0. Then du = -q, dt = q.
+ * Then the gradients with respect to h and r:
+ *   mul:  dh = du * r, dr = du * h.
+ *   add:  dh = dr = du.
+ *   cmul: dh_re = du_re*r_re + du_im*r_im; dh_im = du_im*r_re - du_re*r_im; dr is the same with h in place of r.
+ * The term of an edge in a row of x_dst is dh (head_src = 0) or dt, in a row of x_src the other one, in a row of rel dr. There
+ * are three sums, each in one stated order:
+ *   Per-target rows (grad_dst). Left to right in edge order. +0.0 without edges.
+ *   Per-source rows (grad_src). The order of (2p): ascending edge position within a source, left to right within chunks of
+ *   C = wholememory_ext_csc_aggregate_chunk_edges(), chunk sums added in chunk order. +0.0 for a source without edges.
+ *   grad_rel[k]. The same chunked order with the relation as the key: the edges of relation k in ascending edge position,
+ *   chunks of C, chunk sums in chunk order. +0.0 for a relation without edges.
+ * An edge_type outside [0, num_relations) scores +0.0; its term in a per-target and in a per-source sum is +0.0 in every
+ * column, and no row of grad_rel reads it (the id sort of edge_type has the key bound num_relations and leaves it out of every
+ * run). The two edge indices are built with the library's id sort, scratch from p_env_fns, each only when its gradient is asked
+ * for. col_ind is treated as by (2p).
+ * n_edges = 0 and n_dst = 0 are valid: what there is to write (the rows of the requested gradients, +0.0) is written.
+ * INVALID_INPUT, before any device work and under every backend: null pointers (row_ptr; col_ind, edge_type, score of the
+ * forward and grad_score when there are edges; score of the backward for the l2 models when there are edges; x_src with n_src
+ * > 0; x_dst with n_dst > 0; rel; p_env_fns), negative sizes, 2^31 or more edges, targets or source rows, num_relations
+ * outside [1, 2^31), dim outside [1, 2^31 / 4), an odd dim for the complex models, an unknown model and any stride smaller
+ * than dim. NOT_SUPPORTED (nothing queued) when the device backend has no such kernels. */
+enum wholememory_error_code_t wholememory_ext_csc_kge_score_forward(const int32_t* row_ptr,
+                                                                    const int32_t* col_ind,
+                                                                    const int32_t* edge_type,
+                                                                    int64_t n_edges,
+                                                                    int64_t n_dst,
+                                                                    int64_t n_src,
+                                                                    int64_t num_relations,
+                                                                    const float* x_src,
+                                                                    int64_t x_src_stride,
+                                                                    const float* x_dst,
+                                                                    int64_t x_dst_stride,
+                                                                    const float* rel,
+                                                                    int64_t rel_stride,
+                                                                    int64_t dim,
+                                                                    int model,
+                                                                    int head_src,
+                                                                    float* score,
+                                                                    struct wholememory_env_func_t* p_env_fns,
+                                                                    void* stream);
+enum wholememory_error_code_t wholememory_ext_csc_kge_score_backward(const int32_t* row_ptr,
+                                                                     const int32_t* col_ind,
+                                                                     const int32_t* edge_type,
+                                                                     int64_t n_edges,
+                                                                     int64_t n_dst,
+                                                                     int64_t n_src,
+                                                                     int64_t num_relations,
+                                                                     const float* x_src,
+                                                                     int64_t x_src_stride,
+                                                                     const float* x_dst,
+                                                                     int64_t x_dst_stride,
+                                                                     const float* rel,
+                                                                     int64_t rel_stride,
+                                                                     int64_t dim,
+                                                                     int model,
+                                                                     int head_src,
+                                                                     const float* score,
+                                                                     const float* grad_score,
+                                                                     float* grad_src,
+                                                                     int64_t grad_src_stride,
+                                                                     float* grad_dst,
+                                                                     int64_t grad_dst_stride,
+                                                                     float* grad_rel,
+                                                                     int64_t grad_rel_stride,
+                                                                     struct wholememory_env_func_t* p_env_fns,
+                                                                     void* stream);
 
 /* ---- (3) testing seam ---------------------------------------------------------------------- */
 /* Replaces the device backend. Refuses (WHOLEMEMORY_NOT_SUPPORTED) unless the environment has

@@ -331,6 +331,11 @@ PROTOTYPES = {
                                                  _vp]),
     "wholememory_ext_csc_edge_dot_backward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _i64,
                                                   _vp, _i64, _P(EnvFunc), _vp]),
+    "wholememory_ext_csc_kge_score_forward": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                                                  _i64, _i, _i, _vp, _P(EnvFunc), _vp]),
+    "wholememory_ext_csc_kge_score_backward": (_i, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                                                   _i64, _i, _i, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _P(EnvFunc),
+                                                   _vp]),
     "wholememory_ext_csc_pna_aggregate_forward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i, _f, _vp, _i64, _vp,
                                                        _vp, _vp, _vp, _P(EnvFunc), _vp]),
     "wholememory_ext_csc_pna_aggregate_backward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i, _vp, _vp, _vp, _vp,

@@ -565,6 +565,31 @@ struct wm_rwr_args : wm_csr_graph {
   int* out_counts;      // [n, T]: 0 there
 };
 
+// the relation-typed score of every edge of a sampled CSC block (kernels/kge.hip, the `kge_score_n2n` op, wholegraph_amd_ext.h
+// section 2u): wm_edot_args plus a relation table and one int32 type per edge position. rows / strides in ELEMENTS (fp32); the
+// complex models read a row as [re | im], dim / 2 columns each
+enum wm_kge_model : int { WM_KGE_DISTMULT = 0, WM_KGE_TRANSE_L1 = 1, WM_KGE_TRANSE_L2 = 2, WM_KGE_COMPLEX = 3, WM_KGE_ROTATE = 4 };
+struct wm_kge_args : wm_csc_block {
+  const int32_t* edge_type;   // [n_edges]; a type outside [0, num_relations) scores +0.0, its term in every sum is +0.0
+  int64_t dim, num_relations;
+  int model;                  // wm_kge_model
+  int head_src;               // 0: the head of an edge is its target's row, the tail its source row; 1: the roles swapped
+  const float* x_src;         // [n_src, x_src_stride], dim columns used
+  int64_t x_src_stride;
+  const float* x_dst;         // [n_dst, x_dst_stride]: row d belongs to target d
+  int64_t x_dst_stride;
+  const float* rel;           // [num_relations, rel_stride]
+  int64_t rel_stride;
+  float* score;               // [n_edges]: written by the forward, read by the backward of the l2 models
+  const float* grad;          // backward: dL/dscore [n_edges]
+  float* grad_src;            // backward: [n_src, grad_src_stride] or nullptr
+  int64_t grad_src_stride;
+  float* grad_dst;            // backward: [n_dst, grad_dst_stride] or nullptr
+  int64_t grad_dst_stride;
+  float* grad_rel;            // backward: [num_relations, grad_rel_stride] or nullptr
+  int64_t grad_rel_stride;
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -858,6 +883,14 @@ struct wm_device_backend {
   size_t (*tysample_workspace_bytes)(int64_t n);
   int (*tysample_count)(const wm_tysample_args* a, void* stream);
   int (*tysample_select)(const wm_tysample_args* a, void* stream);
+  // ---- relation-typed edge score of a sampled CSC block (kernels/kge.hip, wholegraph_amd_ext.h section 2u); nullptr in a
+  // backend without it ----
+  // forward: score. backward: whichever of grad_src, grad_dst and grad_rel is not null. ix: the index of gat_backward (read
+  // for grad_src only), rel_ix: the same index over edge_type with key bound num_relations (read for grad_rel only); each all
+  // null otherwise. workspace of kge_backward_workspace_bytes
+  int (*kge_forward)(const wm_kge_args* a, void* stream);
+  size_t (*kge_backward_workspace_bytes)(const wm_kge_args* a);
+  int (*kge_backward)(const wm_kge_args* a, const wm_edge_index& ix, const wm_edge_index& rel_ix, void* workspace, void* stream);
 };
 
 }  // extern "C"

@@ -120,6 +120,9 @@ int hip_rwr_top(const wm_rwr_args* a, void* stream);
 size_t hip_tysample_workspace_bytes(int64_t n);
 int hip_tysample_count(const wm_tysample_args* a, void* stream);
 int hip_tysample_select(const wm_tysample_args* a, void* stream);
+int hip_kge_forward(const wm_kge_args* a, void* stream);
+size_t hip_kge_backward_workspace_bytes(const wm_kge_args* a);
+int hip_kge_backward(const wm_kge_args* a, const wm_edge_index& ix, const wm_edge_index& rel_ix, void* workspace, void* stream);
 
 namespace {
 
@@ -340,6 +343,9 @@ const wm_device_backend kHipBackend = {
   hip_tysample_workspace_bytes,
   hip_tysample_count,
   hip_tysample_select,
+  hip_kge_forward,
+  hip_kge_backward_workspace_bytes,
+  hip_kge_backward,
 };
 
 }  // namespace

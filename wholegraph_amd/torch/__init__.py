@@ -14,6 +14,8 @@ layer ``cugraphops.TransformerConv`` on ``transformer_aggregation`` (model name 
 WholeMemory table, and ``quantized``, 8-bit row-quantized tables whose gather dequantizes the rows it reads; and
 ``edge_dot.edge_dot_n2n``, the score of an edge as the dot product of its endpoint rows, with ``skipgram.skipgram_block`` and
 the ``node2vec.Node2Vec`` model that train embeddings on the walks and negatives of ``GraphStructure``; and
+``kge_score.kge_score_n2n``, the relation-typed score of an edge (DistMult, TransE, ComplEx, RotatE), with ``kge.kge_block``
+and the ``kge.KGEModel`` model that trains knowledge-graph embeddings on filtered negatives; and
 ``saint.SubgraphGNNModel``, the layers above on the induced subgraphs of ``GraphStructure.induced_subgraph`` and
 ``GraphStructure.saint_random_walk_subgraph``: subgraph-wise training; and ``temporal.TimeEncoder`` and
 ``temporal.TemporalGNNModel``, ``EdgeGATConv`` layers over the temporal trees of ``GraphStructure.multilayer_temporal_sample``,
@@ -26,7 +28,7 @@ importance neighbourhoods of ``GraphStructure.multilayer_pinsage_sample``; and, 
 from . import comm, embedding, graph_ops, graph_structure, initialize, tensor, utils, wholegraph_ops, wholememory_ops
 from . import aggregation, cugraphops, edge_gat_aggregation, gat_aggregation, gather_aggregation, gnn_model
 from . import gatv2_aggregation, pna_aggregation, quantized, rel_aggregation, transformer_aggregation, weighted_aggregation
-from . import edge_dot, node2vec, pinsage, saint, skipgram, temporal
+from . import edge_dot, kge, kge_score, node2vec, pinsage, saint, skipgram, temporal
 
 _PUBLIC = {
     comm: ("WholeMemoryCommunicator create_group_communicator destroy_communicator get_global_communicator "
@@ -47,6 +49,8 @@ _PUBLIC = {
     edge_dot: "edge_dot_n2n",
     skipgram: "skipgram_block centers_of",
     node2vec: "Node2Vec",
+    kge_score: "kge_score_n2n",
+    kge: "kge_block KGEModel",
     saint: "SubgraphGNNModel",
     temporal: "TimeEncoder TemporalGNNModel",
     pinsage: "PinSAGEModel",
@@ -55,7 +59,8 @@ _PUBLIC = {
 }
 __all__ = ["graph_ops", "wholegraph_ops", "aggregation", "cugraphops", "gat_aggregation", "gnn_model", "weighted_aggregation",
            "gather_aggregation", "edge_gat_aggregation", "gatv2_aggregation", "rel_aggregation", "quantized",
-           "transformer_aggregation", "pna_aggregation", "edge_dot", "skipgram", "node2vec", "saint", "temporal", "pinsage"]
+           "transformer_aggregation", "pna_aggregation", "edge_dot", "skipgram", "node2vec", "saint", "temporal", "pinsage",
+           "kge_score", "kge"]
 for _module, _names in _PUBLIC.items():
     for _name in _names.split():
         globals()[_name] = getattr(_module, _name)

@@ -43,6 +43,8 @@
  *      (2u) the relation-typed score of every edge of a sampled CSC block: the decoder of the knowledge-graph embedding
  *      models TransE, DistMult, ComplEx and RotatE (forward and a deterministic backward into both row tensors and the
  *      relation table).
+ *      (2v) LABOR layer-neighbour sampling over the same CSR graph: one random variate per neighbour NODE, shared by all
+ *      centres of a hop, so that their samples overlap and the hop touches fewer distinct nodes (DGL's LaborSampler).
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -1652,6 +1654,56 @@ enum wholememory_error_code_t wholememory_ext_csc_kge_score_backward(const int32
                                                                      int64_t grad_rel_stride,
                                                                      struct wholememory_env_func_t* p_env_fns,
                                                                      void* stream);
+
+/* ---- (2v) LABOR layer-neighbour sampling over a CSR graph held in WholeMemory ------------------------------------------------ */
+/* Layer-neighbour sampling (Balin and Catalyurek, "Layer-Neighbor Sampling - Defusing Neighborhood Explosion in GNNs", NeurIPS
+ * 2023; DGL's LaborSampler). The samplers above draw per (centre, position), so two centres that share a neighbourhood pick
+ * different nodes from it. Here ONE variate is drawn per neighbour node and every centre of the call ranks its neighbours by
+ * it: each centre still gets a uniform sample of its own row, but the samples overlap as much as they can, and the hop hands
+ * fewer distinct nodes to append_unique and to the feature gather. Tensors, rows, outputs and completion are those of (2r)
+ * without the times: row_ptr int64 [n_nodes + 1] and col_ind int32 or int64 [n_edges], CONTINUOUS or CHUNKED, in device or
+ * host memory, or plain device arrays wrapped with wholememory_make_tensor_from_pointer; center_nodes int32 or int64 [n] on the
+ * device; output_offset_tensor the caller's, int32 with at least n + 1 entries, on the device; dest (col_ind's dtype) and, with
+ * a context for them, center_localid int32 and edge_gid int64 allocated through p_env_fns once the total is known.
+ *
+ * Row of centre i, with u = center_nodes[i]: empty when u is outside [0, n_nodes) or when (s, e) = (row_ptr[u], row_ptr[u + 1])
+ * does not satisfy 0 <= s <= e <= n_edges and e - s < 2^31 (the rule of (2o), (2q) and (2r)); else N = e - s neighbours,
+ * neighbour j at position s + j. A col_ind entry is copied, never used as an index.
+ * Variate. For a neighbour entry with value c (sign-extended to 64 bits), v(c) is the first 32-bit output of
+ * stream(seed, (uint64)c, 0) of (2m). It depends on the seed and the node id only, not on i, j, n or the launch geometry; two
+ * edges to the same node share it. M = max_sample_count.
+ * mode 0, fixed count (sequential Poisson sampling): c_i = min(N, M); M <= 0 means every neighbour; M > 64 is INVALID_INPUT, as
+ * in (2r). When N > M the M neighbours with the smallest v are chosen, ties to the lowest j: the largest composite
+ * (uint64(0xFFFFFFFF - v) << 32) | (0xFFFFFFFF - j) wins, the order of (2r)'s keys.
+ * mode 1, Poisson (the paper's LABOR-0): neighbour j is taken exactly when uint64(v) * uint64(N) < (uint64(M) << 32), in
+ * integers; a row with N <= M is taken whole. M is in 1 .. 2^31 - 1, M <= 0 is INVALID_INPUT. c_i is the number taken, about
+ * min(N, M) in expectation.
+ * Output order. Within a centre the output is in ascending j; center_localid[k] = i, edge_gid[k] = s + j. offsets is the
+ * exclusive prefix of the c_i, offsets[n] the total. The rows of the first 100 centres of a batch of 512 equal a batch of
+ * those 100; a centre that occurs twice gets the same row twice.
+ *
+ * One host round trip, for the total, and completion as in (2r) (wholememory_ext_set_async_completion).
+ *
+ * Errors, in this order; all but the last are answered before any device work. INVALID_INPUT: a NULL row_ptr, col_ind,
+ * center_nodes, offset tensor, p_env_fns or output_dest_memory_context; one of the four tensors not 1-D; mode not 0 or 1;
+ * max_sample_count > 64 in mode 0 or <= 0 in mode 1; n >= 2^31 - 1; an offset tensor with fewer than n + 1 entries.
+ * LOGIC_ERROR: row_ptr not int64, col_ind or center_nodes not int32 / int64, offsets not int32. INVALID_INPUT for a HIERARCHY
+ * tensor, NOT_IMPLEMENTED for a DISTRIBUTED one. NOT_SUPPORTED, nothing queued, when the device backend has no such kernels.
+ * INVALID_INPUT when the total is >= 2^31: answered after the count, with no output allocated. n = 0 succeeds: it writes
+ * offsets[0] = 0 and allocates empty outputs. */
+enum wholememory_error_code_t wholememory_ext_csr_labor_sample(
+  wholememory_tensor_t wm_csr_row_ptr_tensor,
+  wholememory_tensor_t wm_csr_col_ptr_tensor,
+  wholememory_tensor_t center_nodes_tensor,     /* [n] int32 / int64, device */
+  int max_sample_count,                         /* mode 0: <= 0 every neighbour, else at most 64; mode 1: >= 1 */
+  int mode,                                     /* 0: fixed count, 1: Poisson */
+  unsigned long long random_seed,
+  wholememory_tensor_t output_offset_tensor,    /* int32, at least n + 1 entries, device */
+  void* output_dest_memory_context,             /* col_ind's dtype [total] */
+  void* output_center_localid_memory_context,   /* int32 [total] or NULL */
+  void* output_edge_gid_memory_context,         /* int64 [total] or NULL: positions in csr_col_ptr */
+  wholememory_env_func_t* p_env_fns,
+  void* stream);
 
 /* ---- (3) testing seam ---------------------------------------------------------------------- */
 /* Replaces the device backend. Refuses (WHOLEMEMORY_NOT_SUPPORTED) unless the environment has

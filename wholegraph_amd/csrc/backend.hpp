@@ -549,6 +549,26 @@ struct wm_tysample_args : wm_csr_graph {
   int* out_edge_type;           // [total] or nullptr
 };
 
+// LABOR layer-neighbour sampling on such a graph (kernels/labor.hip, wholegraph_amd_ext.h section 2v; weights, timestamps and
+// types stay empty): per centre i the neighbours of centers[i] chosen by the variate of the neighbour NODE, the
+// max_sample_count smallest (mode 0) or those under max_sample_count / N (mode 1), in row order. Two steps around the host
+// learning the size: count, select
+struct wm_labor_args : wm_csr_graph {
+  const void* centers;          // [n] device
+  wholememory_dtype_t center_dtype;
+  int64_t n;                    // centres; 0 < n < 2^31 - 1
+  int max_sample_count;         // mode 0: <= 0 every neighbour, at most 64; mode 1: 1 .. 2^31 - 1
+  int mode;                     // 0: fixed count; 1: Poisson
+  uint64_t random_seed;
+  void* workspace;              // labor_workspace_bytes(n) bytes
+  int* counts;                  // [n + 1] device: entries per centre, counts[n] = 0 (written by count)
+  int64_t* total;               // one word the device can write (pinned or device): the sum of counts in 64 bits (written by count)
+  const int* offsets;           // [n + 1] device: exclusive prefix of counts (read by select)
+  void* out_ids;                // [total] col_dtype
+  int* out_center_lid;          // [total] or nullptr
+  int64_t* out_edge_gid;        // [total] or nullptr
+};
+
 // PinSAGE importance neighbourhoods on such a graph (kernels/rwr.hip, wholegraph_amd_ext.h section 2s; the weights stay empty):
 // per seed, num_walks random walks with restart of walk_length steps, the visits counted, the num_neighbors most visited nodes
 // with their counts. One launch; nothing is allocated and nothing read back
@@ -891,6 +911,11 @@ struct wm_device_backend {
   int (*kge_forward)(const wm_kge_args* a, void* stream);
   size_t (*kge_backward_workspace_bytes)(const wm_kge_args* a);
   int (*kge_backward)(const wm_kge_args* a, const wm_edge_index& ix, const wm_edge_index& rel_ix, void* workspace, void* stream);
+  // ---- LABOR layer-neighbour sampling (kernels/labor.hip, wholegraph_amd_ext.h section 2v); nullptr in a backend without it ----
+  // count writes a->counts and a->total (its partial sums go through the workspace), select the outputs
+  size_t (*labor_workspace_bytes)(int64_t n);
+  int (*labor_count)(const wm_labor_args* a, void* stream);
+  int (*labor_select)(const wm_labor_args* a, void* stream);
 };
 
 }  // extern "C"

@@ -123,6 +123,9 @@ int hip_tysample_select(const wm_tysample_args* a, void* stream);
 int hip_kge_forward(const wm_kge_args* a, void* stream);
 size_t hip_kge_backward_workspace_bytes(const wm_kge_args* a);
 int hip_kge_backward(const wm_kge_args* a, const wm_edge_index& ix, const wm_edge_index& rel_ix, void* workspace, void* stream);
+size_t hip_labor_workspace_bytes(int64_t n);
+int hip_labor_count(const wm_labor_args* a, void* stream);
+int hip_labor_select(const wm_labor_args* a, void* stream);
 
 namespace {
 
@@ -346,6 +349,9 @@ const wm_device_backend kHipBackend = {
   hip_kge_forward,
   hip_kge_backward_workspace_bytes,
   hip_kge_backward,
+  hip_labor_workspace_bytes,
+  hip_labor_count,
+  hip_labor_select,
 };
 
 }  // namespace

@@ -1,6 +1,6 @@
 // wholegraph_amd — the running top-G of a group of G lanes, shared by the units that select the largest keys of a row without
-// LDS (graph.hip: sample_weighted_small_kernel, a 64-bit key; tsample.hip and tysample.hip: a two-word key; rwr.hip: a 64-bit
-// key). The key type K has top_key_max, top_key_min and top_key_xor (the key of the lane j away): those of uint64_t and of
+// LDS (graph.hip: sample_weighted_small_kernel, a 64-bit key; tsample.hip, tysample.hip and labor.hip: a two-word key; rwr.hip:
+// a 64-bit key). The key type K has top_key_max, top_key_min and top_key_xor (the key of the lane j away): those of uint64_t and of
 // tsample.hpp's ts_key are here.
 // Lane i of the group holds the i-th largest key seen so far; a batch of G keys, one per lane, is sorted across the lanes
 // (bitonic network of shuffles) and merged: top[i] = max(top[i], batch[G - 1 - i]) holds the G largest of both as a bitonic

@@ -353,6 +353,38 @@ class GraphStructure(object):
             frontier = widened
         return _layer_lists(layers, node_ids) + (attrs,)
 
+    # ------------------------------------------------------------------------------------------ layer-neighbour sampling
+    def labor_sample_one_hop(self, center_nodes_tensor: torch.Tensor, max_sample_count: int, *, mode: str = "fixed",
+                             random_seed: Union[int, None] = None, need_center_local_output: bool = False,
+                             need_edge_output: bool = False):
+        """Extension: LABOR layer-neighbour sampling of one hop (``wholegraph_ops.labor_sample``): the centres rank their
+        neighbours by one variate per neighbour node, so their samples overlap.
+        -> csr_row_ptr, sampled_nodes[, center_node_local_id][, edge_index]"""
+        return wholegraph_ops.labor_sample(self.csr_row_ptr.wmb_tensor, self.csr_col_ind.wmb_tensor, center_nodes_tensor,
+                                           max_sample_count, random_seed, mode, need_center_local_output, need_edge_output)
+
+    def multilayer_labor_sample(self, node_ids: torch.Tensor, max_neighbors: List[int], *, mode: str = "fixed",
+                                layer_dependency: bool = False, random_seeds: Optional[Sequence[int]] = None):
+        """Extension: len(max_neighbors) LABOR hops outwards from node_ids, hop by hop with append_unique. Returns the four
+        lists of ``multilayer_sample_without_replacement``. layer_dependency: all hops share ONE seed (random_seeds then holds
+        one), so a node keeps its variate from hop to hop and the layers overlap as well (the paper's option); otherwise one
+        seed per hop."""
+        hops = len(max_neighbors)
+        if random_seeds is None:
+            random_seeds = [random.getrandbits(64) for _ in range(1 if layer_dependency else hops)]
+        assert len(random_seeds) == (1 if layer_dependency else hops), "one seed per hop, a single one with layer_dependency"
+        layers = [None] * hops
+        frontier = node_ids
+        for depth, fanout in enumerate(max_neighbors):          # depth 0 = next to the seeds = layer hops - 1
+            offsets, neighbours, centre_lid = self.labor_sample_one_hop(
+                frontier, fanout, mode=mode, random_seed=random_seeds[0 if layer_dependency else depth],
+                need_center_local_output=True)
+            widened, neighbour_pos = graph_ops.append_unique(frontier, neighbours.to(frontier.dtype),
+                                                             need_neighbor_raw_to_unique=True)
+            layers[hops - 1 - depth] = _Hop(widened, torch.stack([neighbour_pos, centre_lid]), offsets, neighbour_pos)
+            frontier = widened
+        return _layer_lists(layers, node_ids)
+
     # ------------------------------------------------------------------------------------------ several hops
     def multilayer_sample_without_replacement(self, node_ids: torch.Tensor, max_neighbors: List[int],
                                               weight_name: Union[str, None] = None, *,

@@ -609,6 +609,41 @@ def typed_sample_without_replacement(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tenso
     return out + ((etype.get_tensor(),) if need_type_output else ())
 
 
+LABOR_MODES = {"fixed": 0, "poisson": 1}
+LABOR_MAX_FIXED_FANOUT = 64
+
+
+def labor_sample(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, center_nodes_tensor: torch.Tensor, max_sample_count: int,
+                 random_seed: Union[int, None] = None, mode: str = "fixed", need_center_local_output: bool = False,
+                 need_edge_output: bool = False):
+    """Extension (wholememory_ext_csr_labor_sample, include/wholememory/wholegraph_amd_ext.h section 2v): LABOR layer-neighbour
+    sampling, DGL's LaborSampler. One variate is drawn per neighbour NODE from (random_seed, node id) and every centre ranks its
+    neighbours by it, so centres that share neighbours pick the same ones and the hop touches fewer distinct nodes. mode
+    "fixed": the max_sample_count (<= 64; <= 0: all) neighbours with the smallest variate; "poisson" (LABOR-0): every
+    neighbour whose variate is below max_sample_count / degree, about max_sample_count of them (max_sample_count >= 1).
+    Either way a centre's neighbours come in row order and are a uniform sample of its row. Returns what the other samplers
+    return: (sample_offset int32 [n + 1], sampled node ids[, center local id int32][, edge id int64]). One host round trip."""
+    if mode not in LABOR_MODES:
+        raise ValueError("mode must be one of %s, got %r" % (sorted(LABOR_MODES), mode))
+    m = int(max_sample_count)
+    if (mode == "fixed" and m > LABOR_MAX_FIXED_FANOUT) or (mode == "poisson" and not 1 <= m < (1 << 31)):
+        raise ValueError("max_sample_count must be at most %d in mode 'fixed' and lie in [1, 2^31) in mode 'poisson', got %r"
+                         % (LABOR_MAX_FIXED_FANOUT, max_sample_count))
+    if center_nodes_tensor.dim() != 1:
+        raise ValueError("center_nodes_tensor must be 1-D")
+    row, col = _handle(wm_csr_row_ptr_tensor), _handle(wm_csr_col_ptr_tensor)
+    offset = torch.empty(center_nodes_tensor.shape[0] + 1, device=op_device(), dtype=torch.int)
+    dest = TorchMemoryContext()
+    lid = TorchMemoryContext() if need_center_local_output else None
+    egid = TorchMemoryContext() if need_edge_output else None
+    wc, wo = wrap_torch_tensor(center_nodes_tensor), wrap_torch_tensor(offset)
+    wmb.check(wmb.lib().wholememory_ext_csr_labor_sample(
+        row, col, wc.handle, max(m, -1), LABOR_MODES[mode], _seed64(random_seed), wo.handle, C.c_void_p(dest.get_c_context()),
+        C.c_void_p(lid.get_c_context() if lid else 0), C.c_void_p(egid.get_c_context() if egid else 0),
+        get_wholegraph_env_fns(), C.c_void_p(get_stream())))
+    return _sample_outputs(offset, dest, lid, egid, need_center_local_output, need_edge_output)
+
+
 def generate_random_positive_int_cpu(random_seed, sub_sequence, output_random_value_count):
     output = torch.empty((output_random_value_count,), dtype=torch.int)
     w = wrap_torch_tensor(output)

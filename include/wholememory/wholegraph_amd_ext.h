@@ -45,6 +45,8 @@
  *      relation table).
  *      (2v) LABOR layer-neighbour sampling over the same CSR graph: one random variate per neighbour NODE, shared by all
  *      centres of a hop, so that their samples overlap and the hop touches fewer distinct nodes (DGL's LaborSampler).
+ *      (2w) the rank of a target row among all rows of a WholeMemory table under a dot, l1 or l2 score, with a filter block:
+ *      the counts behind filtered mean rank, MRR and Hits@k of the embedding models, without a [queries, rows] matrix.
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -1702,6 +1704,56 @@ enum wholememory_error_code_t wholememory_ext_csr_labor_sample(
   void* output_dest_memory_context,             /* col_ind's dtype [total] */
   void* output_center_localid_memory_context,   /* int32 [total] or NULL */
   void* output_edge_gid_memory_context,         /* int64 [total] or NULL: positions in csr_col_ptr */
+  wholememory_env_func_t* p_env_fns,
+  void* stream);
+
+/* ---- (2w) rank of a target row among the rows of a WholeMemory table (`rank_rows`) ------------------------------------------- */
+/* For every query b, how many rows of a table score above, and exactly, the score of the query's target row: the filtered
+ * rank behind mean rank, MRR and Hits@k (realistic rank = 1 + greater + equal / 2). The [B, N] score matrix is never formed.
+ * table: fp32 [N, F], CONTINUOUS or CHUNKED (or a plain device array wrapped with wholememory_make_tensor_from_pointer), read
+ * with its row stride and storage offset; a row lies within one rank. query: fp32 [B, >= F] on the device, rows contiguous,
+ * any row stride >= F. target: int32 or int64 [B] global row ids. measure: 0 dot, 1 l1, 2 l2. The call counts over the rows
+ * of [entity_begin, entity_end), 0 <= entity_begin <= entity_end <= N; counts are additive over disjoint ranges, so a table
+ * can be swept in pieces, or by several ranks, and the results added. Optional filter block (both tensors or neither):
+ * filter_row_ptr int32 or int64 [B + 1], filter_ids [M] of target's dtype; the ids filter_ids[filter_row_ptr[b] ..
+ * filter_row_ptr[b + 1]) are rows query b is not ranked against. The ids of one filter row must be DISTINCT (the caller's
+ * promise: an id that occurs twice is taken out twice). An id outside [entity_begin, entity_end), or equal to target[b], is
+ * ignored; an entry at a position no row covers is ignored. Outputs: greater and equal, int64 with at least B entries,
+ * written (not added to) by the call.
+ *
+ * The contract, in the style of (2u): every `*`, `+`, `-` and abs is one fp32 operation rounded on its own, no fused
+ * multiply-add. The score s(b, e) of u = query[b] against t = table[e] is ONE accumulator that starts at +0.0 and walks the
+ * columns c = 0 .. F - 1 in ascending order:
+ *   dot  acc = acc + u_c * t_c                  s = acc
+ *   l1   acc = acc + abs(u_c - t_c)             s = -acc
+ *   l2   d = u_c - t_c; acc = acc + d * d       s = -acc     (no square root: the rank is the same, a root only makes ties)
+ * thr[b] = s(b, target[b]), from the table row target[b] wherever in [0, N) it lies (inside the range or not).
+ *   greater[b] = the number of e in [entity_begin, entity_end) with e != target[b], e not in b's filter row, s(b, e) > thr[b]
+ *   equal[b]   = the same with ==
+ * A target outside [0, N) gives greater[b] = equal[b] = -1, and no table row is read for it. A NaN score compares false both
+ * ways: a NaN row counts nowhere, and under a NaN thr both counts are 0. The counts are integers, so the result does not
+ * depend on the launch geometry or on the order in which the kernels add them.
+ *
+ * Errors, in this order; every answer comes before any device work. INVALID_INPUT: a NULL table, query, target, greater, equal
+ * or p_env_fns; only one of the two filter tensors; table or query not 2-D, another tensor not 1-D; B >= 2^31 - 1 or F < 1;
+ * rows that are not contiguous, a query with fewer than F columns or a row stride < F; target not [B], greater or equal
+ * shorter than B; a range outside [0, N]; a measure outside 0 .. 2; filter_row_ptr not [B + 1]. LOGIC_ERROR: table or query
+ * not fp32; target not int32 / int64; greater or equal not int64; filter_row_ptr not int32 / int64; filter_ids not of target's
+ * dtype. INVALID_INPUT for a HIERARCHY table, NOT_IMPLEMENTED for a DISTRIBUTED one (rank the local rows on every rank and add).
+ * NOT_SUPPORTED, nothing queued, when the device backend has no such kernels. B = 0 succeeds and writes nothing; an empty
+ * range succeeds with the outputs zeroed (-1 for a target outside the table). One scratch allocation of B floats through
+ * p_env_fns; no host round trip. */
+enum wholememory_error_code_t wholememory_ext_rank_rows(
+  wholememory_tensor_t table_tensor,            /* fp32 [N, F] */
+  wholememory_tensor_t query_tensor,            /* fp32 [B, >= F], device */
+  wholememory_tensor_t target_tensor,           /* int32 / int64 [B], device */
+  int measure,                                  /* 0 dot, 1 l1, 2 l2 */
+  int64_t entity_begin,
+  int64_t entity_end,
+  wholememory_tensor_t filter_row_ptr_tensor,   /* int32 / int64 [B + 1], device, or NULL */
+  wholememory_tensor_t filter_ids_tensor,       /* target's dtype [M], device, or NULL */
+  wholememory_tensor_t greater_tensor,          /* int64 [>= B], device */
+  wholememory_tensor_t equal_tensor,            /* int64 [>= B], device */
   wholememory_env_func_t* p_env_fns,
   void* stream);
 

@@ -610,6 +610,32 @@ struct wm_kge_args : wm_csc_block {
   int64_t grad_rel_stride;
 };
 
+// the rank of a target row among the rows of a WholeMemory table (kernels/rank.hip, the `rank_rows` op, wholegraph_amd_ext.h
+// section 2w): per query b, how many rows e of [entity_begin, entity_end) score above (greater) and exactly (equal) the score
+// of row target[b], the target and the ids of b's filter row left out. `gref` addresses the table (continuous or chunked);
+// stride / offset / dim in ELEMENTS (fp32)
+struct wm_rank_args {
+  wholememory_gref_t gref;
+  int64_t table_rows;               // rows of the (sub)tensor: targets and the range lie in [0, table_rows]
+  int64_t table_stride;
+  int64_t table_storage_offset;
+  int64_t dim;
+  const float* query;               // [n_queries, query_stride], dim columns used
+  int64_t query_stride;
+  int64_t n_queries;
+  const void* target;               // [n_queries] int32 / int64, device
+  wholememory_dtype_t id_dtype;     // of target and filter_ids
+  int measure;                      // 0 dot, 1 l1, 2 l2
+  int64_t entity_begin, entity_end;
+  const void* filter_row_ptr;       // [n_queries + 1] int32 / int64, or nullptr: no filter
+  wholememory_dtype_t filter_row_ptr_dtype;
+  const void* filter_ids;           // [n_filter]
+  int64_t n_filter;
+  float* thr;                       // [n_queries] scratch: the target's score, NaN for a target outside the table
+  int64_t* greater;                 // [n_queries]
+  int64_t* equal;                   // [n_queries]
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -916,6 +942,13 @@ struct wm_device_backend {
   size_t (*labor_workspace_bytes)(int64_t n);
   int (*labor_count)(const wm_labor_args* a, void* stream);
   int (*labor_select)(const wm_labor_args* a, void* stream);
+  // ---- the rank of a target row among the rows of a table (kernels/rank.hip, wholegraph_amd_ext.h section 2w); nullptr in a
+  // backend without it ----
+  // threshold writes a->thr and the initial greater / equal (0, or -1 for a target outside the table); sweep adds the counts
+  // of the range; filter takes the counted rows of the filter block out again. In this order, on one stream
+  int (*rank_threshold)(const wm_rank_args* a, void* stream);
+  int (*rank_sweep)(const wm_rank_args* a, void* stream);
+  int (*rank_filter)(const wm_rank_args* a, void* stream);
 };
 
 }  // extern "C"

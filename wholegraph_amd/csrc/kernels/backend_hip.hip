@@ -126,6 +126,9 @@ int hip_kge_backward(const wm_kge_args* a, const wm_edge_index& ix, const wm_edg
 size_t hip_labor_workspace_bytes(int64_t n);
 int hip_labor_count(const wm_labor_args* a, void* stream);
 int hip_labor_select(const wm_labor_args* a, void* stream);
+int hip_rank_threshold(const wm_rank_args* a, void* stream);
+int hip_rank_sweep(const wm_rank_args* a, void* stream);
+int hip_rank_filter(const wm_rank_args* a, void* stream);
 
 namespace {
 
@@ -352,6 +355,9 @@ const wm_device_backend kHipBackend = {
   hip_labor_workspace_bytes,
   hip_labor_count,
   hip_labor_select,
+  hip_rank_threshold,
+  hip_rank_sweep,
+  hip_rank_filter,
 };
 
 }  // namespace

@@ -34,11 +34,12 @@ inline gref_view make_view(const wholememory_gref_t& g)
   return v;
 }
 
+// where element elem_index lives (rank.hip: once per table row, the row's elements then follow it: a row lies in one rank)
 template <typename T>
-__device__ __forceinline__ T gref_load(const gref_view& v, int64_t elem_index)
+__device__ __forceinline__ const T* gref_address(const gref_view& v, int64_t elem_index)
 {
   const size_t off = static_cast<size_t>(elem_index) * sizeof(T);
-  if (v.chunk_stride == 0) return *reinterpret_cast<const T*>(v.base + off);
+  if (v.chunk_stride == 0) return reinterpret_cast<const T*>(v.base + off);
   int rank;
   size_t start;
   if (v.same_chunk) {
@@ -50,7 +51,13 @@ __device__ __forceinline__ T gref_load(const gref_view& v, int64_t elem_index)
       if (off >= v.rank_offsets[r]) rank = r;
     start = v.rank_offsets[rank];
   }
-  return *reinterpret_cast<const T*>(v.rank_ptrs[rank] + (off - start));
+  return reinterpret_cast<const T*>(v.rank_ptrs[rank] + (off - start));
+}
+
+template <typename T>
+__device__ __forceinline__ T gref_load(const gref_view& v, int64_t elem_index)
+{
+  return *gref_address<T>(v, elem_index);
 }
 
 }  // namespace wm

@@ -15,7 +15,9 @@ WholeMemory table, and ``quantized``, 8-bit row-quantized tables whose gather de
 ``edge_dot.edge_dot_n2n``, the score of an edge as the dot product of its endpoint rows, with ``skipgram.skipgram_block`` and
 the ``node2vec.Node2Vec`` model that train embeddings on the walks and negatives of ``GraphStructure``; and
 ``kge_score.kge_score_n2n``, the relation-typed score of an edge (DistMult, TransE, ComplEx, RotatE), with ``kge.kge_block``
-and the ``kge.KGEModel`` model that trains knowledge-graph embeddings on filtered negatives; and
+and the ``kge.KGEModel`` model that trains knowledge-graph embeddings on filtered negatives and evaluates them
+(``KGEModel.rank`` / ``KGEModel.test``: filtered mean rank, MRR, Hits@k) on ``wholegraph_ops.rank_rows``, the rank of a target
+row among all rows of a WholeMemory table; and
 ``saint.SubgraphGNNModel``, the layers above on the induced subgraphs of ``GraphStructure.induced_subgraph`` and
 ``GraphStructure.saint_random_walk_subgraph``: subgraph-wise training; and ``temporal.TimeEncoder`` and
 ``temporal.TemporalGNNModel``, ``EdgeGATConv`` layers over the temporal trees of ``GraphStructure.multilayer_temporal_sample``,

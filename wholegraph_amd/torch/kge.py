@@ -13,6 +13,7 @@ from typing import NamedTuple, Union
 import torch
 import torch.nn.functional as F
 
+from . import wholegraph_ops
 from .embedding import EmbeddingLookupFn, WholeMemoryEmbedding
 from .graph_ops import append_unique
 from .graph_structure import GraphStructure
@@ -149,3 +150,75 @@ class KGEModel(torch.nn.Module):
 
     def forward(self, triples: torch.Tensor, random_seed: Union[int, None] = None) -> torch.Tensor:
         return self.loss(self.sample(triples, random_seed))
+
+    # ---- evaluation: the filtered rank of the true entity among all entities (``wholegraph_ops.rank_rows``) ----
+
+    def rank_queries(self, anchor_rows: torch.Tensor, rel_rows: torch.Tensor) -> torch.Tensor:
+        """[B, F]: the row q of a triple such that the model's score of entity row e on the corrupted side is ``rank_rows``'
+        measure of (q, e). With a the anchor's row (the head under corrupt="tail", else the tail) and r the relation's:
+
+        ===========  =======  ==================  ==========================================
+        model        measure  corrupt="tail"      corrupt="head"
+        ===========  =======  ==================  ==========================================
+        distmult     dot      h * r               r * t
+        transe_l1/2  l1 / l2  h + r               t - r
+        complex      dot      h o r               conj(r) o t
+        rotate       l2       h o r               conj(r) o t   (|h o r - t| = |h - conj(r) o t| needs |r| = 1,
+                                                  which cat(cos, sin) of ``relation_rows`` has up to rounding)
+        ===========  =======  ==================  ==========================================
+
+        o is the complex product of header section 2u over rows read as [re | im]. l2 ranks by the squared distance."""
+        a, r, tail = anchor_rows, rel_rows, self.corrupt == "tail"
+        if self.model == "distmult":
+            return a * r
+        if self.model in ("transe_l1", "transe_l2"):
+            return a + r if tail else a - r
+        d = a.shape[1] // 2
+        a_re, a_im, r_re, r_im = a[:, :d], a[:, d:], r[:, :d], r[:, d:]
+        if tail:
+            return torch.cat([a_re * r_re - a_im * r_im, a_re * r_im + a_im * r_re], dim=1)
+        return torch.cat([r_re * a_re + r_im * a_im, r_re * a_im - r_im * a_re], dim=1)
+
+    def known_neighbours(self, anchors: torch.Tensor):
+        """(row_ptr int64 [B + 1], ids [M]): per anchor its distinct neighbours in graph_structure, ascending: the entities
+        ``sample`` never draws as its negatives, and the filter block of ``rank``"""
+        g, n = self.graph_structure, anchors.shape[0]
+        offset, nbr = wholegraph_ops.unweighted_sample_without_replacement(g.csr_row_ptr, g.csr_col_ind, anchors, -1)
+        rows = torch.repeat_interleave(torch.arange(n, device=nbr.device), (offset[1:] - offset[:-1]).long())
+        keys = torch.unique(rows * g.node_count + nbr.long())      # (sorted: by row, then id)
+        row_ptr = torch.zeros(n + 1, dtype=torch.int64, device=nbr.device)
+        torch.cumsum(torch.bincount(torch.div(keys, g.node_count, rounding_mode="floor"), minlength=n), 0, out=row_ptr[1:])
+        return row_ptr, (keys % g.node_count).to(anchors.dtype)
+
+    @torch.no_grad()
+    def rank(self, triples: torch.Tensor, *, filtered: bool = True, batch_size: int = 1024):
+        """(greater, equal), int64 [T] on the device: for every triple, how many entities on the side that ``corrupt`` names
+        score above, and exactly, the true one (``rank_rows`` over the whole entity table; the true entity is left out).
+        filtered: the known neighbours of the triple's anchor are left out too. Reads the table, changes nothing."""
+        g = self.graph_structure
+        if triples.dim() != 2 or triples.shape[1] != 3:
+            raise ValueError("triples must be [T, 3] as (head, relation, tail) (got shape %s)" % (tuple(triples.shape),))
+        heads, rels, tails = triples.to(g.csr_col_ind.dtype).cuda().t().contiguous().unbind(0)
+        anchors, others = (heads, tails) if self.corrupt == "tail" else (tails, heads)
+        table, rel = self.embedding.get_embedding_tensor(), self.relation_rows().detach()
+        measure = {"distmult": "dot", "complex": "dot", "transe_l1": "l1"}.get(self.model, "l2")
+        counts = torch.empty((2, anchors.shape[0]), dtype=torch.int64, device=anchors.device)
+        for s in range(0, anchors.shape[0], int(batch_size)):
+            a = anchors[s:s + int(batch_size)]
+            rows = self.embedding.gather(a, is_training=False, force_dtype=torch.float32)
+            query = self.rank_queries(rows, rel.index_select(0, rels[s:s + int(batch_size)].long()))
+            row_ptr, ids = self.known_neighbours(a) if filtered else (None, None)
+            greater, equal = wholegraph_ops.rank_rows(table, query, others[s:s + int(batch_size)], measure=measure,
+                                                      filter_row_ptr=row_ptr, filter_ids=ids)
+            counts[0, s:s + int(batch_size)], counts[1, s:s + int(batch_size)] = greater, equal
+        return counts[0], counts[1]
+
+    @torch.no_grad()
+    def test(self, triples: torch.Tensor, *, k=(1, 3, 10), filtered: bool = True, batch_size: int = 1024):
+        """(mean_rank, mrr, {k: hits@k}) of the triples under the realistic rank 1 + greater + equal / 2 (PyG's
+        ``KGEModel.test``, PyKEEN's "realistic")"""
+        greater, equal = self.rank(triples, filtered=filtered, batch_size=batch_size)
+        rank = 1.0 + greater.double() + equal.double() / 2.0
+        if rank.shape[0] == 0:
+            return float("nan"), float("nan"), {int(kk): float("nan") for kk in k}
+        return float(rank.mean()), float((1.0 / rank).mean()), {int(kk): float((rank <= kk).double().mean()) for kk in k}

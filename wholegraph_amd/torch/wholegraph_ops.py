@@ -644,6 +644,40 @@ def labor_sample(wm_csr_row_ptr_tensor, wm_csr_col_ptr_tensor, center_nodes_tens
     return _sample_outputs(offset, dest, lid, egid, need_center_local_output, need_edge_output)
 
 
+RANK_MEASURES = {"dot": 0, "l1": 1, "l2": 2}
+RANK_QUERY_TILE = 64      # queries per workgroup of the sweep: the table is read ceil(B / RANK_QUERY_TILE) times
+
+
+def rank_rows(table_tensor, query: torch.Tensor, target: torch.Tensor, *, measure: str = "dot", entity_range=None,
+              filter_row_ptr: Union[torch.Tensor, None] = None, filter_ids: Union[torch.Tensor, None] = None):
+    """Extension (wholememory_ext_rank_rows, include/wholememory/wholegraph_amd_ext.h section 2w): where the row target[b] of a
+    WholeMemory table ranks among all its rows for query[b]. table_tensor: fp32 [N, F], CONTINUOUS or CHUNKED; query: fp32
+    [B, >= F] on the device; target: int32 / int64 [B] global row ids; measure "dot" (score u . t), "l1" (-sum |u - t|) or "l2"
+    (-sum (u - t)^2), each one fp32 accumulator over ascending columns. entity_range = (begin, end) counts over those rows only
+    (default: all; counts add over disjoint ranges). filter_row_ptr [B + 1] and filter_ids [M] (target's dtype; the ids of a
+    row distinct) name rows query b is not ranked against. Returns (greater, equal), int64 [B] on the device: the rows that
+    score above, and exactly, the target's score, the target itself left out; -1, -1 for a target outside the table. The
+    realistic rank is 1 + greater + equal / 2."""
+    if measure not in RANK_MEASURES:
+        raise ValueError("measure must be one of %s, got %r" % (sorted(RANK_MEASURES), measure))
+    if (filter_row_ptr is None) != (filter_ids is None):
+        raise ValueError("filter_row_ptr and filter_ids come together or not at all")
+    if query.dim() != 2 or target.dim() != 1 or target.shape[0] != query.shape[0]:
+        raise ValueError("query must be [B, >= F] and target [B] (got %s and %s)" % (tuple(query.shape), tuple(target.shape)))
+    table = _handle(table_tensor)
+    n_rows = int(wmb.lib().wholememory_tensor_get_tensor_description(table).contents.sizes[0])
+    begin, end = (0, n_rows) if entity_range is None else (int(entity_range[0]), int(entity_range[1]))
+    if query.shape[0] > 0 and query.stride(1) != 1:
+        query = query.contiguous()
+    counts = torch.empty((2, query.shape[0]), device=op_device(), dtype=torch.int64)
+    wrapped = [wrap_torch_tensor(t) for t in (query, target.contiguous(), counts[0], counts[1])]
+    wf = [wrap_torch_tensor(t.contiguous()) for t in (filter_row_ptr, filter_ids)] if filter_ids is not None else None
+    wmb.check(wmb.lib().wholememory_ext_rank_rows(
+        table, wrapped[0].handle, wrapped[1].handle, RANK_MEASURES[measure], begin, end, wf[0].handle if wf else None,
+        wf[1].handle if wf else None, wrapped[2].handle, wrapped[3].handle, get_wholegraph_env_fns(), C.c_void_p(get_stream())))
+    return counts[0], counts[1]
+
+
 def generate_random_positive_int_cpu(random_seed, sub_sequence, output_random_value_count):
     output = torch.empty((output_random_value_count,), dtype=torch.int)
     w = wrap_torch_tensor(output)

@@ -47,6 +47,8 @@
  *      centres of a hop, so that their samples overlap and the hop touches fewer distinct nodes (DGL's LaborSampler).
  *      (2w) the rank of a target row among all rows of a WholeMemory table under a dot, l1 or l2 score, with a filter block:
  *      the counts behind filtered mean rank, MRR and Hits@k of the embedding models, without a [queries, rows] matrix.
+ *      (2x) the k best rows of a WholeMemory table per query under the same score and filter block, in one total order
+ *      (higher score, then lower id): what the embedding models are served with, without a [queries, rows] matrix.
  *  (3) the testing seam for the device backend (see wholegraph_amd/csrc/backend.hpp).
  */
 #ifndef WHOLEMEMORY_WHOLEGRAPH_AMD_EXT_H_
@@ -1754,6 +1756,53 @@ enum wholememory_error_code_t wholememory_ext_rank_rows(
   wholememory_tensor_t filter_ids_tensor,       /* target's dtype [M], device, or NULL */
   wholememory_tensor_t greater_tensor,          /* int64 [>= B], device */
   wholememory_tensor_t equal_tensor,            /* int64 [>= B], device */
+  wholememory_env_func_t* p_env_fns,
+  void* stream);
+
+/* ---- (2x) the k best rows of a WholeMemory table per query (`topk_rows`) ------------------------------------------------------ */
+/* For every query b, the k rows of [entity_begin, entity_end) with the highest score s(b, e), the rows of b's filter row left
+ * out: what an embedding model is served with ("which k entities complete (h, r, ?)", "which items are nearest to this
+ * row"). The [B, N] score matrix is never formed. table, query, measure, the range and the optional filter block are those of
+ * (2w): table fp32 [N, F], CONTINUOUS or CHUNKED (or a wrapped device array), read with its row stride and storage offset;
+ * query fp32 [B, >= F] on the device, rows contiguous, any row stride >= F; measure 0 dot, 1 l1, 2 l2; 0 <= entity_begin <=
+ * entity_end <= N; filter_row_ptr int32 or int64 [B + 1] and filter_ids int32 or int64 [M], both or neither. There is no
+ * target. k lies in 1 .. 64. The ids of one filter row must be ASCENDING (the caller's promise: the op searches the row;
+ * duplicates are harmless); an id outside the range is ignored. Outputs: ids int64 [B, k] and scores fp32 [B, k], rows
+ * contiguous (any row stride >= k), written by the call.
+ *
+ * The score is the contract of (2w), word for word: ONE fp32 accumulator from +0.0 over the columns in ascending order, every
+ * `*`, `+`, `-` and abs rounded on its own, no fused multiply-add; l1 and l2 are negated and l2 takes no root. Both ops
+ * score with the same device function, so a row gets the same bits in both.
+ *
+ * Order: position j of row b holds the j-th best row. A higher score comes first, and among equal scores the LOWER row id;
+ * -0.0 and +0.0 are equal, as `==` makes them in (2w) (a zero score is returned as +0.0). A row with a NaN score is never
+ * returned. Where fewer than k rows qualify, the remaining positions hold id -1 and score NaN. This is a total order of the
+ * qualifying rows, so the answer is unique: it does not depend on the launch geometry, on how the table is split among
+ * workgroups, or on the order in which candidates meet.
+ *
+ * A call covers at most 2^31 rows. Results over disjoint ranges merge by the same order (higher score, then lower id; drop
+ * the -1 entries), so a larger table, or a DISTRIBUTED one, is swept in pieces, or by several ranks over their local rows,
+ * and the pieces' answers merged — as the counts of (2w) are added.
+ *
+ * Errors, in this order; every answer comes before any device work. INVALID_INPUT: a NULL table, query, ids, scores or
+ * p_env_fns; only one of the two filter tensors; table, query, ids or scores not 2-D, a filter tensor not 1-D; B >= 2^31 - 1
+ * or F < 1; rows that are not contiguous, a query with fewer than F columns or a row stride < F; k outside 1 .. 64; ids or
+ * scores not [B, k] with contiguous rows; a range outside [0, N] or of more than 2^31 rows; a measure outside 0 .. 2;
+ * filter_row_ptr not [B + 1]. LOGIC_ERROR: table, query or scores not fp32; ids not int64; filter_row_ptr or filter_ids not
+ * int32 / int64. INVALID_INPUT for a HIERARCHY table, NOT_IMPLEMENTED for a DISTRIBUTED one. NOT_SUPPORTED, nothing queued,
+ * when the device backend has no such kernels. B = 0 succeeds and writes nothing; an empty range succeeds with every position
+ * -1 / NaN. One scratch allocation through p_env_fns (the partial tops of the table's splits); no host round trip. */
+enum wholememory_error_code_t wholememory_ext_topk_rows(
+  wholememory_tensor_t table_tensor,            /* fp32 [N, F] */
+  wholememory_tensor_t query_tensor,            /* fp32 [B, >= F], device */
+  int k,                                        /* 1 .. 64 */
+  int measure,                                  /* 0 dot, 1 l1, 2 l2 */
+  int64_t entity_begin,
+  int64_t entity_end,
+  wholememory_tensor_t filter_row_ptr_tensor,   /* int32 / int64 [B + 1], device, or NULL */
+  wholememory_tensor_t filter_ids_tensor,       /* int32 / int64 [M], ascending per row, device, or NULL */
+  wholememory_tensor_t ids_tensor,              /* int64 [B, k], device */
+  wholememory_tensor_t scores_tensor,           /* fp32 [B, k], device */
   wholememory_env_func_t* p_env_fns,
   void* stream);
 

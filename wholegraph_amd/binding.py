@@ -293,6 +293,7 @@ PROTOTYPES = {
                                              _P(EnvFunc), _vp]),
     "wholememory_ext_csr_labor_sample": (_i, [_vp, _vp, _vp, _i, _i, C.c_ulonglong, _vp, _vp, _vp, _vp, _P(EnvFunc), _vp]),
     "wholememory_ext_rank_rows": (_i, [_vp, _vp, _vp, _i, _i64, _i64, _vp, _vp, _vp, _vp, _P(EnvFunc), _vp]),
+    "wholememory_ext_topk_rows": (_i, [_vp, _vp, _i, _i, _i64, _i64, _vp, _vp, _vp, _vp, _P(EnvFunc), _vp]),
     "wholememory_ext_csc_aggregate_forward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i, _vp, _i64, _P(EnvFunc),
                                                   _vp]),
     "wholememory_ext_csc_aggregate_backward": (_i, [_vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i, _vp, _i64, _P(EnvFunc),

@@ -636,6 +636,34 @@ struct wm_rank_args {
   int64_t* equal;                   // [n_queries]
 };
 
+// the k best rows of a WholeMemory table per query (kernels/topk.hip, the `topk_rows` op, wholegraph_amd_ext.h section 2x):
+// per query b the k rows e of [entity_begin, entity_end) with the highest score, higher first and the lower id first among
+// equal scores, the ids of b's filter row (ascending) and rows of NaN score left out. Table, query, measure and filter as in
+// wm_rank_args
+struct wm_topk_args {
+  wholememory_gref_t gref;
+  int64_t table_rows;
+  int64_t table_stride;
+  int64_t table_storage_offset;
+  int64_t dim;
+  const float* query;               // [n_queries, query_stride], dim columns used
+  int64_t query_stride;
+  int64_t n_queries;
+  int measure;                      // 0 dot, 1 l1, 2 l2
+  int64_t entity_begin, entity_end; // at most 2^31 rows
+  const void* filter_row_ptr;       // [n_queries + 1] int32 / int64, or nullptr: no filter
+  wholememory_dtype_t filter_row_ptr_dtype;
+  const void* filter_ids;           // [n_filter] int32 / int64
+  wholememory_dtype_t filter_ids_dtype;
+  int64_t n_filter;
+  int k;                            // 1 .. kTopkMax
+  void* workspace;                  // topk_workspace_bytes(a): the splits' running tops, written by sweep, read by merge
+  int64_t* ids;                     // [n_queries, ids_stride], k columns written; -1 where fewer than k rows qualify
+  int64_t ids_stride;
+  float* scores;                    // [n_queries, scores_stride], k columns written; NaN there
+  int64_t scores_stride;
+};
+
 struct wm_device_backend {
   const char* name;
   // memory / stream
@@ -949,6 +977,13 @@ struct wm_device_backend {
   int (*rank_threshold)(const wm_rank_args* a, void* stream);
   int (*rank_sweep)(const wm_rank_args* a, void* stream);
   int (*rank_filter)(const wm_rank_args* a, void* stream);
+  // ---- the k best rows of a table per query (kernels/topk.hip, wholegraph_amd_ext.h section 2x); nullptr in a backend
+  // without it ----
+  // sweep writes every split's running top of every query into a->workspace; merge folds the splits and writes ids / scores.
+  // In this order, on one stream; both see the same a (the number of splits is a function of it)
+  size_t (*topk_workspace_bytes)(const wm_topk_args* a);
+  int (*topk_sweep)(const wm_topk_args* a, void* stream);
+  int (*topk_merge)(const wm_topk_args* a, void* stream);
 };
 
 }  // extern "C"

@@ -129,6 +129,9 @@ int hip_labor_select(const wm_labor_args* a, void* stream);
 int hip_rank_threshold(const wm_rank_args* a, void* stream);
 int hip_rank_sweep(const wm_rank_args* a, void* stream);
 int hip_rank_filter(const wm_rank_args* a, void* stream);
+size_t hip_topk_workspace_bytes(const wm_topk_args* a);
+int hip_topk_sweep(const wm_topk_args* a, void* stream);
+int hip_topk_merge(const wm_topk_args* a, void* stream);
 
 namespace {
 
@@ -358,6 +361,9 @@ const wm_device_backend kHipBackend = {
   hip_rank_threshold,
   hip_rank_sweep,
   hip_rank_filter,
+  hip_topk_workspace_bytes,
+  hip_topk_sweep,
+  hip_topk_merge,
 };
 
 }  // namespace

@@ -3,25 +3,18 @@
 // (filtered MRR / Hits@k of KGEModel), without the [B, N] score matrix.
 //
 // The contract fixes the arithmetic: one fp32 accumulator per (query, row), the columns in ascending order, every operation
-// rounded on its own. rank_step is that step; the three passes call it, so a row scores the same bits wherever it is scored.
+// rounded on its own. rank_step (rank_tile.cuh) is that step; the three passes call it, so a row scores the same bits wherever it is scored.
 // MFMA cannot keep that order, so the sweep is a register-tiled VALU kernel.
 //
 //   threshold  one lane per query: thr[b] = score(b, target[b]), NaN for a target outside the table; greater / equal start at
 //              0 (-1 for such a target). No memset: the outputs are cleared here.
-//   sweep      a workgroup of 256 lanes owns kRankEntityTile = 256 rows x kRankQueryTile = 64 queries and walks the columns
-//              in slices of kRankSlice = 32. Per slice it stages both tiles in LDS, row-major with a row pitch of 36 floats:
-//              a lane's 16-byte store and its 16-byte read of 4 columns of one row start at bank 4 * row mod 32 (36 r mod 64
-//              with 64 banks: 16 consecutive rows cover them once), so neither conflicts. Table rows are loaded 16 bytes a
-//              lane, 8 lanes a row slice (one 128-byte line); their addresses are resolved once per row and tile through the
-//              chunked view and kept in LDS. Lane (tx, ty), tx = lane % 32, ty = lane / 32, holds the 8 x 8 accumulators of
-//              rows tx + 32 i and queries ty + 8 j: a wave reads two query rows (a broadcast each) and 32 consecutive table
-//              rows per 16-byte read, 16 reads per 4 columns and 64 pairs. After the last slice a lane compares its pairs
-//              with thr, leaves out the target and the rows past the range, the 32 lanes of a query add their counts with
-//              shuffles, and one lane adds them to greater / equal with an integer atomic (the order of integer adds does not
-//              matter; a partials buffer would be tiles x B x 16 bytes). Columns past F are staged as +0.0 in both tiles:
-//              they add +0.0 in every measure, so any F >= 1 is served. The grid walks (row tile, query tile) pairs, query
-//              tiles fastest, so that the workgroups resident together read the same table rows; it is sized by blocks_for
-//              and strides.
+//   sweep      a workgroup of 256 lanes owns kRankEntityTile = 256 rows x kRankQueryTile = 64 queries and scores them with
+//              the staged tile walk of rank_tile.cuh (shared with kernels/topk.hip: LDS staging at a pitch of 36 floats,
+//              8 x 8 accumulators a lane). After the last slice a lane compares its pairs with thr, leaves out the target
+//              and the rows past the range, the 32 lanes of a query add their counts with shuffles, and one lane adds them
+//              to greater / equal with an integer atomic (the order of integer adds does not matter; a partials buffer
+//              would be tiles x B x 16 bytes). The grid walks (row tile, query tile) pairs, query tiles fastest, so that
+//              the workgroups resident together read the same table rows; it is sized by blocks_for and strides.
 //   filter     one lane per entry of the filter block: the query it belongs to (a search of filter_row_ptr), the score of
 //              its row, and one taken from greater or equal where the sweep counted that row.
 #include <hip/hip_runtime.h>
@@ -32,27 +25,12 @@
 #include "agg_common.cuh"
 #include "device_common.cuh"
 #include "gref_view.cuh"
+#include "rank_tile.cuh"
 
 namespace wm {
 namespace {
 
-constexpr int kRkBlock = 256;
-constexpr int kRkTx    = 32;                        // lanes along the table rows
-constexpr int kRkTy    = kRkBlock / kRkTx;          // lanes along the queries
-constexpr int kRkRe    = kRankEntityTile / kRkTx;   // table rows of a lane
-constexpr int kRkRq    = kRankQueryTile / kRkTy;    // queries of a lane
-constexpr int kRkPitch = kRankSlice + 4;            // floats between two rows of a staged tile
-constexpr int kRkQuads = kRankSlice / 4;            // 16-byte pieces of a row slice
-static_assert(kRkRe == 8 && kRkRq == 8, "a lane holds 8 x 8 accumulators");
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct rank_params {
-  gref_view table;
-  int64_t table_rows, stride, offset;   // elements
-  int64_t F;
-  const float* query;
-  int64_t query_stride, B;
+struct rank_params : rank_operands {
   const void* target;
   int ids64;
   int64_t begin, end;
@@ -64,35 +42,6 @@ struct rank_params {
   int64_t* greater;
   int64_t* equal;
 };
-
-// the per-column step of section 2w and the score of a finished accumulator
-template <int MEASURE>
-__device__ __forceinline__ float rank_step(float acc, float u, float t)
-{
-  if constexpr (MEASURE == 0) {
-    return acc + u * t;
-  } else if constexpr (MEASURE == 1) {
-    return acc + fabsf(u - t);
-  } else {
-    const float d = u - t;
-    return acc + d * d;
-  }
-}
-template <int MEASURE>
-__device__ __forceinline__ float rank_score(float acc)
-{
-  return MEASURE == 0 ? acc : -acc;
-}
-
-__device__ __forceinline__ int64_t id_at(const void* ids, int is64, int64_t i)
-{
-  return is64 ? static_cast<const int64_t*>(ids)[i] : static_cast<int64_t>(static_cast<const int32_t*>(ids)[i]);
-}
-
-__device__ __forceinline__ const float* table_row(const rank_params& p, int64_t e)
-{
-  return gref_address<float>(p.table, p.offset + e * p.stride);
-}
 
 // s(b, e) by one lane; e in [0, table_rows)
 template <int MEASURE>
@@ -117,78 +66,17 @@ __global__ __launch_bounds__(kRkBlock) void rank_threshold_kernel(rank_params p)
   }
 }
 
-// columns c .. c + 3 of a row, +0.0 past F and for a row that is not there. VEC == 4: every row start is 16-byte aligned
-// and F a multiple of 4
-template <int VEC>
-__device__ __forceinline__ f32x4 load_quad(const float* row, int64_t c, int64_t F)
-{
-  f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (row == nullptr || c >= F) return v;
-  if constexpr (VEC == 4) {
-    v = ld_global<f32x4>(row + c);
-  } else {
-    v[0] = row[c];
-    if (c + 1 < F) v[1] = row[c + 1];
-    if (c + 2 < F) v[2] = row[c + 2];
-    if (c + 3 < F) v[3] = row[c + 3];
-  }
-  return v;
-}
-
 template <int MEASURE, int VEC>
 __global__ __launch_bounds__(kRkBlock) void rank_sweep_kernel(rank_params p, int64_t n_qtiles, int64_t n_tiles)
 {
-  __shared__ __attribute__((aligned(16))) float es[kRankEntityTile * kRkPitch];
-  __shared__ __attribute__((aligned(16))) float qs[kRankQueryTile * kRkPitch];
-  __shared__ const float* erow[kRankEntityTile];
+  __shared__ rank_tile_lds lds;
   const int tid = threadIdx.x;
   const int tx = tid % kRkTx, ty = tid / kRkTx;
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const int64_t e0 = p.begin + (tile / n_qtiles) * kRankEntityTile;
     const int64_t b0 = (tile % n_qtiles) * kRankQueryTile;
-    {
-      const int64_t e = e0 + tid;   // (kRankEntityTile == kRkBlock: a row per lane)
-      erow[tid]       = e < p.end ? table_row(p, e) : nullptr;
-    }
     float acc[kRkRq][kRkRe];
-#pragma unroll
-    for (int j = 0; j < kRkRq; ++j)
-#pragma unroll
-      for (int i = 0; i < kRkRe; ++i) acc[j][i] = 0.0f;
-    __syncthreads();
-    for (int64_t k0 = 0; k0 < p.F; k0 += kRankSlice) {
-#pragma unroll
-      for (int n = 0; n < kRankEntityTile * kRkQuads / kRkBlock; ++n) {
-        const int l = tid + n * kRkBlock;
-        const int r = l / kRkQuads, c = (l % kRkQuads) * 4;
-        *reinterpret_cast<f32x4*>(&es[r * kRkPitch + c]) = load_quad<VEC>(erow[r], k0 + c, p.F);
-      }
-#pragma unroll
-      for (int n = 0; n < kRankQueryTile * kRkQuads / kRkBlock; ++n) {
-        const int l = tid + n * kRkBlock;
-        const int r = l / kRkQuads, c = (l % kRkQuads) * 4;
-        const int64_t b = b0 + r;
-        *reinterpret_cast<f32x4*>(&qs[r * kRkPitch + c]) =
-          load_quad<VEC>(b < p.B ? p.query + b * p.query_stride : nullptr, k0 + c, p.F);
-      }
-      __syncthreads();
-      const int64_t left = p.F - k0;
-      const int kend     = left < kRankSlice ? static_cast<int>((left + 3) & ~int64_t(3)) : kRankSlice;
-      for (int kk = 0; kk < kend; kk += 4) {
-        f32x4 ev[kRkRe], qv[kRkRq];
-#pragma unroll
-        for (int i = 0; i < kRkRe; ++i) ev[i] = *reinterpret_cast<const f32x4*>(&es[(tx + kRkTx * i) * kRkPitch + kk]);
-#pragma unroll
-        for (int j = 0; j < kRkRq; ++j) qv[j] = *reinterpret_cast<const f32x4*>(&qs[(ty + kRkTy * j) * kRkPitch + kk]);
-#pragma unroll
-        for (int c = 0; c < 4; ++c)
-#pragma unroll
-          for (int j = 0; j < kRkRq; ++j)
-#pragma unroll
-            for (int i = 0; i < kRkRe; ++i) acc[j][i] = rank_step<MEASURE>(acc[j][i], qv[j][c], ev[i][c]);
-      }
-      __syncthreads();
-    }
+    rank_tile_walk<MEASURE, VEC>(p, e0, p.end, b0, lds, acc);
 #pragma unroll
     for (int j = 0; j < kRkRq; ++j) {
       const int64_t b = b0 + ty + kRkTy * j;
@@ -268,22 +156,6 @@ bool args_ok(const wm_rank_args* a)
          (a->id_dtype == WHOLEMEMORY_DT_INT || a->id_dtype == WHOLEMEMORY_DT_INT64);
 }
 
-// every row start of the table and of the queries 16-byte aligned, and a row a whole number of 16-byte pieces?
-bool quads_ok(const wm_rank_args* a)
-{
-  if (a->dim % 4 != 0 || a->table_stride % 4 != 0 || a->table_storage_offset % 4 != 0 || a->query_stride % 4 != 0 ||
-      reinterpret_cast<uintptr_t>(a->query) % 16 != 0)
-    return false;
-  const wholememory_gref_t& g = a->gref;
-  if (g.stride == 0) return reinterpret_cast<uintptr_t>(g.pointer) % 16 == 0;
-  if (g.same_chunk) return g.stride % 16 == 0;   // (the per-rank bases are allocations)
-  gref_host_tables t;
-  if (!lookup_gref_tables(g.pointer, &t) || t.world_size != g.world_size) return false;
-  for (int r = 0; r < t.world_size; r++)
-    if (t.rank_offsets[r] % 16 != 0 || reinterpret_cast<uintptr_t>(t.rank_ptrs[r]) % 16 != 0) return false;
-  return true;
-}
-
 #define WM_RANK_BY_MEASURE(LAUNCH_)   \
   do {                                \
     if (a->measure == 0) LAUNCH_(0);  \
@@ -315,7 +187,7 @@ int hip_rank_sweep(const wm_rank_args* a, void* stream_v)
   const int64_t n_etiles = (p.end - p.begin + kRankEntityTile - 1) / kRankEntityTile;
   const int64_t n_qtiles = (p.B + kRankQueryTile - 1) / kRankQueryTile;
   const int64_t n_tiles  = n_etiles * n_qtiles;
-  const bool quads       = quads_ok(a);
+  const bool quads       = rank_quads_ok(a->gref, a->dim, a->table_stride, a->table_storage_offset, a->query, a->query_stride);
 #define WM_RANK_SWEEP(M_)                                                                                              \
   do {                                                                                                                 \
     if (quads)                                                                                                         \

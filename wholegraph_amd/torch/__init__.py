@@ -17,7 +17,8 @@ the ``node2vec.Node2Vec`` model that train embeddings on the walks and negatives
 ``kge_score.kge_score_n2n``, the relation-typed score of an edge (DistMult, TransE, ComplEx, RotatE), with ``kge.kge_block``
 and the ``kge.KGEModel`` model that trains knowledge-graph embeddings on filtered negatives and evaluates them
 (``KGEModel.rank`` / ``KGEModel.test``: filtered mean rank, MRR, Hits@k) on ``wholegraph_ops.rank_rows``, the rank of a target
-row among all rows of a WholeMemory table; and
+row among all rows of a WholeMemory table, and serves them (``KGEModel.predict``) on ``wholegraph_ops.topk_rows``, the k best
+rows of a table per query; and
 ``saint.SubgraphGNNModel``, the layers above on the induced subgraphs of ``GraphStructure.induced_subgraph`` and
 ``GraphStructure.saint_random_walk_subgraph``: subgraph-wise training; and ``temporal.TimeEncoder`` and
 ``temporal.TemporalGNNModel``, ``EdgeGATConv`` layers over the temporal trees of ``GraphStructure.multilayer_temporal_sample``,

@@ -181,7 +181,7 @@ class KGEModel(torch.nn.Module):
 
     def known_neighbours(self, anchors: torch.Tensor):
         """(row_ptr int64 [B + 1], ids [M]): per anchor its distinct neighbours in graph_structure, ascending: the entities
-        ``sample`` never draws as its negatives, and the filter block of ``rank``"""
+        ``sample`` never draws as its negatives, and the filter block of ``rank`` and ``predict``"""
         g, n = self.graph_structure, anchors.shape[0]
         offset, nbr = wholegraph_ops.unweighted_sample_without_replacement(g.csr_row_ptr, g.csr_col_ind, anchors, -1)
         rows = torch.repeat_interleave(torch.arange(n, device=nbr.device), (offset[1:] - offset[:-1]).long())
@@ -189,6 +189,20 @@ class KGEModel(torch.nn.Module):
         row_ptr = torch.zeros(n + 1, dtype=torch.int64, device=nbr.device)
         torch.cumsum(torch.bincount(torch.div(keys, g.node_count, rounding_mode="floor"), minlength=n), 0, out=row_ptr[1:])
         return row_ptr, (keys % g.node_count).to(anchors.dtype)
+
+    def _table_queries(self, anchors: torch.Tensor, rels: torch.Tensor, filtered: bool, batch_size: int):
+        """what ``rank`` and ``predict`` walk: per batch of anchors (slice, query rows, filter_row_ptr, filter_ids), then the
+        entity table and the measure under which ``rank_queries``' rows score it"""
+        table, rel = self.embedding.get_embedding_tensor(), self.relation_rows().detach()
+        measure = {"distmult": "dot", "complex": "dot", "transe_l1": "l1"}.get(self.model, "l2")
+
+        def batches():
+            for s in range(0, anchors.shape[0], int(batch_size)):
+                part = slice(s, s + int(batch_size))
+                rows = self.embedding.gather(anchors[part], is_training=False, force_dtype=torch.float32)
+                query = self.rank_queries(rows, rel.index_select(0, rels[part].long()))
+                yield (part, query) + (self.known_neighbours(anchors[part]) if filtered else (None, None))
+        return batches(), table, measure
 
     @torch.no_grad()
     def rank(self, triples: torch.Tensor, *, filtered: bool = True, batch_size: int = 1024):
@@ -200,18 +214,31 @@ class KGEModel(torch.nn.Module):
             raise ValueError("triples must be [T, 3] as (head, relation, tail) (got shape %s)" % (tuple(triples.shape),))
         heads, rels, tails = triples.to(g.csr_col_ind.dtype).cuda().t().contiguous().unbind(0)
         anchors, others = (heads, tails) if self.corrupt == "tail" else (tails, heads)
-        table, rel = self.embedding.get_embedding_tensor(), self.relation_rows().detach()
-        measure = {"distmult": "dot", "complex": "dot", "transe_l1": "l1"}.get(self.model, "l2")
+        batches, table, measure = self._table_queries(anchors, rels, filtered, batch_size)
         counts = torch.empty((2, anchors.shape[0]), dtype=torch.int64, device=anchors.device)
-        for s in range(0, anchors.shape[0], int(batch_size)):
-            a = anchors[s:s + int(batch_size)]
-            rows = self.embedding.gather(a, is_training=False, force_dtype=torch.float32)
-            query = self.rank_queries(rows, rel.index_select(0, rels[s:s + int(batch_size)].long()))
-            row_ptr, ids = self.known_neighbours(a) if filtered else (None, None)
-            greater, equal = wholegraph_ops.rank_rows(table, query, others[s:s + int(batch_size)], measure=measure,
-                                                      filter_row_ptr=row_ptr, filter_ids=ids)
-            counts[0, s:s + int(batch_size)], counts[1, s:s + int(batch_size)] = greater, equal
+        for part, query, row_ptr, ids in batches:
+            counts[0, part], counts[1, part] = wholegraph_ops.rank_rows(table, query, others[part], measure=measure,
+                                                                        filter_row_ptr=row_ptr, filter_ids=ids)
         return counts[0], counts[1]
+
+    @torch.no_grad()
+    def predict(self, anchors: torch.Tensor, rels: torch.Tensor, k: int = 10, *, filtered: bool = True, batch_size: int = 1024):
+        """(ids int64 [T, k], scores fp32 [T, k]) on the device: for every (anchor, relation) the k best entities on the side
+        that ``corrupt`` names, best first, the lower id first among equal scores (``topk_rows`` over the whole entity table;
+        k <= 64). The scores are ``rank``'s: the model's score, for the l2 models the negated SQUARED distance. filtered: the
+        known neighbours of the anchor are left out. Where fewer than k entities remain the tail is -1 / NaN. Reads the
+        table, changes nothing."""
+        g = self.graph_structure
+        if anchors.dim() != 1 or rels.shape != anchors.shape:
+            raise ValueError("anchors and rels must be [T] (got %s and %s)" % (tuple(anchors.shape), tuple(rels.shape)))
+        anchors, rels = anchors.to(g.csr_col_ind.dtype).cuda().contiguous(), rels.cuda()
+        batches, table, measure = self._table_queries(anchors, rels, filtered, batch_size)
+        ids = torch.empty((anchors.shape[0], int(k)), dtype=torch.int64, device=anchors.device)
+        scores = torch.empty((anchors.shape[0], int(k)), dtype=torch.float32, device=anchors.device)
+        for part, query, row_ptr, fids in batches:
+            ids[part], scores[part] = wholegraph_ops.topk_rows(table, query, k, measure=measure, filter_row_ptr=row_ptr,
+                                                               filter_ids=fids)
+        return ids, scores
 
     @torch.no_grad()
     def test(self, triples: torch.Tensor, *, k=(1, 3, 10), filtered: bool = True, batch_size: int = 1024):

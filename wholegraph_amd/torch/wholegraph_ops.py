@@ -678,6 +678,40 @@ def rank_rows(table_tensor, query: torch.Tensor, target: torch.Tensor, *, measur
     return counts[0], counts[1]
 
 
+TOPK_MAX = 64      # the most rows a call returns per query
+
+
+def topk_rows(table_tensor, query: torch.Tensor, k: int, *, measure: str = "dot", entity_range=None,
+              filter_row_ptr: Union[torch.Tensor, None] = None, filter_ids: Union[torch.Tensor, None] = None):
+    """Extension (wholememory_ext_topk_rows, include/wholememory/wholegraph_amd_ext.h section 2x): the k best rows of a
+    WholeMemory table for every query. table_tensor, query, measure, entity_range and the filter block as in ``rank_rows``
+    (the same score, bit for bit); k in 1 .. 64; filter_ids int32 / int64 with the ids of a row ASCENDING. Returns (ids int64
+    [B, k], scores fp32 [B, k]) on the device: position j holds the j-th best row of the range that is not in the query's
+    filter row, higher score first and the lower id first among equal scores; a row of NaN score is never returned, and
+    where fewer than k rows qualify the tail is -1 / NaN. Answers over disjoint ranges merge by the same order."""
+    if measure not in RANK_MEASURES:
+        raise ValueError("measure must be one of %s, got %r" % (sorted(RANK_MEASURES), measure))
+    if (filter_row_ptr is None) != (filter_ids is None):
+        raise ValueError("filter_row_ptr and filter_ids come together or not at all")
+    if not 1 <= int(k) <= TOPK_MAX:
+        raise ValueError("k must lie in 1 .. %d, got %r" % (TOPK_MAX, k))
+    if query.dim() != 2:
+        raise ValueError("query must be [B, >= F] (got %s)" % (tuple(query.shape),))
+    table = _handle(table_tensor)
+    n_rows = int(wmb.lib().wholememory_tensor_get_tensor_description(table).contents.sizes[0])
+    begin, end = (0, n_rows) if entity_range is None else (int(entity_range[0]), int(entity_range[1]))
+    if query.shape[0] > 0 and query.stride(1) != 1:
+        query = query.contiguous()
+    ids = torch.empty((query.shape[0], int(k)), device=op_device(), dtype=torch.int64)
+    scores = torch.empty((query.shape[0], int(k)), device=op_device(), dtype=torch.float32)
+    wrapped = [wrap_torch_tensor(t) for t in (query, ids, scores)]
+    wf = [wrap_torch_tensor(t.contiguous()) for t in (filter_row_ptr, filter_ids)] if filter_ids is not None else None
+    wmb.check(wmb.lib().wholememory_ext_topk_rows(
+        table, wrapped[0].handle, int(k), RANK_MEASURES[measure], begin, end, wf[0].handle if wf else None,
+        wf[1].handle if wf else None, wrapped[1].handle, wrapped[2].handle, get_wholegraph_env_fns(), C.c_void_p(get_stream())))
+    return ids, scores
+
+
 def generate_random_positive_int_cpu(random_seed, sub_sequence, output_random_value_count):
     output = torch.empty((output_random_value_count,), dtype=torch.int)
     w = wrap_torch_tensor(output)
